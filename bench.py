@@ -30,6 +30,9 @@ with the HG(0.7) stand-in of rounds 1-2 (continuity).  With several GPUs the lin
 measurement of configs[3] (fields gathered through the C ABI under RCCL) beside the weak-scaling headline.  `--groups 1` (default) runs the headline's order loop as one column group on one
 stream, so that every kernel is timed alone on the GPU (the roofline objects are per kernel); the library by itself takes two
 groups on two streams for a batch of more than 256 columns, which is faster: `two_groups` holds that measurement (same sweep, same bits).
+`--dump-outputs DIR`: after the timed steps, what the caller received from the last one (TOA / surface rows, order counts, status,
+the field; with several ranks what rank 0 gathered) goes to DIR/*.npy in float64, 64 MB at most: fixed seeded samples of the columns
+where the whole would not fit (dump_selection).  The inputs follow from the arguments alone, so two builds compare output for output.
 """
 import argparse
 import json
@@ -314,6 +317,54 @@ def extra_case(O, dev, local_rank, n_columns, L, N, aerosol, steps, check_cols, 
         ln.close()
 
 
+DUMP_LIMIT_BYTES = 64_000_000     # the whole dump, every file with its header
+DUMP_HEADER_BYTES = 4096          # allowance for the .npy headers of the (at most seven) files
+
+
+def dump_selection(B, L, N, with_field=True, limit=DUMP_LIMIT_BYTES):
+    """(row columns, field columns) of a dump of B columns, both sorted positions in 0..B-1, the second a subset of the
+    first.  Per row column: the TOA-up and surface-down rows (2N values), order count, status and sweep index; per field
+    column the L x 2N field and its sweep index, all float64.  The rows of every column are kept when they fit in a quarter
+    of the limit, otherwise a fixed seeded sample of them; the field columns are a fixed seeded sample of the row columns
+    that fits in what is left.  Everything together stays within `limit` bytes."""
+    rng = np.random.default_rng(20251015)
+    per_row = (2 * N + 3) * 8
+    n_rows = min(B, (limit // 4) // per_row)
+    rows = np.arange(B) if n_rows == B else np.sort(rng.choice(B, n_rows, replace=False))
+    if not with_field:
+        return rows, rows[:0]
+    k = min(n_rows, (limit - DUMP_HEADER_BYTES - n_rows * per_row) // ((L * 2 * N + 1) * 8))
+    field = rows if k == n_rows else np.sort(rng.choice(rows, k, replace=False))
+    return rows, field
+
+
+def dump_outputs(out_dir, L, N, toa_up, surface_down, n_orders, status=None, field=None, columns=None):
+    """What a caller of the timed path received from its last step, as float64 .npy files in `out_dir`; every argument has one
+    row per column (torch tensors or arrays).  `columns.npy`: the sweep's index of the columns kept (`columns`, default
+    0..B-1), with their `toa_up.npy`, `surface_down.npy` [., N], `n_orders.npy` and `status.npy` (when given); `I.npy` [k, L, 2N]:
+    the field of the columns `I_columns.npy` (when given).  Which columns: dump_selection.  Returns the file names."""
+    import torch
+
+    def pick(x, idx):
+        if isinstance(x, torch.Tensor):
+            return x.index_select(0, torch.as_tensor(idx, device=x.device)).cpu().numpy()
+        return np.asarray(x)[idx]
+
+    B = len(n_orders)
+    columns = np.arange(B) if columns is None else np.asarray(columns)
+    rows, cols = dump_selection(B, L, N, with_field=field is not None)
+    arrays = {"columns": columns[rows], "toa_up": pick(toa_up, rows), "surface_down": pick(surface_down, rows),
+              "n_orders": pick(n_orders, rows)}
+    if status is not None:
+        arrays["status"] = pick(status, rows)
+    if field is not None:
+        arrays["I"], arrays["I_columns"] = pick(field, cols), columns[cols]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(x, dtype=np.float64))
+    return sorted(name + ".npy" for name in arrays)
+
+
 def measure_strong(a, dev, local_rank, rank, world, on_gpu):
     """BASELINE configs[3] beside a weak-scaling headline: ONE sweep of --columns columns dealt to the ranks, every rank solves its
     shard, the fields are gathered to rank 0 once per step (no collective in the order loop).  Timed like the headline: barrier +
@@ -415,7 +466,12 @@ def main():
                          "torch.distributed point-to-point (field) or through the C ABI's sosrt_gather (abi) "
                          "(default: digest for weak scaling, field for strong)")
     ap.add_argument("--check-columns", type=int, default=3, help="columns compared with the oracle after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the caller received from the last timed step as DIR/<name>.npy, "
+                         "64 MB at most (see dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if a.gather is None:
         a.gather = "field" if a.scaling == "strong" else "digest"
     if a.scaling == "strong" and a.gather == "digest" and a.gpus > 1:
@@ -583,6 +639,23 @@ def main():
     # holds the transport and the contraction of all of them) -- the same in every step
     ol_stats = lanes[0].s.order_loop_stats(True)
     ol_orders_per_step = int(ol_stats[2])
+    # what the caller received from the last timed step, before anything after the timed region runs on the lanes again: with
+    # one rank, the lane's field, order counts and status; with several, what rank 0 gathered (the digests of every rank's columns,
+    # or the whole fields and order counts, the ranks' blocks one after the other in weak scaling, in sweep order in strong)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        if world == 1:
+            last = lanes[(a.steps - 1) % len(lanes)]
+            dumped = dump_outputs(a.dump_outputs, L, N, last.I[:, 0, N:], last.I[:, L - 1, :N], last.n, last.st, last.I, mine)
+        elif a.gather == "digest":
+            g = torch.cat(dig_bufs)
+            dumped = dump_outputs(a.dump_outputs, L, N, g[:, :N], g[:, N:2 * N], g[:, 2 * N])
+        else:
+            gI, gn = gathered["I"], gathered["n"]
+            if strong:
+                gI, gn = plan.restore(gI), plan.restore(gn)
+            gn = gn.reshape(-1)
+            dumped = dump_outputs(a.dump_outputs, L, N, gI[:, 0, N:], gI[:, L - 1, :N], gn, field=gI)
 
     # Outside the timed region: sampled columns of the field the last timed step left on the device against the oracle.
     # Rank 0, its own columns.
@@ -719,6 +792,8 @@ def main():
         }
         if check is not None:
             out["check"] = check
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "files": dumped}
         r_gemm = {"bound": "mfma", "kernel": "k_jn_gemm", "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS,
                   "unit": "TFLOP/s", "frac": achieved / FP64_MFMA_PEAK_TFLOPS, "traffic": None,
                   "avg_launch_ms": gemm_ms / max(gemm_launches, 1), "launches": gemm_launches,

@@ -17,6 +17,11 @@ def _json_line(out):
     return json.loads(lines[0])
 
 
+def _dump(path):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path))}
+
+
 def test_bench_single_gpu_line():
     r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--columns", "64", "--no-cpu-baseline", "--no-extras"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -96,31 +101,35 @@ def test_bench_two_column_groups_at_the_headline_size():
     assert d["extras"]["c2"]["check"]["ok"] and d["extras"]["c3"]["check"]["ok"] and d["extras"]["c5"]["check"]["ok"]
 
 
-def test_bench_two_ranks_share_the_gpu():
+def test_bench_two_ranks_share_the_gpu(tmp_path):
     env = dict(os.environ, SOSRT_BENCH_BACKEND="gloo", SOSRT_BENCH_SHARE_GPU="1")
     port = 29600 + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--columns", "27",
-           "--inflight", "2", "--aerosol", "hg"]
+           "--inflight", "2", "--aerosol", "hg", "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["columns_per_gpu"] == [27, 27] and "cpu_baseline" not in d
     assert len(d["config"]["orders_per_step_per_rank"]) == 2 and d["check"]["ok"]
+    # --dump-outputs: what rank 0 gathered in the last step, the digests of both ranks' columns one block after the other
+    out = _dump(tmp_path)
+    assert sorted(out) == ["columns", "n_orders", "surface_down", "toa_up"] and out["toa_up"].shape == out["surface_down"].shape == (54, 128)
+    assert [int((out["n_orders"][r * 27:(r + 1) * 27] - 1).sum()) for r in (0, 1)] == d["config"]["orders_per_step_per_rank"]
     # the same run also measures ONE sweep over the two ranks (BASELINE configs[3]) beside the weak-scaling headline
     st = d["strong"]
     assert st["scaling"] == "strong" and st["n_gpus"] == 2 and st["value"] > 0 and st["gather_places_columns"]
     assert sorted(st["columns_per_gpu"]) == [13, 14]
 
 
-def test_bench_strong_scaling_spawns_its_own_ranks():
+def test_bench_strong_scaling_spawns_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher environment starts the two ranks itself; --scaling strong deals ONE
     sweep to them by expected work and gathers the whole fields to rank 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SOSRT_BENCH_BACKEND="gloo", SOSRT_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--scaling", "strong", "--steps", "2", "--warmup", "1",
-                        "--columns", "27"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--columns", "27", "--dump-outputs", str(tmp_path)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0
@@ -128,3 +137,38 @@ def test_bench_strong_scaling_spawns_its_own_ranks():
     per = d["config"]["orders_per_step_per_rank"]
     assert max(per) / min(per) < 1.3                      # the deal balances the sum of orders
     assert d["check"]["ok"] and d["check"]["gather_places_columns"]
+    # --dump-outputs: the whole fields rank 0 gathered in the last step, in sweep order
+    import numpy as np
+    out = _dump(tmp_path)
+    assert out["I"].shape == (27, 200, 256) and np.array_equal(out["I_columns"], np.arange(27)) and np.array_equal(out["columns"], np.arange(27))
+    assert np.array_equal(out["I"][:, 0, 128:], out["toa_up"]) and int((out["n_orders"] - 1).sum()) == sum(per)
+
+
+def test_bench_dumps_the_outputs_of_its_last_step(tmp_path):
+    """`--dump-outputs DIR`: 216 columns at (200, 128) -- a field of 88 MB, so a seeded sample of its columns, the rows of every
+    column -- in float64, under 64 MB in all, consistent with the line, and the same from one run to the next; 64 columns with three
+    lanes and two steps: the whole field of the lane that ran the last step (the third lane never runs, its order counts are 0)."""
+    import numpy as np
+    dumps = []
+    for run, cols, steps, extra in (("a", 216, 3, []), ("b", 216, 3, []), ("c", 64, 2, ["--inflight", "3"])):
+        r = subprocess.run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", "0", "--columns", str(cols), "--no-cpu-baseline",
+                            "--no-extras", "--pipelined", "0", "--check-columns", "1", "--dump-outputs", str(tmp_path / run)] + extra,
+                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _json_line(r.stdout)
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["check"]["ok"]
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == d["dumped_outputs"]["files"] == ["I.npy", "I_columns.npy", "columns.npy", "n_orders.npy", "status.npy",
+                                                         "surface_down.npy", "toa_up.npy"]
+        assert sum((tmp_path / run / f).stat().st_size for f in files) <= 64 * 1000 * 1000
+        out = _dump(tmp_path / run)
+        assert all(x.dtype == np.float64 for x in out.values())
+        assert np.array_equal(out["columns"], np.arange(cols))
+        ic = out["I_columns"].astype(int)
+        assert out["I"].shape == (len(ic), 200, 256) and np.all(np.diff(ic) > 0)
+        assert len(ic) == cols if cols == 64 else 0 < len(ic) < cols
+        assert out["toa_up"].shape == out["surface_down"].shape == (cols, 128)
+        assert np.array_equal(out["I"][:, 0, 128:], out["toa_up"][ic]) and np.array_equal(out["I"][:, 199, :128], out["surface_down"][ic])
+        assert int((out["n_orders"] - 1).sum()) == d["config"]["orders_per_step"] and not np.any(out["status"])
+        dumps.append(out)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
