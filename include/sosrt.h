@@ -59,9 +59,11 @@ const char* sosrt_last_error(void);
 /* 100 * major + minor of the ABI this library was built from.  101 (round 4): sosrt_set_stream(h, NULL) names the legacy default
  * stream (100 read NULL as "the handle's own stream"); the per-handle launch plan (sosrt_plan_launch) and the order loop that
  * runs several orders per launch (sosrt_set_order_loop) were added (sosrt_plan_launch may answer SOSRT_PLAN_GEMM_LIVE16_REGS since the
- * second half of that round).  A binding checks sosrt_version() >= the SOSRT_VERSION it
- * was written against. */
-#define SOSRT_VERSION 101
+ * second half of that round).  102: the azimuth-resolved solve -- Fourier modes of the phase functions
+ * (sosrt_phase_modes, sosrt_phase_p0_modes[_dev]), fixed order counts per column (sosrt_set_order_targets) and the
+ * synthesis in azimuth (sosrt_azimuth_accumulate_dev); nothing that existed before changes.  A binding checks
+ * sosrt_version() >= the SOSRT_VERSION it was written against. */
+#define SOSRT_VERSION 102
 int sosrt_version(void);
 
 /* ---- handle ------------------------------------------------------------------------------- */
@@ -236,6 +238,43 @@ int sosrt_phase_p0_dev(sosrt_t* h, int B, int kind, double g, const double* d_mu
 int sosrt_phase_p0(sosrt_t* h, int B, int kind, double g, const double* mu0, double* P0_out);
 /* P(mu, mu') [2N][2N] row-major with the column normalisation trapz(P[:, n], mu) = 4 (phase:107-131); host output */
 int sosrt_phase_matrix(sosrt_t* h, int kind, double g, double* P_out);
+
+/* ---- azimuth-resolved radiance: Fourier modes in azimuth ------------------------------------------
+ * The builders above average over the azimuth.  With the reference's scattering cosine c(a, b, phi) = -(mu_a mu_b + s_a s_b
+ * cos phi), s = sqrt(1 - mu^2), and phi_q = linspace(0, pi, nphi), mode m of a pair of directions is the trapezoid rule
+ *     R^m(a, b) = trapz_q [p(c(a, b, phi_q)) + (-1)^m p(c(a, b, phi_q + pi))] cos(m phi_q)
+ * and the modes are normalised by the m = 0 ring of the same nphi:
+ *     P0^m[b][a] = R^m(a, mu0_b) / (4 pi) * 2 / Z0_b,  Z0_b = trapz_mu(R^0(., mu0_b) / (4 pi))
+ *     P^m[a][n]  = R^m(a, n) / (2 pi) * 4 / Z_n,       Z_n  = trapz_mu(R^0(., n) / (2 pi)).
+ * Mode m of the radiance obeys the order loop of the azimuth average with (P^m, P0^m) in place of (P, P0), and
+ *     I(t, mu, phi) = sum_{m=0}^{M} (2 - delta_m0) I^m(t, mu) cos(m phi).
+ * Azimuth convention: phi is the ring's angle; phi = 0 with an upward mu = mu0 is exact back-scatter (toward the sun).
+ * Mode 0 is always the output of sosrt_phase_matrix / sosrt_phase_p0 (the reference's 25-point ring), bit for bit;
+ * modes m >= 1 use nphi points, 1 <= m <= min(SOSRT_MAX_MODES, nphi - 2) (higher modes alias on nphi points).
+ * Isotropic scattering has no mode m >= 1, Rayleigh none above 2 (p is quadratic in cos phi): exact zeros.  Every mode keeps the flip symmetry P^m(-mu, -mu') = P^m(mu, mu'), so
+ * sosrt_set_phase takes the symmetric contraction for them by itself. */
+#define SOSRT_MAX_MODES 64
+/* modes m_first .. m_first + m_count - 1 of P: P_out [m_count][2N][2N], host output */
+int sosrt_phase_modes(sosrt_t* h, int kind, double g, int m_first, int m_count, int nphi, double* P_out);
+/* the same modes of P0 for B columns: P0_out [m_count][B][2N] (the [B][2N] block of one mode is what sosrt_solve_dev reads).
+ * _dev: d_mu0 [B], d_P0_out device pointers, enqueued on the handle's stream (synchronises it first when a mode m >= 1 is asked
+ * for: the weights of the modes go to the device). */
+int sosrt_phase_p0_modes_dev(sosrt_t* h, int B, int kind, double g, int m_first, int m_count, int nphi, const double* d_mu0,
+                             double* d_P0_out);
+int sosrt_phase_p0_modes(sosrt_t* h, int B, int kind, double g, int m_first, int m_count, int nphi, const double* mu0,
+                         double* P0_out);
+/* Fixed order counts.  A mode m >= 1 has no usable In/I test (its I^m crosses zero and vanishes at mu = +-1, and whole modes
+ * vanish).  While targets are set (d_targets: device int [B] of the solves that follow, the caller's buffer, read by every
+ * solve until cleared; NULL = off, the default) column b runs exactly max(target[b], 1) orders: the ratio is written but not
+ * tested, reaching the target is SOSRT_COL_OK, and only a target above the order budget gives SOSRT_COL_MAXORDERS.  The
+ * order-loop launch (sosrt_set_order_loop) is not planned while targets are set.  The azimuth-resolved driver runs mode m
+ * for the n[b] orders the mode-0 solve of the same column ran. */
+int sosrt_set_order_targets(sosrt_t* h, const int* d_targets);
+/* synthesis: out[b][lev][dir][j] (+)= (2 - delta_m0) * I^m[b][levels[lev]][dir] * cos(m * phi[j]); m == 0 writes out, m >= 1
+ * adds to it.  d_Im [B][L][2N], d_levels [nlev] (0 <= level < L; a level outside gives NaN rows), d_phi [nphi_out] (radians),
+ * d_out [B][nlev][2N][nphi_out]; device pointers, enqueued on the handle's stream. */
+int sosrt_azimuth_accumulate_dev(sosrt_t* h, int B, int m, const double* d_Im, int nlev, const int* d_levels, int nphi_out,
+                                 const double* d_phi, double* d_out);
 
 /* ---- multi-GPU: one process per GPU, columns sharded, ONE collective at the end ------------------
  * Nothing in SOS_Aer_main_specular.py:104-458 couples columns, so the order loop never communicates; these entry

@@ -95,6 +95,9 @@ struct sosrt_handle {
     double *d_phi = nullptr;             // [2][kNPhi] cos(phi), trapz weights of phi = linspace(0, pi, kNPhi) (phase:81-82)
     double *d_z = nullptr;               // [L] altitude grid of the host epilogue
     double *d_tab = nullptr;             // [2][ntab] table of SOSRT_PHASE_TABLE
+    double *d_modetab = nullptr;         // cos(phi_q) [nphi] and w_q cos(m phi_q) [1 + m_count][nphi] of the last mode builder
+    size_t modetab_cap = 0;
+    const int* d_targets = nullptr;      // sosrt_set_order_targets (caller's device array [B]); null: the spec:309 test
     int ntab = 0;
     bool resident = false;               // d_tau / d_I hold the inputs / result of the last sosrt_solve (of resident_B columns)
     int resident_B = 0;
@@ -277,6 +280,7 @@ Conv make_conv(sosrt_handle* h, double tol) {
     Conv c;
     c.active = h->d_active; c.norders = h->d_norders; c.status = h->d_status;
     c.nactive = h->d_nactive; c.ratio = h->d_ratio; c.tol = tol; c.redo = h->d_redo;
+    c.target = nullptr;                 // (the solve sets its own: sosrt_set_order_targets)
     return c;
 }
 
@@ -727,7 +731,7 @@ int sosrt_destroy(sosrt_t* h) {
                         h->d_idx_down, h->d_scal, h->d_desc, h->d_rca, h->d_rcr, h->d_slabrows, h->d_mainrows, h->d_tau, h->d_P0a,
                         h->d_P0r, h->d_Jn, h->d_InA, h->d_InB, h->d_I, h->d_E, h->d_active, h->d_norders, h->d_status,
                         h->d_nactive_sets, h->d_ratio, h->d_redo, h->d_erep, h->d_tauhash, h->d_Wmix, h->d_mixca, h->d_mixcr,
-                        h->d_mixgroup, h->d_Wa_s, h->d_Wr_s, h->d_Wmix_s, h->d_scan_scratch, h->d_scan_sync, h->d_w, h->d_phi, h->d_z, h->d_tab, h->d_slabtilegroup, h->d_livelist, h->d_Wa32, h->d_Wmix32, h->d_nz, h->d_zr0, h->d_zmix, h->d_zwr, h->d_zdtr, h->d_olsync, h->d_ollog};
+                        h->d_mixgroup, h->d_Wa_s, h->d_Wr_s, h->d_Wmix_s, h->d_scan_scratch, h->d_scan_sync, h->d_w, h->d_phi, h->d_z, h->d_tab, h->d_slabtilegroup, h->d_livelist, h->d_Wa32, h->d_Wmix32, h->d_nz, h->d_zr0, h->d_zmix, h->d_zwr, h->d_zdtr, h->d_olsync, h->d_ollog, h->d_modetab};
         for (void* p : ptrs)
             if (p) hipFree(p);
         if (h->h_pub) hipHostFree(h->h_pub);
@@ -1277,7 +1281,7 @@ __global__ void k_init_from_I1(Grid g, const double* __restrict__ I1, double* __
         for (int m = 1; m < g.N; ++m) { const double x = 1.0 / last[m]; if (x > bb) bb = x; }
         const double r = (bb > a) ? bb : a;
         cv.ratio[b] = r; cv.norders[b] = 1; cv.status[b] = SOSRT_COL_OK;
-        const int go = (r >= cv.tol) ? 1 : 0;
+        const int go = conv_go(cv, b, 1, r) ? 1 : 0;
         cv.active[b] = go;
         if (go) atomicAdd(cv.nactive, 1);
     }
@@ -1371,6 +1375,7 @@ int sosrt_solve_dev(sosrt_t* h, int B, const double* d_tau, const double* d_P0_a
         q.cv = make_conv(h, tol);
         q.cv.active += q.b0; q.cv.norders += q.b0; q.cv.status += q.b0; q.cv.ratio += q.b0; q.cv.redo += q.b0;
         q.cv.nactive = h->d_nactive + k;
+        if (h->d_targets) q.cv.target = h->d_targets + q.b0;
     }
     auto start_group = [&](int k) {
         GroupState& q = gs[k];
@@ -1493,7 +1498,7 @@ int sosrt_solve_dev(sosrt_t* h, int B, const double* d_tau, const double* d_P0_a
             oi.simple_zones = h->simple_zones; oi.slabs_mixed = h->nslab == 0 || h->mix_groups > 0;
             oi.need_small = g.nsmall > 0 && h->need_small; oi.saving = d_I_saved_out != nullptr;
             oi.orders_left = h->order_budget - q.n;
-            oi.cu_share = q.ol_off ? 0 : h->cu_count / NG;
+            oi.cu_share = (q.ol_off || h->d_targets) ? 0 : h->cu_count / NG;   // (no order-loop launch with order targets)
             LaunchPlan pl = plan_order(h, shape, oi);
             if (pl.order_loop) {
                 // its workgroups wait for each other: they must all fit the CUs no other order-loop launch of this process holds
@@ -1792,6 +1797,132 @@ int sosrt_phase_matrix(sosrt_t* h, int kind, double g, double* P_out) {
     rc = body();
     hipFree(dP);
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Fourier modes in azimuth
+// ---------------------------------------------------------------------------------------------
+static int modes_check(sosrt_handle* h, int kind, double g, int m_first, int m_count, int nphi) {
+    if (int e = phase_check(h, kind, g)) return e;
+    if (m_first < 0 || m_count < 1) return fail(SOSRT_E_INVALID, "modes: need m_first >= 0 and m_count >= 1 (got %d, %d)", m_first, m_count);
+    const int m_last = m_first + m_count - 1;
+    if (m_last > SOSRT_MAX_MODES) return fail(SOSRT_E_INVALID, "modes: the highest mode is %d, at most SOSRT_MAX_MODES = %d", m_last, SOSRT_MAX_MODES);
+    if (m_last >= 1 && m_last > nphi - 2)
+        return fail(SOSRT_E_INVALID, "modes: mode %d needs nphi >= %d (a trapezoid rule of nphi points on [0, pi] aliases higher modes; got %d)",
+                    m_last, m_last + 2, nphi);
+    return 0;
+}
+
+// uploads cos(phi_q) and the weights of modes [mf, mf + mc) (row 0: the m = 0 ring) for phi = linspace(0, pi, nphi);
+// synchronises the handle's stream first: an earlier builder may still read the buffer
+static int modes_table(sosrt_handle* h, int nphi, int mf, int mc) {
+    const size_t need = (size_t)(2 + mc) * nphi;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (need > h->modetab_cap) {
+        if (h->d_modetab) { hipFree(h->d_modetab); h->d_modetab = nullptr; h->modetab_cap = 0; }
+        if (int e = dalloc(&h->d_modetab, need)) return e;
+        h->modetab_cap = need;
+    }
+    std::vector<double> phi(nphi), t(need);
+    const double pi = 3.141592653589793, step = pi / (nphi - 1);
+    for (int q = 0; q < nphi; ++q) phi[q] = q * step;          // np.linspace(0, pi, nphi)
+    phi[nphi - 1] = pi;
+    for (int q = 0; q < nphi; ++q) {
+        const double w = ((q > 0 ? phi[q] - phi[q - 1] : 0.0) + (q + 1 < nphi ? phi[q + 1] - phi[q] : 0.0)) / 2;
+        t[q] = std::cos(phi[q]);
+        t[nphi + q] = w;
+        for (int j = 1; j <= mc; ++j) t[(size_t)(1 + j) * nphi + q] = w * std::cos((mf + j - 1) * phi[q]);
+    }
+    HIPCHK(hipMemcpy(h->d_modetab, t.data(), need * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int sosrt_phase_modes(sosrt_t* h, int kind, double g, int m_first, int m_count, int nphi, double* P_out) {
+    if (int e = modes_check(h, kind, g, m_first, m_count, nphi)) return e;
+    if (!P_out) return fail(SOSRT_E_INVALID, "null argument");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t DD = (size_t)h->D * h->D;
+    const int mf = m_first > 0 ? m_first : 1, mc = m_first > 0 ? m_count : m_count - 1;   // modes m >= 1 of the request
+    if (mc > 0)
+        if (int e = modes_table(h, nphi, mf, mc)) return e;
+    double* dP = nullptr;
+    if (int e = dalloc(&dP, m_count * DD)) return e;
+    auto body = [&]() -> int {
+        if (m_first == 0)                                  // mode 0 is the existing builder's output, bit for bit (25-point ring)
+            launch_phase_matrix(s, h->g, h->d_w, kind, g, h->d_tab, h->d_tab ? h->d_tab + h->ntab : nullptr, h->ntab, h->d_phi,
+                                h->d_phi + kNPhi, kNPhi, dP);
+        if (mc > 0)
+            launch_phase_modes(s, h->g, h->d_w, kind, g, h->d_tab, h->d_tab ? h->d_tab + h->ntab : nullptr, h->ntab, h->d_modetab,
+                               h->d_modetab + nphi, nphi, mf, mc, dP + (m_count - mc) * DD);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(P_out, dP, m_count * DD * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = body();
+    hipFree(dP);
+    return rc;
+}
+
+int sosrt_phase_p0_modes_dev(sosrt_t* h, int B, int kind, double g, int m_first, int m_count, int nphi, const double* d_mu0,
+                             double* d_P0_out) {
+    if (int e = modes_check(h, kind, g, m_first, m_count, nphi)) return e;
+    if (B < 1 || !d_mu0 || !d_P0_out) return fail(SOSRT_E_INVALID, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    const int mf = m_first > 0 ? m_first : 1, mc = m_first > 0 ? m_count : m_count - 1;
+    if (mc > 0)
+        if (int e = modes_table(h, nphi, mf, mc)) return e;
+    if (m_first == 0)
+        launch_phase_p0(h->stream, h->g, h->d_w, B, kind, g, h->d_tab, h->d_tab ? h->d_tab + h->ntab : nullptr, h->ntab, h->d_phi,
+                        h->d_phi + kNPhi, kNPhi, d_mu0, d_P0_out);
+    if (mc > 0)
+        launch_phase_p0_modes(h->stream, h->g, h->d_w, B, kind, g, h->d_tab, h->d_tab ? h->d_tab + h->ntab : nullptr, h->ntab,
+                              h->d_modetab, h->d_modetab + nphi, nphi, mf, mc, d_mu0, d_P0_out + (size_t)(m_count - mc) * B * h->D);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_phase_p0_modes(sosrt_t* h, int B, int kind, double g, int m_first, int m_count, int nphi, const double* mu0,
+                         double* P0_out) {
+    if (int e = modes_check(h, kind, g, m_first, m_count, nphi)) return e;
+    if (B < 1 || B > h->max_batch || !mu0 || !P0_out) return fail(SOSRT_E_INVALID, "bad argument (B must be 1..max_batch)");
+    for (int b = 0; b < B; ++b)
+        if (!(mu0[b] > 0 && mu0[b] <= 1)) return fail(SOSRT_E_INVALID, "column %d: mu0 must be in (0, 1]", b);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t n = (size_t)m_count * B * h->D;
+    double* dP = nullptr;
+    if (int e = dalloc(&dP, n + B)) return e;
+    auto body = [&]() -> int {
+        HIPCHK(hipMemcpyAsync(dP + n, mu0, B * sizeof(double), hipMemcpyHostToDevice, s));
+        if (int e = sosrt_phase_p0_modes_dev(h, B, kind, g, m_first, m_count, nphi, dP + n, dP)) return e;
+        HIPCHK(hipMemcpyAsync(P0_out, dP, n * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(s);
+    hipFree(dP);
+    return rc;
+}
+
+int sosrt_set_order_targets(sosrt_t* h, const int* d_targets) {
+    if (int e = need_gpu(h)) return e;
+    h->d_targets = d_targets;
+    return 0;
+}
+
+int sosrt_azimuth_accumulate_dev(sosrt_t* h, int B, int m, const double* d_Im, int nlev, const int* d_levels, int nphi_out,
+                                 const double* d_phi, double* d_out) {
+    if (int e = need_gpu(h)) return e;
+    if (B < 1 || m < 0 || nlev < 1 || nphi_out < 1 || !d_Im || !d_levels || !d_phi || !d_out)
+        return fail(SOSRT_E_INVALID, "azimuth accumulate: bad argument (B=%d m=%d nlev=%d nphi_out=%d)", B, m, nlev, nphi_out);
+    if ((long long)B * nlev > 0x7fffffffLL) return fail(SOSRT_E_INVALID, "azimuth accumulate: B * nlev too large");
+    HIPCHK(hipSetDevice(h->device));
+    launch_azimuth_accumulate(h->stream, h->g, B, m, d_Im, nlev, d_levels, nphi_out, d_phi, d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

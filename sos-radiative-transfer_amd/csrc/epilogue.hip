@@ -10,10 +10,17 @@
 //   k_phase_p0      azimuth-averaged first-order phase function P0(mu, mu0) of every column of a sweep
 //                   (phase:86-103, 148-165, 245-262): a mu0 sweep needs a fresh P0 per column.
 //   k_phase_matrix  P(mu, mu') with the reference's column normalisation (phase:107-131, 169-193, 266-290).
+//   k_phase_modes / k_phase_p0_modes
+//                   Fourier modes m >= 1 of the same two in azimuth (the azimuth-resolved solve): one
+//                   evaluation of p per (pair, phi node) feeds every requested mode and the m = 0 ring that normalises.
+//   k_azimuth_accumulate
+//                   synthesis I(phi) = sum_m (2 - delta_m0) I^m cos(m phi) on the requested levels.
 //
 // Phase-function kinds: isotropic (phase:68), Rayleigh (phase:79), Henyey-Greenstein (phase:141) and a
 // tabulated function with the reference's linear interpolation (phase:198-236; fwc:3,173 is its table).
 #include "kernels.hpp"
+
+#include <type_traits>
 
 #include "../../include/sosrt.h"
 
@@ -200,6 +207,115 @@ __global__ __launch_bounds__(256) void k_phase_matrix(Grid g, const double* __re
     for (int m = tid; m < D; m += blockDim.x) P[(size_t)m * D + n] = 4 * P[(size_t)m * D + n] / norm;
 }
 
+// Ring of mode m: R^m(a, b) = trapz_q [p(c(phi_q)) + (-1)^m p(c(phi_q + pi))] cos(m phi_q),
+// c(phi) = -(mu_a mu_b + s_a s_b cos phi), phi_q = linspace(0, pi, nphi).  acc[0] is the m = 0 ring (the normaliser),
+// acc[j], 1 <= j <= mc, mode mf + j - 1.  tab[j][q] = w_q cos(m_j phi_q) (row 0: w_q).  K is a compile-time bound so that
+// the accumulators stay in registers; the guard j <= mc is uniform.
+template <int K>
+__device__ __forceinline__ void ring_modes(const PhaseFn& p, double cc, double ss, const double* __restrict__ cosphi,
+                                           const double* __restrict__ tab, int nphi, int mf, int mc, double (&acc)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = 0;
+    for (int q = 0; q < nphi; ++q) {
+        const double x = ss * cosphi[q];
+        const double p1 = p(-(cc + x)), p2 = p(-(cc - x));
+        const double sp = p1 + p2, sm = p1 - p2;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (j <= mc) acc[j] += tab[(size_t)j * nphi + q] * ((j > 0 && ((mf + j - 1) & 1)) ? sm : sp);
+    }
+}
+
+// Rayleigh's p is quadratic in cos phi: its modes m >= 3 are zero, not rounding noise (a matrix of noise has no flip symmetry to
+// rounding and would cost the solve of that mode the full contraction product)
+__device__ __forceinline__ bool vanishes(const PhaseFn& p, int m) { return p.kind == SOSRT_PHASE_RAYLEIGH && m >= 3; }
+
+// P^m[a][n] = R^m(a, n) / (2 pi) * 4 / Z_n, Z_n = trapz_mu(R^0(., n) / (2 pi)); out [mc][D][D]; one workgroup per column n
+template <int K>
+__global__ __launch_bounds__(256) void k_phase_modes(Grid g, const double* __restrict__ w_all, PhaseFn p,
+                                                     const double* __restrict__ cosphi, const double* __restrict__ tab,
+                                                     int nphi, int mf, int mc, double* __restrict__ P) {
+    const int n = blockIdx.x, tid = threadIdx.x, D = g.D;
+    const size_t DD = (size_t)D * D;
+    __shared__ double s_red[8];
+    if (p.kind == SOSRT_PHASE_ISO) {                                  // no azimuth dependence: every mode m >= 1 vanishes
+        for (int j = 0; j < mc; ++j)
+            for (int m = tid; m < D; m += blockDim.x) P[j * DD + (size_t)m * D + n] = 0.0;
+        return;
+    }
+    const double mun = g.mu[n], sn = sqrt(1 - mun * mun);
+    double part = 0;
+    for (int m0 = 0; m0 < D; m0 += blockDim.x) {
+        const int m = m0 + tid;
+        if (m < D) {
+            const double mu = g.mu[m];
+            double acc[K];
+            ring_modes<K>(p, mu * mun, sn * sqrt(1 - mu * mu), cosphi, tab, nphi, mf, mc, acc);
+            part += w_all[m] * (acc[0] / (2 * SOSRT_PI));
+#pragma unroll
+            for (int j = 1; j < K; ++j)
+                if (j <= mc) P[(j - 1) * DD + (size_t)m * D + n] = vanishes(p, mf + j - 1) ? 0.0 : acc[j] / (2 * SOSRT_PI);
+        }
+    }
+    const double norm = bsum(part, s_red);
+    for (int m = tid; m < D; m += blockDim.x)                         // (each thread rescales what it wrote)
+        for (int j = 0; j < mc; ++j) P[j * DD + (size_t)m * D + n] = 4 * P[j * DD + (size_t)m * D + n] / norm;
+}
+
+// P0^m[b][a] = R^m(a, mu0_b) / (4 pi) * 2 / Z0_b, Z0_b = trapz_mu(R^0(., mu0_b) / (4 pi)); out [mc][B][D]; one workgroup per column
+template <int K>
+__global__ __launch_bounds__(256) void k_phase_p0_modes(Grid g, const double* __restrict__ w_all, int B, PhaseFn p,
+                                                        const double* __restrict__ cosphi, const double* __restrict__ tab,
+                                                        int nphi, int mf, int mc, const double* __restrict__ mu0_all,
+                                                        double* __restrict__ P0_all) {
+    const int b = blockIdx.x, tid = threadIdx.x, D = g.D;
+    const size_t BD = (size_t)B * D;
+    __shared__ double s_red[8];
+    double* P0 = P0_all + (size_t)b * D;
+    if (p.kind == SOSRT_PHASE_ISO) {
+        for (int j = 0; j < mc; ++j)
+            for (int m = tid; m < D; m += blockDim.x) P0[j * BD + m] = 0.0;
+        return;
+    }
+    const double mu0 = mu0_all[b];
+    const double s0 = sqrt(1 - mu0 * mu0);
+    double part = 0;
+    for (int m0 = 0; m0 < D; m0 += blockDim.x) {
+        const int m = m0 + tid;
+        if (m < D) {
+            const double mu = g.mu[m];
+            double acc[K];
+            ring_modes<K>(p, mu * mu0, s0 * sqrt(1 - mu * mu), cosphi, tab, nphi, mf, mc, acc);
+            part += w_all[m] * (acc[0] / (4 * SOSRT_PI));
+#pragma unroll
+            for (int j = 1; j < K; ++j)
+                if (j <= mc) P0[(j - 1) * BD + m] = vanishes(p, mf + j - 1) ? 0.0 : acc[j] / (4 * SOSRT_PI);
+        }
+    }
+    const double norm = bsum(part, s_red);
+    for (int m = tid; m < D; m += blockDim.x)
+        for (int j = 0; j < mc; ++j) P0[j * BD + m] = P0[j * BD + m] / norm * 2;
+}
+
+// out[b][lev][dir][j]: mode 0 writes I^0 itself, modes m >= 1 add 2 I^m cos(m phi_j).  One workgroup per (column, level);
+// a level outside [0, L) gives NaN rows instead of a read out of bounds.
+__global__ __launch_bounds__(256) void k_azimuth_accumulate(int L, int D, int m, const double* __restrict__ Im, int nlev,
+                                                            const int* __restrict__ levels, int nphi, const double* __restrict__ phi,
+                                                            double* __restrict__ out) {
+    const int b = blockIdx.x / nlev, lev = blockIdx.x % nlev;
+    const int t = levels[lev];
+    const bool ok = t >= 0 && t < L;
+    const double* row = Im + ((size_t)b * L + (ok ? t : 0)) * D;
+    double* o = out + (size_t)blockIdx.x * D * nphi;
+    const int n = D * nphi;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int dir = i / nphi, j = i - dir * nphi;
+        const double v = ok ? row[dir] : __builtin_nan("");
+        if (m == 0) o[i] = v;
+        else o[i] += 2 * v * cos(m * phi[j]);
+    }
+}
+
 }  // namespace
 
 void launch_epilogue(hipStream_t s, const Grid& g, const double* w, int B, const double* tau, const double* I,
@@ -219,6 +335,40 @@ void launch_phase_matrix(hipStream_t s, const Grid& g, const double* w, int kind
                          const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi, double* P) {
     PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
     hipLaunchKernelGGL(k_phase_matrix, dim3(g.D), dim3(256), 0, s, g, w, p, cosphi, wphi, nphi, P);
+}
+
+template <typename F>
+static void modes_dispatch(int mc, F&& f) {
+    // accumulators: the m = 0 ring plus mc modes, rounded up to a compiled size
+    if (mc + 1 <= 9) f(std::integral_constant<int, 9>());
+    else if (mc + 1 <= 17) f(std::integral_constant<int, 17>());
+    else if (mc + 1 <= 33) f(std::integral_constant<int, 33>());
+    else f(std::integral_constant<int, kMaxModes + 1>());
+}
+
+void launch_phase_modes(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
+                        const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
+                        int m_count, double* P_out) {
+    PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
+    modes_dispatch(m_count, [&](auto k) {
+        hipLaunchKernelGGL(k_phase_modes<decltype(k)::value>, dim3(g.D), dim3(256), 0, s, g, w, p, cosphi, tab, nphi, m_first,
+                           m_count, P_out);
+    });
+}
+
+void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
+                           const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
+                           int m_count, const double* mu0, double* P0_out) {
+    PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
+    modes_dispatch(m_count, [&](auto k) {
+        hipLaunchKernelGGL(k_phase_p0_modes<decltype(k)::value>, dim3(B), dim3(256), 0, s, g, w, B, p, cosphi, tab, nphi,
+                           m_first, m_count, mu0, P0_out);
+    });
+}
+
+void launch_azimuth_accumulate(hipStream_t s, const Grid& g, int B, int m, const double* Im, int nlev, const int* levels,
+                               int nphi_out, const double* phi, double* out) {
+    hipLaunchKernelGGL(k_azimuth_accumulate, dim3(B * nlev), dim3(256), 0, s, g.L, g.D, m, Im, nlev, levels, nphi_out, phi, out);
 }
 
 }  // namespace sosrt

@@ -365,7 +365,7 @@ __global__ void k_first_order(Grid g, const double* __restrict__ tau_all, const 
             cv.ratio[b] = r;
             cv.norders[b] = 1;
             cv.status[b] = SOSRT_COL_OK;
-            const int go = (r >= cv.tol) ? 1 : 0;
+            const int go = conv_go(cv, b, 1, r) ? 1 : 0;
             cv.active[b] = go;
             if (go) atomicAdd(cv.nactive, 1);
         }
@@ -563,7 +563,7 @@ __global__ void k_first_order_readme(Grid g, const double* __restrict__ w_all, c
             cv.ratio[b] = r;
             cv.norders[b] = 1;
             cv.status[b] = SOSRT_COL_OK;
-            const int go = (r >= cv.tol) ? 1 : 0;
+            const int go = conv_go(cv, b, 1, r) ? 1 : 0;
             cv.active[b] = go;
             if (go) atomicAdd(cv.nactive, 1);
         }
@@ -1048,7 +1048,7 @@ __global__ __launch_bounds__(MAXT) void k_transport(TransportArgs a) {
         if (tid == 0) {
             a.cv.ratio[b] = r;
             a.cv.norders[b] = a.order;
-            if (!(r >= a.cv.tol)) {
+            if (!conv_go(a.cv, b, a.order, r)) {
                 a.cv.active[b] = 0;
                 atomicSub(a.cv.nactive, 1);
             }

@@ -76,8 +76,15 @@ struct Conv {
     int* nactive;              // [1]
     double* ratio;             // [B] last value of the spec:309 test
     int* redo;                 // [B] set by k_transport_fast when the column needs the general upward sweep
+    const int* target;         // [B] or null: fixed order counts (sosrt_set_order_targets), the ratio is written but not tested
     double tol;
 };
+
+// The stop decision of every order: go on while the spec:309 ratio is >= tol, or -- with order targets -- while the column
+// has run fewer orders than its target.  Without targets the expression is the one it always was (same bits).
+__device__ __forceinline__ bool conv_go(const Conv& cv, int b, int order, double r) {
+    return cv.target ? order < cv.target[b] : r >= cv.tol;
+}
 
 constexpr int GEMM_BM = 64, GEMM_BN = 128, GEMM_KC = 16;
 #ifndef SOSRT_GEMM_RT
@@ -294,6 +301,19 @@ void launch_phase_p0(hipStream_t s, const Grid& g, const double* w, int B, int k
                      const double* mu0, double* P0);
 void launch_phase_matrix(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
                          const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi, double* P);
+// Fourier modes of the phase function in azimuth (sosrt_phase_modes): modes [m_first, m_first + m_count) with m_first >= 1 of
+// P^m (P_out [m_count][D][D]) or of P0^m (P0_out [m_count][B][D]); tab [1 + m_count][nphi] holds the trapezoid weights of
+// phi = linspace(0, pi, nphi) (row 0, the m = 0 ring that normalises) and w_q cos(m phi_q) of each mode; cosphi [nphi].
+constexpr int kMaxModes = 64;      // SOSRT_MAX_MODES
+void launch_phase_modes(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
+                        const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
+                        int m_count, double* P_out);
+void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
+                           const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
+                           int m_count, const double* mu0, double* P0_out);
+// out[b][lev][dir][j] (+)= (2 - delta_m0) I^m[b][levels[lev]][dir] cos(m phi[j])   (m == 0 writes, m >= 1 adds)
+void launch_azimuth_accumulate(hipStream_t s, const Grid& g, int B, int m, const double* Im, int nlev, const int* levels,
+                               int nphi_out, const double* phi, double* out);
 void launch_limit_rows(hipStream_t s, const Grid& g, int R, int table, const double* rows, double* out);
 void launch_asymptotic(hipStream_t s, int R, int stride, const int* len, const double* J, const double* tau,
                        const double* tau_t, const double* mu, double* out);

@@ -375,7 +375,7 @@ __global__ __launch_bounds__(MAXT) void k_transport_fast(TransportArgs a) {
         if (tid == 0) {
             a.cv.ratio[b] = r;
             a.cv.norders[b] = a.order;
-            if (!(r >= a.cv.tol)) {
+            if (!conv_go(a.cv, b, a.order, r)) {
                 a.cv.active[b] = 0;
                 atomicSub(a.cv.nactive, 1);
             }

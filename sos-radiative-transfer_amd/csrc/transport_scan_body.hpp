@@ -1120,12 +1120,12 @@ __device__ __forceinline__ int transport_scan_order(const TransportArgs& a, int 
         if (tid == 0) {
             a.cv.ratio[b] = r;
             a.cv.norders[b] = a.order;
-            if (!(r >= a.cv.tol)) {
+            if (!conv_go(a.cv, b, a.order, r)) {
                 a.cv.active[b] = 0;
                 atomicSub(a.cv.nactive, 1);
             }
         }
-        return leave(!(r >= a.cv.tol) ? 1 : 0);
+        return leave(!conv_go(a.cv, b, a.order, r) ? 1 : 0);
     } else if (tid == 0 && a.cv.status) {
         a.cv.status[b] = SOSRT_COL_OK;
     }

@@ -20,6 +20,7 @@ PLAN_TRANSPORT_GENERAL, PLAN_TRANSPORT_FAST, PLAN_TRANSPORT_RING, PLAN_TRANSPORT
 CONTRACT_F64, CONTRACT_F32, CONTRACT_F64_FULL = 0, 1, 2
 FIRST_ORDER_CODED, FIRST_ORDER_README = 0, 1
 PHASE_ISO, PHASE_RAYLEIGH, PHASE_HG, PHASE_TABLE = 0, 1, 2, 3
+MAX_MODES = 64
 
 _dp = POINTER(c_double)
 _ip = POINTER(c_int)
@@ -58,6 +59,11 @@ SIGNATURES = {
     "sosrt_phase_p0_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
     "sosrt_phase_p0": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
     "sosrt_phase_matrix": (c_int, [c_void_p, c_int, c_double, c_void_p]),
+    "sosrt_phase_modes": (c_int, [c_void_p, c_int, c_double, c_int, c_int, c_int, c_void_p]),
+    "sosrt_phase_p0_modes_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sosrt_phase_p0_modes": (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sosrt_set_order_targets": (c_int, [c_void_p, c_void_p]),
+    "sosrt_azimuth_accumulate_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_comm_unique_id": (c_int, [c_void_p]),
     "sosrt_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "sosrt_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

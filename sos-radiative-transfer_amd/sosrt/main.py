@@ -48,6 +48,8 @@ class BatchResult:
     idx_up: int
     idx_down: int
     I_saved: Optional[np.ndarray] = None
+    I_azimuth: Optional[np.ndarray] = None   # [B, nlev, 2N, len(azimuths)] (azimuths=...): radiance at the requested levels
+    mode_status: Optional[np.ndarray] = None  # [M + 1, B] status of the solve of every Fourier mode (row 0 is `status`)
 
 
 _solvers = {}
@@ -90,7 +92,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   nb_layers=200, nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7,
                   mie_atm=None, mie_aer=None,
                   P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular", tol=1e-4, max_orders=256,
-                  save_orders=False, device=0, devices=None, raise_on_error=True, first_order="coded") -> BatchResult:
+                  save_orders=False, device=0, devices=None, raise_on_error=True, first_order="coded", azimuths=None,
+                  n_modes=None, nphi_modes=None, levels=(0, -1)) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -98,7 +101,16 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     `first_order='readme'`: the README's Lambertian first order
     (Solver.set_first_order; parity unpinned, single device).  `devices=[0, 1, ...]` shards the columns over several
     GPUs of the node, one worker process each, and gathers the fields (sosrt.dist.solve_on_devices; per-order
-    fields are not gathered)."""
+    fields are not gathered).
+
+    `azimuths` (radians, array): also the azimuth-resolved radiance I(phi) at the rows `levels` (default TOA and surface),
+    BatchResult.I_azimuth [B, len(levels), 2N, len(azimuths)], from the Fourier modes m = 0 .. `n_modes` (default 16) of the
+    phase functions (`azimuth_modes`; modes m >= 1 built on `nphi_modes` azimuth nodes, default max(25, 2 n_modes + 1)).  phi
+    follows the reference's ring: phi = 0 with an upward mu = mu0 is exact back-scatter.  I, n and status are those of the
+    plain call, bit for bit.  Needs named phase functions (not arrays), the specular surface and a single device."""
+    if azimuths is not None:
+        M, nphi, lev = _azimuth_args(azimuths, n_modes, nphi_modes, levels, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface,
+                                     devices, first_order)
     if devices is not None and len(devices) > 1:
         if save_orders:
             raise ValueError("save_orders is not available with devices=[...]")
@@ -125,7 +137,96 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         s.set_first_order("coded")                           # (the solver is cached)
     if raise_on_error:
         _raise_status(r.status, N)
-    return BatchResult(I=r.I, n=r.n, status=r.status, tau=tau, mu=mu, idx_up=iu, idx_down=idn, I_saved=r.I_saved)
+    out = BatchResult(I=r.I, n=r.n, status=r.status, tau=tau, mu=mu, idx_up=iu, idx_down=idn, I_saved=r.I_saved)
+    if azimuths is not None:
+        mu0v = np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
+        out.I_azimuth, out.mode_status = azimuth_modes(s, tau, r, mu0v, azimuths, M, nphi, lev, atm_phase_fun, g_atm, mie_atm,
+                                                       aer_phase_fun, g_aer, mie_aer, device)
+        if raise_on_error:
+            _raise_status(out.mode_status, N)
+    return out
+
+
+def _azimuth_args(azimuths, n_modes, nphi_modes, levels, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface, devices, first_order):
+    """Checks of the azimuth-resolved call, made before any handle exists: (M, nphi, levels as row indices)."""
+    if any(x is not None for x in (P_atm, P_aer, P0_atm, P0_aer)):
+        raise ValueError("azimuths need named phase functions: the Fourier modes cannot be derived from azimuth-averaged arrays")
+    if surface != "specular" or first_order != "coded":
+        raise ValueError("azimuths are available with the specular surface only (the Lambertian terms of modes m >= 1 are not built)")
+    if devices is not None and len(devices) > 1:
+        raise ValueError("azimuths are not available with devices=[...]")
+    phi = np.asarray(azimuths, dtype=np.float64)
+    if phi.ndim != 1 or phi.size == 0 or not np.all(np.isfinite(phi)):
+        raise ValueError("azimuths must be a non-empty 1-d array of finite angles (radians)")
+    M = 16 if n_modes is None else int(n_modes)
+    if not 1 <= M <= _lib.MAX_MODES:
+        raise ValueError("n_modes must be in 1..%d (got %d)" % (_lib.MAX_MODES, M))
+    nphi = max(25, 2 * M + 1) if nphi_modes is None else int(nphi_modes)
+    if M > nphi - 2:
+        raise ValueError("n_modes = %d needs nphi_modes >= %d (got %d)" % (M, M + 2, nphi))
+    L = int(nb_layers)
+    lev = [int(x) for x in np.atleast_1d(levels)]
+    if not lev or any(not -L <= x < L for x in lev):
+        raise ValueError("levels must be row indices in [-%d, %d)" % (L, L))
+    return M, nphi, [x + L if x < 0 else x for x in lev]
+
+
+def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
+                  mie_aer, device=0):
+    """Modes m = 1..M of the solve `r` (the mode-0 result of handle `s`, whose columns are set): per mode the matrices and
+    first-order vectors of both phase functions, a solve with the order counts of mode 0 (sosrt_set_order_targets), and the
+    synthesis at `levels`.  Returns (I_azimuth [B, nlev, 2N, len(azimuths)], mode status [M + 1, B]).  The handle's mode-0
+    phase matrices are put back and its targets cleared afterwards, also on error."""
+    import torch
+    from .inputs import _scalar_phase
+    B, L = tau.shape
+    D = s.D
+    dev = torch.device("cuda", device)
+    P_mode0 = s._P
+    status = np.zeros((M + 1, B), dtype=np.int32)
+    status[0] = r.status
+    with torch.cuda.device(dev):
+        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        try:
+            d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
+            d_mu0 = torch.from_numpy(np.ascontiguousarray(mu0, dtype=np.float64)).to(dev)
+            d_target = torch.from_numpy(np.ascontiguousarray(r.n, dtype=np.int32)).to(dev)
+            d_lev = torch.tensor(levels, dtype=torch.int32, device=dev)
+            d_phi = torch.from_numpy(np.ascontiguousarray(azimuths, dtype=np.float64)).to(dev)
+            nlev, nout = len(levels), d_phi.numel()
+            d_out = torch.empty((B, nlev, D, nout), dtype=torch.float64, device=dev)
+            d_Im = torch.from_numpy(np.ascontiguousarray(r.I)).to(dev)
+            s.azimuth_accumulate_device(0, d_Im.data_ptr(), d_lev.data_ptr(), nlev, d_phi.data_ptr(), nout, d_out.data_ptr(), B=B)
+            # modes m >= 1 of both phase functions: the matrices to the host (one fold each in set_phase), the first-order
+            # vectors where the solve reads them
+            Pm, d_P0 = [], []
+            for name, g, mie in ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)):
+                kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **(mie or {}))[1]
+                if tab is not None:
+                    s.set_phase_table(*tab)
+                Pm.append(s.phase_modes(kind, 1, M, nphi, g))
+                p0 = torch.empty((M, B, D), dtype=torch.float64, device=dev)
+                s.phase_p0_modes_device(kind, d_mu0.data_ptr(), p0.data_ptr(), B, 1, M, nphi, g)
+                d_P0.append(p0)
+            d_n = torch.zeros(B, dtype=torch.int32, device=dev)
+            d_st = torch.zeros((M, B), dtype=torch.int32, device=dev)
+            s.set_order_targets(d_target.data_ptr())
+            for m in range(1, M + 1):
+                s.synchronize()                              # (set_phase rewrites the matrices the previous mode's solve read)
+                s.set_phase(Pm[0][m - 1], Pm[1][m - 1])
+                s.solve_device(d_tau.data_ptr(), d_P0[0][m - 1].data_ptr(), d_P0[1][m - 1].data_ptr(), d_Im.data_ptr(),
+                               d_n_orders=d_n.data_ptr(), d_status=d_st[m - 1].data_ptr())
+                s.azimuth_accumulate_device(m, d_Im.data_ptr(), d_lev.data_ptr(), nlev, d_phi.data_ptr(), nout, d_out.data_ptr(), B=B)
+            s.synchronize()
+            status[1:] = d_st.cpu().numpy()
+            I_az = d_out.cpu().numpy()
+        finally:
+            s.synchronize()
+            s.set_order_targets(None)
+            s.set_stream(None)
+            if P_mode0[0] is not None:
+                s.set_phase(*P_mode0)
+    return I_az, status
 
 
 def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down, nb_layers, nb_angles,

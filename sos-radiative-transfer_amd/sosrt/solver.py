@@ -320,6 +320,44 @@ class Solver:
         check(lib().sosrt_phase_matrix(self._h, self._KINDS[kind], float(g), _ptr(out)))
         return out
 
+    # ---- Fourier modes in azimuth (sosrt.h: azimuth-resolved radiance) ----
+    def phase_modes(self, kind, m_first, m_count, nphi=25, g=0.0):
+        """Modes m_first .. m_first + m_count - 1 of P -> [m_count, 2N, 2N].  Mode 0 is `phase_matrix` bit for bit; modes
+        m >= 1 use the nphi-point ring (1 <= m <= min(64, nphi - 2))."""
+        out = np.empty((int(m_count), self.D, self.D))
+        check(lib().sosrt_phase_modes(self._h, self._KINDS[kind], float(g), int(m_first), int(m_count), int(nphi), _ptr(out)))
+        return out
+
+    def phase_p0_modes(self, kind, mu0, m_first, m_count, nphi=25, g=0.0):
+        """The same modes of P0 for an array of mu0 -> [m_count, len(mu0), 2N]."""
+        m = np.ascontiguousarray(np.atleast_1d(mu0), dtype=np.float64)
+        out = np.empty((int(m_count), m.size, self.D))
+        step = max(1, self.max_batch)
+        for i in range(0, m.size, step):
+            mm = np.ascontiguousarray(m[i:i + step])
+            oo = np.empty((int(m_count), mm.size, self.D))
+            check(lib().sosrt_phase_p0_modes(self._h, int(mm.size), self._KINDS[kind], float(g), int(m_first), int(m_count),
+                                             int(nphi), _ptr(mm), _ptr(oo)))
+            out[:, i:i + step] = oo
+        return out
+
+    def phase_p0_modes_device(self, kind, d_mu0: int, d_P0_out: int, B: int, m_first, m_count, nphi=25, g=0.0):
+        """Device twin: d_mu0 [B], d_P0_out [m_count][B][2N] (addresses), enqueued on the handle's stream."""
+        check(lib().sosrt_phase_p0_modes_dev(self._h, int(B), self._KINDS[kind], float(g), int(m_first), int(m_count), int(nphi),
+                                             ctypes.c_void_p(d_mu0), ctypes.c_void_p(d_P0_out)))
+
+    def set_order_targets(self, d_targets: Optional[int]):
+        """Fixed order counts for the solves that follow: `d_targets` is the device address of an int32 [B] array (kept by the
+        caller while set), None / 0 switches back to the convergence test."""
+        check(lib().sosrt_set_order_targets(self._h, ctypes.c_void_p(d_targets) if d_targets else None))
+
+    def azimuth_accumulate_device(self, m: int, d_Im: int, d_levels: int, nlev: int, d_phi: int, nphi_out: int, d_out: int,
+                                  B: Optional[int] = None):
+        """out[b][lev][dir][j] (+)= (2 - delta_m0) I^m[b][levels[lev]][dir] cos(m phi[j]) on device addresses (m = 0 writes)."""
+        check(lib().sosrt_azimuth_accumulate_dev(self._h, int(self.B if B is None else B), int(m), ctypes.c_void_p(d_Im), int(nlev),
+                                                 ctypes.c_void_p(d_levels), int(nphi_out), ctypes.c_void_p(d_phi),
+                                                 ctypes.c_void_p(d_out)))
+
     # ---- multi-GPU gather over RCCL (one process per GPU) -------------------------
     @staticmethod
     def comm_unique_id() -> bytes:
