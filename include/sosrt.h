@@ -61,9 +61,10 @@ const char* sosrt_last_error(void);
  * runs several orders per launch (sosrt_set_order_loop) were added (sosrt_plan_launch may answer SOSRT_PLAN_GEMM_LIVE16_REGS since the
  * second half of that round).  102: the azimuth-resolved solve -- Fourier modes of the phase functions
  * (sosrt_phase_modes, sosrt_phase_p0_modes[_dev]), fixed order counts per column (sosrt_set_order_targets) and the
- * synthesis in azimuth (sosrt_azimuth_accumulate_dev); nothing that existed before changes.  A binding checks
+ * synthesis in azimuth (sosrt_azimuth_accumulate_dev); nothing that existed before changes.  103: the low-rank form of the
+ * plain rows (sosrt_phase_rank, SOSRT_CONTRACT_F64_DENSE); results move within SOSRT_LOWRANK_TOL.  A binding checks
  * sosrt_version() >= the SOSRT_VERSION it was written against. */
-#define SOSRT_VERSION 102
+#define SOSRT_VERSION 103
 int sosrt_version(void);
 
 /* ---- handle ------------------------------------------------------------------------------- */
@@ -126,11 +127,22 @@ int sosrt_set_first_order(sosrt_t* h, int mode);
  * max |W[k][m] - W[2N-1-k][2N-1-m]| / max |W| (sosrt_phase_asymmetry); at or below SOSRT_SYMMETRY_TOL (the rounding of
  * the phase-matrix builders: 1e-14 for the reference's) the symmetric form is used on the symmetric part of W, so Jn moves
  * by at most that fraction of max |W| sum |In_1| -- four orders of magnitude inside the 1e-10 parity bar; above it (any
- * matrix without the symmetry) the full product runs.  SOSRT_CONTRACT_F64_FULL forces the full product. */
+ * matrix without the symmetry) the full product runs.  SOSRT_CONTRACT_F64_FULL forces the full product.
+ *
+ * Within SOSRT_CONTRACT_F64 the plain rows (every row outside a column's aerosol slab: Jn = ca In_1 W_atm) also use a low rank of
+ * W_atm when it has one: sosrt_set_phase factors W_atm = U V (U: 2N x r, V: r x 2N, r <= 4) by cross approximation and accepts r
+ * when max |W_atm - U V| <= SOSRT_LOWRANK_TOL max |W_atm| -- the Rayleigh matrix has r = 2 (the azimuth average of 3/4 (1 +
+ * cos^2) is 3/8 (3 - mu^2 - mu'^2 + 3 mu^2 mu'^2)), iso r = 1, a zero matrix r = 0.  A plain row is then r dot products and an
+ * r-term expansion, Jn = ca (In_1 U) V, and moves by at most SOSRT_LOWRANK_TOL max |W_atm| sum |In_1| (the argument of the
+ * symmetric form).  The slab rows keep the MFMA product.  SOSRT_CONTRACT_F64_DENSE is SOSRT_CONTRACT_F64 without the low-rank
+ * form (the MFMA product, symmetric when the matrices allow it, on every row: for A/B runs and tests).  SOSRT_CONTRACT_F32 is
+ * always the dense product. */
 #define SOSRT_CONTRACT_F64 0
 #define SOSRT_CONTRACT_F32 1
 #define SOSRT_CONTRACT_F64_FULL 2
+#define SOSRT_CONTRACT_F64_DENSE 3
 #define SOSRT_SYMMETRY_TOL 1e-12
+#define SOSRT_LOWRANK_TOL 1e-12
 int sosrt_set_contraction(sosrt_t* h, int mode);
 
 /* The order loop of spec:309-458 runs an order as two launches (source function, transport) and the host learns the live count
@@ -148,6 +160,10 @@ int sosrt_set_order_loop(sosrt_t* h, int mode);
 int sosrt_order_loop_stats(sosrt_t* h, int* launches, int* refused, long long* column_orders /* nullable: (column, order) pairs run inside them; synchronises */);
 /* asymmetry of the folded matrices of the last sosrt_set_phase (see above); *uses_symmetry: what the next solve will do */
 int sosrt_phase_asymmetry(sosrt_t* h, double* asymmetry, int* uses_symmetry);
+/* low rank of the folded W_atm of the last sosrt_set_phase (see above): *rank = r, or -1 when no r <= 4 meets the bar (a NaN, or a
+ * matrix that is not low-rank); *residual = max |W_atm - U V| / max |W_atm| of the factors (or of the last step tried); *uses:
+ * whether the next solve computes its plain rows in the low-rank form */
+int sosrt_phase_rank(sosrt_t* h, int* rank, double* residual, int* uses);
 
 /* per-column scalars (the locals of spec:23-53).  Arrays have B entries.
  *   THREE_ZONE : idx_up, idx_down (spec:40), mu0, grd_alb, alb_atm, alb_aer, dtau_atm, dtau_aer

@@ -129,6 +129,10 @@ struct sosrt_handle {
     bool sym_ok = false;                 // asymmetry <= SOSRT_SYMMETRY_TOL
     bool sym_dirty = true, symmix_dirty = true;
     double *d_Wa_s = nullptr, *d_Wr_s = nullptr, *d_Wmix_s = nullptr;
+    // low-rank form of the plain rows (jn_gemm_tile.hpp, lowrank_rows): W_atm = U V by cross approximation in sosrt_set_phase
+    int lr_rank = -1;                    // terms of the accepted factorisation; -1: none within SOSRT_LOWRANK_TOL
+    double lr_residual = 0;              // max |W_atm - U V| / max |W_atm| after the last step taken
+    double *d_lrU = nullptr, *d_lrV = nullptr;   // [kLowRankMax][D] each: U transposed, V
     size_t mixs_capacity = 0;
     float *d_Wa32 = nullptr, *d_Wmix32 = nullptr;   // float copies of W_atm and of the combined slab matrices (SOSRT_CONTRACT_F32)
     size_t mix32_capacity = 0;
@@ -323,7 +327,64 @@ int ensure_w32(sosrt_handle* h) {
     return 0;
 }
 
-bool use_sym(const sosrt_handle* h) { return h->contraction == SOSRT_CONTRACT_F64 && h->sym_ok; }
+bool use_sym(const sosrt_handle* h) {
+    return (h->contraction == SOSRT_CONTRACT_F64 || h->contraction == SOSRT_CONTRACT_F64_DENSE) && h->sym_ok;
+}
+bool use_lowrank(const sosrt_handle* h) { return h->contraction == SOSRT_CONTRACT_F64 && h->lr_rank >= 0; }
+
+// Cross approximation of a folded matrix W [D][D] (row k, column m): up to kLowRankMax steps of Gaussian elimination with
+// complete pivoting, U[k][q] = R[k][j] / R[i][j], V[q][m] = R[i][m] for the largest |R[i][j]| of the Schur complement R, which
+// then loses that term.  The rank is the first step count whose complement is at most SOSRT_LOWRANK_TOL of max |W|, and the
+// certificate is then computed from the factors themselves: max |W - U V| <= SOSRT_LOWRANK_TOL max |W|.  A NaN anywhere, or no
+// such count, gives -1.  Ut [kLowRankMax][D] = U transposed, V [kLowRankMax][D], zero beyond the rank.
+int lowrank_factor(const std::vector<double>& W, int D, std::vector<double>& Ut, std::vector<double>& V, double* residual) {
+    Ut.assign((size_t)kLowRankMax * D, 0.0);
+    V.assign((size_t)kLowRankMax * D, 0.0);
+    auto absmax = [](const std::vector<double>& X, size_t* at) {
+        double amax = 0;
+        bool nan = false;
+        for (size_t e = 0; e < X.size(); ++e) {
+            const double ax = std::fabs(X[e]);
+            nan |= std::isnan(ax);
+            if (ax > amax) { amax = ax; if (at) *at = e; }
+        }
+        return nan ? std::nan("") : amax;
+    };
+    std::vector<double> R(W);
+    const double wmax = absmax(W, nullptr);
+    *residual = wmax;
+    if (!std::isfinite(wmax)) return -1;
+    int rank = -1;
+    for (int r = 0; r <= kLowRankMax; ++r) {
+        size_t at = 0;
+        const double amax = absmax(R, &at);
+        *residual = wmax > 0 ? amax / wmax : amax;
+        if (std::isnan(amax)) return -1;
+        if (amax <= SOSRT_LOWRANK_TOL * wmax) { rank = r; break; }
+        if (r == kLowRankMax) return -1;
+        const int i = (int)(at / D), j = (int)(at % D);
+        const long double piv = R[at];
+        for (int k = 0; k < D; ++k) Ut[(size_t)r * D + k] = (double)(R[(size_t)k * D + j] / piv);
+        for (int m = 0; m < D; ++m) V[(size_t)r * D + m] = R[(size_t)i * D + m];
+        for (int k = 0; k < D; ++k) {
+            const long double u = Ut[(size_t)r * D + k];
+            double* row = &R[(size_t)k * D];
+            const double* v = &V[(size_t)r * D];
+            for (int m = 0; m < D; ++m) row[m] = (double)(row[m] - u * v[m]);
+        }
+    }
+    // the certificate, from the factors the device will use
+    double res = 0;
+    for (int k = 0; k < D; ++k)
+        for (int m = 0; m < D; ++m) {
+            long double uv = 0;
+            for (int q = 0; q < rank; ++q) uv += (long double)Ut[(size_t)q * D + k] * V[(size_t)q * D + m];
+            const double d = std::fabs((double)(W[(size_t)k * D + m] - uv));
+            if (!(d <= res)) res = d;                   // (a NaN ends up here and refuses the factors below)
+        }
+    *residual = wmax > 0 ? res / wmax : res;
+    return (res <= SOSRT_LOWRANK_TOL * wmax) ? rank : -1;
+}
 
 // combined slab matrices and, for the symmetric contraction, the folded copies of every matrix (on stream s)
 int ensure_matrices(sosrt_handle* h, hipStream_t s) {
@@ -400,6 +461,7 @@ void run_source(sosrt_handle* h, const double* In_1, double* Jn, const int* acti
     if (h->mix_groups > 0) {
         ga.Wmix = h->d_Wmix; ga.mix_group = h->d_mixgroup; ga.slab_tile_group = h->d_slabtilegroup + h->slab_off[g0] / 32;
     }
+    if (use_lowrank(h)) { ga.lr_rank = h->lr_rank; ga.lrU = h->d_lrU; ga.lrV = h->d_lrV; }
     if (use_sym(h)) {
         ga.sym = 1; ga.Ks = (h->g.N + GEMM_KC - 1) / GEMM_KC * GEMM_KC;
 #ifdef SOSRT_DIAG
@@ -652,6 +714,8 @@ int sosrt_create(int device, int L, int N, int max_batch, int max_orders, sosrt_
             if ((e = dalloc(&h->d_mu, g.D))) return e;
             if ((e = dalloc(&h->d_Wa, (size_t)g.Dp * g.Wld))) return e;
             if ((e = dalloc(&h->d_Wr, (size_t)g.Dp * g.Wld))) return e;
+            if ((e = dalloc(&h->d_lrU, (size_t)kLowRankMax * g.D))) return e;
+            if ((e = dalloc(&h->d_lrV, (size_t)kLowRankMax * g.D))) return e;
             if ((e = dalloc(&h->d_wfdn, N))) return e;
             if ((e = dalloc(&h->d_wfup, N))) return e;
             if ((e = dalloc(&h->d_w, g.D))) return e;
@@ -731,7 +795,7 @@ int sosrt_destroy(sosrt_t* h) {
                         h->d_idx_down, h->d_scal, h->d_desc, h->d_rca, h->d_rcr, h->d_slabrows, h->d_mainrows, h->d_tau, h->d_P0a,
                         h->d_P0r, h->d_Jn, h->d_InA, h->d_InB, h->d_I, h->d_E, h->d_active, h->d_norders, h->d_status,
                         h->d_nactive_sets, h->d_ratio, h->d_redo, h->d_erep, h->d_tauhash, h->d_Wmix, h->d_mixca, h->d_mixcr,
-                        h->d_mixgroup, h->d_Wa_s, h->d_Wr_s, h->d_Wmix_s, h->d_scan_scratch, h->d_scan_sync, h->d_w, h->d_phi, h->d_z, h->d_tab, h->d_slabtilegroup, h->d_livelist, h->d_Wa32, h->d_Wmix32, h->d_nz, h->d_zr0, h->d_zmix, h->d_zwr, h->d_zdtr, h->d_olsync, h->d_ollog, h->d_modetab};
+                        h->d_mixgroup, h->d_Wa_s, h->d_Wr_s, h->d_Wmix_s, h->d_scan_scratch, h->d_scan_sync, h->d_w, h->d_phi, h->d_z, h->d_tab, h->d_slabtilegroup, h->d_livelist, h->d_Wa32, h->d_Wmix32, h->d_nz, h->d_zr0, h->d_zmix, h->d_zwr, h->d_zdtr, h->d_olsync, h->d_ollog, h->d_modetab, h->d_lrU, h->d_lrV};
         for (void* p : ptrs)
             if (p) hipFree(p);
         if (h->h_pub) hipHostFree(h->h_pub);
@@ -786,7 +850,7 @@ int sosrt_set_first_order(sosrt_t* h, int mode) {
 
 int sosrt_set_contraction(sosrt_t* h, int mode) {
     if (int e = need_gpu(h)) return e;
-    if (mode != SOSRT_CONTRACT_F64 && mode != SOSRT_CONTRACT_F32 && mode != SOSRT_CONTRACT_F64_FULL) return fail(SOSRT_E_INVALID, "unknown contraction mode %d", mode);
+    if (mode != SOSRT_CONTRACT_F64 && mode != SOSRT_CONTRACT_F32 && mode != SOSRT_CONTRACT_F64_FULL && mode != SOSRT_CONTRACT_F64_DENSE) return fail(SOSRT_E_INVALID, "unknown contraction mode %d", mode);
     if (mode == SOSRT_CONTRACT_F32) {
         HIPCHK(hipSetDevice(h->device));
         const size_t per = (size_t)h->g.Dp * h->g.Wld;
@@ -858,6 +922,15 @@ int sosrt_phase_asymmetry(sosrt_t* h, double* asymmetry, int* uses_symmetry) {
     if (!h->have_phase) return fail(SOSRT_E_STATE, "sosrt_set_phase has not been called");
     if (asymmetry) *asymmetry = h->asymmetry;
     if (uses_symmetry) *uses_symmetry = use_sym(h) ? 1 : 0;
+    return 0;
+}
+
+int sosrt_phase_rank(sosrt_t* h, int* rank, double* residual, int* uses) {
+    if (!h) return fail(SOSRT_E_INVALID, "null handle");
+    if (!h->have_phase) return fail(SOSRT_E_STATE, "sosrt_set_phase has not been called");
+    if (rank) *rank = h->lr_rank;
+    if (residual) *residual = h->lr_residual;
+    if (uses) *uses = use_lowrank(h) ? 1 : 0;
     return 0;
 }
 
@@ -952,11 +1025,16 @@ int sosrt_set_phase(sosrt_t* h, const double* P_atm, const double* P_aer) {
         // (a compile-time constant: nothing in the environment can put the symmetric form on a matrix without the symmetry)
         h->sym_ok = h->asymmetry <= SOSRT_SYMMETRY_TOL;
     }
+    // low rank of W_atm (see sosrt.h, sosrt_phase_rank): from the matrix alone, never from the batch
+    std::vector<double> lrU, lrV;
+    h->lr_rank = lowrank_factor(h->Wa_h, h->D, lrU, lrV, &h->lr_residual);
     if (h->gpu) {
         HIPCHK(hipSetDevice(h->device));
         const Grid& g = h->g;
         HIPCHK(hipMemcpy2D(h->d_Wa, g.Wld * sizeof(double), h->Wa_h.data(), g.D * sizeof(double), g.D * sizeof(double),
                            g.D, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_lrU, lrU.data(), lrU.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_lrV, lrV.data(), lrV.size() * sizeof(double), hipMemcpyHostToDevice));
         if (P_aer)
             HIPCHK(hipMemcpy2D(h->d_Wr, g.Wld * sizeof(double), h->Wr_h.data(), g.D * sizeof(double),
                                g.D * sizeof(double), g.D, hipMemcpyHostToDevice));
@@ -1522,6 +1600,7 @@ int sosrt_solve_dev(sosrt_t* h, int B, const double* d_tau, const double* d_P0_a
                 ga.A = nullptr; ga.Wa = h->d_Wa_s; ga.Wr = h->d_Wr_s; ga.ca = h->d_rca; ga.cr = h->d_rcr;
                 ga.D = g.D; ga.Dp = g.Dp; ga.Wld = g.Wld; ga.L = h->L; ga.C = h->d_Jn;
                 ga.sym = 1; ga.Ks = (g.N + GEMM_KC - 1) / GEMM_KC * GEMM_KC;
+                if (use_lowrank(h)) { ga.lr_rank = h->lr_rank; ga.lrU = h->d_lrU; ga.lrV = h->d_lrV; }
                 ga.max_main = h->max_main; ga.max_slab = h->max_slab;
                 ga.idx_up = h->nslab > 0 ? h->d_idx_up : nullptr; ga.idx_down = h->nslab > 0 ? h->d_idx_down : nullptr;
                 if (h->mix_groups > 0) { ga.Wmix = h->d_Wmix_s; ga.mix_group = h->d_mixgroup; }

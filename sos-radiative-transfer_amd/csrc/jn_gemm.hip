@@ -27,6 +27,12 @@
 // product, and -- when the folded matrices are flip-symmetric, as every phase function of the scattering
 // angle makes them -- two N x N products on the sum and the difference of a row's two halves (SYM below):
 // half the flops.
+//
+// The plain rows need no product at all when W_atm has a low rank (SOSRT_CONTRACT_F64, g.lr_rank >= 0: Rayleigh
+// r = 2, iso r = 1; sosrt_set_phase certifies max |W_atm - U V| <= 1e-12 max |W_atm|): Jn = ca (In_1 U) V, r dot
+// products and an r-term expansion per row, 16 D bytes of HBM and no MFMA (jn_gemm_tile.hpp: lowrank_rows).  The
+// launches keep their grids and their duties; a workgroup that would have held a tile of plain rows streams its
+// share of that tile's rows instead, and the slab tiles -- now the long ones -- are numbered first.
 #include "jn_gemm_tile.hpp"
 
 namespace sosrt {
@@ -87,11 +93,21 @@ __global__ __launch_bounds__(256, GEMM_WPS) void k_jn_gemm(GemmArgs g) {
     // tile read the same rows of In_1: numbering them 8 apart puts them on one XCD, a few dispatches apart,
     // so that In_1 comes from HBM once instead of once per column tile.
     const int tiles_main = (g.n_main + 16 * GEMM_RT - 1) / (16 * GEMM_RT);
-    const int tiles = tiles_main + (g.n_slab + DENSE_SLAB_ROWS - 1) / DENSE_SLAB_ROWS;
+    const int tiles_slab = (g.n_slab + DENSE_SLAB_ROWS - 1) / DENSE_SLAB_ROWS;
+    const int tiles = tiles_main + tiles_slab;
     const int nct = (g.D + GEMM_BN - 1) / GEMM_BN;
     const int id = blockIdx.x;
-    const int tile = (id / (8 * nct)) * 8 + (id & 7), bn0 = ((id >> 3) % nct) * GEMM_BN;
+    int tile = (id / (8 * nct)) * 8 + (id & 7);
+    const int bn0 = ((id >> 3) % nct) * GEMM_BN;
     if (tile >= tiles) return;
+    if (g.lr_rank >= 0) {
+        // low-rank plain rows: a stream, the short tiles -- the slab tiles go first (renumbered to the end of the MFMA form's order)
+        if (tile >= tiles_slab) {
+            lowrank_tile<false>(g, ListRows{g.rows_main, g.n_main}, tile - tiles_slab, 16 * GEMM_RT, bn0, true);
+            return;
+        }
+        tile += tiles_main;
+    }
     if (tile < tiles_main) {
         gemm_tile<GEMM_RT, false, false, SYM>(g, sA, sB, &s_any, tile, bn0, ListRows{g.rows_main, g.n_main}, true);
     } else if (g.Wmix && g.slab_tile_group) {
@@ -132,7 +148,8 @@ __device__ __forceinline__ void gemm_live_columns(const GemmArgs& g, double* sA,
     const int cap = g.live_cap > 0 ? g.live_cap : 1;
     const int tq = xq / cap, ci = xq % cap;
     if (tq >= ts + tm) return;                           // (uniform) padding of the grid
-    const int tt = tq < tm ? ts + tq : tq - tm;          // tt < ts: slab tile tt; else plain tile tt - ts
+    // (low-rank plain rows: they are the short tiles, the slab tiles go first)
+    const int tt = g.lr_rank >= 0 ? tq : (tq < tm ? ts + tq : tq - tm);   // tt < ts: slab tile tt; else plain tile tt - ts
 #else
     const int ci = xq / (ts + tm), tt = xq % (ts + tm);
 #endif
@@ -171,7 +188,8 @@ __device__ __forceinline__ void gemm_live_columns(const GemmArgs& g, double* sA,
     } else {
         const int t2 = tt - ts;
         if (t2 * 16 * RT >= g.L - ns) return;
-        gemm_tile<RT, false, DEEP, SYM>(g, sA, sB, nullptr, t2, bn0, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, false);
+        if (g.lr_rank >= 0) lowrank_tile<false>(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, t2, 16 * RT, bn0, false);
+        else gemm_tile<RT, false, DEEP, SYM>(g, sA, sB, nullptr, t2, bn0, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, false);
     }
 }
 
@@ -228,7 +246,8 @@ __global__ __launch_bounds__(256, 1) void k_jn_gemm_lone(GemmArgs g) {
     const int cap = g.live_cap > 0 ? g.live_cap : 1;
     const int tq = xq / cap, ci = xq % cap;
     if (tq >= ts + tm) return;                           // (uniform) padding of the grid
-    const int tt = tq < tm ? ts + tq : tq - tm;          // tt < ts: slab tile tt; else plain tile tt - ts (the short slab tiles last)
+    // tt < ts: slab tile tt; else plain tile tt - ts (the short slab tiles last -- low-rank plain rows: those are the short ones)
+    const int tt = g.lr_rank >= 0 ? tq : (tq < tm ? ts + tq : tq - tm);
     // The ci-th live column of the launch and, in the same round trip, what the tile needs to know of it: every thread looks at
     // one candidate column's flag and descriptors.  The requests of the first 256 candidates leave before anything else ...
     int fl = 0, iu_c = 0, id_c = -1, mg_c = 0;
@@ -243,7 +262,7 @@ __global__ __launch_bounds__(256, 1) void k_jn_gemm_lone(GemmArgs g) {
     // ... and behind them, for a plain tile, the first two register blocks of its matrix: W_atm whatever the column
     LoneFrag f0, f1;
     const int nkb = (g.Ks >> 2) / LONE_KB;
-    if (tt >= ts) {
+    if (tt >= ts && g.lr_rank < 0) {
         const int mcol = (bn0 >> 1) + (__builtin_amdgcn_readfirstlane(tid) >> 6) * 16 + (lane & 15);
         const __amdgpu_buffer_rsrc_t rW = make_rsrc(g.Wa, g.Dp * g.Wld * 8);
         lone_load(f0, rW, 0, lane >> 4, g.Wld, g.Wld >> 1, mcol);
@@ -288,7 +307,8 @@ __global__ __launch_bounds__(256, 1) void k_jn_gemm_lone(GemmArgs g) {
         else gemm_tile_lone<true, false>(g, s_lone, tt, bn0, ColumnRows{b * g.L, iu, ns, ns, true}, f0, f1);
     } else {
         if ((tt - ts) * 16 >= g.L - ns) return;
-        gemm_tile_lone<false, true>(g, s_lone, tt - ts, bn0, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, f0, f1);
+        if (g.lr_rank >= 0) lowrank_tile<false>(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, tt - ts, 16, bn0, false);
+        else gemm_tile_lone<false, true>(g, s_lone, tt - ts, bn0, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, f0, f1);
     }
 }
 

@@ -419,6 +419,108 @@ __device__ __forceinline__ void gemm_tile_lone(const GemmArgs& g, double* sRaw, 
     }
 }
 
+// The plain rows in the LOW-RANK form (g.lr_rank >= 0: sosrt_set_phase found W_atm = U V with r <= kLowRankMax terms to within
+// SOSRT_LOWRANK_TOL, e.g. r = 2 for Rayleigh, 1 for iso, 0 for a zero matrix):
+//     Jn[m] = ca (sum_q M_q V[q][m]),   M_q = sum_k In_1[k] U[k][q]
+// -- r dot products of length D and an r-term expansion instead of a D x D product: a stream, 16 D bytes a row.  One wave, one
+// row (LR_ROWS rows at a time, to keep that many rows' bytes in flight and share the loads of U and V).  A lane sums the elements
+// k = 2 lane + 128 j in order of j (one fma chain per moment), a fixed xor butterfly over the 64 lanes gives every lane the same
+// sum, and lane l writes m = 2 l + 128 j, 16 bytes a lane.  Every tiling, the order loop's included, computes its plain rows here,
+// so a row's bits do not depend on the tiling, the batch or the launch.  rows[i] < 0: no row.  COH: the order loop's loads past
+// the L1 and write-through stores (gemm_tile, COH).
+constexpr int LR_ROWS = 4;
+template <bool COH>
+__device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows)[LR_ROWS], int lane) {
+    const int D = g.D, R = g.lr_rank;
+    // (a missing row: a buffer of no bytes -- its loads return zeros, its stores are dropped)
+    __amdgpu_buffer_rsrc_t rA[LR_ROWS], rC[LR_ROWS];
+    double cf[LR_ROWS];
+#pragma unroll
+    for (int i = 0; i < LR_ROWS; ++i) {
+        const int r = rows[i] >= 0 ? rows[i] : rows[0];
+        const int bytes = rows[i] >= 0 ? D * 8 : 0;
+        rA[i] = make_rsrc(g.A + (size_t)r * D, bytes);
+        rC[i] = make_rsrc(g.C + (size_t)r * D, bytes);
+        cf[i] = rows[i] >= 0 ? g.ca[rows[i]] : 0.0;
+    }
+    const double* __restrict__ U = g.lrU;
+    const double* __restrict__ V = g.lrV;
+    double m[LR_ROWS][kLowRankMax];
+#pragma unroll
+    for (int i = 0; i < LR_ROWS; ++i)
+#pragma unroll
+        for (int q = 0; q < kLowRankMax; ++q) m[i][q] = 0.0;
+#pragma unroll 2
+    for (int k = 2 * lane; k < D; k += 128) {
+        double2 x[LR_ROWS];
+#pragma unroll
+        for (int i = 0; i < LR_ROWS; ++i) x[i] = bload2_aux<COH ? 16 : 0>(rA[i], k * 8, 0);
+#pragma unroll
+        for (int q = 0; q < kLowRankMax; ++q) {
+            if (q < R) {
+                const double2 u = *reinterpret_cast<const double2*>(U + (size_t)q * D + k);
+#pragma unroll
+                for (int i = 0; i < LR_ROWS; ++i) m[i][q] = __builtin_fma(x[i].y, u.y, __builtin_fma(x[i].x, u.x, m[i][q]));
+            }
+        }
+    }
+    // (lane l and lane l ^ s add the same two numbers: every lane ends with the same bits)
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1)
+#pragma unroll
+        for (int q = 0; q < kLowRankMax; ++q)
+            if (q < R) {
+#pragma unroll
+                for (int i = 0; i < LR_ROWS; ++i) m[i][q] += __shfl_xor(m[i][q], s);
+            }
+#pragma unroll 2
+    for (int k = 2 * lane; k < D; k += 128) {
+        double2 o[LR_ROWS];
+#pragma unroll
+        for (int i = 0; i < LR_ROWS; ++i) o[i] = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int q = 0; q < kLowRankMax; ++q) {
+            if (q < R) {
+                const double2 v = *reinterpret_cast<const double2*>(V + (size_t)q * D + k);
+#pragma unroll
+                for (int i = 0; i < LR_ROWS; ++i) {
+                    o[i].x = __builtin_fma(m[i][q], v.x, o[i].x);
+                    o[i].y = __builtin_fma(m[i][q], v.y, o[i].y);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < LR_ROWS; ++i) bstore2_aux<COH ? 17 : 0>(rC[i], k * 8, 0, make_double2(cf[i] * o[i].x, cf[i] * o[i].y));
+    }
+}
+// A tile's plain rows in the low-rank form, where the MFMA tilings would have put a tile of BM rows x GEMM_BN columns of Jn: the
+// workgroup of column tile ct (of nct) takes the rows lr = ct + nct j of the tile, its waves LR_ROWS rows at a time.
+// check_active: rows of converged columns are skipped (the dense tiling's check of its tiles).
+template <bool COH, class RowOf>
+__device__ __forceinline__ void lowrank_tile(const GemmArgs& g, RowOf row_of, int tile, int BM, int bn0, bool check_active) {
+    const int nct = (g.D + GEMM_BN - 1) / GEMM_BN, ct = bn0 / GEMM_BN;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x) >> 6;
+    const int per = (BM - ct + nct - 1) / nct;           // rows of this workgroup
+    const bool chk = check_active && g.active && g.check_tiles;
+    for (int j = LR_ROWS * wave; j < per; j += 4 * LR_ROWS) {
+        int rows[LR_ROWS];
+        int n = 0;
+#pragma unroll
+        for (int i = 0; i < LR_ROWS; ++i) {
+            int r = j + i < per ? __builtin_amdgcn_readfirstlane(row_of(tile * BM + ct + nct * (j + i))) : -1;
+            if (chk && r >= 0 && !g.active[r / g.L]) r = -1;
+            rows[i] = r;
+            n += r >= 0 ? 1 : 0;
+        }
+        if (n == 0) continue;
+        if (rows[0] < 0)                                 // (row 0 names the buffers of the missing rows)
+#pragma unroll
+            for (int i = 1; i < LR_ROWS; ++i)
+                if (rows[i] >= 0) { rows[0] = rows[i]; rows[i] = -1; break; }
+        lowrank_rows<COH>(g, rows, lane);
+    }
+}
+
 constexpr int TAIL_RT_SLAB = 1;     // MFMA row tiles of the live-column tilings: slab rows (16-row tiles)
 constexpr int TAIL_RT = 2;          // ... plain rows of the small tiling (32-row tiles)
 

@@ -211,7 +211,13 @@ struct GemmArgs {
     int sym = 0;
     int Ks = 0;                      // N rounded up to the k-chunk
     int check_tiles = 1;             // dense kernel: skip the tiles whose columns have all converged (two barriers and a dependent load per tile)
+    // low-rank form of the plain rows (jn_gemm_tile.hpp, lowrank_rows): W_atm = U V with lr_rank <= kLowRankMax terms; -1: the
+    // plain rows are tiles of the MFMA product like the slab rows
+    int lr_rank = -1;
+    const double* lrU = nullptr;     // [kLowRankMax][D]: lrU[q][k] = U[k][q]
+    const double* lrV = nullptr;     // [kLowRankMax][D]: lrV[q][m] = V[q][m]
 };
+constexpr int kLowRankMax = 4;
 
 // (publish_live_now: by the calling thread, whichever workgroup it belongs to)
 __device__ inline void publish_live_now(const GemmArgs& g) {

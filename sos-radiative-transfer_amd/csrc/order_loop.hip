@@ -207,7 +207,8 @@ __global__ __launch_bounds__(768) void k_order_loop(OrderLoopArgs p) {
                         else gemm_tile<TAIL_RT_SLAB, true, kOlDeep, true, ColumnRows, true>(gk, sA, sB, nullptr, tt, bn0, cr, false);
                     } else {
                         const ColumnRows cr{bg * L, iu, ns, L - ns, false};
-                        if (astage) gemm_tile<TAIL_RT, false, true, true, ColumnRows, true, true>(gk, sA, sB, nullptr, tt - ts, bn0, cr, false, nullptr, sRaw);
+                        if (gk.lr_rank >= 0) lowrank_tile<true>(gk, cr, tt - ts, 16 * TAIL_RT, bn0, false);
+                        else if (astage) gemm_tile<TAIL_RT, false, true, true, ColumnRows, true, true>(gk, sA, sB, nullptr, tt - ts, bn0, cr, false, nullptr, sRaw);
                         else gemm_tile<TAIL_RT, false, kOlDeep, true, ColumnRows, true>(gk, sA, sB, nullptr, tt - ts, bn0, cr, false);
                     }
                     // the tile's rows (write-through) acknowledged by every wave, then one lane counts it

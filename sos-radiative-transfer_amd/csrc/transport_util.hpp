@@ -72,6 +72,13 @@ __device__ __forceinline__ void bstore2(__amdgpu_buffer_rsrc_t r, int voff, int 
     v.z = (unsigned)__double2loint(x.y); v.w = (unsigned)__double2hiint(x.y);
     __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 0);
 }
+template <int AUX>
+__device__ __forceinline__ void bstore2_aux(__amdgpu_buffer_rsrc_t r, int voff, int soff, double2 x) {
+    u32x4 v;
+    v.x = (unsigned)__double2loint(x.x); v.y = (unsigned)__double2hiint(x.x);
+    v.z = (unsigned)__double2loint(x.y); v.w = (unsigned)__double2hiint(x.y);
+    __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, AUX);
+}
 
 // value of lane + 1 (wave_shl:1); lane 63 keeps its own
 __device__ __forceinline__ double lane_up1(double v) {

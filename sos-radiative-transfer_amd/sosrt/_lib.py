@@ -17,7 +17,7 @@ SURFACE_NONE, SURFACE_SPECULAR, SURFACE_LAMBERTIAN, SURFACE_LAMBERTIAN_README = 
 K_GEMM, K_TRANSPORT, K_FIRST, K_SMALLMU, K_ORDER_LOOP = 0, 1, 2, 3, 4
 PLAN_GEMM_DENSE, PLAN_GEMM_LIVE64, PLAN_GEMM_LIVE32, PLAN_GEMM_LIVE32_DEEP, PLAN_GEMM_LIVE16_REGS = 0, 1, 2, 3, 4
 PLAN_TRANSPORT_GENERAL, PLAN_TRANSPORT_FAST, PLAN_TRANSPORT_RING, PLAN_TRANSPORT_SCAN = 0, 1, 3, 4
-CONTRACT_F64, CONTRACT_F32, CONTRACT_F64_FULL = 0, 1, 2
+CONTRACT_F64, CONTRACT_F32, CONTRACT_F64_FULL, CONTRACT_F64_DENSE = 0, 1, 2, 3
 FIRST_ORDER_CODED, FIRST_ORDER_README = 0, 1
 PHASE_ISO, PHASE_RAYLEIGH, PHASE_HG, PHASE_TABLE = 0, 1, 2, 3
 MAX_MODES = 64
@@ -38,6 +38,7 @@ SIGNATURES = {
     "sosrt_set_order_budget": (c_int, [c_void_p, c_int]),
     "sosrt_set_contraction": (c_int, [c_void_p, c_int]),
     "sosrt_phase_asymmetry": (c_int, [c_void_p, POINTER(c_double), _ip]),
+    "sosrt_phase_rank": (c_int, [c_void_p, _ip, POINTER(c_double), _ip]),
     "sosrt_set_order_loop": (c_int, [c_void_p, c_int]),
     "sosrt_order_loop_stats": (c_int, [c_void_p, _ip, _ip, POINTER(c_longlong)]),
     "sosrt_plan_launch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, _ip]),

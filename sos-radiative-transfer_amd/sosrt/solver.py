@@ -82,12 +82,14 @@ class Solver:
         check(lib().sosrt_synchronize(self._h))
 
     def set_contraction(self, mode="f64"):
-        """'f64' (default, the parity path: fp64 MFMA, using the flip symmetry of the folded matrices when they have it) |
-        'f64_full' (fp64 MFMA, always the full 2N x 2N product) | 'f32' (float operands and accumulator in the Jn
-        contraction: opt-in, about 3e-7 away from the fp64 result; BASELINE configs[4])."""
-        m = {"f64": _lib.CONTRACT_F64, "f32": _lib.CONTRACT_F32, "f64_full": _lib.CONTRACT_F64_FULL}.get(mode)
+        """'f64' (default, the parity path: fp64; the plain rows in the low-rank form of W_atm when it has one, the MFMA product
+        elsewhere, using the flip symmetry of the folded matrices when they have it) | 'f64_dense' ('f64' without the low-rank
+        form: the MFMA product on every row) | 'f64_full' (fp64 MFMA, always the full 2N x 2N product) | 'f32' (float operands
+        and accumulator in the dense Jn contraction: opt-in, about 3e-7 away from the fp64 result; BASELINE configs[4])."""
+        m = {"f64": _lib.CONTRACT_F64, "f32": _lib.CONTRACT_F32, "f64_full": _lib.CONTRACT_F64_FULL,
+             "f64_dense": _lib.CONTRACT_F64_DENSE}.get(mode)
         if m is None:
-            raise ValueError("contraction must be 'f64', 'f64_full' or 'f32'")
+            raise ValueError("contraction must be 'f64', 'f64_dense', 'f64_full' or 'f32'")
         check(lib().sosrt_set_contraction(self._h, m))
 
     def set_order_budget(self, max_orders: int):
@@ -113,6 +115,13 @@ class Solver:
         a, u = ctypes.c_double(), ctypes.c_int()
         check(lib().sosrt_phase_asymmetry(self._h, ctypes.byref(a), ctypes.byref(u)))
         return a.value, bool(u.value)
+
+    def phase_rank(self):
+        """(rank r of the low-rank form of the folded W_atm, or -1; max |W_atm - U V| / max |W_atm|; whether the next solve
+        computes its plain rows in that form)"""
+        r, a, u = ctypes.c_int(), ctypes.c_double(), ctypes.c_int()
+        check(lib().sosrt_phase_rank(self._h, ctypes.byref(r), ctypes.byref(a), ctypes.byref(u)))
+        return r.value, a.value, bool(u.value)
 
     def set_first_order(self, mode="coded"):
         """'coded' (default): spec:104-292, what both mains of the reference compute (specularly reflected beam).

@@ -17,7 +17,8 @@ print("solve %d of %d: %d kernels, %.1f us from first start to last end" % (whic
 order, prev_end = 1, None
 print("%5s %-28s %9s %9s %9s %8s" % ("order", "kernel", "start_us", "dur_us", "gap_us", "grid"))
 for r in sv:
-    name = r["Kernel_Name"].split("(")[0].split("<")[0].replace("void ", "").replace("sosrt::", "").replace("(anonymous namespace)::", "")
+    # (the namespace goes first: "(anonymous namespace)::" would otherwise end the name at its "(")
+    name = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].split("<")[0].replace("void ", "").replace("sosrt::", "")
     st, en = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
     if "k_jn_gemm" in name: order += 1
     gap = (st - prev_end) / 1e3 if prev_end else 0.0
