@@ -21,15 +21,20 @@ the N rank processes are started from here through torch.distributed.run, before
       torch.distributed point-to-point (ncclSend / ncclRecv under RCCL), `--gather abi`: the library's own sosrt_gather.
 No collective runs inside the order loop.
 
-Prints ONE JSON line on rank 0 (see the contract in the task description).  Beside the headline (N = 1 only, outside its
-timed region, `--no-extras` skips them): `extras.c2` / `extras.c3` = one EVA column at N_mu = 128 / 256 (BASELINE
-configs[1], [2]: single-column latency), `extras.c5` = the 4096-column wildfire sweep at L = 400, N = 256 (configs[4]),
+Prints ONE JSON line on rank 0: `metric`, `value` (columns/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...
+A plain run does only what the headline needs: it sets up, warms up, times the steps, dumps (`--dump-outputs`) and prints
+the line, with the per-kernel roofline read off the timed steps themselves.  Everything else runs only under `--full`, after
+the timed region: the check against the oracle (`check`), `two_groups`, `pipelined`, the extras, `cpu_baseline` and, with
+several GPUs, `strong`.
+
+With `--full`, beside the headline (N = 1 only, outside its timed region, `--no-extras` skips them): `extras.c2` /
+`extras.c3` = one EVA column at N_mu = 128 / 256 (BASELINE configs[1], [2]: single-column latency), `extras.c5` = the 4096-column wildfire sweep at L = 400, N = 256 (configs[4]),
 each with its own check against the oracle; `extras.c4_shard` = the 64 columns rank 0 gets when the C4 sweep is dealt to 8 GPUs
 (BASELINE configs[3]: what bounds the 8-GPU strong-scaling number, measurable on one GPU); `extras.c4_hg` = the headline sweep
-with the HG(0.7) stand-in of rounds 1-2 (continuity).  With several GPUs the line also carries `strong`: the ONE-sweep-over-the-node
+with the HG(0.7) stand-in of rounds 1-2 (continuity).  With several GPUs and `--full` the line also carries `strong`: the ONE-sweep-over-the-node
 measurement of configs[3] (fields gathered through the C ABI under RCCL) beside the weak-scaling headline.  `--groups 1` (default) runs the headline's order loop as one column group on one
 stream, so that every kernel is timed alone on the GPU (the roofline objects are per kernel); the library by itself takes two
-groups on two streams for a batch of more than 256 columns, which is faster: `two_groups` holds that measurement (same sweep, same bits).
+groups on two streams for a batch of more than 256 columns, which is faster: `two_groups` (`--full`) holds that measurement (same sweep, same bits).
 `--dump-outputs DIR`: after the timed steps, what the caller received from the last one (TOA / surface rows, order counts, status,
 the field; with several ranks what rank 0 gathered) goes to DIR/*.npy in float64, 64 MB at most: fixed seeded samples of the columns
 where the whole would not fit (dump_selection).  The inputs follow from the arguments alone, so two builds compare output for output.
@@ -455,17 +460,21 @@ def main():
                          "library's own choice (two groups on two streams for a batch of this size: contraction and transport of "
                          "the halves side by side, faster, per-launch durations no longer those of a kernel alone) -- measured "
                          "beside the headline as `two_groups`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C2 / C3 / C5 figures beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run what the headline does not need: the check against the oracle, "
+                         "two_groups, pipelined, the extras, the CPU baseline and, with several GPUs, the strong-scaling "
+                         "measurement (the four options below select among them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip two_groups and the C2 / C3 / C5 figures beside the headline")
     ap.add_argument("--pipelined", type=int, default=3,
-                    help="after the timed region, also measure the throughput with this many steps in flight on "
+                    help="with --full: after the timed region, also measure the throughput with this many steps in flight on "
                          "separate streams (0: skip); reported beside the headline value, never instead of it")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--gather", choices=("digest", "field", "abi"), default=None,
                     help="what rank 0 receives per step: TOA/surface rows + order counts (digest), or the whole fields through "
                          "torch.distributed point-to-point (field) or through the C ABI's sosrt_gather (abi) "
                          "(default: digest for weak scaling, field for strong)")
-    ap.add_argument("--check-columns", type=int, default=3, help="columns compared with the oracle after the timed region")
+    ap.add_argument("--check-columns", type=int, default=3, help="with --full: columns compared with the oracle after the timed region")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the caller received from the last timed step as DIR/<name>.npy, "
                          "64 MB at most (see dump_outputs)")
@@ -657,14 +666,14 @@ def main():
             gn = gn.reshape(-1)
             dumped = dump_outputs(a.dump_outputs, L, N, gI[:, 0, N:], gI[:, L - 1, :N], gn, field=gI)
 
-    # Outside the timed region: sampled columns of the field the last timed step left on the device against the oracle.
-    # Rank 0, its own columns.
+    # Outside the timed region, with --full: sampled columns of the field the last timed step left on the device against the
+    # oracle.  Rank 0, its own columns.
     check = None
     O = None
-    if rank == 0:
+    if rank == 0 and a.full:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import sos_oracle as O
-    if rank == 0 and a.check_columns > 0:
+    if rank == 0 and a.full and a.check_columns > 0:
         last = lanes[(a.steps - 1) % len(lanes)]
         cols = sorted(set(np.linspace(0, B - 1, min(B, a.check_columns)).astype(int).tolist()))
         check = dict(last.check(O, cols), columns=[int(mine[b]) for b in cols])
@@ -681,12 +690,12 @@ def main():
             check["gather_places_columns"] = bool(torch.equal(gI[sel], mineI))
             check["ok"] = bool(check["ok"] and check["gather_places_columns"])
 
-    # Beside the headline too: the same sweep with the order loop the library chooses by itself for a batch of this size -- two
+    # Beside the headline too (--full): the same sweep with the order loop the library chooses by itself for a batch of this size -- two
     # column groups on two streams -- one step at a time; the field must have the headline's bits.
     two = None
     # (measured before the `pipelined` lanes exist: HIP maps streams onto a few hardware queues, and with eight streams alive the
     # two streams of this handle can land on one queue and serialise)
-    if world == 1 and a.groups == "1" and not a.no_extras:
+    if a.full and world == 1 and a.groups == "1" and not a.no_extras:
         os.environ.pop("SOSRT_GROUPS", None)
         l2 = Lane(w, dev, local_rank, a.max_orders, lanes[0].shared())
         os.environ["SOSRT_GROUPS"] = a.groups
@@ -706,11 +715,11 @@ def main():
         finally:
             l2.close()
 
-    # Beside the headline (one step at a time, one stream: every kernel timing above is of a launch that
+    # Beside the headline, with --full (one step at a time, one stream: every kernel timing above is of a launch that
     # has the GPU to itself): the same steps with `--pipelined` of them in flight on separate streams and
     # handles.  The tail of one sweep's order loop then overlaps the dense launches of the next.
     pipe = None
-    if a.pipelined > 1 and len(lanes) == 1 and world == 1:
+    if a.full and a.pipelined > 1 and len(lanes) == 1 and world == 1:
         while len(lanes) < a.pipelined:
             lanes.append(Lane(w, dev, local_rank, a.max_orders, lanes[0].shared()))
             execs.append(ThreadPoolExecutor(max_workers=1))
@@ -724,7 +733,7 @@ def main():
         pipe = {"steps_in_flight": a.pipelined, "steps": psteps, "value": B * psteps / dtp, "unit": "columns/s",
                 "ms_per_step": dtp / psteps * 1e3}
 
-    # Several GPUs, weak-scaling headline: the same command also measures BASELINE configs[3] -- ONE sweep over the node, dealt to
+    # Several GPUs, weak-scaling headline, --full: the same command also measures BASELINE configs[3] -- ONE sweep over the node, dealt to
     # the ranks by expected work (sosrt.dist.GatherPlan), the whole fields gathered to rank 0 once per step (through the C ABI's
     # sosrt_gather under RCCL; torch.distributed point-to-point in the gloo rehearsal) -- so that one driver run yields both curves.
     # (measured AFTER every collective of the weak-scaling headline below, under a watchdog: the headline must not depend on it)
@@ -858,7 +867,7 @@ def main():
             out["pipelined"] = pipe
         if two:
             out["two_groups"] = two
-        if world == 1 and not a.no_extras:
+        if a.full and world == 1 and not a.no_extras:
             # the other single-GPU configurations of BASELINE.json, outside the headline's timed region
             for ln in lanes:
                 ln.close()
@@ -892,14 +901,14 @@ def main():
             except Exception as e:                      # an extra must not take the headline line with it
                 ex["error"] = "%s: %s" % (type(e).__name__, e)
             out["extras"] = ex
-        if world == 1:
+        if a.full and world == 1:
             out["strong"] = {"status": "unmeasured: one GPU.  With --gpus N this object holds the one-sweep-over-the-node measurement of "
                                        "BASELINE configs[3] (512 columns dealt to the ranks, fields gathered to rank 0)",
                              "single_gpu_proxy": "extras.c4_shard"}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(w)
     stuck = False
-    if world > 1 and not strong:
+    if a.full and world > 1 and not strong:
         # The one-sweep-over-the-node measurement, in a thread the main thread waits for with a limit: its gather (the C ABI's
         # sosrt_gather under RCCL) has never run with more than one rank on this pool's one-GPU boxes, and a collective that does not
         # complete must cost the line its `strong` object, not the line.

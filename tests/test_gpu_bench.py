@@ -23,7 +23,7 @@ def _dump(path):
 
 
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--columns", "64", "--no-cpu-baseline", "--no-extras"],
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--columns", "64", "--full", "--no-cpu-baseline", "--no-extras"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -48,11 +48,34 @@ def test_bench_single_gpu_line():
     assert d["strong"]["status"].startswith("unmeasured")
 
 
+def test_bench_plain_run_is_lean(tmp_path):
+    """Without --full the run times its steps, dumps and prints the line, nothing else; the timed steps are those of a --full run:
+    the same order counts and the same outputs, bit for bit."""
+    import numpy as np
+    lines = {}
+    for run, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-extras", "--pipelined", "0", "--check-columns", "1"])):
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--columns", "64",
+                            "--dump-outputs", str(tmp_path / run)] + extra, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[run] = _json_line(r.stdout)
+    d, f = lines["plain"], lines["full"]
+    assert d["unit"] == "columns/s" and d["value"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) < 1e-9 * d["value"]
+    assert d["metric"] == f["metric"] and d["roofline"]["kernel"] in ("k_jn_gemm", "k_transport_ring + k_transport_scan")
+    for k in ("check", "two_groups", "pipelined", "extras", "cpu_baseline", "strong"):
+        assert k not in d, k
+    assert f["check"]["ok"]
+    assert d["config"]["orders_per_step"] == f["config"]["orders_per_step"] and d["config"]["not_converged"] == 0
+    out, ref = _dump(tmp_path / "plain"), _dump(tmp_path / "full")
+    assert sorted(out) == sorted(ref) == sorted(x[:-4] for x in d["dumped_outputs"]["files"])
+    assert all(np.array_equal(out[k], ref[k]) for k in ref)
+
+
 def test_bench_accounts_for_order_loop_launches():
     """SOSRT_ORDER_LOOP=1 (opt-in): 216 columns -- the first orders are two launches each; once at most 128 columns are live the
     rest of the solve is ONE order-loop launch, priced on a line of its own; the (column, order) pairs of a step are in one or
     the other."""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--columns", "216", "--no-cpu-baseline", "--no-extras",
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--columns", "216", "--full", "--no-cpu-baseline", "--no-extras",
                         "--pipelined", "0"], cwd=ROOT, env=dict(os.environ, SOSRT_ORDER_LOOP="1"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -68,7 +91,7 @@ def test_bench_accounts_for_order_loop_launches():
 def test_bench_extras_c2_c3_c5_and_hg_stand_in():
     """The other single-GPU configurations of BASELINE.json beside the headline: one EVA column at N_mu = 128 and 256
     (single-column latency), the 4096-column wildfire sweep at L = 400, N = 256, each checked against the oracle."""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--columns", "27", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--columns", "27", "--full", "--no-cpu-baseline",
                         "--aerosol", "hg", "--pipelined", "0"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -88,7 +111,7 @@ def test_bench_extras_c2_c3_c5_and_hg_stand_in():
 def test_bench_two_column_groups_at_the_headline_size():
     """512 columns at (200, 128): the library takes two column groups by itself (one field of the batch = 210 MB); `two_groups`
     measures that loop beside the one-group headline and must find the headline's bits."""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--pipelined", "0",
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--pipelined", "0",
                         "--check-columns", "1"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -106,7 +129,7 @@ def test_bench_two_ranks_share_the_gpu(tmp_path):
     port = 29600 + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--columns", "27",
-           "--inflight", "2", "--aerosol", "hg", "--dump-outputs", str(tmp_path)]
+           "--inflight", "2", "--aerosol", "hg", "--full", "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = _json_line(r.stdout)
@@ -129,7 +152,7 @@ def test_bench_strong_scaling_spawns_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SOSRT_BENCH_BACKEND="gloo", SOSRT_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--scaling", "strong", "--steps", "2", "--warmup", "1",
-                        "--columns", "27", "--dump-outputs", str(tmp_path)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--columns", "27", "--full", "--dump-outputs", str(tmp_path)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0
@@ -151,7 +174,7 @@ def test_bench_dumps_the_outputs_of_its_last_step(tmp_path):
     import numpy as np
     dumps = []
     for run, cols, steps, extra in (("a", 216, 3, []), ("b", 216, 3, []), ("c", 64, 2, ["--inflight", "3"])):
-        r = subprocess.run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", "0", "--columns", str(cols), "--no-cpu-baseline",
+        r = subprocess.run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", "0", "--columns", str(cols), "--full", "--no-cpu-baseline",
                             "--no-extras", "--pipelined", "0", "--check-columns", "1", "--dump-outputs", str(tmp_path / run)] + extra,
                            cwd=ROOT, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]

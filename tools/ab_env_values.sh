@@ -4,7 +4,7 @@ mkdir -p gpurun_out; out=gpurun_out/ab_env_values.log; : > $out
 for rep in 1 2 3; do
   for v in $vals; do
     echo "val $v" >> $out
-    env $var=$v timeout -k 10 200 python bench.py "$@" --steps 20 --warmup 3 --no-extras --no-cpu-baseline --pipelined 0 --check-columns 1 >> $out 2>&1 || exit 1
+    env $var=$v timeout -k 10 200 python bench.py --full "$@" --steps 20 --warmup 3 --no-extras --no-cpu-baseline --pipelined 0 --check-columns 1 >> $out 2>&1 || exit 1
   done
 done
 python3 - <<'PY'

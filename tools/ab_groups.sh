@@ -4,7 +4,7 @@ out=gpurun_out/ab_groups.log; : > $out
 run() {  # columns layers angles aerosol steps
   for rep in 1 2; do for gq in 1 2; do
     echo "cfg $1 $2 $3 $4 groups=$gq" >> $out
-    timeout -k 10 200 python bench.py --groups $gq --columns $1 --layers $2 --angles $3 --aerosol $4 --steps $5 --warmup 2 --no-extras --no-cpu-baseline --pipelined 0 --check-columns 1 >> $out 2>&1 || return 1
+    timeout -k 10 200 python bench.py --full --groups $gq --columns $1 --layers $2 --angles $3 --aerosol $4 --steps $5 --warmup 2 --no-extras --no-cpu-baseline --pipelined 0 --check-columns 1 >> $out 2>&1 || return 1
   done; done
 }
 if [ -n "$SHAPES" ]; then eval "$SHAPES"; else

@@ -4,7 +4,7 @@ out=gpurun_out/ab_libs_extras.log; : > $out
 for rep in 1 2; do
   for l in $1; do
     echo "lib $l" >> $out
-    SOSRT_LIB=$PWD/sos-radiative-transfer_amd/$l timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --pipelined 0 --check-columns 1 >> $out 2>&1 || exit 1
+    SOSRT_LIB=$PWD/sos-radiative-transfer_amd/$l timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --pipelined 0 --check-columns 1 >> $out 2>&1 || exit 1
   done
 done
 python3 - <<'PY'

@@ -1,11 +1,14 @@
 #!/bin/bash
-# usage: benchcmp.sh tag "ENV=.. ENV=.." ...   (pairs)
+# usage: benchcmp.sh tag "ENV=.. ENV=.." ...   (pairs; logs go to $OUT, default the current directory)
+out=${OUT:-.}
+mkdir -p "$out"
 while [ $# -gt 1 ]; do
   tag=$1; envs=$2; shift 2
-  env $envs timeout -k 10 200 python bench.py --no-cpu-baseline --check-columns 1 --pipelined 0 > gpurun_out/r2_b_$tag.log 2>&1
-  python - "$tag" <<PY
+  log=$out/benchcmp_$tag.log
+  env $envs timeout -k 10 200 python bench.py --full --no-cpu-baseline --check-columns 1 --pipelined 0 > "$log" 2>&1
+  python - "$tag" "$log" <<PY
 import json,sys
-tag=sys.argv[1]; f="gpurun_out/r2_b_%s.log"%tag
+tag, f = sys.argv[1], sys.argv[2]
 try:
     d=[json.loads(l) for l in open(f) if l.startswith("{")][0]
     k=d["kernel_ms_per_step"]
