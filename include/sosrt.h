@@ -262,7 +262,9 @@ int sosrt_phase_matrix(sosrt_t* h, int kind, double g, double* P_out);
  * and the modes are normalised by the m = 0 ring of the same nphi:
  *     P0^m[b][a] = R^m(a, mu0_b) / (4 pi) * 2 / Z0_b,  Z0_b = trapz_mu(R^0(., mu0_b) / (4 pi))
  *     P^m[a][n]  = R^m(a, n) / (2 pi) * 4 / Z_n,       Z_n  = trapz_mu(R^0(., n) / (2 pi)).
- * Mode m of the radiance obeys the order loop of the azimuth average with (P^m, P0^m) in place of (P, P0), and
+ * Mode m of the radiance obeys the order loop of the azimuth average with ((-1)^m P^m, P0^m) in place of (P, P0): the
+ * contraction pairs P[a][flip b] with I[b] (the reference's fold), and with c above that pair is the physical scattering
+ * cosine at phi + pi, whose mode m is (-1)^m times the one at phi; P0 has no fold.  Then
  *     I(t, mu, phi) = sum_{m=0}^{M} (2 - delta_m0) I^m(t, mu) cos(m phi).
  * Azimuth convention: phi is the ring's angle; phi = 0 with an upward mu = mu0 is exact back-scatter (toward the sun).
  * Mode 0 is always the output of sosrt_phase_matrix / sosrt_phase_p0 (the reference's 25-point ring), bit for bit;

@@ -213,7 +213,9 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
             s.set_order_targets(d_target.data_ptr())
             for m in range(1, M + 1):
                 s.synchronize()                              # (set_phase rewrites the matrices the previous mode's solve read)
-                s.set_phase(Pm[0][m - 1], Pm[1][m - 1])
+                # the solve of mode m takes (-1)^m P^m: its contraction reads P[a][flip b], the stored matrix at phi + pi
+                sgn = -1.0 if m & 1 else 1.0
+                s.set_phase(sgn * Pm[0][m - 1], sgn * Pm[1][m - 1])
                 s.solve_device(d_tau.data_ptr(), d_P0[0][m - 1].data_ptr(), d_P0[1][m - 1].data_ptr(), d_Im.data_ptr(),
                                d_n_orders=d_n.data_ptr(), d_status=d_st[m - 1].data_ptr())
                 s.azimuth_accumulate_device(m, d_Im.data_ptr(), d_lev.data_ptr(), nlev, d_phi.data_ptr(), nout, d_out.data_ptr(), B=B)

@@ -27,6 +27,13 @@ def phase_modes(fn, mu, ms, nphi):
     return np.stack([4 * R[1 + i] / Z for i in range(len(ms))])
 
 
+def solve_modes(fn, mu, ms, nphi):
+    """The matrices a solve of mode m takes, (-1)^m P^m [len(ms), 2N, 2N]: the source function pairs P[a][flip b] with
+    I[b] (the reference's fold), and with the cosine above that pair is the physical scattering cosine at phi + pi, whose
+    mode m is (-1)^m times the one at phi.  P0^m has no fold and no factor."""
+    return np.stack([(-1) ** m * P for m, P in zip(ms, phase_modes(fn, mu, ms, nphi))])
+
+
 def phase_p0_modes(fn, mu, mu0, ms, nphi):
     """P0^m [len(ms), 2N] for one mu0: R^m / (4 pi) * 2 / Z0, Z0 = trapz_mu(R^0(., mu0) / (4 pi))."""
     R = ring_modes(fn, mu, np.array([float(mu0)]), [0] + list(ms), nphi)[:, :, 0] / (4 * np.pi)

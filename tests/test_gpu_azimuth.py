@@ -175,9 +175,10 @@ def _oracle_fixed(c, k):
     return I
 
 
-def test_driver_three_zone_modes_against_the_oracle():
+def test_driver_three_zone_signed_modes_against_the_oracle():
     """SOS_Aer_batch(..., azimuths=...) at TOA and surface against the oracle's mode fields synthesized the same way
-    (g3-style Rayleigh + HG, L = 60, N = 64, three columns, M = 3)."""
+    (g3-style Rayleigh + HG, L = 60, N = 64, three columns, M = 3), the oracle solving mode m with (-1)^m P^m, the sign of
+    the reference's fold (azimuth_np.solve_modes; tests/test_azimuth_host.py checks it against a direct azimuth solve)."""
     L, N, M, nphi = 60, 64, 3, 25
     mu0 = np.array([0.35, 0.6, 0.85])
     phi = np.linspace(0, 2 * np.pi, 9)
@@ -186,7 +187,7 @@ def test_driver_three_zone_modes_against_the_oracle():
     assert r.I_azimuth.shape == (3, 2, 2 * N, len(phi)) and r.mode_status.shape == (M + 1, 3) and not r.mode_status.any()
     mu = inputs.direction_grid(N)
     ray, hg = inputs._scalar_phase("rayleigh")[0], inputs._scalar_phase("hg", 0.7)[0]
-    Pa, Pr = A.phase_modes(ray, mu, range(1, M + 1), nphi), A.phase_modes(hg, mu, range(1, M + 1), nphi)
+    Pa, Pr = A.solve_modes(ray, mu, range(1, M + 1), nphi), A.solve_modes(hg, mu, range(1, M + 1), nphi)
     for b in range(3):
         P0a = A.phase_p0_modes(ray, mu, mu0[b], range(1, M + 1), nphi)
         P0r = A.phase_p0_modes(hg, mu, mu0[b], range(1, M + 1), nphi)
