@@ -62,9 +62,10 @@ const char* sosrt_last_error(void);
  * second half of that round).  102: the azimuth-resolved solve -- Fourier modes of the phase functions
  * (sosrt_phase_modes, sosrt_phase_p0_modes[_dev]), fixed order counts per column (sosrt_set_order_targets) and the
  * synthesis in azimuth (sosrt_azimuth_accumulate_dev); nothing that existed before changes.  103: the low-rank form of the
- * plain rows (sosrt_phase_rank, SOSRT_CONTRACT_F64_DENSE); results move within SOSRT_LOWRANK_TOL.  A binding checks
- * sosrt_version() >= the SOSRT_VERSION it was written against. */
-#define SOSRT_VERSION 103
+ * plain rows (sosrt_phase_rank, SOSRT_CONTRACT_F64_DENSE); results move within SOSRT_LOWRANK_TOL.  104: Mie tables built on the
+ * device (sosrt_mie_ensembles[_dev], sosrt_mie_efficiencies, sosrt_mie_timing, sosrt_phase_table_dev); nothing that existed
+ * before changes.  A binding checks sosrt_version() >= the SOSRT_VERSION it was written against. */
+#define SOSRT_VERSION 104
 int sosrt_version(void);
 
 /* ---- handle ------------------------------------------------------------------------------- */
@@ -248,6 +249,42 @@ int sosrt_epilogue(sosrt_t* h, int B, int beam_norm, const double* z_profile, do
 #define SOSRT_PHASE_TABLE     3   /* phase:238 fwc: a tabulated p(cos Theta), linear interpolation phase:198  */
 /* table of SOSRT_PHASE_TABLE (host arrays, tab_mu ascending; fwc:3,173 is the reference's table) */
 int sosrt_phase_table(sosrt_t* h, const double* tab_mu, const double* tab_p, int ntab);
+/* The same from device arrays, in stream order (no trip through the host): d_tab_mu NULL means the uniform abscissa
+ * linspace(-1, 1, ntab), what sosrt_mie_ensembles tabulates on.  Ascending order of a caller's d_tab_mu is not checked. */
+int sosrt_phase_table_dev(sosrt_t* h, const double* d_tab_mu, const double* d_tab_p, int ntab);
+
+/* ---- Lorenz-Mie tables on the device ------------------------------------------------------------
+ * The series of Bohren & Huffman (1983) ch. 4 with the term counts of the package's host module: x = 2 pi r / wl,
+ * n_max = round(x + 4 x^(1/3) + 2) terms, logarithmic derivative D_n(mx) downward from max(n_max, |mx|) + 16.  m = m_re + i m_im
+ * with m_im > 0 ABSORBING (time factor exp(-i w t)); a caller under the other convention conjugates first.
+ *
+ * sosrt_mie_ensembles: S log-normal ensembles, phase:398-489.  Radii linspace(r_min, r_max, nb_radius) (micrometres, as wl
+ * and r_m), n(r) = exp(-(ln r - ln r_m)^2 / (2 ln^2 sig)) / r, each sphere's intensity (|S1|^2 + |S2|^2) / (2 pi x^2 Q_ext)
+ * weighted by n(r) Q_sca(r), trapezoid over r: p_out [S][ntab] on mu = linspace(-1, 1, ntab), un-normalised (every consumer
+ * normalises).  nb_radius = 1 is ONE SPHERE of radius r_min without weights (phase:299; r_m, sig, r_max are not read).
+ * bulk_out [S][3] (may be NULL), same trapezoid: {single-scattering albedo int n r^2 Q_sca / int n r^2 Q_ext, asymmetry
+ * parameter int n r^2 Q_sca g / int n r^2 Q_sca, mean extinction cross-section pi int n r^2 Q_ext / int n in the square of
+ * the unit of r}; one sphere: {Q_sca / Q_ext, g, pi r^2 Q_ext}.  Sums run in a fixed order: the same call gives the same
+ * bits, and a batch the bits of its single calls.
+ * wl, m_re, m_im, r_m, sig [S] are HOST arrays in both forms (the workspaces are sized from them); _dev: d_p_out and
+ * d_bulk_out are device pointers and the work is enqueued on the handle's stream.
+ * Caps: x <= SOSRT_MIE_MAX_X and |m x| <= SOSRT_MIE_MAX_MX for every sphere, and a workspace (32 n_max bytes per sphere plus
+ * 8 ntab bytes per four radii) of at most SOSRT_MIE_MAX_WORKSPACE bytes per call; beyond them, and for sig <= 1, ntab < 2,
+ * nb_radius < 1: SOSRT_E_INVALID, a message, nothing written. */
+#define SOSRT_MIE_MAX_X 20000.0
+#define SOSRT_MIE_MAX_MX 200000.0
+#define SOSRT_MIE_MAX_WORKSPACE (2ull << 30)
+int sosrt_mie_ensembles(sosrt_t* h, int S, const double* wl, const double* m_re, const double* m_im, const double* r_m,
+                        const double* sig, int nb_radius, double r_min, double r_max, int ntab, double* p_out, double* bulk_out);
+int sosrt_mie_ensembles_dev(sosrt_t* h, int S, const double* wl, const double* m_re, const double* m_im, const double* r_m,
+                            const double* sig, int nb_radius, double r_min, double r_max, int ntab, double* d_p_out,
+                            double* d_bulk_out);
+/* The coefficient kernel alone: out [K][4] = {Q_ext, Q_sca, Q_back, g} of K spheres (m_re, m_im, x [K]; host arrays) */
+int sosrt_mie_efficiencies(sosrt_t* h, int K, const double* m_re, const double* m_im, const double* x, double* out);
+/* milliseconds the three kernels of the last sosrt_mie_ensembles[_dev] took (coefficients, angles, integration; HIP events
+ * around each; waits for them) */
+int sosrt_mie_timing(sosrt_t* h, double* ms /*[3]*/);
+
 /* P0(mu, mu0[b]) for B columns (phase:86-103): 25-point azimuth trapezoid, normalised to trapz(P0, mu) = 2.
  * _dev: d_mu0 [B] and d_P0_out [B][2N] are device pointers (a mu0 sweep builds its P0 where the solve reads it). */
 int sosrt_phase_p0_dev(sosrt_t* h, int B, int kind, double g, const double* d_mu0, double* d_P0_out);

@@ -2,6 +2,7 @@
 // buffers, the order loop with lagged convergence polling, HIP-event profiling.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -99,6 +100,13 @@ struct sosrt_handle {
     size_t modetab_cap = 0;
     const int* d_targets = nullptr;      // sosrt_set_order_targets (caller's device array [B]); null: the spec:309 test
     int ntab = 0;
+    // Mie tables (sosrt_mie_ensembles): device arena and pinned staging of the per-call parameters, both grow-only; the
+    // event orders a refill of the staging buffer behind the copy out of it; mie_t: events around the three kernels
+    char* d_mie = nullptr;
+    char* h_mie = nullptr;
+    size_t mie_cap = 0, mie_hcap = 0;
+    hipEvent_t mie_ev = nullptr, mie_t[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool mie_timed = false;
     bool resident = false;               // d_tau / d_I hold the inputs / result of the last sosrt_solve (of resident_B columns)
     int resident_B = 0;
     FixTab* d_fix = nullptr;
@@ -202,6 +210,17 @@ int dalloc(T** p, size_t n) {
     hipError_t e = hipMalloc((void**)p, n * sizeof(T));
     if (e != hipSuccess) return fail(SOSRT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
     return 0;
+}
+
+// np.linspace(a, b, n): i * step + a with the last point set to b (no contraction of the product and the sum)
+void mie_linspace(double a, double b, int n, double* out) {
+    if (n == 1) { out[0] = a; return; }
+    const double step = (b - a) / (n - 1);
+    for (int i = 0; i < n; ++i) {
+        volatile double t = i * step;
+        out[i] = t + a;
+    }
+    out[n - 1] = b;
 }
 
 // the pools grow on demand (a long profiled run must not end up with timings of its first steps only)
@@ -800,6 +819,11 @@ int sosrt_destroy(sosrt_t* h) {
             if (p) hipFree(p);
         if (h->h_pub) hipHostFree(h->h_pub);
         if (h->h_oldone) hipHostFree(h->h_oldone);
+        if (h->d_mie) hipFree(h->d_mie);
+        if (h->h_mie) hipHostFree(h->h_mie);
+        if (h->mie_ev) hipEventDestroy(h->mie_ev);
+        for (auto& e : h->mie_t)
+            if (e) hipEventDestroy(e);
 
         for (auto& p : h->prof)
             for (auto& e : p.ev) hipEventDestroy(e);
@@ -1820,6 +1844,225 @@ int sosrt_phase_table(sosrt_t* h, const double* tab_mu, const double* tab_p, int
     HIPCHK(hipMemcpy(h->d_tab, tab_mu, ntab * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_tab + ntab, tab_p, ntab * sizeof(double), hipMemcpyHostToDevice));
     h->ntab = ntab;
+    return 0;
+}
+
+int sosrt_phase_table_dev(sosrt_t* h, const double* d_tab_mu, const double* d_tab_p, int ntab) {
+    if (int e = need_gpu(h)) return e;
+    if (!d_tab_p || ntab < 2) return fail(SOSRT_E_INVALID, "a table needs at least two points");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    if (h->ntab != ntab || !h->d_tab) {                      // (a table of the same length is overwritten in stream order)
+        HIPCHK(hipStreamSynchronize(s));
+        if (h->d_tab) { hipFree(h->d_tab); h->d_tab = nullptr; h->ntab = 0; }
+        if (int e = dalloc(&h->d_tab, 2 * (size_t)ntab)) return e;
+        h->ntab = ntab;
+    }
+    if (d_tab_mu) {
+        HIPCHK(hipMemcpyAsync(h->d_tab, d_tab_mu, ntab * sizeof(double), hipMemcpyDeviceToDevice, s));
+    } else {
+        std::vector<double> mu(ntab);
+        mie_linspace(-1.0, 1.0, ntab, mu.data());
+        HIPCHK(hipMemcpyAsync(h->d_tab, mu.data(), ntab * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));                     // (mu leaves scope)
+    }
+    HIPCHK(hipMemcpyAsync(h->d_tab + ntab, d_tab_p, ntab * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Lorenz-Mie tables on the device
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct MiePlan {
+    int S = 0, R = 0, ntab = 0, n_cap = 0;
+    size_t o_x, o_radii, o_mu, o_tn, o_mre, o_mim, o_rm, o_sig, o_nmax, o_nstart, in_bytes;   // staged by the host
+    size_t o_ab, o_qw, o_part, o_p, o_bulk, bytes;                                              // written by the kernels
+};
+
+size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// Terms of the series and start of the downward recurrence, as mie.mie_coefficients counts them
+int mie_counts(double m_re, double m_im, double x, int* nmax, int* nstart) {
+    if (!(x > 0) || !std::isfinite(x) || !std::isfinite(m_re) || !std::isfinite(m_im) || (m_re == 0 && m_im == 0))
+        return fail(SOSRT_E_INVALID, "Mie: the size parameter must be positive and finite and the refractive index non-zero (x = %g, m = %g%+gi)", x, m_re, m_im);
+    const double amx = std::hypot(m_re * x, m_im * x);
+    if (x > SOSRT_MIE_MAX_X || amx > SOSRT_MIE_MAX_MX)
+        return fail(SOSRT_E_INVALID, "Mie: x = %g, |m x| = %g are beyond the caps SOSRT_MIE_MAX_X = %g, SOSRT_MIE_MAX_MX = %g", x,
+                    amx, (double)SOSRT_MIE_MAX_X, (double)SOSRT_MIE_MAX_MX);
+    *nmax = (int)std::nearbyint(x + 4.0 * std::pow(x, 1.0 / 3.0) + 2.0);
+    *nstart = (int)(std::max((double)*nmax, amx) + 16);
+    return 0;
+}
+
+// Lays the call out, grows the arena and the staging buffer, and waits until the staging buffer may be refilled
+int mie_prepare(sosrt_handle* h, MiePlan& p, bool tables) {
+    const size_t n = (size_t)p.S * p.R;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += up256(bytes); return at; };
+    p.o_x = take(n * 8); p.o_radii = take((size_t)p.R * 8); p.o_mu = take((size_t)p.ntab * 8); p.o_tn = take(((size_t)p.n_cap + 1) * 8);
+    p.o_mre = take((size_t)p.S * 8); p.o_mim = take((size_t)p.S * 8); p.o_rm = take((size_t)p.S * 8); p.o_sig = take((size_t)p.S * 8);
+    p.o_nmax = take(n * 4); p.o_nstart = take(n * 4);
+    p.in_bytes = o;
+    p.o_ab = take(n * p.n_cap * 4 * 8); p.o_qw = take(n * kMieQ * 8);
+    p.o_part = take(tables ? (size_t)p.S * mie_chunks(p.R) * p.ntab * 8 : 0);
+    p.o_p = take(tables ? (size_t)p.S * p.ntab * 8 : 0); p.o_bulk = take((size_t)p.S * 3 * 8);
+    p.bytes = o;
+    if (p.bytes > (size_t)SOSRT_MIE_MAX_WORKSPACE)
+        return fail(SOSRT_E_INVALID, "Mie: the call needs %zu bytes of workspace, more than SOSRT_MIE_MAX_WORKSPACE = %zu: split it", p.bytes,
+                    (size_t)SOSRT_MIE_MAX_WORKSPACE);
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->mie_ev) {
+        HIPCHK(hipEventCreateWithFlags(&h->mie_ev, hipEventDisableTiming));
+        for (auto& e : h->mie_t) HIPCHK(hipEventCreate(&e));
+    }
+    if (p.bytes > h->mie_cap) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->d_mie) { hipFree(h->d_mie); h->d_mie = nullptr; h->mie_cap = 0; }
+        if (int e = dalloc(&h->d_mie, p.bytes)) return e;
+        h->mie_cap = p.bytes;
+    }
+    HIPCHK(hipEventSynchronize(h->mie_ev));                  // (never recorded: returns at once)
+    if (p.in_bytes > h->mie_hcap) {
+        if (h->h_mie) { hipHostFree(h->h_mie); h->h_mie = nullptr; h->mie_hcap = 0; }
+        HIPCHK(hipHostMalloc((void**)&h->h_mie, p.in_bytes, hipHostMallocDefault));
+        h->mie_hcap = p.in_bytes;
+    }
+    return 0;
+}
+
+// stages the inputs, copies them and launches the coefficient kernel (with `tables`, the other two as well)
+int mie_run(sosrt_handle* h, const MiePlan& p, bool tables) {
+    hipStream_t s = h->stream;
+    double* tn = (double*)(h->h_mie + p.o_tn);
+    tn[0] = 0;
+    for (int n = 1; n <= p.n_cap; ++n) tn[n] = (n + 1.0) / n;
+    HIPCHK(hipMemcpyAsync(h->d_mie, h->h_mie, p.in_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(h->mie_ev, s));
+    char* d = h->d_mie;
+    auto D = [&](size_t off) { return (double*)(d + off); };
+    const int n = p.S * p.R;
+    HIPCHK(hipEventRecord(h->mie_t[0], s));
+    launch_mie_coefficients(s, n, p.R, p.n_cap, D(p.o_x), (const int*)(d + p.o_nmax), (const int*)(d + p.o_nstart), D(p.o_mre),
+                            D(p.o_mim), tables ? D(p.o_radii) : nullptr, D(p.o_rm), D(p.o_sig), D(p.o_ab), D(p.o_qw));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->mie_t[1], s));
+    if (tables) {
+        launch_mie_angles(s, p.S, p.R, p.ntab, p.n_cap, D(p.o_mu), D(p.o_ab), (const int*)(d + p.o_nmax), D(p.o_tn), D(p.o_qw),
+                          D(p.o_part));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->mie_t[2], s));
+        launch_mie_integrate(s, p.S, p.R, p.ntab, D(p.o_part), D(p.o_radii), D(p.o_qw), D(p.o_p), D(p.o_bulk));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->mie_t[3], s));
+    }
+    h->mie_timed = tables;
+    return 0;
+}
+
+int mie_ensembles(sosrt_handle* h, int S, const double* wl, const double* m_re, const double* m_im, const double* r_m,
+                  const double* sig, int nb_radius, double r_min, double r_max, int ntab, double* p_out, double* bulk_out,
+                  bool dev) {
+    if (int e = need_gpu(h)) return e;
+    if (S < 1 || !wl || !m_re || !m_im || !p_out) return fail(SOSRT_E_INVALID, "Mie: need S >= 1, wl, m_re, m_im and p_out");
+    if (ntab < 2) return fail(SOSRT_E_INVALID, "Mie: a table needs at least two points (ntab = %d)", ntab);
+    if (nb_radius < 1) return fail(SOSRT_E_INVALID, "Mie: nb_radius must be >= 1 (got %d)", nb_radius);
+    if (!(r_min > 0) || !std::isfinite(r_min)) return fail(SOSRT_E_INVALID, "Mie: r_min must be positive (got %g)", r_min);
+    if (nb_radius > 1 && (!(r_max > r_min) || !std::isfinite(r_max))) return fail(SOSRT_E_INVALID, "Mie: need r_max > r_min (got %g, %g)", r_max, r_min);
+    if (nb_radius > 1 && (!r_m || !sig)) return fail(SOSRT_E_INVALID, "Mie: an ensemble needs r_m and sig");
+    if ((long long)S * nb_radius > (1 << 24)) return fail(SOSRT_E_INVALID, "Mie: S * nb_radius too large");
+    if (S > 65535) return fail(SOSRT_E_INVALID, "Mie: at most 65535 ensembles in a call");
+    for (int s = 0; s < S; ++s) {
+        if (!(wl[s] > 0) || !std::isfinite(wl[s])) return fail(SOSRT_E_INVALID, "Mie: ensemble %d: the wavelength must be positive (got %g)", s, wl[s]);
+        if (nb_radius > 1 && (!(sig[s] > 1) || !std::isfinite(sig[s]))) return fail(SOSRT_E_INVALID, "Mie: ensemble %d: sig must be > 1 (got %g)", s, sig[s]);
+        if (nb_radius > 1 && (!(r_m[s] > 0) || !std::isfinite(r_m[s]))) return fail(SOSRT_E_INVALID, "Mie: ensemble %d: r_m must be positive (got %g)", s, r_m[s]);
+    }
+    const int R = nb_radius;
+    std::vector<double> radii(R), x((size_t)S * R);
+    std::vector<int> nmax((size_t)S * R), nstart((size_t)S * R);
+    mie_linspace(r_min, r_max, R, radii.data());
+    MiePlan p;
+    p.S = S; p.R = R; p.ntab = ntab;
+    for (int s = 0; s < S; ++s)
+        for (int i = 0; i < R; ++i) {
+            const size_t k = (size_t)s * R + i;
+            x[k] = 2 * M_PI * radii[i] / wl[s];              // (2 pi r) / wl, as mie.log_normal_bulk_phase writes it
+            if (int e = mie_counts(m_re[s], m_im[s], x[k], &nmax[k], &nstart[k])) return e;
+            p.n_cap = std::max(p.n_cap, nmax[k]);
+        }
+    if (int e = mie_prepare(h, p, true)) return e;
+    char* hm = h->h_mie;
+    memcpy(hm + p.o_x, x.data(), x.size() * 8);
+    memcpy(hm + p.o_radii, radii.data(), radii.size() * 8);
+    mie_linspace(-1.0, 1.0, ntab, (double*)(hm + p.o_mu));
+    memcpy(hm + p.o_mre, m_re, (size_t)S * 8);
+    memcpy(hm + p.o_mim, m_im, (size_t)S * 8);
+    for (int s = 0; s < S; ++s) {
+        ((double*)(hm + p.o_rm))[s] = R > 1 ? r_m[s] : 1.0;
+        ((double*)(hm + p.o_sig))[s] = R > 1 ? sig[s] : 2.0;
+    }
+    memcpy(hm + p.o_nmax, nmax.data(), nmax.size() * 4);
+    memcpy(hm + p.o_nstart, nstart.data(), nstart.size() * 4);
+    if (int e = mie_run(h, p, true)) return e;
+    hipStream_t st = h->stream;
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHK(hipMemcpyAsync(p_out, h->d_mie + p.o_p, (size_t)S * ntab * 8, kind, st));
+    if (bulk_out) HIPCHK(hipMemcpyAsync(bulk_out, h->d_mie + p.o_bulk, (size_t)S * 3 * 8, kind, st));
+    if (!dev) HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // namespace
+
+int sosrt_mie_ensembles(sosrt_t* h, int S, const double* wl, const double* m_re, const double* m_im, const double* r_m,
+                        const double* sig, int nb_radius, double r_min, double r_max, int ntab, double* p_out, double* bulk_out) {
+    return mie_ensembles(h, S, wl, m_re, m_im, r_m, sig, nb_radius, r_min, r_max, ntab, p_out, bulk_out, false);
+}
+
+int sosrt_mie_ensembles_dev(sosrt_t* h, int S, const double* wl, const double* m_re, const double* m_im, const double* r_m,
+                            const double* sig, int nb_radius, double r_min, double r_max, int ntab, double* d_p_out,
+                            double* d_bulk_out) {
+    return mie_ensembles(h, S, wl, m_re, m_im, r_m, sig, nb_radius, r_min, r_max, ntab, d_p_out, d_bulk_out, true);
+}
+
+int sosrt_mie_efficiencies(sosrt_t* h, int K, const double* m_re, const double* m_im, const double* x, double* out) {
+    if (int e = need_gpu(h)) return e;
+    if (K < 1 || K > (1 << 24) || !m_re || !m_im || !x || !out) return fail(SOSRT_E_INVALID, "Mie: need 1 <= K <= 2^24, m_re, m_im, x and out");
+    std::vector<int> nmax(K), nstart(K);
+    MiePlan p;
+    p.S = K; p.R = 1; p.ntab = 0;
+    for (int k = 0; k < K; ++k) {
+        if (int e = mie_counts(m_re[k], m_im[k], x[k], &nmax[k], &nstart[k])) return e;
+        p.n_cap = std::max(p.n_cap, nmax[k]);
+    }
+    if (int e = mie_prepare(h, p, false)) return e;
+    char* hm = h->h_mie;
+    memcpy(hm + p.o_x, x, (size_t)K * 8);
+    memcpy(hm + p.o_mre, m_re, (size_t)K * 8);
+    memcpy(hm + p.o_mim, m_im, (size_t)K * 8);
+    memcpy(hm + p.o_nmax, nmax.data(), (size_t)K * 4);
+    memcpy(hm + p.o_nstart, nstart.data(), (size_t)K * 4);
+    if (int e = mie_run(h, p, false)) return e;
+    hipStream_t st = h->stream;
+    std::vector<double> q((size_t)K * kMieQ);
+    HIPCHK(hipMemcpyAsync(q.data(), h->d_mie + p.o_qw, q.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < K; ++k) memcpy(out + 4 * (size_t)k, q.data() + (size_t)k * kMieQ, 4 * sizeof(double));
+    return 0;
+}
+
+int sosrt_mie_timing(sosrt_t* h, double* ms) {
+    if (int e = need_gpu(h)) return e;
+    if (!ms) return fail(SOSRT_E_INVALID, "null argument");
+    if (!h->mie_timed) return fail(SOSRT_E_STATE, "sosrt_mie_ensembles has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize(h->mie_t[3]));
+    for (int k = 0; k < 3; ++k) {
+        float t = 0;
+        HIPCHK(hipEventElapsedTime(&t, h->mie_t[k], h->mie_t[k + 1]));
+        ms[k] = t;
+    }
     return 0;
 }
 

@@ -320,6 +320,19 @@ void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B,
 // out[b][lev][dir][j] (+)= (2 - delta_m0) I^m[b][levels[lev]][dir] cos(m phi[j])   (m == 0 writes, m >= 1 adds)
 void launch_azimuth_accumulate(hipStream_t s, const Grid& g, int B, int m, const double* Im, int nlev, const int* levels,
                                int nphi_out, const double* phi, double* out);
+// Lorenz-Mie tables (sosrt_mie_ensembles).  nlanes = S * R spheres, lane = s * R + i; x, nmax, nstart [nlanes]
+// (size parameter, terms of the series, start of the downward recurrence: from the host, mie.mie_coefficients' counts);
+// ab [nlanes][n_cap][4] and qw [nlanes][kMieQ] workspaces; tn [n_cap + 1]: (n + 1) / n; part [S][mie_chunks(R)][ntab].
+constexpr int kMieQ = 6;           // Q_ext, Q_sca, Q_back, g, n(r), weight in the table
+constexpr int kMieChunk = 4;       // radii per workgroup of the angle kernel (fixed: a batch and its single calls sum alike)
+inline int mie_chunks(int R) { return (R + kMieChunk - 1) / kMieChunk; }
+void launch_mie_coefficients(hipStream_t s, int nlanes, int R, int n_cap, const double* x, const int* nmax, const int* nstart,
+                             const double* m_re, const double* m_im, const double* radii, const double* r_m, const double* sig,
+                             double* ab, double* qw);
+void launch_mie_angles(hipStream_t s, int S, int R, int ntab, int n_cap, const double* mu, const double* ab, const int* nmax,
+                       const double* tn, const double* qw, double* part);
+void launch_mie_integrate(hipStream_t s, int S, int R, int ntab, const double* part, const double* radii, const double* qw,
+                          double* p, double* bulk);
 void launch_limit_rows(hipStream_t s, const Grid& g, int R, int table, const double* rows, double* out);
 void launch_asymptotic(hipStream_t s, int R, int stride, const int* len, const double* J, const double* tau,
                        const double* tau_t, const double* mu, double* out);

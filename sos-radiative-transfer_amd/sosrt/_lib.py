@@ -57,6 +57,11 @@ SIGNATURES = {
     "sosrt_epilogue_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 6),
     "sosrt_epilogue": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 6),
     "sosrt_phase_table": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    "sosrt_phase_table_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    "sosrt_mie_ensembles": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_double, c_double, c_int, c_void_p, c_void_p]),
+    "sosrt_mie_ensembles_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_double, c_double, c_int, c_void_p, c_void_p]),
+    "sosrt_mie_efficiencies": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sosrt_mie_timing": (c_int, [c_void_p, _dp]),
     "sosrt_phase_p0_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
     "sosrt_phase_p0": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
     "sosrt_phase_matrix": (c_int, [c_void_p, c_int, c_double, c_void_p]),

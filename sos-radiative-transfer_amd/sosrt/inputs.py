@@ -117,21 +117,47 @@ def _bulk(name, **kw):
     return _bulk_cache[key]
 
 
-def scenario_table(name, lambda0=None, indx=None, r_m=None, sig=None, indx_convention="absorbing"):
+def _on_device(device, fn):
+    """fn(solver) on the caller's `Solver`, or (device=True / a device number) on a small handle of its own."""
+    from .solver import Solver
+    if isinstance(device, Solver):
+        return fn(device)
+    s = Solver(2, 4, max_batch=1, max_orders=1, device=0 if device is True else int(device))
+    try:
+        return fn(s)
+    finally:
+        s.close()
+
+
+def _bulk_device(name, device, **kw):
+    """`_bulk` from the device builder (sosrt_mie_ensembles), cached under the same key plus a device tag."""
+    key = (name,) + tuple(sorted(kw.items())) + ("device",)
+    if key not in _bulk_cache:
+        _bulk_cache[key] = _on_device(device, lambda s: _mie.log_normal_bulk_phase_device(s, **kw))[:2]
+    return _bulk_cache[key]
+
+
+def scenario_table(name, lambda0=None, indx=None, r_m=None, sig=None, indx_convention="absorbing", device=None):
     """The (mu_diff, p) table of 'eva' | 'wildfire' (README.md:95-111 unless overridden): what `phase_function` evaluates on
     the host and `phase_function_device` hands to the device table kernel (SOSRT_PHASE_TABLE).  Parity unpinned (own Mie
     series, sosrt/mie.py).  `indx_convention`: how the sign of Im(indx) is read -- 'absorbing' (default: any imaginary part
-    absorbs), 'n+ik', 'n-ik' (miepython's documented sign); sosrt/mie.py."""
+    absorbs), 'n+ik', 'n-ik' (miepython's documented sign); sosrt/mie.py.  `device`: None (default) the host series; True, a
+    device number or a `Solver`: the table comes from the HIP kernels (within 1e-12 of the host's)."""
     kw = dict(_mie.SCENARIOS[name])
     for k, v in (("wl", lambda0), ("m", indx), ("r_m", r_m), ("sig", sig)):
         if v:
             kw[k] = v
     kw["m"] = _mie.refractive_index(kw["m"], indx_convention)          # (the cache key holds the index as the series takes it)
+    if device is not None and device is not False:
+        return _bulk_device(name, device, convention="n+ik", **kw)
     return _bulk(name, convention="n+ik", **kw)
 
 
-def _scalar_phase(name, g=0.0, r=None, lambda0=None, indx=None, r_m=None, sig=None, table=None, indx_convention="absorbing"):
-    """p(cos Theta) as a NumPy callable, and -- for the device builders -- its (kind, table) form."""
+def _scalar_phase(name, g=0.0, r=None, lambda0=None, indx=None, r_m=None, sig=None, table=None, indx_convention="absorbing",
+                  device=None):
+    """p(cos Theta) as a NumPy callable, and -- for the device builders -- its (kind, table) form.  `device` (None | True | a
+    device number | a `Solver`): the Mie-derived tables from the device builder instead of the host series."""
+    on_device = device is not None and device is not False
     if name == "rayleigh":
         return (lambda c: (3 / 4) * (1 + c * c)), ("rayleigh", None)
     if name == "hg":
@@ -140,14 +166,18 @@ def _scalar_phase(name, g=0.0, r=None, lambda0=None, indx=None, r_m=None, sig=No
         mt, pt = fwc_table() if table is None else (np.asarray(table[0], dtype=np.float64), np.asarray(table[1], dtype=np.float64))
         return (lambda c: interpolate_table(mt, pt, c)), ("table", (mt, pt))
     if name in ("eva", "wildfire"):
-        mt, pt = scenario_table(name, lambda0, indx, r_m, sig, indx_convention)
+        mt, pt = scenario_table(name, lambda0, indx, r_m, sig, indx_convention, device)
         return (lambda c: interpolate_table(mt, pt, c)), ("table", (mt, pt))
     if name == "mie":
         if not (r and lambda0 and indx):
             raise ValueError("'mie' needs r, lambda0 and indx")
         x = 2 * np.pi * r / lambda0
         mt = np.linspace(-1, 1, 6001)                       # phase:684-694 (compute_P's grid of scattering cosines)
-        pt = _mie.i_unpolarized(complex(indx), x, mt, indx_convention)
+        if on_device:
+            pt = _on_device(device, lambda s: _mie.log_normal_bulk_phase_device(s, lambda0, complex(indx), nb_radius=1, r_min=r,
+                                                                                convention=indx_convention))[1]
+        else:
+            pt = _mie.i_unpolarized(complex(indx), x, mt, indx_convention)
         return (lambda c: interpolate_table(mt, pt, c)), ("table", (mt, pt))
     raise ValueError("unknown phase function %r" % (name,))
 
@@ -168,7 +198,8 @@ def phase_function_device(name, nb_angles, mu, mu0, g=0.0, r=None, lambda0=None,
     """The same on the GPU: `mu0` may be an array (one P0 row per column).  Returns (P0 [len(mu0), 2N] or [2N] for a
     scalar mu0, P [2N, 2N] or None when matrix=False).  Every name `phase_function` takes: 'iso' | 'rayleigh' | 'hg' |
     'fwc' | 'table' | 'mie' | 'eva' | 'wildfire' -- the Mie-derived ones as tables on the scattering cosine (the Mie series
-    and the size integration run once on the host, sosrt/mie.py; the O(D^2 * 50) azimuth averages on the device)."""
+    and the size integration run once on the host, sosrt/mie.py -- or on the device with `device=` in `_scalar_phase` /
+    `scenario_table`; the O(D^2 * 50) azimuth averages on the device)."""
     from .solver import Solver
     scalar = np.ndim(mu0) == 0
     m = np.atleast_1d(np.asarray(mu0, dtype=np.float64))

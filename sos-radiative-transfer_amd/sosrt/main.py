@@ -79,9 +79,13 @@ def _raise_status(status, nb_angles):
 def device_phase(s: Solver, name, mu0, g=0.0, mie=None, matrix=True):
     """(P0 rows [len(mu0), 2N], P [2N, 2N] or None) of a named phase function, azimuth-averaged by the HIP kernels of solver
     `s` (phase:79-133 and its siblings; the grid must be set).  `mie` = dict(r=, lambda0=, indx=, r_m=, sig=) for 'mie' /
-    'eva' / 'wildfire', whose phase function goes to the device as a table on the scattering cosine."""
+    'eva' / 'wildfire', whose phase function goes to the device as a table on the scattering cosine; `device=True` in that dict
+    builds the table with the device's Mie kernels instead of the host series."""
     from .inputs import _scalar_phase
-    kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **(mie or {}))[1]
+    kw = dict(mie or {})
+    if kw.get("device") is True:                             # device=True: the Mie table from the kernels of this handle
+        kw["device"] = s
+    kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **kw)[1]
     if tab is not None:
         s.set_phase_table(*tab)
     P0 = s.phase_p0(kind, mu0, g)
@@ -97,7 +101,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
-    sig=) for the Mie-derived ones ('eva' and 'wildfire' default to the README's scenarios).
+    sig=[, device=True: the Mie table from the device builder]) for the Mie-derived ones ('eva' and 'wildfire' default to the
+    README's scenarios).
     `first_order='readme'`: the README's Lambertian first order
     (Solver.set_first_order; parity unpinned, single device).  `devices=[0, 1, ...]` shards the columns over several
     GPUs of the node, one worker process each, and gathers the fields (sosrt.dist.solve_on_devices; per-order
@@ -145,6 +150,85 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         if raise_on_error:
             _raise_status(out.mode_status, N)
     return out
+
+
+def _spectrum_args(wavelengths, tauStar_aer, angstrom, lambda_ref, aer, alb_aer, tauStar_atm_ref):
+    """Checks of `SOS_Aer_spectrum`, made before any handle exists: (wl [W], tauStar_aer [W], tauStar_atm [W], m [W], r_m [W],
+    sig [W])."""
+    wl = np.atleast_1d(np.asarray(wavelengths, dtype=np.float64))
+    if wl.ndim != 1 or wl.size == 0 or not np.all(np.isfinite(wl)) or np.any(wl <= 0):
+        raise ValueError("wavelengths must be a non-empty 1-d array of positive numbers (micrometres)")
+    if not (np.isfinite(lambda_ref) and lambda_ref > 0):
+        raise ValueError("lambda_ref must be positive")
+    if not isinstance(aer, dict) or set(aer) - {"m", "r_m", "sig"} or set(("m", "r_m", "sig")) - set(aer):
+        raise ValueError("aer must be dict(m=, r_m=, sig=): refractive index (scalar or one per wavelength), median radius and "
+                         "geometric standard deviation of the log-normal ensemble")
+    if not (alb_aer == "mie" or np.ndim(alb_aer) == 0 or np.shape(alb_aer) == wl.shape):
+        raise ValueError("alb_aer must be 'mie' (the ensemble's single-scattering albedo), a number or one number per wavelength")
+    if callable(tauStar_aer):
+        if angstrom is not None:
+            raise ValueError("give tauStar_aer as a function of the wavelength or an Angstrom exponent, not both")
+        t_aer = np.array([float(tauStar_aer(w)) for w in wl])
+    elif angstrom is not None:
+        if np.ndim(tauStar_aer) != 0:
+            raise ValueError("with an Angstrom exponent tauStar_aer is the optical depth at lambda_ref (a scalar)")
+        t_aer = float(tauStar_aer) * (wl / lambda_ref) ** (-float(angstrom))
+    else:
+        t_aer = np.asarray(tauStar_aer, dtype=np.float64)
+        if t_aer.ndim != 0 and t_aer.shape != wl.shape:
+            raise ValueError("tauStar_aer must be a scalar, one value per wavelength or a function of the wavelength")
+        t_aer = np.broadcast_to(t_aer, wl.shape).copy()
+    if np.any(t_aer < 0) or not np.all(np.isfinite(t_aer)):
+        raise ValueError("tauStar_aer must be finite and >= 0")
+    t_atm = float(tauStar_atm_ref) * (lambda_ref / wl) ** 4
+    try:
+        m, r_m, sig = (np.broadcast_to(np.asarray(aer[k]), wl.shape) for k in ("m", "r_m", "sig"))
+    except ValueError:
+        raise ValueError("aer: m, r_m and sig must be scalars or one value per wavelength") from None
+    return wl, t_aer, t_atm, m.astype(complex), r_m.astype(np.float64), sig.astype(np.float64)
+
+
+def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=None, lambda_ref=0.550, tauStar_atm_ref=0.124,
+                     alb_aer="mie", alb_atm=1.0, nb_radius=100, r_min=0.01, r_max=10.0, ntab=6001, indx_convention="absorbing",
+                     atm_phase_fun="rayleigh", g_atm=0.0, nb_layers=200, nb_angles=128, max_orders=256, device=0, **batch_kw):
+    """A spectrum of batches: for every wavelength (micrometres) the columns (mu0, grd_alb) of `SOS_Aer_batch` with a log-normal
+    Mie aerosol `aer` = dict(m=, r_m=, sig=) (each a scalar or one value per wavelength).  The molecular optical depth is
+    tauStar_atm_ref (lambda_ref / wl)^4; the aerosol's is `tauStar_aer`: a function of the wavelength, one value per wavelength,
+    a constant, or -- with `angstrom` -- its value at lambda_ref scaled by (wl / lambda_ref)^-angstrom.  `alb_aer='mie'`
+    (default) takes every ensemble's own single-scattering albedo.  All ensembles are tabulated in ONE call of the device's
+    Mie kernels (`Solver.mie_ensembles_device`); per wavelength the table is handed to the azimuth builders on the device
+    (`Solver.set_phase_table_dev`) and the columns go through `SOS_Aer_batch` (further keywords are passed on).
+    Returns (list of BatchResult, one per wavelength; bulk [W, 3]: albedo, asymmetry parameter, mean extinction cross-section)."""
+    import torch
+    from . import mie as _mie
+    wl, t_aer, t_atm, m, r_m, sig = _spectrum_args(wavelengths, tauStar_aer, angstrom, lambda_ref, aer, alb_aer, tauStar_atm_ref)
+    for k in ("P_aer", "P0_aer", "aer_phase_fun", "mie_aer", "tauStar_atm", "devices", "azimuths"):
+        if k in batch_kw:
+            raise ValueError("SOS_Aer_spectrum sets %s itself" % k)
+    m = np.array([_mie.refractive_index(v, indx_convention) for v in m])
+    mu0v, _ = np.broadcast_arrays(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), np.atleast_1d(np.asarray(grd_alb, dtype=np.float64)))
+    L, N, W = int(nb_layers), int(nb_angles), wl.size
+    s = get_solver(L, N, mu0v.shape[0], max_orders, device)
+    mu = direction_grid(N)
+    if not s.same_grid(mu):
+        s.set_grid(mu)
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        d_p = torch.empty((W, int(ntab)), dtype=torch.float64, device=dev)
+        d_bulk = torch.empty((W, 3), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        s.mie_ensembles_device(d_p.data_ptr(), d_bulk.data_ptr(), wl, m, r_m, sig, nb_radius, r_min, r_max, ntab)
+        s.synchronize()
+        bulk = d_bulk.cpu().numpy()
+        omega = bulk[:, 0] if isinstance(alb_aer, str) else np.broadcast_to(np.asarray(alb_aer, dtype=np.float64), wl.shape)
+        out = []
+        for w in range(W):
+            s.set_phase_table_dev(d_p[w].data_ptr(), int(ntab))
+            P0r, P_aer = s.phase_p0("table", mu0v), s.phase_matrix("table")
+            out.append(SOS_Aer_batch(mu0, t_aer[w], grd_alb, tauStar_atm=t_atm[w], alb_atm=alb_atm, alb_aer=omega[w],
+                                     nb_layers=L, nb_angles=N, atm_phase_fun=atm_phase_fun, g_atm=g_atm, P_aer=P_aer, P0_aer=P0r,
+                                     max_orders=max_orders, device=device, **batch_kw))
+    return out, bulk
 
 
 def _azimuth_args(azimuths, n_modes, nphi_modes, levels, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface, devices, first_order):

@@ -23,7 +23,8 @@ m -> n + i|k|), so `1.7 + 0.03j` and `1.7 - 0.03j` give the same, absorbing, sph
 for callers who want exactly that.  The choice is an argument of every public function here and of
 `inputs.phase_function(..., indx_convention=)`.
 
-Inputs of the hot path only -- host NumPy, not on the timed path.
+Inputs of the hot path only.  The functions below are host NumPy (the record the device builder is tested against);
+`log_normal_bulk_phase_device` builds the same tables with the HIP kernels of csrc/epilogue.hip (opt-in).
 """
 from __future__ import annotations
 
@@ -135,6 +136,19 @@ def log_normal_bulk_phase(wl, m, r_m, sig, nb_radius=100, r_min=0.01, r_max=10.0
         P[i] = i_unpolarized(m, x, mu_d, "n+ik")
     w = n_r * qsca
     return mu_d, _trapz(w[:, None] * P, radii, axis=0)
+
+
+def log_normal_bulk_phase_device(solver, wl, m, r_m=None, sig=None, nb_radius=100, r_min=0.01, r_max=10.0, nb_mu=6001,
+                                 convention="absorbing"):
+    """`log_normal_bulk_phase` on the device of `solver` (a `sosrt.solver.Solver`): returns (mu_diff [nb_mu], p, bulk) with
+    p [nb_mu] and bulk [3] = (single-scattering albedo, asymmetry parameter, mean extinction cross-section) of the ensemble
+    for scalar arguments; array arguments (broadcast to [S]) give p [S, nb_mu] and bulk [S, 3] from one call.
+    nb_radius = 1: one sphere of radius r_min (`i_unpolarized`)."""
+    scalar = all(np.ndim(a) == 0 for a in (wl, m, r_m, sig) if a is not None)
+    mm = np.array([refractive_index(v, convention) for v in np.atleast_1d(np.asarray(m, dtype=complex)).ravel()]).reshape(np.shape(np.atleast_1d(m)))
+    p, bulk = solver.mie_ensembles(wl, mm, r_m, sig, nb_radius, r_min, r_max, nb_mu)
+    mu_d = np.linspace(-1, 1, nb_mu)
+    return (mu_d, p[0], bulk[0]) if scalar else (mu_d, p, bulk)
 
 
 def tabulated_phase(mu_d, p):

@@ -309,6 +309,53 @@ class Solver:
         tp = _f64(tab_p, tm.shape, "tab_p")
         check(lib().sosrt_phase_table(self._h, _ptr(tm), _ptr(tp), int(tm.size)))
 
+    def set_phase_table_dev(self, d_tab_p: int, ntab: int, d_tab_mu: int = 0):
+        """The table from DEVICE arrays (addresses), in stream order: `d_tab_p` [ntab] on the uniform abscissa
+        linspace(-1, 1, ntab) -- a row of `mie_ensembles_device`'s output -- or on `d_tab_mu` [ntab]."""
+        check(lib().sosrt_phase_table_dev(self._h, ctypes.c_void_p(d_tab_mu) if d_tab_mu else None, ctypes.c_void_p(d_tab_p),
+                                          int(ntab)))
+
+    # ---- Lorenz-Mie tables on the device (sosrt.h; DESIGN section 12) ----------------
+    @staticmethod
+    def _mie_args(wl, m, r_m, sig):
+        wl, mm, rm, sg = np.broadcast_arrays(*[np.atleast_1d(np.asarray(a)) for a in (wl, m, 1.0 if r_m is None else r_m,
+                                                                                     2.0 if sig is None else sig)])
+        mm = mm.astype(np.complex128)
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        return f(wl), f(mm.real), f(mm.imag), f(rm), f(sg)
+
+    def mie_ensembles(self, wl, m, r_m=None, sig=None, nb_radius=100, r_min=0.01, r_max=10.0, ntab=6001):
+        """Phase tables of S log-normal Mie ensembles (arrays broadcast to [S]; `m` = n + ik with k > 0 absorbing, see
+        `mie.refractive_index`) -> (p [S, ntab] on linspace(-1, 1, ntab), bulk [S, 3] = single-scattering albedo, asymmetry
+        parameter, mean extinction cross-section).  nb_radius = 1: one sphere of radius r_min."""
+        a = self._mie_args(wl, m, r_m, sig)
+        S = a[0].size
+        p, bulk = np.empty((S, max(int(ntab), 0))), np.empty((S, 3))
+        check(lib().sosrt_mie_ensembles(self._h, S, *[_ptr(v) for v in a], int(nb_radius), float(r_min), float(r_max), int(ntab),
+                                        _ptr(p), _ptr(bulk)))
+        return p, bulk
+
+    def mie_ensembles_device(self, d_p_out: int, d_bulk_out: int, wl, m, r_m=None, sig=None, nb_radius=100, r_min=0.01,
+                             r_max=10.0, ntab=6001):
+        """The same into device buffers (addresses; [S, ntab] and [S, 3] or 0), enqueued on the handle's stream."""
+        a = self._mie_args(wl, m, r_m, sig)
+        check(lib().sosrt_mie_ensembles_dev(self._h, a[0].size, *[_ptr(v) for v in a], int(nb_radius), float(r_min), float(r_max),
+                                            int(ntab), ctypes.c_void_p(d_p_out), ctypes.c_void_p(d_bulk_out) if d_bulk_out else None))
+
+    def mie_efficiencies(self, m, x):
+        """(Q_ext, Q_sca, Q_back, g) of K spheres -> [K, 4] (`m`, `x` broadcast; m = n + ik, k > 0 absorbing)."""
+        mm, xx = np.broadcast_arrays(np.atleast_1d(np.asarray(m, dtype=np.complex128)), np.atleast_1d(np.asarray(x, dtype=np.float64)))
+        mr, mi, xx = (np.ascontiguousarray(v, dtype=np.float64) for v in (mm.real, mm.imag, xx))
+        out = np.empty((xx.size, 4))
+        check(lib().sosrt_mie_efficiencies(self._h, int(xx.size), _ptr(mr), _ptr(mi), _ptr(xx), _ptr(out)))
+        return out
+
+    def mie_timing(self):
+        """Milliseconds of the three kernels of the last `mie_ensembles` (coefficients, angles, integration)."""
+        ms = (ctypes.c_double * 3)()
+        check(lib().sosrt_mie_timing(self._h, ms))
+        return tuple(ms)
+
     def phase_p0(self, kind, mu0, g=0.0):
         """P0(mu, mu0[b]) for an array of mu0 -> [len(mu0), 2N]."""
         m = np.ascontiguousarray(np.atleast_1d(mu0), dtype=np.float64)
