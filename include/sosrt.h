@@ -64,8 +64,11 @@ const char* sosrt_last_error(void);
  * synthesis in azimuth (sosrt_azimuth_accumulate_dev); nothing that existed before changes.  103: the low-rank form of the
  * plain rows (sosrt_phase_rank, SOSRT_CONTRACT_F64_DENSE); results move within SOSRT_LOWRANK_TOL.  104: Mie tables built on the
  * device (sosrt_mie_ensembles[_dev], sosrt_mie_efficiencies, sosrt_mie_timing, sosrt_phase_table_dev); nothing that existed
- * before changes.  A binding checks sosrt_version() >= the SOSRT_VERSION it was written against. */
-#define SOSRT_VERSION 104
+ * before changes.  105: several aerosol phase matrices on one handle, chosen per column or per aerosol zone
+ * (sosrt_set_phase_sets[_dev], sosrt_phase_matrix_dev, sosrt_set_aerosol_sets, sosrt_phase_sets_info; sosrt_plan_fold answers
+ * for every set); nothing that
+ * existed before changes.  A binding checks sosrt_version() >= the SOSRT_VERSION it was written against. */
+#define SOSRT_VERSION 105
 int sosrt_version(void);
 
 /* ---- handle ------------------------------------------------------------------------------- */
@@ -103,6 +106,50 @@ int sosrt_set_grid(sosrt_t* h, const double* mu);
 /* phase matrices P(mu, mu') [2N x 2N] (outputs of phase_func, phase:12); P_aer may be NULL for the
  * single-slab geometry.  Folded on the host into W[k][m] = w_k P[m][2N-1-k] (I1_In:73, spec:321). */
 int sosrt_set_phase(sosrt_t* h, const double* P_atm, const double* P_aer);
+
+/* ---- several aerosol phase matrices in one batch ----------------------------------------------------------------------
+ * sosrt_set_phase_sets: as sosrt_set_phase with S aerosol matrices P_aer [S][2N][2N] (host), 1 <= S <= SOSRT_MAX_PHASE_SETS.
+ * S = 1 is sosrt_set_phase, bit for bit.  The symmetric form of the contraction is taken only if W_atm and EVERY set pass
+ * SOSRT_SYMMETRY_TOL (sosrt_phase_asymmetry reports the maximum over them); the low-rank factor is of W_atm alone.
+ * sosrt_plan_fold(h, 1 + s, ..) returns the fold of set s.
+ *
+ * sosrt_set_aerosol_sets: which set the aerosol of a column reads.  Called after sosrt_set_columns with nzmax = 1
+ * (zone_set [B]: one set per column) or after sosrt_set_columns_zones with its nzmax (zone_set [B][nzmax]: one set per
+ * aerosol zone; entries of clear zones are ignored).  Every sosrt_set_columns* call puts all columns back on set 0, so a
+ * caller that never calls this sees no change.  A set outside 0..S-1, or a later sosrt_set_phase* with fewer sets than the
+ * current columns use: SOSRT_E_INVALID with a message, nothing changed.
+ *
+ * How it is computed.  The slab rows of the contraction are multiplied by combined matrices ca W_atm + cr W_aer, one per
+ * distinct coefficient pair of the batch ("group"); with sets a group is a distinct (set, ca, cr), and a batch with several
+ * aerosols runs the same single pass over its slab rows, at the same flop count, with the bits each column has in a batch
+ * of its own set alone.  While every column is on set 0 the cache holds 32 groups and a batch with more takes two passes
+ * (W_atm, then W_aer), as before.  With another set in use the cache may hold up to 128 groups within 256 MiB of combined
+ * matrices (never fewer than 32: 128 groups up to N = 256, 32 at N = 501); a batch with more groups takes the two passes
+ * too: its slab rows are then listed set by set, and the second pass of a tile (dense tiling) or of a column (live-column
+ * tilings) reads the W_aer of its set.  Two passes sum a slab row in another order than the single pass (same 1e-10 parity,
+ * not the same bits).  The float contraction has no two-pass form (SOSRT_E_INVALID beyond the cache, as before).
+ *
+ * P0_aer of sosrt_first_order / sosrt_solve[_dev] stays [B][2N] when sets are per column (nzmax = 1): the caller passes
+ * each column the P0 of its own set, as it always did.  After sosrt_set_aerosol_sets with nzmax > 1, P0_aer is
+ * [B][nzmax][2N] and aerosol zone z of column b reads row (b, z) (the values in rows of clear zones are ignored), until the next
+ * sosrt_set_columns* call.
+ *
+ * Not combined with sets: SOSRT_FIRST_ORDER_README (it reads the one W_aer element by element) -- sosrt_set_first_order and
+ * sosrt_set_phase_sets with S > 1 refuse each other with SOSRT_E_INVALID.
+ *
+ * sosrt_phase_sets_info: out[4] = { sets of the last sosrt_set_phase*, groups of the current columns (0: none, or two passes),
+ * 1 if the slab rows of the current columns take the single pass, groups the cache would hold with sets in use }. */
+#define SOSRT_MAX_PHASE_SETS 64
+int sosrt_set_phase_sets(sosrt_t* h, const double* P_atm, int S, const double* P_aer /*[S][2N][2N]*/);
+/* The same with the aerosol matrices in DEVICE memory (d_P_aer [S][2N][2N], e.g. written by sosrt_phase_matrix_dev): fold
+ * and asymmetry measure run as kernels in the handle's stream order, so the matrices go from the azimuth builders to the
+ * contraction without visiting the host; a few partial maxima come back to decide the symmetric form (the call waits for
+ * them).  The folds have the bits of the host fold (sosrt_plan_fold fetches one when asked); for NaN-free matrices the
+ * asymmetry is the host loop's number, and any NaN switches the symmetric form off.  P_atm stays a host pointer: its low-rank
+ * factorisation is host code.  S = 1 is allowed.  d_P_aer may be freed once the call returns. */
+int sosrt_set_phase_sets_dev(sosrt_t* h, const double* P_atm /*host*/, int S, const double* d_P_aer /*device*/);
+int sosrt_set_aerosol_sets(sosrt_t* h, int B, int nzmax, const int* zone_set /*[B][nzmax]*/);
+int sosrt_phase_sets_info(sosrt_t* h, int* out /*[4]*/);
 
 /* First order of the solve.  CODED (default): spec:104-292 -- what both mains of the reference compute, with the specularly
  * reflected beam (SOS_Aer_main_lambertian.py's first-order blocks are the same formulas; its lines 274-276 crash).
@@ -194,7 +241,8 @@ int sosrt_set_columns_zones(sosrt_t* h, int B, int surface, int nzmax, const int
 
 /* ---- step level (host pointers): parity surface of SOS_Aer_I1_In.py ------------------------- */
 /* I1_NumInt (I1_In:13) / three-zone first order (spec:104-292).
- * tau [B][L], P0_atm / P0_aer [B][2N] (P0_aer may be NULL for SINGLE_SLAB), I1 out [B][L][2N] */
+ * tau [B][L], P0_atm / P0_aer [B][2N] (P0_aer may be NULL for SINGLE_SLAB), I1 out [B][L][2N].
+ * P0_aer is [B][nzmax][2N] after sosrt_set_aerosol_sets with nzmax > 1 (one row per zone of the caller's table). */
 int sosrt_first_order(sosrt_t* h, int B, const double* tau, const double* P0_atm, const double* P0_aer,
                       double* I1_out);
 /* Jn_NumInt (I1_In:62) / spec:314-323.  In_1 [B][L][2N] -> Jn [B][L][2N] */
@@ -209,7 +257,8 @@ int sosrt_transport(sosrt_t* h, int B, const double* tau, const double* Jn, doub
  * max_orders unless sosrt_set_saved_orders was called);
  * n_orders_out [B] (the final n of spec:307-310); status_out [B] or NULL; I1_in (nullable,
  * [B][L][2N]) replaces the computed first order (used to pin the Lambertian n>=2 path).
- * I_out may be NULL: the field then stays on the device for sosrt_epilogue. */
+ * I_out may be NULL: the field then stays on the device for sosrt_epilogue.
+ * P0_aer is [B][nzmax][2N] after sosrt_set_aerosol_sets with nzmax > 1 (see there); the same holds for sosrt_solve_dev. */
 int sosrt_solve(sosrt_t* h, int B, const double* tau, const double* P0_atm, const double* P0_aer,
                 double tol, const double* I1_in,
                 double* I_out, double* I_saved_out, int* n_orders_out, int* status_out);
@@ -291,6 +340,8 @@ int sosrt_phase_p0_dev(sosrt_t* h, int B, int kind, double g, const double* d_mu
 int sosrt_phase_p0(sosrt_t* h, int B, int kind, double g, const double* mu0, double* P0_out);
 /* P(mu, mu') [2N][2N] row-major with the column normalisation trapz(P[:, n], mu) = 4 (phase:107-131); host output */
 int sosrt_phase_matrix(sosrt_t* h, int kind, double g, double* P_out);
+/* the same matrix left in device memory (d_P_out [2N][2N]), enqueued on the handle's stream: what sosrt_set_phase_sets_dev reads */
+int sosrt_phase_matrix_dev(sosrt_t* h, int kind, double g, double* d_P_out);
 
 /* ---- azimuth-resolved radiance: Fourier modes in azimuth ------------------------------------------
  * The builders above average over the azimuth.  With the reference's scattering cosine c(a, b, phi) = -(mu_a mu_b + s_a s_b
@@ -360,7 +411,8 @@ int sosrt_asymptotic_down(sosrt_t* h, int R, int stride, const int* len, const d
 
 /* ---- plan introspection (host only, no GPU needed) ------------------------------------------ */
 int sosrt_plan_weights(sosrt_t* h, double* w_out /*2N*/);
-int sosrt_plan_fold(sosrt_t* h, int which /*0 atm, 1 aer*/, double* W_out /*2N x 2N, W[k][m]*/);
+/* (which: until ABI 104 any non-zero value meant W_aer; from 105 on a value outside 0 .. sets is SOSRT_E_INVALID) */
+int sosrt_plan_fold(sosrt_t* h, int which /*0 atm, 1 aer, 1 + s: aerosol set s of sosrt_set_phase_sets*/, double* W_out /*2N x 2N, W[k][m]*/);
 /* a4b table for a given rewritten-angle count idx: s0 (first source lane), ns (sources),
  * C_out [idx][ns] (ns <= 5). */
 int sosrt_plan_fix_table(sosrt_t* h, int idx, int* s0, int* ns, double* C_out);

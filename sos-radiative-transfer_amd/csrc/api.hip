@@ -126,6 +126,27 @@ struct sosrt_handle {
     int max_main = 0, max_slab = 0;      // most plain / slab rows of any column
     // slab rows of the live-column tilings: one pass over ca W_atm + cr W_aer per distinct (ca, cr) of the batch
     static constexpr int kMaxMixGroups = 32;
+    // Several aerosol phase sets (sosrt_set_phase_sets): a group is a distinct (set, ca, cr).  While every column uses set 0 the
+    // cache holds kMaxMixGroups matrices, as it always did; once sosrt_set_aerosol_sets names another set it may grow to
+    // kMaxMixGroupsSets, bounded by kMixCacheBytes of combined matrices (never below kMaxMixGroups).
+    static constexpr int kMaxMixGroupsSets = 128;
+    static constexpr size_t kMixCacheBytes = 256ull << 20;
+    int mix_groups_max = 1 << 30;        // SOSRT_MIX_GROUPS: an upper bound on either cache (tests, A/B)
+    bool wr_on_device = false;           // the sets were folded on the device (sosrt_set_phase_sets_dev): Wr_h / Wrx_h are filled on demand
+    int nsets = 1;                       // aerosol phase sets of the last sosrt_set_phase* (1 also when there is no P_aer)
+    std::vector<std::vector<double>> Wrx_h;   // folds of the sets 1 .. nsets-1 (set 0 is Wr_h)
+    double* d_Wrsets = nullptr;          // [nsets][Dp][Wld] folds of all sets (nsets > 1 only; set 0 is in d_Wr as well)
+    size_t wrsets_capacity = 0;
+    double* d_Wrsets_s = nullptr;        // their flip-symmetric folds (symmetric contraction)
+    size_t wrsets_s_capacity = 0;
+    int* d_mixset = nullptr;             // [kMaxMixGroupsSets] set of a group
+    int max_set_used = 0;                // largest set index the current columns name (sosrt_set_aerosol_sets)
+    int p0_zones = 0;                    // > 0: P0_aer of the first order is [B][p0_zones][2N], one row per zone of the caller's table
+    double* d_P0rz = nullptr;            // staging of such a P0_aer for the host entry points
+    size_t p0rz_capacity = 0;
+    // host copy of the current columns' zone tables: sosrt_set_aerosol_sets groups the slab rows again
+    std::vector<int> c_nz, c_zr0, c_zmix, c_zset;
+    std::vector<double> c_zwr, c_zdtr, c_alb_atm, c_dtau_atm;
     int mix_groups = 0;                  // 0: disabled (too many distinct pairs, or no slab)
     bool mix_dirty = true;
     double *d_Wmix = nullptr, *d_mixca = nullptr, *d_mixcr = nullptr;
@@ -135,7 +156,7 @@ struct sosrt_handle {
     // flip-symmetric contraction (jn_gemm.hip, SYM): folded copies [k][S | A] of W_atm, W_aer and the combined matrices
     double asymmetry = 0;                // max |W[k][m] - W[D-1-k][D-1-m]| / max |W| of the last sosrt_set_phase
     bool sym_ok = false;                 // asymmetry <= SOSRT_SYMMETRY_TOL
-    bool sym_dirty = true, symmix_dirty = true;
+    bool sym_dirty = true, symmix_dirty = true, symsets_dirty = true;
     double *d_Wa_s = nullptr, *d_Wr_s = nullptr, *d_Wmix_s = nullptr;
     // low-rank form of the plain rows (jn_gemm_tile.hpp, lowrank_rows): W_atm = U V by cross approximation in sosrt_set_phase
     int lr_rank = -1;                    // terms of the accepted factorisation; -1: none within SOSRT_LOWRANK_TOL
@@ -412,7 +433,9 @@ int ensure_matrices(sosrt_handle* h, hipStream_t s) {
     const bool mixed = h->mix_groups > 0 && h->mix_dirty;
     if (mixed) {
         prof_break(h);
-        launch_wmix(s, per, h->mix_groups, h->d_Wa, h->d_Wr, h->d_mixca, h->d_mixcr, h->d_Wmix);
+        const bool sets = h->max_set_used > 0;
+        launch_wmix(s, per, h->mix_groups, h->d_Wa, sets ? h->d_Wrsets : h->d_Wr, h->d_mixca, h->d_mixcr, h->d_Wmix,
+                    sets ? h->d_mixset : nullptr);
         h->mix_dirty = false;
         h->symmix_dirty = true;
     }
@@ -424,6 +447,21 @@ int ensure_matrices(sosrt_handle* h, hipStream_t s) {
         launch_symfold(s, 1, g.N, g.D, g.Dp, g.Wld, h->d_Wa, h->d_Wa_s);
         launch_symfold(s, 1, g.N, g.D, g.Dp, g.Wld, h->d_Wr, h->d_Wr_s);
         h->sym_dirty = false;
+        h->symsets_dirty = true;
+    }
+    // the folded copies of every set: only the two-pass form with sets reads them
+    if (h->symsets_dirty && h->nsets > 1 && h->mix_groups == 0 && h->max_set_used > 0) {
+        prof_break(h);
+        {
+            if (per * h->nsets > h->wrsets_s_capacity) {
+                if (h->d_Wrsets_s) hipFree(h->d_Wrsets_s);
+                h->d_Wrsets_s = nullptr; h->wrsets_s_capacity = 0;
+                if (int e = dalloc(&h->d_Wrsets_s, per * h->nsets)) return e;
+                h->wrsets_s_capacity = per * h->nsets;
+            }
+            launch_symfold(s, h->nsets, g.N, g.D, g.Dp, g.Wld, h->d_Wrsets, h->d_Wrsets_s);
+        }
+        h->symsets_dirty = false;
     }
     if (h->mix_groups > 0 && h->symmix_dirty) {
         prof_break(h);
@@ -480,6 +518,10 @@ void run_source(sosrt_handle* h, const double* In_1, double* Jn, const int* acti
     if (h->mix_groups > 0) {
         ga.Wmix = h->d_Wmix; ga.mix_group = h->d_mixgroup; ga.slab_tile_group = h->d_slabtilegroup + h->slab_off[g0] / 32;
     }
+    const bool two_pass_sets = h->mix_groups == 0 && h->max_set_used > 0 && h->nslab > 0;
+    if (two_pass_sets) {                               // the second pass picks the W_aer of a tile's / a column's set
+        ga.Wr = h->d_Wrsets; ga.mix_group = h->d_mixgroup; ga.slab_tile_group = h->d_slabtilegroup + h->slab_off[g0] / 32;
+    }
     if (use_lowrank(h)) { ga.lr_rank = h->lr_rank; ga.lrU = h->d_lrU; ga.lrV = h->d_lrV; }
     if (use_sym(h)) {
         ga.sym = 1; ga.Ks = (h->g.N + GEMM_KC - 1) / GEMM_KC * GEMM_KC;
@@ -489,7 +531,7 @@ void run_source(sosrt_handle* h, const double* In_1, double* Jn, const int* acti
         // at sosrt_create
         if (h->diag_ks_mult > 1 && ga.Ks * h->diag_ks_mult <= h->g.Dp) ga.Ks *= h->diag_ks_mult;
 #endif
-        ga.Wa = h->d_Wa_s; ga.Wr = h->d_Wr_s;
+        ga.Wa = h->d_Wa_s; ga.Wr = two_pass_sets ? h->d_Wrsets_s : h->d_Wr_s;
         if (ga.Wmix) ga.Wmix = h->d_Wmix_s;
     }
     if (h->contraction == SOSRT_CONTRACT_F32) {
@@ -700,6 +742,7 @@ int sosrt_create(int device, int L, int N, int max_batch, int max_orders, sosrt_
     if (const char* ev = getenv("SOSRT_GEMM_REGS")) h->gemm_regs_cols = atoi(ev);           // (A/B: 0 = the staged tilings for every live count)
     if (const char* ev = getenv("SOSRT_GROUPS")) h->want_groups = atoi(ev) >= 2 ? 2 : (atoi(ev) == 1 ? 1 : 0);      // column groups of the order loop (0: auto)
     if (const char* ev = getenv("SOSRT_SPLIT_MIN")) h->split_min = atoi(ev);                  // smallest batch that is split
+    if (const char* ev = getenv("SOSRT_MIX_GROUPS")) h->mix_groups_max = atoi(ev);          // (tests, A/B: fewer combined matrices than the cache would hold -- the two-pass form sooner)
 #ifdef SOSRT_DIAG   // measurement knobs of DESIGN section 5 (items 1, 5, 8): diagnostic builds only (-DSOSRT_DIAG), never in the product library
     if (const char* ev = getenv("SOSRT_STAGGER")) h->stagger = atof(ev);
     if (const char* ev = getenv("SOSRT_GROUP_SPLIT")) h->split_at = atoi(ev);
@@ -753,8 +796,8 @@ int sosrt_create(int device, int L, int N, int max_batch, int max_orders, sosrt_
             if ((e = dalloc(&h->d_desc, mb))) return e;
             if ((e = dalloc(&h->d_rca, mb * L))) return e;
             if ((e = dalloc(&h->d_rcr, mb * L))) return e;
-            if ((e = dalloc(&h->d_slabrows, mb * L + 64 * (size_t)sosrt_handle::kMaxMixGroups * sosrt_handle::kMaxGroups))) return e;   // + padding
-            if ((e = dalloc(&h->d_slabtilegroup, mb * L / 32 + 2 * sosrt_handle::kMaxMixGroups * sosrt_handle::kMaxGroups + 2))) return e;
+            if ((e = dalloc(&h->d_slabrows, mb * L + 64 * (size_t)sosrt_handle::kMaxMixGroupsSets * sosrt_handle::kMaxGroups))) return e;   // + padding
+            if ((e = dalloc(&h->d_slabtilegroup, mb * L / 32 + 2 * sosrt_handle::kMaxMixGroupsSets * sosrt_handle::kMaxGroups + 2))) return e;
             if ((e = dalloc(&h->d_mainrows, mb * L))) return e;
             if ((e = dalloc(&h->d_tau, mb * L))) return e;
             if ((e = dalloc(&h->d_P0a, mb * g.D))) return e;
@@ -774,8 +817,9 @@ int sosrt_create(int device, int L, int N, int max_batch, int max_orders, sosrt_
             if ((e = dalloc(&h->d_erep, mb))) return e;
             if ((e = dalloc(&h->d_mixgroup, mb))) return e;
             if ((e = dalloc(&h->d_livelist, mb))) return e;
-            if ((e = dalloc(&h->d_mixca, sosrt_handle::kMaxMixGroups))) return e;
-            if ((e = dalloc(&h->d_mixcr, sosrt_handle::kMaxMixGroups))) return e;
+            if ((e = dalloc(&h->d_mixca, sosrt_handle::kMaxMixGroupsSets))) return e;
+            if ((e = dalloc(&h->d_mixcr, sosrt_handle::kMaxMixGroupsSets))) return e;
+            if ((e = dalloc(&h->d_mixset, sosrt_handle::kMaxMixGroupsSets))) return e;
             if ((e = dalloc(&h->d_tauhash, mb))) return e;
             if ((e = dalloc(&h->d_ratio, mb))) return e;
             if ((e = dalloc(&h->d_scan_scratch, mb * transport_scan_scratch_doubles()))) return e;
@@ -814,7 +858,7 @@ int sosrt_destroy(sosrt_t* h) {
                         h->d_idx_down, h->d_scal, h->d_desc, h->d_rca, h->d_rcr, h->d_slabrows, h->d_mainrows, h->d_tau, h->d_P0a,
                         h->d_P0r, h->d_Jn, h->d_InA, h->d_InB, h->d_I, h->d_E, h->d_active, h->d_norders, h->d_status,
                         h->d_nactive_sets, h->d_ratio, h->d_redo, h->d_erep, h->d_tauhash, h->d_Wmix, h->d_mixca, h->d_mixcr,
-                        h->d_mixgroup, h->d_Wa_s, h->d_Wr_s, h->d_Wmix_s, h->d_scan_scratch, h->d_scan_sync, h->d_w, h->d_phi, h->d_z, h->d_tab, h->d_slabtilegroup, h->d_livelist, h->d_Wa32, h->d_Wmix32, h->d_nz, h->d_zr0, h->d_zmix, h->d_zwr, h->d_zdtr, h->d_olsync, h->d_ollog, h->d_modetab, h->d_lrU, h->d_lrV};
+                        h->d_mixgroup, h->d_Wa_s, h->d_Wr_s, h->d_Wmix_s, h->d_scan_scratch, h->d_scan_sync, h->d_w, h->d_phi, h->d_z, h->d_tab, h->d_slabtilegroup, h->d_livelist, h->d_Wa32, h->d_Wmix32, h->d_nz, h->d_zr0, h->d_zmix, h->d_zwr, h->d_zdtr, h->d_olsync, h->d_ollog, h->d_modetab, h->d_lrU, h->d_lrV, h->d_Wrsets, h->d_Wrsets_s, h->d_mixset, h->d_P0rz};
         for (void* p : ptrs)
             if (p) hipFree(p);
         if (h->h_pub) hipHostFree(h->h_pub);
@@ -866,6 +910,8 @@ int sosrt_set_order_budget(sosrt_t* h, int max_orders) {
 int sosrt_set_first_order(sosrt_t* h, int mode) {
     if (int e = need_gpu(h)) return e;
     if (mode != SOSRT_FIRST_ORDER_CODED && mode != SOSRT_FIRST_ORDER_README) return fail(SOSRT_E_INVALID, "unknown first-order mode %d", mode);
+    if (mode == SOSRT_FIRST_ORDER_README && (h->nsets > 1 || h->p0_zones > 0))
+        return fail(SOSRT_E_INVALID, "SOSRT_FIRST_ORDER_README reads one aerosol matrix: it cannot be combined with several phase sets");
     if (mode == SOSRT_FIRST_ORDER_README && h->geom != SOSRT_GEOM_THREE_ZONE)
         return fail(SOSRT_E_INVALID, "the README's Lambertian first order needs the three-zone geometry (it has a surface)");
     h->first_order_mode = mode;
@@ -1019,21 +1065,38 @@ int sosrt_set_grid(sosrt_t* h, const double* mu) {
     return 0;
 }
 
-int sosrt_set_phase(sosrt_t* h, const double* P_atm, const double* P_aer) {
+static int mix_group_cap(const sosrt_handle* h, bool sets);
+// Common part of sosrt_set_phase / sosrt_set_phase_sets[_dev]: S aerosol matrices [S][2N][2N] (S = 0: none), host (P_aer) or
+// device (d_P_aer: folded and measured on the device, in the handle's stream order; the host keeps no copy of their folds
+// until sosrt_plan_fold asks for one)
+static int set_phase_impl(sosrt_handle* h, const double* P_atm, int S, const double* P_aer, const double* d_P_aer = nullptr) {
     if (!h || !P_atm) return fail(SOSRT_E_INVALID, "null argument");
     if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
+    if (h->have_cols && h->max_set_used >= (S > 0 ? S : 1))
+        return fail(SOSRT_E_INVALID, "the current columns use aerosol set %d, but only %d set(s) are given (sosrt_set_columns resets them to set 0)",
+                    h->max_set_used, S > 0 ? S : 1);
+    if (S > 1 && h->first_order_mode == SOSRT_FIRST_ORDER_README)
+        return fail(SOSRT_E_INVALID, "SOSRT_FIRST_ORDER_README reads one aerosol matrix: it cannot be combined with %d phase sets", S);
+    const size_t DD = (size_t)h->D * h->D;
     h->plan.fold(P_atm, h->Wa_h);
-    h->have_aer = P_aer != nullptr;
-    if (P_aer) h->plan.fold(P_aer, h->Wr_h);
+    h->have_aer = S > 0;
+    h->wr_on_device = d_P_aer != nullptr;
+    if (S > 0 && !d_P_aer) h->plan.fold(P_aer, h->Wr_h);
     else h->Wr_h.clear();
+    h->Wrx_h.clear();
+    h->Wrx_h.resize(S > 1 ? S - 1 : 0);
+    for (int q = 1; q < S && !d_P_aer; ++q) h->plan.fold(P_aer + (size_t)q * DD, h->Wrx_h[q - 1]);
+    h->nsets = S > 1 ? S : 1;
     h->have_phase = true;
     h->mix_dirty = true;
     h->w32_dirty = true;
-    h->sym_dirty = true; h->symmix_dirty = true;
-    {   // flip symmetry of the folded matrices (see sosrt.h, sosrt_set_contraction)
+    h->sym_dirty = true; h->symmix_dirty = true; h->symsets_dirty = true;
+    {   // flip symmetry of the folded matrices (see sosrt.h, sosrt_set_contraction): the maximum over W_atm and every set
         const int D = h->D;
         h->asymmetry = 0;
-        for (const std::vector<double>* W : {&h->Wa_h, &h->Wr_h}) {
+        std::vector<const std::vector<double>*> all = {&h->Wa_h, &h->Wr_h};
+        for (const auto& W : h->Wrx_h) all.push_back(&W);
+        for (const std::vector<double>* W : all) {
             if (W->empty()) continue;
             double wmax = 0, amax = 0;
             for (int k = 0; k < D; ++k)
@@ -1047,7 +1110,7 @@ int sosrt_set_phase(sosrt_t* h, const double* P_atm, const double* P_aer) {
             if (!(r <= h->asymmetry)) h->asymmetry = r;
         }
         // (a compile-time constant: nothing in the environment can put the symmetric form on a matrix without the symmetry)
-        h->sym_ok = h->asymmetry <= SOSRT_SYMMETRY_TOL;
+        h->sym_ok = h->asymmetry <= SOSRT_SYMMETRY_TOL;      // (device sets: their measure joins below)
     }
     // low rank of W_atm (see sosrt.h, sosrt_phase_rank): from the matrix alone, never from the batch
     std::vector<double> lrU, lrV;
@@ -1059,10 +1122,167 @@ int sosrt_set_phase(sosrt_t* h, const double* P_atm, const double* P_aer) {
                            g.D, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_lrU, lrU.data(), lrU.size() * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_lrV, lrV.data(), lrV.size() * sizeof(double), hipMemcpyHostToDevice));
-        if (P_aer)
+        if (S > 0 && !d_P_aer)
             HIPCHK(hipMemcpy2D(h->d_Wr, g.Wld * sizeof(double), h->Wr_h.data(), g.D * sizeof(double),
                                g.D * sizeof(double), g.D, hipMemcpyHostToDevice));
+        if (d_P_aer) {
+            // fold and asymmetry measure on the device: the matrices never visit the host, two partial maxima per block do
+            constexpr int kAsymBlocks = 32;
+            const size_t per = (size_t)g.Dp * g.Wld, scratch = (size_t)2 * kAsymBlocks * S;
+            if (per * S + scratch > h->wrsets_capacity) {
+                if (h->d_Wrsets) hipFree(h->d_Wrsets);       // (hipFree synchronises: no launch still reads it)
+                h->d_Wrsets = nullptr; h->wrsets_capacity = 0;
+                if (int e = dalloc(&h->d_Wrsets, per * S + scratch)) return e;
+                h->wrsets_capacity = per * S + scratch;
+            }
+            hipStream_t s = h->stream;
+            double* d_part = h->d_Wrsets + per * S;
+            HIPCHK(hipMemsetAsync(h->d_Wrsets, 0, per * S * sizeof(double), s));       // the padding rows and columns stay zero
+            launch_fold_sets(s, S, g.D, g.Wld, per, h->d_w, d_P_aer, h->d_Wrsets);
+            launch_fold_asymmetry(s, S, kAsymBlocks, g.D, g.Wld, per, h->d_Wrsets, d_part);
+            HIPCHK(hipMemcpyAsync(h->d_Wr, h->d_Wrsets, per * sizeof(double), hipMemcpyDeviceToDevice, s));
+            std::vector<double> part(scratch);
+            HIPCHK(hipMemcpyAsync(part.data(), d_part, scratch * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipGetLastError());
+            for (int q = 0; q < S; ++q) {
+                double wmax = 0, amax = 0;
+                for (int b = 0; b < kAsymBlocks; ++b) {
+                    const double w = part[((size_t)q * kAsymBlocks + b) * 2], a = part[((size_t)q * kAsymBlocks + b) * 2 + 1];
+                    if (!(w <= wmax)) wmax = w;              // (a NaN ends up here, as in the host loop)
+                    if (!(a <= amax)) amax = a;
+                }
+                const double r = (wmax != wmax || amax != amax) ? std::nan("") : (wmax > 0 ? amax / wmax : 0.0);
+                if (!(r <= h->asymmetry)) h->asymmetry = r;
+            }
+            h->sym_ok = h->asymmetry <= SOSRT_SYMMETRY_TOL;
+        } else if (S > 1) {
+            const size_t per = (size_t)g.Dp * g.Wld;
+            if (per * S > h->wrsets_capacity) {
+                if (h->d_Wrsets) hipFree(h->d_Wrsets);       // (hipFree synchronises: no launch still reads it)
+                h->d_Wrsets = nullptr; h->wrsets_capacity = 0;
+                if (int e = dalloc(&h->d_Wrsets, per * S)) return e;
+                h->wrsets_capacity = per * S;
+            }
+            HIPCHK(hipMemset(h->d_Wrsets, 0, per * S * sizeof(double)));       // the padding rows and columns stay zero
+            for (int q = 0; q < S; ++q)
+                HIPCHK(hipMemcpy2D(h->d_Wrsets + q * per, g.Wld * sizeof(double), (q ? h->Wrx_h[q - 1] : h->Wr_h).data(),
+                                   g.D * sizeof(double), g.D * sizeof(double), g.D, hipMemcpyHostToDevice));
+        }
     }
+    return 0;
+}
+
+int sosrt_set_phase(sosrt_t* h, const double* P_atm, const double* P_aer) {
+    return set_phase_impl(h, P_atm, P_aer ? 1 : 0, P_aer);
+}
+
+int sosrt_set_phase_sets(sosrt_t* h, const double* P_atm, int S, const double* P_aer) {
+    if (!h || !P_atm || !P_aer) return fail(SOSRT_E_INVALID, "null argument");
+    if (S < 1 || S > SOSRT_MAX_PHASE_SETS) return fail(SOSRT_E_INVALID, "S=%d outside 1..SOSRT_MAX_PHASE_SETS=%d", S, SOSRT_MAX_PHASE_SETS);
+    return set_phase_impl(h, P_atm, S, P_aer);
+}
+
+int sosrt_set_phase_sets_dev(sosrt_t* h, const double* P_atm, int S, const double* d_P_aer) {
+    if (!h || !P_atm || !d_P_aer) return fail(SOSRT_E_INVALID, "null argument");
+    if (S < 1 || S > SOSRT_MAX_PHASE_SETS) return fail(SOSRT_E_INVALID, "S=%d outside 1..SOSRT_MAX_PHASE_SETS=%d", S, SOSRT_MAX_PHASE_SETS);
+    if (int e = need_gpu(h)) return e;
+    return set_phase_impl(h, P_atm, S, nullptr, d_P_aer);
+}
+
+int sosrt_phase_sets_info(sosrt_t* h, int* out) {
+    if (!h || !out) return fail(SOSRT_E_INVALID, "null argument");
+    out[0] = h->nsets;
+    out[1] = h->have_cols ? h->mix_groups : 0;
+    out[2] = (h->have_cols && (h->nslab == 0 || h->mix_groups > 0)) ? 1 : 0;
+    out[3] = h->have_grid ? mix_group_cap(h, true) : 0;
+    return 0;
+}
+
+// Combined-matrix groups of the current columns: the distinct (aerosol set, ca, cr) of their aerosol zones (spec:321:
+// (w_atm/4) f_atm on W_atm, (w_aer/4) f_aer on W_aer), per (column, slab).
+struct MixGroups {
+    std::vector<double> ca, cr;
+    std::vector<int> set, gid /*[B][kMaxZones], -1: clear zone*/, gcol /*[B]: the live-column tilings, one slab per column*/;
+};
+// groups the cache may hold: kMaxMixGroups while every column uses set 0 (what it always held), more with several sets in use
+static int mix_group_cap(const sosrt_handle* h, bool sets) {
+    if (h->mix_groups_max < sosrt_handle::kMaxMixGroups) return h->mix_groups_max < 0 ? 0 : h->mix_groups_max;
+    if (!sets) return sosrt_handle::kMaxMixGroups;
+    const size_t per = (size_t)h->g.Dp * h->g.Wld * sizeof(double);
+    size_t n = per ? sosrt_handle::kMixCacheBytes / per : 0;
+    if (n > (size_t)sosrt_handle::kMaxMixGroupsSets) n = sosrt_handle::kMaxMixGroupsSets;
+    if (n < (size_t)sosrt_handle::kMaxMixGroups) n = sosrt_handle::kMaxMixGroups;
+    if (n > (size_t)h->mix_groups_max) n = h->mix_groups_max;
+    return (int)n;
+}
+// false: more than `cap` groups
+static bool collect_mix_groups(const sosrt_handle* h, int B, const std::vector<int>& zset, int cap, MixGroups& mg) {
+    mg.gid.assign((size_t)B * kMaxZones, -1);
+    mg.gcol.assign(B, 0);
+    for (int b = 0; b < B; ++b) {
+        for (int z = 0; z < h->c_nz[b]; ++z) {
+            if (!h->c_zmix[b * kMaxZones + z]) continue;
+            const double da = h->c_dtau_atm[b], dr = h->c_zdtr[b * kMaxZones + z];
+            const double ca = (h->c_alb_atm[b] / 4) * (da / (da + dr)), cr = (h->c_zwr[b * kMaxZones + z] / 4) * (dr / (da + dr));
+            const int st = zset[b * kMaxZones + z];
+            int k = 0;
+            while (k < (int)mg.ca.size() && !(mg.ca[k] == ca && mg.cr[k] == cr && mg.set[k] == st)) ++k;
+            if (k == (int)mg.ca.size()) {
+                if (k == cap) return false;
+                mg.ca.push_back(ca); mg.cr.push_back(cr); mg.set.push_back(st);
+            }
+            mg.gid[b * kMaxZones + z] = k;
+            mg.gcol[b] = k;
+        }
+    }
+    return true;
+}
+// uploads the groups and lists the slab rows of the dense contraction group by group.  A failed allocation of the cache leaves
+// the two-pass form (mix_groups = 0) over the row lists as sosrt_set_columns wrote them -- a choice that is only open while
+// every column uses set 0, so with sets in use it is an error.
+static int apply_mix_groups(sosrt_handle* h, int B, const MixGroups& mg) {
+    const int L = h->L;
+    const std::vector<int>&nz = h->c_nz, &zr0 = h->c_zr0;
+    auto zone_end = [&](int b, int z) { return z + 1 < nz[b] ? zr0[b * kMaxZones + z + 1] - 1 : L - 1; };
+    const size_t per = (size_t)h->g.Dp * h->g.Wld, need = per * mg.ca.size();
+    if (need > h->mix_capacity) {
+        if (h->d_Wmix) hipFree(h->d_Wmix);
+        h->d_Wmix = nullptr; h->mix_capacity = 0;
+        if (hipMalloc((void**)&h->d_Wmix, need * sizeof(double)) == hipSuccess) h->mix_capacity = need;
+        else (void)hipGetLastError();
+    }
+    if (h->mix_capacity < need) {
+        if (h->max_set_used > 0) {
+            h->have_cols = false;
+            return fail(SOSRT_E_NOMEM, "no memory for the %zu combined matrices of a batch with several aerosol sets", mg.ca.size());
+        }
+        return 0;
+    }
+    HIPCHK(hipMemcpy(h->d_mixca, mg.ca.data(), mg.ca.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_mixcr, mg.cr.data(), mg.cr.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_mixset, mg.set.data(), mg.set.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_mixgroup, mg.gcol.data(), B * sizeof(int), hipMemcpyHostToDevice));
+    h->mix_groups = (int)mg.ca.size();
+    // slab rows of the dense contraction listed, per column group of the order loop, group by group, every group padded
+    // to whole 32-row tiles
+    std::vector<int> grouped, tilegroup;
+    for (int cg = 0; cg < h->ngroups; ++cg) {
+        for (int k = 0; k < h->mix_groups; ++k) {
+            for (int b = h->gb[cg]; b < h->gb[cg + 1]; ++b)
+                for (int z = 0; z < nz[b]; ++z)
+                    if (mg.gid[b * kMaxZones + z] == k)
+                        for (int t = zr0[b * kMaxZones + z]; t <= zone_end(b, z); ++t) grouped.push_back(b * L + t);
+            while (grouped.size() % 64) grouped.push_back(-1);   // whole 64-row tiles (two 32-row tiles of the same group)
+            while (tilegroup.size() < grouped.size() / 32) tilegroup.push_back(k);
+        }
+        h->slab_off[cg + 1] = (int)grouped.size();
+    }
+    HIPCHK(hipMemcpy(h->d_slabrows, grouped.data(), grouped.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_slabtilegroup, tilegroup.data(), tilegroup.size() * sizeof(int), hipMemcpyHostToDevice));
+    h->nslab = (int)grouped.size();
+    h->mix_dirty = true;
+    h->w32_dirty = true;
     return 0;
 }
 
@@ -1156,58 +1376,18 @@ static int set_columns_impl(sosrt_handle* h, int B, int geometry, int surface, c
     h->mix_groups = 0;
     h->mix_dirty = true;
     h->w32_dirty = true;
+    // every column starts on aerosol set 0 (sosrt_set_aerosol_sets changes that), P0_aer is one row per column
+    h->max_set_used = 0;
+    h->p0_zones = 0;
+    h->c_nz = nz; h->c_zr0 = zr0; h->c_zmix = zmix; h->c_zwr = zwr; h->c_zdtr = zdtr;
+    h->c_zset.assign((size_t)B * kMaxZones, 0);
+    h->c_alb_atm.assign(alb_atm, alb_atm + B);
+    h->c_dtau_atm.assign(B, 1.0);
+    if (dtau_atm) h->c_dtau_atm.assign(dtau_atm, dtau_atm + B);
     if (geometry == SOSRT_GEOM_THREE_ZONE && h->nslab > 0) {
-        // distinct slab coefficient pairs (spec:321: (w_atm/4) f_atm on W_atm, (w_aer/4) f_aer on W_aer), per (column, slab)
-        std::vector<double> gca, gcr;
-        std::vector<int> gid((size_t)B * kMaxZones, -1), gcol(B, 0);
-        bool ok = true;
-        for (int b = 0; b < B && ok; ++b) {
-            for (int z = 0; z < nz[b] && ok; ++z) {
-                if (!zmix[b * kMaxZones + z]) continue;
-                const double da = dtau_atm[b], dr = zdtr[b * kMaxZones + z];
-                const double ca = (alb_atm[b] / 4) * (da / (da + dr)), cr = (zwr[b * kMaxZones + z] / 4) * (dr / (da + dr));
-                int k = 0;
-                while (k < (int)gca.size() && !(gca[k] == ca && gcr[k] == cr)) ++k;
-                if (k == (int)gca.size()) {
-                    if (k == sosrt_handle::kMaxMixGroups) { ok = false; break; }
-                    gca.push_back(ca); gcr.push_back(cr);
-                }
-                gid[b * kMaxZones + z] = k;
-                gcol[b] = k;                         // the live-column tilings: one slab per column
-            }
-        }
-        if (ok) {
-            const size_t per = (size_t)h->g.Dp * h->g.Wld, need = per * gca.size();
-            if (need > h->mix_capacity) {
-                if (h->d_Wmix) hipFree(h->d_Wmix);
-                h->d_Wmix = nullptr; h->mix_capacity = 0;
-                if (hipMalloc((void**)&h->d_Wmix, need * sizeof(double)) == hipSuccess) h->mix_capacity = need;
-                else (void)hipGetLastError();
-            }
-            if (h->mix_capacity >= need) {
-                HIPCHK(hipMemcpy(h->d_mixca, gca.data(), gca.size() * sizeof(double), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(h->d_mixcr, gcr.data(), gcr.size() * sizeof(double), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(h->d_mixgroup, gcol.data(), B * sizeof(int), hipMemcpyHostToDevice));
-                h->mix_groups = (int)gca.size();
-                // slab rows of the dense contraction listed, per column group of the order loop, coefficient pair by
-                // coefficient pair, every pair padded to whole 32-row tiles
-                std::vector<int> grouped, tilegroup;
-                for (int cg = 0; cg < h->ngroups; ++cg) {
-                    for (int k = 0; k < h->mix_groups; ++k) {
-                        for (int b = h->gb[cg]; b < h->gb[cg + 1]; ++b)
-                            for (int z = 0; z < nz[b]; ++z)
-                                if (gid[b * kMaxZones + z] == k)
-                                    for (int t = zr0[b * kMaxZones + z]; t <= zone_end(b, z); ++t) grouped.push_back(b * L + t);
-                        while (grouped.size() % 64) grouped.push_back(-1);   // whole 64-row tiles (two 32-row tiles of the same pair)
-                        while (tilegroup.size() < grouped.size() / 32) tilegroup.push_back(k);
-                    }
-                    h->slab_off[cg + 1] = (int)grouped.size();
-                }
-                HIPCHK(hipMemcpy(h->d_slabrows, grouped.data(), grouped.size() * sizeof(int), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(h->d_slabtilegroup, tilegroup.data(), tilegroup.size() * sizeof(int), hipMemcpyHostToDevice));
-                h->nslab = (int)grouped.size();
-            }
-        }
+        MixGroups mg;
+        if (collect_mix_groups(h, B, h->c_zset, mix_group_cap(h, false), mg))
+            if (int e = apply_mix_groups(h, B, mg)) return e;
     }
     h->B = B; h->geom = geometry; h->surface = surface;
     h->have_cols = true;
@@ -1278,9 +1458,107 @@ int sosrt_set_columns_zones(sosrt_t* h, int B, int surface, int nzmax, const int
     return set_columns_impl(h, B, SOSRT_GEOM_THREE_ZONE, surface, nz, zr0, zmix, zwr, zdtr, mu0, grd_alb, alb_atm, dtau_atm, tauStar_tot);
 }
 
+// The slab rows of a batch with more groups than the cache, for the two passes (W_atm, then W_aer).  Every column on set 0:
+// column by column, as sosrt_set_columns lists them.  With sets in use: per column group of the order loop set by set, every
+// set padded to whole 64-row tiles, so that a tile of the dense tiling has ONE set (d_slabtilegroup: the set of every 32 rows)
+// and its second pass reads that set's W_aer; the live-column tilings (columns with one slab) read the set of their column
+// (d_mixgroup).
+static int apply_two_pass_rows(sosrt_handle* h, int B) {
+    const int L = h->L;
+    const std::vector<int>&nz = h->c_nz, &zr0 = h->c_zr0;
+    auto zone_end = [&](int b, int z) { return z + 1 < nz[b] ? zr0[b * kMaxZones + z + 1] - 1 : L - 1; };
+    const bool sets = h->max_set_used > 0;
+    std::vector<int> slab, tileset, colset(B, 0);
+    for (int k = 0; k < h->ngroups; ++k) {
+        for (int st = 0; st < (sets ? h->nsets : 1); ++st) {
+            for (int b = h->gb[k]; b < h->gb[k + 1]; ++b)
+                for (int z = 0; z < nz[b]; ++z)
+                    if (h->c_zmix[b * kMaxZones + z] && (!sets || h->c_zset[b * kMaxZones + z] == st)) {
+                        for (int t = zr0[b * kMaxZones + z]; t <= zone_end(b, z); ++t) slab.push_back(b * L + t);
+                        colset[b] = st;
+                    }
+            if (sets) {
+                while (slab.size() % 64) slab.push_back(-1);
+                while (tileset.size() < slab.size() / 32) tileset.push_back(st);
+            }
+        }
+        h->slab_off[k + 1] = (int)slab.size();
+    }
+    if (!slab.empty()) HIPCHK(hipMemcpy(h->d_slabrows, slab.data(), slab.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (sets) {
+        if (!tileset.empty()) HIPCHK(hipMemcpy(h->d_slabtilegroup, tileset.data(), tileset.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_mixgroup, colset.data(), B * sizeof(int), hipMemcpyHostToDevice));
+    }
+    h->nslab = (int)slab.size();
+    h->mix_groups = 0;
+    h->mix_dirty = true;
+    h->w32_dirty = true;
+    return 0;
+}
+
+int sosrt_set_aerosol_sets(sosrt_t* h, int B, int nzmax, const int* zone_set) {
+    if (!h || !zone_set) return fail(SOSRT_E_INVALID, "null argument");
+    if (nzmax < 1 || nzmax > kMaxZones) return fail(SOSRT_E_INVALID, "nzmax must be in 1..%d (got %d)", kMaxZones, nzmax);
+    if (B < 1) return fail(SOSRT_E_INVALID, "B=%d must be >= 1", B);
+    if (!h->have_phase) return fail(SOSRT_E_STATE, "sosrt_set_phase has not been called");
+    if (int e = need_gpu(h)) return e;
+    if (!h->have_cols) return fail(SOSRT_E_STATE, "sosrt_set_columns has not been called");
+    if (B != h->B) return fail(SOSRT_E_INVALID, "B=%d does not match sosrt_set_columns (B=%d)", B, h->B);
+    if (h->geom != SOSRT_GEOM_THREE_ZONE) return fail(SOSRT_E_INVALID, "aerosol sets need the three-zone geometry (a single slab has no aerosol)");
+    // nzmax = 1: one set per column, for each of its aerosol zones; else one per zone of the caller's table
+    std::vector<int> zset((size_t)B * kMaxZones, 0);
+    int top = 0;
+    for (int b = 0; b < B; ++b) {
+        if (nzmax > 1 && h->c_nz[b] > nzmax) return fail(SOSRT_E_INVALID, "column %d has %d zones, nzmax is %d", b, h->c_nz[b], nzmax);
+        for (int z = 0; z < h->c_nz[b]; ++z) {
+            if (!h->c_zmix[b * kMaxZones + z]) continue;           // entries of clear zones are ignored
+            const int st = nzmax == 1 ? zone_set[b] : zone_set[b * nzmax + z];
+            if (st < 0 || st >= h->nsets)
+                return fail(SOSRT_E_INVALID, "column %d zone %d: aerosol set %d outside 0..%d (sosrt_set_phase_sets)", b, z, st, h->nsets - 1);
+            zset[b * kMaxZones + z] = st;
+            top = st > top ? st : top;
+        }
+    }
+    MixGroups mg;
+    const int cap = mix_group_cap(h, top > 0);
+    // (beyond the cache the slab rows take two passes, W_atm and then the W_aer of their set: apply_two_pass_rows)
+    const bool fits = collect_mix_groups(h, B, zset, cap, mg);
+    const bool regroup = top > 0 || h->max_set_used > 0;      // (all on set 0 before and after: the groups sosrt_set_columns built stand)
+    h->c_zset = zset;
+    h->max_set_used = top;
+    h->p0_zones = nzmax > 1 ? nzmax : 0;
+    if (regroup && (!fits || !mg.ca.empty())) {
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (int e = fits ? apply_mix_groups(h, B, mg) : apply_two_pass_rows(h, B)) return e;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // step level
 // ---------------------------------------------------------------------------------------------
+// host P0_aer -> device: [B][2N], or [B][p0_zones][2N] when the zone table carries aerosol sets (sosrt_set_aerosol_sets)
+static int stage_p0_aer(sosrt_handle* h, int B, const double* P0_aer, hipStream_t s, const double** d_out) {
+    *d_out = nullptr;
+    if (!P0_aer) return 0;
+    if (h->p0_zones == 0) {
+        HIPCHK(hipMemcpyAsync(h->d_P0r, P0_aer, (size_t)B * h->D * sizeof(double), hipMemcpyHostToDevice, s));
+        *d_out = h->d_P0r;
+        return 0;
+    }
+    const size_t need = (size_t)B * h->p0_zones * h->D;
+    if (need > h->p0rz_capacity) {
+        if (h->d_P0rz) hipFree(h->d_P0rz);
+        h->d_P0rz = nullptr; h->p0rz_capacity = 0;
+        if (int e = dalloc(&h->d_P0rz, need)) return e;
+        h->p0rz_capacity = need;
+    }
+    HIPCHK(hipMemcpyAsync(h->d_P0rz, P0_aer, need * sizeof(double), hipMemcpyHostToDevice, s));
+    *d_out = h->d_P0rz;
+    return 0;
+}
+
 int sosrt_first_order(sosrt_t* h, int B, const double* tau, const double* P0_atm, const double* P0_aer,
                       double* I1_out) {
     if (int e = check_ready(h, B, false)) return e;
@@ -1291,15 +1569,16 @@ int sosrt_first_order(sosrt_t* h, int B, const double* tau, const double* P0_atm
     const size_t n = (size_t)B * h->L * h->D;
     HIPCHK(hipMemcpyAsync(h->d_tau, tau, (size_t)B * h->L * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_P0a, P0_atm, (size_t)B * h->D * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (P0_aer) HIPCHK(hipMemcpyAsync(h->d_P0r, P0_aer, (size_t)B * h->D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const double* d_p0r = nullptr;
+    if (int e = stage_p0_aer(h, B, P0_aer, h->stream, &d_p0r)) return e;
     launch_prepare(h->stream, h->g, B, h->geom, h->surface, scalars_of(h), h->d_tau, h->d_desc, h->d_rca, h->d_rcr);
     prof_begin(h, SOSRT_K_FIRST);
     if (h->first_order_mode == SOSRT_FIRST_ORDER_README)
-        launch_first_order_readme(h->stream, h->g, h->d_w, B, h->d_tau, h->d_P0a, P0_aer ? h->d_P0r : nullptr, h->d_desc, h->d_InA,
+        launch_first_order_readme(h->stream, h->g, h->d_w, B, h->d_tau, h->d_P0a, d_p0r, h->d_desc, h->d_InA,
                                   nullptr, nullptr, 0, make_conv(h, 0), 0);
     else
-        launch_first_order(h->stream, h->g, B, h->d_tau, h->d_P0a, P0_aer ? h->d_P0r : nullptr, h->d_desc, h->d_InA, nullptr,
-                           nullptr, 0, make_conv(h, 0), 0);
+        launch_first_order(h->stream, h->g, B, h->d_tau, h->d_P0a, d_p0r, h->d_desc, h->d_InA, nullptr,
+                           nullptr, 0, make_conv(h, 0), 0, h->p0_zones);
     prof_end(h, SOSRT_K_FIRST);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(I1_out, h->d_InA, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1495,8 +1774,9 @@ int sosrt_solve_dev(sosrt_t* h, int B, const double* d_tau, const double* d_P0_a
                                       saved_stride, q.cv, 1);
         else
             launch_first_order(sg, g, q.nb, d_tau + (size_t)q.b0 * h->L, d_P0_atm + (size_t)q.b0 * g.D,
-                               d_P0_aer ? d_P0_aer + (size_t)q.b0 * g.D : nullptr, h->d_desc + q.b0, d_I_out + fo, nullptr,
-                               d_I_saved_out ? d_I_saved_out + (size_t)q.b0 * saved_stride : nullptr, saved_stride, q.cv, 1);
+                               d_P0_aer ? d_P0_aer + (size_t)q.b0 * g.D * (h->p0_zones > 0 ? h->p0_zones : 1) : nullptr, h->d_desc + q.b0,
+                               d_I_out + fo, nullptr, d_I_saved_out ? d_I_saved_out + (size_t)q.b0 * saved_stride : nullptr, saved_stride,
+                               q.cv, 1, h->p0_zones);
         prof_end(h, SOSRT_K_FIRST, k);
     };
     start_group(0);
@@ -1713,7 +1993,8 @@ int sosrt_solve(sosrt_t* h, int B, const double* tau, const double* P0_atm, cons
     const size_t LD = (size_t)h->L * h->D, n = (size_t)B * LD;
     HIPCHK(hipMemcpyAsync(h->d_tau, tau, (size_t)B * h->L * sizeof(double), hipMemcpyHostToDevice, s));
     if (P0_atm) HIPCHK(hipMemcpyAsync(h->d_P0a, P0_atm, (size_t)B * h->D * sizeof(double), hipMemcpyHostToDevice, s));
-    if (P0_aer) HIPCHK(hipMemcpyAsync(h->d_P0r, P0_aer, (size_t)B * h->D * sizeof(double), hipMemcpyHostToDevice, s));
+    const double* d_p0r = nullptr;
+    if (int e = stage_p0_aer(h, B, P0_aer, s, &d_p0r)) return e;
     double* d_I1 = nullptr;
     double* d_saved = nullptr;
     int rc = 0;
@@ -1726,7 +2007,7 @@ int sosrt_solve(sosrt_t* h, int B, const double* tau, const double* P0_atm, cons
             if (int e = dalloc(&d_saved, (size_t)B * h->saved_slots * LD)) return e;
             HIPCHK(hipMemsetAsync(d_saved, 0, (size_t)B * h->saved_slots * LD * sizeof(double), s));
         }
-        if (int e = sosrt_solve_dev(h, B, h->d_tau, P0_atm ? h->d_P0a : nullptr, P0_aer ? h->d_P0r : nullptr, tol, d_I1,
+        if (int e = sosrt_solve_dev(h, B, h->d_tau, P0_atm ? h->d_P0a : nullptr, d_p0r, tol, d_I1,
                                     h->d_I, d_saved, nullptr, nullptr))
             return e;
         if (I_out) HIPCHK(hipMemcpyAsync(I_out, h->d_I, n * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2099,6 +2380,16 @@ int sosrt_phase_p0(sosrt_t* h, int B, int kind, double g, const double* mu0, dou
     return 0;
 }
 
+int sosrt_phase_matrix_dev(sosrt_t* h, int kind, double g, double* d_P_out) {
+    if (int e = phase_check(h, kind, g)) return e;
+    if (!d_P_out) return fail(SOSRT_E_INVALID, "null argument");
+    HIPCHK(hipSetDevice(h->device));
+    launch_phase_matrix(h->stream, h->g, h->d_w, kind, g, h->d_tab, h->d_tab ? h->d_tab + h->ntab : nullptr, h->ntab, h->d_phi,
+                        h->d_phi + kNPhi, kNPhi, d_P_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int sosrt_phase_matrix(sosrt_t* h, int kind, double g, double* P_out) {
     if (int e = phase_check(h, kind, g)) return e;
     if (!P_out) return fail(SOSRT_E_INVALID, "null argument");
@@ -2385,7 +2676,15 @@ int sosrt_plan_weights(sosrt_t* h, double* w_out) {
 int sosrt_plan_fold(sosrt_t* h, int which, double* W_out) {
     if (!h || !W_out) return fail(SOSRT_E_INVALID, "null argument");
     if (!h->have_phase) return fail(SOSRT_E_STATE, "sosrt_set_phase has not been called");
-    const std::vector<double>& W = which ? h->Wr_h : h->Wa_h;
+    if (which < 0 || which > h->nsets) return fail(SOSRT_E_INVALID, "which=%d: 0 is W_atm, 1 + s the aerosol set s of %d", which, h->nsets);
+    std::vector<double>& W = which > 1 ? h->Wrx_h[which - 2] : (which ? h->Wr_h : h->Wa_h);
+    if (which >= 1 && h->wr_on_device && h->have_aer && W.empty()) {       // a fold made on the device: fetched when asked for
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        W.assign((size_t)h->D * h->D, 0.0);
+        HIPCHK(hipMemcpy2D(W.data(), h->D * sizeof(double), h->d_Wrsets + (size_t)(which - 1) * h->g.Dp * h->g.Wld,
+                           h->g.Wld * sizeof(double), h->D * sizeof(double), h->D, hipMemcpyDeviceToHost));
+    }
     if (W.empty()) return fail(SOSRT_E_STATE, "that phase matrix was not set");
     memcpy(W_out, W.data(), W.size() * sizeof(double));
     return 0;

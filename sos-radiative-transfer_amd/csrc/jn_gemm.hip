@@ -118,6 +118,13 @@ __global__ __launch_bounds__(256, GEMM_WPS) void k_jn_gemm(GemmArgs g) {
         // (the host lists a group for every 32 slab rows)
         gemm_tile<DENSE_SLAB_RT, false, false, SYM>(g, sA, sB, &s_any, st, bn0, ListRows{g.rows_slab, g.n_slab}, true,
                                                     g.Wmix + (size_t)g.slab_tile_group[st * DENSE_SLAB_ROWS / 32] * g.Dp * g.Wld);
+    } else if (g.slab_tile_group) {
+        // two passes with several aerosol sets: the slab rows are listed set by set, and the second pass of a tile reads the
+        // W_aer of its set (g.Wr: [sets][Dp][Wld])
+        const int st = tile - tiles_main;
+        GemmArgs gs = g;
+        gs.Wr = g.Wr + (size_t)g.slab_tile_group[st * DENSE_SLAB_ROWS / 32] * g.Dp * g.Wld;
+        gemm_tile<DENSE_SLAB_RT, true, false, SYM>(gs, sA, sB, &s_any, st, bn0, ListRows{g.rows_slab, g.n_slab}, true);
     } else {
         gemm_tile<DENSE_SLAB_RT, true, false, SYM>(g, sA, sB, &s_any, tile - tiles_main, bn0, ListRows{g.rows_slab, g.n_slab}, true);
     }
@@ -183,7 +190,11 @@ __device__ __forceinline__ void gemm_live_columns(const GemmArgs& g, double* sA,
         if (g.Wmix)      // SLAB = false: a single pass, over the column's combined matrix
             gemm_tile<TAIL_RT_SLAB, false, DEEP, SYM>(g, sA, sB, nullptr, tt, bn0, ColumnRows{b * g.L, iu, ns, ns, true},
                                                       false, g.Wmix + (size_t)g.mix_group[b] * g.Dp * g.Wld);
-        else
+        else if (g.mix_group) {                          // two passes, the second over the W_aer of the column's set
+            GemmArgs gs = g;
+            gs.Wr = g.Wr + (size_t)g.mix_group[b] * g.Dp * g.Wld;
+            gemm_tile<TAIL_RT_SLAB, true, DEEP, SYM>(gs, sA, sB, nullptr, tt, bn0, ColumnRows{b * g.L, iu, ns, ns, true}, false);
+        } else
             gemm_tile<TAIL_RT_SLAB, true, DEEP, SYM>(g, sA, sB, nullptr, tt, bn0, ColumnRows{b * g.L, iu, ns, ns, true}, false);
     } else {
         const int t2 = tt - ts;
@@ -256,7 +267,7 @@ __global__ __launch_bounds__(256, 1) void k_jn_gemm_lone(GemmArgs g) {
         fl = g.active[c];
         if (g.idx_up) {
             iu_c = g.idx_up[c]; id_c = g.idx_down[c];
-            if (g.Wmix) mg_c = g.mix_group[c];
+            if (g.mix_group) mg_c = g.mix_group[c];
         }
     }
     // ... and behind them, for a plain tile, the first two register blocks of its matrix: W_atm whatever the column
@@ -292,7 +303,7 @@ __global__ __launch_bounds__(256, 1) void k_jn_gemm_lone(GemmArgs g) {
             fl = g.active[c];
             if (g.idx_up) {
                 iu_c = g.idx_up[c]; id_c = g.idx_down[c];
-                if (g.Wmix) mg_c = g.mix_group[c];
+                if (g.mix_group) mg_c = g.mix_group[c];
             }
         }
     }
@@ -304,7 +315,11 @@ __global__ __launch_bounds__(256, 1) void k_jn_gemm_lone(GemmArgs g) {
     if (tt < ts) {
         if (tt * 16 >= ns) return;
         if (g.Wmix) gemm_tile_lone<false, false>(g, s_lone, tt, bn0, ColumnRows{b * g.L, iu, ns, ns, true}, f0, f1, g.Wmix + (size_t)mg * g.Dp * g.Wld);
-        else gemm_tile_lone<true, false>(g, s_lone, tt, bn0, ColumnRows{b * g.L, iu, ns, ns, true}, f0, f1);
+        else if (g.mix_group) {                          // two passes, the second over the W_aer of the column's set
+            GemmArgs gs = g;
+            gs.Wr = g.Wr + (size_t)mg * g.Dp * g.Wld;
+            gemm_tile_lone<true, false>(gs, s_lone, tt, bn0, ColumnRows{b * g.L, iu, ns, ns, true}, f0, f1);
+        } else gemm_tile_lone<true, false>(g, s_lone, tt, bn0, ColumnRows{b * g.L, iu, ns, ns, true}, f0, f1);
     } else {
         if ((tt - ts) * 16 >= g.L - ns) return;
         if (g.lr_rank >= 0) lowrank_tile<false>(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, tt - ts, 16, bn0, false);
@@ -344,17 +359,89 @@ void launch_gemm_tail(hipStream_t s, const GemmArgs& a, int cols, bool small_til
     }
 }
 
-// Wmix[g] = ca[g] W_atm + cr[g] W_aer for every distinct slab coefficient pair of the batch
+// Wmix[g] = ca[g] W_atm + cr[g] W_aer for every distinct slab coefficient pair of the batch; with several aerosol phase sets
+// (gset: the set of a group, Wr: [sets][n]) a group is a distinct (set, ca, cr) and reads the W_aer of its set -- the same
+// expression, so a group's matrix has the bits it has in a batch of its set alone
 __global__ void k_wmix(size_t n, int ngroups, const double* __restrict__ Wa, const double* __restrict__ Wr,
-                       const double* __restrict__ ca, const double* __restrict__ cr, double* __restrict__ Wmix) {
+                       const double* __restrict__ ca, const double* __restrict__ cr, double* __restrict__ Wmix,
+                       const int* __restrict__ gset) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (gset) {
+        const double a = Wa[i];
+        for (int gq = 0; gq < ngroups; ++gq) {
+            const double r = Wr[(size_t)gset[gq] * n + i];
+            Wmix[(size_t)gq * n + i] = ca[gq] * a + cr[gq] * r;
+        }
+        return;
+    }
     const double a = Wa[i], r = Wr[i];
     for (int gq = 0; gq < ngroups; ++gq) Wmix[(size_t)gq * n + i] = ca[gq] * a + cr[gq] * r;
 }
 void launch_wmix(hipStream_t s, size_t n, int ngroups, const double* Wa, const double* Wr, const double* ca, const double* cr,
-                 double* Wmix) {
-    hipLaunchKernelGGL(k_wmix, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, ngroups, Wa, Wr, ca, cr, Wmix);
+                 double* Wmix, const int* gset) {
+    hipLaunchKernelGGL(k_wmix, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, ngroups, Wa, Wr, ca, cr, Wmix, gset);
+}
+
+// The fold of sosrt_set_phase on the device: W[q][k][m] = w_k P[q][m][D-1-k] for S matrices P [S][D][D] -> W [S][Dp][Wld]
+// (the padding is zeroed by the caller).  One product per element, the host fold's (plan.cpp, Plan::fold): the same bits.
+// 32 x 32 tiles through LDS, so that the transposed read and the write are both along rows.
+__global__ __launch_bounds__(256) void k_fold_sets(int D, int Wld, size_t per, const double* __restrict__ w,
+                                                   const double* __restrict__ P, double* __restrict__ W) {
+    __shared__ double tile[32][33];
+    const int q = blockIdx.z, k0 = blockIdx.y * 32, m0 = blockIdx.x * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const double* Pq = P + (size_t)q * D * D;
+    for (int j = ty; j < 32; j += 8) {                  // tile[j][i] = P[m0 + j][D-1-(k0 + i)]
+        const int m = m0 + j, k = k0 + tx;
+        if (m < D && k < D) tile[j][tx] = Pq[(size_t)m * D + (D - 1 - k)];
+    }
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8) {                  // W[k0 + i][m0 + tx] = w[k0 + i] * tile[tx][i]
+        const int k = k0 + i, m = m0 + tx;
+        if (k < D && m < D) W[(size_t)q * per + (size_t)k * Wld + m] = w[k] * tile[tx][i];
+    }
+}
+void launch_fold_sets(hipStream_t s, int S, int D, int Wld, size_t per, const double* w, const double* P, double* W) {
+    const unsigned nt = (unsigned)((D + 31) / 32);
+    hipLaunchKernelGGL(k_fold_sets, dim3(nt, nt, (unsigned)S), dim3(256), 0, s, D, Wld, per, w, P, W);
+}
+
+// The flip-asymmetry measure of sosrt_set_phase on folded device matrices W [S][Dp][Wld]: per matrix and per block of the grid
+// out[q][blk] = { max |W[k][m]|, max |W[k][m] - W[D-1-k][D-1-m]| }, NaN in both when the block met a NaN (fmax drops NaN
+// operands, hence the flag).  Maxima and one division on the host: the host loop's value for NaN-free matrices.
+__global__ __launch_bounds__(256) void k_fold_asymmetry(int D, int Wld, size_t per, const double* __restrict__ W,
+                                                        double* __restrict__ out) {
+    __shared__ double s_w[4], s_a[4];
+    __shared__ int s_nan[4];
+    const int q = blockIdx.y, tid = threadIdx.x;
+    const double* Wq = W + (size_t)q * per;
+    double wmax = 0, amax = 0;
+    int nan = 0;
+    const size_t n = (size_t)D * D;
+    for (size_t e = (size_t)blockIdx.x * 256 + tid; e < n; e += (size_t)gridDim.x * 256) {
+        const int k = (int)(e / D), m = (int)(e % D);
+        const double x = Wq[(size_t)k * Wld + m], y = Wq[(size_t)(D - 1 - k) * Wld + (D - 1 - m)];
+        const double ax = fabs(x), d = fabs(x - y);
+        nan |= (ax != ax) || (d != d);
+        wmax = fmax(wmax, ax); amax = fmax(amax, d);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        wmax = fmax(wmax, __shfl_xor(wmax, o, 64)); amax = fmax(amax, __shfl_xor(amax, o, 64));
+        nan |= __shfl_xor(nan, o, 64);
+    }
+    if ((tid & 63) == 0) { s_w[tid >> 6] = wmax; s_a[tid >> 6] = amax; s_nan[tid >> 6] = nan; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int i = 1; i < 4; ++i) { wmax = fmax(wmax, s_w[i]); amax = fmax(amax, s_a[i]); nan |= s_nan[i]; }
+        double* o = out + ((size_t)q * gridDim.x + blockIdx.x) * 2;
+        o[0] = nan ? __builtin_nan("") : wmax;
+        o[1] = nan ? __builtin_nan("") : amax;
+    }
+}
+void launch_fold_asymmetry(hipStream_t s, int S, int nblk, int D, int Wld, size_t per, const double* W, double* out) {
+    hipLaunchKernelGGL(k_fold_asymmetry, dim3((unsigned)nblk, (unsigned)S), dim3(256), 0, s, D, Wld, per, W, out);
 }
 
 void launch_gemm(hipStream_t s, const GemmArgs& a) {

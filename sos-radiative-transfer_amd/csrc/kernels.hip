@@ -182,10 +182,13 @@ void launch_prepare(hipStream_t s, const Grid& g, int B, int geom, int surface, 
 // attenuated last row of the previous one ("scatt_before", spec:147,176,240,270).
 // ------------------------------------------------------------------------------------------
 constexpr double kFactorMax = 1e150;    // largest zone constant the one-exponential factorisation of k_first_order is used with
+// ZP0: the zone table carries aerosol sets -- P0r_all is [B][p0z][D] and zone z of a column reads its own row (the other
+// instantiation is the kernel as it was: one row per column, read once)
+template <bool ZP0>
 __global__ void k_first_order(Grid g, const double* __restrict__ tau_all, const double* __restrict__ P0a_all,
                               const double* __restrict__ P0r_all, const ColDesc* __restrict__ desc,
                               double* __restrict__ I1_all, double* __restrict__ I_all, double* __restrict__ saved,
-                              size_t saved_col_stride, Conv cv, int do_conv) {
+                              size_t saved_col_stride, Conv cv, int do_conv, int p0z) {
     // blockIdx.y = 0: the downward half of the field, 1: the upward half and the loop test.  The upward
     // half needs the downward radiance at the surface (spec:211); it evaluates that one row itself (the
     // same closed form, one row per zone) instead of waiting for the other workgroup.
@@ -206,7 +209,7 @@ __global__ void k_first_order(Grid g, const double* __restrict__ tau_all, const 
     if (tid == 0) d = desc[b];
     const double* tau = tau_all + (size_t)b * L;
     const double* P0a = P0a_all + (size_t)b * D;
-    const double* P0r = P0r_all ? P0r_all + (size_t)b * D : P0a;
+    const double* P0r = P0r_all ? P0r_all + (size_t)b * (ZP0 ? p0z : 1) * D : P0a;
     double* I1 = I1_all + (size_t)b * L * D;
     double* Iacc = I_all ? I_all + (size_t)b * L * D : nullptr;
     double* sv = saved ? saved + (size_t)b * saved_col_stride : nullptr;
@@ -238,13 +241,15 @@ __global__ void k_first_order(Grid g, const double* __restrict__ tau_all, const 
         const int mm = valid ? m : 0, mir = 2 * N - 1 - mm;
         const double mu = g.mu[mm];
         const double qa = d.wa * P0a[mm] * c4pi, qam = d.wa * P0a[mir] * c4pi;
-        const double pa = P0a[mm], pam = P0a[mir], pr = P0r[mm], prm = P0r[mir];
+        const double pa = P0a[mm], pam = P0a[mir];
+        double pr = P0r[mm], prm = P0r[mir];
         const bool near = fabs(mu + mu0) < 0.0001;          // spec:111
         const bool node = m > N - 2;                         // the mu = 0- node (spec:128-131)
         const double gd = mu0 / (mu0 + mu), gs = mu0 / (mu0 - mu);
         const double rmu = 1.0 / mu;
         double Ib = 0, vlast = 0;
         for (int z = 0; z < d.nz; ++z) {
+            if (ZP0) { pr = P0r[(size_t)z * D + mm]; prm = P0r[(size_t)z * D + mir]; }
             const double qx = (d.wa * pa * d.fa[z] + d.wr[z] * pr * d.fr[z]) * c4pi;       // spec:149
             const double qxm = (d.wa * pam * d.fa[z] + d.wr[z] * prm * d.fr[z]) * c4pi;
             const double q = d.mix[z] ? qx : qa, qm = d.mix[z] ? qxm : qam;
@@ -304,7 +309,8 @@ __global__ void k_first_order(Grid g, const double* __restrict__ tau_all, const 
         const int j = valid ? tid : 0, m = N + j, mir = N - 1 - j;
         const double mu = g.mu[m];
         const double qa = d.wa * P0a[m] * c4pi, qam = d.wa * P0a[mir] * c4pi;
-        const double pa = P0a[m], pam = P0a[mir], pr = P0r[m], prm = P0r[mir];
+        const double pa = P0a[m], pam = P0a[mir];
+        double pr = P0r[m], prm = P0r[mir];
         const bool near = fabs(mu - mu0) < 0.0001;           // spec:204
         const bool node = j < 1;                             // the mu = 0+ node (spec:221-224)
         const double gd = mu0 / (mu0 + mu), gs = mu0 / (mu0 - mu);
@@ -313,6 +319,7 @@ __global__ void k_first_order(Grid g, const double* __restrict__ tau_all, const 
         double vlast = 0;
         for (int z = d.nz - 1; z >= 0; --z) {
             const bool bottom = z == d.nz - 1;
+            if (ZP0) { pr = P0r[(size_t)z * D + m]; prm = P0r[(size_t)z * D + mir]; }
             const double qx = (d.wa * pa * d.fa[z] + d.wr[z] * pr * d.fr[z]) * c4pi;       // spec:242
             const double qxm = (d.wa * pam * d.fa[z] + d.wr[z] * prm * d.fr[z]) * c4pi;
             const double q = d.mix[z] ? qx : qa, qm = d.mix[z] ? qxm : qam;
@@ -583,7 +590,7 @@ void launch_first_order_readme(hipStream_t s, const Grid& g, const double* w, in
 
 void launch_first_order(hipStream_t s, const Grid& g, int B, const double* tau, const double* P0a, const double* P0r,
                         const ColDesc* desc, double* I1_out, double* I_out, double* saved, size_t saved_col_stride,
-                        Conv cv, int do_conv) {
+                        Conv cv, int do_conv, int p0r_zones) {
     const int nt = round64(g.N);
     const size_t shm = (size_t)(3 * g.L + nt + nt / 64 + 4) * sizeof(double);
     // row blocks per half column: enough workgroups to give every SIMD several waves (the rows are chains of fp64
@@ -591,8 +598,12 @@ void launch_first_order(hipStream_t s, const Grid& g, int B, const double* tau, 
     int nblk = (4096 + 2 * B - 1) / (2 * B);
     nblk = nblk < 1 ? 1 : (nblk > 8 ? 8 : nblk);
     while (nblk > 1 && g.L / nblk < 24) --nblk;
-    hipLaunchKernelGGL(k_first_order, dim3(B, 2, nblk), dim3(nt), shm, s, g, tau, P0a, P0r, desc, I1_out, I_out, saved,
-                       saved_col_stride, cv, do_conv);
+    if (P0r && p0r_zones > 0)
+        hipLaunchKernelGGL(k_first_order<true>, dim3(B, 2, nblk), dim3(nt), shm, s, g, tau, P0a, P0r, desc, I1_out, I_out, saved,
+                           saved_col_stride, cv, do_conv, p0r_zones);
+    else
+        hipLaunchKernelGGL(k_first_order<false>, dim3(B, 2, nblk), dim3(nt), shm, s, g, tau, P0a, P0r, desc, I1_out, I_out, saved,
+                           saved_col_stride, cv, do_conv, 0);
 }
 
 // ------------------------------------------------------------------------------------------

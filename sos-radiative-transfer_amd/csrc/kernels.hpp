@@ -170,7 +170,7 @@ void launch_first_order_readme(hipStream_t s, const Grid& g, const double* w, in
                                size_t saved_col_stride, Conv cv, int do_conv);
 void launch_first_order(hipStream_t s, const Grid& g, int B, const double* tau, const double* P0a, const double* P0r,
                         const ColDesc* desc, double* I1_out, double* I_out, double* saved, size_t saved_col_stride,
-                        Conv cv, int do_conv);
+                        Conv cv, int do_conv, int p0r_zones = 0 /* > 0: P0r is [B][p0r_zones][D], zone z of a column reads its row z */);
 // Jn = diag(ca) A Wa for the rows of `rows_main`, and diag(ca) A Wa + diag(cr) A Wr for the rows of
 // `rows_slab` (spec:321), in one launch.  Row lists hold global row ids; rows_main == nullptr means
 // the identity list 0..n_main-1.
@@ -268,7 +268,11 @@ hipError_t launch_order_loop(hipStream_t s, int grid, bool split, const OrderLoo
 void launch_gemm_f32(hipStream_t s, const GemmArgs& a, const float* Wa32, const float* Wmix32);
 void launch_to_float(hipStream_t s, size_t n, const double* src, float* dst);
 void launch_wmix(hipStream_t s, size_t n, int ngroups, const double* Wa, const double* Wr, const double* ca, const double* cr,
-                 double* Wmix);
+                 double* Wmix, const int* gset = nullptr /* [ngroups] aerosol set of a group: Wr is then [sets][n] */);
+// device fold of S phase matrices P [S][D][D] into W [S][Dp][Wld] (W[k][m] = w_k P[m][D-1-k], the host fold's bits), and the
+// partial maxima {max |W|, max |W - flip W|} of its flip-asymmetry measure, out [S][nblk][2]
+void launch_fold_sets(hipStream_t s, int S, int D, int Wld, size_t per, const double* w, const double* P, double* W);
+void launch_fold_asymmetry(hipStream_t s, int S, int nblk, int D, int Wld, size_t per, const double* W, double* out);
 // the flip-symmetric folding [k][S | A] of `nmat` contraction matrices [Dp][Wld]
 void launch_symfold(hipStream_t s, int nmat, int N, int D, int Dp, int Wld, const double* W, double* SA);
 // some columns have converged (at most `cols` are live, an upper bound): workgroups only for live

@@ -21,6 +21,7 @@ CONTRACT_F64, CONTRACT_F32, CONTRACT_F64_FULL, CONTRACT_F64_DENSE = 0, 1, 2, 3
 FIRST_ORDER_CODED, FIRST_ORDER_README = 0, 1
 PHASE_ISO, PHASE_RAYLEIGH, PHASE_HG, PHASE_TABLE = 0, 1, 2, 3
 MAX_MODES = 64
+MAX_PHASE_SETS = 64
 
 _dp = POINTER(c_double)
 _ip = POINTER(c_int)
@@ -45,6 +46,11 @@ SIGNATURES = {
     "sosrt_set_first_order": (c_int, [c_void_p, c_int]),
     "sosrt_set_grid": (c_int, [c_void_p, c_void_p]),
     "sosrt_set_phase": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "sosrt_set_phase_sets": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "sosrt_set_phase_sets_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "sosrt_phase_matrix_dev": (c_int, [c_void_p, c_int, c_double, c_void_p]),
+    "sosrt_set_aerosol_sets": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "sosrt_phase_sets_info": (c_int, [c_void_p, _ip]),
     "sosrt_set_columns": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 9),
     "sosrt_set_columns_zones": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 10),
     "sosrt_first_order": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from .inputs import direction_grid, slab_indices, tau_profile
-from .solver import Solver
+from .solver import DevicePhaseSets, Solver
 
 # the literals of SOS_Aer_main_specular.py:23-96
 DEFAULTS = dict(
@@ -97,7 +97,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   mie_atm=None, mie_aer=None,
                   P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular", tol=1e-4, max_orders=256,
                   save_orders=False, device=0, devices=None, raise_on_error=True, first_order="coded", azimuths=None,
-                  n_modes=None, nphi_modes=None, levels=(0, -1)) -> BatchResult:
+                  n_modes=None, nphi_modes=None, levels=(0, -1), aer_set=None) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -108,11 +108,27 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     GPUs of the node, one worker process each, and gathers the fields (sosrt.dist.solve_on_devices; per-order
     fields are not gathered).
 
+    `aer_set` [B] (integers): SEVERAL AEROSOLS IN ONE BATCH, column b takes aerosol aer_set[b].  Either `P_aer` is a stack
+    [S, 2N, 2N] with `P0_aer` [B, 2N] (each column the P0 of its own aerosol), or `aer_phase_fun` (and, where they differ,
+    `g_aer` / `mie_aer`) is a list of S names (numbers / dicts) and the matrices and every column's P0 are built on the device.
+    (A `solver.DevicePhaseSets` in `P_aer` names a stack that is already on the device.)
+    Column b has the bits it has in a batch of its own aerosol alone (Solver.set_phase_sets / set_aerosol_sets).  Not with
+    `azimuths`, `first_order='readme'` or several `devices`.
+
     `azimuths` (radians, array): also the azimuth-resolved radiance I(phi) at the rows `levels` (default TOA and surface),
     BatchResult.I_azimuth [B, len(levels), 2N, len(azimuths)], from the Fourier modes m = 0 .. `n_modes` (default 16) of the
     phase functions (`azimuth_modes`; modes m >= 1 built on `nphi_modes` azimuth nodes, default max(25, 2 n_modes + 1)).  phi
     follows the reference's ring: phi = 0 with an upward mu = mu0 is exact back-scatter.  I, n and status are those of the
     plain call, bit for bit.  Needs named phase functions (not arrays), the specular surface and a single device."""
+    if aer_set is not None:
+        if azimuths is not None:
+            raise ValueError("azimuths are not available with aer_set (the mode driver swaps the handle's one pair of matrices per mode)")
+        if first_order != "coded":
+            raise ValueError("first_order='readme' is not available with aer_set (it reads one aerosol matrix)")
+        if devices is not None and len(devices) > 1:
+            raise ValueError("devices=[...] is not available with aer_set: solve each shard with SOS_Aer_batch(device=...)")
+    elif np.ndim(P_aer) == 3 or isinstance(aer_phase_fun, (list, tuple)):
+        raise ValueError("several aerosols (a stack P_aer [S, 2N, 2N] or a list of names) need aer_set [B]")
     if azimuths is not None:
         M, nphi, lev = _azimuth_args(azimuths, n_modes, nphi_modes, levels, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface,
                                      devices, first_order)
@@ -134,12 +150,15 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         device = int(devices[0])
     s, tau, P0a, P0r, mu, iu, idn, N = _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
                                                       nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm,
-                                                      mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device)
-    s.set_first_order(first_order)
+                                                      mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device,
+                                                      aer_set=aer_set)
     try:
+        s.set_first_order(first_order)
         r = s.solve(tau, P0a, P0r, tol=tol, save_orders=save_orders)
     finally:
         s.set_first_order("coded")                           # (the solver is cached)
+        if aer_set is not None:
+            _columns_to_set0(s, tau.shape[0])
     if raise_on_error:
         _raise_status(r.status, N)
     out = BatchResult(I=r.I, n=r.n, status=r.status, tau=tau, mu=mu, idx_up=iu, idx_down=idn, I_saved=r.I_saved)
@@ -150,6 +169,21 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         if raise_on_error:
             _raise_status(out.mode_status, N)
     return out
+
+
+def _columns_to_set0(s, B):
+    """A cached handle's columns back on aerosol set 0, from a `finally`: an error here must not hide the one in flight."""
+    try:
+        s.set_aerosol_sets(np.zeros(B, dtype=np.int32))
+    except Exception:
+        pass
+
+
+def _same_aerosol(a, b):
+    """Two (name, g, mie dict or None) specifications name the same aerosol (values may be NumPy scalars or arrays)."""
+    if a[0] != b[0] or not np.array_equal(a[1], b[1]) or (a[2] is None) != (b[2] is None):
+        return False
+    return a[2] is None or (set(a[2]) == set(b[2]) and all(np.array_equal(a[2][k], b[2][k]) for k in a[2]))
 
 
 def _spectrum_args(wavelengths, tauStar_aer, angstrom, lambda_ref, aer, alb_aer, tauStar_atm_ref):
@@ -190,7 +224,8 @@ def _spectrum_args(wavelengths, tauStar_aer, angstrom, lambda_ref, aer, alb_aer,
 
 def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=None, lambda_ref=0.550, tauStar_atm_ref=0.124,
                      alb_aer="mie", alb_atm=1.0, nb_radius=100, r_min=0.01, r_max=10.0, ntab=6001, indx_convention="absorbing",
-                     atm_phase_fun="rayleigh", g_atm=0.0, nb_layers=200, nb_angles=128, max_orders=256, device=0, **batch_kw):
+                     atm_phase_fun="rayleigh", g_atm=0.0, nb_layers=200, nb_angles=128, max_orders=256, device=0,
+                     one_batch=False, **batch_kw):
     """A spectrum of batches: for every wavelength (micrometres) the columns (mu0, grd_alb) of `SOS_Aer_batch` with a log-normal
     Mie aerosol `aer` = dict(m=, r_m=, sig=) (each a scalar or one value per wavelength).  The molecular optical depth is
     tauStar_atm_ref (lambda_ref / wl)^4; the aerosol's is `tauStar_aer`: a function of the wavelength, one value per wavelength,
@@ -198,6 +233,10 @@ def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=No
     (default) takes every ensemble's own single-scattering albedo.  All ensembles are tabulated in ONE call of the device's
     Mie kernels (`Solver.mie_ensembles_device`); per wavelength the table is handed to the azimuth builders on the device
     (`Solver.set_phase_table_dev`) and the columns go through `SOS_Aer_batch` (further keywords are passed on).
+    `one_batch=True`: all W x C columns in ONE solve, the wavelength as the aerosol set of its columns (at most 64 wavelengths;
+    `Solver.set_phase_sets`), instead of W small solves in the latency regime; the same list of results, column for column the
+    bits of the loop while both take the single pass.  The matrices stay on the device: `Solver.phase_matrix_device` writes
+    them where `Solver.set_phase_sets_device` folds them.
     Returns (list of BatchResult, one per wavelength; bulk [W, 3]: albedo, asymmetry parameter, mean extinction cross-section)."""
     import torch
     from . import mie as _mie
@@ -208,7 +247,10 @@ def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=No
     m = np.array([_mie.refractive_index(v, indx_convention) for v in m])
     mu0v, _ = np.broadcast_arrays(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), np.atleast_1d(np.asarray(grd_alb, dtype=np.float64)))
     L, N, W = int(nb_layers), int(nb_angles), wl.size
-    s = get_solver(L, N, mu0v.shape[0], max_orders, device)
+    C = mu0v.shape[0]
+    if one_batch and W > _lib.MAX_PHASE_SETS:
+        raise ValueError("one_batch=True takes at most %d wavelengths (got %d)" % (_lib.MAX_PHASE_SETS, W))
+    s = get_solver(L, N, W * C if one_batch else C, max_orders, device)
     mu = direction_grid(N)
     if not s.same_grid(mu):
         s.set_grid(mu)
@@ -221,6 +263,24 @@ def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=No
         s.synchronize()
         bulk = d_bulk.cpu().numpy()
         omega = bulk[:, 0] if isinstance(alb_aer, str) else np.broadcast_to(np.asarray(alb_aer, dtype=np.float64), wl.shape)
+        if one_batch:
+            P0r = np.empty((W, C, 2 * N))
+            d_P = torch.empty((W, 2 * N, 2 * N), dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            for w in range(W):
+                s.set_phase_table_dev(d_p[w].data_ptr(), int(ntab))
+                s.phase_matrix_device("table", d_P[w].data_ptr())
+                P0r[w] = s.phase_p0("table", mu0v)
+            P_sets = DevicePhaseSets(d_P.data_ptr(), W, keep=d_P)
+            rep_w = lambda v: np.repeat(np.asarray(v, dtype=np.float64), C)
+            tile_c = lambda v: np.tile(np.broadcast_to(np.atleast_1d(np.asarray(v, dtype=np.float64)), (C,)), W)
+            r = SOS_Aer_batch(tile_c(mu0), rep_w(t_aer), tile_c(grd_alb), tauStar_atm=rep_w(t_atm), alb_atm=alb_atm,
+                              alb_aer=rep_w(omega), nb_layers=L, nb_angles=N, atm_phase_fun=atm_phase_fun, g_atm=g_atm,
+                              P_aer=P_sets, P0_aer=P0r.reshape(W * C, 2 * N), aer_set=np.repeat(np.arange(W, dtype=np.int32), C),
+                              max_orders=max_orders, device=device, **batch_kw)
+            cut = lambda a, w: None if a is None else a[w * C:(w + 1) * C]
+            return [BatchResult(I=cut(r.I, w), n=cut(r.n, w), status=cut(r.status, w), tau=cut(r.tau, w), mu=r.mu, idx_up=r.idx_up,
+                                idx_down=r.idx_down, I_saved=cut(r.I_saved, w)) for w in range(W)], bulk
         out = []
         for w in range(W):
             s.set_phase_table_dev(d_p[w].data_ptr(), int(ntab))
@@ -317,7 +377,7 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
 
 def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down, nb_layers, nb_angles,
                    atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm, mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface,
-                   max_orders, device, p0_on_host=True):
+                   max_orders, device, p0_on_host=True, aer_set=None):
     """Everything before the order loop (spec:23-96): optical-depth grids, direction grid, phase matrices folded into the
     handle, per-column scalars.  Returns the solver and the per-column inputs."""
     mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer = np.broadcast_arrays(
@@ -338,6 +398,49 @@ def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0,
     if P_atm is None or P0_atm is None:
         P0a, Pm = device_phase(s, atm_phase_fun, mu0, g_atm, mie_atm, matrix=P_atm is None)
         P_atm = Pm if P_atm is None else P_atm
+    if aer_set is not None:
+        sets = np.ascontiguousarray(aer_set)
+        if sets.shape != (B,) or not np.issubdtype(sets.dtype, np.integer):
+            raise ValueError("aer_set must be %d integers (one aerosol per column)" % B)
+        on_device = isinstance(P_aer, DevicePhaseSets)
+        if on_device:
+            if P0_aer is None or np.shape(P0_aer) != (B, 2 * N):
+                raise ValueError("aer_set with matrices on the device needs P0_aer [B, 2N] (each column the P0 of its aerosol)")
+        elif P_aer is not None:
+            P_aer = np.ascontiguousarray(P_aer, dtype=np.float64)
+            if P_aer.ndim != 3 or P0_aer is None or np.shape(P0_aer) != (B, 2 * N):
+                raise ValueError("aer_set with arrays needs P_aer [S, 2N, 2N] and P0_aer [B, 2N] (each column the P0 of its aerosol)")
+        else:
+            if not isinstance(aer_phase_fun, (list, tuple)):
+                raise ValueError("aer_set needs a list of names in aer_phase_fun (or a stack P_aer [S, 2N, 2N] with P0_aer)")
+            S = len(aer_phase_fun)
+            per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * S
+            gs, ms = per(g_aer), per(mie_aer)
+            if len(gs) != S or len(ms) != S:
+                raise ValueError("g_aer and mie_aer must be single values or lists as long as aer_phase_fun")
+            if sets.size and (sets.min() < 0 or sets.max() >= S):
+                raise ValueError("aer_set names aerosol %d, aer_phase_fun has %d" % (int(sets.max() if sets.max() >= S else sets.min()), S))
+            built, P0r = [], np.zeros((B, 2 * N))
+            for k in range(S):
+                # (an aerosol that no column uses still gets its matrix: set indices keep their meaning; its P0 row is not needed)
+                cols = np.flatnonzero(sets == k)
+                p0, Pm = device_phase(s, aer_phase_fun[k], mu0[cols] if cols.size else mu0[:1], gs[k], ms[k])
+                if cols.size:
+                    P0r[cols] = p0
+                built.append(Pm)
+            P_aer = np.stack(built)
+        if P0_aer is not None:
+            P0r = np.ascontiguousarray(P0_aer, dtype=np.float64)
+        if P0_atm is not None:
+            P0a = np.ascontiguousarray(np.broadcast_to(P0_atm, (B, 2 * N)))
+        if on_device:
+            s.set_phase_sets_device(P_atm, P_aer.address, P_aer.S)
+        elif not s.same_phase(P_atm, P_aer):
+            s.set_phase_sets(P_atm, P_aer)
+        s.set_columns(np.full(B, iu), np.full(B, idn), mu0, grd_alb, alb_atm, alb_aer,
+                      tauStar_atm / L, tauStar_aer / (idn + 1 - iu), tauStar_atm + tauStar_aer, surface=surface)
+        s.set_aerosol_sets(sets.astype(np.int32))
+        return s, tau, P0a, P0r, mu, iu, idn, N
     if P_aer is None or P0_aer is None:
         P0r, Pm = device_phase(s, aer_phase_fun, mu0, g_aer, mie_aer, matrix=P_aer is None)
         P_aer = Pm if P_aer is None else P_aer
@@ -390,7 +493,11 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
     """Columns with SEVERAL aerosol layers (the reference has one): `slabs` = [(z_up, z_down, tauStar_aer,
     alb_aer), ...] from the top down, shared by the B columns of the arrays `mu0`, `grd_alb`.  Every formula of the path is
     evaluated per zone as the reference writes it for its three zones; one layer gives `SOS_Aer_batch`'s result bit for
-    bit.  All layers share the aerosol phase function.  `idx_up` / `idx_down` of the result are those of the first layer."""
+    bit.  A slab may name ITS OWN AEROSOL in a fifth entry -- a phase-function name ('hg' with `g_aer`, 'eva', 'wildfire', ...)
+    or a dict(name=, g=, and the keywords of `mie_aer`) -- e.g. slabs=[(25, 17, 0.12, 0.97, "eva"), (15, 14, 0.0075, 0.9,
+    "wildfire")]; slabs without one take (`aer_phase_fun`, `g_aer`, `mie_aer`), and when no slab has one all layers share
+    that phase function exactly as before.  `P_aer` cannot be combined with a fifth entry.  `idx_up` / `idx_down` of the
+    result are those of the first layer."""
     from .inputs import tau_profile_slabs
     mu0, grd_alb = np.broadcast_arrays(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), np.atleast_1d(np.asarray(grd_alb, dtype=np.float64)))
     B, L, N = mu0.shape[0], int(nb_layers), int(nb_angles)
@@ -404,13 +511,47 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
     # P0(mu, mu0) per column, and the matrices that were not handed in, on the device
     P0a, Pm = device_phase(s, atm_phase_fun, mu0, g_atm, mie_atm, matrix=P_atm is None)
     P_atm = Pm if P_atm is None else P_atm
-    P0r, Pm = device_phase(s, aer_phase_fun, mu0, g_aer, mie_aer, matrix=P_aer is None)
-    P_aer = Pm if P_aer is None else P_aer
-    if not s.same_phase(P_atm, P_aer):
-        s.set_phase(P_atm, P_aer)
+    own = any(len(x) > 4 for x in slabs)
+    if own:
+        if P_aer is not None:
+            raise ValueError("P_aer cannot be combined with slabs that name their own aerosol")
+        # the distinct aerosols of the slabs, in order of appearance: one phase set each
+        def spec(x):
+            a = x[4] if len(x) > 4 else None
+            if a is None:
+                return (aer_phase_fun, g_aer, mie_aer)
+            if isinstance(a, str):
+                return (a, g_aer, None)
+            a = dict(a)
+            return (a.pop("name", aer_phase_fun), a.pop("g", g_aer), a or None)
+        specs, zset = [], np.zeros(len(r0), dtype=np.int32)
+        for j, x in enumerate(slabs):
+            sp = spec(x)
+            k = next((i for i, y in enumerate(specs) if _same_aerosol(y, sp)), len(specs))
+            if k == len(specs):
+                specs.append(sp)
+            zset[1 + 2 * j] = k
+        built = [device_phase(s, name, mu0, g, mie) for name, g, mie in specs]
+        P0r = np.zeros((B, len(r0), 2 * N))
+        for j in range(len(slabs)):
+            P0r[:, 1 + 2 * j] = built[zset[1 + 2 * j]][0]
+        P_sets = np.stack([b[1] for b in built])
+        if not s.same_phase(P_atm, P_sets):
+            s.set_phase_sets(P_atm, P_sets)
+    else:
+        P0r, Pm = device_phase(s, aer_phase_fun, mu0, g_aer, mie_aer, matrix=P_aer is None)
+        P_aer = Pm if P_aer is None else P_aer
+        if not s.same_phase(P_atm, P_aer):
+            s.set_phase(P_atm, P_aer)
     s.set_columns_zones(np.tile(r0, (B, 1)), mix, mu0, grd_alb, alb_atm, tauStar_atm / L, zwr, dta,
                         tauStar_atm + sum(x[2] for x in slabs), surface=surface)
-    r = s.solve(np.tile(tau, (B, 1)), P0a, P0r, tol=tol)
+    try:
+        if own:
+            s.set_aerosol_sets(np.tile(zset, (B, 1)))
+        r = s.solve(np.tile(tau, (B, 1)), P0a, P0r, tol=tol)
+    finally:
+        if own:                                              # (the solver is cached: its columns go back to set 0)
+            _columns_to_set0(s, B)
     if raise_on_error:
         _raise_status(r.status, N)
     return BatchResult(I=r.I, n=r.n, status=r.status, tau=np.tile(tau, (B, 1)), mu=mu, idx_up=int(r0[1]), idx_down=int(r0[2]) - 1)

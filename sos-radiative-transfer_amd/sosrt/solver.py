@@ -36,6 +36,15 @@ def _vec(x, B, name):
 
 
 @dataclass
+class DevicePhaseSets:
+    """S aerosol phase matrices resident on the device ([S, 2N, 2N] float64 at `address`), for `SOS_Aer_batch(P_aer=...)`
+    with `aer_set`: they are handed to `Solver.set_phase_sets_device`.  `keep` holds whatever owns the memory."""
+    address: int
+    S: int
+    keep: object = None
+
+
+@dataclass
 class SolveResult:
     I: np.ndarray                  # [B, L, 2N]
     n: np.ndarray                  # [B] final order count (spec:307-310)
@@ -56,6 +65,7 @@ class Solver:
         self.order_budget = self.max_orders
         self.mu = None
         self._P = (None, None)
+        self._p0_zones = 0          # > 0: P0_aer is [B, _p0_zones, 2N] (set_aerosol_sets with a zone table)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -145,6 +155,44 @@ class Solver:
         check(lib().sosrt_set_phase(self._h, _ptr(Pa), _ptr(Pr)))
         self._P = (Pa.copy(), None if Pr is None else Pr.copy())
 
+    def set_phase_sets(self, P_atm, P_aer_sets):
+        """Several aerosol phase matrices `P_aer_sets` [S, 2N, 2N] beside one P_atm; `set_aerosol_sets` says which one the
+        aerosol of a column (or of an aerosol zone) reads -- set 0 until then.  S = 1 is `set_phase`, bit for bit."""
+        Pa = _f64(P_atm, (self.D, self.D), "P_atm")
+        Pr = np.ascontiguousarray(P_aer_sets, dtype=np.float64)
+        if Pr.ndim != 3 or Pr.shape[1:] != (self.D, self.D):
+            raise ValueError("P_aer_sets has shape %s, expected (S, %d, %d)" % (Pr.shape, self.D, self.D))
+        check(lib().sosrt_set_phase_sets(self._h, _ptr(Pa), int(Pr.shape[0]), _ptr(Pr)))
+        self._P = (Pa.copy(), Pr.copy())
+
+    def set_phase_sets_device(self, P_atm, d_P_aer: int, S: int):
+        """`set_phase_sets` with the S aerosol matrices in device memory (address of [S, 2N, 2N] float64, e.g. filled by
+        `phase_matrix_device`): folded and measured by kernels in the handle's stream order, no trip through the host."""
+        Pa = _f64(P_atm, (self.D, self.D), "P_atm")
+        check(lib().sosrt_set_phase_sets_dev(self._h, _ptr(Pa), int(S), ctypes.c_void_p(d_P_aer) if d_P_aer else None))
+        self._P = (None, None)          # (what the device buffer held is not known here: the next same_phase says no)
+
+    def set_aerosol_sets(self, sets):
+        """Aerosol set per column (`sets` [B], after `set_columns`) or per zone of the zone table (`sets` [B, nzmax] with the
+        nzmax of `set_columns_zones`; entries of clear zones are ignored).  With a [B, nzmax] table, P0_aer of `first_order`
+        and `solve` is [B, nzmax, 2N]: aerosol zone z of column b reads row (b, z).  `set_columns*` puts every column back
+        on set 0."""
+        z = np.ascontiguousarray(sets, dtype=np.int32)
+        if z.ndim == 1:
+            z = z.reshape(-1, 1)
+        if z.ndim != 2 or z.shape[0] != self.B:
+            raise ValueError("sets has shape %s, expected (%d,) or (%d, nzmax)" % (np.shape(sets), self.B, self.B))
+        check(lib().sosrt_set_aerosol_sets(self._h, int(z.shape[0]), int(z.shape[1]), _ptr(z)))
+        self._p0_zones = int(z.shape[1]) if z.shape[1] > 1 else 0
+
+    def phase_sets_info(self):
+        """{'sets': phase sets on the handle, 'groups': combined-matrix groups of the current columns (0: none, or two
+        passes), 'single_pass': whether their slab rows take the single pass, 'group_cap': groups the cache holds with sets
+        in use}"""
+        out = (ctypes.c_int * 4)()
+        check(lib().sosrt_phase_sets_info(self._h, out))
+        return {"sets": out[0], "groups": out[1], "single_pass": bool(out[2]), "group_cap": out[3]}
+
     def same_grid(self, mu):
         return self.mu is not None and np.array_equal(self.mu, np.asarray(mu, dtype=np.float64))
 
@@ -154,7 +202,8 @@ class Solver:
             return False
         if (r is None) != (P_aer is None):
             return False
-        return r is None or np.array_equal(r, P_aer)
+        # (a stack of sets [S, 2N, 2N] is a different state from one matrix [2N, 2N], also for S = 1: shapes must agree)
+        return r is None or (np.shape(r) == np.shape(P_aer) and np.array_equal(r, P_aer))
 
     def set_columns(self, idx_up, idx_down, mu0, grd_alb, alb_atm, alb_aer, dtau_atm, dtau_aer, tauStar_tot,
                     surface="specular"):
@@ -172,6 +221,7 @@ class Solver:
                                         (dtau_atm, "dtau_atm"), (dtau_aer, "dtau_aer"), (tauStar_tot, "tauStar_tot"))]
         check(lib().sosrt_set_columns(self._h, B, _lib.GEOM_THREE_ZONE, sf, _ptr(iu), _ptr(idn), *[_ptr(x) for x in v]))
         self.B = B
+        self._p0_zones = 0
 
     def set_columns_zones(self, zone_r0, zone_mix, mu0, grd_alb, alb_atm, dtau_atm, zone_alb_aer, zone_dtau_aer, tauStar_tot,
                           nz=None, surface="specular"):
@@ -193,6 +243,7 @@ class Solver:
         check(lib().sosrt_set_columns_zones(self._h, B, sf, nzmax, _ptr(nzv), _ptr(zr0), _ptr(zmix), _ptr(v[0]), _ptr(v[1]),
                                             _ptr(v[2]), _ptr(v[3]), _ptr(zwr), _ptr(zdt), _ptr(v[4])))
         self.B = B
+        self._p0_zones = 0
 
     def set_columns_single_slab(self, mu0, alb, tauStar):
         """Single homogeneous slab over a black surface (I1_In:13-130)."""
@@ -201,13 +252,17 @@ class Solver:
         check(lib().sosrt_set_columns(self._h, B, _lib.GEOM_SINGLE_SLAB, _lib.SURFACE_NONE, None, None, _ptr(m), None,
                                       _ptr(a), None, None, None, _ptr(t)))
         self.B = B
+        self._p0_zones = 0
+
+    def _p0_shape(self):
+        return (self.B, self._p0_zones, self.D) if self._p0_zones else (self.B, self.D)
 
     # ---- step level ----------------------------------------------------------
     def first_order(self, tau, P0_atm, P0_aer=None):
         B = self.B
         tau = _f64(tau, (B, self.L), "tau")
         Pa = _f64(P0_atm, (B, self.D), "P0_atm")
-        Pr = None if P0_aer is None else _f64(P0_aer, (B, self.D), "P0_aer")
+        Pr = None if P0_aer is None else _f64(P0_aer, self._p0_shape(), "P0_aer")
         out = np.empty((B, self.L, self.D))
         check(lib().sosrt_first_order(self._h, B, _ptr(tau), _ptr(Pa), _ptr(Pr), _ptr(out)))
         return out
@@ -234,7 +289,7 @@ class Solver:
         B = self.B
         tau = _f64(tau, (B, self.L), "tau")
         Pa = None if P0_atm is None else _f64(P0_atm, (B, self.D), "P0_atm")
-        Pr = None if P0_aer is None else _f64(P0_aer, (B, self.D), "P0_aer")
+        Pr = None if P0_aer is None else _f64(P0_aer, self._p0_shape(), "P0_aer")
         I1a = None if I1 is None else _f64(I1, (B, self.L, self.D), "I1")
         I = np.empty((B, self.L, self.D)) if fetch_field else None
         n = np.zeros(B, dtype=np.int32)
@@ -375,6 +430,10 @@ class Solver:
         out = np.empty((self.D, self.D))
         check(lib().sosrt_phase_matrix(self._h, self._KINDS[kind], float(g), _ptr(out)))
         return out
+
+    def phase_matrix_device(self, kind, d_P_out: int, g=0.0):
+        """`phase_matrix` left on the device: d_P_out is the address of [2N, 2N] float64; enqueued on the handle's stream."""
+        check(lib().sosrt_phase_matrix_dev(self._h, self._KINDS[kind], float(g), ctypes.c_void_p(d_P_out) if d_P_out else None))
 
     # ---- Fourier modes in azimuth (sosrt.h: azimuth-resolved radiance; DESIGN section 11) ----
     def phase_modes(self, kind, m_first, m_count, nphi=25, g=0.0):
