@@ -8,6 +8,7 @@ import gpu_model as M
 import sos_oracle as O
 from sosrt import inputs
 from sosrt.solver import Solver
+from legendre_phase import factor as _factor
 from util import assert_close, column_case, g1_case, golden
 
 ALG = 5e-13
@@ -62,25 +63,6 @@ def test_zero_matrix_is_rank_zero_and_a_positive_rank_one_matrix_is_accepted():
     P = np.outer(rng.uniform(0.5, 2.0, D), rng.uniform(0.5, 2.0, D))   # no flip symmetry
     r, res, uses = _rank(N, P)
     assert (r, uses) == (1, True) and res <= 1e-14
-
-
-def _factor(W, rmax=4, tol=1e-12):
-    """The library's cross approximation (api.hip, lowrank_factor) in NumPy: U [D, r], V [r, D]."""
-    R = W.copy()
-    wmax = np.max(np.abs(W))
-    U, V = [], []
-    for _ in range(rmax + 1):
-        i, j = np.unravel_index(np.argmax(np.abs(R)), R.shape)
-        if abs(R[i, j]) <= tol * wmax:
-            break
-        U.append(R[:, j] / R[i, j])
-        V.append(R[i, :].copy())
-        R = R - np.outer(U[-1], V[-1])
-    assert len(U) <= rmax
-    U = np.array(U).T.reshape(W.shape[0], len(U))
-    V = np.array(V).reshape(len(V), W.shape[1])
-    assert np.max(np.abs(W - U @ V)) <= tol * wmax
-    return U, V
 
 
 def _source_factored(In_1, U, V, Wa, Wr, ca, cr, slab):
