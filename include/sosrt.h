@@ -151,6 +151,32 @@ int sosrt_set_phase_sets_dev(sosrt_t* h, const double* P_atm /*host*/, int S, co
 int sosrt_set_aerosol_sets(sosrt_t* h, int B, int nzmax, const int* zone_set /*[B][nzmax]*/);
 int sosrt_phase_sets_info(sosrt_t* h, int* out /*[4]*/);
 
+/* Several ATMOSPHERE phase matrices in one batch: what the Fourier modes of one scene need when they are
+ * solved as the columns (m, b) of one batch -- mode m reads (-1)^m P_atm^m.  Detected by symbol; SOSRT_VERSION is unchanged.
+ * sosrt_set_atm_phase_sets: S_atm matrices P_atm_sets [S_atm][2N][2N] (host), 1 <= S_atm <= SOSRT_MAX_PHASE_SETS, called AFTER
+ * sosrt_set_phase* (which defines the aerosol matrices and atmosphere set 0, and puts S_atm back to 1).  Set 0 of the stack
+ * replaces the handle's W_atm, exactly as sosrt_set_phase would have stored that matrix.  Every set is folded and must pass
+ * the two certificates of sosrt_set_phase's W_atm: a low-rank factorisation of rank <= 4 within SOSRT_LOWRANK_TOL
+ * (sosrt_phase_rank; iso 1, Rayleigh's modes 2, 1, 1, 0, ...; a zero matrix has rank 0) and flip symmetry within
+ * SOSRT_SYMMETRY_TOL.  A set that fails either, or holds a NaN or an infinity, gives SOSRT_E_INVALID and the handle is left
+ * as it was.  The choice of the symmetric contraction made by sosrt_set_phase* stands.
+ * sosrt_set_atmosphere_sets: col_set [B], the atmosphere set of every current column (one per column, not per zone).  Every
+ * sosrt_set_columns* call puts all columns back on set 0, so a caller that never calls this sees no change.  The plain rows
+ * of a column take the low-rank factors of its set, its slab rows the combined matrix ca W_atm[set] + cr W_aer[aerosol set]:
+ * a combined-matrix group is a distinct (atmosphere set, aerosol set, ca, cr), within the cache of sosrt_phase_sets_info.
+ * A column on set s has the bits of the same column on a handle whose sosrt_set_phase got that set's matrix.
+ * Refused with SOSRT_E_INVALID (and nothing changes) while S_atm > 1 or a column is off atmosphere set 0:
+ *   - a batch with more groups than the cache holds (its two-pass form reads the one W_atm);
+ *   - SOSRT_CONTRACT_F64_DENSE, _FULL and _F32, in either order of the calls (their plain rows are MFMA tiles over row lists
+ *     that straddle columns), and matrices sosrt_set_phase* found not flip-symmetric;
+ *   - SOSRT_FIRST_ORDER_README, in either order;
+ *   - sosrt_set_phase* while a column is off set 0 (reset the columns first).
+ * The order-loop launch is not planned while a column is off set 0.
+ * sosrt_atm_sets_info: out[2] = { S_atm, 1 if any current column is off atmosphere set 0 }. */
+int sosrt_set_atm_phase_sets(sosrt_t* h, int S_atm, const double* P_atm_sets /*host [S_atm][2N][2N]*/);
+int sosrt_set_atmosphere_sets(sosrt_t* h, int B, const int* col_set /*[B]*/);
+int sosrt_atm_sets_info(sosrt_t* h, int* out /*[2]*/);
+
 /* First order of the solve.  CODED (default): spec:104-292 -- what both mains of the reference compute, with the specularly
  * reflected beam (SOS_Aer_main_lambertian.py's first-order blocks are the same formulas; its lines 274-276 crash).
  * README: the Lambertian first order of the reference's README.md:126-171 -- direct beam + the beam reflected isotropically by
@@ -362,6 +388,11 @@ int sosrt_phase_matrix_dev(sosrt_t* h, int kind, double g, double* d_P_out);
 #define SOSRT_MAX_MODES 64
 /* modes m_first .. m_first + m_count - 1 of P: P_out [m_count][2N][2N], host output */
 int sosrt_phase_modes(sosrt_t* h, int kind, double g, int m_first, int m_count, int nphi, double* P_out);
+/* sosrt_phase_modes with the matrices LEFT ON THE DEVICE: d_P_out [m_count][2N][2N], enqueued on the handle's stream (which
+ * is synchronised first when a mode m >= 1 is asked for).  sign_odd != 0: mode m is written as (-1)^m P^m, what the solve of
+ * mode m takes -- negation is exact, so these are the bits of the host's -1.0 * P.  The output goes straight into
+ * sosrt_set_phase_sets_dev. */
+int sosrt_phase_modes_dev(sosrt_t* h, int kind, double g, int m_first, int m_count, int nphi, int sign_odd, double* d_P_out);
 /* the same modes of P0 for B columns: P0_out [m_count][B][2N] (the [B][2N] block of one mode is what sosrt_solve_dev reads).
  * _dev: d_mu0 [B], d_P0_out device pointers, enqueued on the handle's stream (synchronises it first when a mode m >= 1 is asked
  * for: the weights of the modes go to the device). */
@@ -381,6 +412,11 @@ int sosrt_set_order_targets(sosrt_t* h, const int* d_targets);
  * d_out [B][nlev][2N][nphi_out]; device pointers, enqueued on the handle's stream. */
 int sosrt_azimuth_accumulate_dev(sosrt_t* h, int B, int m, const double* d_Im, int nlev, const int* d_levels, int nphi_out,
                                  const double* d_phi, double* d_out);
+/* the whole sum in ONE launch: d_I0 [B][L][2N] is mode 0, d_Im [M][B][L][2N] the modes 1..M (0 <= M <= SOSRT_MAX_MODES; may be
+ * NULL for M = 0) -- the layout of a batch whose column index is (m, b).  The terms are added in ascending m, so d_out has the
+ * bits of sosrt_azimuth_accumulate_dev called for m = 0, 1, .., M, and is written once instead of rewritten per mode. */
+int sosrt_azimuth_synthesize_dev(sosrt_t* h, int B, int M, const double* d_I0, const double* d_Im, int nlev, const int* d_levels,
+                                 int nphi_out, const double* d_phi, double* d_out);
 
 /* ---- multi-GPU: one process per GPU, columns sharded, ONE collective at the end ------------------
  * Nothing in SOS_Aer_main_specular.py:104-458 couples columns, so the order loop never communicates; these entry

@@ -141,6 +141,18 @@ struct sosrt_handle {
     size_t wrsets_s_capacity = 0;
     int* d_mixset = nullptr;             // [kMaxMixGroupsSets] set of a group
     int max_set_used = 0;                // largest set index the current columns name (sosrt_set_aerosol_sets)
+    // Atmosphere phase sets (sosrt_set_atm_phase_sets): natm folded matrices, each certified low-rank, and
+    // which one a column reads (sosrt_set_atmosphere_sets).  Set 0 is W_atm itself (d_Wa, d_lrU / d_lrV); the stacks below exist
+    // from the first call on and are read only while a column is off set 0 (max_atm_used > 0).
+    int natm = 1;                        // atmosphere sets of the last sosrt_set_atm_phase_sets (1 after every sosrt_set_phase*)
+    int max_atm_used = 0;                // largest atmosphere set the current columns name
+    std::vector<int> c_atmset;           // [B] atmosphere set of a column
+    double* d_Wasets = nullptr;          // [natm][Dp][Wld] folds of all sets
+    double *d_lrUsets = nullptr, *d_lrVsets = nullptr;   // [natm][kLowRankMax][D] their factors
+    int* d_lrranks = nullptr;            // [natm] their ranks
+    int atm_capacity = 0;                // sets the four stacks hold
+    int* d_colatm = nullptr;             // [max_batch] atmosphere set of a column
+    int* d_mixatm = nullptr;             // [kMaxMixGroupsSets] atmosphere set of a group
     int p0_zones = 0;                    // > 0: P0_aer of the first order is [B][p0_zones][2N], one row per zone of the caller's table
     double* d_P0rz = nullptr;            // staging of such a P0_aer for the host entry points
     size_t p0rz_capacity = 0;
@@ -433,9 +445,9 @@ int ensure_matrices(sosrt_handle* h, hipStream_t s) {
     const bool mixed = h->mix_groups > 0 && h->mix_dirty;
     if (mixed) {
         prof_break(h);
-        const bool sets = h->max_set_used > 0;
-        launch_wmix(s, per, h->mix_groups, h->d_Wa, sets ? h->d_Wrsets : h->d_Wr, h->d_mixca, h->d_mixcr, h->d_Wmix,
-                    sets ? h->d_mixset : nullptr);
+        const bool sets = h->max_set_used > 0, atm = h->max_atm_used > 0;
+        launch_wmix(s, per, h->mix_groups, atm ? h->d_Wasets : h->d_Wa, sets ? h->d_Wrsets : h->d_Wr, h->d_mixca, h->d_mixcr,
+                    h->d_Wmix, sets ? h->d_mixset : nullptr, atm ? h->d_mixatm : nullptr);
         h->mix_dirty = false;
         h->symmix_dirty = true;
     }
@@ -523,6 +535,16 @@ void run_source(sosrt_handle* h, const double* In_1, double* Jn, const int* acti
         ga.Wr = h->d_Wrsets; ga.mix_group = h->d_mixgroup; ga.slab_tile_group = h->d_slabtilegroup + h->slab_off[g0] / 32;
     }
     if (use_lowrank(h)) { ga.lr_rank = h->lr_rank; ga.lrU = h->d_lrU; ga.lrV = h->d_lrV; }
+    // atmosphere sets in use: the launches' twins that pick a plain row's factors by its column's set (every set is low-rank, the
+    // contraction is the symmetric f64 one: sosrt_set_atm_phase_sets / sosrt_set_atmosphere_sets refuse anything else)
+    AtmSets at;
+    const AtmSets* atp = nullptr;
+    if (h->max_atm_used > 0) {
+        at.col_atm = h->d_colatm + (h->nslab > 0 ? 0 : h->gb[g0]);
+        at.lr_ranks = h->d_lrranks;
+        ga.lrU = h->d_lrUsets; ga.lrV = h->d_lrVsets;
+        atp = &at;
+    }
     if (use_sym(h)) {
         ga.sym = 1; ga.Ks = (h->g.N + GEMM_KC - 1) / GEMM_KC * GEMM_KC;
 #ifdef SOSRT_DIAG
@@ -555,13 +577,13 @@ void run_source(sosrt_handle* h, const double* In_1, double* Jn, const int* acti
         ga.max_main = h->max_main; ga.max_slab = h->max_slab;
         ga.idx_up = h->nslab > 0 ? h->d_idx_up : nullptr; ga.idx_down = h->nslab > 0 ? h->d_idx_down : nullptr;
         ga.live_list = h->d_livelist + h->gb[g0]; ga.live_cap = tail_cols;
-        launch_gemm_tail(s, ga, tail_cols, tail_cols <= h->gemm_small_cols, regs_tile);
+        launch_gemm_tail(s, ga, tail_cols, tail_cols <= h->gemm_small_cols, regs_tile, atp);
     } else {
         if (dense_live_cap > 0 && active && h->nslab >= 0) {     // the dense tiling writes the transport's live list too
             ga.col0 = h->nslab > 0 ? h->gb[g0] : 0; ga.B = h->gb[g1] - h->gb[g0];
             ga.live_list = h->d_livelist + h->gb[g0]; ga.live_cap = dense_live_cap;
         }
-        launch_gemm(s, ga);
+        launch_gemm(s, ga, atp);
     }
     prof_end(h, SOSRT_K_GEMM, pg);
 }
@@ -820,6 +842,8 @@ int sosrt_create(int device, int L, int N, int max_batch, int max_orders, sosrt_
             if ((e = dalloc(&h->d_mixca, sosrt_handle::kMaxMixGroupsSets))) return e;
             if ((e = dalloc(&h->d_mixcr, sosrt_handle::kMaxMixGroupsSets))) return e;
             if ((e = dalloc(&h->d_mixset, sosrt_handle::kMaxMixGroupsSets))) return e;
+            if ((e = dalloc(&h->d_mixatm, sosrt_handle::kMaxMixGroupsSets))) return e;
+            if ((e = dalloc(&h->d_colatm, mb))) return e;
             if ((e = dalloc(&h->d_tauhash, mb))) return e;
             if ((e = dalloc(&h->d_ratio, mb))) return e;
             if ((e = dalloc(&h->d_scan_scratch, mb * transport_scan_scratch_doubles()))) return e;
@@ -858,7 +882,8 @@ int sosrt_destroy(sosrt_t* h) {
                         h->d_idx_down, h->d_scal, h->d_desc, h->d_rca, h->d_rcr, h->d_slabrows, h->d_mainrows, h->d_tau, h->d_P0a,
                         h->d_P0r, h->d_Jn, h->d_InA, h->d_InB, h->d_I, h->d_E, h->d_active, h->d_norders, h->d_status,
                         h->d_nactive_sets, h->d_ratio, h->d_redo, h->d_erep, h->d_tauhash, h->d_Wmix, h->d_mixca, h->d_mixcr,
-                        h->d_mixgroup, h->d_Wa_s, h->d_Wr_s, h->d_Wmix_s, h->d_scan_scratch, h->d_scan_sync, h->d_w, h->d_phi, h->d_z, h->d_tab, h->d_slabtilegroup, h->d_livelist, h->d_Wa32, h->d_Wmix32, h->d_nz, h->d_zr0, h->d_zmix, h->d_zwr, h->d_zdtr, h->d_olsync, h->d_ollog, h->d_modetab, h->d_lrU, h->d_lrV, h->d_Wrsets, h->d_Wrsets_s, h->d_mixset, h->d_P0rz};
+                        h->d_mixgroup, h->d_Wa_s, h->d_Wr_s, h->d_Wmix_s, h->d_scan_scratch, h->d_scan_sync, h->d_w, h->d_phi, h->d_z, h->d_tab, h->d_slabtilegroup, h->d_livelist, h->d_Wa32, h->d_Wmix32, h->d_nz, h->d_zr0, h->d_zmix, h->d_zwr, h->d_zdtr, h->d_olsync, h->d_ollog, h->d_modetab, h->d_lrU, h->d_lrV, h->d_Wrsets, h->d_Wrsets_s, h->d_mixset, h->d_P0rz,
+                        h->d_Wasets, h->d_lrUsets, h->d_lrVsets, h->d_lrranks, h->d_colatm, h->d_mixatm};
         for (void* p : ptrs)
             if (p) hipFree(p);
         if (h->h_pub) hipHostFree(h->h_pub);
@@ -912,6 +937,8 @@ int sosrt_set_first_order(sosrt_t* h, int mode) {
     if (mode != SOSRT_FIRST_ORDER_CODED && mode != SOSRT_FIRST_ORDER_README) return fail(SOSRT_E_INVALID, "unknown first-order mode %d", mode);
     if (mode == SOSRT_FIRST_ORDER_README && (h->nsets > 1 || h->p0_zones > 0))
         return fail(SOSRT_E_INVALID, "SOSRT_FIRST_ORDER_README reads one aerosol matrix: it cannot be combined with several phase sets");
+    if (mode == SOSRT_FIRST_ORDER_README && (h->natm > 1 || h->max_atm_used > 0))
+        return fail(SOSRT_E_INVALID, "SOSRT_FIRST_ORDER_README reads one atmosphere matrix: it cannot be combined with atmosphere phase sets");
     if (mode == SOSRT_FIRST_ORDER_README && h->geom != SOSRT_GEOM_THREE_ZONE)
         return fail(SOSRT_E_INVALID, "the README's Lambertian first order needs the three-zone geometry (it has a surface)");
     h->first_order_mode = mode;
@@ -921,6 +948,9 @@ int sosrt_set_first_order(sosrt_t* h, int mode) {
 int sosrt_set_contraction(sosrt_t* h, int mode) {
     if (int e = need_gpu(h)) return e;
     if (mode != SOSRT_CONTRACT_F64 && mode != SOSRT_CONTRACT_F32 && mode != SOSRT_CONTRACT_F64_FULL && mode != SOSRT_CONTRACT_F64_DENSE) return fail(SOSRT_E_INVALID, "unknown contraction mode %d", mode);
+    if (mode != SOSRT_CONTRACT_F64 && (h->natm > 1 || h->max_atm_used > 0))
+        return fail(SOSRT_E_INVALID, "atmosphere phase sets are in use: their plain rows exist in the low-rank form of SOSRT_CONTRACT_F64 only "
+                                     "(the other contractions tile row lists that straddle columns)");
     if (mode == SOSRT_CONTRACT_F32) {
         HIPCHK(hipSetDevice(h->device));
         const size_t per = (size_t)h->g.Dp * h->g.Wld;
@@ -1065,6 +1095,20 @@ int sosrt_set_grid(sosrt_t* h, const double* mu) {
     return 0;
 }
 
+// max |W[k][m] - W[D-1-k][D-1-m]| / max |W| of a folded matrix: the flip-symmetry measure of sosrt_set_phase* and of
+// sosrt_set_atm_phase_sets (see sosrt.h, sosrt_set_contraction)
+static double flip_asymmetry(const std::vector<double>& W, int D) {
+    double wmax = 0, amax = 0;
+    for (int k = 0; k < D; ++k)
+        for (int m = 0; m < D; ++m) {
+            const double x = W[(size_t)k * D + m], y = W[(size_t)(D - 1 - k) * D + (D - 1 - m)];
+            const double ax = std::fabs(x), d = std::fabs(x - y);
+            if (!(ax <= wmax)) wmax = ax;          // a NaN ends up here and switches the symmetric form off
+            if (!(d <= amax)) amax = d;
+        }
+    return wmax > 0 ? amax / wmax : 0.0;
+}
+
 static int mix_group_cap(const sosrt_handle* h, bool sets);
 // Common part of sosrt_set_phase / sosrt_set_phase_sets[_dev]: S aerosol matrices [S][2N][2N] (S = 0: none), host (P_aer) or
 // device (d_P_aer: folded and measured on the device, in the handle's stream order; the host keeps no copy of their folds
@@ -1077,6 +1121,9 @@ static int set_phase_impl(sosrt_handle* h, const double* P_atm, int S, const dou
                     h->max_set_used, S > 0 ? S : 1);
     if (S > 1 && h->first_order_mode == SOSRT_FIRST_ORDER_README)
         return fail(SOSRT_E_INVALID, "SOSRT_FIRST_ORDER_README reads one aerosol matrix: it cannot be combined with %d phase sets", S);
+    if (h->have_cols && h->max_atm_used > 0)
+        return fail(SOSRT_E_INVALID, "the current columns use atmosphere set %d, and sosrt_set_phase leaves one atmosphere set (sosrt_set_columns resets them to set 0)",
+                    h->max_atm_used);
     const size_t DD = (size_t)h->D * h->D;
     h->plan.fold(P_atm, h->Wa_h);
     h->have_aer = S > 0;
@@ -1087,6 +1134,7 @@ static int set_phase_impl(sosrt_handle* h, const double* P_atm, int S, const dou
     h->Wrx_h.resize(S > 1 ? S - 1 : 0);
     for (int q = 1; q < S && !d_P_aer; ++q) h->plan.fold(P_aer + (size_t)q * DD, h->Wrx_h[q - 1]);
     h->nsets = S > 1 ? S : 1;
+    h->natm = 1;
     h->have_phase = true;
     h->mix_dirty = true;
     h->w32_dirty = true;
@@ -1098,15 +1146,7 @@ static int set_phase_impl(sosrt_handle* h, const double* P_atm, int S, const dou
         for (const auto& W : h->Wrx_h) all.push_back(&W);
         for (const std::vector<double>* W : all) {
             if (W->empty()) continue;
-            double wmax = 0, amax = 0;
-            for (int k = 0; k < D; ++k)
-                for (int m = 0; m < D; ++m) {
-                    const double x = (*W)[(size_t)k * D + m], y = (*W)[(size_t)(D - 1 - k) * D + (D - 1 - m)];
-                    const double ax = std::fabs(x), d = std::fabs(x - y);
-                    if (!(ax <= wmax)) wmax = ax;          // a NaN ends up here and switches the symmetric form off
-                    if (!(d <= amax)) amax = d;
-                }
-            const double r = wmax > 0 ? amax / wmax : 0.0;
+            const double r = flip_asymmetry(*W, D);
             if (!(r <= h->asymmetry)) h->asymmetry = r;
         }
         // (a compile-time constant: nothing in the environment can put the symmetric form on a matrix without the symmetry)
@@ -1199,11 +1239,12 @@ int sosrt_phase_sets_info(sosrt_t* h, int* out) {
     return 0;
 }
 
-// Combined-matrix groups of the current columns: the distinct (aerosol set, ca, cr) of their aerosol zones (spec:321:
-// (w_atm/4) f_atm on W_atm, (w_aer/4) f_aer on W_aer), per (column, slab).
+// Combined-matrix groups of the current columns: the distinct (atmosphere set, aerosol set, ca, cr) of their aerosol zones
+// (spec:321: (w_atm/4) f_atm on W_atm, (w_aer/4) f_aer on W_aer), per (column, slab).
 struct MixGroups {
     std::vector<double> ca, cr;
     std::vector<int> set, gid /*[B][kMaxZones], -1: clear zone*/, gcol /*[B]: the live-column tilings, one slab per column*/;
+    std::vector<int> atm;                // atmosphere set of a group (sosrt_set_atmosphere_sets; all 0 otherwise)
 };
 // groups the cache may hold: kMaxMixGroups while every column uses set 0 (what it always held), more with several sets in use
 static int mix_group_cap(const sosrt_handle* h, bool sets) {
@@ -1217,7 +1258,8 @@ static int mix_group_cap(const sosrt_handle* h, bool sets) {
     return (int)n;
 }
 // false: more than `cap` groups
-static bool collect_mix_groups(const sosrt_handle* h, int B, const std::vector<int>& zset, int cap, MixGroups& mg) {
+static bool collect_mix_groups(const sosrt_handle* h, int B, const std::vector<int>& zset, const std::vector<int>& aset, int cap,
+                               MixGroups& mg) {
     mg.gid.assign((size_t)B * kMaxZones, -1);
     mg.gcol.assign(B, 0);
     for (int b = 0; b < B; ++b) {
@@ -1225,12 +1267,12 @@ static bool collect_mix_groups(const sosrt_handle* h, int B, const std::vector<i
             if (!h->c_zmix[b * kMaxZones + z]) continue;
             const double da = h->c_dtau_atm[b], dr = h->c_zdtr[b * kMaxZones + z];
             const double ca = (h->c_alb_atm[b] / 4) * (da / (da + dr)), cr = (h->c_zwr[b * kMaxZones + z] / 4) * (dr / (da + dr));
-            const int st = zset[b * kMaxZones + z];
+            const int st = zset[b * kMaxZones + z], at = aset[b];
             int k = 0;
-            while (k < (int)mg.ca.size() && !(mg.ca[k] == ca && mg.cr[k] == cr && mg.set[k] == st)) ++k;
+            while (k < (int)mg.ca.size() && !(mg.ca[k] == ca && mg.cr[k] == cr && mg.set[k] == st && mg.atm[k] == at)) ++k;
             if (k == (int)mg.ca.size()) {
                 if (k == cap) return false;
-                mg.ca.push_back(ca); mg.cr.push_back(cr); mg.set.push_back(st);
+                mg.ca.push_back(ca); mg.cr.push_back(cr); mg.set.push_back(st); mg.atm.push_back(at);
             }
             mg.gid[b * kMaxZones + z] = k;
             mg.gcol[b] = k;
@@ -1253,15 +1295,16 @@ static int apply_mix_groups(sosrt_handle* h, int B, const MixGroups& mg) {
         else (void)hipGetLastError();
     }
     if (h->mix_capacity < need) {
-        if (h->max_set_used > 0) {
+        if (h->max_set_used > 0 || h->max_atm_used > 0) {
             h->have_cols = false;
-            return fail(SOSRT_E_NOMEM, "no memory for the %zu combined matrices of a batch with several aerosol sets", mg.ca.size());
+            return fail(SOSRT_E_NOMEM, "no memory for the %zu combined matrices of a batch with several phase sets", mg.ca.size());
         }
         return 0;
     }
     HIPCHK(hipMemcpy(h->d_mixca, mg.ca.data(), mg.ca.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_mixcr, mg.cr.data(), mg.cr.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_mixset, mg.set.data(), mg.set.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_mixatm, mg.atm.data(), mg.atm.size() * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_mixgroup, mg.gcol.data(), B * sizeof(int), hipMemcpyHostToDevice));
     h->mix_groups = (int)mg.ca.size();
     // slab rows of the dense contraction listed, per column group of the order loop, group by group, every group padded
@@ -1378,6 +1421,8 @@ static int set_columns_impl(sosrt_handle* h, int B, int geometry, int surface, c
     h->w32_dirty = true;
     // every column starts on aerosol set 0 (sosrt_set_aerosol_sets changes that), P0_aer is one row per column
     h->max_set_used = 0;
+    h->max_atm_used = 0;                     // ... and on atmosphere set 0 (sosrt_set_atmosphere_sets)
+    h->c_atmset.assign(B, 0);
     h->p0_zones = 0;
     h->c_nz = nz; h->c_zr0 = zr0; h->c_zmix = zmix; h->c_zwr = zwr; h->c_zdtr = zdtr;
     h->c_zset.assign((size_t)B * kMaxZones, 0);
@@ -1386,7 +1431,7 @@ static int set_columns_impl(sosrt_handle* h, int B, int geometry, int surface, c
     if (dtau_atm) h->c_dtau_atm.assign(dtau_atm, dtau_atm + B);
     if (geometry == SOSRT_GEOM_THREE_ZONE && h->nslab > 0) {
         MixGroups mg;
-        if (collect_mix_groups(h, B, h->c_zset, mix_group_cap(h, false), mg))
+        if (collect_mix_groups(h, B, h->c_zset, h->c_atmset, mix_group_cap(h, false), mg))
             if (int e = apply_mix_groups(h, B, mg)) return e;
     }
     h->B = B; h->geom = geometry; h->surface = surface;
@@ -1520,9 +1565,12 @@ int sosrt_set_aerosol_sets(sosrt_t* h, int B, int nzmax, const int* zone_set) {
         }
     }
     MixGroups mg;
-    const int cap = mix_group_cap(h, top > 0);
+    const int cap = mix_group_cap(h, top > 0 || h->max_atm_used > 0);
     // (beyond the cache the slab rows take two passes, W_atm and then the W_aer of their set: apply_two_pass_rows)
-    const bool fits = collect_mix_groups(h, B, zset, cap, mg);
+    const bool fits = collect_mix_groups(h, B, zset, h->c_atmset, cap, mg);
+    if (!fits && h->max_atm_used > 0)
+        return fail(SOSRT_E_INVALID, "more than %d distinct (atmosphere set, aerosol set, ca, cr) groups: the two-pass form that a batch beyond the "
+                                     "cache takes reads one W_atm, and the current columns use atmosphere sets", cap);
     const bool regroup = top > 0 || h->max_set_used > 0;      // (all on set 0 before and after: the groups sosrt_set_columns built stand)
     h->c_zset = zset;
     h->max_set_used = top;
@@ -1532,6 +1580,139 @@ int sosrt_set_aerosol_sets(sosrt_t* h, int B, int nzmax, const int* zone_set) {
         HIPCHK(hipStreamSynchronize(h->stream));
         if (int e = fits ? apply_mix_groups(h, B, mg) : apply_two_pass_rows(h, B)) return e;
     }
+    return 0;
+}
+
+int sosrt_set_atm_phase_sets(sosrt_t* h, int S_atm, const double* P_atm_sets) {
+    if (!h || !P_atm_sets) return fail(SOSRT_E_INVALID, "null argument");
+    if (int e = need_gpu(h)) return e;
+    if (!h->have_phase) return fail(SOSRT_E_STATE, "sosrt_set_phase has not been called (it defines the aerosol matrices; the atmosphere sets follow it)");
+    if (S_atm < 1 || S_atm > SOSRT_MAX_PHASE_SETS)
+        return fail(SOSRT_E_INVALID, "S_atm=%d outside 1..SOSRT_MAX_PHASE_SETS=%d", S_atm, SOSRT_MAX_PHASE_SETS);
+    if (h->have_cols && h->max_atm_used >= S_atm)
+        return fail(SOSRT_E_INVALID, "the current columns use atmosphere set %d, but only %d set(s) are given (sosrt_set_columns resets them to set 0)",
+                    h->max_atm_used, S_atm);
+    if (S_atm > 1) {
+        if (h->contraction != SOSRT_CONTRACT_F64)
+            return fail(SOSRT_E_INVALID, "atmosphere phase sets need SOSRT_CONTRACT_F64: their plain rows exist in its low-rank form only "
+                                         "(the other contractions tile row lists that straddle columns)");
+        if (h->first_order_mode == SOSRT_FIRST_ORDER_README)
+            return fail(SOSRT_E_INVALID, "SOSRT_FIRST_ORDER_README reads one atmosphere matrix: it cannot be combined with %d atmosphere sets", S_atm);
+        if (!h->sym_ok)
+            return fail(SOSRT_E_INVALID, "atmosphere phase sets need the flip-symmetric contraction, and the matrices of the last sosrt_set_phase "
+                                         "are not symmetric (asymmetry %.3g > %.3g)", h->asymmetry, (double)SOSRT_SYMMETRY_TOL);
+    }
+    // every set: folded as sosrt_set_phase folds W_atm, then the same two certificates; nothing changes unless all pass
+    const int D = h->D;
+    const size_t DD = (size_t)D * D, LR = (size_t)kLowRankMax * D;
+    std::vector<std::vector<double>> W(S_atm);
+    std::vector<double> U(LR * S_atm), V(LR * S_atm), res(S_atm);
+    std::vector<int> ranks(S_atm);
+    double asym = 0;
+    for (int q = 0; q < S_atm; ++q) {
+        h->plan.fold(P_atm_sets + (size_t)q * DD, W[q]);
+        std::vector<double> u, v;
+        ranks[q] = lowrank_factor(W[q], D, u, v, &res[q]);
+        if (ranks[q] < 0)
+            return fail(SOSRT_E_INVALID, "atmosphere set %d is not low-rank: no factorisation of at most %d terms within %.3g of its largest element "
+                                         "(residual %.3g; a NaN or an infinity gives this too) -- atmosphere sets take the low-rank form of the plain rows only",
+                        q, kLowRankMax, (double)SOSRT_LOWRANK_TOL, res[q]);
+        const double r = flip_asymmetry(W[q], D);
+        if (!(r <= SOSRT_SYMMETRY_TOL))
+            return fail(SOSRT_E_INVALID, "atmosphere set %d is not flip-symmetric: asymmetry %.3g > %.3g", q, r, (double)SOSRT_SYMMETRY_TOL);
+        if (r > asym) asym = r;
+        std::copy(u.begin(), u.end(), U.begin() + LR * q);
+        std::copy(v.begin(), v.end(), V.begin() + LR * q);
+    }
+    HIPCHK(hipSetDevice(h->device));
+    const Grid& g = h->g;
+    const size_t per = (size_t)g.Dp * g.Wld;
+    if (S_atm > h->atm_capacity) {                       // (the new stacks first: a failure leaves the old ones in place)
+        double *nW = nullptr, *nU = nullptr, *nV = nullptr;
+        int* nR = nullptr;
+        int e = dalloc(&nW, per * S_atm);
+        if (!e) e = dalloc(&nU, LR * S_atm);
+        if (!e) e = dalloc(&nV, LR * S_atm);
+        if (!e) e = dalloc(&nR, (size_t)S_atm);
+        if (e) {
+            for (void* p : {(void*)nW, (void*)nU, (void*)nV, (void*)nR})
+                if (p) hipFree(p);
+            return e;
+        }
+        for (void* p : {(void*)h->d_Wasets, (void*)h->d_lrUsets, (void*)h->d_lrVsets, (void*)h->d_lrranks})
+            if (p) hipFree(p);                           // (hipFree synchronises: no launch still reads them)
+        h->d_Wasets = nW; h->d_lrUsets = nU; h->d_lrVsets = nV; h->d_lrranks = nR;
+        h->atm_capacity = S_atm;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));             // a solve in flight still reads W_atm
+    HIPCHK(hipMemset(h->d_Wasets, 0, per * S_atm * sizeof(double)));       // the padding rows and columns stay zero
+    for (int q = 0; q < S_atm; ++q)
+        HIPCHK(hipMemcpy2D(h->d_Wasets + q * per, g.Wld * sizeof(double), W[q].data(), g.D * sizeof(double), g.D * sizeof(double),
+                           g.D, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_lrUsets, U.data(), U.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_lrVsets, V.data(), V.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_lrranks, ranks.data(), ranks.size() * sizeof(int), hipMemcpyHostToDevice));
+    // set 0 is the handle's W_atm: what sosrt_set_phase would have left for this matrix
+    h->Wa_h = W[0];
+    HIPCHK(hipMemcpy2D(h->d_Wa, g.Wld * sizeof(double), h->Wa_h.data(), g.D * sizeof(double), g.D * sizeof(double), g.D,
+                       hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_lrU, U.data(), LR * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_lrV, V.data(), LR * sizeof(double), hipMemcpyHostToDevice));
+    h->lr_rank = ranks[0]; h->lr_residual = res[0];
+    if (asym > h->asymmetry) h->asymmetry = asym;        // (still within the tolerance: the choice of the symmetric form stands)
+    h->natm = S_atm;
+    h->mix_dirty = true; h->w32_dirty = true;
+    h->sym_dirty = true; h->symmix_dirty = true;
+    return 0;
+}
+
+int sosrt_set_atmosphere_sets(sosrt_t* h, int B, const int* col_set) {
+    if (!h || !col_set) return fail(SOSRT_E_INVALID, "null argument");
+    if (B < 1) return fail(SOSRT_E_INVALID, "B=%d must be >= 1", B);
+    if (int e = need_gpu(h)) return e;
+    if (!h->have_phase) return fail(SOSRT_E_STATE, "sosrt_set_phase has not been called");
+    if (!h->have_cols) return fail(SOSRT_E_STATE, "sosrt_set_columns has not been called");
+    if (B != h->B) return fail(SOSRT_E_INVALID, "B=%d does not match sosrt_set_columns (B=%d)", B, h->B);
+    std::vector<int> aset(col_set, col_set + B);
+    int top = 0;
+    for (int b = 0; b < B; ++b) {
+        if (aset[b] < 0 || aset[b] >= h->natm)
+            return fail(SOSRT_E_INVALID, "column %d: atmosphere set %d outside 0..%d (sosrt_set_atm_phase_sets)", b, aset[b], h->natm - 1);
+        top = aset[b] > top ? aset[b] : top;
+    }
+    if (top == 0 && h->max_atm_used == 0) return 0;      // all on set 0 before and after: nothing to do
+    if (top > 0) {
+        // (what sosrt_set_atm_phase_sets accepted S_atm > 1 under; sosrt_set_contraction / sosrt_set_first_order keep it so)
+        if (!use_lowrank(h) || !use_sym(h))
+            return fail(SOSRT_E_INVALID, "atmosphere sets need the low-rank plain rows and the flip-symmetric form of SOSRT_CONTRACT_F64");
+        if (h->first_order_mode == SOSRT_FIRST_ORDER_README)
+            return fail(SOSRT_E_INVALID, "SOSRT_FIRST_ORDER_README reads one atmosphere matrix: it cannot be combined with atmosphere sets");
+    }
+    const bool slabs = h->geom == SOSRT_GEOM_THREE_ZONE && h->nslab > 0;
+    MixGroups mg;
+    bool fits = true;
+    if (slabs) {
+        const int cap = mix_group_cap(h, top > 0 || h->max_set_used > 0);
+        fits = collect_mix_groups(h, B, h->c_zset, aset, cap, mg);
+        if (!fits && top > 0)
+            return fail(SOSRT_E_INVALID, "more than %d distinct (atmosphere set, aerosol set, ca, cr) groups: the two-pass form that a batch beyond the "
+                                         "cache takes reads one W_atm, so it is not available with atmosphere sets", cap);
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(h->d_colatm, aset.data(), B * sizeof(int), hipMemcpyHostToDevice));
+    h->c_atmset = aset;
+    h->max_atm_used = top;
+    h->resident = false;
+    if (slabs)
+        if (int e = fits ? apply_mix_groups(h, B, mg) : apply_two_pass_rows(h, B)) return e;
+    return 0;
+}
+
+int sosrt_atm_sets_info(sosrt_t* h, int* out) {
+    if (!h || !out) return fail(SOSRT_E_INVALID, "null argument");
+    out[0] = h->natm;
+    out[1] = (h->have_cols && h->max_atm_used > 0) ? 1 : 0;
     return 0;
 }
 
@@ -1880,7 +2061,7 @@ int sosrt_solve_dev(sosrt_t* h, int B, const double* d_tau, const double* d_P0_a
             oi.simple_zones = h->simple_zones; oi.slabs_mixed = h->nslab == 0 || h->mix_groups > 0;
             oi.need_small = g.nsmall > 0 && h->need_small; oi.saving = d_I_saved_out != nullptr;
             oi.orders_left = h->order_budget - q.n;
-            oi.cu_share = (q.ol_off || h->d_targets) ? 0 : h->cu_count / NG;   // (no order-loop launch with order targets)
+            oi.cu_share = (q.ol_off || h->d_targets || h->max_atm_used > 0) ? 0 : h->cu_count / NG;   // (no order-loop launch with order targets, or atmosphere sets)
             LaunchPlan pl = plan_order(h, shape, oi);
             if (pl.order_loop) {
                 // its workgroups wait for each other: they must all fit the CUs no other order-loop launch of this process holds
@@ -2478,6 +2659,26 @@ int sosrt_phase_modes(sosrt_t* h, int kind, double g, int m_first, int m_count, 
     return rc;
 }
 
+int sosrt_phase_modes_dev(sosrt_t* h, int kind, double g, int m_first, int m_count, int nphi, int sign_odd, double* d_P_out) {
+    if (int e = modes_check(h, kind, g, m_first, m_count, nphi)) return e;
+    if (!d_P_out) return fail(SOSRT_E_INVALID, "null argument");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t DD = (size_t)h->D * h->D;
+    const int mf = m_first > 0 ? m_first : 1, mc = m_first > 0 ? m_count : m_count - 1;   // modes m >= 1 of the request
+    if (mc > 0)
+        if (int e = modes_table(h, nphi, mf, mc)) return e;
+    if (m_first == 0)
+        launch_phase_matrix(s, h->g, h->d_w, kind, g, h->d_tab, h->d_tab ? h->d_tab + h->ntab : nullptr, h->ntab, h->d_phi,
+                            h->d_phi + kNPhi, kNPhi, d_P_out);
+    if (mc > 0)
+        launch_phase_modes(s, h->g, h->d_w, kind, g, h->d_tab, h->d_tab ? h->d_tab + h->ntab : nullptr, h->ntab, h->d_modetab,
+                           h->d_modetab + nphi, nphi, mf, mc, d_P_out + (m_count - mc) * DD);
+    if (sign_odd) launch_negate_odd_modes(s, DD, m_first, m_count, d_P_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int sosrt_phase_p0_modes_dev(sosrt_t* h, int B, int kind, double g, int m_first, int m_count, int nphi, const double* d_mu0,
                              double* d_P0_out) {
     if (int e = modes_check(h, kind, g, m_first, m_count, nphi)) return e;
@@ -2534,6 +2735,19 @@ int sosrt_azimuth_accumulate_dev(sosrt_t* h, int B, int m, const double* d_Im, i
     if ((long long)B * nlev > 0x7fffffffLL) return fail(SOSRT_E_INVALID, "azimuth accumulate: B * nlev too large");
     HIPCHK(hipSetDevice(h->device));
     launch_azimuth_accumulate(h->stream, h->g, B, m, d_Im, nlev, d_levels, nphi_out, d_phi, d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_azimuth_synthesize_dev(sosrt_t* h, int B, int M, const double* d_I0, const double* d_Im, int nlev, const int* d_levels,
+                                 int nphi_out, const double* d_phi, double* d_out) {
+    if (int e = need_gpu(h)) return e;
+    if (B < 1 || M < 0 || M > SOSRT_MAX_MODES || nlev < 1 || nphi_out < 1 || !d_I0 || (M > 0 && !d_Im) || !d_levels || !d_phi || !d_out)
+        return fail(SOSRT_E_INVALID, "azimuth synthesize: bad argument (B=%d M=%d nlev=%d nphi_out=%d; M is at most SOSRT_MAX_MODES = %d)",
+                    B, M, nlev, nphi_out, SOSRT_MAX_MODES);
+    if ((long long)B * nlev > 0x7fffffffLL) return fail(SOSRT_E_INVALID, "azimuth synthesize: B * nlev too large");
+    HIPCHK(hipSetDevice(h->device));
+    launch_azimuth_synthesize(h->stream, h->g, B, M, d_I0, d_Im, nlev, d_levels, nphi_out, d_phi, d_out);
     HIPCHK(hipGetLastError());
     return 0;
 }

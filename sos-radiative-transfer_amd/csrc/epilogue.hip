@@ -302,6 +302,9 @@ __global__ __launch_bounds__(256) void k_phase_p0_modes(Grid g, const double* __
         for (int j = 0; j < mc; ++j) P0[j * BD + m] = P0[j * BD + m] / norm * 2;
 }
 
+// one term of the synthesis, sum_m (2 - delta_m0) I^m cos(m phi): both kernels below add it, in ascending m
+__device__ __forceinline__ double azimuth_term(double acc, double v, int m, double phi) { return acc + 2 * v * cos(m * phi); }
+
 // out[b][lev][dir][j]: mode 0 writes I^0 itself, modes m >= 1 add 2 I^m cos(m phi_j).  One workgroup per (column, level);
 // a level outside [0, L) gives NaN rows instead of a read out of bounds.
 __global__ __launch_bounds__(256) void k_azimuth_accumulate(int L, int D, int m, const double* __restrict__ Im, int nlev,
@@ -317,8 +320,40 @@ __global__ __launch_bounds__(256) void k_azimuth_accumulate(int L, int D, int m,
         const int dir = i / nphi, j = i - dir * nphi;
         const double v = ok ? row[dir] : __builtin_nan("");
         if (m == 0) o[i] = v;
-        else o[i] += 2 * v * cos(m * phi[j]);
+        else o[i] = azimuth_term(o[i], v, m, phi[j]);
     }
+}
+
+// The same sum over all modes in one launch: I0 [B][L][D] is mode 0, Im [M][B][L][D] the modes 1..M; `out` is written once
+// instead of read and rewritten per mode.  The terms are added in ascending m: the bits of the sequence of launches above.
+__global__ __launch_bounds__(256) void k_azimuth_synthesize(int B, int L, int D, int M, const double* __restrict__ I0,
+                                                            const double* __restrict__ Im, int nlev,
+                                                            const int* __restrict__ levels, int nphi,
+                                                            const double* __restrict__ phi, double* __restrict__ out) {
+    const int b = blockIdx.x / nlev, lev = blockIdx.x % nlev;
+    const int t = levels[lev];
+    const bool ok = t >= 0 && t < L;
+    const size_t ro = ((size_t)b * L + (ok ? t : 0)) * D, BLD = (size_t)B * L * D;
+    double* o = out + (size_t)blockIdx.x * D * nphi;
+    const int n = D * nphi;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int dir = i / nphi, j = i - dir * nphi;
+        const double ph = phi[j];
+        double acc = ok ? I0[ro + dir] : __builtin_nan("");
+        for (int m = 1; m <= M; ++m) {
+            const double v = ok ? Im[(size_t)(m - 1) * BLD + ro + dir] : __builtin_nan("");
+            acc = azimuth_term(acc, v, m, ph);
+        }
+        o[i] = acc;
+    }
+}
+
+// sosrt_phase_modes_dev, sign_odd: mode m is handed on as (-1)^m P^m (negation is exact)
+__global__ void k_negate_odd_modes(size_t n, int m_first, int m_count, double* __restrict__ P) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int j = 0; j < m_count; ++j)
+        if ((m_first + j) & 1) P[(size_t)j * n + i] = -P[(size_t)j * n + i];
 }
 
 
@@ -577,6 +612,15 @@ void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B,
 void launch_azimuth_accumulate(hipStream_t s, const Grid& g, int B, int m, const double* Im, int nlev, const int* levels,
                                int nphi_out, const double* phi, double* out) {
     hipLaunchKernelGGL(k_azimuth_accumulate, dim3(B * nlev), dim3(256), 0, s, g.L, g.D, m, Im, nlev, levels, nphi_out, phi, out);
+}
+
+void launch_azimuth_synthesize(hipStream_t s, const Grid& g, int B, int M, const double* I0, const double* Im, int nlev,
+                               const int* levels, int nphi_out, const double* phi, double* out) {
+    hipLaunchKernelGGL(k_azimuth_synthesize, dim3(B * nlev), dim3(256), 0, s, B, g.L, g.D, M, I0, Im, nlev, levels, nphi_out, phi, out);
+}
+
+void launch_negate_odd_modes(hipStream_t s, size_t n, int m_first, int m_count, double* P) {
+    hipLaunchKernelGGL(k_negate_odd_modes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, m_first, m_count, P);
 }
 
 void launch_mie_coefficients(hipStream_t s, int nlanes, int R, int n_cap, const double* x, const int* nmax, const int* nstart,

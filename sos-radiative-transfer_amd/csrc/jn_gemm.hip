@@ -79,8 +79,10 @@ __device__ __forceinline__ void write_live_list(const GemmArgs& g) {
     for (int i = before + tid; i < g.live_cap; i += 256) g.live_list[i] = -1;
 }
 
-template <bool SYM>
-__global__ __launch_bounds__(256, GEMM_WPS) void k_jn_gemm(GemmArgs g) {
+// ATM (here and below): the kernel of a batch with atmosphere phase sets in use -- its plain rows are always in the low-rank
+// form, a row with the factors of its column's set (AtmSets); symmetric form only
+template <bool SYM, bool ATM>
+__device__ __forceinline__ void jn_gemm_dense(const GemmArgs& g, const AtmSets& at) {
     if (g.live_list && blockIdx.x == gridDim.x - 1) {    // (the launch's extra workgroup: launch_gemm)
         write_live_list(g);
         return;
@@ -100,10 +102,10 @@ __global__ __launch_bounds__(256, GEMM_WPS) void k_jn_gemm(GemmArgs g) {
     int tile = (id / (8 * nct)) * 8 + (id & 7);
     const int bn0 = ((id >> 3) % nct) * GEMM_BN;
     if (tile >= tiles) return;
-    if (g.lr_rank >= 0) {
+    if (ATM || g.lr_rank >= 0) {
         // low-rank plain rows: a stream, the short tiles -- the slab tiles go first (renumbered to the end of the MFMA form's order)
         if (tile >= tiles_slab) {
-            lowrank_tile<false>(g, ListRows{g.rows_main, g.n_main}, tile - tiles_slab, 16 * GEMM_RT, bn0, true);
+            lowrank_tile<false, ListRows, ATM>(g, ListRows{g.rows_main, g.n_main}, tile - tiles_slab, 16 * GEMM_RT, bn0, true, at);
             return;
         }
         tile += tiles_main;
@@ -129,6 +131,9 @@ __global__ __launch_bounds__(256, GEMM_WPS) void k_jn_gemm(GemmArgs g) {
         gemm_tile<DENSE_SLAB_RT, true, false, SYM>(g, sA, sB, &s_any, tile - tiles_main, bn0, ListRows{g.rows_slab, g.n_slab}, true);
     }
 }
+template <bool SYM>
+__global__ __launch_bounds__(256, GEMM_WPS) void k_jn_gemm(GemmArgs g) { jn_gemm_dense<SYM, false>(g, AtmSets()); }
+__global__ __launch_bounds__(256, GEMM_WPS) void k_jn_gemm_atm(GemmArgs g, AtmSets at) { jn_gemm_dense<true, true>(g, at); }
 
 // The same contraction once some columns have converged.  Tiling the row lists would launch a
 // workgroup for every tile of every column, and the few live tiles would queue behind thousands of
@@ -136,8 +141,8 @@ __global__ __launch_bounds__(256, GEMM_WPS) void k_jn_gemm(GemmArgs g) {
 // workgroup finds the i-th live column itself (a prefix count over the live flags) and tiles that
 // column's rows: 16-row tiles for the slab rows, scheduled first because their double pass over k is
 // the critical path of the launch, then the tiles of the plain rows.
-template <int RT, bool DEEP, bool SYM>
-__device__ __forceinline__ void gemm_live_columns(const GemmArgs& g, double* sA, double* sB) {
+template <int RT, bool DEEP, bool SYM, bool ATM = false>
+__device__ __forceinline__ void gemm_live_columns(const GemmArgs& g, double* sA, double* sB, const AtmSets& at = AtmSets()) {
     __shared__ int s_w[4];
     __shared__ int s_col;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -156,7 +161,7 @@ __device__ __forceinline__ void gemm_live_columns(const GemmArgs& g, double* sA,
     const int tq = xq / cap, ci = xq % cap;
     if (tq >= ts + tm) return;                           // (uniform) padding of the grid
     // (low-rank plain rows: they are the short tiles, the slab tiles go first)
-    const int tt = g.lr_rank >= 0 ? tq : (tq < tm ? ts + tq : tq - tm);   // tt < ts: slab tile tt; else plain tile tt - ts
+    const int tt = (ATM || g.lr_rank >= 0) ? tq : (tq < tm ? ts + tq : tq - tm);   // tt < ts: slab tile tt; else plain tile tt - ts
 #else
     const int ci = xq / (ts + tm), tt = xq % (ts + tm);
 #endif
@@ -199,7 +204,7 @@ __device__ __forceinline__ void gemm_live_columns(const GemmArgs& g, double* sA,
     } else {
         const int t2 = tt - ts;
         if (t2 * 16 * RT >= g.L - ns) return;
-        if (g.lr_rank >= 0) lowrank_tile<false>(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, t2, 16 * RT, bn0, false);
+        if (ATM || g.lr_rank >= 0) lowrank_tile<false, ColumnRows, ATM>(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, t2, 16 * RT, bn0, false, at);
         else gemm_tile<RT, false, DEEP, SYM>(g, sA, sB, nullptr, t2, bn0, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, false);
     }
 }
@@ -211,6 +216,12 @@ __global__ __launch_bounds__(256, SYM ? 4 : GEMM_WPS) void k_jn_gemm_cols(GemmAr
     __shared__ double sA[(SYM ? 2 : 1) * 16 * GEMM_RT * A_LD];
     __shared__ double sB[GEMM_KC * B_LD];
     gemm_live_columns<GEMM_RT, false, SYM>(g, sA, sB);
+}
+__global__ __launch_bounds__(256, 4) void k_jn_gemm_cols_atm(GemmArgs g, AtmSets at) {
+    publish_live(g);
+    __shared__ double sA[2 * 16 * GEMM_RT * A_LD];
+    __shared__ double sB[GEMM_KC * B_LD];
+    gemm_live_columns<GEMM_RT, false, true, true>(g, sA, sB, at);
 }
 // few live columns: 32-row tiles (more workgroups, so more CUs take part) and deeper staging, since
 // such a workgroup is alone on its CU
@@ -226,6 +237,12 @@ __global__ __launch_bounds__(256, SYM ? kTailWpsSym : 2) void k_jn_gemm_tail(Gem
     __shared__ double sB[GEMM_KC * B_LD];
     gemm_live_columns<TAIL_RT, SYM ? kTailDeepSym : true, SYM>(g, sA, sB);
 }
+__global__ __launch_bounds__(256, kTailWpsSym) void k_jn_gemm_tail_atm(GemmArgs g, AtmSets at) {
+    publish_live(g);
+    __shared__ double sA[2 * 16 * TAIL_RT * A_LD];
+    __shared__ double sB[GEMM_KC * B_LD];
+    gemm_live_columns<TAIL_RT, kTailDeepSym, true, true>(g, sA, sB, at);
+}
 // the last few columns (at most kTailDeepCols live): a workgroup is alone on its CU and every k-chunk is a trip to L2 or HBM that
 // nothing else hides, so both operands are staged two chunks ahead (the register budget no longer matters: one workgroup per CU)
 constexpr int kTailDeepCols = 32;
@@ -235,13 +252,20 @@ __global__ __launch_bounds__(256, 2) void k_jn_gemm_tail_deep(GemmArgs g) {
     __shared__ double sB[GEMM_KC * B_LD];
     gemm_live_columns<TAIL_RT, true, true>(g, sA, sB);
 }
+__global__ __launch_bounds__(256, 2) void k_jn_gemm_tail_deep_atm(GemmArgs g, AtmSets at) {
+    publish_live(g);
+    __shared__ double sA[2 * 16 * TAIL_RT * A_LD];
+    __shared__ double sB[GEMM_KC * B_LD];
+    gemm_live_columns<TAIL_RT, true, true, true>(g, sA, sB, at);
+}
 
 // the last handful of columns (api.hip: plan_order, SOSRT_PLAN_GEMM_LIVE16_REGS): one tile's latency is the launch's, so the tile
 // keeps its share of the folded matrix in registers and has no barrier in its k-loop (jn_gemm_tile.hpp: gemm_tile_lone), and the
 // way to the tile is three memory round trips -- live flags; the column's slab rows and matrix group, requested together; operands
 // -- with the report to the host on a workgroup of its own (the last one: its release at system scope and the load in front of it
 // would otherwise be in front of the first tile).  Tile-major numbering as in gemm_live_columns, 16-row tiles for all rows.
-__global__ __launch_bounds__(256, 1) void k_jn_gemm_lone(GemmArgs g) {
+template <bool ATM>
+__device__ __forceinline__ void jn_gemm_lone(const GemmArgs& g, const AtmSets& at) {
     extern __shared__ __attribute__((aligned(16))) double s_lone[];
     __shared__ int s_w[4];
     __shared__ int s_col[4];                             // the tile's column, its first slab row, slab rows, matrix group
@@ -258,7 +282,7 @@ __global__ __launch_bounds__(256, 1) void k_jn_gemm_lone(GemmArgs g) {
     const int tq = xq / cap, ci = xq % cap;
     if (tq >= ts + tm) return;                           // (uniform) padding of the grid
     // tt < ts: slab tile tt; else plain tile tt - ts (the short slab tiles last -- low-rank plain rows: those are the short ones)
-    const int tt = g.lr_rank >= 0 ? tq : (tq < tm ? ts + tq : tq - tm);
+    const int tt = (ATM || g.lr_rank >= 0) ? tq : (tq < tm ? ts + tq : tq - tm);
     // The ci-th live column of the launch and, in the same round trip, what the tile needs to know of it: every thread looks at
     // one candidate column's flag and descriptors.  The requests of the first 256 candidates leave before anything else ...
     int fl = 0, iu_c = 0, id_c = -1, mg_c = 0;
@@ -273,7 +297,7 @@ __global__ __launch_bounds__(256, 1) void k_jn_gemm_lone(GemmArgs g) {
     // ... and behind them, for a plain tile, the first two register blocks of its matrix: W_atm whatever the column
     LoneFrag f0, f1;
     const int nkb = (g.Ks >> 2) / LONE_KB;
-    if (tt >= ts && g.lr_rank < 0) {
+    if (!ATM && tt >= ts && g.lr_rank < 0) {
         const int mcol = (bn0 >> 1) + (__builtin_amdgcn_readfirstlane(tid) >> 6) * 16 + (lane & 15);
         const __amdgpu_buffer_rsrc_t rW = make_rsrc(g.Wa, g.Dp * g.Wld * 8);
         lone_load(f0, rW, 0, lane >> 4, g.Wld, g.Wld >> 1, mcol);
@@ -322,14 +346,16 @@ __global__ __launch_bounds__(256, 1) void k_jn_gemm_lone(GemmArgs g) {
         } else gemm_tile_lone<true, false>(g, s_lone, tt, bn0, ColumnRows{b * g.L, iu, ns, ns, true}, f0, f1);
     } else {
         if ((tt - ts) * 16 >= g.L - ns) return;
-        if (g.lr_rank >= 0) lowrank_tile<false>(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, tt - ts, 16, bn0, false);
+        if (ATM || g.lr_rank >= 0) lowrank_tile<false, ColumnRows, ATM>(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, tt - ts, 16, bn0, false, at);
         else gemm_tile_lone<false, true>(g, s_lone, tt - ts, bn0, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, f0, f1);
     }
 }
+__global__ __launch_bounds__(256, 1) void k_jn_gemm_lone(GemmArgs g) { jn_gemm_lone<false>(g, AtmSets()); }
+__global__ __launch_bounds__(256, 1) void k_jn_gemm_lone_atm(GemmArgs g, AtmSets at) { jn_gemm_lone<true>(g, at); }
 
 }  // namespace
 
-void launch_gemm_tail(hipStream_t s, const GemmArgs& a, int cols, bool small_tiles, bool regs) {
+void launch_gemm_tail(hipStream_t s, const GemmArgs& a, int cols, bool small_tiles, bool regs, const AtmSets* at) {
     if (regs && a.sym) {
         const int ts = (a.max_slab + 15) / 16, tm = (a.max_main + 15) / 16;
         if (cols <= 0 || ts + tm <= 0) return;
@@ -338,9 +364,12 @@ void launch_gemm_tail(hipStream_t s, const GemmArgs& a, int cols, bool small_til
         static PerDeviceOnce big_lds;                           // (more than 64 KB of dynamic LDS from N = 256 on)
         if (big_lds.first()) {
             hipFuncSetAttribute(reinterpret_cast<const void*>(k_jn_gemm_lone), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+            hipFuncSetAttribute(reinterpret_cast<const void*>(k_jn_gemm_lone_atm), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         }
         // (+ 1: the workgroup that reports to the host)
-        hipLaunchKernelGGL(k_jn_gemm_lone, dim3((unsigned)((cols * (ts + tm) + 7) / 8 * 8 * nct + 1)), dim3(256), (size_t)lds, s, a);
+        const dim3 lgrid((unsigned)((cols * (ts + tm) + 7) / 8 * 8 * nct + 1));
+        if (at) hipLaunchKernelGGL(k_jn_gemm_lone_atm, lgrid, dim3(256), (size_t)lds, s, a, *at);
+        else hipLaunchKernelGGL(k_jn_gemm_lone, lgrid, dim3(256), (size_t)lds, s, a);
         return;
     }
     const int rt = small_tiles ? TAIL_RT : GEMM_RT;
@@ -349,6 +378,12 @@ void launch_gemm_tail(hipStream_t s, const GemmArgs& a, int cols, bool small_til
     if (cols <= 0 || ts + tm <= 0) return;
     const int nct = (a.D + GEMM_BN - 1) / GEMM_BN;
     dim3 grid((unsigned)((cols * (ts + tm) + 7) / 8 * 8 * nct));
+    if (at) {                                            // atmosphere sets in use (api.hip: symmetric form only)
+        if (small_tiles && cols <= kTailDeepCols) hipLaunchKernelGGL(k_jn_gemm_tail_deep_atm, grid, dim3(256), 0, s, a, *at);
+        else if (small_tiles) hipLaunchKernelGGL(k_jn_gemm_tail_atm, grid, dim3(256), 0, s, a, *at);
+        else hipLaunchKernelGGL(k_jn_gemm_cols_atm, grid, dim3(256), (size_t)a.pad_lds, s, a, *at);
+        return;
+    }
     if (small_tiles) {
         if (a.sym && cols <= kTailDeepCols) hipLaunchKernelGGL(k_jn_gemm_tail_deep, grid, dim3(256), 0, s, a);
         else if (a.sym) hipLaunchKernelGGL(k_jn_gemm_tail<true>, grid, dim3(256), 0, s, a);
@@ -361,7 +396,8 @@ void launch_gemm_tail(hipStream_t s, const GemmArgs& a, int cols, bool small_til
 
 // Wmix[g] = ca[g] W_atm + cr[g] W_aer for every distinct slab coefficient pair of the batch; with several aerosol phase sets
 // (gset: the set of a group, Wr: [sets][n]) a group is a distinct (set, ca, cr) and reads the W_aer of its set -- the same
-// expression, so a group's matrix has the bits it has in a batch of its set alone
+// expression, so a group's matrix has the bits it has in a batch of its set alone; with atmosphere sets in use (gatm: Wa is
+// [sets][n]) a group is a distinct (atmosphere set, aerosol set, ca, cr) and reads the W_atm of its set as well
 __global__ void k_wmix(size_t n, int ngroups, const double* __restrict__ Wa, const double* __restrict__ Wr,
                        const double* __restrict__ ca, const double* __restrict__ cr, double* __restrict__ Wmix,
                        const int* __restrict__ gset) {
@@ -378,9 +414,23 @@ __global__ void k_wmix(size_t n, int ngroups, const double* __restrict__ Wa, con
     const double a = Wa[i], r = Wr[i];
     for (int gq = 0; gq < ngroups; ++gq) Wmix[(size_t)gq * n + i] = ca[gq] * a + cr[gq] * r;
 }
+// atmosphere sets too (a kernel of its own: k_wmix stays the code it was)
+__global__ void k_wmix_atm(size_t n, int ngroups, const double* __restrict__ Wa, const double* __restrict__ Wr,
+                           const double* __restrict__ ca, const double* __restrict__ cr, double* __restrict__ Wmix,
+                           const int* __restrict__ gset, const int* __restrict__ gatm) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int gq = 0; gq < ngroups; ++gq) {
+        const double a = Wa[(size_t)gatm[gq] * n + i];
+        const double r = Wr[(size_t)(gset ? gset[gq] : 0) * n + i];
+        Wmix[(size_t)gq * n + i] = ca[gq] * a + cr[gq] * r;
+    }
+}
 void launch_wmix(hipStream_t s, size_t n, int ngroups, const double* Wa, const double* Wr, const double* ca, const double* cr,
-                 double* Wmix, const int* gset) {
-    hipLaunchKernelGGL(k_wmix, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, ngroups, Wa, Wr, ca, cr, Wmix, gset);
+                 double* Wmix, const int* gset, const int* gatm) {
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (gatm) hipLaunchKernelGGL(k_wmix_atm, grid, dim3(256), 0, s, n, ngroups, Wa, Wr, ca, cr, Wmix, gset, gatm);
+    else hipLaunchKernelGGL(k_wmix, grid, dim3(256), 0, s, n, ngroups, Wa, Wr, ca, cr, Wmix, gset);
 }
 
 // The fold of sosrt_set_phase on the device: W[q][k][m] = w_k P[q][m][D-1-k] for S matrices P [S][D][D] -> W [S][Dp][Wld]
@@ -444,13 +494,14 @@ void launch_fold_asymmetry(hipStream_t s, int S, int nblk, int D, int Wld, size_
     hipLaunchKernelGGL(k_fold_asymmetry, dim3((unsigned)nblk, (unsigned)S), dim3(256), 0, s, D, Wld, per, W, out);
 }
 
-void launch_gemm(hipStream_t s, const GemmArgs& a) {
+void launch_gemm(hipStream_t s, const GemmArgs& a, const AtmSets* at) {
     const int tiles = (a.n_main + 16 * GEMM_RT - 1) / (16 * GEMM_RT) + (a.n_slab + DENSE_SLAB_ROWS - 1) / DENSE_SLAB_ROWS;
     if (tiles <= 0) return;
     const int nct = (a.D + GEMM_BN - 1) / GEMM_BN;
     // (+ 1 with a live list: the workgroup that writes it)
     dim3 grid((unsigned)((tiles + 7) / 8 * 8 * nct + (a.live_list ? 1 : 0)));
-    if (a.sym) hipLaunchKernelGGL(k_jn_gemm<true>, grid, dim3(256), (size_t)a.pad_lds, s, a);
+    if (at) hipLaunchKernelGGL(k_jn_gemm_atm, grid, dim3(256), (size_t)a.pad_lds, s, a, *at);
+    else if (a.sym) hipLaunchKernelGGL(k_jn_gemm<true>, grid, dim3(256), (size_t)a.pad_lds, s, a);
     else hipLaunchKernelGGL(k_jn_gemm<false>, grid, dim3(256), (size_t)a.pad_lds, s, a);
 }
 

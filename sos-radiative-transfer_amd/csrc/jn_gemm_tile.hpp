@@ -429,12 +429,19 @@ __device__ __forceinline__ void gemm_tile_lone(const GemmArgs& g, double* sRaw, 
 // so a row's bits do not depend on the tiling, the batch or the launch.  rows[i] < 0: no row.  COH: the order loop's loads past
 // the L1 and write-through stores (gemm_tile, COH).
 constexpr int LR_ROWS = 4;
-template <bool COH>
-__device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows)[LR_ROWS], int lane) {
+// ATM (atmosphere phase sets in use, `at`): a row's factors and rank are those of its column's set (row / L -> column -> set),
+// so the LR_ROWS rows of a wave may read LR_ROWS different U, V and ranks -- all wave-uniform.  A row's sums are formed exactly as
+// without the flag (same elements per lane, same order of j, same butterfly, same order of q in the expansion): a column on set s
+// has the bits of a handle whose W_atm is that set.  A set of rank 0 writes zeros.
+template <bool COH, bool ATM = false>
+__device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows)[LR_ROWS], int lane, const AtmSets& at = AtmSets()) {
     const int D = g.D, R = g.lr_rank;
     // (a missing row: a buffer of no bytes -- its loads return zeros, its stores are dropped)
     __amdgpu_buffer_rsrc_t rA[LR_ROWS], rC[LR_ROWS];
     double cf[LR_ROWS];
+    int Ri[LR_ROWS];
+    const double* __restrict__ Ui[LR_ROWS];
+    const double* __restrict__ Vi[LR_ROWS];
 #pragma unroll
     for (int i = 0; i < LR_ROWS; ++i) {
         const int r = rows[i] >= 0 ? rows[i] : rows[0];
@@ -442,6 +449,12 @@ __device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows
         rA[i] = make_rsrc(g.A + (size_t)r * D, bytes);
         rC[i] = make_rsrc(g.C + (size_t)r * D, bytes);
         cf[i] = rows[i] >= 0 ? g.ca[rows[i]] : 0.0;
+        if constexpr (ATM) {
+            const int st = __builtin_amdgcn_readfirstlane(at.col_atm[r / g.L]);
+            Ri[i] = __builtin_amdgcn_readfirstlane(at.lr_ranks[st]);
+            Ui[i] = g.lrU + (size_t)st * kLowRankMax * D;
+            Vi[i] = g.lrV + (size_t)st * kLowRankMax * D;
+        }
     }
     const double* __restrict__ U = g.lrU;
     const double* __restrict__ V = g.lrV;
@@ -457,7 +470,14 @@ __device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows
         for (int i = 0; i < LR_ROWS; ++i) x[i] = bload2_aux<COH ? 16 : 0>(rA[i], k * 8, 0);
 #pragma unroll
         for (int q = 0; q < kLowRankMax; ++q) {
-            if (q < R) {
+            if constexpr (ATM) {
+#pragma unroll
+                for (int i = 0; i < LR_ROWS; ++i)
+                    if (q < Ri[i]) {
+                        const double2 u = *reinterpret_cast<const double2*>(Ui[i] + (size_t)q * D + k);
+                        m[i][q] = __builtin_fma(x[i].y, u.y, __builtin_fma(x[i].x, u.x, m[i][q]));
+                    }
+            } else if (q < R) {
                 const double2 u = *reinterpret_cast<const double2*>(U + (size_t)q * D + k);
 #pragma unroll
                 for (int i = 0; i < LR_ROWS; ++i) m[i][q] = __builtin_fma(x[i].y, u.y, __builtin_fma(x[i].x, u.x, m[i][q]));
@@ -468,11 +488,16 @@ __device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1)
 #pragma unroll
-        for (int q = 0; q < kLowRankMax; ++q)
-            if (q < R) {
+        for (int q = 0; q < kLowRankMax; ++q) {
+            if constexpr (ATM) {
+#pragma unroll
+                for (int i = 0; i < LR_ROWS; ++i)
+                    if (q < Ri[i]) m[i][q] += __shfl_xor(m[i][q], s);
+            } else if (q < R) {
 #pragma unroll
                 for (int i = 0; i < LR_ROWS; ++i) m[i][q] += __shfl_xor(m[i][q], s);
             }
+        }
 #pragma unroll 2
     for (int k = 2 * lane; k < D; k += 128) {
         double2 o[LR_ROWS];
@@ -480,7 +505,15 @@ __device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows
         for (int i = 0; i < LR_ROWS; ++i) o[i] = make_double2(0.0, 0.0);
 #pragma unroll
         for (int q = 0; q < kLowRankMax; ++q) {
-            if (q < R) {
+            if constexpr (ATM) {
+#pragma unroll
+                for (int i = 0; i < LR_ROWS; ++i)
+                    if (q < Ri[i]) {
+                        const double2 v = *reinterpret_cast<const double2*>(Vi[i] + (size_t)q * D + k);
+                        o[i].x = __builtin_fma(m[i][q], v.x, o[i].x);
+                        o[i].y = __builtin_fma(m[i][q], v.y, o[i].y);
+                    }
+            } else if (q < R) {
                 const double2 v = *reinterpret_cast<const double2*>(V + (size_t)q * D + k);
 #pragma unroll
                 for (int i = 0; i < LR_ROWS; ++i) {
@@ -496,8 +529,9 @@ __device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows
 // A tile's plain rows in the low-rank form, where the MFMA tilings would have put a tile of BM rows x GEMM_BN columns of Jn: the
 // workgroup of column tile ct (of nct) takes the rows lr = ct + nct j of the tile, its waves LR_ROWS rows at a time.
 // check_active: rows of converged columns are skipped (the dense tiling's check of its tiles).
-template <bool COH, class RowOf>
-__device__ __forceinline__ void lowrank_tile(const GemmArgs& g, RowOf row_of, int tile, int BM, int bn0, bool check_active) {
+template <bool COH, class RowOf, bool ATM = false>
+__device__ __forceinline__ void lowrank_tile(const GemmArgs& g, RowOf row_of, int tile, int BM, int bn0, bool check_active,
+                                             const AtmSets& at = AtmSets()) {
     const int nct = (g.D + GEMM_BN - 1) / GEMM_BN, ct = bn0 / GEMM_BN;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x) >> 6;
     const int per = (BM - ct + nct - 1) / nct;           // rows of this workgroup
@@ -517,7 +551,7 @@ __device__ __forceinline__ void lowrank_tile(const GemmArgs& g, RowOf row_of, in
 #pragma unroll
             for (int i = 1; i < LR_ROWS; ++i)
                 if (rows[i] >= 0) { rows[0] = rows[i]; rows[i] = -1; break; }
-        lowrank_rows<COH>(g, rows, lane);
+        lowrank_rows<COH, ATM>(g, rows, lane, at);
     }
 }
 

@@ -217,6 +217,13 @@ struct GemmArgs {
     const double* lrU = nullptr;     // [kLowRankMax][D]: lrU[q][k] = U[k][q]
     const double* lrV = nullptr;     // [kLowRankMax][D]: lrV[q][m] = V[q][m]
 };
+// Atmosphere phase sets in use (sosrt_set_atmosphere_sets): a plain row takes the factors of its column's set.  The launches
+// that read this are kernels of their own (jn_gemm.hip, *_atm) with this as a second argument, and GemmArgs::lrU / lrV are then
+// [sets][kLowRankMax][D]; the kernels of a handle without such sets are the code, and the arguments, they always were.
+struct AtmSets {
+    const int* col_atm = nullptr;    // [batch] atmosphere set of a column (indexed like GemmArgs::active)
+    const int* lr_ranks = nullptr;   // [sets] rank of a set's factors (0 .. kLowRankMax)
+};
 constexpr int kLowRankMax = 4;
 
 // (publish_live_now: by the calling thread, whichever workgroup it belongs to)
@@ -242,7 +249,7 @@ struct PerDeviceOnce {
         return true;
     }
 };
-void launch_gemm(hipStream_t s, const GemmArgs& a);
+void launch_gemm(hipStream_t s, const GemmArgs& a, const AtmSets* at = nullptr);
 struct OrderLoopArgs {
     TransportArgs t;           // the column group's view (every per-column pointer offset to its first column): g, tau, Jn, I, desc, cv, Etab, erep, scan_scratch, scan_sync
     GemmArgs gm;               // the batch's view (whole-batch pointers, global column ids): folded matrices, Wmix, mix_group, idx_up / idx_down, ca / cr, C = Jn
@@ -268,7 +275,8 @@ hipError_t launch_order_loop(hipStream_t s, int grid, bool split, const OrderLoo
 void launch_gemm_f32(hipStream_t s, const GemmArgs& a, const float* Wa32, const float* Wmix32);
 void launch_to_float(hipStream_t s, size_t n, const double* src, float* dst);
 void launch_wmix(hipStream_t s, size_t n, int ngroups, const double* Wa, const double* Wr, const double* ca, const double* cr,
-                 double* Wmix, const int* gset = nullptr /* [ngroups] aerosol set of a group: Wr is then [sets][n] */);
+                 double* Wmix, const int* gset = nullptr /* [ngroups] aerosol set of a group: Wr is then [sets][n] */,
+                 const int* gatm = nullptr /* [ngroups] atmosphere set of a group: Wa is then [sets][n] */);
 // device fold of S phase matrices P [S][D][D] into W [S][Dp][Wld] (W[k][m] = w_k P[m][D-1-k], the host fold's bits), and the
 // partial maxima {max |W|, max |W - flip W|} of its flip-asymmetry measure, out [S][nblk][2]
 void launch_fold_sets(hipStream_t s, int S, int D, int Wld, size_t per, const double* w, const double* P, double* W);
@@ -277,7 +285,7 @@ void launch_fold_asymmetry(hipStream_t s, int S, int nblk, int D, int Wld, size_
 void launch_symfold(hipStream_t s, int nmat, int N, int D, int Dp, int Wld, const double* W, double* SA);
 // some columns have converged (at most `cols` are live, an upper bound): workgroups only for live
 // columns; small_tiles: 32-row tiles and deeper staging for the last few
-void launch_gemm_tail(hipStream_t s, const GemmArgs& a, int cols, bool small_tiles, bool regs = false);
+void launch_gemm_tail(hipStream_t s, const GemmArgs& a, int cols, bool small_tiles, bool regs = false, const AtmSets* at = nullptr);
 void launch_smallmu(hipStream_t s, const Grid& g, int B, const double* tau, const double* Jn, double* In,
                     const ColDesc* desc, const int* active);
 void launch_transport(hipStream_t s, const Grid& g, int B, const double* tau, const double* Jn, double* In, double* I,
@@ -324,6 +332,12 @@ void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B,
 // out[b][lev][dir][j] (+)= (2 - delta_m0) I^m[b][levels[lev]][dir] cos(m phi[j])   (m == 0 writes, m >= 1 adds)
 void launch_azimuth_accumulate(hipStream_t s, const Grid& g, int B, int m, const double* Im, int nlev, const int* levels,
                                int nphi_out, const double* phi, double* out);
+// the whole sum in one launch: out[b][lev][dir][j] = I0[b][levels[lev]][dir] + sum_{m = 1..M} 2 Im[m-1][b][levels[lev]][dir] cos(m phi[j]),
+// the terms added in ascending m (the bits of the sequence of launches above)
+void launch_azimuth_synthesize(hipStream_t s, const Grid& g, int B, int M, const double* I0, const double* Im, int nlev,
+                               const int* levels, int nphi_out, const double* phi, double* out);
+// P[j] = -P[j] for the odd modes m_first + j of P [m_count][n] (sosrt_phase_modes_dev, sign_odd)
+void launch_negate_odd_modes(hipStream_t s, size_t n, int m_first, int m_count, double* P);
 // Lorenz-Mie tables (sosrt_mie_ensembles).  nlanes = S * R spheres, lane = s * R + i; x, nmax, nstart [nlanes]
 // (size parameter, terms of the series, start of the downward recurrence: from the host, mie.mie_coefficients' counts);
 // ab [nlanes][n_cap][4] and qw [nlanes][kMieQ] workspaces; tn [n_cap + 1]: (n + 1) / n; part [S][mie_chunks(R)][ntab].

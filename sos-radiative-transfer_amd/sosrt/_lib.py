@@ -51,6 +51,9 @@ SIGNATURES = {
     "sosrt_phase_matrix_dev": (c_int, [c_void_p, c_int, c_double, c_void_p]),
     "sosrt_set_aerosol_sets": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "sosrt_phase_sets_info": (c_int, [c_void_p, _ip]),
+    "sosrt_set_atm_phase_sets": (c_int, [c_void_p, c_int, c_void_p]),
+    "sosrt_set_atmosphere_sets": (c_int, [c_void_p, c_int, c_void_p]),
+    "sosrt_atm_sets_info": (c_int, [c_void_p, _ip]),
     "sosrt_set_columns": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 9),
     "sosrt_set_columns_zones": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 10),
     "sosrt_first_order": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -72,10 +75,12 @@ SIGNATURES = {
     "sosrt_phase_p0": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
     "sosrt_phase_matrix": (c_int, [c_void_p, c_int, c_double, c_void_p]),
     "sosrt_phase_modes": (c_int, [c_void_p, c_int, c_double, c_int, c_int, c_int, c_void_p]),
+    "sosrt_phase_modes_dev": (c_int, [c_void_p, c_int, c_double, c_int, c_int, c_int, c_int, c_void_p]),
     "sosrt_phase_p0_modes_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sosrt_phase_p0_modes": (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sosrt_set_order_targets": (c_int, [c_void_p, c_void_p]),
     "sosrt_azimuth_accumulate_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "sosrt_azimuth_synthesize_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_comm_unique_id": (c_int, [c_void_p]),
     "sosrt_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "sosrt_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

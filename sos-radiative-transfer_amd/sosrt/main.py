@@ -97,7 +97,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   mie_atm=None, mie_aer=None,
                   P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular", tol=1e-4, max_orders=256,
                   save_orders=False, device=0, devices=None, raise_on_error=True, first_order="coded", azimuths=None,
-                  n_modes=None, nphi_modes=None, levels=(0, -1), aer_set=None) -> BatchResult:
+                  n_modes=None, nphi_modes=None, levels=(0, -1), aer_set=None, mode_batch=False, mode_chunk=None) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -119,7 +119,16 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     BatchResult.I_azimuth [B, len(levels), 2N, len(azimuths)], from the Fourier modes m = 0 .. `n_modes` (default 16) of the
     phase functions (`azimuth_modes`; modes m >= 1 built on `nphi_modes` azimuth nodes, default max(25, 2 n_modes + 1)).  phi
     follows the reference's ring: phi = 0 with an upward mu = mu0 is exact back-scatter.  I, n and status are those of the
-    plain call, bit for bit.  Needs named phase functions (not arrays), the specular surface and a single device."""
+    plain call, bit for bit.  Needs named phase functions (not arrays), the specular surface and a single device.
+    `mode_batch=True` (opt-in; the default is the loop over the modes): the modes m >= 1 of all B columns are solved as ONE
+    batch of c x B columns per chunk of c modes, the mode as the atmosphere and aerosol phase set of its columns
+    (`azimuth_modes_batched`), and one launch sums all modes -- for a few columns, whose per-mode solves are bound by latency.
+    Same bits as the loop.  c is the largest count that keeps c B columns within MODE_BATCH_FIELD_BYTES per field buffer,
+    c x (distinct slab coefficient pairs) within the combined-matrix cache, and c <= 64; `mode_chunk=k` forces c = k.  The
+    atmosphere's modes must be low-rank (iso, Rayleigh): otherwise ValueError, and `mode_batch=False` works.  Memory: the chunk
+    bounds the handle's buffers only.  The fields of all modes wait for the one synthesis launch, n_modes x B x L x 2N doubles
+    whatever c is (the loop keeps one mode's); beyond MODE_BATCH_MODES_BYTES the call is refused.  The cached handle is made
+    c B columns wide and, like every widened handle of `get_solver`, stays that wide for later calls of this shape."""
     if aer_set is not None:
         if azimuths is not None:
             raise ValueError("azimuths are not available with aer_set (the mode driver swaps the handle's one pair of matrices per mode)")
@@ -131,7 +140,9 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         raise ValueError("several aerosols (a stack P_aer [S, 2N, 2N] or a list of names) need aer_set [B]")
     if azimuths is not None:
         M, nphi, lev = _azimuth_args(azimuths, n_modes, nphi_modes, levels, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface,
-                                     devices, first_order)
+                                     devices, first_order, mode_batch=mode_batch, mode_chunk=mode_chunk)
+    elif mode_batch or mode_chunk is not None:
+        raise ValueError("mode_batch / mode_chunk belong to the azimuth-resolved call: give azimuths")
     if devices is not None and len(devices) > 1:
         if save_orders:
             raise ValueError("save_orders is not available with devices=[...]")
@@ -148,6 +159,12 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         return r
     if devices is not None and len(devices) == 1:
         device = int(devices[0])
+    if azimuths is not None and mode_batch:
+        # the handle that serves the mode-0 solve below is the one that takes the batch of c x B columns: made wide enough here
+        cols = np.broadcast_arrays(*[np.atleast_1d(np.asarray(x, dtype=np.float64))
+                                     for x in (mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer)])
+        c_cap = _mode_chunk_cap(cols[0].shape[0], int(nb_layers), int(nb_angles), M, mode_chunk)
+        get_solver(int(nb_layers), int(nb_angles), c_cap * cols[0].shape[0], max_orders, device)
     s, tau, P0a, P0r, mu, iu, idn, N = _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
                                                       nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm,
                                                       mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device,
@@ -164,8 +181,15 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     out = BatchResult(I=r.I, n=r.n, status=r.status, tau=tau, mu=mu, idx_up=iu, idx_down=idn, I_saved=r.I_saved)
     if azimuths is not None:
         mu0v = np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
-        out.I_azimuth, out.mode_status = azimuth_modes(s, tau, r, mu0v, azimuths, M, nphi, lev, atm_phase_fun, g_atm, mie_atm,
-                                                       aer_phase_fun, g_aer, mie_aer, device)
+        if mode_batch:
+            L_ = tau.shape[1]
+            colargs = (np.full(tau.shape[0], iu), np.full(tau.shape[0], idn), cols[0], cols[2], cols[4], cols[5], cols[3] / L_,
+                       cols[1] / (idn + 1 - iu), cols[3] + cols[1])
+            out.I_azimuth, out.mode_status = azimuth_modes_batched(s, tau, r, colargs, azimuths, M, nphi, lev, atm_phase_fun, g_atm,
+                                                                   mie_atm, aer_phase_fun, g_aer, mie_aer, c_cap, device)
+        else:
+            out.I_azimuth, out.mode_status = azimuth_modes(s, tau, r, mu0v, azimuths, M, nphi, lev, atm_phase_fun, g_atm, mie_atm,
+                                                           aer_phase_fun, g_aer, mie_aer, device)
         if raise_on_error:
             _raise_status(out.mode_status, N)
     return out
@@ -291,8 +315,16 @@ def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=No
     return out, bulk
 
 
-def _azimuth_args(azimuths, n_modes, nphi_modes, levels, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface, devices, first_order):
+def _azimuth_args(azimuths, n_modes, nphi_modes, levels, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface, devices, first_order,
+                  mode_batch=False, mode_chunk=None):
     """Checks of the azimuth-resolved call, made before any handle exists: (M, nphi, levels as row indices)."""
+    if not isinstance(mode_batch, (bool, np.bool_)):
+        raise ValueError("mode_batch must be True or False (got %r)" % (mode_batch,))
+    if mode_chunk is not None:
+        if not mode_batch:
+            raise ValueError("mode_chunk is the chunk of mode_batch=True")
+        if isinstance(mode_chunk, (bool, np.bool_)) or not isinstance(mode_chunk, (int, np.integer)) or not 1 <= mode_chunk <= _lib.MAX_PHASE_SETS:
+            raise ValueError("mode_chunk must be an integer in 1..%d (got %r)" % (_lib.MAX_PHASE_SETS, mode_chunk))
     if any(x is not None for x in (P_atm, P_aer, P0_atm, P0_aer)):
         raise ValueError("azimuths need named phase functions: the Fourier modes cannot be derived from azimuth-averaged arrays")
     if surface != "specular" or first_order != "coded":
@@ -370,6 +402,122 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
             s.synchronize()
             s.set_order_targets(None)
             s.set_stream(None)
+            if P_mode0[0] is not None:
+                s.set_phase(*P_mode0)
+    return I_az, status
+
+
+# mode_batch=True: a chunk of c modes is a batch of c x B columns, and every field buffer of the handle (and the chunk's share of
+# the driver's) holds c B L 2N doubles.  The chunk is cut so that one such buffer stays within MODE_BATCH_FIELD_BYTES (2621
+# columns at L = 200, N = 128).  The chunk does not bound the whole call: the one synthesis launch at the end reads the fields of
+# ALL modes, so the driver holds M B L 2N doubles whatever c is (the loop holds one mode's) -- 3.4 GB for M = 16 modes of 512
+# columns at L = 200, N = 128.  A call whose modes exceed MODE_BATCH_MODES_BYTES is refused.
+MODE_BATCH_FIELD_BYTES = 1 << 30
+MODE_BATCH_MODES_BYTES = 16 << 30
+
+
+def _mode_chunk_cap(B, L, N, M, mode_chunk):
+    """Modes per chunk by the size of the field and the number of phase sets (the combined-matrix cache is asked later, of the
+    handle): the forced `mode_chunk`, or min(M, 64, what MODE_BATCH_FIELD_BYTES holds).  Refuses a call whose M fields
+    [B, L, 2N], which the driver keeps for the one synthesis launch whatever the chunk, exceed MODE_BATCH_MODES_BYTES."""
+    field = B * L * 2 * N * 8
+    if M * field > MODE_BATCH_MODES_BYTES:
+        raise ValueError("mode_batch=True keeps the fields of all %d modes of these %d columns for the synthesis: %d bytes, more than "
+                         "MODE_BATCH_MODES_BYTES = %d; mode_batch=False works" % (M, B, M * field, MODE_BATCH_MODES_BYTES))
+    if mode_chunk is not None:
+        return int(mode_chunk)
+    c = min(M, _lib.MAX_PHASE_SETS, MODE_BATCH_FIELD_BYTES // field)
+    if c < 1:
+        raise ValueError("mode_batch=True: one mode of these %d columns is a field of %d bytes, more than MODE_BATCH_FIELD_BYTES = %d; "
+                         "mode_batch=False works" % (B, field, MODE_BATCH_FIELD_BYTES))
+    return int(c)
+
+
+def azimuth_modes_batched(s: Solver, tau, r, colargs, azimuths, M, nphi, levels, atm_phase_fun, g_atm, mie_atm, aer_phase_fun,
+                          g_aer, mie_aer, c_cap, device=0):
+    """`azimuth_modes` with the modes solved as batches: a chunk of c modes is ONE solve of c x B columns with column index
+    (m, b) -- mode m as the atmosphere set and the aerosol set of its B columns (Solver.set_atm_phase_sets /
+    set_phase_sets_device), P0 rows from the mode builder's [m][B][2N] layout, tau, the column scalars `colargs` (the arguments
+    of `Solver.set_columns` for the B columns) and the order targets r.n tiled -- and one launch sums all modes.  Same return
+    value, same bits.  c = min(c_cap, cache of combined matrices // distinct slab coefficient pairs of the B columns).  The
+    handle's columns, mode-0 matrices and targets are put back afterwards, also on error."""
+    import torch
+    from .inputs import _scalar_phase
+    B, L = tau.shape
+    D = s.D
+    dev = torch.device("cuda", device)
+    P_mode0 = s._P
+    status = np.zeros((M + 1, B), dtype=np.int32)
+    status[0] = r.status
+    # distinct (ca, cr) of the columns' slabs, as the handle will count them per phase set (spec:321)
+    da, dr = colargs[6], colargs[7]
+    pairs = len({((wa / 4) * (a / (a + b)), (wr / 4) * (b / (a + b))) for wa, wr, a, b in zip(colargs[4], colargs[5], da, dr)})
+    cache = s.phase_sets_info()["group_cap"]
+    c = min(c_cap, cache // pairs, s.max_batch // B)
+    if c < 1:
+        raise ValueError("mode_batch=True: the %d distinct slab coefficient pairs of these columns do not fit the cache of %d combined "
+                         "matrices even for one mode; mode_batch=False works" % (pairs, cache))
+    tile = lambda v, k: np.tile(np.asarray(v), k)
+    with torch.cuda.device(dev):
+        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        try:
+            d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
+            d_mu0 = torch.from_numpy(np.array(colargs[2], dtype=np.float64)).to(dev)      # (a copy: broadcast views are read-only)
+            d_target = torch.from_numpy(np.ascontiguousarray(r.n, dtype=np.int32)).to(dev)
+            d_lev = torch.tensor(levels, dtype=torch.int32, device=dev)
+            d_phi = torch.from_numpy(np.ascontiguousarray(azimuths, dtype=np.float64)).to(dev)
+            nlev, nout = len(levels), d_phi.numel()
+            d_out = torch.empty((B, nlev, D, nout), dtype=torch.float64, device=dev)
+            d_I0 = torch.from_numpy(np.ascontiguousarray(r.I)).to(dev)
+            d_Im = torch.empty((M, B, L, D), dtype=torch.float64, device=dev)
+            # modes 1..M: the atmosphere's matrices to the host (their low-rank factorisation is host code), the aerosol's stay on
+            # the device, both as (-1)^m P^m (the solve of mode m reads the stored matrix at phi + pi); the first-order vectors
+            d_P0 = []
+            d_Paer = torch.empty((M, D, D), dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            for which, (name, g, mie) in enumerate(((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer))):
+                kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **(mie or {}))[1]
+                if tab is not None:
+                    s.set_phase_table(*tab)
+                if which == 0:
+                    sgn = np.where(np.arange(1, M + 1) & 1, -1.0, 1.0)[:, None, None]
+                    P_atm_m = sgn * s.phase_modes(kind, 1, M, nphi, g)
+                else:
+                    s.phase_modes_device(kind, d_Paer.data_ptr(), 1, M, nphi, g, sign_odd=True)
+                p0 = torch.empty((M, B, D), dtype=torch.float64, device=dev)
+                s.phase_p0_modes_device(kind, d_mu0.data_ptr(), p0.data_ptr(), B, 1, M, nphi, g)
+                d_P0.append(p0)
+            d_st = torch.zeros((M, B), dtype=torch.int32, device=dev)
+            for m0 in range(1, M + 1, c):
+                cc = min(c, M + 1 - m0)
+                s.synchronize()                              # (the setters rewrite what the previous chunk's solve read)
+                s.set_columns(*[tile(v, cc) for v in colargs])
+                s.set_phase_sets_device(P_atm_m[m0 - 1], d_Paer[m0 - 1].data_ptr(), cc)
+                try:
+                    s.set_atm_phase_sets(P_atm_m[m0 - 1:m0 - 1 + cc])
+                    sets = np.repeat(np.arange(cc, dtype=np.int32), B)
+                    s.set_aerosol_sets(sets)
+                    s.set_atmosphere_sets(sets)
+                except ValueError as e:
+                    raise ValueError("mode_batch=True is not available here: %s; mode_batch=False works" % e) from None
+                d_tau_c, d_tgt_c = d_tau.repeat(cc, 1), d_target.repeat(cc)
+                d_n = torch.zeros(cc * B, dtype=torch.int32, device=dev)
+                s.set_order_targets(d_tgt_c.data_ptr())
+                s.solve_device(d_tau_c.data_ptr(), d_P0[0][m0 - 1].data_ptr(), d_P0[1][m0 - 1].data_ptr(),
+                               d_Im[m0 - 1].data_ptr(), d_n_orders=d_n.data_ptr(), d_status=d_st[m0 - 1].data_ptr())
+                s.synchronize()                              # (d_tau_c, d_tgt_c and d_n go out of scope)
+                s.set_order_targets(None)
+            s.azimuth_synthesize_device(M, d_I0.data_ptr(), d_Im.data_ptr(), d_lev.data_ptr(), nlev, d_phi.data_ptr(), nout,
+                                        d_out.data_ptr(), B=B)
+            s.synchronize()
+            status[1:] = d_st.cpu().numpy()
+            I_az = d_out.cpu().numpy()
+        finally:
+            s.synchronize()
+            s.set_order_targets(None)
+            s.set_stream(None)
+            # the cached handle as the plain call left it: its B columns (on set 0 of both kinds), then the mode-0 matrices
+            s.set_columns(*colargs)
             if P_mode0[0] is not None:
                 s.set_phase(*P_mode0)
     return I_az, status

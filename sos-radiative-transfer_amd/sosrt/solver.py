@@ -193,6 +193,29 @@ class Solver:
         check(lib().sosrt_phase_sets_info(self._h, out))
         return {"sets": out[0], "groups": out[1], "single_pass": bool(out[2]), "group_cap": out[3]}
 
+    def set_atm_phase_sets(self, P_atm_sets):
+        """Several ATMOSPHERE phase matrices `P_atm_sets` [S_atm, 2N, 2N], after `set_phase*` (set 0 replaces its P_atm);
+        `set_atmosphere_sets` says which one a column reads -- set 0 until then.  Every set must be low-rank (rank <= 4) and
+        flip-symmetric like the P_atm of `set_phase`; otherwise ValueError and the handle is unchanged (sosrt.h)."""
+        Pa = np.ascontiguousarray(P_atm_sets, dtype=np.float64)
+        if Pa.ndim != 3 or Pa.shape[1:] != (self.D, self.D):
+            raise ValueError("P_atm_sets has shape %s, expected (S_atm, %d, %d)" % (Pa.shape, self.D, self.D))
+        check(lib().sosrt_set_atm_phase_sets(self._h, int(Pa.shape[0]), _ptr(Pa)))
+        self._P = (None, None)          # (set 0 replaced P_atm: the next same_phase says no)
+
+    def set_atmosphere_sets(self, sets):
+        """Atmosphere set per column (`sets` [B], after `set_columns*`, which puts every column back on set 0)."""
+        z = np.ascontiguousarray(sets, dtype=np.int32)
+        if z.shape != (self.B,):
+            raise ValueError("sets has shape %s, expected (%d,)" % (np.shape(sets), self.B))
+        check(lib().sosrt_set_atmosphere_sets(self._h, int(self.B), _ptr(z)))
+
+    def atm_sets_info(self):
+        """{'sets': atmosphere sets on the handle, 'in_use': whether a current column is off atmosphere set 0}"""
+        out = (ctypes.c_int * 2)()
+        check(lib().sosrt_atm_sets_info(self._h, out))
+        return {"sets": out[0], "in_use": bool(out[1])}
+
     def same_grid(self, mu):
         return self.mu is not None and np.array_equal(self.mu, np.asarray(mu, dtype=np.float64))
 
@@ -443,6 +466,12 @@ class Solver:
         check(lib().sosrt_phase_modes(self._h, self._KINDS[kind], float(g), int(m_first), int(m_count), int(nphi), _ptr(out)))
         return out
 
+    def phase_modes_device(self, kind, d_P_out: int, m_first, m_count, nphi=25, g=0.0, sign_odd=False):
+        """`phase_modes` left on the device: d_P_out is the address of [m_count, 2N, 2N] float64; enqueued on the handle's
+        stream.  sign_odd: mode m is written as (-1)^m P^m, what the solve of mode m takes (`set_phase_sets_device`)."""
+        check(lib().sosrt_phase_modes_dev(self._h, self._KINDS[kind], float(g), int(m_first), int(m_count), int(nphi),
+                                          1 if sign_odd else 0, ctypes.c_void_p(d_P_out) if d_P_out else None))
+
     def phase_p0_modes(self, kind, mu0, m_first, m_count, nphi=25, g=0.0):
         """The same modes of P0 for an array of mu0 -> [m_count, len(mu0), 2N]."""
         m = np.ascontiguousarray(np.atleast_1d(mu0), dtype=np.float64)
@@ -472,6 +501,15 @@ class Solver:
         check(lib().sosrt_azimuth_accumulate_dev(self._h, int(self.B if B is None else B), int(m), ctypes.c_void_p(d_Im), int(nlev),
                                                  ctypes.c_void_p(d_levels), int(nphi_out), ctypes.c_void_p(d_phi),
                                                  ctypes.c_void_p(d_out)))
+
+    def azimuth_synthesize_device(self, M: int, d_I0: int, d_Im: int, d_levels: int, nlev: int, d_phi: int, nphi_out: int,
+                                  d_out: int, B: Optional[int] = None):
+        """The whole synthesis in one launch: out[b][lev][dir][j] = I0[b][levels[lev]][dir] + sum_{m=1..M} 2 Im[m-1][b][levels[lev]]
+        [dir] cos(m phi[j]) on device addresses (d_I0 [B, L, 2N], d_Im [M, B, L, 2N]); the bits of `azimuth_accumulate_device`
+        called for m = 0..M."""
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_azimuth_synthesize_dev(self._h, int(self.B if B is None else B), int(M), vp(d_I0), vp(d_Im), int(nlev),
+                                                 vp(d_levels), int(nphi_out), vp(d_phi), vp(d_out)))
 
     # ---- multi-GPU gather over RCCL (one process per GPU) -------------------------
     @staticmethod
