@@ -127,4 +127,54 @@ FixTable Plan::make_fix_table(int idx) const {
     return t;
 }
 
+int lowrank_factor(const std::vector<double>& W, int D, int kmax, double tol, std::vector<double>& Ut, std::vector<double>& V,
+                   double* residual) {
+    Ut.assign((size_t)kmax * D, 0.0);
+    V.assign((size_t)kmax * D, 0.0);
+    auto absmax = [](const std::vector<double>& X, size_t* at) {
+        double amax = 0;
+        bool nan = false;
+        for (size_t e = 0; e < X.size(); ++e) {
+            const double ax = std::fabs(X[e]);
+            nan |= std::isnan(ax);
+            if (ax > amax) { amax = ax; if (at) *at = e; }
+        }
+        return nan ? std::nan("") : amax;
+    };
+    std::vector<double> R(W);
+    const double wmax = absmax(W, nullptr);
+    *residual = wmax;
+    if (!std::isfinite(wmax)) return -1;
+    int rank = -1;
+    for (int r = 0; r <= kmax; ++r) {
+        size_t at = 0;
+        const double amax = absmax(R, &at);
+        *residual = wmax > 0 ? amax / wmax : amax;
+        if (std::isnan(amax)) return -1;
+        if (amax <= tol * wmax) { rank = r; break; }
+        if (r == kmax) return -1;
+        const int i = (int)(at / D), j = (int)(at % D);
+        const long double piv = R[at];
+        for (int k = 0; k < D; ++k) Ut[(size_t)r * D + k] = (double)(R[(size_t)k * D + j] / piv);
+        for (int m = 0; m < D; ++m) V[(size_t)r * D + m] = R[(size_t)i * D + m];
+        for (int k = 0; k < D; ++k) {
+            const long double u = Ut[(size_t)r * D + k];
+            double* row = &R[(size_t)k * D];
+            const double* v = &V[(size_t)r * D];
+            for (int m = 0; m < D; ++m) row[m] = (double)(row[m] - u * v[m]);
+        }
+    }
+    // the certificate, from the factors the device will use
+    double res = 0;
+    for (int k = 0; k < D; ++k)
+        for (int m = 0; m < D; ++m) {
+            long double uv = 0;
+            for (int q = 0; q < rank; ++q) uv += (long double)Ut[(size_t)q * D + k] * V[(size_t)q * D + m];
+            const double d = std::fabs((double)(W[(size_t)k * D + m] - uv));
+            if (!(d <= res)) res = d;                   // (a NaN ends up here and refuses the factors below)
+        }
+    *residual = wmax > 0 ? res / wmax : res;
+    return (res <= tol * wmax) ? rank : -1;
+}
+
 }  // namespace sosrt

@@ -39,4 +39,12 @@ struct Plan {
     FixTable make_fix_table(int idx) const;
 };
 
+// Cross approximation of a folded matrix W [D][D] (row k, column m): up to kmax (kLowRankMax) steps of Gaussian elimination with
+// complete pivoting, U[k][q] = R[k][j] / R[i][j], V[q][m] = R[i][m] for the largest |R[i][j]| of the Schur complement R, which
+// then loses that term.  The rank is the first step count whose complement is at most tol (SOSRT_LOWRANK_TOL) of max |W|, and the
+// certificate is then computed from the factors themselves: max |W - U V| <= tol max |W|.  A NaN anywhere, or no
+// such count, gives -1.  Ut [kmax][D] = U transposed, V [kmax][D], zero beyond the rank.
+int lowrank_factor(const std::vector<double>& W, int D, int kmax, double tol, std::vector<double>& Ut, std::vector<double>& V,
+                   double* residual);
+
 }  // namespace sosrt

@@ -109,8 +109,10 @@ class Solver:
         self.order_budget = int(max_orders)
 
     def set_order_loop(self, on=True):
-        """Whether the last orders of the last few live columns run in ONE launch (csrc/order_loop.hip; default on: same
-        bits, no launches and no host round trip per order) or every order stays two launches."""
+        """Whether the last orders of the last few live columns run in ONE launch (csrc/order_loop.hip).  0 / False (the
+        library's default: the launch has the same bits and was measured slower) every order stays two launches; 1 / True
+        one launch where the launch plan says so; 2 a test mode whose launch is always refused, so that the hand-back to
+        the two-launch orders runs (include/sosrt.h, sosrt_set_order_loop)."""
         check(lib().sosrt_set_order_loop(self._h, int(on) if on in (0, 1, 2) else (1 if on else 0)))
 
     def order_loop_stats(self, column_orders=False):

@@ -45,7 +45,7 @@ def legendre_phase(N, mu, a, mu0=None, no_flip=False):
 
 
 def factor(W, rmax=4, tol=1e-12):
-    """The library's cross approximation (api.hip, lowrank_factor) in NumPy: U [D, r], V [r, D]."""
+    """The library's cross approximation (plan.cpp, lowrank_factor) in NumPy: U [D, r], V [r, D]."""
     R = W.copy()
     wmax = np.max(np.abs(W))
     U, V = [], []

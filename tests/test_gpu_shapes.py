@@ -475,7 +475,7 @@ def test_order_loop_kernel_keeps_the_bits(L, N, B, surface, monkeypatch):
                                                   (35, 192, 4, "specular", 2)])
 def test_register_resident_contraction_tile_keeps_the_bits(L, N, B, surface, pairs, monkeypatch):
     """The contraction of the last few live columns (csrc/jn_gemm_tile.hpp: gemm_tile_lone -- 16-row tiles, a lane's fragments of the
-    folded matrix in registers, no barrier in the k-loop; api.hip: SOSRT_PLAN_GEMM_LIVE16_REGS) against the staged live-column
+    folded matrix in registers, no barrier in the k-loop; solve.hip: SOSRT_PLAN_GEMM_LIVE16_REGS) against the staged live-column
     tilings (SOSRT_GEMM_REGS=0): same order counts, same statuses, the same bits -- a lone column, several columns, N = 256 (more
     than 64 KB of LDS), a Lambertian surface, more slab coefficient pairs than combined matrices (two passes), a group of more than
     256 columns (two rounds of candidates in the search for the tile's column) and a shape whose last tiles are ragged."""

@@ -182,7 +182,7 @@ def test_mie_series_and_log_normal_ensemble():
 
 
 def test_launch_plan_of_the_order_loop():
-    """sosrt_plan_launch: the one function the order loop of sosrt_solve_dev decides with (csrc/api.hip: plan_order), on
+    """sosrt_plan_launch: the one function the order loop of sosrt_solve_dev decides with (csrc/solve.hip: plan_order), on
     host-only handles -- over the direction count, the live count, the surface and the zone count."""
     T, G = _lib, _lib
     def plan(N, L, batch, live, order_loop=True, **kw):

@@ -120,3 +120,17 @@ def test_the_superposition_helper_reproduces_the_oracle_when_all_zones_share_a_s
     swapped = solve_column_zone_sets(c, [lo, hi])
     assert np.max(np.abs(mixed.I - ref.I)) > 1e-3 * scale
     assert np.max(np.abs(mixed.I - swapped.I)) > 1e-3 * scale
+
+
+def test_the_reallocation_walk_shape_plans_the_live_tiling():
+    """The shape of test_gpu_phase_sets.test_buffers_regrown_on_one_handle_leave_no_stale_state (L = 24, N = 16, B = 4, three
+    zones, specular) takes the contraction over the live columns from the first order on and can hold several phase sets'
+    mix groups: that test walks the buffers of the path the sweeps run.  (The group count itself needs columns, which a
+    host-only handle cannot take; the device test asserts it.)"""
+    s = Solver(24, 16, max_batch=4, device=-1)
+    s.set_grid(inputs.direction_grid(16))
+    p = s.plan_launch(4, 4)
+    assert p["groups"] == 1 and p["gemm"] != _lib.PLAN_GEMM_DENSE and p["tail_cols"] == 4
+    info = s.phase_sets_info()
+    assert info["sets"] == 1 and info["group_cap"] >= 4
+    s.close()
