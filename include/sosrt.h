@@ -471,6 +471,18 @@ int sosrt_plan_fix_count(double tau_ref, int N);  /* I1_In:124-127 */
 #define SOSRT_PLAN_TRANSPORT_RING    3   /* transport_ring.hip                                                                  */
 #define SOSRT_PLAN_TRANSPORT_SCAN    4   /* transport_scan.hip (chunk-parallel)                                                 */
 int sosrt_plan_launch(sosrt_t* h, int batch, int live, int surface, int zones, int cus, int* out /*[9]*/);
+/* The same plan's decision on the ring kernel's moment mode (both launches of the order: the contraction writes a 64-byte
+ * moment record per plain row instead of the row of Jn, the ring kernel expands it -- the same bits): *on = 1 or 0.  Unlike
+ * sosrt_plan_launch it plans with the phase matrices the handle HAS (none: no low-rank form, so 0).  flags: what a host-only
+ * handle cannot be told otherwise.  SOSRT_RING_MOMENTS=0 at sosrt_create turns the mode off for the handle. */
+#define SOSRT_PLAN_SAVED_ORDERS 1   /* the caller wants every order's field                */
+#define SOSRT_PLAN_ATM_SETS     2   /* some column reads an atmosphere phase set            */
+#define SOSRT_PLAN_NEED_SMALLMU 4   /* some |mu| < 0.01 lane keeps its k_smallmu value      */
+int sosrt_plan_ring_moments(sosrt_t* h, int batch, int live, int surface, int zones, int cus, int flags, int* on);
+/* What the last solve did, where the query above says what a plan would allow: the (column group, order) pairs that the contraction
+ * and the ring kernel ran in moment mode, and all the pairs that the two-launch loop ran (either pointer nullable).  The mode also
+ * stays off while some |mu| < 0.01 lane keeps its k_smallmu value, which only the solve knows (SOSRT_PLAN_NEED_SMALLMU). */
+int sosrt_ring_moments_stats(sosrt_t* h, int* moment_orders, int* orders);
 
 /* ---- profiling: HIP-event timing of the dominant kernels on the handle's stream ------------- */
 #define SOSRT_K_GEMM      0

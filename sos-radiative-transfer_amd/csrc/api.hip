@@ -64,6 +64,7 @@ int sosrt_create(int device, int L, int N, int max_batch, int max_orders, sosrt_
     if (const char* ev = getenv("SOSRT_TRANSPORT"))
         h->tr.mode = strcmp(ev, "general") == 0 ? 0 : (strcmp(ev, "ring") == 0 ? 2 : (strcmp(ev, "scan") == 0 ? 4 : (strcmp(ev, "auto") == 0 ? 3 : 1)));
     if (const char* ev = getenv("SOSRT_SCAN_COLS")) h->tr.scan_cols = atoi(ev);
+    if (const char* ev = getenv("SOSRT_RING_MOMENTS")) h->tr.ring_moments = atoi(ev) != 0;
     if (const char* ev = getenv("SOSRT_SCAN_SPLIT")) h->tr.scan_split = atoi(ev);
     if (const char* ev = getenv("SOSRT_GEMM_TAIL")) h->gemm.gemm_tail_cols = atoi(ev);
     if (const char* ev = getenv("SOSRT_GEMM_TAIL_FRAC")) h->gemm.gemm_tail_frac = atof(ev);
@@ -156,6 +157,7 @@ int sosrt_create(int device, int L, int N, int max_batch, int max_orders, sosrt_
             if ((e = dalloc(&h->fld.d_ratio, mb))) return e;
             if ((e = dalloc(&h->tr.d_scan_scratch, mb * transport_scan_scratch_doubles()))) return e;
             if ((e = dalloc(&h->tr.d_scan_sync, 2 * mb))) return e;
+            if ((e = dalloc(&h->tr.d_mom, mb * L * kMomDoubles))) return e;
             if ((e = dalloc(&h->ol.d_sync, sosrt_handle::kMaxGroups * order_loop_sync_ints(kOrderLoopMaxCols)))) return e;
             HIPCHK(hipHostMalloc((void**)&h->ol.h_done, 2 * sosrt_handle::kMaxGroups * sizeof(int), hipHostMallocCoherent));
             memset(h->ol.h_done, 0, 2 * sosrt_handle::kMaxGroups * sizeof(int));
@@ -191,7 +193,7 @@ int sosrt_destroy(sosrt_t* h) {
                         h->fld.d_P0r, h->fld.d_Jn, h->fld.d_InA, h->fld.d_InB, h->fld.d_I, h->fld.d_E, h->fld.d_active, h->fld.d_norders, h->fld.d_status,
                         h->fld.d_nactive_sets, h->fld.d_ratio, h->fld.d_redo, h->fld.d_erep, h->fld.d_tauhash, h->cols.d_mixca, h->cols.d_mixcr,
                         h->cols.d_mixgroup, h->phase.d_Wa_s, h->phase.d_Wr_s, h->tr.d_scan_scratch, h->tr.d_scan_sync, h->grid.d_w, h->grid.d_phi, h->grid.d_z, h->pf.d_tab, h->cols.d_slabtilegroup, h->gemm.d_livelist, h->phase.d_Wa32, h->cols.d_nz, h->cols.d_zr0, h->cols.d_zmix, h->cols.d_zwr, h->cols.d_zdtr, h->ol.d_sync, h->ol.d_log, h->phase.d_lrU, h->phase.d_lrV, h->cols.d_mixset,
-                        h->cols.d_colatm, h->cols.d_mixatm};
+                        h->cols.d_colatm, h->cols.d_mixatm, h->tr.d_mom};
         for (void* p : ptrs)
             if (p) hipFree(p);
         if (h->fld.h_pub) hipHostFree(h->fld.h_pub);
@@ -298,6 +300,12 @@ int sosrt_order_loop_stats(sosrt_t* h, int* launches, int* refused, long long* c
     return 0;
 }
 
+int sosrt_ring_moments_stats(sosrt_t* h, int* moment_orders, int* orders) {
+    if (!h) return fail(SOSRT_E_INVALID, "null handle");
+    if (moment_orders) *moment_orders = h->tr.moment_orders;
+    if (orders) *orders = h->tr.orders;
+    return 0;
+}
 
 int sosrt_synchronize(sosrt_t* h) {
     if (int e = need_gpu(h)) return e;

@@ -211,6 +211,11 @@ struct sosrt_handle {
         int scan_cols = 200;                 // SOSRT_SCAN_COLS
         bool ring_ok = false, scan_ok = false, scan_split_ok = false, fast_ok = false;
         int scan_split = 1;                  // SOSRT_SCAN_SPLIT: two workgroups per column when at most half as many columns are live as the device has CUs
+        // Moment mode of the ring kernel: in an order whose transport is the ring kernel for every column of the
+        // group, the contraction writes a 64-byte moment record per plain row instead of the row of Jn and the ring kernel expands it
+        int ring_moments = 1;                // SOSRT_RING_MOMENTS=0: rows of Jn always (A/B inside one process)
+        double* d_mom = nullptr;             // [max_batch][L][kMomDoubles] records
+        int moment_orders = 0, orders = 0;   // the last solve: (group, order) pairs transported in moment mode / by the two-launch loop (sosrt_ring_moments_stats)
         double* d_scan_scratch = nullptr;    // [max_batch][transport_scan_scratch_doubles()] exchange rows of the split form
         int* d_scan_sync = nullptr;          // [max_batch][2] {arrivals, flags}, zero between launches
     } tr;

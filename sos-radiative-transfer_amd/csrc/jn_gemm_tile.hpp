@@ -498,14 +498,29 @@ __device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows
                 for (int i = 0; i < LR_ROWS; ++i) m[i][q] += __shfl_xor(m[i][q], s);
             }
         }
+    // Moment mode (g.mom: the ring transport expands the rows itself): lanes 0 .. 3 write the row's record {M_0 .. M_3, ca, 0, 0, 0},
+    // 16 bytes each, through a descriptor of 64 bytes (a missing row: of none), and the row of C is not written.
+    if constexpr (!COH && !ATM) {
+        if (g.mom) {
+#pragma unroll
+            for (int i = 0; i < LR_ROWS; ++i) {
+                const int r = rows[i] >= 0 ? rows[i] : rows[0];
+                const __amdgpu_buffer_rsrc_t rM = make_rsrc(g.mom + (size_t)r * kMomDoubles, rows[i] >= 0 ? kMomDoubles * 8 : 0);
+                const double x = lane == 0 ? m[i][0] : (lane == 1 ? m[i][2] : (lane == 2 ? cf[i] : 0.0));
+                const double y = lane == 0 ? m[i][1] : (lane == 1 ? m[i][3] : 0.0);
+                bstore2(rM, lane * 16, 0, make_double2(x, y));
+            }
+            return;
+        }
+    }
 #pragma unroll 2
     for (int k = 2 * lane; k < D; k += 128) {
-        double2 o[LR_ROWS];
+        if constexpr (ATM) {
+            double2 o[LR_ROWS];
 #pragma unroll
-        for (int i = 0; i < LR_ROWS; ++i) o[i] = make_double2(0.0, 0.0);
+            for (int i = 0; i < LR_ROWS; ++i) o[i] = make_double2(0.0, 0.0);
 #pragma unroll
-        for (int q = 0; q < kLowRankMax; ++q) {
-            if constexpr (ATM) {
+            for (int q = 0; q < kLowRankMax; ++q) {
 #pragma unroll
                 for (int i = 0; i < LR_ROWS; ++i)
                     if (q < Ri[i]) {
@@ -513,17 +528,24 @@ __device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows
                         o[i].x = __builtin_fma(m[i][q], v.x, o[i].x);
                         o[i].y = __builtin_fma(m[i][q], v.y, o[i].y);
                     }
-            } else if (q < R) {
-                const double2 v = *reinterpret_cast<const double2*>(V + (size_t)q * D + k);
+            }
 #pragma unroll
-                for (int i = 0; i < LR_ROWS; ++i) {
-                    o[i].x = __builtin_fma(m[i][q], v.x, o[i].x);
-                    o[i].y = __builtin_fma(m[i][q], v.y, o[i].y);
+            for (int i = 0; i < LR_ROWS; ++i) bstore2_aux<COH ? 17 : 0>(rC[i], k * 8, 0, make_double2(cf[i] * o[i].x, cf[i] * o[i].y));
+        } else {
+            // (lr_expand: the expansion shared with the ring transport's moment mode)
+            double vx[kLowRankMax], vy[kLowRankMax];
+#pragma unroll
+            for (int q = 0; q < kLowRankMax; ++q) {
+                vx[q] = 0.0; vy[q] = 0.0;
+                if (q < R) {
+                    const double2 v = *reinterpret_cast<const double2*>(V + (size_t)q * D + k);
+                    vx[q] = v.x; vy[q] = v.y;
                 }
             }
-        }
 #pragma unroll
-        for (int i = 0; i < LR_ROWS; ++i) bstore2_aux<COH ? 17 : 0>(rC[i], k * 8, 0, make_double2(cf[i] * o[i].x, cf[i] * o[i].y));
+            for (int i = 0; i < LR_ROWS; ++i)
+                bstore2_aux<COH ? 17 : 0>(rC[i], k * 8, 0, make_double2(lr_expand(m[i], vx, R, cf[i]), lr_expand(m[i], vy, R, cf[i])));
+        }
     }
 }
 // A tile's plain rows in the low-rank form, where the MFMA tilings would have put a tile of BM rows x GEMM_BN columns of Jn: the

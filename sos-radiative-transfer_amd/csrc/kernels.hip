@@ -1182,12 +1182,14 @@ bool transport_fast_ok(const Plan& plan) {
 void launch_transport(hipStream_t s, const Grid& g, int B, const double* tau, const double* Jn, double* In, double* I,
                       double* saved, size_t saved_col_stride, const ColDesc* desc, Conv cv, int order,
                       int accumulate, const double* Etab, int mode, const int* erep, int live, const int* live_list,
-                      int ring_slots, int scan_split, double* scan_scratch, int* scan_sync, int nzcap) {
+                      int ring_slots, int scan_split, double* scan_scratch, int* scan_sync, int nzcap, const double* mom,
+                      const double* lrV, int lr_rank) {
     const int nt = round64(g.N);
     const size_t shm = (size_t)(g.L + 2 * TC * (nt + 2) + 2 * nt + nt / 64 + 2) * sizeof(double);
     TransportArgs a{g, tau, Jn, In, I, accumulate ? saved : nullptr, saved_col_stride, desc, cv, order, accumulate, Etab, Etab ? erep : nullptr, g_transport_stamps};
     a.slots = ring_slots;
     a.nzcap = nzcap > kRingZones ? nzcap : kRingZones;
+    if (mode == 3 && mom && accumulate && !saved && a.nzcap <= kRingZones) { a.mom = mom; a.lrV = lrV; a.lr_rank = lr_rank; }       // (the ring kernel alone reads moment records)
     if (mode == 4 && scan_split && scan_scratch && scan_sync) { a.scan_split = 1; a.scan_scratch = scan_scratch; a.scan_sync = scan_sync; }
     if ((mode == 3 || mode == 4) && accumulate && live > 0 && live < B && live_list) {       // ring / scan kernel over the live columns only
         a.live = live;

@@ -132,6 +132,12 @@ struct TransportArgs {
     int scan_split = 0;
     double* scan_scratch = nullptr;
     int* scan_sync = nullptr;
+    // ring kernel, moment mode (plan_order: LaunchPlan::moments): the plain rows' source comes as moment records
+    // [B][L][kMomDoubles] (jn_gemm_tile.hpp, lowrank_rows) and is expanded with the factor V of W_atm = U V; Jn then holds
+    // the slab rows only.  Null: every row of Jn is read, as always.
+    const double* mom = nullptr;
+    const double* lrV = nullptr;   // [kLowRankMax][D]
+    int lr_rank = 0;
 };
 void launch_transport_fast(hipStream_t s, dim3 grid, dim3 block, const TransportArgs& a);
 // transport_ring.hip: same sweeps, rows streamed through an LDS ring by loader waves
@@ -216,6 +222,10 @@ struct GemmArgs {
     int lr_rank = -1;
     const double* lrU = nullptr;     // [kLowRankMax][D]: lrU[q][k] = U[k][q]
     const double* lrV = nullptr;     // [kLowRankMax][D]: lrV[q][m] = V[q][m]
+    // Moment records of the plain rows, [rows][kMomDoubles] indexed like C's rows: {M_0 .. M_3, ca, padding}.  Set: lowrank_rows
+    // writes a row's record and NOT its row of C (the ring transport expands the record itself, transport_util.hpp: lr_expand).
+    // Null: rows of C, as always.  Never set for the order loop's contraction role or with atmosphere sets.
+    double* mom = nullptr;
 };
 // Atmosphere phase sets in use (sosrt_set_atmosphere_sets): a plain row takes the factors of its column's set.  The launches
 // that read this are kernels of their own (jn_gemm.hip, *_atm) with this as a second argument, and GemmArgs::lrU / lrV are then
@@ -225,6 +235,7 @@ struct AtmSets {
     const int* lr_ranks = nullptr;   // [sets] rank of a set's factors (0 .. kLowRankMax)
 };
 constexpr int kLowRankMax = 4;
+constexpr int kMomDoubles = 8;     // a moment record: 64 bytes, 64-byte aligned
 
 // (publish_live_now: by the calling thread, whichever workgroup it belongs to)
 __device__ inline void publish_live_now(const GemmArgs& g) {
@@ -292,7 +303,7 @@ void launch_transport(hipStream_t s, const Grid& g, int B, const double* tau, co
                       double* saved, size_t saved_col_stride, const ColDesc* desc, Conv cv, int order, int accumulate,
                       const double* Etab, int mode, const int* erep = nullptr, int live = 0, const int* live_list = nullptr,
                       int ring_slots = 0, int scan_split = 0, double* scan_scratch = nullptr, int* scan_sync = nullptr,
-                      int nzcap = kRingZones);
+                      int nzcap = kRingZones, const double* mom = nullptr, const double* lrV = nullptr, int lr_rank = 0);
 bool transport_fast_ok(const Plan& plan);
 // erep (nullable): tables are built only for columns with erep[b] == b
 void launch_attenuation(hipStream_t s, const Grid& g, int B, const double* tau, double* Etab, const int* erep);

@@ -84,6 +84,7 @@ struct SourceOpts {
     bool all_live = false;               // the host knows every column of the launch to be live
     bool regs_tile = false;              // live columns: the register-resident 16-row tile (SOSRT_PLAN_GEMM_LIVE16_REGS)
     int dense_live_cap = 0;              // > 0: the dense tiling writes the transport's live list, of this capacity
+    bool moments = false;                // the plain rows as moment records, not rows of Jn (LaunchPlan::moments)
 };
 
 // Jn for every row of a column group (grp < 0: the whole batch) in one launch: plain rows against W_atm, slab rows
@@ -108,6 +109,8 @@ void run_source(sosrt_handle* h, const double* In_1, double* Jn, const int* acti
         ga.cr += (size_t)col0 * h->L;
         if (active) active += col0;
     }
+    // (records are indexed like the rows of Jn: by global row, or from the group's first row with the identity list)
+    if (o.moments) ga.mom = h->tr.d_mom + (h->cols.nslab > 0 ? 0 : (size_t)col0 * h->L * kMomDoubles);
     ga.rows_slab = h->cols.d_slabrows + h->grp.slab_off[g0]; ga.n_slab = h->grp.slab_off[g1] - h->grp.slab_off[g0];
     ga.C = Jn; ga.active = active;
     if (ga.mix_group) ga.slab_tile_group = h->cols.d_slabtilegroup + h->grp.slab_off[g0] / 32;
@@ -194,6 +197,7 @@ struct OrderInputs {                     // what the plan of one order depends o
     bool saving = false;                 // the caller wants every order's field (I_saved)
     int orders_left = 1 << 30;           // order budget from this order on
     int cu_share = 0;                    // CUs an order-loop launch of this group may take (0: none)
+    bool atm_sets = false;               // some column reads an atmosphere phase set other than W_atm
 };
 struct LaunchPlan {
     int tail_cols = 0;                   // contraction over the live columns: capacity of the launch (0: dense tiling over the row lists)
@@ -205,6 +209,7 @@ struct LaunchPlan {
     int order_loop = 0;                  // this and every later order of the group in ONE order-loop launch
     int ol_parts = 0;                    // ... workgroups per column of its transport role
     int ol_grid = 0;                     // ... workgroups of the launch
+    int moments = 0;                     // both launches of the order: moment records for the plain rows, expanded by the ring kernel
 };
 LaunchPlan plan_order(const sosrt_handle* h, const SolveShape& sh, const OrderInputs& in) {
     LaunchPlan pl;
@@ -273,6 +278,11 @@ LaunchPlan plan_order(const sosrt_handle* h, const SolveShape& sh, const OrderIn
         }
         if (pl.order_loop) pl.ol_grid = in.cu_share;
     }
+    // Moment mode, for the contraction and the transport of the order at once: the plain rows in the low-rank form of the symmetric
+    // f64 contraction, one W_atm for the batch, no saved orders, the ring kernel for every column of the group (its three-zone
+    // instantiation) and no k_smallmu launch, which reads rows of Jn.  Anything else: rows of Jn, as always.
+    pl.moments = (h->tr.ring_moments && use_lowrank(h) && use_sym(h) && !in.atm_sets && !in.saving && !pl.order_loop &&
+                  pl.transport == SOSRT_PLAN_TRANSPORT_RING && sh.nzcap <= kRingZones && !in.need_small) ? 1 : 0;
     return pl;
 }
 
@@ -296,17 +306,16 @@ void ol_release(int device, int n) {
 }
 
 
-}  // namespace
-
-extern "C" {
-
-int sosrt_plan_launch(sosrt_t* h, int batch, int live, int surface, int zones, int cus, int* out) {
-    if (!h || !out) return fail(SOSRT_E_INVALID, "null argument");
+// The plan of one order as the host-only queries ask for it: a batch of `batch` (clear, slab, clear)-like columns with up to `zones`
+// zones as sosrt_set_columns and the order loop of sosrt_solve_dev see it -- the column groups, then the plan of an order of the
+// first group with `live` columns of it live.  flags: SOSRT_PLAN_*.  assume_sym: a handle without matrices plans for flip-symmetric
+// ones, what every phase function of the scattering angle gives.
+int plan_query(sosrt_handle* h, int batch, int live, int surface, int zones, int cus, int flags, bool assume_sym, int* groups,
+               LaunchPlan* out) {
+    if (!h) return fail(SOSRT_E_INVALID, "null argument");
     if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
     if (batch < 1 || live < 0 || live > batch) return fail(SOSRT_E_INVALID, "need 0 <= live <= batch, batch >= 1");
     if (zones < 1 || zones > kMaxZones) return fail(SOSRT_E_INVALID, "zones must be in 1..%d", kMaxZones);
-    // as sosrt_set_columns and the order loop of sosrt_solve_dev see a batch of `batch` (clear, slab, clear)-like columns with up to
-    // `zones` zones: the column groups, then the plan of an order of the first group with `live` columns of it live
     int want = h->grp.want_groups;
     if (want == 0) want = batch > h->grp.split_min ? 2 : 1;
     const int ng = (want >= 2 && batch >= h->grp.split_min && batch >= 2) ? 2 : 1;
@@ -318,13 +327,38 @@ int sosrt_plan_launch(sosrt_t* h, int batch, int live, int surface, int zones, i
     oi.nb = nb; oi.known = live < nb ? live : nb; oi.surface = surface;
     oi.simple_zones = zones == 3 || zones == 1;
     oi.cu_share = h->cu_count / ng;
+    oi.saving = (flags & SOSRT_PLAN_SAVED_ORDERS) != 0;
+    oi.atm_sets = (flags & SOSRT_PLAN_ATM_SETS) != 0 || h->cols.max_atm_used > 0;
+    oi.need_small = (flags & SOSRT_PLAN_NEED_SMALLMU) != 0 && h->g.nsmall > 0;
     const bool saved_sym = h->phase.sym_ok;
-    if (!h->have_phase) h->phase.sym_ok = true;            // (no matrices yet: plan for flip-symmetric ones, what every phase function of the scattering angle gives)
-    const LaunchPlan pl = plan_order(h, sh, oi);
+    if (assume_sym && !h->have_phase) h->phase.sym_ok = true;
+    *out = plan_order(h, sh, oi);
     h->phase.sym_ok = saved_sym;
     h->cu_count = saved_cus;
+    *groups = ng;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sosrt_plan_launch(sosrt_t* h, int batch, int live, int surface, int zones, int cus, int* out) {
+    if (!out) return fail(SOSRT_E_INVALID, "null argument");
+    int ng = 0;
+    LaunchPlan pl;
+    if (int e = plan_query(h, batch, live, surface, zones, cus, 0, true, &ng, &pl)) return e;
     out[0] = ng; out[1] = pl.gemm; out[2] = pl.tail_cols; out[3] = pl.transport; out[4] = pl.parts; out[5] = pl.repair;
     out[6] = pl.order_loop; out[7] = pl.ol_parts; out[8] = pl.ol_grid;
+    return 0;
+}
+
+int sosrt_plan_ring_moments(sosrt_t* h, int batch, int live, int surface, int zones, int cus, int flags, int* on) {
+    if (!on) return fail(SOSRT_E_INVALID, "null argument");
+    int ng = 0;
+    LaunchPlan pl;
+    if (int e = plan_query(h, batch, live, surface, zones, cus, flags, false, &ng, &pl)) return e;
+    *on = pl.moments;
     return 0;
 }
 
@@ -535,6 +569,7 @@ struct SolveRun {
         }
         if (int e = ensure_matrices(h, s)) return e;
         h->ol.launches = 0; h->ol.refused = 0;
+        h->tr.moment_orders = 0; h->tr.orders = 0;
         for (bool& u : h->ol.group_used) u = false;
         tagbase = ((++h->fld.pub_seq) & 0x3fff) << 16;      // tag of order n = tagbase + n
         live_groups = NG;
@@ -656,6 +691,7 @@ struct SolveRun {
         oi.simple_zones = h->cols.simple_zones; oi.slabs_mixed = h->cols.nslab == 0 || h->cols.mix_groups > 0;
         oi.need_small = h->g.nsmall > 0 && h->fld.need_small; oi.saving = d_I_saved_out != nullptr;
         oi.orders_left = h->order_budget - q.n;
+        oi.atm_sets = h->cols.max_atm_used > 0;
         oi.cu_share = (q.ol_off || h->d_targets || h->cols.max_atm_used > 0) ? 0 : h->cu_count / NG;   // (no order-loop launch with order targets, or atmosphere sets)
         return oi;
     }
@@ -721,6 +757,7 @@ struct SolveRun {
         SourceOpts so;
         so.tail_cols = pl.tail_cols; so.pub_tag = tagbase + n - 1; so.grp = k; so.all_live = q.known == q.nb;
         so.regs_tile = pl.gemm == SOSRT_PLAN_GEMM_LIVE16_REGS; so.dense_live_cap = pl.tail_cols > 0 ? 0 : pl.live_cap;
+        so.moments = pl.moments != 0;
         run_source(h, q.In_1, h->fld.d_Jn, h->fld.d_active, so);
         if (g.nsmall > 0 && h->fld.need_small) {      // skipped once the device has reported that every such lane is rewritten anyway
             prof_begin(h, SOSRT_K_SMALLMU, k);
@@ -737,7 +774,8 @@ struct SolveRun {
             launch_transport(sg, gt, q.nb, tau_g, h->fld.d_Jn + fo, q.In + fo, d_I_out + fo, sv_n, saved_stride, h->cols.d_desc + q.b0, q.cv, n, 1,
                              h->fld.d_E, pl.transport, erep_g, pl.live_cap, h->gemm.d_livelist + q.b0, NG > 1 ? h->grp.coresident_slots : 0,
                              pl.parts > 1 ? 1 : 0, h->tr.d_scan_scratch + (size_t)q.b0 * transport_scan_scratch_doubles(),
-                             h->tr.d_scan_sync + 2 * q.b0, shape.nzcap);
+                             h->tr.d_scan_sync + 2 * q.b0, shape.nzcap,
+                             pl.moments ? h->tr.d_mom + (size_t)q.b0 * h->L * kMomDoubles : nullptr, h->phase.d_lrV, h->phase.lr_rank);
             if (pl.repair)                           // register-streaming kernel: a search that leaves wave 0 is redone by the
                 launch_transport(sg, g, q.nb, tau_g, h->fld.d_Jn + fo, q.In + fo, d_I_out + fo, sv_n, saved_stride, h->cols.d_desc + q.b0, q.cv, n, 1,
                                  h->fld.d_E, 2, erep_g);         // general kernel (flag cv.redo); the ring kernel redoes it itself
@@ -746,6 +784,8 @@ struct SolveRun {
                              h->tr.use_etab ? h->fld.d_E : nullptr, 0, erep_g);
         }
         prof_end(h, SOSRT_K_TRANSPORT, k);
+        ++h->tr.orders;
+        if (pl.moments) ++h->tr.moment_orders;
         if (q.In_1 == d_I_out) { q.In_1 = q.In; q.In = h->fld.d_InA; }      // (after the second order: the buffer the first order left unused)
         else { double* tmp = q.In_1; q.In_1 = q.In; q.In = tmp; }
     }

@@ -52,7 +52,13 @@ __device__ __forceinline__ void wg_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-template <bool ACC, bool SAVED, int PIECES, bool MZ>
+// MOM (moment mode; ACC, not SAVED, not MZ): the plain rows of Jn are not in memory.  The contraction of the order wrote a
+// record of kMomDoubles doubles per plain row instead (a.mom: the row's low-rank moments and its coefficient, lowrank_rows), and
+// a row's elements are lr_expand of that record -- the bits the contraction would have written.  The loaders fetch a plain row's
+// record with the instruction that would fetch its row of Jn (one instruction per row and piece either way: the counted waits
+// do not change), into the start of the row's place in the slot; the computing waves read it there, every lane the same address.
+// Slab rows come as rows of Jn.  Whether a row is plain is a scalar comparison with the column's slab rows, alike in every wave.
+template <bool ACC, bool SAVED, int PIECES, bool MZ, bool MOM = false>
 __global__ __launch_bounds__(512) void k_transport_ring(TransportArgs a, int NS, int dbg_arg, int fixcap) {
     constexpr int NWL = 2;                                     // loader waves
 #ifdef SOSRT_RING_DEBUG
@@ -118,6 +124,12 @@ __global__ __launch_bounds__(512) void k_transport_ring(TransportArgs a, int NS,
     const __amdgpu_buffer_rsrc_t rIl = make_rsrc(ACC ? a.I + (size_t)b * L * D : a.In, ACC ? lbytes : 0);
     const __amdgpu_buffer_rsrc_t rI = make_rsrc(ACC ? a.I + (size_t)b * L * D : a.In, ACC ? sbytes : 0);
     const __amdgpu_buffer_rsrc_t rS = make_rsrc(SAVED ? a.saved + (size_t)b * a.saved_col_stride : a.In, SAVED ? sbytes : 0);
+    // moment mode: the slab rows [sl0, sl1] of the column -- zone 1 of a (clear, slab, clear) column; no such zone: every row is plain
+    const int sl0 = (MOM && nz == 3 && dg->mix[1]) ? dg->r0[1] : (1 << 30), sl1 = MOM ? dg->r0[2] - 1 : 0;
+    auto plain_row = [&](int t) { return MOM && (t < sl0 || t > sl1); };
+    const double* const Jn_col = a.Jn + (size_t)b * L * D;
+    const double* const mom_col = MOM ? a.mom + (size_t)b * L * kMomDoubles : nullptr;
+    const int lr_rank = MOM ? a.lr_rank : 0;
     const int NCH = (L + TC - 1) / TC, NQ = 2 * NCH, R = NS - 1;
     const bool valid = tid < N;
     const int tidc = valid ? tid : N - 1;
@@ -158,10 +170,19 @@ __global__ __launch_bounds__(512) void k_transport_ring(TransportArgs a, int NS,
         for (int i = 0; i < TC / NWL; ++i) {
             const int u = i * NWL + lid;
             const int row = up ? max(L - 1 - j * TC - u, 0) : min(j * TC + u, L - 1);
+            const bool pr = plain_row(row);
 #pragma unroll
             for (int p = 0; p < PIECES; ++p) {
                 const int so = row * RB + half + p * 1024;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (0 * TC + u) * RS + p * 128), 16, vo, so, 0, 0);
+                if constexpr (MOM) {
+                    // a plain row: its record through a descriptor that starts at the record and ends behind it (lanes 4 .. 63 are
+                    // out of range and fetch nothing; a scalar offset would count against the range), the second piece through an
+                    // empty one
+                    const __amdgpu_buffer_rsrc_t rX = make_rsrc(pr ? mom_col + (size_t)row * kMomDoubles : Jn_col, pr ? (p == 0 ? kMomDoubles * 8 : 0) : lbytes);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_t)(dst + (0 * TC + u) * RS + p * 128), 16, vo, pr ? 0 : so, 0, 0);
+                } else {
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (0 * TC + u) * RS + p * 128), 16, vo, so, 0, 0);
+                }
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rE, (lds_ptr_t)(dst + (1 * TC + u) * RS + p * 128), 16, vo, so, 0, 0);
                 if (ACC) __builtin_amdgcn_raw_ptr_buffer_load_lds(rIl, (lds_ptr_t)(dst + (2 * TC + u) * RS + p * 128), 16, vo, so, 0, 0);
             }
@@ -224,6 +245,36 @@ __global__ __launch_bounds__(512) void k_transport_ring(TransportArgs a, int NS,
     } else {
     stamp(1);
     const double mu_up = (valid && tid > 0) ? g.mu[N + tidc] : 1.0;   // loaded here: no global load may follow the first store
+    // moment mode: V[q][m] of this thread's downward and upward direction (likewise)
+    double Vdn[kLowRankMax] = {0, 0, 0, 0}, Vup[kLowRankMax] = {0, 0, 0, 0};
+    if constexpr (MOM) {
+#pragma unroll
+        for (int q = 0; q < kLowRankMax; ++q)
+            if (q < lr_rank) { Vdn[q] = a.lrV[(size_t)q * D + tidc]; Vup[q] = a.lrV[(size_t)q * D + N + tidc]; }
+    }
+    // a chunk's rows of Jn out of its slot (sp: this thread's element of the slot's first row).  Moment mode: a plain row is
+    // the expansion of its record.  A chunk outside the general body lies inside one zone: its rows are all plain or all slab.
+    auto read_J = [&](auto special_t, const double* sp, double (&Jc)[TC], int t_first, int dir, const double (&V)[kLowRankMax]) __attribute__((always_inline)) {
+        constexpr bool SP = decltype(special_t)::value;
+        if constexpr (!MOM) {
+#pragma unroll
+            for (int u = 0; u < TC; ++u) Jc[u] = sp[(0 * TC + u) * RS];
+        } else if constexpr (!SP) {
+            if (plain_row(t_first)) {
+#pragma unroll
+                for (int u = 0; u < TC; ++u) Jc[u] = lr_expand_record(sp - tid + (0 * TC + u) * RS, V, lr_rank);
+            } else {
+#pragma unroll
+                for (int u = 0; u < TC; ++u) Jc[u] = sp[(0 * TC + u) * RS];
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < TC; ++u) {
+                const int t = min(max(t_first + dir * u, 0), L - 1);       // (the rows the loaders fetched at the ragged ends)
+                Jc[u] = plain_row(t) ? lr_expand_record(sp - tid + (0 * TC + u) * RS, V, lr_rank) : sp[(0 * TC + u) * RS];
+            }
+        }
+    };
     // Transposed work items for the two mu -> 0 treatments: lane = 8 * (row of the chunk) + (position).
     const int uT = lane >> 3, pT = lane & 7;
     const double muT = (pT + 1 < N) ? g.mu[N + pT + 1] : 1.0;          // upward direction N + pT + 1
@@ -378,9 +429,9 @@ __global__ __launch_bounds__(512) void k_transport_ring(TransportArgs a, int NS,
             const double* sp = ring + (size_t)slot_rd * SLOT + tid;
             slot_rd = slot_rd + 1 == NS ? 0 : slot_rd + 1;
             double Jc[TC], Ic[TC], Ec[TC];
+            read_J(special_t, sp, Jc, t0, 1, Vdn);
 #pragma unroll
             for (int u = 0; u < TC; ++u) {
-                Jc[u] = sp[(0 * TC + u) * RS];
                 Ec[u] = sp[(1 * TC + u) * RS];
                 Ic[u] = ACC ? sp[(2 * TC + u) * RS] : 0.0;
             }
@@ -568,9 +619,9 @@ __global__ __launch_bounds__(512) void k_transport_ring(TransportArgs a, int NS,
             const double* sp = ring + (size_t)slot_rd * SLOT + tid;
             slot_rd = slot_rd + 1 == NS ? 0 : slot_rd + 1;
             double Jc[TC], Ic[TC], Ec[TC];
+            read_J(special_t, sp, Jc, t0, -1, Vup);
 #pragma unroll
             for (int u = 0; u < TC; ++u) {
-                Jc[u] = sp[(0 * TC + u) * RS];
                 Ec[u] = sp[(1 * TC + u) * RS];
                 Ic[u] = ACC ? sp[(2 * TC + u) * RS] : 0.0;
             }
@@ -612,8 +663,26 @@ __global__ __launch_bounds__(512) void k_transport_ring(TransportArgs a, int NS,
     if (s_flag[0]) {
         // The first row of a zone has no stop among the lanes of wave 0, and its blended value is the state of the zone above
         // (spec:403-406 has no bound): redo that sweep here, row by row (redo_upward_sweep; the ring is free by now).
-        const bool missing = redo_upward_sweep<ACC, SAVED, MZ>(L, N, RB, zr, s_hd, g.mu, rJ, rE, rIn, rI, rS, Bv, ring,
-                                                            rup_v, rup_i);
+        bool missing;
+        if constexpr (MOM) {
+            // (its plain rows: the records again, from memory -- the sweeps are over, a load may wait here)
+            struct RowsOfMoments {
+                const double* mom_col; const double* lrV; int r, D, m, sl0, sl1;
+                __device__ __forceinline__ double operator()(int t, double jn) const {
+                    if (!(t < sl0 || t > sl1)) return jn;
+                    double V[kLowRankMax] = {0, 0, 0, 0};
+#pragma unroll
+                    for (int q = 0; q < kLowRankMax; ++q)
+                        if (q < r) V[q] = lrV[(size_t)q * D + m];
+                    return lr_expand_record(mom_col + (size_t)t * kMomDoubles, V, r);
+                }
+            };
+            const RowsOfMoments jsrc{mom_col, a.lrV, lr_rank, D, N + (tid < N ? tid : 0), sl0, sl1};
+            missing = redo_upward_sweep<ACC, SAVED, MZ, 0, 0, RowsOfMoments>(L, N, RB, zr, s_hd, g.mu, rJ, rE, rIn, rI, rS, Bv, ring,
+                                                                            rup_v, rup_i, jsrc);
+        } else {
+            missing = redo_upward_sweep<ACC, SAVED, MZ>(L, N, RB, zr, s_hd, g.mu, rJ, rE, rIn, rI, rS, Bv, ring, rup_v, rup_i);
+        }
         if (missing) {                                                  // the reference raises IndexError (spec:404)
             if (tid == 0) {
                 a.cv.status[b] = SOSRT_COL_INDEXERROR;
@@ -668,7 +737,14 @@ void launch_p(hipStream_t s, dim3 grid, dim3 block, const TransportArgs& a, int 
         if (a.nzcap > kRingZones) SOSRT_RING_LAUNCH_Z(ACC_, SAVED_, true);                                     \
         else SOSRT_RING_LAUNCH_Z(ACC_, SAVED_, false);                                                         \
     } while (0)
-    if (a.accumulate) {
+    if (a.mom) {
+        // moment mode (plan_order turns it on only for these launches): accumulating, no saved orders, up to three zones
+        auto kern = k_transport_ring<true, false, PIECES, false, true>;
+        static PerDeviceOnce big_lds;
+        if (big_lds.first())
+            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRingLdsBytes);
+        hipLaunchKernelGGL(kern, grid, block, shm, s, a, NS, g_ring_debug, ring_fixcap(a.g));
+    } else if (a.accumulate) {
         if (a.saved) SOSRT_RING_LAUNCH(true, true);
         else SOSRT_RING_LAUNCH(true, false);
     } else {

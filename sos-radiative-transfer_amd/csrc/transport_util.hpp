@@ -130,6 +130,24 @@ __device__ __forceinline__ double blend_val(double w, double r0, double rk) {
 //   In_limit:113-141 as a linear map: acc + c x
 __device__ __forceinline__ double fix_acc(double c, double x, double acc) { return __builtin_fma(c, x, acc); }
 
+// ---- a plain row's source from its low-rank moments -------------------------------------------------------------------------
+// One element of a plain row of Jn (jn_gemm_tile.hpp, lowrank_rows):  ca (sum_q M_q V[q][m]),  the r terms added in order of q
+// from zero, one fma each, then one product.  The contraction's expansion and the ring transport's moment mode both call this,
+// so a plain Jn[m] has the same bits whichever kernel forms it.  V holds V[q][m] of the caller's m; terms q >= r are not touched.
+__device__ __forceinline__ double lr_expand(const double (&M)[kLowRankMax], const double (&V)[kLowRankMax], int r, double ca) {
+#pragma clang fp contract(off)
+    double o = 0.0;
+#pragma unroll
+    for (int q = 0; q < kLowRankMax; ++q)
+        if (q < r) o = __builtin_fma(M[q], V[q], o);
+    return ca * o;
+}
+// ... from a row's moment record {M_0 .. M_3, ca, padding} (kMomDoubles doubles, in LDS or in memory; every lane the same address)
+__device__ __forceinline__ double lr_expand_record(const double* rec, const double (&V)[kLowRankMax], int r) {
+    const double M[kLowRankMax] = {rec[0], rec[1], rec[2], rec[3]};
+    return lr_expand(M, V, r, rec[4]);
+}
+
 // ---- the zone table as the sweeps look at it -------------------------------------------------------------------------------
 // Which rows end a zone that has another below it, which rows start a zone other than the first, which zone a row is in.  The
 // reference's three zones (spec:113-449) are two boundaries held in scalars -- the sweeps of a (clear, slab, clear) column
@@ -312,12 +330,17 @@ __device__ SOSRT_HELPER_INLINE bool finish_flagged_rows(const int* s_nf, int L, 
 // issued a chunk of kRedoRows rows ahead, so a row costs two barriers instead of two memory round trips (round 2: 3 us per row,
 // 650 us for a 200-row column that the rest of its launch then waited for).
 // s_work: kRedoRows-independent, 2 N + 4 doubles.  Returns true if some row has no stop at all (IndexError, spec:404).
+// JSrc: what a row's source is, given the row and what rJ holds of it -- the value itself (RowsOfJn), or, in the ring kernel's
+// moment mode, the expansion of the row's moment record where the row is plain.
+struct RowsOfJn {
+    __device__ __forceinline__ double operator()(int, double jn) const { return jn; }
+};
 constexpr int kRedoRows = 8;
-template <bool ACC, bool SAVED, bool MZ, int LDX = 0, int STX = 0>
+template <bool ACC, bool SAVED, bool MZ, int LDX = 0, int STX = 0, class JSrc = RowsOfJn>
 __device__ SOSRT_HELPER_INLINE bool redo_upward_sweep(int L, int N, int RB, const ZoneRows<MZ>& zr, const double* s_hd,
                                   const double* __restrict__ gmu, __amdgpu_buffer_rsrc_t rJ, __amdgpu_buffer_rsrc_t rE,
                                   __amdgpu_buffer_rsrc_t rIn, __amdgpu_buffer_rsrc_t rI, __amdgpu_buffer_rsrc_t rS, double U0,
-                                  double* s_work, double& rup_v, double& rup_i) {
+                                  double* s_work, double& rup_v, double& rup_i, const JSrc& jsrc = JSrc()) {
     const int tid = threadIdx.x;
     double* s_row = s_work;                                             // [2][N + 2] alternating rows
     int* s_kf = reinterpret_cast<int*>(s_work + 2 * (N + 2));          // [2]
@@ -336,7 +359,7 @@ __device__ SOSRT_HELPER_INLINE bool redo_upward_sweep(int L, int N, int RB, cons
 #pragma unroll
         for (int u = 0; u < kRedoRows; ++u) {
             const int t = max(t0 - u, 0);
-            Jc[u] = bload_aux<LDX>(rJ, vo, t * RB);
+            Jc[u] = jsrc(t, bload_aux<LDX>(rJ, vo, t * RB));
             Ec[u] = bload(rE, vo, t * RB);
             xo[u] = bload_aux<LDX ? LDX : 1>(rIn, vo, t * RB);
             Io[u] = ACC ? bload_aux<LDX ? LDX : 1>(rI, vo, t * RB) : 0.0;

@@ -43,6 +43,8 @@ SIGNATURES = {
     "sosrt_set_order_loop": (c_int, [c_void_p, c_int]),
     "sosrt_order_loop_stats": (c_int, [c_void_p, _ip, _ip, POINTER(c_longlong)]),
     "sosrt_plan_launch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, _ip]),
+    "sosrt_plan_ring_moments": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, _ip]),
+    "sosrt_ring_moments_stats": (c_int, [c_void_p, _ip, _ip]),
     "sosrt_set_first_order": (c_int, [c_void_p, c_int]),
     "sosrt_set_grid": (c_int, [c_void_p, c_void_p]),
     "sosrt_set_phase": (c_int, [c_void_p, c_void_p, c_void_p]),
