@@ -265,16 +265,20 @@ hipError_t launch_order_loop_t(hipStream_t s, int grid, const OrderLoopArgs& p) 
 
 // whether the order-loop kernel takes this shape (the handle-level conditions -- symmetric contraction, zone layout, no saved
 // orders -- are the caller's): the chunk-parallel transport in its split form (two to four workgroups per column; specular
-// surface or none) or, failing that, with one workgroup per column
+// surface or none) or, failing that, with one workgroup per column.  The kernel instantiates the plain forms only (the body has no
+// FUSED WIDE instantiation: one mask word of chunks with a zone boundary, 16-byte stage fills, LDS sized for twelve stages), so
+// the shapes of the split form's WIDE instantiation -- odd N, N > 256, more than 64 chunks per sweep (L > 512) -- are refused here
 bool order_loop_ok(const Grid& g, bool split) {
     if (g.nsmall != 0) return false;                    // (the caller passes nsmall = 0 once no |mu| < 0.01 lane keeps its k_smallmu value)
-    return split ? (transport_scan_split_ok(g) && transport_scan_fits(g, kRingZones, true))
+    return split ? (transport_scan_split_ok(g) && !transport_scan_wide(g) && transport_scan_fits(g, kRingZones, true))
                  : (transport_scan_ok(g) && transport_scan_fits(g, kRingZones, false));
 }
 
 int order_loop_parts(const Grid& g, bool split) { return split ? transport_scan_parts(g) : 1; }
 
 hipError_t launch_order_loop(hipStream_t s, int grid, bool split, const OrderLoopArgs& p) {
+    // whatever the plan said: no launch at a shape the kernel's instantiations do not hold (its LDS would be sized for another form)
+    if (grid < 1 || !order_loop_ok(p.t.g, split)) return hipErrorInvalidValue;
     if (split) {
         if (p.t.g.N == 128) return launch_order_loop_t<true, 128>(s, grid, p);
         if (p.t.g.N == 256) return launch_order_loop_t<true, 256>(s, grid, p);

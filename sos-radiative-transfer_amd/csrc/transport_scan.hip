@@ -22,6 +22,7 @@ __global__ __launch_bounds__(768) void k_transport_scan(TransportArgs a, int fix
 }
 
 // shapes of the split form that take its WIDE instantiation (transport_scan_body.hpp): odd N, N > 256, more than 64 chunks per sweep
+// (transport_scan_wide below, for the other files)
 inline bool scan_wide(const Grid& g) { return (g.N & 1) || g.N > 256 || (g.L + TC - 1) / TC > 64; }
 
 // the WIDE instantiation of the split form (with or without saved orders; columns of three zones, or of up to a.nzcap: ZoneRows<true>)
@@ -101,6 +102,7 @@ bool transport_scan_split_ok(const Grid& g) {
     if (scan_wide(g)) return (g.L + TC - 1) / TC <= kScanChunks && scan_lds_bytes<true, true>(g) <= kScanLdsBytes;
     return scan_lds_bytes<true>(g) <= kScanLdsBytes;
 }
+bool transport_scan_wide(const Grid& g) { return scan_wide(g); }
 int transport_scan_parts(const Grid& g) { return (g.N + 63) / 64; }
 // whether the per-zone tables of a batch whose columns have up to nzcap zones still fit beside the stages
 bool transport_scan_fits(const Grid& g, int nzcap, bool split) {

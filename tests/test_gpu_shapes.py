@@ -431,10 +431,32 @@ def test_transport_kernel_follows_the_live_count_with_the_same_bits(monkeypatch)
     fresh()
 
 
-@pytest.mark.parametrize("L,N,B,surface", [(200, 128, 1, "specular"), (200, 128, 24, "specular"), (72, 64, 40, "specular"),
-                                           (200, 256, 3, "specular"), (50, 32, 7, "specular"), (90, 192, 5, "specular"),
-                                           (72, 128, 9, "lambertian"), (41, 100, 6, "specular"), (200, 128, 150, "specular")])
-def test_order_loop_kernel_keeps_the_bits(L, N, B, surface, monkeypatch):
+def _fresh_solvers():
+    from sosrt import main as M
+    for s_ in list(M._solvers.values()):
+        s_.close()
+    M._solvers.clear()
+
+
+# (L, N, B, surface[, z_up, z_down]).  The second block: the kernel's last legal chunk count, 64 chunks of 8 rows per sweep (bit 63
+# of the one mask word of chunks with a zone boundary is the last chunk's), and zone boundaries in the upper half of that word --
+# the default slab (z_up = 25, z_down = 17 of 120) is rows 405 .. 439 of 512, chunks 50 .. 54
+_OL_SHAPES = [(200, 128, 1, "specular"), (200, 128, 24, "specular"), (72, 64, 40, "specular"),
+              (200, 256, 3, "specular"), (50, 32, 7, "specular"), (90, 192, 5, "specular"),
+              (72, 128, 9, "lambertian"), (41, 100, 6, "specular"), (200, 128, 150, "specular"),
+              (512, 128, 1, "specular"),          # 64 chunks, two workgroups per column
+              (505, 100, 3, "specular"),          # 64 chunks, the last one a single row; N no multiple of 64
+              (512, 256, 2, "specular"),          # four workgroups per column at the limit
+              (408, 254, 2, "specular"),          # 51 chunks; last part of 62 lanes
+              (504, 64, 4, "specular"),           # one workgroup per column, 63 chunks
+              (512, 128, 3, "lambertian"),        # one workgroup per column at the limit
+              (512, 128, 2, "specular", 100, 90)]  # the slab high in the column (rows 85 .. 128): boundaries in the low bits, the last chunk's bit 63
+
+
+# (the ids of the cases without a slab position stay L-N-B-surface)
+@pytest.mark.parametrize("L,N,B,surface,zs", [c[:4] + (c[4:] or None,) for c in _OL_SHAPES],
+                         ids=["-".join(str(v) for v in c[:4]) + ("-slab_high" if c[4:] else "") for c in _OL_SHAPES])
+def test_order_loop_kernel_keeps_the_bits(L, N, B, surface, zs, monkeypatch):
     """The last orders of the last few live columns in ONE launch (csrc/order_loop.hip: the chunk-parallel transport of each live
     column and the tiles of their source functions as roles of one grid, tied by per-column counters) against the same solve
     with every order as two launches: same order counts, same statuses, the same bits -- for a lone column (the launch starts at
@@ -447,6 +469,14 @@ def test_order_loop_kernel_keeps_the_bits(L, N, B, surface, monkeypatch):
     taer = rng.choice([0.02, 0.12, 0.6, 1.0], B)
     rho = rng.uniform(0.0, 0.8, B)
     kw = dict(tauStar_atm=0.124, alb_aer=0.95, nb_layers=L, nb_angles=N, max_orders=200, surface=surface, raise_on_error=False)
+    if zs is not None:
+        # the slab high case: chunks 10 .. 16 of 64.  The clear zone above it ends at row 84 of 512, at 84 / 511 of the molecular
+        # optical depth: with 0.124 that is 0.020 <= 0.0625, where the reference rewrites int(0.005 N) = 0 directions next to mu = 0
+        # (spec:342-345), the |mu| < 0.01 lanes keep their k_smallmu values and no order-loop launch is planned at all.  0.5 puts
+        # it at 0.082, int(0.02 N) = 2 rewritten directions as in every other case here.
+        assert inputs.slab_indices(120, zs[0], zs[1], L) == (85, 128)
+        assert O.a4b_count(0.124 * 84 / 511, N) == 0 and O.a4b_count(0.5 * 84 / 511, N) == O.a4b_count(0.124 * 404 / 511, N) == 2
+        kw.update(z_up=zs[0], z_down=zs[1], tauStar_atm=0.5)
     out = {}
     for on in ("0", "1"):
         monkeypatch.setenv("SOSRT_ORDER_LOOP", on)
@@ -468,6 +498,54 @@ def test_order_loop_kernel_keeps_the_bits(L, N, B, surface, monkeypatch):
     assert np.array_equal(a.status, b.status)
     assert (a.status == 0).any()
     assert np.array_equal(a.I, b.I)                                            # bit for bit
+
+
+@pytest.mark.parametrize("L,N,B", [(513, 128, 1), (520, 256, 2), (800, 128, 1), (520, 100, 3)])
+def test_order_loop_is_not_launched_beyond_64_chunks(L, N, B, monkeypatch):
+    """More than 64 chunks per sweep (L > 512) is the chunk-parallel transport's WIDE instantiation, which the order-loop kernel
+    does not hold: with the order loop on no launch of it is planned or made (csrc/order_loop.hip: order_loop_ok), every order
+    stays two launches, and order counts, statuses and the field are those of the order loop off, bit for bit."""
+    from sosrt import main as M
+    rng = np.random.default_rng(1000 * L + 7 * N + B)
+    mu0 = rng.uniform(0.2, 1.0, B)
+    taer = rng.choice([0.02, 0.12, 0.6, 1.0], B)
+    rho = rng.uniform(0.0, 0.8, B)
+    kw = dict(tauStar_atm=0.124, alb_aer=0.95, nb_layers=L, nb_angles=N, max_orders=200, surface="specular", raise_on_error=False)
+    out = {}
+    for on in ("0", "1"):
+        monkeypatch.setenv("SOSRT_ORDER_LOOP", on)
+        _fresh_solvers()
+        out[on] = SOS_Aer_batch(mu0, taer, rho, **kw)
+        stats = [s_.order_loop_stats() for s_ in M._solvers.values()]
+        assert stats, "no cached solver"
+        assert stats[0][0] == 0, (on, stats)
+    _fresh_solvers()
+    a, b = out["0"], out["1"]
+    assert np.array_equal(a.n, b.n), (a.n, b.n)
+    assert np.array_equal(a.status, b.status)
+    assert (a.status == 0).any()
+    assert np.array_equal(a.I, b.I)                                            # bit for bit
+
+
+def test_order_loop_at_64_chunks_matches_the_oracle(monkeypatch):
+    """Bits that two launch modes share could both be wrong at the kernel's limit: one column at L = 512 (64 chunks per sweep, the
+    last chunk's bit 63 of the mask word; the slab's boundaries at chunks 50 and 54), N = 128, solved with the order loop on
+    -- every order from the second in the one launch -- against the oracle.  Black ground and a thin aerosol: 8 orders."""
+    from sosrt import main as M
+    L, N, mu0, taer, alb = 512, 128, 0.8, 0.02, 0.9
+    mu = inputs.direction_grid(N)
+    P_atm = inputs.phase_function("rayleigh", N, mu, mu0)[1]
+    P_aer = inputs.phase_function("hg", N, mu, mu0, 0.7)[1]
+    monkeypatch.setenv("SOSRT_ORDER_LOOP", "1")
+    _fresh_solvers()
+    r = SOS_Aer_batch(np.array([mu0]), np.array([taer]), np.array([0.0]), tauStar_atm=0.124, alb_aer=alb, nb_layers=L, nb_angles=N,
+                      P_atm=P_atm, P_aer=P_aer, max_orders=200, surface="specular", raise_on_error=False)
+    stats = [s_.order_loop_stats() for s_ in M._solvers.values()]
+    _fresh_solvers()
+    assert stats and stats[0][0] >= 1 and stats[0][1] == 0, stats             # the launch ran, and was never refused
+    ref = _oracle(mu0, taer, 0.0, L, N, P_atm, P_aer, 25, 17, alb)
+    assert r.status[0] == _lib.COL_OK and r.n[0] == ref.n, (r.status[0], r.n[0], ref.n)
+    assert_close(r.I[0], ref.I, RTOL, "order loop at L=512 N=128")
 
 
 @pytest.mark.parametrize("L,N,B,surface,pairs", [(200, 128, 1, "specular", 1), (200, 128, 9, "specular", 3), (200, 256, 3, "specular", 2),

@@ -261,3 +261,72 @@ def test_launch_plan_of_the_order_loop():
     assert plan(128, 200, 40, 40, cus=64)["order_loop"] == 0
     with pytest.raises(ValueError):
         plan(128, 200, 4, 5)
+    # the order-loop kernel holds the plain forms of the chunk-parallel transport only (its WIDE instantiation has no fused form):
+    # at most 64 chunks of 8 rows per sweep, L <= 512 -- the last shape it takes, and the first ones it does not
+    assert plan(128, 512, 1, 1)["order_loop"] == 1
+    assert plan(128, 513, 1, 1)["order_loop"] == 0
+    assert plan(128, 800, 1, 1)["order_loop"] == 0
+    assert plan(256, 520, 1, 1)["order_loop"] == 0
+    assert plan(100, 800, 1, 1)["order_loop"] == 0
+    p = plan(256, 512, 1, 1)
+    assert (p["order_loop"], p["ol_parts"]) == (1, 4)
+    p = plan(128, 520, 1, 1)                        # ... whose orders stay two launches, the transport in its WIDE instantiation
+    assert (p["transport"], p["parts"], p["order_loop"]) == (T.PLAN_TRANSPORT_SCAN, 2, 0)
+
+
+def test_launch_plan_stays_inside_the_kernels_shape_limits():
+    """Every plan of sosrt_plan_launch, order loop on, against the shape limits of the kernels it names -- written here as plain
+    arithmetic on (N, L, surface, zones) from the kernels' own comments and static asserts, not through the library's
+    predicates.  With chunks = ceil(L / 8), the rows of a sweep in chunks of TC = 8:
+      order-loop kernel (csrc/order_loop.hip): the chunk-parallel transport without its WIDE instantiation, three zones -- N even,
+        N <= 256, chunks <= 64 (one mask word of chunks with a zone boundary), zones <= 3; several workgroups per column:
+        N > 64 and ceil(N / 64) of them; one workgroup per column: N <= 128
+      chunk-parallel kernel, one workgroup per column (csrc/transport_scan.hip, transport_scan_ok): N even, 4 <= N <= 128, chunks <= 64
+      ... split form (transport_scan_split_ok, transport_scan_body.hpp: kScanDirs, kScanChunks): 64 < N <= 512, chunks <= 128,
+        ceil(N / 64) workgroups per column, no Lambertian surface (the reflection must stay inside a part)
+      ring kernel (csrc/transport_ring.hip, transport_ring_ok): N even, 4 <= N <= 256
+    Every violation is collected and reported, not the first one only."""
+    Ns = (4, 6, 32, 62, 64, 66, 70, 100, 126, 128, 129, 130, 192, 200, 254, 256, 257, 258, 300, 500, 501, 512, 514)
+    Ls = (3, 8, 9, 64, 200, 504, 505, 512, 513, 520, 800, 1016, 1024, 1025, 1032)
+    surfaces = (("specular", 3), ("lambertian", 3), ("none", 1), ("specular", 5))
+    batches = ((1, 1), (40, 40), (512, 30), (512, 512))
+    bad, plans = [], 0
+    for N in Ns:
+        for L in Ls:
+            s = Solver(L, N, device=-1)
+            s.set_grid(inputs.direction_grid(N))
+            s.set_order_loop(1)
+            chunks, parts, even = -(-L // 8), -(-N // 64), N % 2 == 0
+            for surface, zones in surfaces:
+                for batch, live in batches:
+                    p = s.plan_launch(batch, live, surface=surface, zones=zones)
+                    plans += 1
+                    broken = []
+                    if p["order_loop"] == 1:
+                        if not (even and N <= 256 and zones <= 3):
+                            broken.append("order loop: N even, N <= 256, zones <= 3")
+                        if chunks > 64:
+                            broken.append("order loop: chunks <= 64")
+                        if p["ol_parts"] > 1 and not (N > 64 and p["ol_parts"] == parts):
+                            broken.append("order loop, split: N > 64, ol_parts == ceil(N / 64)")
+                        if p["ol_parts"] == 1 and N > 128:
+                            broken.append("order loop, one workgroup per column: N <= 128")
+                        if p["ol_parts"] < 1:
+                            broken.append("order loop: ol_parts >= 1")
+                    elif p["order_loop"] != 0:
+                        broken.append("order_loop is 0 or 1")
+                    if p["transport"] == _lib.PLAN_TRANSPORT_SCAN and p["parts"] == 1:
+                        if not (even and 4 <= N <= 128 and chunks <= 64):
+                            broken.append("scan, one workgroup per column: N even, 4 <= N <= 128, chunks <= 64")
+                    if p["transport"] == _lib.PLAN_TRANSPORT_SCAN and p["parts"] != 1:
+                        if not (64 < N <= 512 and chunks <= 128 and p["parts"] == parts):
+                            broken.append("scan, split: 64 < N <= 512, chunks <= 128, parts == ceil(N / 64)")
+                        if surface == "lambertian":
+                            broken.append("scan, split: no Lambertian surface")
+                    if p["transport"] == _lib.PLAN_TRANSPORT_RING and not (even and 4 <= N <= 256):
+                        broken.append("ring: N even, 4 <= N <= 256")
+                    for rule in broken:
+                        bad.append("N=%d L=%d surface=%s zones=%d batch=%d live=%d: %s  (plan %r)" % (N, L, surface, zones, batch, live, rule, p))
+            s.close()
+    assert plans == len(Ns) * len(Ls) * len(surfaces) * len(batches) == 5520
+    assert not bad, "%d plans outside a kernel's limits:\n%s" % (len(bad), "\n".join(bad))
