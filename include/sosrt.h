@@ -421,6 +421,56 @@ int sosrt_azimuth_accumulate_dev(sosrt_t* h, int B, int m, const double* d_Im, i
 int sosrt_azimuth_synthesize_dev(sosrt_t* h, int B, int M, const double* d_I0, const double* d_Im, int nlev, const int* d_levels,
                                  int nphi_out, const double* d_phi, double* d_out);
 
+/* ---- view radiance: the solved field's source integrated off the grid -----------------------------------
+ * The solve returns radiance on its own direction grid.  A sensor looks at a view zenith angle that is not a node, and next to
+ * mu = 0+ the grid's upward lanes are an interpolation (the blend of spec:402-409), not a transport.  This stage integrates the
+ * source function of a resident field along the line of sight at the view cosine itself.  It runs after a solve, reads the
+ * columns of the last sosrt_set_columns* (zone table, mu0, grd_alb, albedos, steps), is enqueued on the handle's stream, and
+ * writes nothing but its outputs and scratch of its own: the handle and the field are as they were.  Detected by symbol;
+ * SOSRT_VERSION is unchanged.
+ *
+ * View cosines mu_view[V] (host), each finite and in [0.01, 1], 1 <= V <= SOSRT_MAX_VIEWS.  Signed lanes s[j], j < 2V:
+ * s[j] = -mu_view[j] (downward) for j < V, s[V + j] = +mu_view[j] (upward); every output is ordered by j.
+ *
+ * sosrt_phase_rows_dev: rows of the stored phase matrix at exit cosines mu_signed [V2] (host, each in [-1, 1], V2 <= 2
+ * SOSRT_MAX_VIEWS) with the stored matrix's own normalisers, d_rows_out[j][n] = 4 ring(s_j, mu_n) / trapz_a ring(mu_a, mu_n)
+ * (ring: the 25-node azimuth rule of sosrt_phase_matrix); at a node the row of sosrt_phase_matrix.  sosrt_phase_p0_rows_dev:
+ * the same of P0, d_out[b][j] = 2 ring(s_j, mu0_b) / trapz_a ring(mu_a, mu0_b).  Isotropic: 2 and 1.
+ *
+ * sosrt_view_radiance_dev: d_scat_out[b][lev][j] is the transport of the source
+ *     S[b][t][j] = ca(b,t) sum_k w_k rows_atm[j][2N-1-k] I_src[b][t][k] + cr(b,t) sum_k w_k rows_aer[j][2N-1-k] I_src[b][t][k]
+ * ((ca, cr): the row coefficients of the contraction, spec:321,323) at the rows `levels` (host, each in [0, L)), with
+ * E = exp(-dtau / mu), dtau the step to the row the sweep comes from:
+ *   SOSRT_VIEW_QUAD_GRID    the grid's arithmetic per lane, without its mu -> 0 treatments: trapezoid rule,
+ *                           D[t] = E D[t-1] + (dtau / 2)(S[t-1] E + S[t]) / mu continuous across zones, U[t] = E U[t+1] + (dtau / 2)
+ *                           (S[t] + S[t+1] E) / mu inside a zone, and the last row of every zone but the bottom one attenuated
+ *                           and not integrated.  With I_src = I - I_last of a solve it reproduces I - I1 at a node.
+ *                           It inherits the trapezoid rule's overshoot where dtau / mu >~ 1.
+ *   SOSRT_VIEW_QUAD_LINEAR  exact attenuation of a piecewise-linear source, U[t] = E U[t+1] + w0 S[t] + w1 S[t+1] with
+ *                           a = (1 - E) / x, x = dtau / mu, w0 = 1 - a, w1 = a - E (a series below x = 0.25), no zone restarts
+ *                           and no gaps: the quadrature for limb-ward views.
+ * Surface: rho times the downward value of the mirror lane (specular), 0 (SOSRT_SURFACE_NONE).
+ * d_first_out[b][lev][j]: the closed-form first order (spec:104-292; I1_In:13-58 for the single slab) at the lanes s_j, from
+ * d_p0rows_atm / d_p0rows_aer [B][2V]; it does not depend on the quadrature.  Either output may be NULL; the inputs of a
+ * NULL output are not read.  The radiance at the view lanes is d_first_out + d_scat_out with I_src the sum of all orders but
+ * the last (I_src = I adds the next term of the series, below tol of I at the rows the stopping rule tests).
+ * Refused with SOSRT_E_INVALID, nothing written: Lambertian surfaces; SOSRT_FIRST_ORDER_README with d_first_out; columns off
+ * aerosol set 0 or atmosphere set 0; V outside 1..SOSRT_MAX_VIEWS; a mu_view that is not finite or outside [0.01, 1]; a level
+ * outside [0, L); B above the current columns; an unknown quadrature; d_first_out without both p0rows.
+ * sosrt_view_timing: milliseconds of the last call's source contraction, sweeps and first order (HIP events; waits for them). */
+#define SOSRT_MAX_VIEWS 64
+#define SOSRT_VIEW_QUAD_GRID   0
+#define SOSRT_VIEW_QUAD_LINEAR 1
+int sosrt_phase_rows_dev(sosrt_t* h, int kind, double g, int V2, const double* mu_signed /*host [V2]*/, double* d_rows_out /*[V2][2N]*/);
+int sosrt_phase_p0_rows_dev(sosrt_t* h, int B, int kind, double g, const double* d_mu0 /*[B]*/, int V2,
+                            const double* mu_signed /*host [V2]*/, double* d_out /*[B][V2]*/);
+int sosrt_view_radiance_dev(sosrt_t* h, int B, int V, const double* mu_view /*host [V]*/, const double* d_tau /*[B][L]*/,
+                            const double* d_I_src /*[B][L][2N]*/, const double* d_rows_atm, const double* d_rows_aer /*[2V][2N]*/,
+                            const double* d_p0rows_atm, const double* d_p0rows_aer /*[B][2V]; needed only with d_first_out*/,
+                            int quadrature, int nlev, const int* levels /*host, rows in [0, L)*/,
+                            double* d_scat_out /*[B][nlev][2V], nullable*/, double* d_first_out /*[B][nlev][2V], nullable*/);
+int sosrt_view_timing(sosrt_t* h, double* ms /*[3]*/);
+
 /* ---- multi-GPU: one process per GPU, columns sharded, ONE collective at the end ------------------
  * Nothing in SOS_Aer_main_specular.py:104-458 couples columns, so the order loop never communicates; these entry
  * points only assemble the results of the ranks on `root` over RCCL (xGMI inside a node).  RCCL is bound at run time

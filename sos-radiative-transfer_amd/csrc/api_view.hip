@@ -1,0 +1,160 @@
+// View radiance (include/sosrt.h): phase rows at view cosines off the grid, and the radiance of a resident
+// field there by source-function integration.  A post-processing stage: it reads the columns of the last sosrt_set_columns* and
+// writes its outputs and scratch of its own (handle.hpp, View), nothing else.  Host code.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "handle.hpp"
+
+using namespace sosrt;
+
+static int view_phase_check(sosrt_handle* h, int kind, double g, int V2, const double* mu_signed, ViewMu* vm) {
+    if (int e = need_gpu(h)) return e;
+    if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
+    if (kind < SOSRT_PHASE_ISO || kind > SOSRT_PHASE_TABLE) return fail(SOSRT_E_INVALID, "unknown phase-function kind %d", kind);
+    if (kind == SOSRT_PHASE_TABLE && !h->pf.d_tab) return fail(SOSRT_E_STATE, "sosrt_phase_table has not been called");
+    if (kind == SOSRT_PHASE_HG && !(std::fabs(g) < 1)) return fail(SOSRT_E_INVALID, "|g| must be < 1 (got %g)", g);
+    if (V2 < 1 || V2 > 2 * SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "V2=%d exit cosines: must be 1..%d", V2, 2 * SOSRT_MAX_VIEWS);
+    if (!mu_signed) return fail(SOSRT_E_INVALID, "null mu_signed");
+    for (int j = 0; j < V2; ++j) {
+        if (!(std::isfinite(mu_signed[j]) && std::fabs(mu_signed[j]) <= 1))
+            return fail(SOSRT_E_INVALID, "mu_signed[%d] = %g is not a cosine in [-1, 1]", j, mu_signed[j]);
+        vm->s[j] = mu_signed[j];
+    }
+    for (int j = V2; j < 2 * kMaxViews; ++j) vm->s[j] = 0;
+    return 0;
+}
+
+extern "C" {
+
+int sosrt_phase_rows_dev(sosrt_t* h, int kind, double g, int V2, const double* mu_signed, double* d_rows_out) {
+    ViewMu vm;
+    if (int e = view_phase_check(h, kind, g, V2, mu_signed, &vm)) return e;
+    if (!d_rows_out) return fail(SOSRT_E_INVALID, "null output");
+    HIPCHK(hipSetDevice(h->device));
+    launch_phase_rows(h->stream, h->g, h->grid.d_w, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr,
+                      h->pf.ntab, h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, V2, vm, d_rows_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_phase_p0_rows_dev(sosrt_t* h, int B, int kind, double g, const double* d_mu0, int V2, const double* mu_signed,
+                            double* d_out) {
+    ViewMu vm;
+    if (int e = view_phase_check(h, kind, g, V2, mu_signed, &vm)) return e;
+    if (B < 1 || !d_mu0 || !d_out) return fail(SOSRT_E_INVALID, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    launch_phase_p0_rows(h->stream, h->g, h->grid.d_w, B, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr,
+                         h->pf.ntab, h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, d_mu0, V2, vm, d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_view_radiance_dev(sosrt_t* h, int B, int V, const double* mu_view, const double* d_tau, const double* d_I_src,
+                            const double* d_rows_atm, const double* d_rows_aer, const double* d_p0rows_atm,
+                            const double* d_p0rows_aer, int quadrature, int nlev, const int* levels, double* d_scat_out,
+                            double* d_first_out) {
+    if (int e = need_gpu(h)) return e;
+    if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
+    if (!h->have_cols) return fail(SOSRT_E_STATE, "sosrt_set_columns has not been called");
+    // ---- what the stage refuses: every check comes before the first launch, so a refused call changes nothing ----
+    if (B < 1 || B > h->B) return fail(SOSRT_E_INVALID, "B=%d: the handle's current columns are %d (sosrt_set_columns)", B, h->B);
+    if (V < 1 || V > SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "V=%d view cosines: must be 1..%d", V, SOSRT_MAX_VIEWS);
+    if (!mu_view) return fail(SOSRT_E_INVALID, "null mu_view");
+    for (int v = 0; v < V; ++v)
+        if (!(std::isfinite(mu_view[v]) && mu_view[v] >= 0.01 && mu_view[v] <= 1))
+            return fail(SOSRT_E_INVALID, "mu_view[%d] = %g: a view cosine must be finite and in [0.01, 1]", v, mu_view[v]);
+    if (quadrature != SOSRT_VIEW_QUAD_GRID && quadrature != SOSRT_VIEW_QUAD_LINEAR)
+        return fail(SOSRT_E_INVALID, "unknown quadrature %d (SOSRT_VIEW_QUAD_GRID or SOSRT_VIEW_QUAD_LINEAR)", quadrature);
+    if (nlev < 1 || !levels) return fail(SOSRT_E_INVALID, "no levels");
+    for (int i = 0; i < nlev; ++i)
+        if (levels[i] < 0 || levels[i] >= h->L) return fail(SOSRT_E_INVALID, "levels[%d] = %d is outside [0, %d)", i, levels[i], h->L);
+    if (h->surface == SOSRT_SURFACE_LAMBERTIAN || h->surface == SOSRT_SURFACE_LAMBERTIAN_README)
+        return fail(SOSRT_E_INVALID, "view radiance is not available over a Lambertian surface: its boundary for the orders n >= 2 needs "
+                                     "the sum over them of the grid's surface row, which the source field does not carry");
+    if (h->cols.max_set_used > 0 || h->cols.p0_zones > 0)
+        return fail(SOSRT_E_INVALID, "view radiance is not available with several aerosol phase sets (sosrt_set_phase_sets, sosrt_set_aerosol_sets)");
+    if (h->cols.max_atm_used > 0)
+        return fail(SOSRT_E_INVALID, "view radiance is not available with atmosphere phase sets (sosrt_set_atm_phase_sets, sosrt_set_atmosphere_sets)");
+    if (!d_scat_out && !d_first_out) return fail(SOSRT_E_INVALID, "neither d_scat_out nor d_first_out: nothing to compute");
+    if (!d_tau) return fail(SOSRT_E_INVALID, "null d_tau");
+    const bool three = h->geom == SOSRT_GEOM_THREE_ZONE;
+    if (d_first_out) {
+        if (h->first_order_mode == SOSRT_FIRST_ORDER_README)
+            return fail(SOSRT_E_INVALID, "the first order at view cosines is the coded one (SOSRT_FIRST_ORDER_CODED); the handle is set to SOSRT_FIRST_ORDER_README");
+        if (!d_p0rows_atm || (three && !d_p0rows_aer)) return fail(SOSRT_E_INVALID, "d_first_out needs d_p0rows_atm and d_p0rows_aer");
+    }
+    if (d_scat_out && (!d_I_src || !d_rows_atm || (three && !d_rows_aer)))
+        return fail(SOSRT_E_INVALID, "d_scat_out needs d_I_src, d_rows_atm and d_rows_aer");
+
+    HIPCHK(hipSetDevice(h->device));
+    prof_break(h);
+    hipStream_t s = h->stream;
+    const int L = h->L, D = h->D, V2 = 2 * V;
+    auto& vw = h->view;
+    for (auto& e : vw.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (int e = vw.d_desc.reserve(h->max_batch)) return e;
+    if (int e = vw.d_rc.reserve((size_t)2 * h->max_batch * L)) return e;
+    if (d_scat_out) {
+        if (int e = vw.d_fold.reserve((size_t)view_source_kpad(D) * view_source_cols(V))) return e;
+        if (int e = vw.d_S.reserve((size_t)B * L * V2)) return e;
+    }
+    ViewMu vm;
+    for (int j = 0; j < 2 * kMaxViews; ++j) vm.s[j] = 0;
+    for (int v = 0; v < V; ++v) { vm.s[v] = -mu_view[v]; vm.s[V + v] = mu_view[v]; }
+    // the zone tables and the row coefficients (ca, cr) of the current columns on the caller's optical depths: the kernel the
+    // solve prepares its own with, writing into this stage's buffers
+    double* rca = vw.d_rc.p;
+    double* rcr = rca + (size_t)h->max_batch * L;
+    launch_prepare(s, h->g, B, h->geom, h->surface, scalars_of(h), d_tau, vw.d_desc.p, rca, rcr);
+    HIPCHK(hipGetLastError());
+    vw.timed_scat = vw.timed_first = false;
+    if (d_scat_out) {
+        HIPCHK(hipEventRecord(vw.ev[0], s));
+        launch_view_source(s, B * L, D, V, h->grid.d_w, d_rows_atm, three ? d_rows_aer : nullptr, d_I_src, rca, rcr, vw.d_fold.p,
+                           vw.d_S.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(vw.ev[1], s));
+    }
+    for (int l0 = 0; l0 < nlev && d_scat_out; l0 += kViewLevels) {
+        ViewLevels lv;
+        lv.n = nlev - l0 < kViewLevels ? nlev - l0 : kViewLevels;
+        for (int i = 0; i < kViewLevels; ++i) lv.t[i] = i < lv.n ? levels[l0 + i] : -1;
+        launch_view_transport(s, B, V, L, quadrature, nlev, d_tau, vw.d_S.p, vw.d_desc.p, vm, lv, d_scat_out + (size_t)l0 * V2);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(vw.ev[2], s));
+    vw.timed_scat = d_scat_out != nullptr;
+    for (int l0 = 0; l0 < nlev && d_first_out; l0 += kViewLevels) {
+        ViewLevels lv;
+        lv.n = nlev - l0 < kViewLevels ? nlev - l0 : kViewLevels;
+        for (int i = 0; i < kViewLevels; ++i) lv.t[i] = i < lv.n ? levels[l0 + i] : -1;
+        launch_view_first_order(s, B, V, L, nlev, d_tau, d_p0rows_atm, three ? d_p0rows_aer : nullptr, vw.d_desc.p, vm, lv,
+                                d_first_out + (size_t)l0 * V2);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(vw.ev[3], s));
+    vw.timed_first = d_first_out != nullptr;
+    return 0;
+}
+
+int sosrt_view_timing(sosrt_t* h, double* ms) {
+    if (int e = need_gpu(h)) return e;
+    if (!ms) return fail(SOSRT_E_INVALID, "null argument");
+    auto& vw = h->view;
+    ms[0] = ms[1] = ms[2] = 0;
+    if (!vw.ev[3]) return fail(SOSRT_E_STATE, "sosrt_view_radiance_dev has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize(vw.ev[3]));
+    float t = 0;
+    if (vw.timed_scat) {
+        HIPCHK(hipEventElapsedTime(&t, vw.ev[0], vw.ev[1])); ms[0] = t;
+        HIPCHK(hipEventElapsedTime(&t, vw.ev[1], vw.ev[2])); ms[1] = t;
+    }
+    if (vw.timed_first) { HIPCHK(hipEventElapsedTime(&t, vw.ev[2], vw.ev[3])); ms[2] = t; }
+    return 0;
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // The handle behind the C ABI (include/sosrt.h) and what every host file of the library needs with it: error text, device
 // allocation, HIP-event profiling, the state checks of the entry points.  Private to csrc: api.hip (life cycle, setters,
 // read-backs), api_phase.hip (phase matrices), api_columns.hip (columns, zones, mix groups), solve.hip (launch plan, order
-// loop), api_phasefn.hip (phase functions, Mie, azimuth modes).  The fields are grouped by the file that owns them.
+// loop), api_phasefn.hip (phase functions, Mie, azimuth modes), api_view.hip (view radiance).  The fields are grouped by the file that owns them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -263,6 +263,15 @@ struct sosrt_handle {
         hipEvent_t mie_ev = nullptr, mie_t[4] = {nullptr, nullptr, nullptr, nullptr};
         bool mie_timed = false;
     } pf;
+
+    struct View {                        // view radiance (api_view.hip): scratch of its own, so that the stage leaves the handle as it was
+        sosrt::GrowBuf<double> d_fold;       // the folded rows [view_source_kpad(D)][view_source_cols(V)]
+        sosrt::GrowBuf<double> d_S;          // [B][L][2V] source at the view lanes
+        sosrt::GrowBuf<double> d_rc;         // [2][max_batch][L] row coefficients (ca, cr) of the call's own k_prepare
+        sosrt::GrowBuf<sosrt::ColDesc> d_desc;   // [max_batch] its zone tables
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around the source, the sweeps and the first order of the last call
+        bool timed_scat = false, timed_first = false;
+    } view;
 
     struct Comm {                        // RCCL communicator of the sharded solve (sosrt_comm_init)
         sosrt::Rccl::comm_t comm = nullptr;

@@ -363,6 +363,36 @@ void launch_mie_angles(hipStream_t s, int S, int R, int ntab, int n_cap, const d
                        const double* tn, const double* qw, double* part);
 void launch_mie_integrate(hipStream_t s, int S, int R, int ntab, const double* part, const double* radii, const double* qw,
                           double* p, double* bulk);
+// view.hip: radiance at view cosines off the direction grid.  The signed view cosines (first the V downward
+// lanes -mu_view, then the V upward ones) and the requested levels travel by value in the kernel arguments: nothing is staged.
+constexpr int kMaxViews = 64;      // SOSRT_MAX_VIEWS
+constexpr int kViewLevels = 256;   // levels per launch of the sweeps (a call with more takes several)
+struct ViewMu {
+    double s[2 * kMaxViews];
+};
+struct ViewLevels {
+    int n;
+    int t[kViewLevels];
+};
+// rows [V2][D] of the stored phase matrix at exit cosines mu.s[j]; out [B][V2] the same of P0 (normalisers recomputed as
+// launch_phase_matrix / launch_phase_p0 compute them)
+void launch_phase_rows(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
+                       const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi, int V2,
+                       const ViewMu& mu, double* rows);
+void launch_phase_p0_rows(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
+                          const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi, const double* mu0,
+                          int V2, const ViewMu& mu, double* out);
+// S [nrows][2V] = diag(ca) Isrc W_atm + diag(cr) Isrc W_aer with the rows folded into Wfold [view_source_kpad(D)][view_source_cols(V)]
+// (scratch); rows_aer may be null (single slab: zeros)
+int view_source_cols(int V);
+int view_source_kpad(int D);
+void launch_view_source(hipStream_t s, int nrows, int D, int V, const double* w, const double* rows_atm, const double* rows_aer,
+                        const double* Isrc, const double* ca, const double* cr, double* Wfold, double* S);
+// out [B][nlev_all][2V] (offset to the first level of lv): the sweeps of S, the closed-form first order
+void launch_view_transport(hipStream_t s, int B, int V, int L, int quad, int nlev_all, const double* tau, const double* S,
+                           const ColDesc* desc, const ViewMu& mu, const ViewLevels& lv, double* out);
+void launch_view_first_order(hipStream_t s, int B, int V, int L, int nlev_all, const double* tau, const double* p0a,
+                             const double* p0r, const ColDesc* desc, const ViewMu& mu, const ViewLevels& lv, double* out);
 void launch_limit_rows(hipStream_t s, const Grid& g, int R, int table, const double* rows, double* out);
 void launch_asymptotic(hipStream_t s, int R, int stride, const int* len, const double* J, const double* tau,
                        const double* tau_t, const double* mu, double* out);

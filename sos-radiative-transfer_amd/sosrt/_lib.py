@@ -22,6 +22,8 @@ FIRST_ORDER_CODED, FIRST_ORDER_README = 0, 1
 PHASE_ISO, PHASE_RAYLEIGH, PHASE_HG, PHASE_TABLE = 0, 1, 2, 3
 MAX_MODES = 64
 MAX_PHASE_SETS = 64
+MAX_VIEWS = 64
+VIEW_QUAD_GRID, VIEW_QUAD_LINEAR = 0, 1
 
 _dp = POINTER(c_double)
 _ip = POINTER(c_int)
@@ -83,6 +85,10 @@ SIGNATURES = {
     "sosrt_set_order_targets": (c_int, [c_void_p, c_void_p]),
     "sosrt_azimuth_accumulate_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_azimuth_synthesize_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "sosrt_phase_rows_dev": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p]),
+    "sosrt_phase_p0_rows_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_int, c_void_p, c_void_p]),
+    "sosrt_view_radiance_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 7 + [c_int, c_int] + [c_void_p] * 3),
+    "sosrt_view_timing": (c_int, [c_void_p, _dp]),
     "sosrt_comm_unique_id": (c_int, [c_void_p]),
     "sosrt_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "sosrt_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

@@ -50,6 +50,10 @@ class BatchResult:
     I_saved: Optional[np.ndarray] = None
     I_azimuth: Optional[np.ndarray] = None   # [B, nlev, 2N, len(azimuths)] (azimuths=...): radiance at the requested levels
     mode_status: Optional[np.ndarray] = None  # [M + 1, B] status of the solve of every Fourier mode (row 0 is `status`)
+    view_mu_signed: Optional[np.ndarray] = None    # [2V] (view_mu=...): the signed view lanes (-view_mu, +view_mu)
+    I_view: Optional[np.ndarray] = None            # [B, nlev, 2V] radiance at the view lanes = I_view_first + I_view_scattered
+    I_view_first: Optional[np.ndarray] = None      # [B, nlev, 2V] its closed-form first order
+    I_view_scattered: Optional[np.ndarray] = None  # [B, nlev, 2V] the transport of the field's source (orders n >= 2)
 
 
 _solvers = {}
@@ -97,7 +101,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   mie_atm=None, mie_aer=None,
                   P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular", tol=1e-4, max_orders=256,
                   save_orders=False, device=0, devices=None, raise_on_error=True, first_order="coded", azimuths=None,
-                  n_modes=None, nphi_modes=None, levels=(0, -1), aer_set=None, mode_batch=False, mode_chunk=None) -> BatchResult:
+                  n_modes=None, nphi_modes=None, levels=(0, -1), aer_set=None, mode_batch=False, mode_chunk=None,
+                  view_mu=None, view_levels=(0, -1), view_quadrature="grid") -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -128,7 +133,22 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     atmosphere's modes must be low-rank (iso, Rayleigh): otherwise ValueError, and `mode_batch=False` works.  Memory: the chunk
     bounds the handle's buffers only.  The fields of all modes wait for the one synthesis launch, n_modes x B x L x 2N doubles
     whatever c is (the loop keeps one mode's); beyond MODE_BATCH_MODES_BYTES the call is refused.  The cached handle is made
-    c B columns wide and, like every widened handle of `get_solver`, stays that wide for later calls of this shape."""
+    c B columns wide and, like every widened handle of `get_solver`, stays that wide for later calls of this shape.
+
+    `view_mu` (array of up to 64 cosines in [0.01, 1]): also the RADIANCE AT VIEW COSINES THAT ARE NOT NODES of the direction
+    grid, at the rows `view_levels` (default TOA and surface): BatchResult.I_view [B, len(view_levels), 2V] on the signed
+    lanes BatchResult.view_mu_signed = (-view_mu, +view_mu), the sum of I_view_first (the closed-form first order at the
+    lanes) and I_view_scattered (the source function of the solved field I, integrated along the line of sight at the view
+    cosine: `Solver.view_radiance_device`).  `view_quadrature='grid'` (default) is the reference's arithmetic per lane -- the
+    trapezoid rule of its transport, without the mu -> 0 treatments of the grid: at a node it returns the grid's value (to
+    the stopping rule's `tol`, because the source of I includes the last computed order, the series' next term); where the
+    optical-depth step over the view cosine is >~ 1 it inherits the trapezoid rule's overshoot.  `'linear'` attenuates a
+    piecewise-linear source exactly: the quadrature for limb-ward views.  I, n and status are those of the plain call, bit
+    for bit.  Needs named phase functions (not arrays), the specular surface, the coded first order and a single device; not
+    with `azimuths` or `aer_set`."""
+    if view_mu is not None:
+        vmu, vlev, vquad = _view_args(view_mu, view_levels, view_quadrature, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface,
+                                      devices, first_order, azimuths, aer_set, atm_phase_fun, aer_phase_fun)
     if aer_set is not None:
         if azimuths is not None:
             raise ValueError("azimuths are not available with aer_set (the mode driver swaps the handle's one pair of matrices per mode)")
@@ -192,7 +212,87 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                                                            aer_phase_fun, g_aer, mie_aer, device)
         if raise_on_error:
             _raise_status(out.mode_status, N)
+    if view_mu is not None:
+        mu0v = np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
+        out.view_mu_signed = np.concatenate((-vmu, vmu))
+        out.I_view_first, out.I_view_scattered = view_radiance(s, tau, r.I, mu0v, vmu, vlev, vquad, atm_phase_fun, g_atm, mie_atm,
+                                                               aer_phase_fun, g_aer, mie_aer, device)
+        out.I_view = out.I_view_first + out.I_view_scattered
     return out
+
+
+def _view_args(view_mu, view_levels, view_quadrature, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface, devices, first_order,
+               azimuths, aer_set, atm_phase_fun, aer_phase_fun):
+    """Checks of the view-radiance call, made before any handle exists: (view_mu [V], levels as row indices, quadrature)."""
+    if azimuths is not None:
+        raise ValueError("view_mu is not available with azimuths (the view stage integrates the azimuth average)")
+    if aer_set is not None or isinstance(aer_phase_fun, (list, tuple)):
+        raise ValueError("view_mu is not available with aer_set (the view stage reads one aerosol phase function)")
+    if devices is not None and len(devices) > 1:
+        raise ValueError("view_mu is not available with devices=[...]")
+    if any(x is not None for x in (P_atm, P_aer, P0_atm, P0_aer)):
+        raise ValueError("view_mu needs named phase functions: rows at view cosines cannot be derived from arrays on the grid")
+    if surface != "specular":
+        raise ValueError("view_mu is available with the specular surface only (the Lambertian boundary of the orders n >= 2 "
+                         "needs the grid's surface row of every order)")
+    if first_order != "coded":
+        raise ValueError("view_mu is available with first_order='coded' only")
+    if view_quadrature not in ("grid", "linear"):
+        raise ValueError("view_quadrature must be 'grid' or 'linear' (got %r)" % (view_quadrature,))
+    vmu = np.array(np.atleast_1d(view_mu), dtype=np.float64)
+    if vmu.ndim != 1 or not 1 <= vmu.size <= _lib.MAX_VIEWS:
+        raise ValueError("view_mu must hold 1..%d cosines" % _lib.MAX_VIEWS)
+    if not np.all(np.isfinite(vmu)) or np.any(vmu < 0.01) or np.any(vmu > 1):
+        raise ValueError("view_mu must be finite cosines in [0.01, 1]")
+    L = int(nb_layers)
+    lev = [int(x) for x in np.atleast_1d(view_levels)]
+    if not lev or any(not -L <= x < L for x in lev):
+        raise ValueError("view_levels must be row indices in [-%d, %d)" % (L, L))
+    return vmu, [x + L if x < 0 else x for x in lev], view_quadrature
+
+
+def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
+                  mie_aer, device=0):
+    """The view stage on the field `I` [B, L, 2N] of handle `s` (whose columns are set): rows of both phase functions at the
+    signed lanes, then `Solver.view_radiance_device` with I_src = I.  Returns (first order, scattered), each [B, nlev, 2V]."""
+    import torch
+    from .inputs import _scalar_phase
+    B, L = tau.shape
+    D, V2 = s.D, 2 * len(view_mu)
+    sgn = np.concatenate((-view_mu, view_mu))
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        try:
+            d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
+            d_I = torch.from_numpy(np.ascontiguousarray(I)).to(dev)
+            d_mu0 = torch.from_numpy(np.array(mu0, dtype=np.float64)).to(dev)
+            rows, p0rows = [], []
+            for name, g, mie in ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)):
+                kw = dict(mie or {})
+                if kw.get("device") is True:                 # (as `device_phase`: the Mie table from this handle's kernels)
+                    kw["device"] = s
+                kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **kw)[1]
+                if tab is not None:
+                    s.set_phase_table(*tab)
+                rw = torch.empty((V2, D), dtype=torch.float64, device=dev)
+                p0 = torch.empty((B, V2), dtype=torch.float64, device=dev)
+                torch.cuda.current_stream(dev).synchronize()
+                s.phase_rows_device(kind, sgn, rw.data_ptr(), g)
+                s.phase_p0_rows_device(kind, d_mu0.data_ptr(), sgn, p0.data_ptr(), B, g)
+                rows.append(rw)
+                p0rows.append(p0)
+            d_scat = torch.empty((B, len(levels), V2), dtype=torch.float64, device=dev)
+            d_first = torch.empty((B, len(levels), V2), dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            s.view_radiance_device(view_mu, d_tau.data_ptr(), d_I.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), levels,
+                                   d_scat_out=d_scat.data_ptr(), d_first_out=d_first.data_ptr(), d_p0rows_atm=p0rows[0].data_ptr(),
+                                   d_p0rows_aer=p0rows[1].data_ptr(), quadrature=quadrature, B=B)
+            s.synchronize()
+            return d_first.cpu().numpy(), d_scat.cpu().numpy()
+        finally:
+            s.synchronize()
+            s.set_stream(None)
 
 
 def _columns_to_set0(s, B):

@@ -492,6 +492,47 @@ class Solver:
         check(lib().sosrt_phase_p0_modes_dev(self._h, int(B), self._KINDS[kind], float(g), int(m_first), int(m_count), int(nphi),
                                              ctypes.c_void_p(d_mu0), ctypes.c_void_p(d_P0_out)))
 
+    # ---- view radiance: the solved field's source integrated off the grid (sosrt.h) ----
+    _QUADS = {"grid": _lib.VIEW_QUAD_GRID, "linear": _lib.VIEW_QUAD_LINEAR}
+
+    def phase_rows_device(self, kind, mu_signed, d_rows_out: int, g=0.0):
+        """Rows of the stored phase matrix at the exit cosines `mu_signed` [V2] (host, off the grid or on it) with the stored
+        matrix's own normalisers: d_rows_out is the address of [V2, 2N] float64; enqueued on the handle's stream."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_signed), dtype=np.float64)
+        check(lib().sosrt_phase_rows_dev(self._h, self._KINDS[kind], float(g), int(m.size), _ptr(m),
+                                         ctypes.c_void_p(d_rows_out) if d_rows_out else None))
+
+    def phase_p0_rows_device(self, kind, d_mu0: int, mu_signed, d_out: int, B: int, g=0.0):
+        """The same of P0 for B columns: d_mu0 [B], d_out [B, V2] (addresses)."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_signed), dtype=np.float64)
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_phase_p0_rows_dev(self._h, int(B), self._KINDS[kind], float(g), vp(d_mu0), int(m.size), _ptr(m), vp(d_out)))
+
+    def view_radiance_device(self, mu_view, d_tau: int, d_I_src: int, d_rows_atm: int, d_rows_aer: int, levels,
+                             d_scat_out: int = 0, d_first_out: int = 0, d_p0rows_atm: int = 0, d_p0rows_aer: int = 0,
+                             quadrature="grid", B: Optional[int] = None):
+        """Radiance at the view cosines `mu_view` [V] (host, each in [0.01, 1], V <= 64) at the rows `levels`, from the field
+        d_I_src [B, L, 2N] and the current columns: d_scat_out [B, nlev, 2V] the transport of the field's source at the signed
+        lanes (-mu_view, +mu_view), d_first_out [B, nlev, 2V] the closed-form first order (needs the p0rows).  quadrature:
+        'grid' (the grid's trapezoid arithmetic: at a node, with I_src = I - I_last, the grid's own I - I1) or 'linear' (exact
+        attenuation of a piecewise-linear source: the one for limb-ward views, where dtau / mu >~ 1).  All d_* are device
+        addresses; enqueued on the handle's stream; nothing but the outputs is written."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
+        lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.int32)
+        q = self._QUADS.get(quadrature, quadrature)
+        if isinstance(q, str) or isinstance(q, bool) or not isinstance(q, (int, np.integer)):
+            raise ValueError("quadrature must be 'grid' or 'linear' (got %r)" % (quadrature,))
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_view_radiance_dev(self._h, int(self.B if B is None else B), int(m.size), _ptr(m), vp(d_tau), vp(d_I_src),
+                                            vp(d_rows_atm), vp(d_rows_aer), vp(d_p0rows_atm), vp(d_p0rows_aer), int(q),
+                                            int(lev.size), _ptr(lev), vp(d_scat_out), vp(d_first_out)))
+
+    def view_timing(self):
+        """Milliseconds of the last `view_radiance_device`: (source contraction, sweeps, first order); waits for them."""
+        ms = (ctypes.c_double * 3)()
+        check(lib().sosrt_view_timing(self._h, ms))
+        return tuple(ms)
+
     def set_order_targets(self, d_targets: Optional[int]):
         """Fixed order counts for the solves that follow: `d_targets` is the device address of an int32 [B] array (kept by the
         caller while set), None / 0 switches back to the convergence test."""
