@@ -471,6 +471,43 @@ int sosrt_view_radiance_dev(sosrt_t* h, int B, int V, const double* mu_view /*ho
                             double* d_scat_out /*[B][nlev][2V], nullable*/, double* d_first_out /*[B][nlev][2V], nullable*/);
 int sosrt_view_timing(sosrt_t* h, double* ms /*[3]*/);
 
+/* ---- azimuth-resolved view radiance: the view stage per Fourier mode ------------------------------------
+ * A sensor looks at a view zenith AND a relative azimuth.  Mode m of the radiance obeys the order loop with ((-1)^m P^m, P0^m),
+ * and the view stage is linear in its rows and in P0: mode m at a view cosine is sosrt_view_radiance_dev run on the resident
+ * I^m with the rows of mode m, and the radiance at (s_j, phi) is the synthesis sum_m (2 - delta_m0) I^m(s_j) cos(m phi) over the
+ * view lanes.  Conventions as above: signed lanes s = (-mu_view, +mu_view), V2 = 2V <= 2 SOSRT_MAX_VIEWS,
+ * c(a, b, phi) = -(mu_a mu_b + s_a s_b cos phi), phi_q = linspace(0, pi, nphi); phi = 0 with an upward mu = mu0 is back-scatter.
+ * The specular surface holds mode by mode, at the same phi.  Detected by symbol; SOSRT_VERSION is unchanged.
+ *
+ * sosrt_phase_rows_modes_dev: d_rows_out[m - m_first][j][n] = R^m(s_j, mu_n) / (2 pi) * 4 / Z_n with the nphi-node normaliser
+ * Z_n of sosrt_phase_modes (the same reduction over the 2N grid exits), so at a node s_j = mu_a the row is row a of
+ * sosrt_phase_modes_dev, bit for bit.  sign_odd != 0 writes (-1)^m rows^m: what the view source of mode m takes, because it
+ * pairs rows[j][2N-1-k] with I[k], the fold of the grid.  sosrt_phase_p0_rows_modes_dev: d_out[m - m_first][b][j] =
+ * R^m(s_j, mu0_b) / (4 pi) * 2 / Z0_b with the normaliser of sosrt_phase_p0_modes.  Modes 1 <= m_first, m_first + m_count - 1
+ * <= min(SOSRT_MAX_MODES, nphi - 2); mode 0 stays sosrt_phase_rows_dev / sosrt_phase_p0_rows_dev.  Isotropic: exact zeros;
+ * Rayleigh m >= 3: exact zeros.  Both synchronise the handle's stream first (the weights of the modes go to the device).
+ *
+ * sosrt_phase_p0_rows_azimuth_dev: d_out[i][b][j] = p(c(s_j, mu0_b, phi_i)) / Z0_b, Z0_b the 25-node normaliser of the stored
+ * P0 (what sosrt_phase_p0_rows_dev divides by): the sum the modes of P0 converge to, without the truncation at M.  The
+ * [B][V2] block of one azimuth is the d_p0rows_* of sosrt_view_radiance_dev (d_scat_out = NULL): the first order at that
+ * azimuth; the mirror lane of the reflected-beam term is at the same phi, because c(-a, -b, phi) = c(a, b, phi).  Isotropic: 1.
+ *
+ * sosrt_view_azimuth_accumulate_dev: d_out[b][lev][j][i] (+)= (2 - delta_m0) d_val[b][lev][j] cos(m phi_i); m == 0 writes,
+ * m >= 1 adds, the term of sosrt_azimuth_accumulate_dev, so calls in ascending m give the bits of that rule.
+ *
+ * Refused with SOSRT_E_INVALID, nothing written: V2 outside 1..2 SOSRT_MAX_VIEWS; a lane that is not finite or outside
+ * [-1, 1]; a mode range outside the limits; nphi_out < 1; B above the current columns.  All enqueued on the handle's stream. */
+int sosrt_phase_rows_modes_dev(sosrt_t* h, int kind, double g, int m_first, int m_count, int nphi, int sign_odd, int V2,
+                               const double* mu_signed /*host [V2]*/, double* d_rows_out /*[m_count][V2][2N]*/);
+int sosrt_phase_p0_rows_modes_dev(sosrt_t* h, int B, int kind, double g, int m_first, int m_count, int nphi,
+                                  const double* d_mu0 /*[B]*/, int V2, const double* mu_signed /*host [V2]*/,
+                                  double* d_out /*[m_count][B][V2]*/);
+int sosrt_phase_p0_rows_azimuth_dev(sosrt_t* h, int B, int kind, double g, const double* d_mu0 /*[B]*/, int V2,
+                                    const double* mu_signed /*host [V2]*/, int nphi_out, const double* d_phi /*[nphi_out]*/,
+                                    double* d_out /*[nphi_out][B][V2]*/);
+int sosrt_view_azimuth_accumulate_dev(sosrt_t* h, int B, int m, int nlev, int V2, const double* d_val /*[B][nlev][V2]*/,
+                                      int nphi_out, const double* d_phi /*[nphi_out]*/, double* d_out /*[B][nlev][V2][nphi_out]*/);
+
 /* ---- multi-GPU: one process per GPU, columns sharded, ONE collective at the end ------------------
  * Nothing in SOS_Aer_main_specular.py:104-458 couples columns, so the order loop never communicates; these entry
  * points only assemble the results of the ranks on `root` over RCCL (xGMI inside a node).  RCCL is bound at run time

@@ -335,7 +335,7 @@ int sosrt_phase_matrix(sosrt_t* h, int kind, double g, double* P_out) {
 // ---------------------------------------------------------------------------------------------
 // Fourier modes in azimuth
 // ---------------------------------------------------------------------------------------------
-static int modes_check(sosrt_handle* h, int kind, double g, int m_first, int m_count, int nphi) {
+int sosrt::modes_check(sosrt_handle* h, int kind, double g, int m_first, int m_count, int nphi) {
     if (int e = phase_check(h, kind, g)) return e;
     if (m_first < 0 || m_count < 1) return fail(SOSRT_E_INVALID, "modes: need m_first >= 0 and m_count >= 1 (got %d, %d)", m_first, m_count);
     const int m_last = m_first + m_count - 1;
@@ -348,7 +348,7 @@ static int modes_check(sosrt_handle* h, int kind, double g, int m_first, int m_c
 
 // uploads cos(phi_q) and the weights of modes [mf, mf + mc) (row 0: the m = 0 ring) for phi = linspace(0, pi, nphi);
 // synchronises the handle's stream first: an earlier builder may still read the buffer
-static int modes_table(sosrt_handle* h, int nphi, int mf, int mc) {
+int sosrt::modes_table(sosrt_handle* h, int nphi, int mf, int mc) {
     const size_t need = (size_t)(2 + mc) * nphi;
     HIPCHK(hipStreamSynchronize(h->stream));
     if (int e = h->pf.d_modetab.reserve(need)) return e;

@@ -9,6 +9,9 @@
 
 using namespace sosrt;
 
+// columns a builder of the azimuth-resolved stage may be asked for: the current ones (before sosrt_set_columns, the handle's width)
+static int view_batch_cap(const sosrt_handle* h) { return h->have_cols ? h->B : h->max_batch; }
+
 static int view_phase_check(sosrt_handle* h, int kind, double g, int V2, const double* mu_signed, ViewMu* vm) {
     if (int e = need_gpu(h)) return e;
     if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
@@ -137,6 +140,72 @@ int sosrt_view_radiance_dev(sosrt_t* h, int B, int V, const double* mu_view, con
     }
     HIPCHK(hipEventRecord(vw.ev[3], s));
     vw.timed_first = d_first_out != nullptr;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// azimuth-resolved view radiance: mode rows and first-order phase values at the view lanes, the synthesis
+// ---------------------------------------------------------------------------------------------
+int sosrt_phase_rows_modes_dev(sosrt_t* h, int kind, double g, int m_first, int m_count, int nphi, int sign_odd, int V2,
+                               const double* mu_signed, double* d_rows_out) {
+    ViewMu vm;
+    if (int e = view_phase_check(h, kind, g, V2, mu_signed, &vm)) return e;
+    if (m_first < 1) return fail(SOSRT_E_INVALID, "mode rows: m_first = %d; mode 0 is sosrt_phase_rows_dev", m_first);
+    if (int e = modes_check(h, kind, g, m_first, m_count, nphi)) return e;
+    if (!d_rows_out) return fail(SOSRT_E_INVALID, "null output");
+    HIPCHK(hipSetDevice(h->device));
+    if (int e = modes_table(h, nphi, m_first, m_count)) return e;
+    launch_phase_rows_modes(h->stream, h->g, h->grid.d_w, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr,
+                            h->pf.ntab, h->pf.d_modetab.p, h->pf.d_modetab.p + nphi, nphi, m_first, m_count, sign_odd, V2, vm,
+                            d_rows_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_phase_p0_rows_modes_dev(sosrt_t* h, int B, int kind, double g, int m_first, int m_count, int nphi, const double* d_mu0,
+                                  int V2, const double* mu_signed, double* d_out) {
+    ViewMu vm;
+    if (int e = view_phase_check(h, kind, g, V2, mu_signed, &vm)) return e;
+    if (m_first < 1) return fail(SOSRT_E_INVALID, "mode rows: m_first = %d; mode 0 is sosrt_phase_p0_rows_dev", m_first);
+    if (int e = modes_check(h, kind, g, m_first, m_count, nphi)) return e;
+    if (B < 1 || !d_mu0 || !d_out) return fail(SOSRT_E_INVALID, "bad argument");
+    if (B > view_batch_cap(h)) return fail(SOSRT_E_INVALID, "B=%d: the handle's current columns are %d", B, view_batch_cap(h));
+    HIPCHK(hipSetDevice(h->device));
+    if (int e = modes_table(h, nphi, m_first, m_count)) return e;
+    launch_phase_p0_rows_modes(h->stream, h->g, h->grid.d_w, B, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr,
+                               h->pf.ntab, h->pf.d_modetab.p, h->pf.d_modetab.p + nphi, nphi, m_first, m_count, d_mu0, V2, vm, d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_phase_p0_rows_azimuth_dev(sosrt_t* h, int B, int kind, double g, const double* d_mu0, int V2, const double* mu_signed,
+                                    int nphi_out, const double* d_phi, double* d_out) {
+    ViewMu vm;
+    if (int e = view_phase_check(h, kind, g, V2, mu_signed, &vm)) return e;
+    if (B < 1 || !d_mu0 || !d_phi || !d_out) return fail(SOSRT_E_INVALID, "bad argument");
+    if (nphi_out < 1) return fail(SOSRT_E_INVALID, "nphi_out = %d: at least one azimuth", nphi_out);
+    if (B > view_batch_cap(h)) return fail(SOSRT_E_INVALID, "B=%d: the handle's current columns are %d", B, view_batch_cap(h));
+    if ((long long)nphi_out * V2 > 0x7fffffffLL) return fail(SOSRT_E_INVALID, "nphi_out * V2 too large");
+    HIPCHK(hipSetDevice(h->device));
+    launch_phase_p0_rows_azimuth(h->stream, h->g, h->grid.d_w, B, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr,
+                                 h->pf.ntab, h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, d_mu0, V2, vm, nphi_out, d_phi, d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_view_azimuth_accumulate_dev(sosrt_t* h, int B, int m, int nlev, int V2, const double* d_val, int nphi_out,
+                                      const double* d_phi, double* d_out) {
+    if (int e = need_gpu(h)) return e;
+    if (B < 1 || nlev < 1 || !d_val || !d_phi || !d_out) return fail(SOSRT_E_INVALID, "view azimuth accumulate: bad argument (B=%d nlev=%d)", B, nlev);
+    if (B > view_batch_cap(h)) return fail(SOSRT_E_INVALID, "B=%d: the handle's current columns are %d", B, view_batch_cap(h));
+    if (m < 0 || m > SOSRT_MAX_MODES) return fail(SOSRT_E_INVALID, "view azimuth accumulate: mode %d is outside 0..SOSRT_MAX_MODES = %d", m, SOSRT_MAX_MODES);
+    if (V2 < 1 || V2 > 2 * SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "V2=%d lanes: must be 1..%d", V2, 2 * SOSRT_MAX_VIEWS);
+    if (nphi_out < 1) return fail(SOSRT_E_INVALID, "nphi_out = %d: at least one azimuth", nphi_out);
+    const size_t n = (size_t)B * nlev * V2;
+    if (n * (size_t)nphi_out > (size_t)0x7fffffff * 256) return fail(SOSRT_E_INVALID, "view azimuth accumulate: output too large");
+    HIPCHK(hipSetDevice(h->device));
+    launch_view_azimuth_accumulate(h->stream, n, m, d_val, nphi_out, d_phi, d_out);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

@@ -172,29 +172,6 @@ __global__ __launch_bounds__(256) void k_phase_matrix(Grid g, const double* __re
     for (int m = tid; m < D; m += blockDim.x) P[(size_t)m * D + n] = 4 * P[(size_t)m * D + n] / norm;
 }
 
-// Ring of mode m: R^m(a, b) = trapz_q [p(c(phi_q)) + (-1)^m p(c(phi_q + pi))] cos(m phi_q),
-// c(phi) = -(mu_a mu_b + s_a s_b cos phi), phi_q = linspace(0, pi, nphi).  acc[0] is the m = 0 ring (the normaliser),
-// acc[j], 1 <= j <= mc, mode mf + j - 1.  tab[j][q] = w_q cos(m_j phi_q) (row 0: w_q).  K is a compile-time bound so that
-// the accumulators stay in registers; the guard j <= mc is uniform.
-template <int K>
-__device__ __forceinline__ void ring_modes(const PhaseFn& p, double cc, double ss, const double* __restrict__ cosphi,
-                                           const double* __restrict__ tab, int nphi, int mf, int mc, double (&acc)[K]) {
-#pragma unroll
-    for (int j = 0; j < K; ++j) acc[j] = 0;
-    for (int q = 0; q < nphi; ++q) {
-        const double x = ss * cosphi[q];
-        const double p1 = p(-(cc + x)), p2 = p(-(cc - x));
-        const double sp = p1 + p2, sm = p1 - p2;
-#pragma unroll
-        for (int j = 0; j < K; ++j)
-            if (j <= mc) acc[j] += tab[(size_t)j * nphi + q] * ((j > 0 && ((mf + j - 1) & 1)) ? sm : sp);
-    }
-}
-
-// Rayleigh's p is quadratic in cos phi: its modes m >= 3 are zero, not rounding noise (a matrix of noise has no flip symmetry to
-// rounding and would cost the solve of that mode the full contraction product)
-__device__ __forceinline__ bool vanishes(const PhaseFn& p, int m) { return p.kind == SOSRT_PHASE_RAYLEIGH && m >= 3; }
-
 // P^m[a][n] = R^m(a, n) / (2 pi) * 4 / Z_n, Z_n = trapz_mu(R^0(., n) / (2 pi)); out [mc][D][D]; one workgroup per column n
 template <int K>
 __global__ __launch_bounds__(256) void k_phase_modes(Grid g, const double* __restrict__ w_all, PhaseFn p,
@@ -282,6 +259,19 @@ __global__ __launch_bounds__(256) void k_azimuth_accumulate(int L, int D, int m,
         if (m == 0) o[i] = v;
         else o[i] = azimuth_term(o[i], v, m, phi[j]);
     }
+}
+
+// The same term at the view lanes: val [n] = [B][nlev][2V] is mode m of the view radiance at the requested
+// levels already, out [n][nphi].  One thread per element of out.
+__global__ __launch_bounds__(256) void k_view_azimuth_accumulate(size_t n, int m, const double* __restrict__ val, int nphi,
+                                                                 const double* __restrict__ phi, double* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * nphi) return;
+    const size_t e = i / nphi;
+    const int j = (int)(i - e * nphi);
+    const double v = val[e];
+    if (m == 0) out[i] = v;
+    else out[i] = azimuth_term(out[i], v, m, phi[j]);
 }
 
 // The same sum over all modes in one launch: I0 [B][L][D] is mode 0, Im [M][B][L][D] the modes 1..M; `out` is written once
@@ -572,6 +562,11 @@ void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B,
 void launch_azimuth_accumulate(hipStream_t s, const Grid& g, int B, int m, const double* Im, int nlev, const int* levels,
                                int nphi_out, const double* phi, double* out) {
     hipLaunchKernelGGL(k_azimuth_accumulate, dim3(B * nlev), dim3(256), 0, s, g.L, g.D, m, Im, nlev, levels, nphi_out, phi, out);
+}
+
+void launch_view_azimuth_accumulate(hipStream_t s, size_t n, int m, const double* val, int nphi_out, const double* phi, double* out) {
+    hipLaunchKernelGGL(k_view_azimuth_accumulate, dim3((unsigned)((n * nphi_out + 255) / 256)), dim3(256), 0, s, n, m, val, nphi_out,
+                       phi, out);
 }
 
 void launch_azimuth_synthesize(hipStream_t s, const Grid& g, int B, int M, const double* I0, const double* Im, int nlev,

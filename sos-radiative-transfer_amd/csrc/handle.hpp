@@ -371,5 +371,9 @@ int ensure_w32(sosrt_handle* h);
 int ensure_matrices(sosrt_handle* h, hipStream_t s);
 // api_columns.hip: groups the cache of combined matrices may hold
 int mix_group_cap(const sosrt_handle* h, bool sets);
+// api_phasefn.hip, shared with the mode builders at view lanes (api_view.hip): the checks of a mode range, and the upload of
+// cos(phi_q) and the weights of modes [mf, mf + mc) into pf.d_modetab (synchronises the handle's stream first)
+int modes_check(sosrt_handle* h, int kind, double g, int m_first, int m_count, int nphi);
+int modes_table(sosrt_handle* h, int nphi, int mf, int mc);
 
 }  // namespace sosrt

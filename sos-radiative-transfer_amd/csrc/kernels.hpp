@@ -382,6 +382,20 @@ void launch_phase_rows(hipStream_t s, const Grid& g, const double* w, int kind, 
 void launch_phase_p0_rows(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
                           const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi, const double* mu0,
                           int V2, const ViewMu& mu, double* out);
+// the same rows of the Fourier modes [m_first, m_first + m_count), m_first >= 1: rows [m_count][V2][D]
+// ((-1)^m rows^m with sign_odd), out [m_count][B][V2]; cosphi, tab as launch_phase_modes takes them
+void launch_phase_rows_modes(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
+                             const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
+                             int m_count, int sign_odd, int V2, const ViewMu& mu, double* rows);
+void launch_phase_p0_rows_modes(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
+                                const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
+                                int m_count, const double* mu0, int V2, const ViewMu& mu, double* out);
+// out [nphi_out][B][V2] = p(c(s_j, mu0_b, phi_i)) / Z0_b with launch_phase_p0_rows' normaliser (cosphi, wphi: its ring)
+void launch_phase_p0_rows_azimuth(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
+                                  const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi,
+                                  const double* mu0, int V2, const ViewMu& mu, int nphi_out, const double* phi, double* out);
+// out [n][nphi_out] (+)= (2 - delta_m0) val[n] cos(m phi[j]), n = B nlev 2V   (m == 0 writes, m >= 1 adds; epilogue.hip)
+void launch_view_azimuth_accumulate(hipStream_t s, size_t n, int m, const double* val, int nphi_out, const double* phi, double* out);
 // S [nrows][2V] = diag(ca) Isrc W_atm + diag(cr) Isrc W_aer with the rows folded into Wfold [view_source_kpad(D)][view_source_cols(V)]
 // (scratch); rows_aer may be null (single slab: zeros)
 int view_source_cols(int V);

@@ -1,5 +1,5 @@
 // The phase functions of the azimuth builders and their ring rule, shared by epilogue.hip (k_phase_p0, k_phase_matrix and the
-// Fourier modes) and view.hip (the same two at view cosines off the grid).
+// Fourier modes) and view.hip (the same at view cosines off the grid).
 // Phase-function kinds: isotropic (phase:68), Rayleigh (phase:79), Henyey-Greenstein (phase:141) and a
 // tabulated function with the reference's linear interpolation (phase:198-236; fwc:3,173 is its table).
 #pragma once
@@ -49,5 +49,28 @@ __device__ __forceinline__ double ring(const PhaseFn& p, double cc, double ss, c
     }
     return acc;
 }
+
+// Ring of mode m: R^m(a, b) = trapz_q [p(c(phi_q)) + (-1)^m p(c(phi_q + pi))] cos(m phi_q),
+// c(phi) = -(mu_a mu_b + s_a s_b cos phi), phi_q = linspace(0, pi, nphi).  acc[0] is the m = 0 ring (the normaliser),
+// acc[j], 1 <= j <= mc, mode mf + j - 1.  tab[j][q] = w_q cos(m_j phi_q) (row 0: w_q).  K is a compile-time bound so that
+// the accumulators stay in registers; the guard j <= mc is uniform.
+template <int K>
+__device__ __forceinline__ void ring_modes(const PhaseFn& p, double cc, double ss, const double* __restrict__ cosphi,
+                                           const double* __restrict__ tab, int nphi, int mf, int mc, double (&acc)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = 0;
+    for (int q = 0; q < nphi; ++q) {
+        const double x = ss * cosphi[q];
+        const double p1 = p(-(cc + x)), p2 = p(-(cc - x));
+        const double sp = p1 + p2, sm = p1 - p2;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (j <= mc) acc[j] += tab[(size_t)j * nphi + q] * ((j > 0 && ((mf + j - 1) & 1)) ? sm : sp);
+    }
+}
+
+// Rayleigh's p is quadratic in cos phi: its modes m >= 3 are zero, not rounding noise (a matrix of noise has no flip symmetry to
+// rounding and would cost the solve of that mode the full contraction product)
+__device__ __forceinline__ bool vanishes(const PhaseFn& p, int m) { return p.kind == SOSRT_PHASE_RAYLEIGH && m >= 3; }
 
 }  // namespace sosrt

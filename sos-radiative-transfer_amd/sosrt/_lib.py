@@ -89,6 +89,10 @@ SIGNATURES = {
     "sosrt_phase_p0_rows_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_view_radiance_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 7 + [c_int, c_int] + [c_void_p] * 3),
     "sosrt_view_timing": (c_int, [c_void_p, _dp]),
+    "sosrt_phase_rows_modes_dev": (c_int, [c_void_p, c_int, c_double, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sosrt_phase_p0_rows_modes_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "sosrt_phase_p0_rows_azimuth_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "sosrt_view_azimuth_accumulate_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_comm_unique_id": (c_int, [c_void_p]),
     "sosrt_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "sosrt_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

@@ -7,7 +7,8 @@ independent columns that share (nb_layers, nb_angles, phase matrices) in one lau
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
@@ -54,6 +55,10 @@ class BatchResult:
     I_view: Optional[np.ndarray] = None            # [B, nlev, 2V] radiance at the view lanes = I_view_first + I_view_scattered
     I_view_first: Optional[np.ndarray] = None      # [B, nlev, 2V] its closed-form first order
     I_view_scattered: Optional[np.ndarray] = None  # [B, nlev, 2V] the transport of the field's source (orders n >= 2)
+    I_view_azimuth: Optional[np.ndarray] = None            # [B, nlev, 2V, len(view_azimuths)] (view_azimuths=...) = _first + _scattered
+    I_view_azimuth_first: Optional[np.ndarray] = None      # its first order: exact at (lane, azimuth), or the sum of the modes'
+    I_view_azimuth_scattered: Optional[np.ndarray] = None  # the synthesis of the per-mode transports of the fields' sources
+    view_mode_status: Optional[np.ndarray] = None          # [M + 1, B] status of the solve of every Fourier mode (row 0 is `status`)
 
 
 _solvers = {}
@@ -102,7 +107,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular", tol=1e-4, max_orders=256,
                   save_orders=False, device=0, devices=None, raise_on_error=True, first_order="coded", azimuths=None,
                   n_modes=None, nphi_modes=None, levels=(0, -1), aer_set=None, mode_batch=False, mode_chunk=None,
-                  view_mu=None, view_levels=(0, -1), view_quadrature="grid") -> BatchResult:
+                  view_mu=None, view_levels=(0, -1), view_quadrature="grid", view_azimuths=None,
+                  view_first_order="exact") -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -145,7 +151,19 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     optical-depth step over the view cosine is >~ 1 it inherits the trapezoid rule's overshoot.  `'linear'` attenuates a
     piecewise-linear source exactly: the quadrature for limb-ward views.  I, n and status are those of the plain call, bit
     for bit.  Needs named phase functions (not arrays), the specular surface, the coded first order and a single device; not
-    with `azimuths` or `aer_set`."""
+    with `azimuths` or `aer_set`.
+
+    `view_azimuths` (radians, array; needs `view_mu`): also the RADIANCE AT A VIEW COSINE AND A RELATIVE AZIMUTH,
+    BatchResult.I_view_azimuth [B, len(view_levels), 2V, len(view_azimuths)] = I_view_azimuth_first + I_view_azimuth_scattered:
+    the view stage run per Fourier mode m = 0 .. `n_modes` (default 16; `nphi_modes` as for `azimuths`) on the field of that
+    mode, solved with the order counts of mode 0, and summed over the modes at the view lanes (`view_azimuth_modes`).  phi = 0
+    with an upward view_mu = mu0 is back-scatter.  `view_first_order='exact'` (default): the first order from the phase
+    function at (lane, azimuth) itself, without the truncation at n_modes, which rings for a forward-peaked aerosol;
+    `'modes'`: the sum of the modes' first orders.  BatchResult.view_mode_status [n_modes + 1, B].  I, n, status and I_view*
+    are those of the call without `view_azimuths`, bit for bit.  Not with `azimuths`, `mode_batch` or `mode_chunk`."""
+    if view_azimuths is not None or view_first_order != "exact":
+        vphi, vM, vnphi = _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_modes, nphi_modes, mode_batch,
+                                             mode_chunk)
     if view_mu is not None:
         vmu, vlev, vquad = _view_args(view_mu, view_levels, view_quadrature, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface,
                                       devices, first_order, azimuths, aer_set, atm_phase_fun, aer_phase_fun)
@@ -218,6 +236,13 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         out.I_view_first, out.I_view_scattered = view_radiance(s, tau, r.I, mu0v, vmu, vlev, vquad, atm_phase_fun, g_atm, mie_atm,
                                                                aer_phase_fun, g_aer, mie_aer, device)
         out.I_view = out.I_view_first + out.I_view_scattered
+        if view_azimuths is not None:
+            out.I_view_azimuth_first, out.I_view_azimuth_scattered, out.view_mode_status = view_azimuth_modes(
+                s, tau, r, mu0v, vmu, vlev, vquad, vphi, vM, vnphi, view_first_order, out.I_view_first, out.I_view_scattered,
+                atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer, device)
+            out.I_view_azimuth = out.I_view_azimuth_first + out.I_view_azimuth_scattered
+            if raise_on_error:
+                _raise_status(out.view_mode_status, N)
     return out
 
 
@@ -225,7 +250,8 @@ def _view_args(view_mu, view_levels, view_quadrature, nb_layers, P_atm, P_aer, P
                azimuths, aer_set, atm_phase_fun, aer_phase_fun):
     """Checks of the view-radiance call, made before any handle exists: (view_mu [V], levels as row indices, quadrature)."""
     if azimuths is not None:
-        raise ValueError("view_mu is not available with azimuths (the view stage integrates the azimuth average)")
+        raise ValueError("view_mu is not available with azimuths (the grid's azimuth synthesis); the radiance at a view cosine "
+                         "and an azimuth is view_azimuths=[...]")
     if aer_set is not None or isinstance(aer_phase_fun, (list, tuple)):
         raise ValueError("view_mu is not available with aer_set (the view stage reads one aerosol phase function)")
     if devices is not None and len(devices) > 1:
@@ -249,6 +275,31 @@ def _view_args(view_mu, view_levels, view_quadrature, nb_layers, P_atm, P_aer, P
     if not lev or any(not -L <= x < L for x in lev):
         raise ValueError("view_levels must be row indices in [-%d, %d)" % (L, L))
     return vmu, [x + L if x < 0 else x for x in lev], view_quadrature
+
+
+def _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_modes, nphi_modes, mode_batch, mode_chunk):
+    """Checks of the azimuth-resolved view call, made before any handle exists (what `view_mu` refuses, `_view_args` refuses
+    next): (azimuths [n], M, nphi)."""
+    if view_first_order not in ("exact", "modes"):
+        raise ValueError("view_first_order must be 'exact' or 'modes' (got %r)" % (view_first_order,))
+    if view_azimuths is None:
+        raise ValueError("view_first_order belongs to the azimuth-resolved view call: give view_azimuths")
+    if view_mu is None:
+        raise ValueError("view_azimuths are the azimuths of the view cosines: give view_mu")
+    if azimuths is not None:
+        raise ValueError("view_azimuths are not available with azimuths (one mode loop serves one of them)")
+    if mode_batch or mode_chunk is not None:
+        raise ValueError("view_azimuths are not available with mode_batch / mode_chunk (the view stage reads one mode's resident field)")
+    phi = np.asarray(view_azimuths, dtype=np.float64)
+    if phi.ndim != 1 or phi.size == 0 or not np.all(np.isfinite(phi)):
+        raise ValueError("view_azimuths must be a non-empty 1-d array of finite angles (radians)")
+    M = 16 if n_modes is None else int(n_modes)
+    if not 1 <= M <= _lib.MAX_MODES:
+        raise ValueError("n_modes must be in 1..%d (got %d)" % (_lib.MAX_MODES, M))
+    nphi = max(25, 2 * M + 1) if nphi_modes is None else int(nphi_modes)
+    if M > nphi - 2:
+        raise ValueError("n_modes = %d needs nphi_modes >= %d (got %d)" % (M, M + 2, nphi))
+    return phi, M, nphi
 
 
 def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
@@ -447,12 +498,33 @@ def _azimuth_args(azimuths, n_modes, nphi_modes, levels, nb_layers, P_atm, P_aer
     return M, nphi, [x + L if x < 0 else x for x in lev]
 
 
-def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
-                  mie_aer, device=0):
-    """Modes m = 1..M of the solve `r` (the mode-0 result of handle `s`, whose columns are set): per mode the matrices and
-    first-order vectors of both phase functions, a solve with the order counts of mode 0 (sosrt_set_order_targets), and the
-    synthesis at `levels`.  Returns (I_azimuth [B, nlev, 2N, len(azimuths)], mode status [M + 1, B]).  The handle's mode-0
-    phase matrices are put back and its targets cleared afterwards, also on error."""
+@dataclass
+class _ModeLoop:
+    """What `begin`, `step` and `finish` of `_solve_modes` see.  The loop fills the fields below; a driver keeps buffers of its
+    own under `own`."""
+    dev: object              # torch device of the handle
+    B: int
+    L: int
+    D: int
+    M: int
+    nphi: int
+    kinds: list              # per phase function (atmosphere, aerosol): (device kind, g); its table, if any, is `tables[i]`
+    tables: list
+    d_tau: object = None     # [B, L]
+    d_mu0: object = None     # [B]
+    d_Im: object = None      # [B, L, 2N]: set by `begin` to the mode-0 field; after the solve of mode m, the field of mode m
+    own: SimpleNamespace = field(default_factory=SimpleNamespace)
+
+
+def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, finish, mie_on_handle=False):
+    """The loop over the Fourier modes m = 1..M of the solve `r` (the mode-0 result of handle `s`, whose columns are set): per
+    mode the matrices and first-order vectors of both phase functions `phases` = ((name, g, mie) of the atmosphere, of the
+    aerosol), a solve with the order counts of mode 0 (sosrt_set_order_targets) into the resident c.d_Im, then `step(c, m)`.
+    The phase functions are resolved once, here (c.kinds, c.tables: what every builder of the loop and of the steps takes);
+    mie_on_handle: `device=True` in a `mie` dict means this handle's Mie kernels, as `device_phase` reads it.  `begin(c)` runs
+    before the modes are built and sets c.d_Im to the mode-0 field; `finish(c)` after the last mode, and its value is returned
+    with the mode status [M + 1, B].  The handle's mode-0 phase matrices are put back and its targets cleared afterwards, also
+    on error."""
     import torch
     from .inputs import _scalar_phase
     B, L = tau.shape
@@ -464,20 +536,23 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
     with torch.cuda.device(dev):
         s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
         try:
-            d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
-            d_mu0 = torch.from_numpy(np.ascontiguousarray(mu0, dtype=np.float64)).to(dev)
+            kinds, tables = [], []
+            for name, g, mie in phases:
+                kw = dict(mie or {})
+                if mie_on_handle and kw.get("device") is True:
+                    kw["device"] = s
+                kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **kw)[1]
+                kinds.append((kind, g))
+                tables.append(tab)
+            c = _ModeLoop(dev=dev, B=B, L=L, D=D, M=M, nphi=nphi, kinds=kinds, tables=tables)
+            c.d_tau = d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
+            c.d_mu0 = d_mu0 = torch.from_numpy(np.ascontiguousarray(mu0, dtype=np.float64)).to(dev)
             d_target = torch.from_numpy(np.ascontiguousarray(r.n, dtype=np.int32)).to(dev)
-            d_lev = torch.tensor(levels, dtype=torch.int32, device=dev)
-            d_phi = torch.from_numpy(np.ascontiguousarray(azimuths, dtype=np.float64)).to(dev)
-            nlev, nout = len(levels), d_phi.numel()
-            d_out = torch.empty((B, nlev, D, nout), dtype=torch.float64, device=dev)
-            d_Im = torch.from_numpy(np.ascontiguousarray(r.I)).to(dev)
-            s.azimuth_accumulate_device(0, d_Im.data_ptr(), d_lev.data_ptr(), nlev, d_phi.data_ptr(), nout, d_out.data_ptr(), B=B)
+            begin(c)
             # modes m >= 1 of both phase functions: the matrices to the host (one fold each in set_phase), the first-order
             # vectors where the solve reads them
             Pm, d_P0 = [], []
-            for name, g, mie in ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)):
-                kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **(mie or {}))[1]
+            for (kind, g), tab in zip(kinds, tables):
                 if tab is not None:
                     s.set_phase_table(*tab)
                 Pm.append(s.phase_modes(kind, 1, M, nphi, g))
@@ -492,19 +567,120 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
                 # the solve of mode m takes (-1)^m P^m: its contraction reads P[a][flip b], the stored matrix at phi + pi
                 sgn = -1.0 if m & 1 else 1.0
                 s.set_phase(sgn * Pm[0][m - 1], sgn * Pm[1][m - 1])
-                s.solve_device(d_tau.data_ptr(), d_P0[0][m - 1].data_ptr(), d_P0[1][m - 1].data_ptr(), d_Im.data_ptr(),
+                s.solve_device(d_tau.data_ptr(), d_P0[0][m - 1].data_ptr(), d_P0[1][m - 1].data_ptr(), c.d_Im.data_ptr(),
                                d_n_orders=d_n.data_ptr(), d_status=d_st[m - 1].data_ptr())
-                s.azimuth_accumulate_device(m, d_Im.data_ptr(), d_lev.data_ptr(), nlev, d_phi.data_ptr(), nout, d_out.data_ptr(), B=B)
+                step(c, m)
             s.synchronize()
             status[1:] = d_st.cpu().numpy()
-            I_az = d_out.cpu().numpy()
+            result = finish(c)
         finally:
             s.synchronize()
             s.set_order_targets(None)
             s.set_stream(None)
             if P_mode0[0] is not None:
                 s.set_phase(*P_mode0)
-    return I_az, status
+    return result, status
+
+
+def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
+                  mie_aer, device=0):
+    """Modes m = 1..M of the solve `r` (the mode-0 result of handle `s`, whose columns are set): per mode the matrices and
+    first-order vectors of both phase functions, a solve with the order counts of mode 0 (sosrt_set_order_targets), and the
+    synthesis at `levels` (`_solve_modes` with the grid's synthesis as its step).  Returns (I_azimuth [B, nlev, 2N,
+    len(azimuths)], mode status [M + 1, B]).  The handle's mode-0 phase matrices are put back and its targets cleared
+    afterwards, also on error."""
+    import torch
+    nlev = len(levels)
+
+    def begin(c):
+        o = c.own
+        o.d_lev = torch.tensor(levels, dtype=torch.int32, device=c.dev)
+        o.d_phi = torch.from_numpy(np.ascontiguousarray(azimuths, dtype=np.float64)).to(c.dev)
+        o.d_out = torch.empty((c.B, nlev, c.D, o.d_phi.numel()), dtype=torch.float64, device=c.dev)
+        c.d_Im = torch.from_numpy(np.ascontiguousarray(r.I)).to(c.dev)
+        step(c, 0)
+
+    def step(c, m):
+        o = c.own
+        s.azimuth_accumulate_device(m, c.d_Im.data_ptr(), o.d_lev.data_ptr(), nlev, o.d_phi.data_ptr(), o.d_phi.numel(),
+                                    o.d_out.data_ptr(), B=c.B)
+
+    return _solve_modes(s, tau, r, mu0, M, nphi, ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)), device,
+                        begin, step, lambda c: c.own.d_out.cpu().numpy())
+
+
+def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azimuths, M, nphi, first_order, first0, scat0,
+                       atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer, device=0):
+    """The view stage per Fourier mode: mode 0 is (`first0`, `scat0`), the result of `view_radiance` on
+    r.I; per mode m >= 1 `_solve_modes` leaves the field I^m resident, `Solver.view_radiance_device` runs on it with the rows
+    (-1)^m rows^m and p0rows^m of both phase functions (built for all modes once, before the loop), and the synthesis adds
+    2 cos(m phi) times the result at the view lanes.  first_order 'exact': the first order is one closed-form evaluation per
+    azimuth from p(c(lane, mu0, phi)) / Z0, written, not accumulated; 'modes': the sum of the modes' first orders.  Returns
+    (first [B, nlev, 2V, len(azimuths)], scattered (same shape), mode status [M + 1, B])."""
+    import torch
+    V2, nlev, nout = 2 * len(view_mu), len(levels), len(azimuths)
+    sgn = np.concatenate((-view_mu, view_mu))
+    modes_first = first_order == "modes"
+
+    def begin(c):
+        dev, B, o = c.dev, c.B, c.own
+        c.d_Im = torch.from_numpy(np.ascontiguousarray(r.I)).to(dev)
+        o.d_phi = torch.from_numpy(np.ascontiguousarray(azimuths, dtype=np.float64)).to(dev)
+        o.rows, o.p0rows, o.p0exact = [], [], []
+        # (the handle runs on torch's current stream here: the builders are ordered after the allocations and uploads)
+        for (kind, g), tab in zip(c.kinds, c.tables):
+            if tab is not None:
+                s.set_phase_table(*tab)
+            rw = torch.empty((M, V2, c.D), dtype=torch.float64, device=dev)
+            s.phase_rows_modes_device(kind, sgn, rw.data_ptr(), 1, M, nphi, g, sign_odd=True)
+            o.rows.append(rw)
+            if modes_first:
+                p0 = torch.empty((M, B, V2), dtype=torch.float64, device=dev)
+                s.phase_p0_rows_modes_device(kind, c.d_mu0.data_ptr(), sgn, p0.data_ptr(), B, 1, M, nphi, g)
+                o.p0rows.append(p0)
+            else:
+                p0 = torch.empty((nout, B, V2), dtype=torch.float64, device=dev)
+                s.phase_p0_rows_azimuth_device(kind, c.d_mu0.data_ptr(), sgn, o.d_phi.data_ptr(), nout, p0.data_ptr(), B, g)
+                o.p0exact.append(p0)
+        o.d_scat = torch.from_numpy(np.ascontiguousarray(scat0)).to(dev)
+        o.d_first = torch.from_numpy(np.ascontiguousarray(first0)).to(dev)
+        o.d_out_scat = torch.empty((B, nlev, V2, nout), dtype=torch.float64, device=dev)
+        o.d_out_first = torch.empty((B, nlev, V2, nout), dtype=torch.float64, device=dev) if modes_first else None
+        accumulate(c, 0)
+
+    def accumulate(c, m):
+        o = c.own
+        s.view_azimuth_accumulate_device(m, o.d_scat.data_ptr(), nlev, V2, o.d_phi.data_ptr(), nout, o.d_out_scat.data_ptr(), B=c.B)
+        if modes_first:
+            s.view_azimuth_accumulate_device(m, o.d_first.data_ptr(), nlev, V2, o.d_phi.data_ptr(), nout, o.d_out_first.data_ptr(),
+                                             B=c.B)
+
+    def step(c, m):
+        o = c.own
+        s.view_radiance_device(view_mu, c.d_tau.data_ptr(), c.d_Im.data_ptr(), o.rows[0][m - 1].data_ptr(),
+                               o.rows[1][m - 1].data_ptr(), levels, d_scat_out=o.d_scat.data_ptr(),
+                               d_first_out=o.d_first.data_ptr() if modes_first else 0,
+                               d_p0rows_atm=o.p0rows[0][m - 1].data_ptr() if modes_first else 0,
+                               d_p0rows_aer=o.p0rows[1][m - 1].data_ptr() if modes_first else 0, quadrature=quadrature, B=c.B)
+        accumulate(c, m)
+
+    def finish(c):
+        o = c.own
+        if modes_first:
+            first = o.d_out_first.cpu().numpy()
+        else:
+            d_f = torch.empty((nout, c.B, nlev, V2), dtype=torch.float64, device=c.dev)
+            for i in range(nout):
+                s.view_radiance_device(view_mu, c.d_tau.data_ptr(), 0, 0, 0, levels, d_first_out=d_f[i].data_ptr(),
+                                       d_p0rows_atm=o.p0exact[0][i].data_ptr(), d_p0rows_aer=o.p0exact[1][i].data_ptr(),
+                                       quadrature=quadrature, B=c.B)
+            s.synchronize()
+            first = d_f.permute(1, 2, 3, 0).contiguous().cpu().numpy()   # (the azimuth last, as the synthesis writes it)
+        return first, o.d_out_scat.cpu().numpy()
+
+    (first, scat), status = _solve_modes(s, tau, r, mu0, M, nphi, ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)),
+                                         device, begin, step, finish, mie_on_handle=True)
+    return first, scat, status
 
 
 # mode_batch=True: a chunk of c modes is a batch of c x B columns, and every field buffer of the handle (and the chunk's share of

@@ -533,6 +533,40 @@ class Solver:
         check(lib().sosrt_view_timing(self._h, ms))
         return tuple(ms)
 
+    # ---- azimuth-resolved view radiance: the view stage per Fourier mode (sosrt.h) ----
+    def phase_rows_modes_device(self, kind, mu_signed, d_rows_out: int, m_first, m_count, nphi=25, g=0.0, sign_odd=False):
+        """Rows of the modes m_first .. m_first + m_count - 1 (m_first >= 1) of the phase function at the exit cosines
+        `mu_signed` [V2] (host), normalised as `phase_modes` normalises: d_rows_out is the address of [m_count, V2, 2N] float64.
+        sign_odd: mode m is written as (-1)^m rows^m, what `view_radiance_device` takes for the field of mode m."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_signed), dtype=np.float64)
+        check(lib().sosrt_phase_rows_modes_dev(self._h, self._KINDS[kind], float(g), int(m_first), int(m_count), int(nphi),
+                                               int(bool(sign_odd)), int(m.size), _ptr(m),
+                                               ctypes.c_void_p(d_rows_out) if d_rows_out else None))
+
+    def phase_p0_rows_modes_device(self, kind, d_mu0: int, mu_signed, d_out: int, B: int, m_first, m_count, nphi=25, g=0.0):
+        """The same of P0 for B columns: d_mu0 [B], d_out [m_count, B, V2] (addresses)."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_signed), dtype=np.float64)
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_phase_p0_rows_modes_dev(self._h, int(B), self._KINDS[kind], float(g), int(m_first), int(m_count),
+                                                  int(nphi), vp(d_mu0), int(m.size), _ptr(m), vp(d_out)))
+
+    def phase_p0_rows_azimuth_device(self, kind, d_mu0: int, mu_signed, d_phi: int, nphi_out: int, d_out: int, B: int, g=0.0):
+        """p(c(s_j, mu0_b, phi_i)) / Z0_b, the first-order phase value at a view lane and an azimuth with the normaliser of
+        `phase_p0_rows_device`: d_mu0 [B], d_phi [nphi_out] (radians), d_out [nphi_out, B, V2] (addresses).  The [B, V2] block of
+        one azimuth is a `d_p0rows_*` of `view_radiance_device`."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_signed), dtype=np.float64)
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_phase_p0_rows_azimuth_dev(self._h, int(B), self._KINDS[kind], float(g), vp(d_mu0), int(m.size), _ptr(m),
+                                                    int(nphi_out), vp(d_phi), vp(d_out)))
+
+    def view_azimuth_accumulate_device(self, m: int, d_val: int, nlev: int, V2: int, d_phi: int, nphi_out: int, d_out: int,
+                                       B: Optional[int] = None):
+        """out[b][lev][j][i] (+)= (2 - delta_m0) val[b][lev][j] cos(m phi[i]) on device addresses (m = 0 writes): the synthesis
+        of `azimuth_accumulate_device` over view lanes, d_val [B, nlev, V2] being mode m of the view radiance."""
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_view_azimuth_accumulate_dev(self._h, int(self.B if B is None else B), int(m), int(nlev), int(V2), vp(d_val),
+                                                      int(nphi_out), vp(d_phi), vp(d_out)))
+
     def set_order_targets(self, d_targets: Optional[int]):
         """Fixed order counts for the solves that follow: `d_targets` is the device address of an int32 [B] array (kept by the
         caller while set), None / 0 switches back to the convergence test."""
