@@ -30,9 +30,11 @@
 //
 // The plain rows need no product at all when W_atm has a low rank (SOSRT_CONTRACT_F64, g.lr_rank >= 0: Rayleigh
 // r = 2, iso r = 1; sosrt_set_phase certifies max |W_atm - U V| <= 1e-12 max |W_atm|): Jn = ca (In_1 U) V, r dot
-// products and an r-term expansion per row, 16 D bytes of HBM and no MFMA (jn_gemm_tile.hpp: lowrank_rows).  The
-// launches keep their grids and their duties; a workgroup that would have held a tile of plain rows streams its
-// share of that tile's rows instead, and the slab tiles -- now the long ones -- are numbered first.
+// products and an r-term expansion per row, 16 D bytes of HBM and no MFMA (jn_gemm_tile.hpp: lowrank_rows, and for a handle
+// without atmosphere sets lowrank_stream).  The launches keep their duties, and the live-column tilings their grids: a workgroup
+// that would have held a tile of plain rows streams its share of that tile's rows instead, and the slab tiles -- now the long
+// ones -- are numbered first.  The dense launch of such a handle is its slab tiles' workgroups, then stream workgroups with a
+// run of the plain list each (launch_gemm, jn_gemm_dense).
 #include "jn_gemm_tile.hpp"
 
 namespace sosrt {
@@ -88,8 +90,9 @@ __device__ __forceinline__ void jn_gemm_dense(const GemmArgs& g, const AtmSets& 
         return;
     }
     publish_live(g);
-    __shared__ double sA[(SYM ? 2 : 1) * 16 * (GEMM_RT > 2 ? GEMM_RT : 2) * A_LD];
-    __shared__ double sB[GEMM_KC * B_LD];
+    constexpr int kSA = (SYM ? 2 : 1) * 16 * (GEMM_RT > 2 ? GEMM_RT : 2) * A_LD, kSB = GEMM_KC * B_LD;
+    __shared__ __attribute__((aligned(16))) double sA[kSA];
+    __shared__ __attribute__((aligned(16))) double sB[kSB];
     __shared__ int s_any;
     // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2.  The column tiles of one row
     // tile read the same rows of In_1: numbering them 8 apart puts them on one XCD, a few dispatches apart,
@@ -99,13 +102,28 @@ __device__ __forceinline__ void jn_gemm_dense(const GemmArgs& g, const AtmSets& 
     const int tiles = tiles_main + tiles_slab;
     const int nct = (g.D + GEMM_BN - 1) / GEMM_BN;
     const int id = blockIdx.x;
+    if (!ATM && g.lr_rank >= 0) {
+        // Low-rank plain rows, no atmosphere sets (launch_gemm sets lr_run and sizes the grid): the slab tiles' workgroups, numbered
+        // as ever so that the column tiles of a slab tile share an XCD, then the stream workgroups, each with a run of lr_run entries
+        // of the plain list, a quarter of it per wave -- a plain row is read by one workgroup only and has no use for the pairing.
+        // No workgroup of this launch holds a TILE of plain rows: the ids that pad the slab tiles to a multiple of 8 leave.
+        const int slab_ids = (tiles_slab + 7) / 8 * 8 * nct;
+        if (id >= slab_ids) {
+            const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x) >> 6;
+            const int rw = g.lr_run >> 2, first = (id - slab_ids) * g.lr_run + wave * rw;
+            lowrank_stream<true>(g, LrRun<ListRows>{ListRows{g.rows_main, g.n_main}, first, 1}, min(max(g.n_main - first, 0), rw), true,
+                           sA, kSA, sB, kSB);
+            return;
+        }
+    }
     int tile = (id / (8 * nct)) * 8 + (id & 7);
     const int bn0 = ((id >> 3) % nct) * GEMM_BN;
     if (tile >= tiles) return;
     if (ATM || g.lr_rank >= 0) {
-        // low-rank plain rows: a stream, the short tiles -- the slab tiles go first (renumbered to the end of the MFMA form's order)
+        // low-rank plain rows: the short workgroups -- the slab tiles go first (renumbered to the end of the MFMA form's order)
         if (tile >= tiles_slab) {
-            lowrank_tile<false, ListRows, ATM>(g, ListRows{g.rows_main, g.n_main}, tile - tiles_slab, 16 * GEMM_RT, bn0, true, at);
+            // (atmosphere sets: a workgroup streams its share of a tile of plain rows, batch by batch)
+            if constexpr (ATM) lowrank_tile<false, ListRows, true>(g, ListRows{g.rows_main, g.n_main}, tile - tiles_slab, 16 * GEMM_RT, bn0, true, at);
             return;
         }
         tile += tiles_main;
@@ -204,7 +222,12 @@ __device__ __forceinline__ void gemm_live_columns(const GemmArgs& g, double* sA,
     } else {
         const int t2 = tt - ts;
         if (t2 * 16 * RT >= g.L - ns) return;
-        if (ATM || g.lr_rank >= 0) lowrank_tile<false, ColumnRows, ATM>(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, t2, 16 * RT, bn0, false, at);
+        // (the 64-row tiling keeps the batch-at-a-time form: its MFMA tile takes all 128 registers, and with the stream beside it in
+        // one kernel the allocator spilled one of them)
+        if (ATM || (RT == GEMM_RT && g.lr_rank >= 0))
+            lowrank_tile<false, ColumnRows, ATM>(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, t2, 16 * RT, bn0, false, at);
+        else if (g.lr_rank >= 0)
+            lowrank_stream_tile(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, t2, 16 * RT, bn0, sA, (SYM ? 2 : 1) * 16 * RT * A_LD, sB, GEMM_KC * B_LD);
         else gemm_tile<RT, false, DEEP, SYM>(g, sA, sB, nullptr, t2, bn0, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, false);
     }
 }
@@ -213,14 +236,14 @@ __device__ __forceinline__ void gemm_live_columns(const GemmArgs& g, double* sA,
 template <bool SYM>
 __global__ __launch_bounds__(256, SYM ? 4 : GEMM_WPS) void k_jn_gemm_cols(GemmArgs g) {
     publish_live(g);
-    __shared__ double sA[(SYM ? 2 : 1) * 16 * GEMM_RT * A_LD];
-    __shared__ double sB[GEMM_KC * B_LD];
+    __shared__ __attribute__((aligned(16))) double sA[(SYM ? 2 : 1) * 16 * GEMM_RT * A_LD];
+    __shared__ __attribute__((aligned(16))) double sB[GEMM_KC * B_LD];
     gemm_live_columns<GEMM_RT, false, SYM>(g, sA, sB);
 }
 __global__ __launch_bounds__(256, 4) void k_jn_gemm_cols_atm(GemmArgs g, AtmSets at) {
     publish_live(g);
-    __shared__ double sA[2 * 16 * GEMM_RT * A_LD];
-    __shared__ double sB[GEMM_KC * B_LD];
+    __shared__ __attribute__((aligned(16))) double sA[2 * 16 * GEMM_RT * A_LD];
+    __shared__ __attribute__((aligned(16))) double sB[GEMM_KC * B_LD];
     gemm_live_columns<GEMM_RT, false, true, true>(g, sA, sB, at);
 }
 // few live columns: 32-row tiles (more workgroups, so more CUs take part) and deeper staging, since
@@ -233,14 +256,14 @@ constexpr int kTailWpsSym = 4;
 template <bool SYM>
 __global__ __launch_bounds__(256, SYM ? kTailWpsSym : 2) void k_jn_gemm_tail(GemmArgs g) {
     publish_live(g);
-    __shared__ double sA[(SYM ? 2 : 1) * 16 * TAIL_RT * A_LD];
-    __shared__ double sB[GEMM_KC * B_LD];
+    __shared__ __attribute__((aligned(16))) double sA[(SYM ? 2 : 1) * 16 * TAIL_RT * A_LD];
+    __shared__ __attribute__((aligned(16))) double sB[GEMM_KC * B_LD];
     gemm_live_columns<TAIL_RT, SYM ? kTailDeepSym : true, SYM>(g, sA, sB);
 }
 __global__ __launch_bounds__(256, kTailWpsSym) void k_jn_gemm_tail_atm(GemmArgs g, AtmSets at) {
     publish_live(g);
-    __shared__ double sA[2 * 16 * TAIL_RT * A_LD];
-    __shared__ double sB[GEMM_KC * B_LD];
+    __shared__ __attribute__((aligned(16))) double sA[2 * 16 * TAIL_RT * A_LD];
+    __shared__ __attribute__((aligned(16))) double sB[GEMM_KC * B_LD];
     gemm_live_columns<TAIL_RT, kTailDeepSym, true, true>(g, sA, sB, at);
 }
 // the last few columns (at most kTailDeepCols live): a workgroup is alone on its CU and every k-chunk is a trip to L2 or HBM that
@@ -248,14 +271,14 @@ __global__ __launch_bounds__(256, kTailWpsSym) void k_jn_gemm_tail_atm(GemmArgs 
 constexpr int kTailDeepCols = 32;
 __global__ __launch_bounds__(256, 2) void k_jn_gemm_tail_deep(GemmArgs g) {
     publish_live(g);
-    __shared__ double sA[2 * 16 * TAIL_RT * A_LD];
-    __shared__ double sB[GEMM_KC * B_LD];
+    __shared__ __attribute__((aligned(16))) double sA[2 * 16 * TAIL_RT * A_LD];
+    __shared__ __attribute__((aligned(16))) double sB[GEMM_KC * B_LD];
     gemm_live_columns<TAIL_RT, true, true>(g, sA, sB);
 }
 __global__ __launch_bounds__(256, 2) void k_jn_gemm_tail_deep_atm(GemmArgs g, AtmSets at) {
     publish_live(g);
-    __shared__ double sA[2 * 16 * TAIL_RT * A_LD];
-    __shared__ double sB[GEMM_KC * B_LD];
+    __shared__ __attribute__((aligned(16))) double sA[2 * 16 * TAIL_RT * A_LD];
+    __shared__ __attribute__((aligned(16))) double sB[GEMM_KC * B_LD];
     gemm_live_columns<TAIL_RT, true, true, true>(g, sA, sB, at);
 }
 
@@ -346,7 +369,9 @@ __device__ __forceinline__ void jn_gemm_lone(const GemmArgs& g, const AtmSets& a
         } else gemm_tile_lone<true, false>(g, s_lone, tt, bn0, ColumnRows{b * g.L, iu, ns, ns, true}, f0, f1);
     } else {
         if ((tt - ts) * 16 >= g.L - ns) return;
-        if (ATM || g.lr_rank >= 0) lowrank_tile<false, ColumnRows, ATM>(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, tt - ts, 16, bn0, false, at);
+        if (ATM) lowrank_tile<false, ColumnRows, true>(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, tt - ts, 16, bn0, false, at);
+        else if (g.lr_rank >= 0)         // (the factors in the two halves of the tile's 16 rows of D + 2 doubles: 4 D doubles fit each)
+            lowrank_stream_tile(g, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, tt - ts, 16, bn0, s_lone, 8 * (g.D + 2), s_lone + 8 * (g.D + 2), 8 * (g.D + 2));
         else gemm_tile_lone<false, true>(g, s_lone, tt - ts, bn0, ColumnRows{b * g.L, iu, ns, g.L - ns, false}, f0, f1);
     }
 }
@@ -494,12 +519,18 @@ void launch_fold_asymmetry(hipStream_t s, int S, int nblk, int D, int Wld, size_
     hipLaunchKernelGGL(k_fold_asymmetry, dim3((unsigned)nblk, (unsigned)S), dim3(256), 0, s, D, Wld, per, W, out);
 }
 
-void launch_gemm(hipStream_t s, const GemmArgs& a, const AtmSets* at) {
-    const int tiles = (a.n_main + 16 * GEMM_RT - 1) / (16 * GEMM_RT) + (a.n_slab + DENSE_SLAB_ROWS - 1) / DENSE_SLAB_ROWS;
+void launch_gemm(hipStream_t s, const GemmArgs& a_, const AtmSets* at, int cus) {
+    GemmArgs a = a_;
+    const int tiles_slab = (a.n_slab + DENSE_SLAB_ROWS - 1) / DENSE_SLAB_ROWS;
+    const int tiles = (a.n_main + 16 * GEMM_RT - 1) / (16 * GEMM_RT) + tiles_slab;
     if (tiles <= 0) return;
     const int nct = (a.D + GEMM_BN - 1) / GEMM_BN;
     // (+ 1 with a live list: the workgroup that writes it)
     dim3 grid((unsigned)((tiles + 7) / 8 * 8 * nct + (a.live_list ? 1 : 0)));
+    if (!at && a.lr_rank >= 0) {                         // the slab tiles' workgroups, then the stream's (jn_gemm_dense)
+        a.lr_run = lr_stream_run(a.n_main, cus);
+        grid.x = (unsigned)((tiles_slab + 7) / 8 * 8 * nct + (a.n_main + a.lr_run - 1) / a.lr_run + (a.live_list ? 1 : 0));
+    }
     if (at) hipLaunchKernelGGL(k_jn_gemm_atm, grid, dim3(256), (size_t)a.pad_lds, s, a, *at);
     else if (a.sym) hipLaunchKernelGGL(k_jn_gemm<true>, grid, dim3(256), (size_t)a.pad_lds, s, a);
     else hipLaunchKernelGGL(k_jn_gemm<false>, grid, dim3(256), (size_t)a.pad_lds, s, a);

@@ -425,14 +425,66 @@ __device__ __forceinline__ void gemm_tile_lone(const GemmArgs& g, double* sRaw, 
 // -- r dot products of length D and an r-term expansion instead of a D x D product: a stream, 16 D bytes a row.  One wave, one
 // row (LR_ROWS rows at a time, to keep that many rows' bytes in flight and share the loads of U and V).  A lane sums the elements
 // k = 2 lane + 128 j in order of j (one fma chain per moment), a fixed xor butterfly over the 64 lanes gives every lane the same
-// sum, and lane l writes m = 2 l + 128 j, 16 bytes a lane.  Every tiling, the order loop's included, computes its plain rows here,
-// so a row's bits do not depend on the tiling, the batch or the launch.  rows[i] < 0: no row.  COH: the order loop's loads past
+// sum, and lane l writes m = 2 l + 128 j, 16 bytes a lane.  Every tiling, the order loop's included, computes its plain rows with the
+// functions below (batch by batch in lowrank_rows, pipelined in lowrank_stream), so a row's bits do not depend on the tiling, the
+// batch or the launch.  rows[i] < 0: no row.  COH: the order loop's loads past
 // the L1 and write-through stores (gemm_tile, COH).
 constexpr int LR_ROWS = 4;
+// ---- a row's arithmetic, shared by every caller: these three functions ARE a plain row's bits -----------------------------------
+// one k-step of a lane's moment chain: element x, then element y
+__device__ __forceinline__ void lr_accum(double& m, double2 x, double2 u) { m = __builtin_fma(x.y, u.y, __builtin_fma(x.x, u.x, m)); }
+// the xor butterfly over the 64 lanes, s = 32 .. 1 (lane l and lane l ^ s add the same two numbers: every lane ends with the same bits)
+// The exchanges are register moves, not trips through the LDS crossbar (__shfl_xor: two ds_bpermute_b32 a step, 96 for the 8
+// moments of a batch at rank 2 -- 2.3 million a dense launch of the headline): the halves and the rows of 16 lanes are swapped
+// by v_permlane32_swap / v_permlane16_swap (both copies start as m: afterwards one holds the lower, one the upper partner in
+// every lane), the steps inside a row of 16 are DPP moves (row_ror:8; row_shl:4 into lanes 0-3 and 8-11 of a row, row_shr:4
+// into the others; quad_perm).  The partners are those of lane ^ s, and a + b = b + a bit for bit: the sums are __shfl_xor's.
+template <int CTRL, int BANKS = 0xf>
+__device__ __forceinline__ double lr_dpp(double keep, double v) {
+    return __hiloint2double(__builtin_amdgcn_update_dpp(__double2hiint(keep), __double2hiint(v), CTRL, 0xf, BANKS, false),
+                            __builtin_amdgcn_update_dpp(__double2loint(keep), __double2loint(v), CTRL, 0xf, BANKS, false));
+}
+// REG = false: __shfl_xor itself -- the atmosphere-set and order-loop kernels, which nobody has timed with the register form, stay
+// the code they were.
+template <bool REG = true>
+__device__ __forceinline__ void lr_butterfly(double& m) {
+    if constexpr (!REG) {
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) m += __shfl_xor(m, s);
+        return;
+    }
+    {
+        const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(m), __double2loint(m), false, false);
+        const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(m), __double2hiint(m), false, false);
+        m = __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);                      // s = 32
+    }
+    {
+        const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(m), __double2loint(m), false, false);
+        const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(m), __double2hiint(m), false, false);
+        m = __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);                      // s = 16
+    }
+    m += lr_dpp<0x128>(m, m);                                                                     // s = 8: row_ror:8
+    m += lr_dpp<0x114, 0xa>(lr_dpp<0x104, 0x5>(m, m), m);                                         // s = 4: row_shl:4 | row_shr:4
+    m += lr_dpp<0x4e>(m, m);                                                                      // s = 2: quad_perm [2, 3, 0, 1]
+    m += lr_dpp<0xb1>(m, m);                                                                      // s = 1: quad_perm [1, 0, 3, 2]
+}
+// Moment mode (g.mom: the ring transport expands the rows itself): lanes 0 .. 3 write the row's record {M_0 .. M_3, ca, 0, 0, 0},
+// 16 bytes each, through a descriptor of 64 bytes (a missing row: of none), and the row of C is not written.
+__device__ __forceinline__ void lr_store_record(__amdgpu_buffer_rsrc_t rM, int lane, const double (&m)[kLowRankMax], double cf) {
+    const double x = lane == 0 ? m[0] : (lane == 1 ? m[2] : (lane == 2 ? cf : 0.0));
+    const double y = lane == 0 ? m[1] : (lane == 1 ? m[3] : 0.0);
+    bstore2(rM, lane * 16, 0, make_double2(x, y));
+}
+// (the expansion: transport_util.hpp, lr_expand -- shared with the ring transport's moment mode)
+
 // ATM (atmosphere phase sets in use, `at`): a row's factors and rank are those of its column's set (row / L -> column -> set),
 // so the LR_ROWS rows of a wave may read LR_ROWS different U, V and ranks -- all wave-uniform.  A row's sums are formed exactly as
 // without the flag (same elements per lane, same order of j, same butterfly, same order of q in the expansion): a column on set s
 // has the bits of a handle whose W_atm is that set.  A set of rank 0 writes zeros.
+//
+// lowrank_rows is the batch-at-a-time form: LR_ROWS rows from the row ids to the stores, the factors read from memory as they are
+// needed.  The atmosphere sets (ATM), the order loop (COH) and the shapes whose factors do not fit the stream's LDS (lowrank_stream)
+// run it; the launches of a plain handle stream (below), and the tests that compare the two bit for bit check each against the other.
 template <bool COH, bool ATM = false>
 __device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows)[LR_ROWS], int lane, const AtmSets& at = AtmSets()) {
     const int D = g.D, R = g.lr_rank;
@@ -473,42 +525,31 @@ __device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows
             if constexpr (ATM) {
 #pragma unroll
                 for (int i = 0; i < LR_ROWS; ++i)
-                    if (q < Ri[i]) {
-                        const double2 u = *reinterpret_cast<const double2*>(Ui[i] + (size_t)q * D + k);
-                        m[i][q] = __builtin_fma(x[i].y, u.y, __builtin_fma(x[i].x, u.x, m[i][q]));
-                    }
+                    if (q < Ri[i]) lr_accum(m[i][q], x[i], *reinterpret_cast<const double2*>(Ui[i] + (size_t)q * D + k));
             } else if (q < R) {
                 const double2 u = *reinterpret_cast<const double2*>(U + (size_t)q * D + k);
 #pragma unroll
-                for (int i = 0; i < LR_ROWS; ++i) m[i][q] = __builtin_fma(x[i].y, u.y, __builtin_fma(x[i].x, u.x, m[i][q]));
+                for (int i = 0; i < LR_ROWS; ++i) lr_accum(m[i][q], x[i], u);
             }
         }
     }
-    // (lane l and lane l ^ s add the same two numbers: every lane ends with the same bits)
 #pragma unroll
-    for (int s = 32; s >= 1; s >>= 1)
+    for (int q = 0; q < kLowRankMax; ++q) {
+        if constexpr (ATM) {
 #pragma unroll
-        for (int q = 0; q < kLowRankMax; ++q) {
-            if constexpr (ATM) {
+            for (int i = 0; i < LR_ROWS; ++i)
+                if (q < Ri[i]) lr_butterfly<false>(m[i][q]);
+        } else if (q < R) {
 #pragma unroll
-                for (int i = 0; i < LR_ROWS; ++i)
-                    if (q < Ri[i]) m[i][q] += __shfl_xor(m[i][q], s);
-            } else if (q < R) {
-#pragma unroll
-                for (int i = 0; i < LR_ROWS; ++i) m[i][q] += __shfl_xor(m[i][q], s);
-            }
+            for (int i = 0; i < LR_ROWS; ++i) lr_butterfly<!COH>(m[i][q]);
         }
-    // Moment mode (g.mom: the ring transport expands the rows itself): lanes 0 .. 3 write the row's record {M_0 .. M_3, ca, 0, 0, 0},
-    // 16 bytes each, through a descriptor of 64 bytes (a missing row: of none), and the row of C is not written.
+    }
     if constexpr (!COH && !ATM) {
         if (g.mom) {
 #pragma unroll
             for (int i = 0; i < LR_ROWS; ++i) {
                 const int r = rows[i] >= 0 ? rows[i] : rows[0];
-                const __amdgpu_buffer_rsrc_t rM = make_rsrc(g.mom + (size_t)r * kMomDoubles, rows[i] >= 0 ? kMomDoubles * 8 : 0);
-                const double x = lane == 0 ? m[i][0] : (lane == 1 ? m[i][2] : (lane == 2 ? cf[i] : 0.0));
-                const double y = lane == 0 ? m[i][1] : (lane == 1 ? m[i][3] : 0.0);
-                bstore2(rM, lane * 16, 0, make_double2(x, y));
+                lr_store_record(make_rsrc(g.mom + (size_t)r * kMomDoubles, rows[i] >= 0 ? kMomDoubles * 8 : 0), lane, m[i], cf[i]);
             }
             return;
         }
@@ -532,7 +573,6 @@ __device__ __forceinline__ void lowrank_rows(const GemmArgs& g, const int (&rows
 #pragma unroll
             for (int i = 0; i < LR_ROWS; ++i) bstore2_aux<COH ? 17 : 0>(rC[i], k * 8, 0, make_double2(cf[i] * o[i].x, cf[i] * o[i].y));
         } else {
-            // (lr_expand: the expansion shared with the ring transport's moment mode)
             double vx[kLowRankMax], vy[kLowRankMax];
 #pragma unroll
             for (int q = 0; q < kLowRankMax; ++q) {
@@ -575,6 +615,237 @@ __device__ __forceinline__ void lowrank_tile(const GemmArgs& g, RowOf row_of, in
                 if (rows[i] >= 0) { rows[0] = rows[i]; rows[i] = -1; break; }
         lowrank_rows<COH, ATM>(g, rows, lane, at);
     }
+}
+
+// ---- the plain rows of a handle without atmosphere sets, outside the order loop: a STREAM -------------------------------------
+// lowrank_rows is a chain of memory round trips per LR_ROWS rows -- row id, live flag, coefficient, the row, U per moment, V per
+// moment, then the stores -- with nothing else in flight in the wave: some 15 trips for 8 KB.  Here a wave is given a run of up to
+// 64 rows and
+//   1. reads their ids lane-parallel (one load), then live flags and coefficients (a second); the rows it has to compute are the
+//      set bits of a ballot, handed to the batches by readlane -- a converged column's rows and a list's padding cost nothing;
+//   2. finds U and V in LDS, brought there once per workgroup while those two loads travel (the MFMA tiles' staging arrays: a stream
+//      workgroup has no other use for them);
+//   3. requests the rows of batch i + 1 before it reduces and stores batch i: two register sets, loop unrolled by two so that a
+//      set in flight is never copied; every request of the loop is unconditional (a batch past the end reads and writes buffers
+//      of no bytes) so that the compiler counts its waits (vmcnt(n)) instead of draining the queue where two paths meet.
+// A unit of the pipeline is LR_ROWS rows x 256 elements (two k-steps, 2 KB a row): all of a row up to D = 256, a row's chunks in
+// order beyond (WIDE), the moments carried from chunk to chunk.  Same elements per lane, same order, same butterfly, same
+// expansion as lowrank_rows -- the functions above.
+struct LrSet { double2 x[LR_ROWS][2]; };
+struct LrCursor {                    // the wave's rows still to come, the LR_ROWS lanes that hold the current batch's, the chunk
+    unsigned long long todo;
+    int sel[LR_ROWS];
+    int c;
+};
+__device__ __forceinline__ void lr_next_batch(LrCursor& cu) {
+#pragma unroll
+    for (int i = 0; i < LR_ROWS; ++i) {
+        cu.sel[i] = cu.todo ? (int)__builtin_ctzll(cu.todo) : -1;
+        cu.todo &= cu.todo - 1;
+    }
+}
+template <bool WIDE>
+__device__ __forceinline__ void lr_issue(const GemmArgs& g, LrSet& X, LrCursor& cu, int rowv, int lane, int nc) {
+    if (!WIDE || cu.c == 0) lr_next_batch(cu);
+    const int k0 = 2 * lane + (WIDE ? 256 * cu.c : 0);
+    // (the requests stay where they are written: moved up into the batch before, they would need a third register set)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < LR_ROWS; ++i) {
+        const int r = cu.sel[i] >= 0 ? __builtin_amdgcn_readlane(rowv, cu.sel[i]) : -1;
+        const __amdgpu_buffer_rsrc_t rA = make_rsrc(g.A + (size_t)(r >= 0 ? r : 0) * g.D, r >= 0 ? g.D * 8 : 0);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) X.x[i][t] = bload2_aux<0>(rA, (k0 + 128 * t) * 8, 0);      // (past the row's end: zeros, never used)
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (WIDE) cu.c = cu.c + 1 == nc ? 0 : cu.c + 1;
+}
+// valid: false for the pipeline's first call, which has no unit yet (X is not read): it stores to buffers of no bytes.
+// RT: the rank, a constant here (lowrank_stream switches on it once): with a run-time rank the tests q < r sit between the
+// updates of 16 moments, and the compiler kept copies of them on either side of every test -- 148 registers, or spills at 128.
+template <bool WIDE, int RT>
+__device__ __forceinline__ void lr_process(const GemmArgs& g, const LrSet& X, LrCursor& cu, double (&m)[LR_ROWS][RT], int rowv,
+                                           double cfv, int lane_, int nc, const double* sU, const double* sV, bool valid) {
+    const int D = g.D;
+    // (an opaque copy of the lane id: what a batch derives from it -- its LDS addresses -- is a few instructions a batch, and
+    // held in registers across the loop instead it was what spilled at rank 4)
+    int lane = lane_;
+    asm volatile("" : "+v"(lane));
+    if (valid && (!WIDE || cu.c == 0)) lr_next_batch(cu);
+    if (!WIDE || (valid && cu.c == 0)) {
+#pragma unroll
+        for (int i = 0; i < LR_ROWS; ++i)
+#pragma unroll
+            for (int q = 0; q < RT; ++q) m[i][q] = 0.0;
+    }
+    const int k0 = 2 * lane + (WIDE ? 256 * cu.c : 0);
+    if (valid) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            // (a lane past the row's end: x = +0.0 from the buffer's bounds and u = -0.0 here, so the product is -0.0 and
+            // fma(x, u, m) = m for EVERY m, -0.0 and NaN included -- where lowrank_rows leaves the lane out)
+            const int k = k0 + 128 * t;
+            const bool in = k < D;
+#pragma unroll
+            for (int q = 0; q < RT; ++q) {
+                double2 u = *reinterpret_cast<const double2*>(sU + q * D + (in ? k : 0));
+                u.x = in ? u.x : -0.0; u.y = in ? u.y : -0.0;
+#pragma unroll
+                for (int i = 0; i < LR_ROWS; ++i) lr_accum(m[i][q], X.x[i][t], u);
+            }
+        }
+    }
+    const bool last = valid && (!WIDE || cu.c + 1 == nc);
+    if (WIDE && valid) cu.c = last ? 0 : cu.c + 1;
+    if (last) {
+#pragma unroll
+        for (int q = 0; q < RT; ++q) {
+#pragma unroll
+            for (int i = 0; i < LR_ROWS; ++i) lr_butterfly(m[i][q]);
+            if (RT > 2) __builtin_amdgcn_sched_barrier(0);       // (a moment's four chains at a time: all sixteen at once need more registers than there are)
+        }
+    }
+    // (not the last chunk of a row: the stores below go to buffers of no bytes -- see 3. above)
+    int row[LR_ROWS];
+    double cf[LR_ROWS];
+#pragma unroll
+    for (int i = 0; i < LR_ROWS; ++i) {
+        const bool have = last && cu.sel[i] >= 0;
+        const int l = have ? cu.sel[i] : 0;
+        row[i] = have ? __builtin_amdgcn_readlane(rowv, l) : -1;
+        cf[i] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(cfv), l), __builtin_amdgcn_readlane(__double2loint(cfv), l));
+    }
+    if (g.mom) {
+#pragma unroll
+        for (int i = 0; i < LR_ROWS; ++i) {
+            const double M[kLowRankMax] = {m[i][0], RT > 1 ? m[i][RT > 1 ? 1 : 0] : 0.0, RT > 2 ? m[i][RT > 2 ? 2 : 0] : 0.0,
+                                           RT > 3 ? m[i][RT > 3 ? 3 : 0] : 0.0};
+            lr_store_record(make_rsrc(g.mom + (size_t)(row[i] >= 0 ? row[i] : 0) * kMomDoubles, row[i] >= 0 ? kMomDoubles * 8 : 0), lane,
+                            M, cf[i]);
+        }
+        return;
+    }
+    if (WIDE && !last) return;                           // (the rows of Jn: several stores a row, only once the row is whole)
+    __amdgpu_buffer_rsrc_t rC[LR_ROWS];
+#pragma unroll
+    for (int i = 0; i < LR_ROWS; ++i) rC[i] = make_rsrc(g.C + (size_t)(row[i] >= 0 ? row[i] : 0) * D, row[i] >= 0 ? D * 8 : 0);
+#pragma unroll 2
+    for (int k = 2 * lane; k < D; k += 128) {
+        double vx[kLowRankMax], vy[kLowRankMax];
+#pragma unroll
+        for (int q = 0; q < kLowRankMax; ++q) {
+            vx[q] = 0.0; vy[q] = 0.0;
+            if (q < RT) {
+                const double2 v = *reinterpret_cast<const double2*>(sV + q * D + k);
+                vx[q] = v.x; vy[q] = v.y;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < LR_ROWS; ++i) {
+            const double M[kLowRankMax] = {m[i][0], RT > 1 ? m[i][RT > 1 ? 1 : 0] : 0.0, RT > 2 ? m[i][RT > 2 ? 2 : 0] : 0.0,
+                                           RT > 3 ? m[i][RT > 3 ? 3 : 0] : 0.0};
+            bstore2_aux<0>(rC[i], k * 8, 0, make_double2(lr_expand(M, vx, RT, cf[i]), lr_expand(M, vy, RT, cf[i])));
+        }
+    }
+}
+// PIPE = false: one unit at a time in one register set -- the live-column tilings, whose waves have a batch or two each (their
+// launches are a few workgroups' latency, and what they gain is the two trips to their rows and the factors in LDS)
+template <bool WIDE, int RT, bool PIPE>
+__device__ __forceinline__ void lr_pipeline(const GemmArgs& g, unsigned long long todo, int rowv, double cfv, int lane,
+                                            const double* sU, const double* sV) {
+    const int nc = WIDE ? (g.D + 255) / 256 : 1;
+    const int nu = ((__popcll(todo) + LR_ROWS - 1) / LR_ROWS) * nc;
+    LrCursor ci{todo, {-1, -1, -1, -1}, 0}, cp = ci;
+    if constexpr (!PIPE) {
+        LrSet X;
+        double m1[LR_ROWS][RT];
+        for (int u = 0; u < nu; ++u) {
+            lr_issue<WIDE>(g, X, ci, rowv, lane, nc);
+            lr_process<WIDE, RT>(g, X, cp, m1, rowv, cfv, lane, nc, sU, sV, true);
+        }
+        return;
+    }
+    // (every register set is requested at ONE place of the loop: a set requested in a prologue as well is a second definition,
+    // and the allocator copied the set in flight between the two -- a full wait; hence the first, empty, lr_process)
+    LrSet X0, X1;
+    double m[LR_ROWS][RT];
+    for (int u = 0; u <= nu; u += 2) {
+        lr_issue<WIDE>(g, X0, ci, rowv, lane, nc);
+        lr_process<WIDE, RT>(g, X1, cp, m, rowv, cfv, lane, nc, sU, sV, u > 0);
+        lr_issue<WIDE>(g, X1, ci, rowv, lane, nc);
+        lr_process<WIDE, RT>(g, X0, cp, m, rowv, cfv, lane, nc, sU, sV, true);
+    }
+}
+template <int RT, bool PIPE>
+__device__ __forceinline__ void lr_pipeline_width(const GemmArgs& g, unsigned long long todo, int rowv, double cfv, int lane,
+                                                  const double* sU, const double* sV) {
+    if (g.D <= 256) lr_pipeline<false, RT, PIPE>(g, todo, rowv, cfv, lane, sU, sV);
+    else lr_pipeline<true, RT, PIPE>(g, todo, rowv, cfv, lane, sU, sV);
+}
+// row of the wave's i-th entry: entry first + stride i of a row list or of a column's rows
+template <class RowOf> struct LrRun {
+    RowOf row_of;
+    int first, stride;
+    __device__ int operator()(int i) const { return row_of(first + stride * i); }
+};
+// The wave's n rows (n <= 64, the same for every lane; a wave of no rows still comes here: the barrier is the workgroup's).
+// sU / sV: LDS for capU / capV doubles.  Factors that do not fit (r D doubles each; V only where rows of Jn are written) stay in
+// memory and the rows go LR_ROWS at a time through lowrank_rows -- still from ids, flags and coefficients read in two trips.
+template <bool PIPE, class RowAt>
+__device__ __forceinline__ void lowrank_stream(const GemmArgs& g, RowAt row_at, int n, bool check_active, double* sU, int capU,
+                                               double* sV, int capV) {
+    // (an opaque copy of the thread id: nothing of the stream is shared with, or held in registers for, the MFMA tiles that the
+    // same kernel holds for other workgroups -- the largest of them has no register to spare)
+    int tid_ = threadIdx.x;
+    asm volatile("" : "+v"(tid_));
+    const int tid = tid_, lane = tid & 63;
+    const int D = g.D, R = g.lr_rank;
+    const bool chk = check_active && g.active && g.check_tiles;
+    const bool lds = R > 0 && R * D <= capU && (g.mom || R * D <= capV);     // (uniform over the launch; rank 0: rows of zeros)
+    int rowv = lane < n ? row_at(lane) : -1;
+    if (lds) {
+        const int n2 = R * D / 2;                        // (D = 2 N: even)
+        for (int e = tid; e < n2; e += 256) {
+            reinterpret_cast<double2*>(sU)[e] = reinterpret_cast<const double2*>(g.lrU)[e];
+            if (!g.mom) reinterpret_cast<double2*>(sV)[e] = reinterpret_cast<const double2*>(g.lrV)[e];
+        }
+    }
+    int live = 1;
+    double cfv = 0.0;
+    if (rowv >= 0) {
+        if (chk) live = g.active[rowv / g.L];
+        cfv = g.ca[rowv];
+    }
+    const unsigned long long todo = __ballot(rowv >= 0 && live != 0);
+    if (lds) {
+        __syncthreads();
+        switch (R) {
+            case 1: lr_pipeline_width<1, PIPE>(g, todo, rowv, cfv, lane, sU, sV); break;
+            case 2: lr_pipeline_width<2, PIPE>(g, todo, rowv, cfv, lane, sU, sV); break;
+            case 3: lr_pipeline_width<3, PIPE>(g, todo, rowv, cfv, lane, sU, sV); break;
+            default: lr_pipeline_width<4, PIPE>(g, todo, rowv, cfv, lane, sU, sV); break;
+        }
+        return;
+    }
+    LrCursor cu{todo, {-1, -1, -1, -1}, 0};
+    while (cu.todo) {
+        lr_next_batch(cu);
+        int rows[LR_ROWS];
+#pragma unroll
+        for (int i = 0; i < LR_ROWS; ++i) rows[i] = cu.sel[i] >= 0 ? __builtin_amdgcn_readlane(rowv, cu.sel[i]) : -1;
+        lowrank_rows<false, false>(g, rows, lane);
+    }
+}
+// The stream over a tile's plain rows, for the live-column tilings: the workgroup of column tile ct (of nct) takes the rows
+// lr = ct + nct j of the tile (lowrank_tile's share), its waves a quarter of them each.
+template <class RowOf>
+__device__ __forceinline__ void lowrank_stream_tile(const GemmArgs& g, RowOf row_of, int tile, int BM, int bn0, double* sU, int capU,
+                                                    double* sV, int capV) {
+    const int nct = (g.D + GEMM_BN - 1) / GEMM_BN, ct = bn0 / GEMM_BN;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x) >> 6;
+    const int per = (BM - ct + nct - 1) / nct;           // rows of this workgroup (BM <= 64)
+    const int rw = (per + 4 * LR_ROWS - 1) / (4 * LR_ROWS) * LR_ROWS;
+    lowrank_stream<false>(g, LrRun<RowOf>{row_of, tile * BM + ct + nct * wave * rw, nct}, min(max(per - wave * rw, 0), rw), false, sU, capU, sV, capV);
 }
 
 constexpr int TAIL_RT_SLAB = 1;     // MFMA row tiles of the live-column tilings: slab rows (16-row tiles)

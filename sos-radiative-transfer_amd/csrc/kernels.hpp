@@ -227,6 +227,8 @@ struct GemmArgs {
     // writes a row's record and NOT its row of C (the ring transport expands the record itself, transport_util.hpp: lr_expand).
     // Null: rows of C, as always.  Never set for the order loop's contraction role or with atmosphere sets.
     double* mom = nullptr;
+    // dense launch, low-rank plain rows without atmosphere sets: rows of the plain list a stream workgroup takes (launch_gemm sets it)
+    int lr_run = 0;
 };
 // Atmosphere phase sets in use (sosrt_set_atmosphere_sets): a plain row takes the factors of its column's set.  The launches
 // that read this are kernels of their own (jn_gemm.hip, *_atm) with this as a second argument, and GemmArgs::lrU / lrV are then
@@ -236,6 +238,18 @@ struct AtmSets {
     const int* lr_ranks = nullptr;   // [sets] rank of a set's factors (0 .. kLowRankMax)
 };
 constexpr int kLowRankMax = 4;
+// The dense launch's stream of low-rank plain rows (jn_gemm_tile.hpp, lowrank_stream): a workgroup takes a run of the plain list
+// long enough for a software pipeline over its waves' batches of 4 rows -- the list dealt over kLrStreamRounds rounds of the
+// launch's resident workgroups (four to a CU), in whole batches per wave, at most 64 rows a wave (its lanes hold the row ids).
+#ifndef SOSRT_LR_STREAM_ROUNDS
+#define SOSRT_LR_STREAM_ROUNDS 2
+#endif
+constexpr int kLrStreamRounds = SOSRT_LR_STREAM_ROUNDS;
+inline int lr_stream_run(int n_main, int cus) {
+    const long long wgs = (long long)(cus > 0 ? cus : 256) * 4 * kLrStreamRounds;
+    const long long run = ((n_main + wgs - 1) / wgs + 15) / 16 * 16;
+    return (int)(run < 16 ? 16 : (run > 256 ? 256 : run));
+}
 constexpr int kMomDoubles = 8;     // a moment record: 64 bytes, 64-byte aligned
 
 // (publish_live_now: by the calling thread, whichever workgroup it belongs to)
@@ -261,7 +275,7 @@ struct PerDeviceOnce {
         return true;
     }
 };
-void launch_gemm(hipStream_t s, const GemmArgs& a, const AtmSets* at = nullptr);
+void launch_gemm(hipStream_t s, const GemmArgs& a, const AtmSets* at = nullptr, int cus = 0 /* CUs of the device: sizes the stream's runs */);
 struct OrderLoopArgs {
     TransportArgs t;           // the column group's view (every per-column pointer offset to its first column): g, tau, Jn, I, desc, cv, Etab, erep, scan_scratch, scan_sync
     GemmArgs gm;               // the batch's view (whole-batch pointers, global column ids): folded matrices, Wmix, mix_group, idx_up / idx_down, ca / cr, C = Jn

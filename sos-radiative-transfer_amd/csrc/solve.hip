@@ -162,7 +162,7 @@ void run_source(sosrt_handle* h, const double* In_1, double* Jn, const int* acti
         ga.live_list = h->gemm.d_livelist + col0; ga.live_cap = live_tiles ? o.tail_cols : o.dense_live_cap;
     }
     if (live_tiles) launch_gemm_tail(s, ga, o.tail_cols, o.tail_cols <= h->gemm.gemm_small_cols, o.regs_tile, atp);
-    else launch_gemm(s, ga, atp);
+    else launch_gemm(s, ga, atp, h->cu_count);
     prof_end(h, SOSRT_K_GEMM, pg);
 }
 
