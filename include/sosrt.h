@@ -508,6 +508,56 @@ int sosrt_phase_p0_rows_azimuth_dev(sosrt_t* h, int B, int kind, double g, const
 int sosrt_view_azimuth_accumulate_dev(sosrt_t* h, int B, int m, int nlev, int V2, const double* d_val /*[B][nlev][V2]*/,
                                       int nphi_out, const double* d_phi /*[nphi_out]*/, double* d_out /*[B][nlev][V2][nphi_out]*/);
 
+/* ---- pseudo-spherical direct beam: the slant path of the beam, first order and flux terms on it ---------
+ * Every solve attenuates the direct solar beam as exp(-tau / mu0), the plane-parallel secant law; at low sun that is the largest
+ * physical error of the path (at mu0 = 0.21 the converged field of the EVA column moves by 6.7 % of its maximum).  In the
+ * pseudo-spherical approximation the beam is attenuated along its slant path through spherical shells and everything scattered is
+ * transported plane-parallel as before: the first order changes, the order loop does not -- the solve is
+ * sosrt_solve_dev(.., d_I1_in = d_I1, ..) with the first order of this stage.  Detected by symbol; SOSRT_VERSION is unchanged.
+ * All three are enqueued on the handle's stream, read the columns of the last sosrt_set_columns / sosrt_set_columns_zones
+ * (mu0, grd_alb, albedos, steps, tauStar_tot, zone table) and write nothing but their outputs: the handle's columns, resident
+ * field, order targets and phase state are as they were.  1 <= B <= the current columns (the first B of them).
+ *
+ * sosrt_beam_slant_dev: levels t = 0..L-1 at altitudes d_z [L] (km, finite, strictly descending, shared by the batch -- the
+ * np.linspace(z0, 0, L) of spec:39), r_t = earth_radius_km + z_t, p^2 = r_t^2 (1 - mu0^2):
+ *     sigma_0 = 0,  sigma_t = sum_{k=1..t} (tau_k - tau_{k-1}) c_{t,k},
+ *     c_{t,k} = (r_{k-1} + r_k) / (sqrt(r_{k-1}^2 - p^2) + sqrt(r_k^2 - p^2))
+ * (the path through shell k over its thickness; 1 at mu0 = 1, -> 1 / mu0 as the radius grows, so sigma -> tau / mu0).
+ * d_mu0 [B] or NULL for the columns' own mu0; a caller's must be finite and in (0, 1].  d_sigma_out [B][L].  An O(L^2) sum per
+ * column.  The call reads d_z (and a caller's d_mu0) back to check them: it waits for the stream's earlier work.
+ *
+ * sosrt_first_order_beam_dev: the first order layer by layer on a beam path d_sigma [B][L] THAT IS AN INPUT (sigma = tau / mu0
+ * gives the coded first order, SOSRT_FIRST_ORDER_CODED, to rounding: how the kernel is pinned).  With F0 = pi / mu0, T =
+ * tauStar_tot, R = F0 rho exp(-sigma_{L-1} - (T - tau_{L-1}) / mu0), q[m] of spec:149 per zone, a = |mu_m|, Delta the optical
+ * thickness of a layer, E = exp(-Delta / a), s = (slant thickness of the layer) / Delta, phi(y) = (1 - exp(-y)) / y:
+ *     downward  D_0 = 0,  D_t = D_{t-1} E + q_t F0 exp(-sigma_t) (Delta / a) phi((1 / a - s) Delta)
+ *                               + [t is not the first row of a zone below the top one] q_t[mirror] R exp(-(T - tau_t) / mu0) (Delta / a) phi((1 / a + 1 / mu0) Delta)
+ *     surface   U_{L-1} = rho D_{L-1}[mirror]
+ *     upward    U_t = U_{t+1} E + q_t F0 exp(-sigma_t) (Delta / a) phi((1 / a + s) Delta)
+ *                               + [t is not the last row of a zone above the bottom one] q_t[mirror] R exp(-(T - tau_t) / mu0) (Delta / a) phi((1 / a - 1 / mu0) Delta)
+ *     mu = 0    q_t F0 exp(-sigma_t) + q_t[mirror] R exp(-(T - tau_t) / mu0)
+ * (layer (t-1, t) of the downward sweep takes the q of row t, layer (t, t+1) of the upward sweep the q of row t; the two
+ * exclusions are the reference's own level choices; the reflected beam travels upward plane-parallel at mu0).  phi is
+ * exact at y = 0, so the |mu -+ mu0| < 1e-4 limit branches of spec:111,204 have no counterpart: on such a lane the result is up to
+ * 1e-4 of the maximum away from the coded first order.  d_P0_atm [B][2N]; d_P0_aer [B][2N], or [B][nzmax][2N] after
+ * sosrt_set_aerosol_sets with nzmax > 1; d_I1_out [B][L][2N].  A layer is assumed thinner than 700 mu0 (exp(Delta / mu0) finite).
+ *
+ * sosrt_epilogue_beam_dev: sosrt_epilogue_dev with the beam terms of the fluxes on the path d_sigma [B][L]: downward
+ * -fb exp(-sigma_t), upward +fb rho exp(-sigma_{L-1}) exp(-(tau_{L-1} - tau_t) / mu0) (fb: F0 / (4 pi) or F0 by beam_norm); with
+ * sigma = tau / mu0 it is sosrt_epilogue_dev to rounding.  Outputs nullable as there.
+ *
+ * Refused with SOSRT_E_INVALID, a message and nothing written: the single-slab geometry; SOSRT_FIRST_ORDER_README; B outside
+ * 1..the current columns; a null pointer (the nullable outputs of the epilogue aside); z not finite or not strictly descending;
+ * earth_radius_km not finite or <= 0; L > 2048.  Open: refraction, a spherical path of the reflected beam or of the scattered
+ * light, the README first order on a slant path. */
+int sosrt_beam_slant_dev(sosrt_t* h, int B, const double* d_tau /*[B][L]*/, const double* d_z /*[L]*/, double earth_radius_km,
+                         const double* d_mu0 /*[B], nullable: the columns' own*/, double* d_sigma_out /*[B][L]*/);
+int sosrt_first_order_beam_dev(sosrt_t* h, int B, const double* d_tau /*[B][L]*/, const double* d_sigma /*[B][L]*/,
+                               const double* d_P0_atm, const double* d_P0_aer, double* d_I1_out /*[B][L][2N]*/);
+int sosrt_epilogue_beam_dev(sosrt_t* h, int B, const double* d_tau, const double* d_I, int beam_norm, const double* d_z_profile,
+                            double* d_flux_down, double* d_flux_up, double* d_diffusivity, double* d_heating_rate,
+                            double* d_net_toa, const double* d_sigma /*[B][L]*/);
+
 /* ---- multi-GPU: one process per GPU, columns sharded, ONE collective at the end ------------------
  * Nothing in SOS_Aer_main_specular.py:104-458 couples columns, so the order loop never communicates; these entry
  * points only assemble the results of the ranks on `root` over RCCL (xGMI inside a node).  RCCL is bound at run time

@@ -93,6 +93,9 @@ SIGNATURES = {
     "sosrt_phase_p0_rows_modes_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_phase_p0_rows_azimuth_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_view_azimuth_accumulate_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "sosrt_beam_slant_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
+    "sosrt_first_order_beam_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 5),
+    "sosrt_epilogue_beam_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 7),
     "sosrt_comm_unique_id": (c_int, [c_void_p]),
     "sosrt_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "sosrt_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

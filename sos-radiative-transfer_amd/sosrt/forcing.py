@@ -21,12 +21,15 @@ import numpy as np
 
 from . import _lib
 from .inputs import direction_grid, phase_function, slab_indices, tau_profile
-from .main import get_solver
+from .main import EARTH_RADIUS_KM, _beam_args, get_solver, solve_spherical
 
 
 def _net_flux_columns(tau, idx_up, idx_down, mu, mu0, grd_alb, alb_atm, alb_aer, dtau_atm, dtau_aer, tauStar_tot, P_atm, P_aer,
-                      P0_atm, P0_aer, max_orders=256, device=0):
-    """TOA net flux (crit:382) of B columns on their grids tau [B, L]; per-column arrays or scalars otherwise."""
+                      P0_atm, P0_aer, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, z0=120):
+    """TOA net flux (crit:382) of B columns on their grids tau [B, L]; per-column arrays or scalars otherwise.
+    beam='spherical': the pseudo-spherical direct beam (main.solve_spherical) on the altitudes np.linspace(z0, 0, L), and the
+    flux's beam terms on the same slant path (the beam epilogue)."""
+    spherical = _beam_args(beam, earth_radius)
     tau = np.atleast_2d(np.asarray(tau, dtype=np.float64))
     B, L = tau.shape
     N = len(mu) // 2
@@ -38,12 +41,16 @@ def _net_flux_columns(tau, idx_up, idx_down, mu, mu0, grd_alb, alb_atm, alb_aer,
     s.set_columns(np.full(B, idx_up), np.full(B, idx_down), mu0, grd_alb, alb_atm, alb_aer, dtau_atm, dtau_aer, tauStar_tot)
     P0a = np.ascontiguousarray(np.broadcast_to(np.asarray(P0_atm, dtype=np.float64), (B, 2 * N)))
     P0r = np.ascontiguousarray(np.broadcast_to(np.asarray(P0_aer, dtype=np.float64), (B, 2 * N)))
-    r = s.solve(tau, P0a, P0r, fetch_field=False)
+    if spherical:
+        r, _, epi = solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, L), earth_radius, device=device, fetch_field=False,
+                                    want=("net_toa",))
+    else:
+        r = s.solve(tau, P0a, P0r, fetch_field=False)
     if np.any(r.status == _lib.COL_INDEXERROR):       # what the reference raises (spec:404)
         raise IndexError("index %d is out of bounds for axis 1 with size %d" % (2 * N, 2 * N))
     if np.any(r.status != 0):
         raise RuntimeError("columns did not converge within %d orders: status %s" % (max_orders, r.status))
-    return s.epilogue(want=("net_toa",))["net_toa"]
+    return epi["net_toa"] if spherical else s.epilogue(want=("net_toa",))["net_toa"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -93,7 +100,8 @@ def SOS_Aer_critical_albedo(tauStar_aer, dtau_aer, tauStar_atm, dtau_atm, P_aer,
 # ---------------------------------------------------------------------------------------------
 # batched over (tauStar_aer, alb_aer)
 # ---------------------------------------------------------------------------------------------
-def _solve_fluxes(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, geom, phases, max_orders, device):
+def _solve_fluxes(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, geom, phases, max_orders, device, beam="plane",
+                  earth_radius=EARTH_RADIUS_KM):
     """TOA net flux (crit:382) of B columns; arrays of length B for tauStar_aer and alb_aer."""
     z0, z_up, z_down, L, N = geom
     P0_atm, P_atm, P0_aer, P_aer = phases
@@ -101,21 +109,26 @@ def _solve_fluxes(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, geom
     tau = np.stack([tau_profile(tauStar_atm, t, z0, z_up, z_down, L) for t in tauStar_aer])
     ta = np.asarray(tauStar_aer, dtype=np.float64)
     return _net_flux_columns(tau, iu, idn, direction_grid(N), mu0, grd_alb, alb_atm, alb_aer, tauStar_atm / L,
-                             ta / (idn + 1 - iu), tauStar_atm + ta, P_atm, P_aer, P0_atm, P0_aer, max_orders, device)
+                             ta / (idn + 1 - iu), tauStar_atm + ta, P_atm, P_aer, P0_atm, P0_aer, max_orders, device, beam, earth_radius,
+                             z0)
 
 
 def toa_net_flux(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, z0=120, z_up=25, z_down=17, nb_layers=200,
                  nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, phases=None,
-                 max_orders=256, device=0):
+                 max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM):
     """Net flux at the top of the atmosphere, -F_down[0] - F_up[0] (crit:377-382), for arrays of
-    (tauStar_aer, alb_aer)."""
+    (tauStar_aer, alb_aer).  beam='spherical' (with `earth_radius`, km): the direct beam on its slant path through spherical
+    shells, in the solve and in the flux's beam terms (main.SOS_Aer_batch); `radiative_forcing` and `critical_albedo` pass
+    both keywords on."""
+    _beam_args(beam, earth_radius)
     ta, wa = np.broadcast_arrays(np.atleast_1d(np.asarray(tauStar_aer, dtype=float)), np.atleast_1d(np.asarray(alb_aer, dtype=float)))
     if phases is None:
         mu = direction_grid(nb_angles)
         P0a, Pa = phase_function(atm_phase_fun, nb_angles, mu, mu0, g_atm)
         P0r, Pr = phase_function(aer_phase_fun, nb_angles, mu, mu0, g_aer)
         phases = (P0a, Pa, P0r, Pr)
-    return _solve_fluxes(mu0, tauStar_atm, ta, grd_alb, alb_atm, wa, (z0, z_up, z_down, nb_layers, nb_angles), phases, max_orders, device)
+    return _solve_fluxes(mu0, tauStar_atm, ta, grd_alb, alb_atm, wa, (z0, z_up, z_down, nb_layers, nb_angles), phases, max_orders, device,
+                         beam, earth_radius)
 
 
 def radiative_forcing(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, baseline="no_aerosol", **kw):

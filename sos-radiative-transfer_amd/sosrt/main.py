@@ -37,6 +37,7 @@ class ColumnResult:
     idx_up: int
     idx_down: int
     status: int
+    beam_slant: Optional[np.ndarray] = None   # [L] (beam='spherical'): slant optical depth of the direct beam at every level
 
 
 @dataclass
@@ -59,6 +60,7 @@ class BatchResult:
     I_view_azimuth_first: Optional[np.ndarray] = None      # its first order: exact at (lane, azimuth), or the sum of the modes'
     I_view_azimuth_scattered: Optional[np.ndarray] = None  # the synthesis of the per-mode transports of the fields' sources
     view_mode_status: Optional[np.ndarray] = None          # [M + 1, B] status of the solve of every Fourier mode (row 0 is `status`)
+    beam_slant: Optional[np.ndarray] = None   # [B, L] (beam='spherical'): slant optical depth of the direct beam at every level
 
 
 _solvers = {}
@@ -101,6 +103,103 @@ def device_phase(s: Solver, name, mu0, g=0.0, mie=None, matrix=True):
     return P0, (s.phase_matrix(kind, g) if matrix else None)
 
 
+EARTH_RADIUS_KM = 6371.0
+
+
+def _beam_args(beam, earth_radius, azimuths=None, view_mu=None, view_azimuths=None, mode_batch=False, mode_chunk=None,
+               first_order="coded", devices=None):
+    """Checks of the `beam` keyword, made before any handle exists: True for the pseudo-spherical beam.  The stages it refuses
+    compute first orders of their own, and those are plane closed forms."""
+    if not isinstance(beam, str) or beam not in ("plane", "spherical"):
+        raise ValueError("beam must be 'plane' or 'spherical' (got %r)" % (beam,))
+    if beam == "plane":
+        return False
+    try:
+        er = float(earth_radius)
+    except (TypeError, ValueError):
+        raise ValueError("earth_radius must be a number of kilometres (got %r)" % (earth_radius,)) from None
+    if not (np.isfinite(er) and er > 0):
+        raise ValueError("earth_radius must be finite and > 0 km (got %r)" % (earth_radius,))
+    if azimuths is not None or mode_batch or mode_chunk is not None:
+        raise ValueError("beam='spherical' is not available with azimuths / mode_batch: the first order of a Fourier mode m >= 1 is "
+                         "the plane closed form")
+    if view_mu is not None or view_azimuths is not None:
+        raise ValueError("beam='spherical' is not available with view_mu / view_azimuths: the first order at a view cosine is the "
+                         "plane closed form")
+    if first_order != "coded":
+        raise ValueError("beam='spherical' is not available with first_order='readme': the isotropically reflected beam of the "
+                         "README's first order has no slant form")
+    if devices is not None and len(devices) > 1:
+        raise ValueError("beam='spherical' is not available with devices=[...]: solve each shard with SOS_Aer_batch(device=...)")
+    return True
+
+
+def solve_spherical(s: Solver, tau, P0a, P0r, z, earth_radius=EARTH_RADIUS_KM, tol=1e-4, save_orders=False, device=0,
+                    fetch_field=True, want=(), z_profile=None, keep_device=False):
+    """The solve of handle `s` (grid, phase matrices and columns set) with the PSEUDO-SPHERICAL DIRECT BEAM:
+    the beam's slant optical depth through spherical shells at the altitudes `z` [L] (km, descending), the first order layer
+    by layer on that path, then the order loop as it is, fed that first order (`Solver.beam_slant_device`,
+    `first_order_beam_device`, `solve_device(d_I1=...)`).  `want`: names of `Solver.epilogue` to compute from the resident
+    field with the beam terms on the slant path (`z_profile` for the heating rate).  Returns (SolveResult, sigma [B, L],
+    dict of the wanted epilogue arrays); keep_device=True: the torch tensors {"I", "n", "status", "tau", "beam_slant"}
+    instead, left on the device.  The handle goes back to its own stream and to its default per-order storage, also on error."""
+    import torch
+    from .solver import SolveResult
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    B, L = tau.shape
+    D = s.D
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        try:
+            up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)    # (a copy: broadcast inputs are read-only)
+            d_tau, d_z, d_P0a, d_P0r = up(tau), up(z), up(P0a), up(P0r)
+            d_sig = torch.empty((B, L), dtype=torch.float64, device=dev)
+            d_I1 = torch.empty((B, L, D), dtype=torch.float64, device=dev)
+            d_I = torch.empty((B, L, D), dtype=torch.float64, device=dev)
+            d_n = torch.zeros(B, dtype=torch.int32, device=dev)
+            d_st = torch.zeros(B, dtype=torch.int32, device=dev)
+            s.beam_slant_device(d_tau.data_ptr(), d_z.data_ptr(), d_sig.data_ptr(), earth_radius, B=B)
+            s.first_order_beam_device(d_tau.data_ptr(), d_sig.data_ptr(), d_P0a.data_ptr(), d_P0r.data_ptr(), d_I1.data_ptr(), B=B)
+            s.solve_device(d_tau.data_ptr(), d_P0a.data_ptr(), d_P0r.data_ptr(), d_I.data_ptr(), tol=tol, d_I1=d_I1.data_ptr(),
+                           d_n_orders=d_n.data_ptr(), d_status=d_st.data_ptr())
+            d_sv = None
+            if save_orders:
+                # (as Solver.solve: the first pass gives n, the second stores exactly max(n) orders per column)
+                s.synchronize()
+                slots = int(max(1, d_n.max().item()))
+                s.set_saved_orders(slots)
+                d_sv = torch.zeros((B, slots, L, D), dtype=torch.float64, device=dev)
+                s.solve_device(d_tau.data_ptr(), d_P0a.data_ptr(), d_P0r.data_ptr(), d_I.data_ptr(), tol=tol, d_I1=d_I1.data_ptr(),
+                               d_I_saved=d_sv.data_ptr(), d_n_orders=d_n.data_ptr(), d_status=d_st.data_ptr())
+            epi = {}
+            want = [k for k in ("flux_down", "flux_up", "diffusivity", "heating_rate", "net_toa")
+                    if k in set(want) and not (k == "heating_rate" and z_profile is None)]
+            if want:
+                d_zp = None if z_profile is None else up(z_profile)
+                d_out = {k: torch.empty((B,) if k == "net_toa" else (B, L), dtype=torch.float64, device=dev) for k in want}
+                ptr = lambda k: d_out[k].data_ptr() if k in d_out else 0
+                s.epilogue_beam_device(d_tau.data_ptr(), d_I.data_ptr(), d_sig.data_ptr(), 0 if d_zp is None else d_zp.data_ptr(),
+                                       "crit", ptr("flux_down"), ptr("flux_up"), ptr("diffusivity"), ptr("heating_rate"),
+                                       ptr("net_toa"), B=B)
+                s.synchronize()
+                epi = {k: v.cpu().numpy() for k, v in d_out.items()}
+            s.synchronize()
+            if keep_device:
+                return {"I": d_I, "n": d_n, "status": d_st, "tau": d_tau, "beam_slant": d_sig}
+            r = SolveResult(I=d_I.cpu().numpy() if fetch_field else None, n=d_n.cpu().numpy(), status=d_st.cpu().numpy(),
+                            I_saved=None if d_sv is None else d_sv.cpu().numpy())
+            return r, d_sig.cpu().numpy(), epi
+        finally:
+            # the solver is cached and goes back to its own stream: drain this one first
+            try:
+                s.synchronize()
+            finally:
+                if save_orders:
+                    s.set_saved_orders(None)
+                s.set_stream(None)
+
+
 def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, alb_aer=1.0, z0=120, z_up=25, z_down=17,
                   nb_layers=200, nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7,
                   mie_atm=None, mie_aer=None,
@@ -108,7 +207,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   save_orders=False, device=0, devices=None, raise_on_error=True, first_order="coded", azimuths=None,
                   n_modes=None, nphi_modes=None, levels=(0, -1), aer_set=None, mode_batch=False, mode_chunk=None,
                   view_mu=None, view_levels=(0, -1), view_quadrature="grid", view_azimuths=None,
-                  view_first_order="exact") -> BatchResult:
+                  view_first_order="exact", beam="plane", earth_radius=EARTH_RADIUS_KM) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -160,7 +259,16 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     with an upward view_mu = mu0 is back-scatter.  `view_first_order='exact'` (default): the first order from the phase
     function at (lane, azimuth) itself, without the truncation at n_modes, which rings for a forward-peaked aerosol;
     `'modes'`: the sum of the modes' first orders.  BatchResult.view_mode_status [n_modes + 1, B].  I, n, status and I_view*
-    are those of the call without `view_azimuths`, bit for bit.  Not with `azimuths`, `mode_batch` or `mode_chunk`."""
+    are those of the call without `view_azimuths`, bit for bit.  Not with `azimuths`, `mode_batch` or `mode_chunk`.
+
+    `beam='spherical'`: the PSEUDO-SPHERICAL DIRECT BEAM.  The direct solar beam is attenuated along its slant path through
+    spherical shells of radius `earth_radius` (km) + np.linspace(z0, 0, nb_layers) instead of exp(-tau / mu0); everything
+    scattered is transported plane-parallel as before (`solve_spherical`; the reflected beam travels upward plane-parallel).
+    At mu0 = 0.21 the converged field moves by about 7 % of its maximum, at mu0 = 0.6 by 0.3 %.  BatchResult.beam_slant [B, L]
+    is the beam's slant optical depth at every level (None for 'plane').  `beam='plane'` (default) is the code path as it
+    was.  Works with phase functions by name or as arrays, `aer_set` and `save_orders`; not with `azimuths`, `view_mu`,
+    `view_azimuths`, `mode_batch`, `first_order='readme'` or several `devices` (their first orders are plane closed forms)."""
+    spherical = _beam_args(beam, earth_radius, azimuths, view_mu, view_azimuths, mode_batch, mode_chunk, first_order, devices)
     if view_azimuths is not None or view_first_order != "exact":
         vphi, vM, vnphi = _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_modes, nphi_modes, mode_batch,
                                              mode_chunk)
@@ -207,16 +315,21 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                                                       nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm,
                                                       mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device,
                                                       aer_set=aer_set)
+    sigma = None
     try:
-        s.set_first_order(first_order)
-        r = s.solve(tau, P0a, P0r, tol=tol, save_orders=save_orders)
+        if spherical:
+            r, sigma, _ = solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, int(nb_layers)), earth_radius, tol, save_orders, device)
+        else:
+            s.set_first_order(first_order)
+            r = s.solve(tau, P0a, P0r, tol=tol, save_orders=save_orders)
     finally:
-        s.set_first_order("coded")                           # (the solver is cached)
+        if not spherical:
+            s.set_first_order("coded")                       # (the solver is cached)
         if aer_set is not None:
             _columns_to_set0(s, tau.shape[0])
     if raise_on_error:
         _raise_status(r.status, N)
-    out = BatchResult(I=r.I, n=r.n, status=r.status, tau=tau, mu=mu, idx_up=iu, idx_down=idn, I_saved=r.I_saved)
+    out = BatchResult(I=r.I, n=r.n, status=r.status, tau=tau, mu=mu, idx_up=iu, idx_down=idn, I_saved=r.I_saved, beam_slant=sigma)
     if azimuths is not None:
         mu0v = np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
         if mode_batch:
@@ -412,10 +525,14 @@ def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=No
     `Solver.set_phase_sets`), instead of W small solves in the latency regime; the same list of results, column for column the
     bits of the loop while both take the single pass.  The matrices stay on the device: `Solver.phase_matrix_device` writes
     them where `Solver.set_phase_sets_device` folds them.
+    `beam='spherical'` and `earth_radius` are passed on like every further keyword: each wavelength's batch is then solved with
+    the pseudo-spherical direct beam, and its BatchResult carries `beam_slant`.
     Returns (list of BatchResult, one per wavelength; bulk [W, 3]: albedo, asymmetry parameter, mean extinction cross-section)."""
     import torch
     from . import mie as _mie
     wl, t_aer, t_atm, m, r_m, sig = _spectrum_args(wavelengths, tauStar_aer, angstrom, lambda_ref, aer, alb_aer, tauStar_atm_ref)
+    _beam_args(batch_kw.get("beam", "plane"), batch_kw.get("earth_radius", EARTH_RADIUS_KM), view_mu=batch_kw.get("view_mu"),
+               view_azimuths=batch_kw.get("view_azimuths"), first_order=batch_kw.get("first_order", "coded"))
     for k in ("P_aer", "P0_aer", "aer_phase_fun", "mie_aer", "tauStar_atm", "devices", "azimuths"):
         if k in batch_kw:
             raise ValueError("SOS_Aer_spectrum sets %s itself" % k)
@@ -455,7 +572,8 @@ def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=No
                               max_orders=max_orders, device=device, **batch_kw)
             cut = lambda a, w: None if a is None else a[w * C:(w + 1) * C]
             return [BatchResult(I=cut(r.I, w), n=cut(r.n, w), status=cut(r.status, w), tau=cut(r.tau, w), mu=r.mu, idx_up=r.idx_up,
-                                idx_down=r.idx_down, I_saved=cut(r.I_saved, w)) for w in range(W)], bulk
+                                idx_down=r.idx_down, I_saved=cut(r.I_saved, w), beam_slant=cut(r.beam_slant, w))
+                    for w in range(W)], bulk
         out = []
         for w in range(W):
             s.set_phase_table_dev(d_p[w].data_ptr(), int(ntab))
@@ -882,14 +1000,20 @@ def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0,
 def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, alb_aer=1.0, z0=120, z_up=25, z_down=17,
                        nb_layers=200, nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7,
                        mie_atm=None, mie_aer=None, P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular",
-                       tol=1e-4, max_orders=256, device=0):
+                       tol=1e-4, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM):
     """`SOS_Aer_batch` with the RESULT LEFT ON THE DEVICE: returns ({"I": [B, L, 2N] float64, "n": [B] int32, "status": [B]
     int32, "tau": [B, L]} as torch tensors on cuda:`device`, (mu, idx_up, idx_down)).  The solve is enqueued on torch's
-    current stream for that device, so the tensors are ordered like any torch result.  What `dist.solve_sharded` gathers."""
+    current stream for that device, so the tensors are ordered like any torch result.  What `dist.solve_sharded` gathers.
+    `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of `SOS_Aer_batch`; the dict then also holds
+    "beam_slant" [B, L]."""
     import torch
+    spherical = _beam_args(beam, earth_radius)
     s, tau, P0a, P0r, mu, iu, idn, N = _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
                                                       nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm,
                                                       mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device)
+    if spherical:
+        return solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, int(nb_layers)), earth_radius, tol, device=device,
+                               keep_device=True), (mu, iu, idn)
     dev = torch.device("cuda", device)
     B, L = tau.shape
     with torch.cuda.device(dev):
@@ -913,7 +1037,8 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
 
 def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=120, nb_layers=200, nb_angles=128,
                    atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, mie_atm=None, mie_aer=None, P_atm=None,
-                   P_aer=None, surface="specular", tol=1e-4, max_orders=256, device=0, raise_on_error=True) -> BatchResult:
+                   P_aer=None, surface="specular", tol=1e-4, max_orders=256, device=0, raise_on_error=True, beam="plane",
+                   earth_radius=EARTH_RADIUS_KM) -> BatchResult:
     """Columns with SEVERAL aerosol layers (the reference has one): `slabs` = [(z_up, z_down, tauStar_aer,
     alb_aer), ...] from the top down, shared by the B columns of the arrays `mu0`, `grd_alb`.  Every formula of the path is
     evaluated per zone as the reference writes it for its three zones; one layer gives `SOS_Aer_batch`'s result bit for
@@ -921,8 +1046,10 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
     or a dict(name=, g=, and the keywords of `mie_aer`) -- e.g. slabs=[(25, 17, 0.12, 0.97, "eva"), (15, 14, 0.0075, 0.9,
     "wildfire")]; slabs without one take (`aer_phase_fun`, `g_aer`, `mie_aer`), and when no slab has one all layers share
     that phase function exactly as before.  `P_aer` cannot be combined with a fifth entry.  `idx_up` / `idx_down` of the
-    result are those of the first layer."""
+    result are those of the first layer.  `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of
+    `SOS_Aer_batch`, BatchResult.beam_slant [B, L]."""
     from .inputs import tau_profile_slabs
+    spherical = _beam_args(beam, earth_radius)
     mu0, grd_alb = np.broadcast_arrays(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), np.atleast_1d(np.asarray(grd_alb, dtype=np.float64)))
     B, L, N = mu0.shape[0], int(nb_layers), int(nb_angles)
     mu = direction_grid(N)
@@ -972,20 +1099,27 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
     try:
         if own:
             s.set_aerosol_sets(np.tile(zset, (B, 1)))
-        r = s.solve(np.tile(tau, (B, 1)), P0a, P0r, tol=tol)
+        sigma = None
+        if spherical:
+            r, sigma, _ = solve_spherical(s, np.tile(tau, (B, 1)), P0a, P0r, np.linspace(z0, 0, L), earth_radius, tol, device=device)
+        else:
+            r = s.solve(np.tile(tau, (B, 1)), P0a, P0r, tol=tol)
     finally:
         if own:                                              # (the solver is cached: its columns go back to set 0)
             _columns_to_set0(s, B)
     if raise_on_error:
         _raise_status(r.status, N)
-    return BatchResult(I=r.I, n=r.n, status=r.status, tau=np.tile(tau, (B, 1)), mu=mu, idx_up=int(r0[1]), idx_down=int(r0[2]) - 1)
+    return BatchResult(I=r.I, n=r.n, status=r.status, tau=np.tile(tau, (B, 1)), mu=mu, idx_up=int(r0[1]), idx_down=int(r0[2]) - 1,
+                       beam_slant=sigma)
 
 
 def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=None, P_aer=None, P0_aer=None, device=0,
-            first_order="coded", **overrides) -> ColumnResult:
+            first_order="coded", beam="plane", earth_radius=EARTH_RADIUS_KM, **overrides) -> ColumnResult:
     """One column with the reference's parameter names (spec:19-96).  `surface` selects the file of
     the reference that would be run ('specular' | 'lambertian'); P*/P0* accept pre-built phase
-    arrays."""
+    arrays.  `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of `SOS_Aer_batch`;
+    ColumnResult.beam_slant [L]."""
+    _beam_args(beam, earth_radius, first_order=first_order)
     unknown = set(overrides) - set(DEFAULTS)
     if unknown:
         raise TypeError("unknown parameter(s): %s" % ", ".join(sorted(unknown)))
@@ -999,7 +1133,8 @@ def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=Non
                       mie_atm=mie["atm"], mie_aer=mie["aer"], P_atm=P_atm, P_aer=P_aer,
                       P0_atm=None if P0_atm is None else np.asarray(P0_atm)[None],
                       P0_aer=None if P0_aer is None else np.asarray(P0_aer)[None],
-                      surface=surface, tol=tol, max_orders=max_orders, save_orders=True, device=device, first_order=first_order)
+                      surface=surface, tol=tol, max_orders=max_orders, save_orders=True, device=device, first_order=first_order,
+                      beam=beam, earth_radius=earth_radius)
     n = int(r.n[0])
     return ColumnResult(I=r.I[0], I_saved=r.I_saved[0, :n].copy(), n=n, tau=r.tau[0], mu=r.mu, idx_up=r.idx_up,
-                        idx_down=r.idx_down, status=int(r.status[0]))
+                        idx_down=r.idx_down, status=int(r.status[0]), beam_slant=None if r.beam_slant is None else r.beam_slant[0])

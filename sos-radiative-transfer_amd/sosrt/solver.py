@@ -381,6 +381,35 @@ class Solver:
         check(lib().sosrt_epilogue_dev(self._h, self.B, vp(d_tau), vp(d_I), 0 if beam_norm == "crit" else 1, vp(d_z),
                                        vp(d_flux_down), vp(d_flux_up), vp(d_diffusivity), vp(d_heating_rate), vp(d_net_toa)))
 
+    # ---- pseudo-spherical direct beam (sosrt.h) --------------------------------
+    def set_saved_orders(self, slots: Optional[int] = None):
+        """Orders per column that the solves that follow store in their per-order output (None: the handle's max_orders)."""
+        check(lib().sosrt_set_saved_orders(self._h, int(self.max_orders if slots is None else slots)))
+
+    def beam_slant_device(self, d_tau: int, d_z: int, d_sigma_out: int, earth_radius=6371.0, d_mu0: int = 0, B: Optional[int] = None):
+        """Slant optical depth of the direct beam through spherical shells: d_tau [B, L], d_z [L] (km, strictly descending),
+        d_sigma_out [B, L] (device addresses); d_mu0 [B] or 0 for the columns' own mu0.  Enqueued on the handle's stream (the
+        call reads d_z back to check it)."""
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_beam_slant_dev(self._h, int(self.B if B is None else B), vp(d_tau), vp(d_z), float(earth_radius),
+                                         vp(d_mu0), vp(d_sigma_out)))
+
+    def first_order_beam_device(self, d_tau: int, d_sigma: int, d_P0_atm: int, d_P0_aer: int, d_I1_out: int, B: Optional[int] = None):
+        """The first order layer by layer on the beam path d_sigma [B, L] (sigma = tau / mu0: the coded first order, to
+        rounding): d_I1_out [B, L, 2N] is the `d_I1` of `solve_device`.  P0 layouts as `solve_device` takes them."""
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_first_order_beam_dev(self._h, int(self.B if B is None else B), vp(d_tau), vp(d_sigma), vp(d_P0_atm),
+                                               vp(d_P0_aer), vp(d_I1_out)))
+
+    def epilogue_beam_device(self, d_tau: int, d_I: int, d_sigma: int, d_z: int = 0, beam_norm="crit", d_flux_down: int = 0,
+                             d_flux_up: int = 0, d_diffusivity: int = 0, d_heating_rate: int = 0, d_net_toa: int = 0,
+                             B: Optional[int] = None):
+        """`epilogue_device` with the beam terms of the fluxes on the path d_sigma [B, L]."""
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_epilogue_beam_dev(self._h, int(self.B if B is None else B), vp(d_tau), vp(d_I),
+                                            0 if beam_norm == "crit" else 1, vp(d_z), vp(d_flux_down), vp(d_flux_up),
+                                            vp(d_diffusivity), vp(d_heating_rate), vp(d_net_toa), vp(d_sigma)))
+
     # ---- phase functions on the device (phase:68-292) ----------------------------
     _KINDS = {"iso": _lib.PHASE_ISO, "rayleigh": _lib.PHASE_RAYLEIGH, "hg": _lib.PHASE_HG, "table": _lib.PHASE_TABLE}
 
