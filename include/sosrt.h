@@ -558,6 +558,46 @@ int sosrt_epilogue_beam_dev(sosrt_t* h, int B, const double* d_tau, const double
                             double* d_flux_down, double* d_flux_up, double* d_diffusivity, double* d_heating_rate,
                             double* d_net_toa, const double* d_sigma /*[B][L]*/);
 
+/* ---- thermal emission: Planck sources in the layers and at the ground ------------------------------------
+ * Every other solve is driven by the solar beam.  This stage computes the radiation the layers and the ground EMIT, the field
+ * I_0 of a thermal problem; the order loop scatters and transports it as it is -- the full field is
+ * sosrt_solve_dev(.., d_I1_in = d_I0, ..), I = sum_{n>=0} I_n, and mu0 does not enter.  Detected by symbol; SOSRT_VERSION is
+ * unchanged.  All three are enqueued on the handle's stream, read the columns of the last sosrt_set_columns /
+ * sosrt_set_columns_zones (grd_alb, albedos, steps, zone table; the handle's surface) and write nothing but their outputs: the
+ * handle's columns, resident field, order targets, phase state and first-order mode are as they were.  1 <= B <= the current
+ * columns (the first B of them).
+ *
+ * d_planck [B][L]: the Planck radiance b_t at level t, in any unit (the field comes out in it); d_planck_surface [B]: the
+ * ground's, b_s; d_emissivity [B]: the ground's emissivity e_s, NULL: 1 - grd_alb.  Emission coefficient of a row's zone:
+ * eps = 1 - alb_atm in a clear zone, 1 - (alb_atm f_atm + alb_aer f_aer) in an aerosol zone (f of spec:149).  The layer between
+ * rows t-1 and t takes the eps of row t in BOTH sweeps.  The source is linear in tau between two levels and attenuated exactly:
+ * a = |mu|, x = Delta / a, E = exp(-x), A = (1 - E) / x, w0 = 1 - A (the row the sweep arrives at), w1 = A - E (the row it
+ * leaves), both 0 at x = 0 and summed as a series below x = 0.25 -- the rule of SOSRT_VIEW_QUAD_LINEAR.
+ *     downward  D_0 = 0,  D_t = D_{t-1} E + eps_t (w0 b_t + w1 b_{t-1})
+ *     ground    U_{L-1} = boundary(D_{L-1}) + e_s b_s
+ *     upward    U_t = U_{t+1} E + eps_{t+1} (w0 b_t + w1 b_{t+1})
+ *     mu = 0    eps_t b_t
+ * boundary: what the order loop applies for the handle's surface (specular: rho times the mirror lane; the two Lambertian
+ * grounds: their scalar of the downward surface row; SOSRT_SURFACE_NONE: 0).
+ *
+ * sosrt_emission_view_dev: the same sweeps at a = mu_view[v], the requested levels only; out lanes as sosrt_view_radiance_dev
+ * ([B][nlev][2V]: first the V downward lanes, then the V upward ones).  Specular and SOSRT_SURFACE_NONE only.
+ * sosrt_epilogue_emission_dev: sosrt_epilogue_dev without the two beam terms.  Outputs nullable as there.
+ *
+ * Refused with SOSRT_E_INVALID, a message and nothing written: the single-slab geometry; B outside 1..the current columns; a
+ * null pointer (d_emissivity and the nullable outputs of the epilogue aside); L > 2048; V, mu_view or levels outside
+ * the limits of sosrt_view_radiance_dev; a Lambertian surface in the view call; the heating rate without z_profile.  No device
+ * array is read back to be checked. */
+int sosrt_emission_dev(sosrt_t* h, int B, const double* d_tau /*[B][L]*/, const double* d_planck /*[B][L]*/,
+                       const double* d_planck_surface /*[B]*/, const double* d_emissivity /*[B], NULL: 1 - grd_alb*/,
+                       double* d_I0_out /*[B][L][2N]: the d_I1_in of sosrt_solve_dev*/);
+int sosrt_emission_view_dev(sosrt_t* h, int B, int V, const double* mu_view /*host [V], each in [0.01, 1]*/,
+                            const double* d_tau, const double* d_planck, const double* d_planck_surface,
+                            const double* d_emissivity, int nlev, const int* levels /*host*/, double* d_out /*[B][nlev][2V]*/);
+int sosrt_epilogue_emission_dev(sosrt_t* h, int B, const double* d_tau, const double* d_I, const double* d_z_profile,
+                                double* d_flux_down, double* d_flux_up, double* d_diffusivity, double* d_heating_rate,
+                                double* d_net_toa);   /* outputs nullable as in sosrt_epilogue_dev */
+
 /* ---- multi-GPU: one process per GPU, columns sharded, ONE collective at the end ------------------
  * Nothing in SOS_Aer_main_specular.py:104-458 couples columns, so the order loop never communicates; these entry
  * points only assemble the results of the ranks on `root` over RCCL (xGMI inside a node).  RCCL is bound at run time

@@ -200,6 +200,121 @@ def solve_spherical(s: Solver, tau, P0a, P0r, z, earth_radius=EARTH_RADIUS_KM, t
                 s.set_stream(None)
 
 
+def _thermal_args(source, planck, planck_surface, surface_emissivity, B, nb_layers, azimuths=None, view_azimuths=None,
+                  mode_batch=False, mode_chunk=None, beam="plane", first_order="coded", devices=None):
+    """Checks of the `source` keyword, made before any handle exists: None for the solar source, else (planck [B, L],
+    planck_surface [B], emissivity [B] or None) of the thermal one."""
+    if not isinstance(source, str) or source not in ("solar", "thermal"):
+        raise ValueError("source must be 'solar' or 'thermal' (got %r)" % (source,))
+    if source == "solar":
+        if planck is not None or planck_surface is not None or surface_emissivity is not None:
+            raise ValueError("planck, planck_surface and surface_emissivity belong to source='thermal': the solar source has no "
+                             "emission term")
+        return None
+    if planck is None or planck_surface is None:
+        raise ValueError("source='thermal' needs planck (the Planck radiance at every level, [L] or [B, L]) and planck_surface "
+                         "(the ground's, a scalar or [B])")
+    if azimuths is not None or mode_batch or mode_chunk is not None or view_azimuths is not None:
+        raise ValueError("source='thermal' is not available with azimuths / mode_batch / view_azimuths: emission is isotropic in "
+                         "azimuth and has only the m = 0 mode")
+    if beam != "plane":
+        raise ValueError("source='thermal' is not available with beam='spherical': the thermal field has no direct beam to bend")
+    if first_order != "coded":
+        raise ValueError("source='thermal' is not available with first_order='readme': the emitted field replaces the first order")
+    if devices is not None and len(devices) > 1:
+        raise ValueError("source='thermal' is not available with devices=[...]: solve each shard with SOS_Aer_batch(device=...)")
+    L = int(nb_layers)
+    try:
+        pl = np.asarray(planck, dtype=np.float64)
+        bs = np.asarray(planck_surface, dtype=np.float64)
+        es = None if surface_emissivity is None else np.asarray(surface_emissivity, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("planck, planck_surface and surface_emissivity must be numbers") from None
+    if pl.shape not in ((L,), (B, L)):
+        raise ValueError("planck must have the shape [L] = (%d,) or [B, L] = (%d, %d): one Planck radiance per level (got %s)"
+                         % (L, B, L, pl.shape))
+    if bs.shape not in ((), (B,)):
+        raise ValueError("planck_surface must be a scalar or [B] = (%d,) (got %s)" % (B, bs.shape))
+    if es is not None and es.shape not in ((), (B,)):
+        raise ValueError("surface_emissivity must be a scalar or [B] = (%d,) (got %s)" % (B, es.shape))
+    full = lambda a, shape: np.ascontiguousarray(np.broadcast_to(a, shape))
+    return full(pl, (B, L)), full(bs, (B,)), None if es is None else full(es, (B,))
+
+
+def _batch_width(*cols):
+    """Columns of a batch whose per-column arguments broadcast to a common length."""
+    try:
+        return int(np.broadcast_shapes(*[np.shape(np.atleast_1d(np.asarray(x))) for x in cols])[0])
+    except ValueError:
+        raise ValueError("the per-column arguments do not broadcast to a common length") from None
+
+
+def solve_thermal(s: Solver, tau, planck, planck_surface, emissivity=None, tol=1e-4, save_orders=False, want=(), z_profile=None,
+                  keep_device=False, device=0, fetch_field=True):
+    """The solve of handle `s` (grid, phase matrices and columns set) with the THERMAL SOURCE: the field the
+    layers and the ground emit (`planck` [B, L] the Planck radiance at every level, `planck_surface` [B], `emissivity` [B] or
+    None for 1 - grd_alb), then the order loop as it is, fed that field (`Solver.emission_device`, `solve_device(d_I1=...)`);
+    mu0 does not enter.  `want`: names of `Solver.epilogue` to compute from the field without beam terms
+    (`epilogue_emission_device`; `z_profile` for the heating rate).  Returns (SolveResult, dict of the wanted epilogue arrays);
+    keep_device=True: the torch tensors {"I", "n", "status", "tau"} instead, left on the device.  The handle goes back to its own
+    stream and to its default per-order storage, also on error."""
+    import torch
+    from .solver import SolveResult
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    B, L = tau.shape
+    D = s.D
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        try:
+            up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)    # (a copy: broadcast inputs are read-only)
+            d_tau, d_pl, d_bs = up(tau), up(np.broadcast_to(planck, (B, L))), up(np.broadcast_to(planck_surface, (B,)))
+            d_es = None if emissivity is None else up(np.broadcast_to(emissivity, (B,)))
+            d_I0 = torch.empty((B, L, D), dtype=torch.float64, device=dev)
+            d_I = torch.empty((B, L, D), dtype=torch.float64, device=dev)
+            d_n = torch.zeros(B, dtype=torch.int32, device=dev)
+            d_st = torch.zeros(B, dtype=torch.int32, device=dev)
+            s.emission_device(d_tau.data_ptr(), d_pl.data_ptr(), d_bs.data_ptr(), d_I0.data_ptr(),
+                              0 if d_es is None else d_es.data_ptr(), B=B)
+            s.solve_device(d_tau.data_ptr(), 0, 0, d_I.data_ptr(), tol=tol, d_I1=d_I0.data_ptr(), d_n_orders=d_n.data_ptr(),
+                           d_status=d_st.data_ptr())
+            d_sv = None
+            if save_orders:
+                # (as Solver.solve: the first pass gives n, the second stores exactly max(n) orders per column)
+                s.synchronize()
+                slots = int(max(1, d_n.max().item()))
+                s.set_saved_orders(slots)
+                d_sv = torch.zeros((B, slots, L, D), dtype=torch.float64, device=dev)
+                s.solve_device(d_tau.data_ptr(), 0, 0, d_I.data_ptr(), tol=tol, d_I1=d_I0.data_ptr(), d_I_saved=d_sv.data_ptr(),
+                               d_n_orders=d_n.data_ptr(), d_status=d_st.data_ptr())
+            epi = {}
+            want = [k for k in ("flux_down", "flux_up", "diffusivity", "heating_rate", "net_toa")
+                    if k in set(want) and not (k == "heating_rate" and z_profile is None)]
+            if want:
+                d_zp = None if z_profile is None else up(z_profile)
+                d_out = {k: torch.empty((B,) if k == "net_toa" else (B, L), dtype=torch.float64, device=dev) for k in want}
+                ptr = lambda k: d_out[k].data_ptr() if k in d_out else 0
+                s.epilogue_emission_device(d_tau.data_ptr(), d_I.data_ptr(), 0 if d_zp is None else d_zp.data_ptr(),
+                                           ptr("flux_down"), ptr("flux_up"), ptr("diffusivity"), ptr("heating_rate"),
+                                           ptr("net_toa"), B=B)
+                s.synchronize()
+                epi = {k: v.cpu().numpy() for k, v in d_out.items()}
+            s.synchronize()
+            if keep_device:
+                return {"I": d_I, "n": d_n, "status": d_st, "tau": d_tau}
+            r = SolveResult(I=d_I.cpu().numpy() if fetch_field else None, n=d_n.cpu().numpy(), status=d_st.cpu().numpy(),
+                            I_saved=None if d_sv is None else d_sv.cpu().numpy())
+            return r, epi
+        finally:
+            # the solver is cached and goes back to its own stream: drain this one first
+            try:
+                s.synchronize()
+            finally:
+                if save_orders:
+                    s.set_saved_orders(None)
+                s.set_stream(None)
+
+
 def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, alb_aer=1.0, z0=120, z_up=25, z_down=17,
                   nb_layers=200, nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7,
                   mie_atm=None, mie_aer=None,
@@ -207,7 +322,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   save_orders=False, device=0, devices=None, raise_on_error=True, first_order="coded", azimuths=None,
                   n_modes=None, nphi_modes=None, levels=(0, -1), aer_set=None, mode_batch=False, mode_chunk=None,
                   view_mu=None, view_levels=(0, -1), view_quadrature="grid", view_azimuths=None,
-                  view_first_order="exact", beam="plane", earth_radius=EARTH_RADIUS_KM) -> BatchResult:
+                  view_first_order="exact", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None,
+                  planck_surface=None, surface_emissivity=None) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -267,7 +383,20 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     At mu0 = 0.21 the converged field moves by about 7 % of its maximum, at mu0 = 0.6 by 0.3 %.  BatchResult.beam_slant [B, L]
     is the beam's slant optical depth at every level (None for 'plane').  `beam='plane'` (default) is the code path as it
     was.  Works with phase functions by name or as arrays, `aer_set` and `save_orders`; not with `azimuths`, `view_mu`,
-    `view_azimuths`, `mode_batch`, `first_order='readme'` or several `devices` (their first orders are plane closed forms)."""
+    `view_azimuths`, `mode_batch`, `first_order='readme'` or several `devices` (their first orders are plane closed forms).
+
+    `source='thermal'`: THERMAL EMISSION instead of the solar beam (`solve_thermal`).  `planck` ([L] or [B, L]) is the Planck
+    radiance at every level in any unit -- the field comes out in it (`thermal.planck_radiance` gives W m-2 sr-1 um-1) --
+    `planck_surface` (scalar or [B]) the ground's, `surface_emissivity` (scalar or [B]) the ground's emissivity, default
+    1 - grd_alb.  A layer emits (1 - its single-scattering albedo) times a Planck radiance linear in tau across it; the order
+    loop scatters and transports the emitted field as it is.  I (and I_saved) are the thermal field; mu0 does not enter.  With
+    `view_mu`, I_view_first is the emission at the view lanes and I_view_scattered the view stage on I.  The orders n >= 1
+    inherit the reference's mu -> 0 treatments, so the lanes next to mu = 0 may overshoot max(planck).  Not with `azimuths`,
+    `mode_batch`, `view_azimuths` (emission has only the m = 0 mode), `beam='spherical'`, `first_order='readme'` or several
+    `devices`.  `source='solar'` (default) is the code path as it was."""
+    thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
+                            _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if source == "thermal" else 0,
+                            nb_layers, azimuths, view_azimuths, mode_batch, mode_chunk, beam, first_order, devices)
     spherical = _beam_args(beam, earth_radius, azimuths, view_mu, view_azimuths, mode_batch, mode_chunk, first_order, devices)
     if view_azimuths is not None or view_first_order != "exact":
         vphi, vM, vnphi = _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_modes, nphi_modes, mode_batch,
@@ -319,11 +448,13 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     try:
         if spherical:
             r, sigma, _ = solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, int(nb_layers)), earth_radius, tol, save_orders, device)
+        elif thermal:
+            r, _ = solve_thermal(s, tau, *thermal, tol=tol, save_orders=save_orders, device=device)
         else:
             s.set_first_order(first_order)
             r = s.solve(tau, P0a, P0r, tol=tol, save_orders=save_orders)
     finally:
-        if not spherical:
+        if not spherical and not thermal:
             s.set_first_order("coded")                       # (the solver is cached)
         if aer_set is not None:
             _columns_to_set0(s, tau.shape[0])
@@ -347,7 +478,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         mu0v = np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
         out.view_mu_signed = np.concatenate((-vmu, vmu))
         out.I_view_first, out.I_view_scattered = view_radiance(s, tau, r.I, mu0v, vmu, vlev, vquad, atm_phase_fun, g_atm, mie_atm,
-                                                               aer_phase_fun, g_aer, mie_aer, device)
+                                                               aer_phase_fun, g_aer, mie_aer, device, thermal=thermal)
         out.I_view = out.I_view_first + out.I_view_scattered
         if view_azimuths is not None:
             out.I_view_azimuth_first, out.I_view_azimuth_scattered, out.view_mode_status = view_azimuth_modes(
@@ -416,9 +547,11 @@ def _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_mod
 
 
 def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
-                  mie_aer, device=0):
+                  mie_aer, device=0, thermal=None):
     """The view stage on the field `I` [B, L, 2N] of handle `s` (whose columns are set): rows of both phase functions at the
-    signed lanes, then `Solver.view_radiance_device` with I_src = I.  Returns (first order, scattered), each [B, nlev, 2V]."""
+    signed lanes, then `Solver.view_radiance_device` with I_src = I.  Returns (first order, scattered), each [B, nlev, 2V].
+    `thermal` = (planck [B, L], planck_surface [B], emissivity [B] or None): I is a thermal field, and the first term is the
+    emission at the view lanes (`Solver.emission_view_device`) instead of the solar first order."""
     import torch
     from .inputs import _scalar_phase
     B, L = tau.shape
@@ -449,6 +582,16 @@ def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase
             d_scat = torch.empty((B, len(levels), V2), dtype=torch.float64, device=dev)
             d_first = torch.empty((B, len(levels), V2), dtype=torch.float64, device=dev)
             torch.cuda.current_stream(dev).synchronize()
+            if thermal is not None:
+                up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)
+                d_pl, d_bs = up(thermal[0]), up(thermal[1])
+                d_es = None if thermal[2] is None else up(thermal[2])
+                s.emission_view_device(view_mu, d_tau.data_ptr(), d_pl.data_ptr(), d_bs.data_ptr(), levels, d_first.data_ptr(),
+                                       0 if d_es is None else d_es.data_ptr(), B=B)
+                s.view_radiance_device(view_mu, d_tau.data_ptr(), d_I.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), levels,
+                                       d_scat_out=d_scat.data_ptr(), quadrature=quadrature, B=B)
+                s.synchronize()
+                return d_first.cpu().numpy(), d_scat.cpu().numpy()
             s.view_radiance_device(view_mu, d_tau.data_ptr(), d_I.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), levels,
                                    d_scat_out=d_scat.data_ptr(), d_first_out=d_first.data_ptr(), d_p0rows_atm=p0rows[0].data_ptr(),
                                    d_p0rows_aer=p0rows[1].data_ptr(), quadrature=quadrature, B=B)
@@ -1000,13 +1143,18 @@ def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0,
 def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, alb_aer=1.0, z0=120, z_up=25, z_down=17,
                        nb_layers=200, nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7,
                        mie_atm=None, mie_aer=None, P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular",
-                       tol=1e-4, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM):
+                       tol=1e-4, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar",
+                       planck=None, planck_surface=None, surface_emissivity=None):
     """`SOS_Aer_batch` with the RESULT LEFT ON THE DEVICE: returns ({"I": [B, L, 2N] float64, "n": [B] int32, "status": [B]
     int32, "tau": [B, L]} as torch tensors on cuda:`device`, (mu, idx_up, idx_down)).  The solve is enqueued on torch's
     current stream for that device, so the tensors are ordered like any torch result.  What `dist.solve_sharded` gathers.
     `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of `SOS_Aer_batch`; the dict then also holds
-    "beam_slant" [B, L]."""
+    "beam_slant" [B, L].  `source='thermal'` (with `planck`, `planck_surface`, `surface_emissivity`): the thermal field of
+    `SOS_Aer_batch`."""
     import torch
+    thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
+                            _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if source == "thermal" else 0,
+                            nb_layers, beam=beam)
     spherical = _beam_args(beam, earth_radius)
     s, tau, P0a, P0r, mu, iu, idn, N = _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
                                                       nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm,
@@ -1014,6 +1162,8 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
     if spherical:
         return solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, int(nb_layers)), earth_radius, tol, device=device,
                                keep_device=True), (mu, iu, idn)
+    if thermal:
+        return solve_thermal(s, tau, *thermal, tol=tol, keep_device=True, device=device), (mu, iu, idn)
     dev = torch.device("cuda", device)
     B, L = tau.shape
     with torch.cuda.device(dev):
@@ -1038,7 +1188,8 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
 def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=120, nb_layers=200, nb_angles=128,
                    atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, mie_atm=None, mie_aer=None, P_atm=None,
                    P_aer=None, surface="specular", tol=1e-4, max_orders=256, device=0, raise_on_error=True, beam="plane",
-                   earth_radius=EARTH_RADIUS_KM) -> BatchResult:
+                   earth_radius=EARTH_RADIUS_KM, source="solar", planck=None, planck_surface=None,
+                   surface_emissivity=None) -> BatchResult:
     """Columns with SEVERAL aerosol layers (the reference has one): `slabs` = [(z_up, z_down, tauStar_aer,
     alb_aer), ...] from the top down, shared by the B columns of the arrays `mu0`, `grd_alb`.  Every formula of the path is
     evaluated per zone as the reference writes it for its three zones; one layer gives `SOS_Aer_batch`'s result bit for
@@ -1047,8 +1198,11 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
     "wildfire")]; slabs without one take (`aer_phase_fun`, `g_aer`, `mie_aer`), and when no slab has one all layers share
     that phase function exactly as before.  `P_aer` cannot be combined with a fifth entry.  `idx_up` / `idx_down` of the
     result are those of the first layer.  `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of
-    `SOS_Aer_batch`, BatchResult.beam_slant [B, L]."""
+    `SOS_Aer_batch`, BatchResult.beam_slant [B, L].  `source='thermal'` (with `planck`, `planck_surface`,
+    `surface_emissivity`): the thermal field of `SOS_Aer_batch`; every aerosol layer emits with its own albedo."""
     from .inputs import tau_profile_slabs
+    thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
+                            _batch_width(mu0, grd_alb) if source == "thermal" else 0, nb_layers, beam=beam)
     spherical = _beam_args(beam, earth_radius)
     mu0, grd_alb = np.broadcast_arrays(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), np.atleast_1d(np.asarray(grd_alb, dtype=np.float64)))
     B, L, N = mu0.shape[0], int(nb_layers), int(nb_angles)
@@ -1102,6 +1256,8 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
         sigma = None
         if spherical:
             r, sigma, _ = solve_spherical(s, np.tile(tau, (B, 1)), P0a, P0r, np.linspace(z0, 0, L), earth_radius, tol, device=device)
+        elif thermal:
+            r, _ = solve_thermal(s, np.tile(tau, (B, 1)), *thermal, tol=tol, device=device)
         else:
             r = s.solve(np.tile(tau, (B, 1)), P0a, P0r, tol=tol)
     finally:
@@ -1114,11 +1270,15 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
 
 
 def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=None, P_aer=None, P0_aer=None, device=0,
-            first_order="coded", beam="plane", earth_radius=EARTH_RADIUS_KM, **overrides) -> ColumnResult:
+            first_order="coded", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None, planck_surface=None,
+            surface_emissivity=None, **overrides) -> ColumnResult:
     """One column with the reference's parameter names (spec:19-96).  `surface` selects the file of
     the reference that would be run ('specular' | 'lambertian'); P*/P0* accept pre-built phase
     arrays.  `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of `SOS_Aer_batch`;
-    ColumnResult.beam_slant [L]."""
+    ColumnResult.beam_slant [L].  `source='thermal'` (with `planck` [L], `planck_surface`, `surface_emissivity`): the thermal
+    field of `SOS_Aer_batch`."""
+    _thermal_args(source, planck, planck_surface, surface_emissivity, 1,
+                  overrides.get("nb_layers", DEFAULTS["nb_layers"]), beam=beam, first_order=first_order)
     _beam_args(beam, earth_radius, first_order=first_order)
     unknown = set(overrides) - set(DEFAULTS)
     if unknown:
@@ -1134,7 +1294,8 @@ def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=Non
                       P0_atm=None if P0_atm is None else np.asarray(P0_atm)[None],
                       P0_aer=None if P0_aer is None else np.asarray(P0_aer)[None],
                       surface=surface, tol=tol, max_orders=max_orders, save_orders=True, device=device, first_order=first_order,
-                      beam=beam, earth_radius=earth_radius)
+                      beam=beam, earth_radius=earth_radius, source=source, planck=planck, planck_surface=planck_surface,
+                      surface_emissivity=surface_emissivity)
     n = int(r.n[0])
     return ColumnResult(I=r.I[0], I_saved=r.I_saved[0, :n].copy(), n=n, tau=r.tau[0], mu=r.mu, idx_up=r.idx_up,
                         idx_down=r.idx_down, status=int(r.status[0]), beam_slant=None if r.beam_slant is None else r.beam_slant[0])

@@ -410,8 +410,37 @@ class Solver:
                                             0 if beam_norm == "crit" else 1, vp(d_z), vp(d_flux_down), vp(d_flux_up),
                                             vp(d_diffusivity), vp(d_heating_rate), vp(d_net_toa), vp(d_sigma)))
 
+    # ---- thermal emission (sosrt.h) ----------------------------------------------
+    def emission_device(self, d_tau: int, d_planck: int, d_planck_surface: int, d_I0_out: int, d_emissivity: int = 0,
+                        B: Optional[int] = None):
+        """The field the layers and the ground emit: d_tau, d_planck [B, L] (the Planck radiance at every level),
+        d_planck_surface [B], d_emissivity [B] or 0 for 1 - grd_alb; d_I0_out [B, L, 2N] is the `d_I1` of `solve_device`.
+        Device addresses; enqueued on the handle's stream; nothing but the output is written."""
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_emission_dev(self._h, int(self.B if B is None else B), vp(d_tau), vp(d_planck), vp(d_planck_surface),
+                                       vp(d_emissivity), vp(d_I0_out)))
+
+    def emission_view_device(self, mu_view, d_tau: int, d_planck: int, d_planck_surface: int, levels, d_out: int,
+                             d_emissivity: int = 0, B: Optional[int] = None):
+        """`emission_device` at the view cosines `mu_view` [V] (host, each in [0.01, 1], V <= 64) and the rows `levels`:
+        d_out [B, nlev, 2V] on the signed lanes (-mu_view, +mu_view).  Specular or no surface."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
+        lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.int32)
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_emission_view_dev(self._h, int(self.B if B is None else B), int(m.size), _ptr(m) if m.size else None,
+                                            vp(d_tau), vp(d_planck), vp(d_planck_surface), vp(d_emissivity), int(lev.size),
+                                            _ptr(lev) if lev.size else None, vp(d_out)))
+
+    def epilogue_emission_device(self, d_tau: int, d_I: int, d_z: int = 0, d_flux_down: int = 0, d_flux_up: int = 0,
+                                 d_diffusivity: int = 0, d_heating_rate: int = 0, d_net_toa: int = 0, B: Optional[int] = None):
+        """`epilogue_device` without the two beam terms: the fluxes, diffusivity, heating rate and TOA net flux of a thermal field."""
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_epilogue_emission_dev(self._h, int(self.B if B is None else B), vp(d_tau), vp(d_I), vp(d_z),
+                                                vp(d_flux_down), vp(d_flux_up), vp(d_diffusivity), vp(d_heating_rate),
+                                                vp(d_net_toa)))
+
     # ---- phase functions on the device (phase:68-292) ----------------------------
-    _KINDS = {"iso": _lib.PHASE_ISO, "rayleigh": _lib.PHASE_RAYLEIGH, "hg": _lib.PHASE_HG, "table": _lib.PHASE_TABLE}
+    _KINDS ={"iso": _lib.PHASE_ISO, "rayleigh": _lib.PHASE_RAYLEIGH, "hg": _lib.PHASE_HG, "table": _lib.PHASE_TABLE}
 
     def set_phase_table(self, tab_mu, tab_p):
         tm = np.ascontiguousarray(tab_mu, dtype=np.float64)
