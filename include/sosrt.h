@@ -598,6 +598,42 @@ int sosrt_epilogue_emission_dev(sosrt_t* h, int B, const double* d_tau, const do
                                 double* d_flux_down, double* d_flux_up, double* d_diffusivity, double* d_heating_rate,
                                 double* d_net_toa);   /* outputs nullable as in sosrt_epilogue_dev */
 
+/* ---- band integration: spectral points in one batch --------------------------------------------------------
+ * A batch of K spectral points x C physical columns is solved as K C library columns laid out point-major, b = k C + c.  Two
+ * stages beside the solve, detected by symbol (SOSRT_VERSION is unchanged).  Both are enqueued on the handle's stream; the Planck
+ * stage reads the handle's L; nothing else of the handle's solve state is read or written (like every stage, a call ends the
+ * run of adjacent launches that the handle's profiling slots keep track of), and no device array is read back.
+ *
+ * sosrt_planck_bands_dev: the Planck radiance of K bands [nu_lo, nu_hi] (wavenumbers, cm^-1) at the L levels and at the ground
+ * of C columns, from temperatures in kelvin.  x = c2 nu / T, c2 = 100 h c / k (CODATA 2018);
+ *     B = 2 k^4 T^4 / (h^3 c^2) [G(x_lo) - G(x_hi)]  W m^-2 sr^-1,   G(x) = int_x^inf t^3 / (e^t - 1) dt,
+ * split at x = 1: below it G = pi^4 / 15 - S(x), S(x) = sum c_k x^{k+3}, c_k = B_k / ((k + 3) k!) over the ten non-zero
+ * Bernoulli terms k = 0, 1, 2, 4, .., 16; at and above it G = sum_{n=1}^{30} e^{-n x} (x^3/n + 3 x^2/n^2 + 6 x/n^3 + 6/n^4).
+ * The difference takes the form that does not cancel: S(x_hi) - S(x_lo) with both edges below 1, the two sums with both at or
+ * above it, (pi^4/15 - S(x_lo)) - G(x_hi) otherwise.  nu_lo = 0 is allowed; pi B(0, inf) = sigma T^4.  A band of width dnu
+ * loses digits by cancellation (up to 6e-13 relative at 1 cm^-1, 6e-11 at 0.01 cm^-1): a monochromatic source is the caller's.
+ * T <= 0 is not refused (the temperatures are not read back): such an entry comes out NaN.  Under normalise = 1 a (k, c) with
+ * no positive value -- every radiance underflows to 0, a band far in the Wien tail of a cold column (x above about 745), or every
+ * temperature is <= 0 -- gets scale = 0 and NaN outputs (0 / 0): the caller tests the scale it reads back.
+ * normalise = 1: per (k, c) scale = max(max_t b_t, b_s); the outputs are b / scale, their maximum exactly 1.0, and d_scale_out
+ * receives scale -- the order loop's mu -> 0 search has an absolute threshold and wants a source of order 1.
+ * normalise = 0: the outputs as computed, scale = 1; d_scale_out may then be NULL.
+ * Refused with SOSRT_E_INVALID, a message and nothing written: C or K < 1; a null pointer (the scale under normalise = 0
+ * aside); an edge that is not finite or is negative; nu_hi <= nu_lo; normalise other than 0 or 1.
+ *
+ * sosrt_band_reduce_dev: out[c][m] = acc_K, acc_0 = accumulate ? out[c][m] : 0, and for k = 0 .. K-1 in this order
+ * acc_{k+1} = fma(w[k][c] s[k][c], x[k][c][m], acc_k) with the product w s rounded once; a NULL d_weight or d_scale stands for
+ * ones.  The result depends neither on the launch geometry nor on how K is split over calls with accumulate = 1.  M is what
+ * the caller sums: L for a flux or heating-rate profile, 1 for net_toa, nlev 2V for view radiances.
+ * Refused: C, K or M < 1; null d_x or d_out. */
+int sosrt_planck_bands_dev(sosrt_t* h, int C, int K, const double* d_T /*[C][L] kelvin at the levels*/,
+                           const double* d_T_surface /*[C]*/, const double* nu_lo /*host [K], cm^-1*/,
+                           const double* nu_hi /*host [K]*/, int normalise, double* d_planck_out /*[K][C][L]*/,
+                           double* d_planck_surface_out /*[K][C]*/, double* d_scale_out /*[K][C]*/);
+int sosrt_band_reduce_dev(sosrt_t* h, int C, int K, int M, const double* d_weight /*[K][C] or NULL: 1*/,
+                          const double* d_scale /*[K][C] or NULL: 1*/, const double* d_x /*[K][C][M]*/,
+                          double* d_out /*[C][M]*/, int accumulate);
+
 /* ---- multi-GPU: one process per GPU, columns sharded, ONE collective at the end ------------------
  * Nothing in SOS_Aer_main_specular.py:104-458 couples columns, so the order loop never communicates; these entry
  * points only assemble the results of the ranks on `root` over RCCL (xGMI inside a node).  RCCL is bound at run time

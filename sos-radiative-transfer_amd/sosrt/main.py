@@ -254,10 +254,11 @@ def solve_thermal(s: Solver, tau, planck, planck_surface, emissivity=None, tol=1
     """The solve of handle `s` (grid, phase matrices and columns set) with the THERMAL SOURCE: the field the
     layers and the ground emit (`planck` [B, L] the Planck radiance at every level, `planck_surface` [B], `emissivity` [B] or
     None for 1 - grd_alb), then the order loop as it is, fed that field (`Solver.emission_device`, `solve_device(d_I1=...)`);
-    mu0 does not enter.  `want`: names of `Solver.epilogue` to compute from the field without beam terms
-    (`epilogue_emission_device`; `z_profile` for the heating rate).  Returns (SolveResult, dict of the wanted epilogue arrays);
-    keep_device=True: the torch tensors {"I", "n", "status", "tau"} instead, left on the device.  The handle goes back to its own
-    stream and to its default per-order storage, also on error."""
+    mu0 does not enter.  The three sources may be float64 torch tensors of those shapes on cuda:`device`: nothing is uploaded
+    for them.  `want`: names of `Solver.epilogue` to compute from the field without beam terms (`epilogue_emission_device`;
+    `z_profile` for the heating rate).  Returns (SolveResult, dict of the wanted epilogue arrays); keep_device=True: the torch
+    tensors {"I", "n", "status", "tau"} instead, left on the device.  The handle goes back to its own stream and to its default
+    per-order storage, also on error."""
     import torch
     from .solver import SolveResult
     tau = np.ascontiguousarray(tau, dtype=np.float64)
@@ -268,8 +269,16 @@ def solve_thermal(s: Solver, tau, planck, planck_surface, emissivity=None, tol=1
         s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
         try:
             up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)    # (a copy: broadcast inputs are read-only)
-            d_tau, d_pl, d_bs = up(tau), up(np.broadcast_to(planck, (B, L))), up(np.broadcast_to(planck_surface, (B,)))
-            d_es = None if emissivity is None else up(np.broadcast_to(emissivity, (B,)))
+            def src(a, shape, name):
+                # a torch tensor on the device is used where it lies (sosrt.bands builds the sources there); NumPy is uploaded
+                if not isinstance(a, torch.Tensor):
+                    return up(np.broadcast_to(a, shape))
+                if a.device != dev or a.dtype != torch.float64 or tuple(a.shape) != shape:
+                    raise ValueError("%s as a torch tensor must be float64 %s on %s (got %s %s on %s)"
+                                     % (name, shape, dev, a.dtype, tuple(a.shape), a.device))
+                return a.contiguous()
+            d_tau, d_pl, d_bs = up(tau), src(planck, (B, L), "planck"), src(planck_surface, (B,), "planck_surface")
+            d_es = None if emissivity is None else src(emissivity, (B,), "surface_emissivity")
             d_I0 = torch.empty((B, L, D), dtype=torch.float64, device=dev)
             d_I = torch.empty((B, L, D), dtype=torch.float64, device=dev)
             d_n = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -1144,13 +1153,14 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
                        nb_layers=200, nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7,
                        mie_atm=None, mie_aer=None, P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular",
                        tol=1e-4, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar",
-                       planck=None, planck_surface=None, surface_emissivity=None):
+                       planck=None, planck_surface=None, surface_emissivity=None, aer_set=None):
     """`SOS_Aer_batch` with the RESULT LEFT ON THE DEVICE: returns ({"I": [B, L, 2N] float64, "n": [B] int32, "status": [B]
     int32, "tau": [B, L]} as torch tensors on cuda:`device`, (mu, idx_up, idx_down)).  The solve is enqueued on torch's
     current stream for that device, so the tensors are ordered like any torch result.  What `dist.solve_sharded` gathers.
     `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of `SOS_Aer_batch`; the dict then also holds
     "beam_slant" [B, L].  `source='thermal'` (with `planck`, `planck_surface`, `surface_emissivity`): the thermal field of
-    `SOS_Aer_batch`."""
+    `SOS_Aer_batch`.  `aer_set` [B] with a list of names in `aer_phase_fun` (or a stack `P_aer`): several aerosols in one batch,
+    as in `SOS_Aer_batch`; the cached handle's columns are back on aerosol set 0 when the call returns, also on error."""
     import torch
     thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
                             _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if source == "thermal" else 0,
@@ -1158,31 +1168,36 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
     spherical = _beam_args(beam, earth_radius)
     s, tau, P0a, P0r, mu, iu, idn, N = _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
                                                       nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm,
-                                                      mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device)
-    if spherical:
-        return solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, int(nb_layers)), earth_radius, tol, device=device,
-                               keep_device=True), (mu, iu, idn)
-    if thermal:
-        return solve_thermal(s, tau, *thermal, tol=tol, keep_device=True, device=device), (mu, iu, idn)
-    dev = torch.device("cuda", device)
-    B, L = tau.shape
-    with torch.cuda.device(dev):
-        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        try:
-            d_tau = torch.from_numpy(tau).to(dev)
-            d_P0a = torch.from_numpy(np.ascontiguousarray(P0a)).to(dev)
-            d_P0r = torch.from_numpy(np.ascontiguousarray(P0r)).to(dev)
-            d_I = torch.empty((B, L, 2 * N), dtype=torch.float64, device=dev)
-            d_n = torch.zeros(B, dtype=torch.int32, device=dev)
-            d_st = torch.zeros(B, dtype=torch.int32, device=dev)
-            s.solve_device(d_tau.data_ptr(), d_P0a.data_ptr(), d_P0r.data_ptr(), d_I.data_ptr(), tol=tol,
-                           d_n_orders=d_n.data_ptr(), d_status=d_st.data_ptr())
-        finally:
-            # the solver is cached and goes back to its own stream: drain this one first, so that the handle's internal
-            # buffers are not reused under the last launches (the order loop has already waited for all but the last two)
-            s.synchronize()
-            s.set_stream(None)
-    return {"I": d_I, "n": d_n, "status": d_st, "tau": d_tau}, (mu, iu, idn)
+                                                      mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device,
+                                                      aer_set=aer_set)
+    try:
+        if spherical:
+            return solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, int(nb_layers)), earth_radius, tol, device=device,
+                                   keep_device=True), (mu, iu, idn)
+        if thermal:
+            return solve_thermal(s, tau, *thermal, tol=tol, keep_device=True, device=device), (mu, iu, idn)
+        dev = torch.device("cuda", device)
+        B, L = tau.shape
+        with torch.cuda.device(dev):
+            s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+            try:
+                d_tau = torch.from_numpy(tau).to(dev)
+                d_P0a = torch.from_numpy(np.ascontiguousarray(P0a)).to(dev)
+                d_P0r = torch.from_numpy(np.ascontiguousarray(P0r)).to(dev)
+                d_I = torch.empty((B, L, 2 * N), dtype=torch.float64, device=dev)
+                d_n = torch.zeros(B, dtype=torch.int32, device=dev)
+                d_st = torch.zeros(B, dtype=torch.int32, device=dev)
+                s.solve_device(d_tau.data_ptr(), d_P0a.data_ptr(), d_P0r.data_ptr(), d_I.data_ptr(), tol=tol,
+                               d_n_orders=d_n.data_ptr(), d_status=d_st.data_ptr())
+            finally:
+                # the solver is cached and goes back to its own stream: drain this one first, so that the handle's internal
+                # buffers are not reused under the last launches (the order loop has already waited for all but the last two)
+                s.synchronize()
+                s.set_stream(None)
+        return {"I": d_I, "n": d_n, "status": d_st, "tau": d_tau}, (mu, iu, idn)
+    finally:
+        if aer_set is not None:
+            _columns_to_set0(s, tau.shape[0])
 
 
 def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=120, nb_layers=200, nb_angles=128,

@@ -439,6 +439,30 @@ class Solver:
                                                 vp(d_flux_down), vp(d_flux_up), vp(d_diffusivity), vp(d_heating_rate),
                                                 vp(d_net_toa)))
 
+    # ---- band integration (sosrt.h) --------------------------------------------------
+    def planck_bands_device(self, d_T: int, d_T_surface: int, nu_lo, nu_hi, d_planck_out: int, d_planck_surface_out: int,
+                            d_scale_out: int = 0, C: int = 1, normalise=True):
+        """Planck band radiances (W m-2 sr-1) of the K bands [nu_lo, nu_hi] (host, cm^-1) at the levels and the ground of C
+        columns: d_T [C, L] and d_T_surface [C] in kelvin; d_planck_out [K, C, L], d_planck_surface_out [K, C], d_scale_out
+        [K, C].  normalise: every (k, c) divided by its maximum, which goes to d_scale_out (0 is allowed without it).  Device
+        addresses; enqueued on the handle's stream; nothing but the outputs is written."""
+        lo = np.ascontiguousarray(np.atleast_1d(nu_lo), dtype=np.float64)
+        hi = np.ascontiguousarray(np.atleast_1d(nu_hi), dtype=np.float64)
+        if lo.ndim != 1 or lo.shape != hi.shape:
+            raise ValueError("nu_lo and nu_hi must be two arrays [K] of one length")
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_planck_bands_dev(self._h, int(C), int(lo.size), vp(d_T), vp(d_T_surface), _ptr(lo) if lo.size else None,
+                                           _ptr(hi) if hi.size else None, int(bool(normalise)), vp(d_planck_out),
+                                           vp(d_planck_surface_out), vp(d_scale_out)))
+
+    def band_reduce_device(self, d_x: int, d_out: int, C: int, K: int, M: int, d_weight: int = 0, d_scale: int = 0,
+                           accumulate=False):
+        """d_out [C, M] = (accumulate ? d_out : 0) + sum over k ascending of (weight[k, c] scale[k, c]) d_x[k, c, m], one fused
+        multiply-add per k; d_weight, d_scale [K, C] or 0 for ones.  The same bits however K is split over accumulating calls."""
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        check(lib().sosrt_band_reduce_dev(self._h, int(C), int(K), int(M), vp(d_weight), vp(d_scale), vp(d_x), vp(d_out),
+                                          int(bool(accumulate))))
+
     # ---- phase functions on the device (phase:68-292) ----------------------------
     _KINDS ={"iso": _lib.PHASE_ISO, "rayleigh": _lib.PHASE_RAYLEIGH, "hg": _lib.PHASE_HG, "table": _lib.PHASE_TABLE}
 
