@@ -212,13 +212,6 @@ def _thermal_inputs(bands, temperature, surface_temperature, tauStar_aer, grd_al
             pc.get("surface_emissivity"))
 
 
-def _raise_status(status, N, max_orders):
-    if np.any(status == _lib.COL_INDEXERROR):
-        raise IndexError("index %d is out of bounds for axis 1 with size %d" % (2 * N, 2 * N))
-    if np.any(status != 0):
-        raise RuntimeError("columns did not converge within %d orders: status %s" % (max_orders, status))
-
-
 class _Sum:
     """The device side of a band sum: per-chunk epilogue buffers [P C, M] and the summed outputs [C, M]."""
 
@@ -227,7 +220,7 @@ class _Sum:
         width = lambda k: 1 if k == "net_toa" else L
         self.buf = {k: torch.empty((PC, width(k)), dtype=torch.float64, device=dev) for k in self.names}
         self.out = {k: torch.zeros((C, width(k)), dtype=torch.float64, device=dev) for k in self.names if k in want}
-        self.C = C
+        self.C, self.per_point = C, per_point
 
     def ptr(self, k):
         return self.buf[k].data_ptr() if k in self.buf else 0
@@ -239,6 +232,34 @@ class _Sum:
     def result(self):
         host = {k: v.cpu().numpy() for k, v in self.out.items()}
         return {k: (host[k][:, 0] if k == "net_toa" else host[k]) if k in host else None for k in WANT}
+
+
+def _sum_points(s, device, acc, P, d_weight, d_scale, solve_chunk, epilogue, N, max_orders):
+    """The chunk loop of both drivers: per chunk of P points `solve_chunk(k0, k1, B)` -> the tensors {"I", "n", "status",
+    "tau"} of its B = (k1 - k0) C columns, left on the device; then, with the handle `s` on torch's stream, `epilogue(d, acc,
+    B)` into the chunk buffers of `acc` and `band_reduce_device` with the weights d_weight [K, C] (and the scales d_scale
+    [K, C], or None), accumulating over the chunks -- the chunks run in ascending order, so the sum adds the points in
+    ascending order.  Any non-zero status raises (`N`, `max_orders`: for the message).  Returns (n [K, C], status [K, C], every
+    point's net_toa [K, C] or None); the summed arrays are `acc.result()`."""
+    import torch
+    (K, C), per_point = d_weight.shape, acc.per_point
+    n_all, st_all, net_all = [], [], []
+    for k0 in range(0, K, P):
+        k1 = min(K, k0 + P)
+        B = (k1 - k0) * C
+        d = solve_chunk(k0, k1, B)
+        with main._on_torch_stream(s, device):
+            epilogue(d, acc, B)
+            acc.reduce(s, k1 - k0, d_weight[k0:k1].data_ptr(), 0 if d_scale is None else d_scale[k0:k1].data_ptr(), k0 == 0)
+            if per_point:
+                net_all.append(acc.buf["net_toa"][:B, 0].clone())
+        n_all.append(d["n"])
+        st_all.append(d["status"])
+    n = torch.cat(n_all).cpu().numpy().reshape(K, C)
+    status = torch.cat(st_all).cpu().numpy().reshape(K, C)
+    main._raise_unconverged(status, N, max_orders)
+    point = torch.cat(net_all).cpu().numpy().reshape(K, C) if per_point else None
+    return n, status, point
 
 
 # ---- the thermal driver -------------------------------------------------------------------------------------------------------------
@@ -277,11 +298,9 @@ def band_thermal(bands, temperature, surface_temperature, tauStar_aer, grd_alb, 
     K, C = pp["weights"].shape
     P = _points_per_solve(points_per_solve, K, C, L, N)
     import torch
-    dev = torch.device("cuda", device)
     s = main.get_solver(L, N, P * C, max_orders, device)
-    up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)      # (a copy: broadcast inputs are read-only)
-    n_all, st_all, net_all = [], [], []
-    with torch.cuda.device(dev):
+    with main._on_torch_stream(s, device) as dev:
+        up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)      # (a copy: broadcast inputs are read-only)
         d_pl = torch.empty((K, C, L), dtype=torch.float64, device=dev)
         d_bs = torch.empty((K, C), dtype=torch.float64, device=dev)
         d_scale = torch.empty((K, C), dtype=torch.float64, device=dev)
@@ -289,49 +308,29 @@ def band_thermal(bands, temperature, surface_temperature, tauStar_aer, grd_alb, 
         d_es = None if es is None else up(np.tile(es, P))
         d_z = up(np.linspace(z0, 0, L)) if "heating_rate" in want else None
         acc = _Sum(torch, dev, want, per_point, P * C, C, L)
-        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        try:
-            s.planck_bands_device(d_T.data_ptr(), d_Ts.data_ptr(), lo, hi, d_pl.data_ptr(), d_bs.data_ptr(), d_scale.data_ptr(), C=C)
-        finally:
-            try:
-                s.synchronize()
-            finally:
-                s.set_stream(None)
-        scale = d_scale.cpu().numpy()
-        if not np.all(scale > 0):
-            k, c = [int(i) for i in np.argwhere(~(scale > 0))[0]]
-            raise ValueError("band %d = [%g, %g] cm^-1 has no Planck radiance in double precision at the temperatures of column %d "
-                             "(every value underflows to 0, scale = %r): there is no source to normalise; leave the band out"
-                             % (k, lo[k], hi[k], c, float(scale[k, c])))
-        for k0 in range(0, K, P):
-            k1 = min(K, k0 + P)
-            B = (k1 - k0) * C
-            flat = lambda a: a[k0:k1].reshape(B)
-            s, tau, _, _, _, _, _, _ = main._prepare_batch(
-                np.full(B, 0.5), flat(pp["tauStar_aer"]), np.tile(rho, k1 - k0), flat(pp["tauStar_atm"]), flat(pp["alb_atm"]),
-                flat(pp["alb_aer"]), z0, z_up, z_down, L, N, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm, mie_aer, None, None,
-                None, None, surface, max_orders, device)
-            d = main.solve_thermal(s, tau, d_pl[k0:k1].reshape(B, L), d_bs[k0:k1].reshape(B), None if d_es is None else d_es[:B],
-                                   tol=tol, keep_device=True, device=device)
-            s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-            try:
-                s.epilogue_emission_device(d["tau"].data_ptr(), d["I"].data_ptr(), 0 if d_z is None else d_z.data_ptr(),
-                                           acc.ptr("flux_down"), acc.ptr("flux_up"), 0, acc.ptr("heating_rate"), acc.ptr("net_toa"), B=B)
-                acc.reduce(s, k1 - k0, d_w[k0:k1].data_ptr(), d_scale[k0:k1].data_ptr(), k0 == 0)
-                if per_point:
-                    net_all.append(acc.buf["net_toa"][:B, 0].clone())
-            finally:
-                try:
-                    s.synchronize()
-                finally:
-                    s.set_stream(None)
-            n_all.append(d["n"])
-            st_all.append(d["status"])
-        n = torch.cat(n_all).cpu().numpy().reshape(K, C)
-        status = torch.cat(st_all).cpu().numpy().reshape(K, C)
-        _raise_status(status, N, max_orders)
-        point = torch.cat(net_all).cpu().numpy().reshape(K, C) * scale if per_point else None
-        return BandResult(n=n, status=status, scale=scale, point_net_toa=point, **acc.result())
+        s.planck_bands_device(d_T.data_ptr(), d_Ts.data_ptr(), lo, hi, d_pl.data_ptr(), d_bs.data_ptr(), d_scale.data_ptr(), C=C)
+    scale = d_scale.cpu().numpy()
+    if not np.all(scale > 0):
+        k, c = [int(i) for i in np.argwhere(~(scale > 0))[0]]
+        raise ValueError("band %d = [%g, %g] cm^-1 has no Planck radiance in double precision at the temperatures of column %d "
+                         "(every value underflows to 0, scale = %r): there is no source to normalise; leave the band out"
+                         % (k, lo[k], hi[k], c, float(scale[k, c])))
+
+    def solve_chunk(k0, k1, B):
+        flat = lambda a: a[k0:k1].reshape(B)
+        _, tau, _, _, _, _, _, _ = main._prepare_batch(
+            np.full(B, 0.5), flat(pp["tauStar_aer"]), np.tile(rho, k1 - k0), flat(pp["tauStar_atm"]), flat(pp["alb_atm"]),
+            flat(pp["alb_aer"]), z0, z_up, z_down, L, N, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm, mie_aer, None, None,
+            None, None, surface, max_orders, device)
+        return main.solve_thermal(s, tau, d_pl[k0:k1].reshape(B, L), d_bs[k0:k1].reshape(B), None if d_es is None else d_es[:B],
+                                  tol=tol, keep_device=True, device=device)
+
+    def epilogue(d, acc, B):
+        s.epilogue_emission_device(d["tau"].data_ptr(), d["I"].data_ptr(), 0 if d_z is None else d_z.data_ptr(),
+                                   acc.ptr("flux_down"), acc.ptr("flux_up"), 0, acc.ptr("heating_rate"), acc.ptr("net_toa"), B=B)
+
+    n, status, point = _sum_points(s, device, acc, P, d_w, d_scale, solve_chunk, epilogue, N, max_orders)
+    return BandResult(n=n, status=status, scale=scale, point_net_toa=None if point is None else point * scale, **acc.result())
 
 
 def band_thermal_forcing(bands, temperature, surface_temperature, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, alb_aer,
@@ -412,44 +411,29 @@ def band_solar(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, a
     K, C = pp["solar_flux"].shape
     P = _points_per_solve(points_per_solve, K, C, L, N)
     import torch
-    dev = torch.device("cuda", device)
     s = main.get_solver(L, N, P * C, max_orders, device)
+    dev = torch.device("cuda", device)
     up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)      # (a copy: broadcast inputs are read-only)
-    n_all, st_all, net_all = [], [], []
-    with torch.cuda.device(dev):
-        d_w = up(pp["solar_flux"])
-        d_z = up(np.linspace(z0, 0, L)) if "heating_rate" in want else None
-        acc = _Sum(torch, dev, want, per_point, P * C, C, L)
-        for k0 in range(0, K, P):
-            k1 = min(K, k0 + P)
-            B = (k1 - k0) * C
-            flat = lambda a: a[k0:k1].reshape(B)
-            tile = lambda a: np.tile(a, k1 - k0)
-            # (the handle's stream, its columns and their aerosol sets are solve_batch_device's to set and to put back)
-            d, _ = main.solve_batch_device(
-                tile(mu0c), flat(pp["tauStar_aer"]), tile(rho), tauStar_atm=flat(pp["tauStar_atm"]), alb_atm=flat(pp["alb_atm"]),
-                alb_aer=flat(pp["alb_aer"]), z0=z0, z_up=z_up, z_down=z_down, nb_layers=L, nb_angles=N, atm_phase_fun=atm_phase_fun,
-                g_atm=g_atm, aer_phase_fun=aer_phase_fun, g_aer=g_aer, mie_atm=mie_atm, mie_aer=mie_aer, surface=surface, tol=tol,
-                max_orders=max_orders, device=device, aer_set=None if sets is None else np.repeat(sets[k0:k1], C))
-            s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-            try:
-                s.epilogue_device(d["tau"].data_ptr(), d["I"].data_ptr(), 0 if d_z is None else d_z.data_ptr(), beam_norm,
-                                  acc.ptr("flux_down"), acc.ptr("flux_up"), 0, acc.ptr("heating_rate"), acc.ptr("net_toa"))
-                acc.reduce(s, k1 - k0, d_w[k0:k1].data_ptr(), 0, k0 == 0)
-                if per_point:
-                    net_all.append(acc.buf["net_toa"][:B, 0].clone())
-            finally:
-                try:
-                    s.synchronize()
-                finally:
-                    s.set_stream(None)
-            n_all.append(d["n"])
-            st_all.append(d["status"])
-        n = torch.cat(n_all).cpu().numpy().reshape(K, C)
-        status = torch.cat(st_all).cpu().numpy().reshape(K, C)
-        _raise_status(status, N, max_orders)
-        point = torch.cat(net_all).cpu().numpy().reshape(K, C) if per_point else None
-        return BandResult(n=n, status=status, point_net_toa=point, **acc.result())
+    d_w = up(pp["solar_flux"])
+    d_z = up(np.linspace(z0, 0, L)) if "heating_rate" in want else None
+    acc = _Sum(torch, dev, want, per_point, P * C, C, L)
+
+    def solve_chunk(k0, k1, B):
+        flat = lambda a: a[k0:k1].reshape(B)
+        tile = lambda a: np.tile(a, k1 - k0)
+        # (the handle's stream, its columns and their aerosol sets are solve_batch_device's to set and to put back)
+        return main.solve_batch_device(
+            tile(mu0c), flat(pp["tauStar_aer"]), tile(rho), tauStar_atm=flat(pp["tauStar_atm"]), alb_atm=flat(pp["alb_atm"]),
+            alb_aer=flat(pp["alb_aer"]), z0=z0, z_up=z_up, z_down=z_down, nb_layers=L, nb_angles=N, atm_phase_fun=atm_phase_fun,
+            g_atm=g_atm, aer_phase_fun=aer_phase_fun, g_aer=g_aer, mie_atm=mie_atm, mie_aer=mie_aer, surface=surface, tol=tol,
+            max_orders=max_orders, device=device, aer_set=None if sets is None else np.repeat(sets[k0:k1], C))[0]
+
+    def epilogue(d, acc, B):
+        s.epilogue_device(d["tau"].data_ptr(), d["I"].data_ptr(), 0 if d_z is None else d_z.data_ptr(), beam_norm,
+                          acc.ptr("flux_down"), acc.ptr("flux_up"), 0, acc.ptr("heating_rate"), acc.ptr("net_toa"))
+
+    n, status, point = _sum_points(s, device, acc, P, d_w, None, solve_chunk, epilogue, N, max_orders)
+    return BandResult(n=n, status=status, point_net_toa=point, **acc.result())
 
 
 def band_solar_forcing(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, alb_aer, beam_norm="crit",

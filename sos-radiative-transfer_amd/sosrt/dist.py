@@ -171,7 +171,7 @@ def solve_sharded(mu0, tauStar_aer, grd_alb, *, group=None, dst=0, device=None, 
 
     import torch
     import torch.distributed as dist
-    from .main import BatchResult, get_solver, solve_batch_device
+    from .main import BatchResult, _on_torch_stream, get_solver, solve_batch_device
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     cols = ("tauStar_atm", "alb_atm", "alb_aer")
     arrs = np.broadcast_arrays(*[np.atleast_1d(np.asarray(x, dtype=np.float64)) for x in
@@ -208,15 +208,13 @@ def solve_sharded(mu0, tauStar_aer, grd_alb, *, group=None, dst=0, device=None, 
     out = {}
     if gather == "abi":
         s = get_solver(L, N, max(1, len(mine)), int(kw.get("max_orders", 256)), device)
-        s.set_stream(torch.cuda.current_stream(tdev).cuda_stream)
-        _comm_for(s, group, dst)
-        # one float64 block per rank: field rows, then tau, order count and status of the column
-        pack = torch.cat([loc["I"].reshape(len(mine), -1), loc["tau"], loc["n"].to(torch.float64)[:, None],
-                          loc["status"].to(torch.float64)[:, None]], dim=1)
-        got = gather_rows(pack, plan, dst=dst, group=group, key="pack", via="abi", solver=s)
-        # the cached solver goes back to its own stream (as solve_batch_device leaves it), once the gather has left this one
-        torch.cuda.current_stream(tdev).synchronize()
-        s.set_stream(None)
+        # (the cached solver goes back to its own stream, as solve_batch_device leaves it, once the gather has left this one)
+        with _on_torch_stream(s, device):
+            _comm_for(s, group, dst)
+            # one float64 block per rank: field rows, then tau, order count and status of the column
+            pack = torch.cat([loc["I"].reshape(len(mine), -1), loc["tau"], loc["n"].to(torch.float64)[:, None],
+                              loc["status"].to(torch.float64)[:, None]], dim=1)
+            got = gather_rows(pack, plan, dst=dst, group=group, key="pack", via="abi", solver=s)
         if rank == dst:
             got = plan.restore(got)
             LD = L * 2 * N

@@ -19,9 +19,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib
 from .inputs import direction_grid, phase_function, slab_indices, tau_profile
-from .main import EARTH_RADIUS_KM, _beam_args, get_solver, solve_spherical
+from .main import EARTH_RADIUS_KM, _beam_args, _raise_unconverged, get_solver, solve_spherical
 
 
 def _net_flux_columns(tau, idx_up, idx_down, mu, mu0, grd_alb, alb_atm, alb_aer, dtau_atm, dtau_aer, tauStar_tot, P_atm, P_aer,
@@ -46,10 +45,7 @@ def _net_flux_columns(tau, idx_up, idx_down, mu, mu0, grd_alb, alb_atm, alb_aer,
                                     want=("net_toa",))
     else:
         r = s.solve(tau, P0a, P0r, fetch_field=False)
-    if np.any(r.status == _lib.COL_INDEXERROR):       # what the reference raises (spec:404)
-        raise IndexError("index %d is out of bounds for axis 1 with size %d" % (2 * N, 2 * N))
-    if np.any(r.status != 0):
-        raise RuntimeError("columns did not converge within %d orders: status %s" % (max_orders, r.status))
+    _raise_unconverged(r.status, N, max_orders)
     return epi["net_toa"] if spherical else s.epilogue(want=("net_toa",))["net_toa"]
 
 

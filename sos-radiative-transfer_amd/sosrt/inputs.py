@@ -173,11 +173,15 @@ def _scalar_phase(name, g=0.0, r=None, lambda0=None, indx=None, r_m=None, sig=No
             raise ValueError("'mie' needs r, lambda0 and indx")
         x = 2 * np.pi * r / lambda0
         mt = np.linspace(-1, 1, 6001)                       # phase:684-694 (compute_P's grid of scattering cosines)
-        if on_device:
-            pt = _on_device(device, lambda s: _mie.log_normal_bulk_phase_device(s, lambda0, complex(indx), nb_radius=1, r_min=r,
-                                                                                convention=indx_convention))[1]
-        else:
-            pt = _mie.i_unpolarized(complex(indx), x, mt, indx_convention)
+        # (cached like the scenario tables: the drivers resolve a phase function before every builder that reads its table)
+        key = ("mie", r, lambda0, complex(indx), indx_convention) + (("device",) if on_device else ())
+        if key not in _bulk_cache:
+            if on_device:
+                _bulk_cache[key] = _on_device(device, lambda s: _mie.log_normal_bulk_phase_device(
+                    s, lambda0, complex(indx), nb_radius=1, r_min=r, convention=indx_convention))[1]
+            else:
+                _bulk_cache[key] = _mie.i_unpolarized(complex(indx), x, mt, indx_convention)
+        pt = _bulk_cache[key]
         return (lambda c: interpolate_table(mt, pt, c)), ("table", (mt, pt))
     raise ValueError("unknown phase function %r" % (name,))
 

@@ -7,6 +7,7 @@ independent columns that share (nb_layers, nb_angles, phase matrices) in one lau
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from types import SimpleNamespace
 from typing import Optional
@@ -87,18 +88,56 @@ def _raise_status(status, nb_angles):
         raise RuntimeError("sosrt: internal error in the transport kernel (SOSRT_COL_INTERNAL)")
 
 
+@contextmanager
+def _on_torch_stream(s: Solver, device):
+    """The cached handle `s` on torch's current stream of cuda:`device`, that device made current: yields the torch device.  On
+    exit the stream is drained and the handle goes back to its own stream -- also when the body raises, and when the drain
+    itself raises (that error propagates).  What a driver has to put back on the handle besides comes after the scope, in a
+    `finally` of its own."""
+    import torch
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        try:
+            yield dev
+        finally:
+            # the solver is cached and goes back to its own stream: drain this one first, so that the handle's internal
+            # buffers are not reused under the last launches (the order loop has already waited for all but the last two)
+            try:
+                s.synchronize()
+            finally:
+                s.set_stream(None)
+
+
+def _phase_kind(s: Solver, name, g=0.0, mie=None):
+    """(kind, g) of a named phase function as the device builders of handle `s` take it; a Mie-derived one ('mie' / 'eva' /
+    'wildfire' / 'fwc') becomes the handle's table on the scattering cosine.  `device=True` in the `mie` dict: the table from
+    the Mie kernels of this handle."""
+    from .inputs import _scalar_phase
+    kw = dict(mie or {})
+    if kw.get("device") is True:
+        kw["device"] = s
+    kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **kw)[1]
+    if tab is not None:
+        s.set_phase_table(*tab)
+    return kind, g
+
+
+def _raise_unconverged(status, nb_angles, max_orders):
+    """The flux drivers (forcing, thermal, bands) sum or difference their columns, so any non-zero status raises: IndexError as
+    the reference does where its mu -> 0 search leaves the grid (spec:404), RuntimeError for anything else."""
+    if np.any(status == _lib.COL_INDEXERROR):
+        raise IndexError("index %d is out of bounds for axis 1 with size %d" % (2 * nb_angles, 2 * nb_angles))
+    if np.any(status != 0):
+        raise RuntimeError("columns did not converge within %d orders: status %s" % (max_orders, status))
+
+
 def device_phase(s: Solver, name, mu0, g=0.0, mie=None, matrix=True):
     """(P0 rows [len(mu0), 2N], P [2N, 2N] or None) of a named phase function, azimuth-averaged by the HIP kernels of solver
     `s` (phase:79-133 and its siblings; the grid must be set).  `mie` = dict(r=, lambda0=, indx=, r_m=, sig=) for 'mie' /
     'eva' / 'wildfire', whose phase function goes to the device as a table on the scattering cosine; `device=True` in that dict
     builds the table with the device's Mie kernels instead of the host series."""
-    from .inputs import _scalar_phase
-    kw = dict(mie or {})
-    if kw.get("device") is True:                             # device=True: the Mie table from the kernels of this handle
-        kw["device"] = s
-    kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **kw)[1]
-    if tab is not None:
-        s.set_phase_table(*tab)
+    kind, g = _phase_kind(s, name, g, mie)
     P0 = s.phase_p0(kind, mu0, g)
     return P0, (s.phase_matrix(kind, g) if matrix else None)
 
@@ -134,6 +173,66 @@ def _beam_args(beam, earth_radius, azimuths=None, view_mu=None, view_azimuths=No
     return True
 
 
+def _solve_resident(s: Solver, tau, P0a, P0r, seed, epilogue, tol=1e-4, save_orders=False, device=0, fetch_field=True, want=(),
+                    z_profile=None, keep_device=False):
+    """A solve of handle `s` (grid, phase matrices and columns set) that stays on the device, on torch's current stream: the
+    uploads, `seed(up, dev, d_tau, B, p0a, p0r)` -> (d_I1 [B, L, 2N] the field the order loop starts from, dict of further
+    tensors to return) or None for the handle's own first order, `solve_device` (with save_orders twice: the first pass gives
+    n, the second stores exactly max(n) orders per column, as Solver.solve), and for the names `want` of `Solver.epilogue`
+    (`z_profile` for the heating rate) `epilogue(d_tau, d_I, d_z, the seed's tensors, the five output addresses, B)`.  `P0a`, `P0r` may be None
+    (address 0).  Returns (SolveResult, the seed's tensors on the host, dict of the wanted epilogue arrays); keep_device=True:
+    the torch tensors {"I", "n", "status", "tau"} and the seed's instead, left on the device.  The handle goes back to its own
+    stream and to its default per-order storage, also on error."""
+    import torch
+    from .solver import SolveResult
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    B, L = tau.shape
+    D = s.D
+    try:
+        with _on_torch_stream(s, device) as dev:
+            def up(a):
+                # (a host copy only where torch could not take the array as it is: broadcast inputs are read-only)
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+            d_tau, d_P0a, d_P0r = up(tau), None if P0a is None else up(P0a), None if P0r is None else up(P0r)
+            p0a, p0r = 0 if d_P0a is None else d_P0a.data_ptr(), 0 if d_P0r is None else d_P0r.data_ptr()
+            d_I1, extra = (None, {}) if seed is None else seed(up, dev, d_tau, B, p0a, p0r)
+            d_I = torch.empty((B, L, D), dtype=torch.float64, device=dev)
+            d_n = torch.zeros(B, dtype=torch.int32, device=dev)
+            d_st = torch.zeros(B, dtype=torch.int32, device=dev)
+            solve = lambda d_sv: s.solve_device(d_tau.data_ptr(), p0a, p0r, d_I.data_ptr(), tol=tol,
+                                                d_I1=0 if d_I1 is None else d_I1.data_ptr(), d_I_saved=0 if d_sv is None else d_sv.data_ptr(),
+                                                d_n_orders=d_n.data_ptr(), d_status=d_st.data_ptr())
+            solve(None)
+            d_sv = None
+            if save_orders:
+                s.synchronize()
+                slots = int(max(1, d_n.max().item()))
+                s.set_saved_orders(slots)
+                d_sv = torch.zeros((B, slots, L, D), dtype=torch.float64, device=dev)
+                solve(d_sv)
+            epi = {}
+            want = [k for k in ("flux_down", "flux_up", "diffusivity", "heating_rate", "net_toa")
+                    if k in set(want) and not (k == "heating_rate" and z_profile is None)]
+            if want:
+                d_zp = None if z_profile is None else up(z_profile)
+                d_out = {k: torch.empty((B,) if k == "net_toa" else (B, L), dtype=torch.float64, device=dev) for k in want}
+                ptr = lambda k: d_out[k].data_ptr() if k in d_out else 0
+                epilogue(d_tau.data_ptr(), d_I.data_ptr(), 0 if d_zp is None else d_zp.data_ptr(), extra,
+                         (ptr("flux_down"), ptr("flux_up"), ptr("diffusivity"), ptr("heating_rate"), ptr("net_toa")), B)
+                s.synchronize()
+                epi = {k: v.cpu().numpy() for k, v in d_out.items()}
+            s.synchronize()
+            if keep_device:
+                return dict({"I": d_I, "n": d_n, "status": d_st, "tau": d_tau}, **extra)
+            r = SolveResult(I=d_I.cpu().numpy() if fetch_field else None, n=d_n.cpu().numpy(), status=d_st.cpu().numpy(),
+                            I_saved=None if d_sv is None else d_sv.cpu().numpy())
+            return r, {k: v.cpu().numpy() for k, v in extra.items()}, epi
+    finally:
+        if save_orders:
+            s.set_saved_orders(None)
+
+
 def solve_spherical(s: Solver, tau, P0a, P0r, z, earth_radius=EARTH_RADIUS_KM, tol=1e-4, save_orders=False, device=0,
                     fetch_field=True, want=(), z_profile=None, keep_device=False):
     """The solve of handle `s` (grid, phase matrices and columns set) with the PSEUDO-SPHERICAL DIRECT BEAM:
@@ -144,60 +243,20 @@ def solve_spherical(s: Solver, tau, P0a, P0r, z, earth_radius=EARTH_RADIUS_KM, t
     dict of the wanted epilogue arrays); keep_device=True: the torch tensors {"I", "n", "status", "tau", "beam_slant"}
     instead, left on the device.  The handle goes back to its own stream and to its default per-order storage, also on error."""
     import torch
-    from .solver import SolveResult
-    tau = np.ascontiguousarray(tau, dtype=np.float64)
-    B, L = tau.shape
-    D = s.D
-    dev = torch.device("cuda", device)
-    with torch.cuda.device(dev):
-        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        try:
-            up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)    # (a copy: broadcast inputs are read-only)
-            d_tau, d_z, d_P0a, d_P0r = up(tau), up(z), up(P0a), up(P0r)
-            d_sig = torch.empty((B, L), dtype=torch.float64, device=dev)
-            d_I1 = torch.empty((B, L, D), dtype=torch.float64, device=dev)
-            d_I = torch.empty((B, L, D), dtype=torch.float64, device=dev)
-            d_n = torch.zeros(B, dtype=torch.int32, device=dev)
-            d_st = torch.zeros(B, dtype=torch.int32, device=dev)
-            s.beam_slant_device(d_tau.data_ptr(), d_z.data_ptr(), d_sig.data_ptr(), earth_radius, B=B)
-            s.first_order_beam_device(d_tau.data_ptr(), d_sig.data_ptr(), d_P0a.data_ptr(), d_P0r.data_ptr(), d_I1.data_ptr(), B=B)
-            s.solve_device(d_tau.data_ptr(), d_P0a.data_ptr(), d_P0r.data_ptr(), d_I.data_ptr(), tol=tol, d_I1=d_I1.data_ptr(),
-                           d_n_orders=d_n.data_ptr(), d_status=d_st.data_ptr())
-            d_sv = None
-            if save_orders:
-                # (as Solver.solve: the first pass gives n, the second stores exactly max(n) orders per column)
-                s.synchronize()
-                slots = int(max(1, d_n.max().item()))
-                s.set_saved_orders(slots)
-                d_sv = torch.zeros((B, slots, L, D), dtype=torch.float64, device=dev)
-                s.solve_device(d_tau.data_ptr(), d_P0a.data_ptr(), d_P0r.data_ptr(), d_I.data_ptr(), tol=tol, d_I1=d_I1.data_ptr(),
-                               d_I_saved=d_sv.data_ptr(), d_n_orders=d_n.data_ptr(), d_status=d_st.data_ptr())
-            epi = {}
-            want = [k for k in ("flux_down", "flux_up", "diffusivity", "heating_rate", "net_toa")
-                    if k in set(want) and not (k == "heating_rate" and z_profile is None)]
-            if want:
-                d_zp = None if z_profile is None else up(z_profile)
-                d_out = {k: torch.empty((B,) if k == "net_toa" else (B, L), dtype=torch.float64, device=dev) for k in want}
-                ptr = lambda k: d_out[k].data_ptr() if k in d_out else 0
-                s.epilogue_beam_device(d_tau.data_ptr(), d_I.data_ptr(), d_sig.data_ptr(), 0 if d_zp is None else d_zp.data_ptr(),
-                                       "crit", ptr("flux_down"), ptr("flux_up"), ptr("diffusivity"), ptr("heating_rate"),
-                                       ptr("net_toa"), B=B)
-                s.synchronize()
-                epi = {k: v.cpu().numpy() for k, v in d_out.items()}
-            s.synchronize()
-            if keep_device:
-                return {"I": d_I, "n": d_n, "status": d_st, "tau": d_tau, "beam_slant": d_sig}
-            r = SolveResult(I=d_I.cpu().numpy() if fetch_field else None, n=d_n.cpu().numpy(), status=d_st.cpu().numpy(),
-                            I_saved=None if d_sv is None else d_sv.cpu().numpy())
-            return r, d_sig.cpu().numpy(), epi
-        finally:
-            # the solver is cached and goes back to its own stream: drain this one first
-            try:
-                s.synchronize()
-            finally:
-                if save_orders:
-                    s.set_saved_orders(None)
-                s.set_stream(None)
+
+    def seed(up, dev, d_tau, B, p0a, p0r):
+        d_z = up(z)
+        d_sig = torch.empty((B, d_tau.shape[1]), dtype=torch.float64, device=dev)
+        d_I1 = torch.empty((B, d_tau.shape[1], s.D), dtype=torch.float64, device=dev)
+        s.beam_slant_device(d_tau.data_ptr(), d_z.data_ptr(), d_sig.data_ptr(), earth_radius, B=B)
+        s.first_order_beam_device(d_tau.data_ptr(), d_sig.data_ptr(), p0a, p0r, d_I1.data_ptr(), B=B)
+        return d_I1, {"beam_slant": d_sig}
+
+    def epilogue(d_tau, d_I, d_zp, extra, out, B):
+        s.epilogue_beam_device(d_tau, d_I, extra["beam_slant"].data_ptr(), d_zp, "crit", *out, B=B)
+
+    r = _solve_resident(s, tau, P0a, P0r, seed, epilogue, tol, save_orders, device, fetch_field, want, z_profile, keep_device)
+    return r if keep_device else (r[0], r[1]["beam_slant"], r[2])
 
 
 def _thermal_args(source, planck, planck_surface, surface_emissivity, B, nb_layers, azimuths=None, view_azimuths=None,
@@ -241,12 +300,19 @@ def _thermal_args(source, planck, planck_surface, surface_emissivity, B, nb_laye
     return full(pl, (B, L)), full(bs, (B,)), None if es is None else full(es, (B,))
 
 
-def _batch_width(*cols):
-    """Columns of a batch whose per-column arguments broadcast to a common length."""
+def _broadcast_columns(*cols):
+    """The per-column arguments of a batch (scalars or arrays) as float64 arrays of their common length (views: nothing is
+    copied)."""
+    cols = [np.atleast_1d(np.asarray(x, dtype=np.float64)) for x in cols]
     try:
-        return int(np.broadcast_shapes(*[np.shape(np.atleast_1d(np.asarray(x))) for x in cols])[0])
+        return np.broadcast_arrays(*cols)
     except ValueError:
         raise ValueError("the per-column arguments do not broadcast to a common length") from None
+
+
+def _batch_width(*cols):
+    """Columns of a batch whose per-column arguments broadcast to a common length."""
+    return int(_broadcast_columns(*cols)[0].shape[0])
 
 
 def solve_thermal(s: Solver, tau, planck, planck_surface, emissivity=None, tol=1e-4, save_orders=False, want=(), z_profile=None,
@@ -260,68 +326,28 @@ def solve_thermal(s: Solver, tau, planck, planck_surface, emissivity=None, tol=1
     tensors {"I", "n", "status", "tau"} instead, left on the device.  The handle goes back to its own stream and to its default
     per-order storage, also on error."""
     import torch
-    from .solver import SolveResult
-    tau = np.ascontiguousarray(tau, dtype=np.float64)
-    B, L = tau.shape
-    D = s.D
-    dev = torch.device("cuda", device)
-    with torch.cuda.device(dev):
-        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        try:
-            up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)    # (a copy: broadcast inputs are read-only)
-            def src(a, shape, name):
-                # a torch tensor on the device is used where it lies (sosrt.bands builds the sources there); NumPy is uploaded
-                if not isinstance(a, torch.Tensor):
-                    return up(np.broadcast_to(a, shape))
-                if a.device != dev or a.dtype != torch.float64 or tuple(a.shape) != shape:
-                    raise ValueError("%s as a torch tensor must be float64 %s on %s (got %s %s on %s)"
-                                     % (name, shape, dev, a.dtype, tuple(a.shape), a.device))
-                return a.contiguous()
-            d_tau, d_pl, d_bs = up(tau), src(planck, (B, L), "planck"), src(planck_surface, (B,), "planck_surface")
-            d_es = None if emissivity is None else src(emissivity, (B,), "surface_emissivity")
-            d_I0 = torch.empty((B, L, D), dtype=torch.float64, device=dev)
-            d_I = torch.empty((B, L, D), dtype=torch.float64, device=dev)
-            d_n = torch.zeros(B, dtype=torch.int32, device=dev)
-            d_st = torch.zeros(B, dtype=torch.int32, device=dev)
-            s.emission_device(d_tau.data_ptr(), d_pl.data_ptr(), d_bs.data_ptr(), d_I0.data_ptr(),
-                              0 if d_es is None else d_es.data_ptr(), B=B)
-            s.solve_device(d_tau.data_ptr(), 0, 0, d_I.data_ptr(), tol=tol, d_I1=d_I0.data_ptr(), d_n_orders=d_n.data_ptr(),
-                           d_status=d_st.data_ptr())
-            d_sv = None
-            if save_orders:
-                # (as Solver.solve: the first pass gives n, the second stores exactly max(n) orders per column)
-                s.synchronize()
-                slots = int(max(1, d_n.max().item()))
-                s.set_saved_orders(slots)
-                d_sv = torch.zeros((B, slots, L, D), dtype=torch.float64, device=dev)
-                s.solve_device(d_tau.data_ptr(), 0, 0, d_I.data_ptr(), tol=tol, d_I1=d_I0.data_ptr(), d_I_saved=d_sv.data_ptr(),
-                               d_n_orders=d_n.data_ptr(), d_status=d_st.data_ptr())
-            epi = {}
-            want = [k for k in ("flux_down", "flux_up", "diffusivity", "heating_rate", "net_toa")
-                    if k in set(want) and not (k == "heating_rate" and z_profile is None)]
-            if want:
-                d_zp = None if z_profile is None else up(z_profile)
-                d_out = {k: torch.empty((B,) if k == "net_toa" else (B, L), dtype=torch.float64, device=dev) for k in want}
-                ptr = lambda k: d_out[k].data_ptr() if k in d_out else 0
-                s.epilogue_emission_device(d_tau.data_ptr(), d_I.data_ptr(), 0 if d_zp is None else d_zp.data_ptr(),
-                                           ptr("flux_down"), ptr("flux_up"), ptr("diffusivity"), ptr("heating_rate"),
-                                           ptr("net_toa"), B=B)
-                s.synchronize()
-                epi = {k: v.cpu().numpy() for k, v in d_out.items()}
-            s.synchronize()
-            if keep_device:
-                return {"I": d_I, "n": d_n, "status": d_st, "tau": d_tau}
-            r = SolveResult(I=d_I.cpu().numpy() if fetch_field else None, n=d_n.cpu().numpy(), status=d_st.cpu().numpy(),
-                            I_saved=None if d_sv is None else d_sv.cpu().numpy())
-            return r, epi
-        finally:
-            # the solver is cached and goes back to its own stream: drain this one first
-            try:
-                s.synchronize()
-            finally:
-                if save_orders:
-                    s.set_saved_orders(None)
-                s.set_stream(None)
+
+    def seed(up, dev, d_tau, B, p0a, p0r):
+        def src(a, shape, name):
+            # a torch tensor on the device is used where it lies (sosrt.bands builds the sources there); NumPy is uploaded
+            if not isinstance(a, torch.Tensor):
+                return up(np.broadcast_to(a, shape))
+            if a.device != dev or a.dtype != torch.float64 or tuple(a.shape) != shape:
+                raise ValueError("%s as a torch tensor must be float64 %s on %s (got %s %s on %s)"
+                                 % (name, shape, dev, a.dtype, tuple(a.shape), a.device))
+            return a.contiguous()
+        L = d_tau.shape[1]
+        d_pl, d_bs = src(planck, (B, L), "planck"), src(planck_surface, (B,), "planck_surface")
+        d_es = None if emissivity is None else src(emissivity, (B,), "surface_emissivity")
+        d_I0 = torch.empty((B, L, s.D), dtype=torch.float64, device=dev)
+        s.emission_device(d_tau.data_ptr(), d_pl.data_ptr(), d_bs.data_ptr(), d_I0.data_ptr(), 0 if d_es is None else d_es.data_ptr(), B=B)
+        return d_I0, {}
+
+    def epilogue(d_tau, d_I, d_zp, extra, out, B):
+        s.epilogue_emission_device(d_tau, d_I, d_zp, *out, B=B)
+
+    r = _solve_resident(s, tau, None, None, seed, epilogue, tol, save_orders, device, fetch_field, want, z_profile, keep_device)
+    return r if keep_device else (r[0], r[2])
 
 
 def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, alb_aer=1.0, z0=120, z_up=25, z_down=17,
@@ -445,8 +471,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         device = int(devices[0])
     if azimuths is not None and mode_batch:
         # the handle that serves the mode-0 solve below is the one that takes the batch of c x B columns: made wide enough here
-        cols = np.broadcast_arrays(*[np.atleast_1d(np.asarray(x, dtype=np.float64))
-                                     for x in (mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer)])
+        cols = _broadcast_columns(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer)
         c_cap = _mode_chunk_cap(cols[0].shape[0], int(nb_layers), int(nb_angles), M, mode_chunk)
         get_solver(int(nb_layers), int(nb_angles), c_cap * cols[0].shape[0], max_orders, device)
     s, tau, P0a, P0r, mu, iu, idn, N = _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
@@ -499,6 +524,34 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     return out
 
 
+def _mode_counts(n_modes, nphi_modes):
+    """(M, nphi) of a call that sums Fourier modes: n_modes (default 16) and the azimuth nodes its modes are built on."""
+    M = 16 if n_modes is None else int(n_modes)
+    if not 1 <= M <= _lib.MAX_MODES:
+        raise ValueError("n_modes must be in 1..%d (got %d)" % (_lib.MAX_MODES, M))
+    nphi = max(25, 2 * M + 1) if nphi_modes is None else int(nphi_modes)
+    if M > nphi - 2:
+        raise ValueError("n_modes = %d needs nphi_modes >= %d (got %d)" % (M, M + 2, nphi))
+    return M, nphi
+
+
+def _level_rows(levels, nb_layers, keyword):
+    """The rows of the keyword `keyword` (`levels` / `view_levels`) as indices from the top: negative ones count from the ground."""
+    L = int(nb_layers)
+    lev = [int(x) for x in np.atleast_1d(levels)]
+    if not lev or any(not -L <= x < L for x in lev):
+        raise ValueError("%s must be row indices in [-%d, %d)" % (keyword, L, L))
+    return [x + L if x < 0 else x for x in lev]
+
+
+def _angle_array(angles, keyword):
+    """The azimuths of the keyword `keyword` (`azimuths` / `view_azimuths`) as a float64 array."""
+    phi = np.asarray(angles, dtype=np.float64)
+    if phi.ndim != 1 or phi.size == 0 or not np.all(np.isfinite(phi)):
+        raise ValueError("%s must be a non-empty 1-d array of finite angles (radians)" % keyword)
+    return phi
+
+
 def _view_args(view_mu, view_levels, view_quadrature, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface, devices, first_order,
                azimuths, aer_set, atm_phase_fun, aer_phase_fun):
     """Checks of the view-radiance call, made before any handle exists: (view_mu [V], levels as row indices, quadrature)."""
@@ -523,11 +576,7 @@ def _view_args(view_mu, view_levels, view_quadrature, nb_layers, P_atm, P_aer, P
         raise ValueError("view_mu must hold 1..%d cosines" % _lib.MAX_VIEWS)
     if not np.all(np.isfinite(vmu)) or np.any(vmu < 0.01) or np.any(vmu > 1):
         raise ValueError("view_mu must be finite cosines in [0.01, 1]")
-    L = int(nb_layers)
-    lev = [int(x) for x in np.atleast_1d(view_levels)]
-    if not lev or any(not -L <= x < L for x in lev):
-        raise ValueError("view_levels must be row indices in [-%d, %d)" % (L, L))
-    return vmu, [x + L if x < 0 else x for x in lev], view_quadrature
+    return vmu, _level_rows(view_levels, nb_layers, "view_levels"), view_quadrature
 
 
 def _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_modes, nphi_modes, mode_batch, mode_chunk):
@@ -543,16 +592,7 @@ def _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_mod
         raise ValueError("view_azimuths are not available with azimuths (one mode loop serves one of them)")
     if mode_batch or mode_chunk is not None:
         raise ValueError("view_azimuths are not available with mode_batch / mode_chunk (the view stage reads one mode's resident field)")
-    phi = np.asarray(view_azimuths, dtype=np.float64)
-    if phi.ndim != 1 or phi.size == 0 or not np.all(np.isfinite(phi)):
-        raise ValueError("view_azimuths must be a non-empty 1-d array of finite angles (radians)")
-    M = 16 if n_modes is None else int(n_modes)
-    if not 1 <= M <= _lib.MAX_MODES:
-        raise ValueError("n_modes must be in 1..%d (got %d)" % (_lib.MAX_MODES, M))
-    nphi = max(25, 2 * M + 1) if nphi_modes is None else int(nphi_modes)
-    if M > nphi - 2:
-        raise ValueError("n_modes = %d needs nphi_modes >= %d (got %d)" % (M, M + 2, nphi))
-    return phi, M, nphi
+    return (_angle_array(view_azimuths, "view_azimuths"),) + _mode_counts(n_modes, nphi_modes)
 
 
 def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
@@ -562,53 +602,41 @@ def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase
     `thermal` = (planck [B, L], planck_surface [B], emissivity [B] or None): I is a thermal field, and the first term is the
     emission at the view lanes (`Solver.emission_view_device`) instead of the solar first order."""
     import torch
-    from .inputs import _scalar_phase
     B, L = tau.shape
     D, V2 = s.D, 2 * len(view_mu)
     sgn = np.concatenate((-view_mu, view_mu))
-    dev = torch.device("cuda", device)
-    with torch.cuda.device(dev):
-        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        try:
-            d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
-            d_I = torch.from_numpy(np.ascontiguousarray(I)).to(dev)
-            d_mu0 = torch.from_numpy(np.array(mu0, dtype=np.float64)).to(dev)
-            rows, p0rows = [], []
-            for name, g, mie in ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)):
-                kw = dict(mie or {})
-                if kw.get("device") is True:                 # (as `device_phase`: the Mie table from this handle's kernels)
-                    kw["device"] = s
-                kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **kw)[1]
-                if tab is not None:
-                    s.set_phase_table(*tab)
-                rw = torch.empty((V2, D), dtype=torch.float64, device=dev)
-                p0 = torch.empty((B, V2), dtype=torch.float64, device=dev)
-                torch.cuda.current_stream(dev).synchronize()
-                s.phase_rows_device(kind, sgn, rw.data_ptr(), g)
-                s.phase_p0_rows_device(kind, d_mu0.data_ptr(), sgn, p0.data_ptr(), B, g)
-                rows.append(rw)
-                p0rows.append(p0)
-            d_scat = torch.empty((B, len(levels), V2), dtype=torch.float64, device=dev)
-            d_first = torch.empty((B, len(levels), V2), dtype=torch.float64, device=dev)
+    with _on_torch_stream(s, device) as dev:
+        up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)    # (a copy: broadcast inputs are read-only)
+        # (the field is large and already contiguous: uploaded from where it lies, not through a host copy)
+        d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
+        d_I = torch.from_numpy(np.ascontiguousarray(I)).to(dev)
+        d_mu0 = up(mu0)
+        rows, p0rows = [], []
+        for phase in ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)):
+            kind, g = _phase_kind(s, *phase)
+            rw = torch.empty((V2, D), dtype=torch.float64, device=dev)
+            p0 = torch.empty((B, V2), dtype=torch.float64, device=dev)
             torch.cuda.current_stream(dev).synchronize()
-            if thermal is not None:
-                up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)
-                d_pl, d_bs = up(thermal[0]), up(thermal[1])
-                d_es = None if thermal[2] is None else up(thermal[2])
-                s.emission_view_device(view_mu, d_tau.data_ptr(), d_pl.data_ptr(), d_bs.data_ptr(), levels, d_first.data_ptr(),
-                                       0 if d_es is None else d_es.data_ptr(), B=B)
-                s.view_radiance_device(view_mu, d_tau.data_ptr(), d_I.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), levels,
-                                       d_scat_out=d_scat.data_ptr(), quadrature=quadrature, B=B)
-                s.synchronize()
-                return d_first.cpu().numpy(), d_scat.cpu().numpy()
-            s.view_radiance_device(view_mu, d_tau.data_ptr(), d_I.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), levels,
-                                   d_scat_out=d_scat.data_ptr(), d_first_out=d_first.data_ptr(), d_p0rows_atm=p0rows[0].data_ptr(),
-                                   d_p0rows_aer=p0rows[1].data_ptr(), quadrature=quadrature, B=B)
-            s.synchronize()
-            return d_first.cpu().numpy(), d_scat.cpu().numpy()
-        finally:
-            s.synchronize()
-            s.set_stream(None)
+            s.phase_rows_device(kind, sgn, rw.data_ptr(), g)
+            s.phase_p0_rows_device(kind, d_mu0.data_ptr(), sgn, p0.data_ptr(), B, g)
+            rows.append(rw)
+            p0rows.append(p0)
+        d_scat = torch.empty((B, len(levels), V2), dtype=torch.float64, device=dev)
+        d_first = torch.empty((B, len(levels), V2), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        first, p0_atm, p0_aer = d_first.data_ptr(), p0rows[0].data_ptr(), p0rows[1].data_ptr()
+        if thermal is not None:
+            # the first term is the emission at the lanes: the view stage gets no first-order addresses and leaves it alone
+            d_pl, d_bs = up(thermal[0]), up(thermal[1])
+            d_es = None if thermal[2] is None else up(thermal[2])
+            s.emission_view_device(view_mu, d_tau.data_ptr(), d_pl.data_ptr(), d_bs.data_ptr(), levels, first,
+                                   0 if d_es is None else d_es.data_ptr(), B=B)
+            first = p0_atm = p0_aer = 0
+        s.view_radiance_device(view_mu, d_tau.data_ptr(), d_I.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), levels,
+                               d_scat_out=d_scat.data_ptr(), d_first_out=first, d_p0rows_atm=p0_atm, d_p0rows_aer=p0_aer,
+                               quadrature=quadrature, B=B)
+        s.synchronize()
+        return d_first.cpu().numpy(), d_scat.cpu().numpy()
 
 
 def _columns_to_set0(s, B):
@@ -752,20 +780,8 @@ def _azimuth_args(azimuths, n_modes, nphi_modes, levels, nb_layers, P_atm, P_aer
         raise ValueError("azimuths are available with the specular surface only (the Lambertian terms of modes m >= 1 are not built)")
     if devices is not None and len(devices) > 1:
         raise ValueError("azimuths are not available with devices=[...]")
-    phi = np.asarray(azimuths, dtype=np.float64)
-    if phi.ndim != 1 or phi.size == 0 or not np.all(np.isfinite(phi)):
-        raise ValueError("azimuths must be a non-empty 1-d array of finite angles (radians)")
-    M = 16 if n_modes is None else int(n_modes)
-    if not 1 <= M <= _lib.MAX_MODES:
-        raise ValueError("n_modes must be in 1..%d (got %d)" % (_lib.MAX_MODES, M))
-    nphi = max(25, 2 * M + 1) if nphi_modes is None else int(nphi_modes)
-    if M > nphi - 2:
-        raise ValueError("n_modes = %d needs nphi_modes >= %d (got %d)" % (M, M + 2, nphi))
-    L = int(nb_layers)
-    lev = [int(x) for x in np.atleast_1d(levels)]
-    if not lev or any(not -L <= x < L for x in lev):
-        raise ValueError("levels must be row indices in [-%d, %d)" % (L, L))
-    return M, nphi, [x + L if x < 0 else x for x in lev]
+    _angle_array(azimuths, "azimuths")
+    return _mode_counts(n_modes, nphi_modes) + (_level_rows(levels, nb_layers, "levels"),)
 
 
 @dataclass
@@ -778,53 +794,40 @@ class _ModeLoop:
     D: int
     M: int
     nphi: int
-    kinds: list              # per phase function (atmosphere, aerosol): (device kind, g); its table, if any, is `tables[i]`
-    tables: list
+    phases: tuple            # ((name, g, mie) of the atmosphere, of the aerosol): what `_phase_kind` takes before a builder
     d_tau: object = None     # [B, L]
     d_mu0: object = None     # [B]
     d_Im: object = None      # [B, L, 2N]: set by `begin` to the mode-0 field; after the solve of mode m, the field of mode m
     own: SimpleNamespace = field(default_factory=SimpleNamespace)
 
 
-def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, finish, mie_on_handle=False):
+def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, finish):
     """The loop over the Fourier modes m = 1..M of the solve `r` (the mode-0 result of handle `s`, whose columns are set): per
     mode the matrices and first-order vectors of both phase functions `phases` = ((name, g, mie) of the atmosphere, of the
     aerosol), a solve with the order counts of mode 0 (sosrt_set_order_targets) into the resident c.d_Im, then `step(c, m)`.
-    The phase functions are resolved once, here (c.kinds, c.tables: what every builder of the loop and of the steps takes);
-    mie_on_handle: `device=True` in a `mie` dict means this handle's Mie kernels, as `device_phase` reads it.  `begin(c)` runs
+    Every builder of the loop and of the steps resolves its phase function with `_phase_kind` (c.phases), which puts a
+    Mie-derived function's table on the handle first: the handle holds one table at a time.  `begin(c)` runs
     before the modes are built and sets c.d_Im to the mode-0 field; `finish(c)` after the last mode, and its value is returned
     with the mode status [M + 1, B].  The handle's mode-0 phase matrices are put back and its targets cleared afterwards, also
     on error."""
     import torch
-    from .inputs import _scalar_phase
     B, L = tau.shape
     D = s.D
-    dev = torch.device("cuda", device)
     P_mode0 = s._P
     status = np.zeros((M + 1, B), dtype=np.int32)
     status[0] = r.status
-    with torch.cuda.device(dev):
-        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        try:
-            kinds, tables = [], []
-            for name, g, mie in phases:
-                kw = dict(mie or {})
-                if mie_on_handle and kw.get("device") is True:
-                    kw["device"] = s
-                kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **kw)[1]
-                kinds.append((kind, g))
-                tables.append(tab)
-            c = _ModeLoop(dev=dev, B=B, L=L, D=D, M=M, nphi=nphi, kinds=kinds, tables=tables)
+    try:
+        with _on_torch_stream(s, device) as dev:
+            c = _ModeLoop(dev=dev, B=B, L=L, D=D, M=M, nphi=nphi, phases=tuple(phases))
             c.d_tau = d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
-            c.d_mu0 = d_mu0 = torch.from_numpy(np.ascontiguousarray(mu0, dtype=np.float64)).to(dev)
+            c.d_mu0 = d_mu0 = torch.from_numpy(np.array(mu0, dtype=np.float64)).to(dev)      # (a copy: broadcast views are read-only)
             d_target = torch.from_numpy(np.ascontiguousarray(r.n, dtype=np.int32)).to(dev)
             begin(c)
             # modes m >= 1 of both phase functions: the matrices to the host (one fold each in set_phase), the first-order
             # vectors where the solve reads them
             Pm, d_P0 = [], []
-            for (kind, g), tab in zip(kinds, tables):
-                if tab is not None:
-                    s.set_phase_table(*tab)
+            for phase in c.phases:
+                kind, g = _phase_kind(s, *phase)
                 Pm.append(s.phase_modes(kind, 1, M, nphi, g))
                 p0 = torch.empty((M, B, D), dtype=torch.float64, device=dev)
                 s.phase_p0_modes_device(kind, d_mu0.data_ptr(), p0.data_ptr(), B, 1, M, nphi, g)
@@ -843,12 +846,10 @@ def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, f
             s.synchronize()
             status[1:] = d_st.cpu().numpy()
             result = finish(c)
-        finally:
-            s.synchronize()
-            s.set_order_targets(None)
-            s.set_stream(None)
-            if P_mode0[0] is not None:
-                s.set_phase(*P_mode0)
+    finally:
+        s.set_order_targets(None)
+        if P_mode0[0] is not None:
+            s.set_phase(*P_mode0)
     return result, status
 
 
@@ -898,9 +899,8 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
         o.d_phi = torch.from_numpy(np.ascontiguousarray(azimuths, dtype=np.float64)).to(dev)
         o.rows, o.p0rows, o.p0exact = [], [], []
         # (the handle runs on torch's current stream here: the builders are ordered after the allocations and uploads)
-        for (kind, g), tab in zip(c.kinds, c.tables):
-            if tab is not None:
-                s.set_phase_table(*tab)
+        for phase in c.phases:
+            kind, g = _phase_kind(s, *phase)
             rw = torch.empty((M, V2, c.D), dtype=torch.float64, device=dev)
             s.phase_rows_modes_device(kind, sgn, rw.data_ptr(), 1, M, nphi, g, sign_odd=True)
             o.rows.append(rw)
@@ -949,7 +949,7 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
         return first, o.d_out_scat.cpu().numpy()
 
     (first, scat), status = _solve_modes(s, tau, r, mu0, M, nphi, ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)),
-                                         device, begin, step, finish, mie_on_handle=True)
+                                         device, begin, step, finish)
     return first, scat, status
 
 
@@ -988,10 +988,8 @@ def azimuth_modes_batched(s: Solver, tau, r, colargs, azimuths, M, nphi, levels,
     value, same bits.  c = min(c_cap, cache of combined matrices // distinct slab coefficient pairs of the B columns).  The
     handle's columns, mode-0 matrices and targets are put back afterwards, also on error."""
     import torch
-    from .inputs import _scalar_phase
     B, L = tau.shape
     D = s.D
-    dev = torch.device("cuda", device)
     P_mode0 = s._P
     status = np.zeros((M + 1, B), dtype=np.int32)
     status[0] = r.status
@@ -1004,9 +1002,8 @@ def azimuth_modes_batched(s: Solver, tau, r, colargs, azimuths, M, nphi, levels,
         raise ValueError("mode_batch=True: the %d distinct slab coefficient pairs of these columns do not fit the cache of %d combined "
                          "matrices even for one mode; mode_batch=False works" % (pairs, cache))
     tile = lambda v, k: np.tile(np.asarray(v), k)
-    with torch.cuda.device(dev):
-        s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        try:
+    try:
+        with _on_torch_stream(s, device) as dev:
             d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
             d_mu0 = torch.from_numpy(np.array(colargs[2], dtype=np.float64)).to(dev)      # (a copy: broadcast views are read-only)
             d_target = torch.from_numpy(np.ascontiguousarray(r.n, dtype=np.int32)).to(dev)
@@ -1021,10 +1018,8 @@ def azimuth_modes_batched(s: Solver, tau, r, colargs, azimuths, M, nphi, levels,
             d_P0 = []
             d_Paer = torch.empty((M, D, D), dtype=torch.float64, device=dev)
             torch.cuda.current_stream(dev).synchronize()
-            for which, (name, g, mie) in enumerate(((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer))):
-                kind, tab = ("iso", None) if name == "iso" else _scalar_phase(name, g, **(mie or {}))[1]
-                if tab is not None:
-                    s.set_phase_table(*tab)
+            for which, phase in enumerate(((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer))):
+                kind, g = _phase_kind(s, *phase)
                 if which == 0:
                     sgn = np.where(np.arange(1, M + 1) & 1, -1.0, 1.0)[:, None, None]
                     P_atm_m = sgn * s.phase_modes(kind, 1, M, nphi, g)
@@ -1058,14 +1053,12 @@ def azimuth_modes_batched(s: Solver, tau, r, colargs, azimuths, M, nphi, levels,
             s.synchronize()
             status[1:] = d_st.cpu().numpy()
             I_az = d_out.cpu().numpy()
-        finally:
-            s.synchronize()
-            s.set_order_targets(None)
-            s.set_stream(None)
-            # the cached handle as the plain call left it: its B columns (on set 0 of both kinds), then the mode-0 matrices
-            s.set_columns(*colargs)
-            if P_mode0[0] is not None:
-                s.set_phase(*P_mode0)
+    finally:
+        s.set_order_targets(None)
+        # the cached handle as the plain call left it: its B columns (on set 0 of both kinds), then the mode-0 matrices
+        s.set_columns(*colargs)
+        if P_mode0[0] is not None:
+            s.set_phase(*P_mode0)
     return I_az, status
 
 
@@ -1074,8 +1067,8 @@ def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0,
                    max_orders, device, p0_on_host=True, aer_set=None):
     """Everything before the order loop (spec:23-96): optical-depth grids, direction grid, phase matrices folded into the
     handle, per-column scalars.  Returns the solver and the per-column inputs."""
-    mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer = np.broadcast_arrays(
-        *[np.atleast_1d(np.asarray(x, dtype=np.float64)) for x in (mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer)])
+    mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer = _broadcast_columns(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm,
+                                                                                  alb_aer)
     B = mu0.shape[0]
     L, N = int(nb_layers), int(nb_angles)
     if z_down > z_up:
@@ -1125,27 +1118,24 @@ def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0,
             P_aer = np.stack(built)
         if P0_aer is not None:
             P0r = np.ascontiguousarray(P0_aer, dtype=np.float64)
-        if P0_atm is not None:
-            P0a = np.ascontiguousarray(np.broadcast_to(P0_atm, (B, 2 * N)))
         if on_device:
             s.set_phase_sets_device(P_atm, P_aer.address, P_aer.S)
         elif not s.same_phase(P_atm, P_aer):
             s.set_phase_sets(P_atm, P_aer)
-        s.set_columns(np.full(B, iu), np.full(B, idn), mu0, grd_alb, alb_atm, alb_aer,
-                      tauStar_atm / L, tauStar_aer / (idn + 1 - iu), tauStar_atm + tauStar_aer, surface=surface)
-        s.set_aerosol_sets(sets.astype(np.int32))
-        return s, tau, P0a, P0r, mu, iu, idn, N
-    if P_aer is None or P0_aer is None:
-        P0r, Pm = device_phase(s, aer_phase_fun, mu0, g_aer, mie_aer, matrix=P_aer is None)
-        P_aer = Pm if P_aer is None else P_aer
+    else:
+        if P_aer is None or P0_aer is None:
+            P0r, Pm = device_phase(s, aer_phase_fun, mu0, g_aer, mie_aer, matrix=P_aer is None)
+            P_aer = Pm if P_aer is None else P_aer
+        if P0_aer is not None:
+            P0r = np.ascontiguousarray(np.broadcast_to(P0_aer, (B, 2 * N)))
+        if not s.same_phase(P_atm, P_aer):
+            s.set_phase(P_atm, P_aer)
     if P0_atm is not None:
         P0a = np.ascontiguousarray(np.broadcast_to(P0_atm, (B, 2 * N)))
-    if P0_aer is not None:
-        P0r = np.ascontiguousarray(np.broadcast_to(P0_aer, (B, 2 * N)))
-    if not s.same_phase(P_atm, P_aer):
-        s.set_phase(P_atm, P_aer)
     s.set_columns(np.full(B, iu), np.full(B, idn), mu0, grd_alb, alb_atm, alb_aer,
                   tauStar_atm / L, tauStar_aer / (idn + 1 - iu), tauStar_atm + tauStar_aer, surface=surface)
+    if aer_set is not None:
+        s.set_aerosol_sets(sets.astype(np.int32))
     return s, tau, P0a, P0r, mu, iu, idn, N
 
 
@@ -1161,7 +1151,6 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
     "beam_slant" [B, L].  `source='thermal'` (with `planck`, `planck_surface`, `surface_emissivity`): the thermal field of
     `SOS_Aer_batch`.  `aer_set` [B] with a list of names in `aer_phase_fun` (or a stack `P_aer`): several aerosols in one batch,
     as in `SOS_Aer_batch`; the cached handle's columns are back on aerosol set 0 when the call returns, also on error."""
-    import torch
     thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
                             _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if source == "thermal" else 0,
                             nb_layers, beam=beam)
@@ -1176,25 +1165,7 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
                                    keep_device=True), (mu, iu, idn)
         if thermal:
             return solve_thermal(s, tau, *thermal, tol=tol, keep_device=True, device=device), (mu, iu, idn)
-        dev = torch.device("cuda", device)
-        B, L = tau.shape
-        with torch.cuda.device(dev):
-            s.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-            try:
-                d_tau = torch.from_numpy(tau).to(dev)
-                d_P0a = torch.from_numpy(np.ascontiguousarray(P0a)).to(dev)
-                d_P0r = torch.from_numpy(np.ascontiguousarray(P0r)).to(dev)
-                d_I = torch.empty((B, L, 2 * N), dtype=torch.float64, device=dev)
-                d_n = torch.zeros(B, dtype=torch.int32, device=dev)
-                d_st = torch.zeros(B, dtype=torch.int32, device=dev)
-                s.solve_device(d_tau.data_ptr(), d_P0a.data_ptr(), d_P0r.data_ptr(), d_I.data_ptr(), tol=tol,
-                               d_n_orders=d_n.data_ptr(), d_status=d_st.data_ptr())
-            finally:
-                # the solver is cached and goes back to its own stream: drain this one first, so that the handle's internal
-                # buffers are not reused under the last launches (the order loop has already waited for all but the last two)
-                s.synchronize()
-                s.set_stream(None)
-        return {"I": d_I, "n": d_n, "status": d_st, "tau": d_tau}, (mu, iu, idn)
+        return _solve_resident(s, tau, P0a, P0r, None, None, tol, device=device, keep_device=True), (mu, iu, idn)
     finally:
         if aer_set is not None:
             _columns_to_set0(s, tau.shape[0])

@@ -30,9 +30,24 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _vp(address):
+    """A device address (an integer, e.g. torch's `tensor.data_ptr()`) as the C ABI takes it; 0 is the null pointer."""
+    return ctypes.c_void_p(address) if address else None
+
+
 def _vec(x, B, name):
     a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (B,)))
     return a
+
+
+def _surface_code(surface):
+    # 'lambertian' is the reference's file as coded (lam:399/401: negative reflected radiance, SURVEY H2);
+    # 'lambertian_readme' the same term with the sign of the reference's README.md:215
+    sf = {"specular": _lib.SURFACE_SPECULAR, "lambertian": _lib.SURFACE_LAMBERTIAN,
+          "lambertian_readme": _lib.SURFACE_LAMBERTIAN_README}.get(surface)
+    if sf is None:
+        raise ValueError("surface must be 'specular', 'lambertian' or 'lambertian_readme', got %r" % (surface,))
+    return sf
 
 
 @dataclass
@@ -234,12 +249,7 @@ class Solver:
                     surface="specular"):
         """Three-zone columns (spec:23-53).  Scalars broadcast over the batch."""
         B = int(np.size(idx_up))
-        # 'lambertian' is the reference's file as coded (lam:399/401: negative reflected radiance, SURVEY H2);
-        # 'lambertian_readme' the same term with the sign of the reference's README.md:215
-        sf = {"specular": _lib.SURFACE_SPECULAR, "lambertian": _lib.SURFACE_LAMBERTIAN,
-              "lambertian_readme": _lib.SURFACE_LAMBERTIAN_README}.get(surface)
-        if sf is None:
-            raise ValueError("surface must be 'specular', 'lambertian' or 'lambertian_readme', got %r" % (surface,))
+        sf = _surface_code(surface)
         iu = _i32(np.reshape(idx_up, (B,)), B, "idx_up")
         idn = _i32(np.reshape(idx_down, (B,)), B, "idx_down")
         v = [_vec(x, B, n) for x, n in ((mu0, "mu0"), (grd_alb, "grd_alb"), (alb_atm, "alb_atm"), (alb_aer, "alb_aer"),
@@ -259,10 +269,7 @@ class Solver:
         zwr = np.ascontiguousarray(np.broadcast_to(np.asarray(zone_alb_aer, dtype=np.float64), (B, nzmax)))
         zdt = np.ascontiguousarray(np.broadcast_to(np.asarray(zone_dtau_aer, dtype=np.float64), (B, nzmax)))
         nzv = np.full(B, nzmax, dtype=np.int32) if nz is None else _i32(np.reshape(nz, (B,)), B, "nz")
-        sf = {"specular": _lib.SURFACE_SPECULAR, "lambertian": _lib.SURFACE_LAMBERTIAN,
-              "lambertian_readme": _lib.SURFACE_LAMBERTIAN_README}.get(surface)
-        if sf is None:
-            raise ValueError("surface must be 'specular', 'lambertian' or 'lambertian_readme', got %r" % (surface,))
+        sf = _surface_code(surface)
         v = [_vec(x, B, n) for x, n in ((mu0, "mu0"), (grd_alb, "grd_alb"), (alb_atm, "alb_atm"), (dtau_atm, "dtau_atm"),
                                         (tauStar_tot, "tauStar_tot"))]
         check(lib().sosrt_set_columns_zones(self._h, B, sf, nzmax, _ptr(nzv), _ptr(zr0), _ptr(zmix), _ptr(v[0]), _ptr(v[1]),
@@ -340,9 +347,8 @@ class Solver:
                      d_I_saved: int = 0, d_n_orders: int = 0, d_status: int = 0):
         """All arguments are device addresses (e.g. torch `tensor.data_ptr()`); work is enqueued on
         the handle's stream (set_stream) and is complete after synchronize()."""
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_solve_dev(self._h, self.B, vp(d_tau), vp(d_P0_atm), vp(d_P0_aer), float(tol), vp(d_I1),
-                                    vp(d_I_out), vp(d_I_saved), vp(d_n_orders), vp(d_status)))
+        check(lib().sosrt_solve_dev(self._h, self.B, _vp(d_tau), _vp(d_P0_atm), _vp(d_P0_aer), float(tol), _vp(d_I1),
+                                    _vp(d_I_out), _vp(d_I_saved), _vp(d_n_orders), _vp(d_status)))
 
     def last_solve_stats(self):
         mo = ctypes.c_int()
@@ -377,9 +383,8 @@ class Solver:
     def epilogue_device(self, d_tau: int, d_I: int, d_z: int = 0, beam_norm="crit", d_flux_down: int = 0, d_flux_up: int = 0,
                         d_diffusivity: int = 0, d_heating_rate: int = 0, d_net_toa: int = 0):
         """Same on caller-owned device buffers (addresses), enqueued on the handle's stream."""
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_epilogue_dev(self._h, self.B, vp(d_tau), vp(d_I), 0 if beam_norm == "crit" else 1, vp(d_z),
-                                       vp(d_flux_down), vp(d_flux_up), vp(d_diffusivity), vp(d_heating_rate), vp(d_net_toa)))
+        check(lib().sosrt_epilogue_dev(self._h, self.B, _vp(d_tau), _vp(d_I), 0 if beam_norm == "crit" else 1, _vp(d_z),
+                                       _vp(d_flux_down), _vp(d_flux_up), _vp(d_diffusivity), _vp(d_heating_rate), _vp(d_net_toa)))
 
     # ---- pseudo-spherical direct beam (sosrt.h; DESIGN section 17) --------------------------------
     def set_saved_orders(self, slots: Optional[int] = None):
@@ -390,25 +395,22 @@ class Solver:
         """Slant optical depth of the direct beam through spherical shells: d_tau [B, L], d_z [L] (km, strictly descending),
         d_sigma_out [B, L] (device addresses); d_mu0 [B] or 0 for the columns' own mu0.  Enqueued on the handle's stream (the
         call reads d_z back to check it)."""
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_beam_slant_dev(self._h, int(self.B if B is None else B), vp(d_tau), vp(d_z), float(earth_radius),
-                                         vp(d_mu0), vp(d_sigma_out)))
+        check(lib().sosrt_beam_slant_dev(self._h, int(self.B if B is None else B), _vp(d_tau), _vp(d_z), float(earth_radius),
+                                         _vp(d_mu0), _vp(d_sigma_out)))
 
     def first_order_beam_device(self, d_tau: int, d_sigma: int, d_P0_atm: int, d_P0_aer: int, d_I1_out: int, B: Optional[int] = None):
         """The first order layer by layer on the beam path d_sigma [B, L] (sigma = tau / mu0: the coded first order, to
         rounding): d_I1_out [B, L, 2N] is the `d_I1` of `solve_device`.  P0 layouts as `solve_device` takes them."""
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_first_order_beam_dev(self._h, int(self.B if B is None else B), vp(d_tau), vp(d_sigma), vp(d_P0_atm),
-                                               vp(d_P0_aer), vp(d_I1_out)))
+        check(lib().sosrt_first_order_beam_dev(self._h, int(self.B if B is None else B), _vp(d_tau), _vp(d_sigma), _vp(d_P0_atm),
+                                               _vp(d_P0_aer), _vp(d_I1_out)))
 
     def epilogue_beam_device(self, d_tau: int, d_I: int, d_sigma: int, d_z: int = 0, beam_norm="crit", d_flux_down: int = 0,
                              d_flux_up: int = 0, d_diffusivity: int = 0, d_heating_rate: int = 0, d_net_toa: int = 0,
                              B: Optional[int] = None):
         """`epilogue_device` with the beam terms of the fluxes on the path d_sigma [B, L]."""
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_epilogue_beam_dev(self._h, int(self.B if B is None else B), vp(d_tau), vp(d_I),
-                                            0 if beam_norm == "crit" else 1, vp(d_z), vp(d_flux_down), vp(d_flux_up),
-                                            vp(d_diffusivity), vp(d_heating_rate), vp(d_net_toa), vp(d_sigma)))
+        check(lib().sosrt_epilogue_beam_dev(self._h, int(self.B if B is None else B), _vp(d_tau), _vp(d_I),
+                                            0 if beam_norm == "crit" else 1, _vp(d_z), _vp(d_flux_down), _vp(d_flux_up),
+                                            _vp(d_diffusivity), _vp(d_heating_rate), _vp(d_net_toa), _vp(d_sigma)))
 
     # ---- thermal emission (sosrt.h; DESIGN section 18) ----------------------------------------------
     def emission_device(self, d_tau: int, d_planck: int, d_planck_surface: int, d_I0_out: int, d_emissivity: int = 0,
@@ -416,9 +418,8 @@ class Solver:
         """The field the layers and the ground emit: d_tau, d_planck [B, L] (the Planck radiance at every level),
         d_planck_surface [B], d_emissivity [B] or 0 for 1 - grd_alb; d_I0_out [B, L, 2N] is the `d_I1` of `solve_device`.
         Device addresses; enqueued on the handle's stream; nothing but the output is written."""
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_emission_dev(self._h, int(self.B if B is None else B), vp(d_tau), vp(d_planck), vp(d_planck_surface),
-                                       vp(d_emissivity), vp(d_I0_out)))
+        check(lib().sosrt_emission_dev(self._h, int(self.B if B is None else B), _vp(d_tau), _vp(d_planck), _vp(d_planck_surface),
+                                       _vp(d_emissivity), _vp(d_I0_out)))
 
     def emission_view_device(self, mu_view, d_tau: int, d_planck: int, d_planck_surface: int, levels, d_out: int,
                              d_emissivity: int = 0, B: Optional[int] = None):
@@ -426,18 +427,16 @@ class Solver:
         d_out [B, nlev, 2V] on the signed lanes (-mu_view, +mu_view).  Specular or no surface."""
         m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
         lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.int32)
-        vp = lambda x: ctypes.c_void_p(x) if x else None
         check(lib().sosrt_emission_view_dev(self._h, int(self.B if B is None else B), int(m.size), _ptr(m) if m.size else None,
-                                            vp(d_tau), vp(d_planck), vp(d_planck_surface), vp(d_emissivity), int(lev.size),
-                                            _ptr(lev) if lev.size else None, vp(d_out)))
+                                            _vp(d_tau), _vp(d_planck), _vp(d_planck_surface), _vp(d_emissivity), int(lev.size),
+                                            _ptr(lev) if lev.size else None, _vp(d_out)))
 
     def epilogue_emission_device(self, d_tau: int, d_I: int, d_z: int = 0, d_flux_down: int = 0, d_flux_up: int = 0,
                                  d_diffusivity: int = 0, d_heating_rate: int = 0, d_net_toa: int = 0, B: Optional[int] = None):
         """`epilogue_device` without the two beam terms: the fluxes, diffusivity, heating rate and TOA net flux of a thermal field."""
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_epilogue_emission_dev(self._h, int(self.B if B is None else B), vp(d_tau), vp(d_I), vp(d_z),
-                                                vp(d_flux_down), vp(d_flux_up), vp(d_diffusivity), vp(d_heating_rate),
-                                                vp(d_net_toa)))
+        check(lib().sosrt_epilogue_emission_dev(self._h, int(self.B if B is None else B), _vp(d_tau), _vp(d_I), _vp(d_z),
+                                                _vp(d_flux_down), _vp(d_flux_up), _vp(d_diffusivity), _vp(d_heating_rate),
+                                                _vp(d_net_toa)))
 
     # ---- band integration (sosrt.h; DESIGN section 19) --------------------------------------------------
     def planck_bands_device(self, d_T: int, d_T_surface: int, nu_lo, nu_hi, d_planck_out: int, d_planck_surface_out: int,
@@ -450,17 +449,15 @@ class Solver:
         hi = np.ascontiguousarray(np.atleast_1d(nu_hi), dtype=np.float64)
         if lo.ndim != 1 or lo.shape != hi.shape:
             raise ValueError("nu_lo and nu_hi must be two arrays [K] of one length")
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_planck_bands_dev(self._h, int(C), int(lo.size), vp(d_T), vp(d_T_surface), _ptr(lo) if lo.size else None,
-                                           _ptr(hi) if hi.size else None, int(bool(normalise)), vp(d_planck_out),
-                                           vp(d_planck_surface_out), vp(d_scale_out)))
+        check(lib().sosrt_planck_bands_dev(self._h, int(C), int(lo.size), _vp(d_T), _vp(d_T_surface), _ptr(lo) if lo.size else None,
+                                           _ptr(hi) if hi.size else None, int(bool(normalise)), _vp(d_planck_out),
+                                           _vp(d_planck_surface_out), _vp(d_scale_out)))
 
     def band_reduce_device(self, d_x: int, d_out: int, C: int, K: int, M: int, d_weight: int = 0, d_scale: int = 0,
                            accumulate=False):
         """d_out [C, M] = (accumulate ? d_out : 0) + sum over k ascending of (weight[k, c] scale[k, c]) d_x[k, c, m], one fused
         multiply-add per k; d_weight, d_scale [K, C] or 0 for ones.  The same bits however K is split over accumulating calls."""
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_band_reduce_dev(self._h, int(C), int(K), int(M), vp(d_weight), vp(d_scale), vp(d_x), vp(d_out),
+        check(lib().sosrt_band_reduce_dev(self._h, int(C), int(K), int(M), _vp(d_weight), _vp(d_scale), _vp(d_x), _vp(d_out),
                                           int(bool(accumulate))))
 
     # ---- phase functions on the device (phase:68-292) ----------------------------
@@ -587,8 +584,7 @@ class Solver:
     def phase_p0_rows_device(self, kind, d_mu0: int, mu_signed, d_out: int, B: int, g=0.0):
         """The same of P0 for B columns: d_mu0 [B], d_out [B, V2] (addresses)."""
         m = np.ascontiguousarray(np.atleast_1d(mu_signed), dtype=np.float64)
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_phase_p0_rows_dev(self._h, int(B), self._KINDS[kind], float(g), vp(d_mu0), int(m.size), _ptr(m), vp(d_out)))
+        check(lib().sosrt_phase_p0_rows_dev(self._h, int(B), self._KINDS[kind], float(g), _vp(d_mu0), int(m.size), _ptr(m), _vp(d_out)))
 
     def view_radiance_device(self, mu_view, d_tau: int, d_I_src: int, d_rows_atm: int, d_rows_aer: int, levels,
                              d_scat_out: int = 0, d_first_out: int = 0, d_p0rows_atm: int = 0, d_p0rows_aer: int = 0,
@@ -604,10 +600,9 @@ class Solver:
         q = self._QUADS.get(quadrature, quadrature)
         if isinstance(q, str) or isinstance(q, bool) or not isinstance(q, (int, np.integer)):
             raise ValueError("quadrature must be 'grid' or 'linear' (got %r)" % (quadrature,))
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_view_radiance_dev(self._h, int(self.B if B is None else B), int(m.size), _ptr(m), vp(d_tau), vp(d_I_src),
-                                            vp(d_rows_atm), vp(d_rows_aer), vp(d_p0rows_atm), vp(d_p0rows_aer), int(q),
-                                            int(lev.size), _ptr(lev), vp(d_scat_out), vp(d_first_out)))
+        check(lib().sosrt_view_radiance_dev(self._h, int(self.B if B is None else B), int(m.size), _ptr(m), _vp(d_tau), _vp(d_I_src),
+                                            _vp(d_rows_atm), _vp(d_rows_aer), _vp(d_p0rows_atm), _vp(d_p0rows_aer), int(q),
+                                            int(lev.size), _ptr(lev), _vp(d_scat_out), _vp(d_first_out)))
 
     def view_timing(self):
         """Milliseconds of the last `view_radiance_device`: (source contraction, sweeps, first order); waits for them."""
@@ -628,26 +623,23 @@ class Solver:
     def phase_p0_rows_modes_device(self, kind, d_mu0: int, mu_signed, d_out: int, B: int, m_first, m_count, nphi=25, g=0.0):
         """The same of P0 for B columns: d_mu0 [B], d_out [m_count, B, V2] (addresses)."""
         m = np.ascontiguousarray(np.atleast_1d(mu_signed), dtype=np.float64)
-        vp = lambda x: ctypes.c_void_p(x) if x else None
         check(lib().sosrt_phase_p0_rows_modes_dev(self._h, int(B), self._KINDS[kind], float(g), int(m_first), int(m_count),
-                                                  int(nphi), vp(d_mu0), int(m.size), _ptr(m), vp(d_out)))
+                                                  int(nphi), _vp(d_mu0), int(m.size), _ptr(m), _vp(d_out)))
 
     def phase_p0_rows_azimuth_device(self, kind, d_mu0: int, mu_signed, d_phi: int, nphi_out: int, d_out: int, B: int, g=0.0):
         """p(c(s_j, mu0_b, phi_i)) / Z0_b, the first-order phase value at a view lane and an azimuth with the normaliser of
         `phase_p0_rows_device`: d_mu0 [B], d_phi [nphi_out] (radians), d_out [nphi_out, B, V2] (addresses).  The [B, V2] block of
         one azimuth is a `d_p0rows_*` of `view_radiance_device`."""
         m = np.ascontiguousarray(np.atleast_1d(mu_signed), dtype=np.float64)
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_phase_p0_rows_azimuth_dev(self._h, int(B), self._KINDS[kind], float(g), vp(d_mu0), int(m.size), _ptr(m),
-                                                    int(nphi_out), vp(d_phi), vp(d_out)))
+        check(lib().sosrt_phase_p0_rows_azimuth_dev(self._h, int(B), self._KINDS[kind], float(g), _vp(d_mu0), int(m.size), _ptr(m),
+                                                    int(nphi_out), _vp(d_phi), _vp(d_out)))
 
     def view_azimuth_accumulate_device(self, m: int, d_val: int, nlev: int, V2: int, d_phi: int, nphi_out: int, d_out: int,
                                        B: Optional[int] = None):
         """out[b][lev][j][i] (+)= (2 - delta_m0) val[b][lev][j] cos(m phi[i]) on device addresses (m = 0 writes): the synthesis
         of `azimuth_accumulate_device` over view lanes, d_val [B, nlev, V2] being mode m of the view radiance."""
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_view_azimuth_accumulate_dev(self._h, int(self.B if B is None else B), int(m), int(nlev), int(V2), vp(d_val),
-                                                      int(nphi_out), vp(d_phi), vp(d_out)))
+        check(lib().sosrt_view_azimuth_accumulate_dev(self._h, int(self.B if B is None else B), int(m), int(nlev), int(V2), _vp(d_val),
+                                                      int(nphi_out), _vp(d_phi), _vp(d_out)))
 
     def set_order_targets(self, d_targets: Optional[int]):
         """Fixed order counts for the solves that follow: `d_targets` is the device address of an int32 [B] array (kept by the
@@ -666,9 +658,8 @@ class Solver:
         """The whole synthesis in one launch: out[b][lev][dir][j] = I0[b][levels[lev]][dir] + sum_{m=1..M} 2 Im[m-1][b][levels[lev]]
         [dir] cos(m phi[j]) on device addresses (d_I0 [B, L, 2N], d_Im [M, B, L, 2N]); the bits of `azimuth_accumulate_device`
         called for m = 0..M."""
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        check(lib().sosrt_azimuth_synthesize_dev(self._h, int(self.B if B is None else B), int(M), vp(d_I0), vp(d_Im), int(nlev),
-                                                 vp(d_levels), int(nphi_out), vp(d_phi), vp(d_out)))
+        check(lib().sosrt_azimuth_synthesize_dev(self._h, int(self.B if B is None else B), int(M), _vp(d_I0), _vp(d_Im), int(nlev),
+                                                 _vp(d_levels), int(nphi_out), _vp(d_phi), _vp(d_out)))
 
     # ---- multi-GPU gather over RCCL (one process per GPU) -------------------------
     @staticmethod

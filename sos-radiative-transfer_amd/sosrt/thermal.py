@@ -8,8 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib
-from .main import _batch_width, _prepare_batch, _thermal_args, solve_thermal
+from .main import _batch_width, _prepare_batch, _raise_unconverged, _thermal_args, solve_thermal
 
 # CODATA 2018 (exact since the 2019 redefinition of the SI)
 PLANCK_H = 6.62607015e-34          # J s
@@ -45,10 +44,7 @@ def thermal_toa_flux(tauStar_aer, grd_alb, planck, planck_surface, surface_emiss
                                               nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm, mie_aer,
                                               None, None, None, None, surface, max_orders, device)
     r, epi = solve_thermal(s, tau, *thermal, tol=tol, want=("flux_up",), device=device, fetch_field=False)
-    if np.any(r.status == _lib.COL_INDEXERROR):
-        raise IndexError("index %d is out of bounds for axis 1 with size %d" % (2 * N, 2 * N))
-    if np.any(r.status != 0):
-        raise RuntimeError("columns did not converge within %d orders: status %s" % (max_orders, r.status))
+    _raise_unconverged(r.status, N, max_orders)
     return epi["flux_up"][:, 0].copy()
 
 
