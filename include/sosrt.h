@@ -634,6 +634,61 @@ int sosrt_band_reduce_dev(sosrt_t* h, int C, int K, int M, const double* d_weigh
                           const double* d_scale /*[K][C] or NULL: 1*/, const double* d_x /*[K][C][M]*/,
                           double* d_out /*[C][M]*/, int accumulate);
 
+/* ---- BRDF ground: a series in ground reflections around the order loop -------------------------------------
+ * The field over a ground that reflects by a bidirectional reflectance factor rho(mu_out, mu_in, phi) is the sum over the number
+ * of ground reflections: the solve over a black ground (specular surface, grd_alb = 0), then per reflection ("bounce") the
+ * downward surface row of the previous term reflected through an operator, its unscattered upward field, and a black-ground
+ * solve started from that field (sosrt_solve_dev, d_I1_in).  Five stages beside the solve, detected by symbol (SOSRT_VERSION is
+ * unchanged); all are enqueued on the handle's stream and write their outputs only -- the handle's columns, resident field,
+ * order targets and phase state stay as they were (like every stage, a call ends the run of adjacent launches that the
+ * handle's profiling slots keep track of).  Only the azimuth mean (mode m = 0) of the BRDF is built.
+ *
+ * Lanes: i = 0 .. N-2 is the upward direction N+1+i, j = 0 .. N-2 the downward direction j; the two mu = 0 nodes (N-1, N) take
+ * no part.  rho_bar(a, b) = (1 / pi) int_0^pi rho(a, b, phi) dphi by the trapezoid rule on nphi nodes of [0, pi].
+ *
+ * sosrt_brdf_operator_dev: the operator with the quadrature of the reflected flux folded in,
+ *     R(i, j) = 2 w_j |mu_j| rho_bar(mu_i, |mu_j|),   w the trapezoid weights of the nodes mu[0 .. N-2],
+ * stored with the lanes i of one j contiguous: d_R_out[j (N-1) + i].  sosrt_brdf_beam_dev: r0[b][i] = rho_bar(mu_i, mu0[b]), the
+ * reflection of the direct beam.  Kinds: SOSRT_BRDF_LAMBERTIAN (no parameters; rho = 1 -- the albedo is the per-column scale of
+ * sosrt_ground_source_dev, and R is the in-loop Lambertian boundary of SOSRT_SURFACE_LAMBERTIAN_README up to the order of
+ * summation) and SOSRT_BRDF_RPV (params = { rho0, k, Theta }, Rahman-Pinty-Verstraete:
+ *     rho = rho0 (a b (a + b))^(k-1) (1 - Theta^2) / (1 + 2 Theta cos g + Theta^2)^(3/2) (1 + (1 - rho0) / (1 + G)),
+ *     cos g = a b + sqrt(1-a^2) sqrt(1-b^2) cos phi,  G^2 = tan^2 a + tan^2 b - 2 tan a tan b cos phi, tan x = sqrt(1-x^2)/x,
+ * G^2 evaluated as max(0, (tan a - tan b)^2 + 4 tan a tan b sin^2(phi/2)), which does not cancel at the hot spot a = b, phi = 0;
+ * rho_bar is symmetric in (a, b)).  A caller with a BRDF of their own fills R and r0 themselves.
+ *
+ * sosrt_ground_source_dev: S[b][i] = scale[b] (sum_j R(i, j) I[b][L-1][j] + r0[b][i] exp(-tau[b][L-1] / mu0[b])), mu0 the
+ * columns'; d_r0 NULL: no beam term (every bounce after the first); d_scale NULL: 1.  The sum runs over j ascending in fused
+ * multiply-adds, one lane per i: a column's bits do not depend on B.
+ *
+ * sosrt_ground_first_order_dev: the unscattered field of the ground source,
+ *     G[b][t][N+1+i] = S[b][i] exp(-(tau[b][L-1] - tau[b][t]) / mu_i),   G[b][t][N] = 0,   G[b][t][0 .. N-1] = 0,
+ * then on every row the mu -> 0+ blend of the order loop's upward sweep (spec:402-409): k = N+1, while |(G[k] - G[k+1]) -
+ * (G[k+1] - G[k+2])| > 1e-4: k += 1; k += 1; lanes N+1 .. k-1 become (1 - w) G[N] + w G[k], w = mu[m] / mu[k].  A search that
+ * would read past lane 2N-1 (the reference raises IndexError there) leaves its row unblended and gives the column
+ * SOSRT_COL_INDEXERROR in d_status (nullable; SOSRT_COL_OK otherwise).
+ *
+ * sosrt_bounce_accumulate_dev: I_total += Ik (one addition per element), and ratio[b] = the larger of max |Ik| / max |I_total|
+ * over the upward lanes of row 0 and over the downward lanes of row L-1 (of the updated total; a row whose total is all zero
+ * counts 0).
+ *
+ * Refused with SOSRT_E_INVALID, a message and nothing written: the single-slab geometry; B outside 1 .. the current columns; a
+ * null pointer (d_r0, d_scale, d_status and the params of a kind without any aside); nphi < 3 or > SOSRT_BRDF_MAX_NPHI; an
+ * unknown kind or a wrong nparams; RPV parameters outside rho0 > 0, k > 0, |Theta| < 1; N < 4. */
+#define SOSRT_BRDF_LAMBERTIAN 0
+#define SOSRT_BRDF_RPV        1
+#define SOSRT_BRDF_MAX_NPHI   65537
+int sosrt_brdf_operator_dev(sosrt_t* h, int kind, const double* params /*host*/, int nparams, int nphi, double* d_R_out /*[N-1][N-1], [j][i]*/);
+int sosrt_brdf_beam_dev(sosrt_t* h, int B, int kind, const double* params /*host*/, int nparams, int nphi, const double* d_mu0 /*[B]*/,
+                        double* d_r0_out /*[B][N-1]*/);
+int sosrt_ground_source_dev(sosrt_t* h, int B, const double* d_I /*[B][L][2N]*/, const double* d_tau /*[B][L]*/,
+                            const double* d_R /*[N-1][N-1], [j][i]*/, const double* d_r0 /*[B][N-1] or NULL*/,
+                            const double* d_scale /*[B] or NULL*/, double* d_S_out /*[B][N-1]*/);
+int sosrt_ground_first_order_dev(sosrt_t* h, int B, const double* d_tau /*[B][L]*/, const double* d_S /*[B][N-1]*/,
+                                 double* d_G_out /*[B][L][2N]*/, int* d_status /*[B] or NULL*/);
+int sosrt_bounce_accumulate_dev(sosrt_t* h, int B, const double* d_Ik /*[B][L][2N]*/, double* d_I_total /*[B][L][2N]*/,
+                                double* d_ratio_out /*[B]*/);
+
 /* ---- multi-GPU: one process per GPU, columns sharded, ONE collective at the end ------------------
  * Nothing in SOS_Aer_main_specular.py:104-458 couples columns, so the order loop never communicates; these entry
  * points only assemble the results of the ranks on `root` over RCCL (xGMI inside a node).  RCCL is bound at run time

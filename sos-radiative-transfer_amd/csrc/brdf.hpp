@@ -1,0 +1,27 @@
+// BRDF ground (include/sosrt.h): launchers of brdf.hip.  Stages beside the solve: the kernels read the grid,
+// the columns' mu0 as sosrt_set_columns* uploaded it (ColScalars) and their arguments, and write their outputs only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
+
+namespace sosrt {
+
+struct BrdfParams {
+    int kind;                          // SOSRT_BRDF_*
+    double p[3];                       // RPV: rho0, k, Theta
+};
+
+// R [N-1][N-1], element (j, i) at j (N-1) + i: 2 w_j |mu_j| rho_bar(mu[N+1+i], |mu_j|)
+void launch_brdf_operator(hipStream_t s, const Grid& g, BrdfParams bp, int nphi, double* R);
+// r0 [B][N-1]: rho_bar(mu[N+1+i], mu0[b])
+void launch_brdf_beam(hipStream_t s, const Grid& g, int B, BrdfParams bp, int nphi, const double* mu0, double* r0);
+// S [B][N-1] = scale (R I[L-1][0 .. N-2] + r0 exp(-tau[L-1] / mu0)); r0, scale nullable
+void launch_ground_source(hipStream_t s, const Grid& g, int B, ColScalars sc, const double* I, const double* tau, const double* R,
+                          const double* r0, const double* scale, double* S);
+// G [B][L][D]: the unscattered field of S with the mu -> 0+ blend on every row; status [B] nullable
+void launch_ground_first_order(hipStream_t s, const Grid& g, int B, const double* tau, const double* S, double* G, int* status);
+// total += Ik; ratio [B]
+void launch_bounce_accumulate(hipStream_t s, const Grid& g, int B, const double* Ik, double* total, double* ratio);
+
+}  // namespace sosrt

@@ -24,6 +24,7 @@ MAX_MODES = 64
 MAX_PHASE_SETS = 64
 MAX_VIEWS = 64
 VIEW_QUAD_GRID, VIEW_QUAD_LINEAR = 0, 1
+BRDF_LAMBERTIAN, BRDF_RPV = 0, 1
 
 _dp = POINTER(c_double)
 _ip = POINTER(c_int)
@@ -101,6 +102,11 @@ SIGNATURES = {
     "sosrt_epilogue_emission_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 8),
     "sosrt_planck_bands_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 3),
     "sosrt_band_reduce_dev": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 4 + [c_int]),
+    "sosrt_brdf_operator_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "sosrt_brdf_beam_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sosrt_ground_source_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 6),
+    "sosrt_ground_first_order_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 4),
+    "sosrt_bounce_accumulate_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 3),
     "sosrt_comm_unique_id": (c_int, [c_void_p]),
     "sosrt_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "sosrt_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

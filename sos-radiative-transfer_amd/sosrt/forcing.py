@@ -20,18 +20,23 @@ from __future__ import annotations
 import numpy as np
 
 from .inputs import direction_grid, phase_function, slab_indices, tau_profile
-from .main import EARTH_RADIUS_KM, _beam_args, _raise_unconverged, get_solver, solve_spherical
+from .main import EARTH_RADIUS_KM, _beam_args, _brdf_args, _raise_unconverged, get_solver, solve_brdf, solve_spherical
 
 
 def _net_flux_columns(tau, idx_up, idx_down, mu, mu0, grd_alb, alb_atm, alb_aer, dtau_atm, dtau_aer, tauStar_tot, P_atm, P_aer,
-                      P0_atm, P0_aer, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, z0=120):
+                      P0_atm, P0_aer, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, z0=120,
+                      surface="specular", brdf=None):
     """TOA net flux (crit:382) of B columns on their grids tau [B, L]; per-column arrays or scalars otherwise.
     beam='spherical': the pseudo-spherical direct beam (main.solve_spherical) on the altitudes np.linspace(z0, 0, L), and the
-    flux's beam terms on the same slant path (the beam epilogue)."""
+    flux's beam terms on the same slant path (the beam epilogue).  surface='brdf' with `brdf`: the BRDF ground of
+    main.SOS_Aer_batch (main.solve_brdf), grd_alb its per-column scale; the flux of the summed field."""
     spherical = _beam_args(beam, earth_radius)
     tau = np.atleast_2d(np.asarray(tau, dtype=np.float64))
     B, L = tau.shape
     N = len(mu) // 2
+    ground = _brdf_args(surface, brdf, grd_alb, N, B, beam=beam)
+    if ground:
+        grd_alb = 0.0                                        # the series' solves run over a black ground
     s = get_solver(L, N, B, max_orders, device)
     if not s.same_grid(mu):
         s.set_grid(mu)
@@ -43,10 +48,12 @@ def _net_flux_columns(tau, idx_up, idx_down, mu, mu0, grd_alb, alb_atm, alb_aer,
     if spherical:
         r, _, epi = solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, L), earth_radius, device=device, fetch_field=False,
                                     want=("net_toa",))
+    elif ground:
+        r, _, epi = solve_brdf(s, tau, P0a, P0r, ground, mu0, device=device, fetch_field=False, want=("net_toa",))
     else:
         r = s.solve(tau, P0a, P0r, fetch_field=False)
     _raise_unconverged(r.status, N, max_orders)
-    return epi["net_toa"] if spherical else s.epilogue(want=("net_toa",))["net_toa"]
+    return epi["net_toa"] if spherical or ground else s.epilogue(want=("net_toa",))["net_toa"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -97,7 +104,7 @@ def SOS_Aer_critical_albedo(tauStar_aer, dtau_aer, tauStar_atm, dtau_atm, P_aer,
 # batched over (tauStar_aer, alb_aer)
 # ---------------------------------------------------------------------------------------------
 def _solve_fluxes(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, geom, phases, max_orders, device, beam="plane",
-                  earth_radius=EARTH_RADIUS_KM):
+                  earth_radius=EARTH_RADIUS_KM, surface="specular", brdf=None):
     """TOA net flux (crit:382) of B columns; arrays of length B for tauStar_aer and alb_aer."""
     z0, z_up, z_down, L, N = geom
     P0_atm, P_atm, P0_aer, P_aer = phases
@@ -106,17 +113,21 @@ def _solve_fluxes(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, geom
     ta = np.asarray(tauStar_aer, dtype=np.float64)
     return _net_flux_columns(tau, iu, idn, direction_grid(N), mu0, grd_alb, alb_atm, alb_aer, tauStar_atm / L,
                              ta / (idn + 1 - iu), tauStar_atm + ta, P_atm, P_aer, P0_atm, P0_aer, max_orders, device, beam, earth_radius,
-                             z0)
+                             z0, surface, brdf)
 
 
 def toa_net_flux(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, z0=120, z_up=25, z_down=17, nb_layers=200,
                  nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, phases=None,
-                 max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM):
+                 max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, surface="specular", brdf=None):
     """Net flux at the top of the atmosphere, -F_down[0] - F_up[0] (crit:377-382), for arrays of
     (tauStar_aer, alb_aer).  beam='spherical' (with `earth_radius`, km): the direct beam on its slant path through spherical
     shells, in the solve and in the flux's beam terms (main.SOS_Aer_batch); `radiative_forcing` and `critical_albedo` pass
-    both keywords on."""
+    both keywords on.  surface='brdf' with `brdf` ('lambertian', ('rpv', rho0, k, theta) or arrays (R, r0)): the BRDF ground
+    of main.SOS_Aer_batch, grd_alb its scale; `radiative_forcing` and `critical_albedo` pass these on too."""
     _beam_args(beam, earth_radius)
+    if surface not in ("specular", "brdf"):
+        raise ValueError("surface must be 'specular' or 'brdf' (got %r)" % (surface,))
+    _brdf_args(surface, brdf, grd_alb, nb_angles, int(np.broadcast(np.atleast_1d(tauStar_aer), np.atleast_1d(alb_aer)).size), beam=beam)
     ta, wa = np.broadcast_arrays(np.atleast_1d(np.asarray(tauStar_aer, dtype=float)), np.atleast_1d(np.asarray(alb_aer, dtype=float)))
     if phases is None:
         mu = direction_grid(nb_angles)
@@ -124,7 +135,7 @@ def toa_net_flux(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, z0
         P0r, Pr = phase_function(aer_phase_fun, nb_angles, mu, mu0, g_aer)
         phases = (P0a, Pa, P0r, Pr)
     return _solve_fluxes(mu0, tauStar_atm, ta, grd_alb, alb_atm, wa, (z0, z_up, z_down, nb_layers, nb_angles), phases, max_orders, device,
-                         beam, earth_radius)
+                         beam, earth_radius, surface, brdf)
 
 
 def radiative_forcing(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, baseline="no_aerosol", **kw):

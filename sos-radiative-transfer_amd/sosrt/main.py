@@ -39,6 +39,8 @@ class ColumnResult:
     idx_down: int
     status: int
     beam_slant: Optional[np.ndarray] = None   # [L] (beam='spherical'): slant optical depth of the direct beam at every level
+    bounces: Optional[int] = None             # (surface='brdf'): ground reflections summed until the series' term fell below tol
+    bounce_ratio: Optional[float] = None      # ... and the last term's share of the sum
 
 
 @dataclass
@@ -62,6 +64,8 @@ class BatchResult:
     I_view_azimuth_scattered: Optional[np.ndarray] = None  # the synthesis of the per-mode transports of the fields' sources
     view_mode_status: Optional[np.ndarray] = None          # [M + 1, B] status of the solve of every Fourier mode (row 0 is `status`)
     beam_slant: Optional[np.ndarray] = None   # [B, L] (beam='spherical'): slant optical depth of the direct beam at every level
+    bounces: Optional[np.ndarray] = None      # [B] (surface='brdf'): the ground reflection at which the column's term fell below tol
+    bounce_ratio: Optional[np.ndarray] = None  # [B] ... and the last term's share of the sum on the TOA-up and surface-down lanes
 
 
 _solvers = {}
@@ -174,13 +178,14 @@ def _beam_args(beam, earth_radius, azimuths=None, view_mu=None, view_azimuths=No
 
 
 def _solve_resident(s: Solver, tau, P0a, P0r, seed, epilogue, tol=1e-4, save_orders=False, device=0, fetch_field=True, want=(),
-                    z_profile=None, keep_device=False):
+                    z_profile=None, keep_device=False, post=None):
     """A solve of handle `s` (grid, phase matrices and columns set) that stays on the device, on torch's current stream: the
     uploads, `seed(up, dev, d_tau, B, p0a, p0r)` -> (d_I1 [B, L, 2N] the field the order loop starts from, dict of further
     tensors to return) or None for the handle's own first order, `solve_device` (with save_orders twice: the first pass gives
     n, the second stores exactly max(n) orders per column, as Solver.solve), and for the names `want` of `Solver.epilogue`
     (`z_profile` for the heating rate) `epilogue(d_tau, d_I, d_z, the seed's tensors, the five output addresses, B)`.  `P0a`, `P0r` may be None
-    (address 0).  Returns (SolveResult, the seed's tensors on the host, dict of the wanted epilogue arrays); keep_device=True:
+    (address 0).  `post(up, dev, d_tau, d_I, d_n, d_st, B, p0a, p0r)` -> dict of further tensors runs between the solve and the
+    epilogue and may add to the field in place (the BRDF ground's bounce loop).  Returns (SolveResult, the seed's tensors on the host, dict of the wanted epilogue arrays); keep_device=True:
     the torch tensors {"I", "n", "status", "tau"} and the seed's instead, left on the device.  The handle goes back to its own
     stream and to its default per-order storage, also on error."""
     import torch
@@ -211,6 +216,8 @@ def _solve_resident(s: Solver, tau, P0a, P0r, seed, epilogue, tol=1e-4, save_ord
                 s.set_saved_orders(slots)
                 d_sv = torch.zeros((B, slots, L, D), dtype=torch.float64, device=dev)
                 solve(d_sv)
+            if post is not None:
+                extra = dict(extra, **post(up, dev, d_tau, d_I, d_n, d_st, B, p0a, p0r))
             epi = {}
             want = [k for k in ("flux_down", "flux_up", "diffusivity", "heating_rate", "net_toa")
                     if k in set(want) and not (k == "heating_rate" and z_profile is None)]
@@ -350,6 +357,141 @@ def solve_thermal(s: Solver, tau, planck, planck_surface, emissivity=None, tol=1
     return r if keep_device else (r[0], r[2])
 
 
+MAX_BOUNCES = 32
+BRDF_NPHI = 65
+
+
+def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None, view_azimuths=None, mode_batch=False,
+               mode_chunk=None, beam="plane", source="solar", first_order="coded", devices=None, save_orders=False):
+    """Checks of surface='brdf', made before any handle exists: None for every other surface, else a namespace (kind, params,
+    R [N-1, N-1] or None, r0 [B, N-1] or None, scale [B]) of the ground `brdf` with `grd_alb` as its per-column scale."""
+    if not (isinstance(surface, str) and surface == "brdf"):
+        if brdf is not None:
+            raise ValueError("brdf belongs to surface='brdf'")
+        return None
+    if brdf is None:
+        raise ValueError("surface='brdf' needs brdf: 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0)")
+    if azimuths is not None or mode_batch or mode_chunk is not None or view_azimuths is not None:
+        raise ValueError("surface='brdf' is not available with azimuths / mode_batch / view_azimuths: only the azimuth mean "
+                         "(mode m = 0) of the BRDF is built")
+    if view_mu is not None:
+        raise ValueError("surface='brdf' is not available with view_mu: the view stage has no ground-reflection term")
+    if beam != "plane":
+        raise ValueError("surface='brdf' is not available with beam='spherical': the reflected beam is the plane one")
+    if source != "solar":
+        raise ValueError("surface='brdf' is not available with source='thermal': the ground's emission over a BRDF is not built")
+    if first_order != "coded":
+        raise ValueError("surface='brdf' is not available with first_order='readme': the series starts from the black-ground solve")
+    if devices is not None and len(devices) > 1:
+        raise ValueError("surface='brdf' is not available with devices=[...]: solve each shard with SOS_Aer_batch(device=...)")
+    if save_orders:
+        raise ValueError("surface='brdf' is not available with save_orders: the field is a sum over ground reflections, each "
+                         "with orders of its own")
+    N = int(nb_angles)
+    if N < 4:
+        raise ValueError("surface='brdf' needs nb_angles >= 4 (got %d)" % N)
+    try:
+        scale = np.asarray(grd_alb, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("grd_alb must be numbers") from None
+    if scale.shape not in ((), (1,), (B,)) or not np.all(np.isfinite(scale)) or np.any(scale < 0):
+        raise ValueError("grd_alb (the ground's per-column scale under surface='brdf') must be finite, >= 0 and a scalar or [B] = (%d,)" % B)
+    scale = np.ascontiguousarray(np.broadcast_to(scale.reshape(-1) if scale.ndim else scale, (B,)))
+    spec = SimpleNamespace(kind=None, params=(), R=None, r0=None, scale=scale)
+    if isinstance(brdf, str):
+        if brdf != "lambertian":
+            raise ValueError("brdf must be 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0) (got %r)" % (brdf,))
+        spec.kind = "lambertian"
+        return spec
+    if not isinstance(brdf, (tuple, list)) or len(brdf) < 2:
+        raise ValueError("brdf must be 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0) (got %r)" % (brdf,))
+    if isinstance(brdf[0], str):
+        if brdf[0] != "rpv" or len(brdf) != 4:
+            raise ValueError("a named brdf is 'lambertian' or ('rpv', rho0, k, theta) (got %r)" % (brdf,))
+        try:
+            rho0, k, theta = (float(x) for x in brdf[1:])
+        except (TypeError, ValueError):
+            raise ValueError("the RPV parameters rho0, k, theta must be numbers (got %r)" % (brdf[1:],)) from None
+        if not (np.isfinite(rho0) and rho0 > 0 and np.isfinite(k) and k > 0 and abs(theta) < 1):
+            raise ValueError("RPV parameters rho0=%g, k=%g, theta=%g: need rho0 > 0, k > 0, |theta| < 1" % (rho0, k, theta))
+        if np.any(scale != 1):
+            raise ValueError("brdf=('rpv', ...) carries its amplitude in rho0: grd_alb must be omitted or 1")
+        spec.kind, spec.params = "rpv", (rho0, k, theta)
+        return spec
+    if len(brdf) != 2:
+        raise ValueError("brdf as arrays is the pair (R [N-1, N-1], r0 [N-1] or [B, N-1])")
+    try:
+        R, r0 = np.asarray(brdf[0], dtype=np.float64), np.asarray(brdf[1], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("brdf as arrays is the pair (R [N-1, N-1], r0 [N-1] or [B, N-1]) of numbers") from None
+    if R.shape != (N - 1, N - 1) or r0.shape not in ((N - 1,), (B, N - 1)):
+        raise ValueError("brdf as arrays: R must be [N-1, N-1] = (%d, %d) and r0 [N-1] or [B, N-1] (got %s and %s)"
+                         % (N - 1, N - 1, R.shape, r0.shape))
+    if not (np.all(np.isfinite(R)) and np.all(np.isfinite(r0))):
+        raise ValueError("brdf as arrays: R and r0 must be finite")
+    spec.R, spec.r0 = R, np.ascontiguousarray(np.broadcast_to(r0, (B, N - 1)))
+    return spec
+
+
+def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BOUNCES, nphi=BRDF_NPHI, device=0, fetch_field=True,
+               want=(), z_profile=None, keep_device=False):
+    """The solve of handle `s` (grid, phase matrices set; columns set over a BLACK ground: the specular surface with albedo 0)
+    over the BRDF GROUND `spec` of `_brdf_args`: the plain solve, then on the device the series in ground
+    reflections -- ground source of the last term's downward surface row (and, in the first bounce, of the direct beam) ->
+    its unscattered field -> the order loop fed that field -> sum -- until every column's term is below `tol` of the sum on
+    the TOA-up and surface-down lanes, or `max_bounces`; B ratios come back per bounce, nothing else.  Every column runs every
+    bounce of the batch.  `want`: names of `Solver.epilogue` from the summed field (`epilogue_device`: over the black ground its
+    reflected-beam term is zero; the reflected beam is in the field).  Returns (SolveResult, {"bounces" [B]: the bounce at
+    which the column fell below tol, "bounce_ratio" [B]: its last ratio}, dict of the wanted epilogue arrays); keep_device=True:
+    the torch tensors {"I", "n", "status", "tau", "bounces", "bounce_ratio"} instead.  n is the black solve's; a column still
+    above tol at the cap has status COL_MAXORDERS, one whose ground rows fail the mu -> 0 search COL_INDEXERROR."""
+    import torch
+    if s.single_slab:
+        raise ValueError("surface='brdf' is not available for the single slab: it has no ground")
+    max_bounces = int(max_bounces)
+    if max_bounces < 1:
+        raise ValueError("max_bounces must be >= 1 (got %d)" % max_bounces)
+
+    def post(up, dev, d_tau, d_I, d_n, d_st, B, p0a, p0r):
+        L, M = d_tau.shape[1], s.N - 1
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        d_scale = up(spec.scale)
+        if spec.R is None:
+            d_mu0, d_R, d_r0 = up(np.broadcast_to(np.asarray(mu0, dtype=np.float64), (B,))), f64(M, M), f64(B, M)
+            s.brdf_operator_device(spec.kind, d_R.data_ptr(), spec.params, nphi)
+            s.brdf_beam_device(spec.kind, d_mu0.data_ptr(), d_r0.data_ptr(), spec.params, nphi, B=B)
+        else:
+            d_R, d_r0 = up(spec.R.T), up(spec.r0)            # (the device reads the lanes i of one j contiguously)
+        d_S, d_G, d_Ik, d_ratio = f64(B, M), f64(B, L, s.D), f64(B, L, s.D), f64(B)
+        d_nk, d_stk, d_gst = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(3))
+        bounces = np.zeros(B, dtype=np.int32)
+        src = d_I                                            # bounce 1 reflects the black solve's surface row
+        for k in range(1, max_bounces + 1):
+            s.ground_source_device(src.data_ptr(), d_tau.data_ptr(), d_R.data_ptr(), d_S.data_ptr(),
+                                   d_r0.data_ptr() if k == 1 else 0, d_scale.data_ptr(), B=B)
+            s.ground_first_order_device(d_tau.data_ptr(), d_S.data_ptr(), d_G.data_ptr(), d_gst.data_ptr(), B=B)
+            s.solve_device(d_tau.data_ptr(), p0a, p0r, d_Ik.data_ptr(), tol=tol, d_I1=d_G.data_ptr(), d_n_orders=d_nk.data_ptr(),
+                           d_status=d_stk.data_ptr())
+            s.bounce_accumulate_device(d_Ik.data_ptr(), d_I.data_ptr(), d_ratio.data_ptr(), B=B)
+            d_st.copy_(torch.where(d_st != 0, d_st, torch.where(d_gst != 0, d_gst, d_stk)))
+            src = d_Ik
+            s.synchronize()
+            ratio = d_ratio.cpu().numpy()
+            bounces[(bounces == 0) & (ratio < tol)] = k
+            if np.all(ratio < tol):
+                break
+        late = torch.from_numpy(bounces == 0).to(dev) & (d_st == 0)
+        d_st.copy_(torch.where(late, torch.full_like(d_st, _lib.COL_MAXORDERS), d_st))
+        bounces[bounces == 0] = k
+        return {"bounces": torch.from_numpy(bounces).to(dev), "bounce_ratio": d_ratio}
+
+    def epilogue(d_tau, d_I, d_zp, extra, out, B):
+        s.epilogue_device(d_tau, d_I, d_zp, "crit", *out)
+
+    r = _solve_resident(s, tau, P0a, P0r, None, epilogue, tol, False, device, fetch_field, want, z_profile, keep_device, post=post)
+    return r if keep_device else (r[0], r[1], r[2])
+
+
 def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, alb_aer=1.0, z0=120, z_up=25, z_down=17,
                   nb_layers=200, nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7,
                   mie_atm=None, mie_aer=None,
@@ -358,7 +500,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   n_modes=None, nphi_modes=None, levels=(0, -1), aer_set=None, mode_batch=False, mode_chunk=None,
                   view_mu=None, view_levels=(0, -1), view_quadrature="grid", view_azimuths=None,
                   view_first_order="exact", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None,
-                  planck_surface=None, surface_emissivity=None) -> BatchResult:
+                  planck_surface=None, surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -428,10 +570,26 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     `view_mu`, I_view_first is the emission at the view lanes and I_view_scattered the view stage on I.  The orders n >= 1
     inherit the reference's mu -> 0 treatments, so the lanes next to mu = 0 may overshoot max(planck).  Not with `azimuths`,
     `mode_batch`, `view_azimuths` (emission has only the m = 0 mode), `beam='spherical'`, `first_order='readme'` or several
-    `devices`.  `source='solar'` (default) is the code path as it was."""
+    `devices`.  `source='solar'` (default) is the code path as it was.
+
+    `surface='brdf'` with `brdf=`: a GROUND WHOSE REFLECTANCE DEPENDS ON THE DIRECTIONS (`solve_brdf`), as a
+    series in ground reflections around the unchanged order loop: the columns are solved over a black ground, then per
+    reflection the last term's downward surface row (and once the direct beam) is reflected through the BRDF's azimuth-mean
+    operator and the order loop transports and scatters that ground source, until every column's term is below `tol` of the
+    sum or `max_bounces` (32; a column still above has status COL_MAXORDERS).  `brdf='lambertian'`: grd_alb[b] is the albedo,
+    so an albedo sweep is one batch; `brdf=('rpv', rho0, k, theta)`: Rahman-Pinty-Verstraete with its hot spot (grd_alb
+    omitted or 1); `brdf=(R, r0)`: a caller's operator R [N-1, N-1] (upward lane N+1+i from downward lane j, the flux
+    quadrature folded in) and beam row r0 [N-1] or [B, N-1], grd_alb a plain scale.  BatchResult.bounces / bounce_ratio [B]; n
+    is the black solve's.  Not with `azimuths`, `view_mu`, `view_azimuths`, `mode_batch`, `beam='spherical'`,
+    `source='thermal'`, `first_order='readme'`, `save_orders` or several `devices`."""
     thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
                             _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if source == "thermal" else 0,
                             nb_layers, azimuths, view_azimuths, mode_batch, mode_chunk, beam, first_order, devices)
+    ground = _brdf_args(surface, brdf, grd_alb, nb_angles,
+                        _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if surface == "brdf" else 0,
+                        azimuths, view_mu, view_azimuths, mode_batch, mode_chunk, beam, source, first_order, devices, save_orders)
+    if ground:
+        surface, grd_alb = "specular", 0.0                   # the series' solves run over a black ground
     spherical = _beam_args(beam, earth_radius, azimuths, view_mu, view_azimuths, mode_batch, mode_chunk, first_order, devices)
     if view_azimuths is not None or view_first_order != "exact":
         vphi, vM, vnphi = _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_modes, nphi_modes, mode_batch,
@@ -479,9 +637,12 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                                                       mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device,
                                                       aer_set=aer_set)
     sigma = None
+    bx = {}
     try:
         if spherical:
             r, sigma, _ = solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, int(nb_layers)), earth_radius, tol, save_orders, device)
+        elif ground:
+            r, bx, _ = solve_brdf(s, tau, P0a, P0r, ground, mu0, tol, max_bounces, device=device)
         elif thermal:
             r, _ = solve_thermal(s, tau, *thermal, tol=tol, save_orders=save_orders, device=device)
         else:
@@ -494,7 +655,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
             _columns_to_set0(s, tau.shape[0])
     if raise_on_error:
         _raise_status(r.status, N)
-    out = BatchResult(I=r.I, n=r.n, status=r.status, tau=tau, mu=mu, idx_up=iu, idx_down=idn, I_saved=r.I_saved, beam_slant=sigma)
+    out = BatchResult(I=r.I, n=r.n, status=r.status, tau=tau, mu=mu, idx_up=iu, idx_down=idn, I_saved=r.I_saved, beam_slant=sigma,
+                      bounces=bx.get("bounces"), bounce_ratio=bx.get("bounce_ratio"))
     if azimuths is not None:
         mu0v = np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
         if mode_batch:
@@ -1143,18 +1305,26 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
                        nb_layers=200, nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7,
                        mie_atm=None, mie_aer=None, P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular",
                        tol=1e-4, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar",
-                       planck=None, planck_surface=None, surface_emissivity=None, aer_set=None):
+                       planck=None, planck_surface=None, surface_emissivity=None, aer_set=None, brdf=None,
+                       max_bounces=MAX_BOUNCES):
     """`SOS_Aer_batch` with the RESULT LEFT ON THE DEVICE: returns ({"I": [B, L, 2N] float64, "n": [B] int32, "status": [B]
     int32, "tau": [B, L]} as torch tensors on cuda:`device`, (mu, idx_up, idx_down)).  The solve is enqueued on torch's
     current stream for that device, so the tensors are ordered like any torch result.  What `dist.solve_sharded` gathers.
     `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of `SOS_Aer_batch`; the dict then also holds
     "beam_slant" [B, L].  `source='thermal'` (with `planck`, `planck_surface`, `surface_emissivity`): the thermal field of
     `SOS_Aer_batch`.  `aer_set` [B] with a list of names in `aer_phase_fun` (or a stack `P_aer`): several aerosols in one batch,
-    as in `SOS_Aer_batch`; the cached handle's columns are back on aerosol set 0 when the call returns, also on error."""
+    as in `SOS_Aer_batch`; the cached handle's columns are back on aerosol set 0 when the call returns, also on error.
+    `surface='brdf'` with `brdf=` (and `max_bounces`): the BRDF ground of `SOS_Aer_batch`; the dict then also holds "bounces"
+    and "bounce_ratio" [B]."""
     thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
                             _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if source == "thermal" else 0,
                             nb_layers, beam=beam)
     spherical = _beam_args(beam, earth_radius)
+    ground = _brdf_args(surface, brdf, grd_alb, nb_angles,
+                        _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if surface == "brdf" else 0,
+                        beam=beam, source=source)
+    if ground:
+        surface, grd_alb = "specular", 0.0
     s, tau, P0a, P0r, mu, iu, idn, N = _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
                                                       nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm,
                                                       mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device,
@@ -1165,6 +1335,8 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
                                    keep_device=True), (mu, iu, idn)
         if thermal:
             return solve_thermal(s, tau, *thermal, tol=tol, keep_device=True, device=device), (mu, iu, idn)
+        if ground:
+            return solve_brdf(s, tau, P0a, P0r, ground, mu0, tol, max_bounces, device=device, keep_device=True), (mu, iu, idn)
         return _solve_resident(s, tau, P0a, P0r, None, None, tol, device=device, keep_device=True), (mu, iu, idn)
     finally:
         if aer_set is not None:
@@ -1175,7 +1347,7 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
                    atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, mie_atm=None, mie_aer=None, P_atm=None,
                    P_aer=None, surface="specular", tol=1e-4, max_orders=256, device=0, raise_on_error=True, beam="plane",
                    earth_radius=EARTH_RADIUS_KM, source="solar", planck=None, planck_surface=None,
-                   surface_emissivity=None) -> BatchResult:
+                   surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES) -> BatchResult:
     """Columns with SEVERAL aerosol layers (the reference has one): `slabs` = [(z_up, z_down, tauStar_aer,
     alb_aer), ...] from the top down, shared by the B columns of the arrays `mu0`, `grd_alb`.  Every formula of the path is
     evaluated per zone as the reference writes it for its three zones; one layer gives `SOS_Aer_batch`'s result bit for
@@ -1185,11 +1357,16 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
     that phase function exactly as before.  `P_aer` cannot be combined with a fifth entry.  `idx_up` / `idx_down` of the
     result are those of the first layer.  `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of
     `SOS_Aer_batch`, BatchResult.beam_slant [B, L].  `source='thermal'` (with `planck`, `planck_surface`,
-    `surface_emissivity`): the thermal field of `SOS_Aer_batch`; every aerosol layer emits with its own albedo."""
+    `surface_emissivity`): the thermal field of `SOS_Aer_batch`; every aerosol layer emits with its own albedo.
+    `surface='brdf'` with `brdf=` (and `max_bounces`): the BRDF ground of `SOS_Aer_batch`; BatchResult.bounces / bounce_ratio."""
     from .inputs import tau_profile_slabs
     thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
                             _batch_width(mu0, grd_alb) if source == "thermal" else 0, nb_layers, beam=beam)
     spherical = _beam_args(beam, earth_radius)
+    ground = _brdf_args(surface, brdf, grd_alb, nb_angles, _batch_width(mu0, grd_alb) if surface == "brdf" else 0, beam=beam,
+                        source=source)
+    if ground:
+        surface, grd_alb = "specular", np.zeros(_batch_width(mu0, grd_alb))
     mu0, grd_alb = np.broadcast_arrays(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), np.atleast_1d(np.asarray(grd_alb, dtype=np.float64)))
     B, L, N = mu0.shape[0], int(nb_layers), int(nb_angles)
     mu = direction_grid(N)
@@ -1240,8 +1417,11 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
         if own:
             s.set_aerosol_sets(np.tile(zset, (B, 1)))
         sigma = None
+        bx = {}
         if spherical:
             r, sigma, _ = solve_spherical(s, np.tile(tau, (B, 1)), P0a, P0r, np.linspace(z0, 0, L), earth_radius, tol, device=device)
+        elif ground:
+            r, bx, _ = solve_brdf(s, np.tile(tau, (B, 1)), P0a, P0r, ground, mu0, tol, max_bounces, device=device)
         elif thermal:
             r, _ = solve_thermal(s, np.tile(tau, (B, 1)), *thermal, tol=tol, device=device)
         else:
@@ -1252,20 +1432,23 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
     if raise_on_error:
         _raise_status(r.status, N)
     return BatchResult(I=r.I, n=r.n, status=r.status, tau=np.tile(tau, (B, 1)), mu=mu, idx_up=int(r0[1]), idx_down=int(r0[2]) - 1,
-                       beam_slant=sigma)
+                       beam_slant=sigma, bounces=bx.get("bounces"), bounce_ratio=bx.get("bounce_ratio"))
 
 
 def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=None, P_aer=None, P0_aer=None, device=0,
             first_order="coded", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None, planck_surface=None,
-            surface_emissivity=None, **overrides) -> ColumnResult:
+            surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES, **overrides) -> ColumnResult:
     """One column with the reference's parameter names (spec:19-96).  `surface` selects the file of
     the reference that would be run ('specular' | 'lambertian'); P*/P0* accept pre-built phase
     arrays.  `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of `SOS_Aer_batch`;
     ColumnResult.beam_slant [L].  `source='thermal'` (with `planck` [L], `planck_surface`, `surface_emissivity`): the thermal
-    field of `SOS_Aer_batch`."""
+    field of `SOS_Aer_batch`.  `surface='brdf'` with `brdf=` (and `max_bounces`): the BRDF ground of `SOS_Aer_batch`;
+    ColumnResult.bounces / bounce_ratio; I_saved is None (the field is a sum over ground reflections) and n the black solve's."""
     _thermal_args(source, planck, planck_surface, surface_emissivity, 1,
                   overrides.get("nb_layers", DEFAULTS["nb_layers"]), beam=beam, first_order=first_order)
     _beam_args(beam, earth_radius, first_order=first_order)
+    ground = _brdf_args(surface, brdf, overrides.get("grd_alb", DEFAULTS["grd_alb"]), overrides.get("nb_angles", DEFAULTS["nb_angles"]),
+                        1, beam=beam, source=source, first_order=first_order)
     unknown = set(overrides) - set(DEFAULTS)
     if unknown:
         raise TypeError("unknown parameter(s): %s" % ", ".join(sorted(unknown)))
@@ -1279,9 +1462,11 @@ def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=Non
                       mie_atm=mie["atm"], mie_aer=mie["aer"], P_atm=P_atm, P_aer=P_aer,
                       P0_atm=None if P0_atm is None else np.asarray(P0_atm)[None],
                       P0_aer=None if P0_aer is None else np.asarray(P0_aer)[None],
-                      surface=surface, tol=tol, max_orders=max_orders, save_orders=True, device=device, first_order=first_order,
+                      surface=surface, tol=tol, max_orders=max_orders, save_orders=not ground, device=device, first_order=first_order,
                       beam=beam, earth_radius=earth_radius, source=source, planck=planck, planck_surface=planck_surface,
-                      surface_emissivity=surface_emissivity)
+                      surface_emissivity=surface_emissivity, brdf=brdf, max_bounces=max_bounces)
     n = int(r.n[0])
-    return ColumnResult(I=r.I[0], I_saved=r.I_saved[0, :n].copy(), n=n, tau=r.tau[0], mu=r.mu, idx_up=r.idx_up,
-                        idx_down=r.idx_down, status=int(r.status[0]), beam_slant=None if r.beam_slant is None else r.beam_slant[0])
+    return ColumnResult(I=r.I[0], I_saved=None if ground else r.I_saved[0, :n].copy(), n=n, tau=r.tau[0], mu=r.mu, idx_up=r.idx_up,
+                        idx_down=r.idx_down, status=int(r.status[0]), beam_slant=None if r.beam_slant is None else r.beam_slant[0],
+                        bounces=None if r.bounces is None else int(r.bounces[0]),
+                        bounce_ratio=None if r.bounce_ratio is None else float(r.bounce_ratio[0]))

@@ -81,6 +81,7 @@ class Solver:
         self.mu = None
         self._P = (None, None)
         self._p0_zones = 0          # > 0: P0_aer is [B, _p0_zones, 2N] (set_aerosol_sets with a zone table)
+        self.single_slab = False    # the current columns are set_columns_single_slab's
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -257,6 +258,7 @@ class Solver:
         check(lib().sosrt_set_columns(self._h, B, _lib.GEOM_THREE_ZONE, sf, _ptr(iu), _ptr(idn), *[_ptr(x) for x in v]))
         self.B = B
         self._p0_zones = 0
+        self.single_slab = False
 
     def set_columns_zones(self, zone_r0, zone_mix, mu0, grd_alb, alb_atm, dtau_atm, zone_alb_aer, zone_dtau_aer, tauStar_tot,
                           nz=None, surface="specular"):
@@ -276,6 +278,7 @@ class Solver:
                                             _ptr(v[2]), _ptr(v[3]), _ptr(zwr), _ptr(zdt), _ptr(v[4])))
         self.B = B
         self._p0_zones = 0
+        self.single_slab = False
 
     def set_columns_single_slab(self, mu0, alb, tauStar):
         """Single homogeneous slab over a black surface (I1_In:13-130)."""
@@ -285,6 +288,7 @@ class Solver:
                                       _ptr(a), None, None, None, _ptr(t)))
         self.B = B
         self._p0_zones = 0
+        self.single_slab = True
 
     def _p0_shape(self):
         return (self.B, self._p0_zones, self.D) if self._p0_zones else (self.B, self.D)
@@ -459,6 +463,48 @@ class Solver:
         multiply-add per k; d_weight, d_scale [K, C] or 0 for ones.  The same bits however K is split over accumulating calls."""
         check(lib().sosrt_band_reduce_dev(self._h, int(C), int(K), int(M), _vp(d_weight), _vp(d_scale), _vp(d_x), _vp(d_out),
                                           int(bool(accumulate))))
+
+    # ---- BRDF ground (sosrt.h; DESIGN section 20) --------------------------------------------------------
+    _BRDF_KINDS = {"lambertian": _lib.BRDF_LAMBERTIAN, "rpv": _lib.BRDF_RPV}
+
+    def _brdf_kind(self, kind, params):
+        k = self._BRDF_KINDS.get(kind)
+        if k is None:
+            raise ValueError("BRDF kind must be 'lambertian' or 'rpv' (got %r)" % (kind,))
+        p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64))) if np.size(params) else np.zeros(0)
+        return k, p
+
+    def brdf_operator_device(self, kind, d_R_out: int, params=(), nphi=65):
+        """The reflection operator of a named BRDF ('lambertian', or 'rpv' with params (rho0, k, Theta)), its azimuth mean on
+        `nphi` trapezoid nodes and the flux quadrature folded in: d_R_out [N-1, N-1] with element (j, i) = 2 w_j |mu_j|
+        rho_bar(mu[N+1+i], |mu_j|), the upward lanes i of one downward lane j contiguous.  Enqueued on the handle's stream."""
+        k, p = self._brdf_kind(kind, params)
+        check(lib().sosrt_brdf_operator_dev(self._h, k, _ptr(p) if p.size else None, int(p.size), int(nphi), _vp(d_R_out)))
+
+    def brdf_beam_device(self, kind, d_mu0: int, d_r0_out: int, params=(), nphi=65, B: Optional[int] = None):
+        """The reflection of the direct beam: d_r0_out [B, N-1] = rho_bar(mu[N+1+i], d_mu0[b])."""
+        k, p = self._brdf_kind(kind, params)
+        check(lib().sosrt_brdf_beam_dev(self._h, int(self.B if B is None else B), k, _ptr(p) if p.size else None, int(p.size),
+                                        int(nphi), _vp(d_mu0), _vp(d_r0_out)))
+
+    def ground_source_device(self, d_I: int, d_tau: int, d_R: int, d_S_out: int, d_r0: int = 0, d_scale: int = 0,
+                             B: Optional[int] = None):
+        """d_S_out [B, N-1] = scale[b] (R I[b, L-1, 0 .. N-2] + r0[b] exp(-tau[b, L-1] / mu0[b])) with the columns' mu0; d_r0 0:
+        no beam term; d_scale 0: 1.  d_R as `brdf_operator_device` writes it."""
+        check(lib().sosrt_ground_source_dev(self._h, int(self.B if B is None else B), _vp(d_I), _vp(d_tau), _vp(d_R), _vp(d_r0),
+                                            _vp(d_scale), _vp(d_S_out)))
+
+    def ground_first_order_device(self, d_tau: int, d_S: int, d_G_out: int, d_status: int = 0, B: Optional[int] = None):
+        """The unscattered upward field of the ground source d_S [B, N-1], with the mu -> 0+ blend of the order loop on every
+        row: d_G_out [B, L, 2N] is the `d_I1` of `solve_device` over a black ground; d_status [B] int32 (COL_INDEXERROR where
+        the blend's search leaves the row)."""
+        check(lib().sosrt_ground_first_order_dev(self._h, int(self.B if B is None else B), _vp(d_tau), _vp(d_S), _vp(d_G_out),
+                                                 _vp(d_status)))
+
+    def bounce_accumulate_device(self, d_Ik: int, d_I_total: int, d_ratio_out: int, B: Optional[int] = None):
+        """d_I_total += d_Ik ([B, L, 2N]); d_ratio_out [B]: the larger of max |Ik| / max |total| on the upward lanes of row 0 and
+        on the downward lanes of row L-1."""
+        check(lib().sosrt_bounce_accumulate_dev(self._h, int(self.B if B is None else B), _vp(d_Ik), _vp(d_I_total), _vp(d_ratio_out)))
 
     # ---- phase functions on the device (phase:68-292) ----------------------------
     _KINDS ={"iso": _lib.PHASE_ISO, "rayleigh": _lib.PHASE_RAYLEIGH, "hg": _lib.PHASE_HG, "table": _lib.PHASE_TABLE}
