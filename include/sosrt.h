@@ -641,7 +641,7 @@ int sosrt_band_reduce_dev(sosrt_t* h, int C, int K, int M, const double* d_weigh
  * solve started from that field (sosrt_solve_dev, d_I1_in).  Five stages beside the solve, detected by symbol (SOSRT_VERSION is
  * unchanged); all are enqueued on the handle's stream and write their outputs only -- the handle's columns, resident field,
  * order targets and phase state stay as they were (like every stage, a call ends the run of adjacent launches that the
- * handle's profiling slots keep track of).  Only the azimuth mean (mode m = 0) of the BRDF is built.
+ * handle's profiling slots keep track of).  These build the azimuth mean (mode m = 0) of the BRDF; its modes m >= 1 follow below.
  *
  * Lanes: i = 0 .. N-2 is the upward direction N+1+i, j = 0 .. N-2 the downward direction j; the two mu = 0 nodes (N-1, N) take
  * no part.  rho_bar(a, b) = (1 / pi) int_0^pi rho(a, b, phi) dphi by the trapezoid rule on nphi nodes of [0, pi].
@@ -688,6 +688,30 @@ int sosrt_ground_first_order_dev(sosrt_t* h, int B, const double* d_tau /*[B][L]
                                  double* d_G_out /*[B][L][2N]*/, int* d_status /*[B] or NULL*/);
 int sosrt_bounce_accumulate_dev(sosrt_t* h, int B, const double* d_Ik /*[B][L][2N]*/, double* d_I_total /*[B][L][2N]*/,
                                 double* d_ratio_out /*[B]*/);
+
+/* ---- BRDF ground, azimuth-resolved: the reflection modes m >= 1 --------------------------------------------
+ * The Fourier modes in azimuth of the BRDF, for the azimuth-resolved radiance over a BRDF ground.  With the ring angle phi of the
+ * azimuth modes above (phi = 0 at an upward mu = mu0 is back-scatter, which is RPV's hot spot phi = 0),
+ *     rho^m(a, b) = (1 / pi) int_0^pi rho(a, b, phi) cos(m phi) dphi
+ * by the trapezoid rule on the nphi nodes phi_q = pi q / (nphi - 1) of rho_bar = rho^0.  cos(m phi_q) is taken of the integer m q
+ * reduced modulo 2 (nphi - 1): node nphi - 1 gives (-1)^m and m = 0 gives 1 exactly, so MODE 0 HAS THE BITS OF
+ * sosrt_brdf_operator_dev / sosrt_brdf_beam_dev at the same nphi.  rho at a (pair, node) is evaluated once per launch for up to 8
+ * modes; more modes are further launches.
+ *     sosrt_brdf_operator_modes_dev   R^m(i, j) = 2 w_j |mu_j| rho^m(mu_i, |mu_j|), d_R_out[m - m_first][j (N-1) + i]
+ *     sosrt_brdf_beam_modes_dev       r0^m[b][i] = rho^m(mu_i, mu0[b]),             d_r0_out[m - m_first][b][i]
+ * The ground source of mode m of the radiance is
+ *     S^m = scale ((-1)^m R^m I^m[L-1] + [bounce 1] r0^m exp(-tau* / mu0)):
+ * the down-welling lane and the reflected lane stand at the BRDF's relative azimuth phi_i - phi_j + pi, the pi of the fold of the
+ * phase matrices, so the operator carries (-1)^m and the beam row, like P0, none.  sign_odd != 0 writes mode m as (-1)^m R^m
+ * (negation is exact): what sosrt_ground_source_dev takes for mode m.  Everything after S^m is the series above unchanged, with
+ * ((-1)^m P^m, order targets) on the handle.  The modes of a Lambertian ground vanish for m >= 1 (to rounding: <= 1e-15).
+ * Modes: m_first >= 0, m_count >= 1, m_first + m_count - 1 <= min(SOSRT_MAX_MODES, nphi - 2).  Refused as the two entry points
+ * above refuse, and for a range of modes outside that, with SOSRT_E_INVALID, a message and nothing written.  Enqueued on the
+ * handle's stream; they write their outputs only. */
+int sosrt_brdf_operator_modes_dev(sosrt_t* h, int kind, const double* params /*host*/, int nparams, int nphi, int m_first, int m_count,
+                                  int sign_odd, double* d_R_out /*[m_count][N-1][N-1], [m][j][i]*/);
+int sosrt_brdf_beam_modes_dev(sosrt_t* h, int B, int kind, const double* params /*host*/, int nparams, int nphi, int m_first,
+                              int m_count, const double* d_mu0 /*[B]*/, double* d_r0_out /*[m_count][B][N-1]*/);
 
 /* ---- multi-GPU: one process per GPU, columns sharded, ONE collective at the end ------------------
  * Nothing in SOS_Aer_main_specular.py:104-458 couples columns, so the order loop never communicates; these entry

@@ -11,7 +11,7 @@
 
 using namespace sosrt;
 
-// what the five entry points refuse alike; every check comes before the first launch, so a refused call writes nothing
+// what the entry points refuse alike; every check comes before the first launch, so a refused call writes nothing
 // (per_column: the call takes a column count; the operator does not)
 static int brdf_check(sosrt_handle* h, int B, bool per_column, const char* what) {
     if (int e = need_gpu(h)) return e;
@@ -70,6 +70,43 @@ int sosrt_brdf_beam_dev(sosrt_t* h, int B, int kind, const double* params, int n
     HIPCHK(hipSetDevice(h->device));
     prof_break(h);
     launch_brdf_beam(h->stream, h->g, B, bp, nphi, d_mu0, d_r0_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the range of Fourier modes the two mode builders take (sosrt.h)
+static int brdf_mode_range(int m_first, int m_count, int nphi, const char* what) {
+    const int m_max = SOSRT_MAX_MODES < nphi - 2 ? SOSRT_MAX_MODES : nphi - 2;
+    if (m_first < 0 || m_count < 1 || m_first > m_max || m_count > m_max - m_first + 1)
+        return fail(SOSRT_E_INVALID, "%s: modes m_first=%d, m_count=%d: need m_first >= 0, m_count >= 1 and the last mode <= "
+                                     "min(SOSRT_MAX_MODES, nphi - 2) = %d", what, m_first, m_count, m_max);
+    return 0;
+}
+
+int sosrt_brdf_operator_modes_dev(sosrt_t* h, int kind, const double* params, int nparams, int nphi, int m_first, int m_count,
+                                  int sign_odd, double* d_R_out) {
+    if (int e = brdf_check(h, 0, false, "sosrt_brdf_operator_modes_dev")) return e;
+    BrdfParams bp;
+    if (int e = brdf_params(kind, params, nparams, nphi, bp, "sosrt_brdf_operator_modes_dev")) return e;
+    if (int e = brdf_mode_range(m_first, m_count, nphi, "sosrt_brdf_operator_modes_dev")) return e;
+    if (!d_R_out) return fail(SOSRT_E_INVALID, "sosrt_brdf_operator_modes_dev: null argument");
+    HIPCHK(hipSetDevice(h->device));
+    prof_break(h);
+    launch_brdf_operator_modes(h->stream, h->g, bp, nphi, m_first, m_count, sign_odd, d_R_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_brdf_beam_modes_dev(sosrt_t* h, int B, int kind, const double* params, int nparams, int nphi, int m_first, int m_count,
+                              const double* d_mu0, double* d_r0_out) {
+    if (int e = brdf_check(h, B, true, "sosrt_brdf_beam_modes_dev")) return e;
+    BrdfParams bp;
+    if (int e = brdf_params(kind, params, nparams, nphi, bp, "sosrt_brdf_beam_modes_dev")) return e;
+    if (int e = brdf_mode_range(m_first, m_count, nphi, "sosrt_brdf_beam_modes_dev")) return e;
+    if (!d_mu0 || !d_r0_out) return fail(SOSRT_E_INVALID, "sosrt_brdf_beam_modes_dev: null argument");
+    HIPCHK(hipSetDevice(h->device));
+    prof_break(h);
+    launch_brdf_beam_modes(h->stream, h->g, B, bp, nphi, m_first, m_count, d_mu0, d_r0_out);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -3,6 +3,9 @@
 //   k_brdf_operator        R(i, j) = 2 w_j |mu_j| rho_bar(mu_i, |mu_j|): one lane per pair, the azimuth nodes in a loop; every
 //                          (pair, node) is evaluated once, the cosines of a chunk of nodes come from LDS.
 //   k_brdf_beam            r0[b][i] = rho_bar(mu_i, mu0[b]): one lane per (column, upward lane), the same loop.
+//   k_brdf_operator_modes   the Fourier modes m of R in azimuth, R^m(i, j) = 2 w_j |mu_j| rho^m(mu_i, |mu_j|), the same
+//   k_brdf_beam_modes      layout and loop: rho at a (pair, node) feeds the register accumulators of up to 8 modes per launch, the
+//                          nodes' weights times cos(m phi) come from LDS; mode 0 has the bits of the two kernels above.
 //   k_ground_source        S = scale (R I_surface + r0 e^{-tau*/mu0}): one workgroup per column, the surface row in LDS, one lane
 //                          per upward lane i, fused multiply-adds over j ascending (R is stored with the lanes i of one j contiguous).
 //   k_ground_first_order   the unscattered upward field of S with the mu -> 0+ blend of the order loop's upward sweep on every
@@ -20,6 +23,7 @@ namespace {
 
 constexpr int kPhiChunk = 256;         // azimuth nodes whose cosines a workgroup holds in LDS at a time
 constexpr double kPi = 3.14159265358979323846;
+constexpr int kModesPerLaunch = 8;     // Fourier modes whose accumulators a lane of the mode kernels holds in registers
 
 // one direction of a pair: cosine, sine, tangent
 struct Dir {
@@ -100,6 +104,96 @@ __global__ __launch_bounds__(256) void k_brdf_beam(Grid g, int B, BrdfParams bp,
     const int b = live ? (int)(idx / M) : 0, i = live ? (int)(idx - (long long)b * M) : 0;
     const double rb = azimuth_mean(bp, live, g.mu[N + 1 + i], mu0[b], nphi, s_cos);
     if (live) r0[idx] = rb;
+}
+
+// ---- Fourier modes of the BRDF in azimuth ----
+// cos(m phi_q) on the nphi nodes phi_q = pi q / (nphi - 1): the integer product m q reduced modulo the 2 (nphi - 1) nodes of the
+// full circle and folded onto [0, pi], so that m = 0 gives 1, node nphi - 1 gives (-1)^m and a quarter turn gives 0, all exactly.
+__device__ __forceinline__ double mode_cos(int m, int q, int nphi, double h) {
+    const int half = nphi - 1, period = 2 * half;
+    int r = (int)(((long long)m * q) % period);
+    if (r > half) r = period - r;
+    if (r == 0) return 1.0;
+    if (r == half) return -1.0;
+    if (2 * r == half) return 0.0;
+    return cos(kPi * r * h);
+}
+
+// rho^m(a, b) = (1 / pi) int_0^pi rho cos(m phi) dphi for the modes m0 .. m0 + nm - 1 (nm <= kModesPerLaunch) by the trapezoid
+// rule of azimuth_mean: rho at a (pair, node) is evaluated once and feeds the accumulators of all modes, which stay in registers
+// (the loops over k have a constant trip count and are unrolled; a mode k >= nm has weight 0).  s_cos: (2 + kModesPerLaunch)
+// kPhiChunk doubles of the workgroup: cos phi, 1 - cos phi and per mode the weight of the node times cos(m phi) for a chunk of
+// nodes.  With m = 0 the weight times 1 is the weight, so mode 0 has the bits of azimuth_mean.  Every thread of the workgroup
+// calls this.
+template <int NM>
+__device__ __forceinline__ void azimuth_modes(const BrdfParams& bp, bool live, double ca, double cb, int nphi, int m0, int nm,
+                                              double* s_cos, double (&acc)[NM]) {
+    double* s_hav = s_cos + kPhiChunk;
+    double* s_wc = s_cos + 2 * kPhiChunk;                    // [NM][kPhiChunk]
+    const Dir a = make_dir(ca), b = make_dir(cb);
+    const double minnaert = bp.kind == SOSRT_BRDF_RPV ? pow(a.c * b.c * (a.c + b.c), bp.p[1] - 1.0) : 1.0;
+    const double h = 1.0 / (nphi - 1);
+#pragma unroll
+    for (int k = 0; k < NM; ++k) acc[k] = 0;
+    for (int q0 = 0; q0 < nphi; q0 += kPhiChunk) {
+        const int nq = min(kPhiChunk, nphi - q0);
+        __syncthreads();
+        for (int q = threadIdx.x; q < nq; q += blockDim.x) {
+            const double phi = kPi * (q0 + q) * h, sh = sin(0.5 * phi);
+            s_cos[q] = q0 + q == nphi - 1 ? -1.0 : cos(phi);
+            s_hav[q] = q0 + q == nphi - 1 ? 2.0 : 2.0 * sh * sh;
+            const double w = (q0 + q == 0 || q0 + q == nphi - 1) ? 0.5 * h : h;
+#pragma unroll
+            for (int k = 0; k < NM; ++k) s_wc[k * kPhiChunk + q] = k < nm ? w * mode_cos(m0 + k, q0 + q, nphi, h) : 0.0;
+        }
+        __syncthreads();
+        if (live) {
+            for (int q = 0; q < nq; ++q) {
+                const double v = bp.kind == SOSRT_BRDF_RPV ? rpv(bp, a, b, minnaert, s_cos[q], s_hav[q]) : 1.0;
+#pragma unroll
+                for (int k = 0; k < NM; ++k) acc[k] = fma(s_wc[k * kPhiChunk + q], v, acc[k]);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_brdf_operator_modes(Grid g, BrdfParams bp, int nphi, int m0, int nm, int sign_odd,
+                                                             double* __restrict__ R) {
+    __shared__ double s_cos[(2 + kModesPerLaunch) * kPhiChunk];
+    const int N = g.N, M = N - 1;
+    const long long pairs = (long long)M * M;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = idx < pairs;
+    const int j = live ? (int)(idx / M) : 0, i = live ? (int)(idx - (long long)j * M) : 0;
+    const double a = g.mu[N + 1 + i], b = -g.mu[j];
+    double rb[kModesPerLaunch];
+    azimuth_modes<kModesPerLaunch>(bp, live, a, b, nphi, m0, nm, s_cos, rb);
+    if (live) {
+        const double w = j == 0 ? (g.mu[1] - g.mu[0]) / 2 : j == M - 1 ? (g.mu[M - 1] - g.mu[M - 2]) / 2 : (g.mu[j + 1] - g.mu[j - 1]) / 2;
+#pragma unroll
+        for (int k = 0; k < kModesPerLaunch; ++k)
+            if (k < nm) {
+                const double v = 2.0 * w * b * rb[k];
+                R[(size_t)k * pairs + idx] = (sign_odd && ((m0 + k) & 1)) ? -v : v;
+            }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_brdf_beam_modes(Grid g, int B, BrdfParams bp, int nphi, int m0, int nm,
+                                                         const double* __restrict__ mu0, double* __restrict__ r0) {
+    __shared__ double s_cos[(2 + kModesPerLaunch) * kPhiChunk];
+    const int N = g.N, M = N - 1;
+    const long long n = (long long)B * M;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = idx < n;
+    const int b = live ? (int)(idx / M) : 0, i = live ? (int)(idx - (long long)b * M) : 0;
+    double rb[kModesPerLaunch];
+    azimuth_modes<kModesPerLaunch>(bp, live, g.mu[N + 1 + i], mu0[b], nphi, m0, nm, s_cos, rb);
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < kModesPerLaunch; ++k)
+            if (k < nm) r0[(size_t)k * n + idx] = rb[k];
+    }
 }
 
 __global__ __launch_bounds__(1024) void k_ground_source(Grid g, int B, ColScalars sc, const double* __restrict__ I_all,
@@ -237,6 +331,22 @@ void launch_brdf_operator(hipStream_t s, const Grid& g, BrdfParams bp, int nphi,
 void launch_brdf_beam(hipStream_t s, const Grid& g, int B, BrdfParams bp, int nphi, const double* mu0, double* r0) {
     const long long n = (long long)B * (g.N - 1);
     hipLaunchKernelGGL(k_brdf_beam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, B, bp, nphi, mu0, r0);
+}
+
+void launch_brdf_operator_modes(hipStream_t s, const Grid& g, BrdfParams bp, int nphi, int m_first, int m_count, int sign_odd,
+                                double* R) {
+    const long long pairs = (long long)(g.N - 1) * (g.N - 1);
+    for (int m = 0; m < m_count; m += kModesPerLaunch)
+        hipLaunchKernelGGL(k_brdf_operator_modes, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, g, bp, nphi, m_first + m,
+                           min(kModesPerLaunch, m_count - m), sign_odd, R + (size_t)m * pairs);
+}
+
+void launch_brdf_beam_modes(hipStream_t s, const Grid& g, int B, BrdfParams bp, int nphi, int m_first, int m_count, const double* mu0,
+                            double* r0) {
+    const long long n = (long long)B * (g.N - 1);
+    for (int m = 0; m < m_count; m += kModesPerLaunch)
+        hipLaunchKernelGGL(k_brdf_beam_modes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, B, bp, nphi, m_first + m,
+                           min(kModesPerLaunch, m_count - m), mu0, r0 + (size_t)m * n);
 }
 
 void launch_ground_source(hipStream_t s, const Grid& g, int B, ColScalars sc, const double* I, const double* tau, const double* R,

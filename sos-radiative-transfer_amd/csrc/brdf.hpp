@@ -16,6 +16,12 @@ struct BrdfParams {
 void launch_brdf_operator(hipStream_t s, const Grid& g, BrdfParams bp, int nphi, double* R);
 // r0 [B][N-1]: rho_bar(mu[N+1+i], mu0[b])
 void launch_brdf_beam(hipStream_t s, const Grid& g, int B, BrdfParams bp, int nphi, const double* mu0, double* r0);
+// Fourier modes m_first .. m_first + m_count - 1 in azimuth, rho^m = (1 / pi) int_0^pi rho cos(m phi) dphi in
+// place of rho_bar: R [m_count][N-1][N-1], mode m as (-1)^m R^m where sign_odd; r0 [m_count][B][N-1].  Mode 0: the bits of the two above.
+void launch_brdf_operator_modes(hipStream_t s, const Grid& g, BrdfParams bp, int nphi, int m_first, int m_count, int sign_odd,
+                                double* R);
+void launch_brdf_beam_modes(hipStream_t s, const Grid& g, int B, BrdfParams bp, int nphi, int m_first, int m_count, const double* mu0,
+                            double* r0);
 // S [B][N-1] = scale (R I[L-1][0 .. N-2] + r0 exp(-tau[L-1] / mu0)); r0, scale nullable
 void launch_ground_source(hipStream_t s, const Grid& g, int B, ColScalars sc, const double* I, const double* tau, const double* R,
                           const double* r0, const double* scale, double* S);

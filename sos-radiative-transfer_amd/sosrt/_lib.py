@@ -104,6 +104,8 @@ SIGNATURES = {
     "sosrt_band_reduce_dev": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 4 + [c_int]),
     "sosrt_brdf_operator_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "sosrt_brdf_beam_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sosrt_brdf_operator_modes_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "sosrt_brdf_beam_modes_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sosrt_ground_source_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 6),
     "sosrt_ground_first_order_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 4),
     "sosrt_bounce_accumulate_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 3),

@@ -66,6 +66,7 @@ class BatchResult:
     beam_slant: Optional[np.ndarray] = None   # [B, L] (beam='spherical'): slant optical depth of the direct beam at every level
     bounces: Optional[np.ndarray] = None      # [B] (surface='brdf'): the ground reflection at which the column's term fell below tol
     bounce_ratio: Optional[np.ndarray] = None  # [B] ... and the last term's share of the sum on the TOA-up and surface-down lanes
+    bounce_orders: Optional[np.ndarray] = None  # [K, B] (surface='brdf'): the orders the solve of every ground reflection ran
 
 
 _solvers = {}
@@ -362,18 +363,30 @@ BRDF_NPHI = 65
 
 
 def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None, view_azimuths=None, mode_batch=False,
-               mode_chunk=None, beam="plane", source="solar", first_order="coded", devices=None, save_orders=False):
+               mode_chunk=None, beam="plane", source="solar", first_order="coded", devices=None, save_orders=False,
+               brdf_modes=False):
     """Checks of surface='brdf', made before any handle exists: None for every other surface, else a namespace (kind, params,
-    R [N-1, N-1] or None, r0 [B, N-1] or None, scale [B]) of the ground `brdf` with `grd_alb` as its per-column scale."""
+    R [N-1, N-1] or None, r0 [B, N-1] or None, scale [B], modes) of the ground `brdf` with `grd_alb` as its per-column scale;
+    modes: the call is the azimuth-resolved one over the ground's Fourier modes (`brdf_modes=True` with `azimuths`)."""
+    if not isinstance(brdf_modes, (bool, np.bool_)):
+        raise ValueError("brdf_modes must be True or False (got %r)" % (brdf_modes,))
     if not (isinstance(surface, str) and surface == "brdf"):
         if brdf is not None:
             raise ValueError("brdf belongs to surface='brdf'")
+        if brdf_modes:
+            raise ValueError("brdf_modes belongs to surface='brdf' (with brdf= and azimuths=)")
         return None
     if brdf is None:
         raise ValueError("surface='brdf' needs brdf: 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0)")
-    if azimuths is not None or mode_batch or mode_chunk is not None or view_azimuths is not None:
+    if brdf_modes:
+        if azimuths is None:
+            raise ValueError("brdf_modes=True is the azimuth-resolved call over the BRDF ground: give azimuths")
+        if mode_batch or mode_chunk is not None or view_azimuths is not None:
+            raise ValueError("surface='brdf' with brdf_modes=True is not available with mode_batch / mode_chunk / view_azimuths: "
+                             "the series in ground reflections runs inside the loop over the modes, on one mode's resident field")
+    elif azimuths is not None or mode_batch or mode_chunk is not None or view_azimuths is not None:
         raise ValueError("surface='brdf' is not available with azimuths / mode_batch / view_azimuths: only the azimuth mean "
-                         "(mode m = 0) of the BRDF is built")
+                         "(mode m = 0) of the BRDF is built (azimuths over the ground's modes m >= 1: brdf_modes=True)")
     if view_mu is not None:
         raise ValueError("surface='brdf' is not available with view_mu: the view stage has no ground-reflection term")
     if beam != "plane":
@@ -397,7 +410,7 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
     if scale.shape not in ((), (1,), (B,)) or not np.all(np.isfinite(scale)) or np.any(scale < 0):
         raise ValueError("grd_alb (the ground's per-column scale under surface='brdf') must be finite, >= 0 and a scalar or [B] = (%d,)" % B)
     scale = np.ascontiguousarray(np.broadcast_to(scale.reshape(-1) if scale.ndim else scale, (B,)))
-    spec = SimpleNamespace(kind=None, params=(), R=None, r0=None, scale=scale)
+    spec = SimpleNamespace(kind=None, params=(), R=None, r0=None, scale=scale, modes=bool(brdf_modes))
     if isinstance(brdf, str):
         if brdf != "lambertian":
             raise ValueError("brdf must be 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0) (got %r)" % (brdf,))
@@ -420,6 +433,8 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
         return spec
     if len(brdf) != 2:
         raise ValueError("brdf as arrays is the pair (R [N-1, N-1], r0 [N-1] or [B, N-1])")
+    if brdf_modes:
+        raise ValueError("brdf as arrays (R, r0) carries no azimuth information: brdf_modes=True needs a named brdf")
     try:
         R, r0 = np.asarray(brdf[0], dtype=np.float64), np.asarray(brdf[1], dtype=np.float64)
     except (TypeError, ValueError):
@@ -442,8 +457,9 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
     the TOA-up and surface-down lanes, or `max_bounces`; B ratios come back per bounce, nothing else.  Every column runs every
     bounce of the batch.  `want`: names of `Solver.epilogue` from the summed field (`epilogue_device`: over the black ground its
     reflected-beam term is zero; the reflected beam is in the field).  Returns (SolveResult, {"bounces" [B]: the bounce at
-    which the column fell below tol, "bounce_ratio" [B]: its last ratio}, dict of the wanted epilogue arrays); keep_device=True:
-    the torch tensors {"I", "n", "status", "tau", "bounces", "bounce_ratio"} instead.  n is the black solve's; a column still
+    which the column fell below tol, "bounce_ratio" [B]: its last ratio, "bounce_orders" [K, B]: the orders the solve of every
+    bounce ran}, dict of the wanted epilogue arrays); keep_device=True: the torch tensors {"I", "n", "status", "tau", "bounces",
+    "bounce_ratio", "bounce_orders"} instead.  n is the black solve's; a column still
     above tol at the cap has status COL_MAXORDERS, one whose ground rows fail the mu -> 0 search COL_INDEXERROR."""
     import torch
     if s.single_slab:
@@ -465,6 +481,7 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
         d_S, d_G, d_Ik, d_ratio = f64(B, M), f64(B, L, s.D), f64(B, L, s.D), f64(B)
         d_nk, d_stk, d_gst = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(3))
         bounces = np.zeros(B, dtype=np.int32)
+        orders = []
         src = d_I                                            # bounce 1 reflects the black solve's surface row
         for k in range(1, max_bounces + 1):
             s.ground_source_device(src.data_ptr(), d_tau.data_ptr(), d_R.data_ptr(), d_S.data_ptr(),
@@ -475,6 +492,7 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
             s.bounce_accumulate_device(d_Ik.data_ptr(), d_I.data_ptr(), d_ratio.data_ptr(), B=B)
             d_st.copy_(torch.where(d_st != 0, d_st, torch.where(d_gst != 0, d_gst, d_stk)))
             src = d_Ik
+            orders.append(d_nk.clone())
             s.synchronize()
             ratio = d_ratio.cpu().numpy()
             bounces[(bounces == 0) & (ratio < tol)] = k
@@ -483,7 +501,7 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
         late = torch.from_numpy(bounces == 0).to(dev) & (d_st == 0)
         d_st.copy_(torch.where(late, torch.full_like(d_st, _lib.COL_MAXORDERS), d_st))
         bounces[bounces == 0] = k
-        return {"bounces": torch.from_numpy(bounces).to(dev), "bounce_ratio": d_ratio}
+        return {"bounces": torch.from_numpy(bounces).to(dev), "bounce_ratio": d_ratio, "bounce_orders": torch.stack(orders)}
 
     def epilogue(d_tau, d_I, d_zp, extra, out, B):
         s.epilogue_device(d_tau, d_I, d_zp, "crit", *out)
@@ -500,7 +518,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   n_modes=None, nphi_modes=None, levels=(0, -1), aer_set=None, mode_batch=False, mode_chunk=None,
                   view_mu=None, view_levels=(0, -1), view_quadrature="grid", view_azimuths=None,
                   view_first_order="exact", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None,
-                  planck_surface=None, surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES) -> BatchResult:
+                  planck_surface=None, surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES,
+                  brdf_modes=False) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -579,15 +598,27 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     sum or `max_bounces` (32; a column still above has status COL_MAXORDERS).  `brdf='lambertian'`: grd_alb[b] is the albedo,
     so an albedo sweep is one batch; `brdf=('rpv', rho0, k, theta)`: Rahman-Pinty-Verstraete with its hot spot (grd_alb
     omitted or 1); `brdf=(R, r0)`: a caller's operator R [N-1, N-1] (upward lane N+1+i from downward lane j, the flux
-    quadrature folded in) and beam row r0 [N-1] or [B, N-1], grd_alb a plain scale.  BatchResult.bounces / bounce_ratio [B]; n
-    is the black solve's.  Not with `azimuths`, `view_mu`, `view_azimuths`, `mode_batch`, `beam='spherical'`,
-    `source='thermal'`, `first_order='readme'`, `save_orders` or several `devices`."""
+    quadrature folded in) and beam row r0 [N-1] or [B, N-1], grd_alb a plain scale.  BatchResult.bounces / bounce_ratio [B]
+    / bounce_orders [K, B] (the orders of every reflection's solve); n is the black solve's.  Not with `view_mu`,
+    `view_azimuths`, `mode_batch`, `beam='spherical'`, `source='thermal'`, `first_order='readme'`, `save_orders` or several
+    `devices`; `azimuths` only with `brdf_modes=True`.
+
+    `brdf_modes=True` (with `surface='brdf'`, a named `brdf` and `azimuths`): the AZIMUTH-RESOLVED RADIANCE OVER THE BRDF GROUND
+    (DESIGN section 21).  The Fourier modes m = 1 .. `n_modes` of the BRDF are built on the device (on the BRDF_NPHI = 65 nodes of
+    its azimuth mean, so n_modes <= 63), and per mode, after the black solve of that mode, the series in ground reflections runs
+    on the mode's resident field with (-1)^m R^m: every mode runs the reflections mode 0 ran, reflection k with the order counts
+    of mode 0's reflection k.  I_azimuth then carries the ground's own azimuth dependence, RPV's hot spot at back-scatter
+    (phi = 0 at an upward mu = mu0) among it; the ground's modes fall off as 1 / m^2 only (the hot spot is a cusp), so what n_modes
+    leaves out is larger than over the specular ground.  `brdf='lambertian'` has no modes m >= 1: its I_azimuth is mode 0 plus
+    the atmosphere's modes over a black ground.  I, n, status, bounces and bounce_ratio are those of the call without
+    `azimuths`, bit for bit; mode_status [n_modes + 1, B] includes the reflections' solves and ground rows."""
     thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
                             _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if source == "thermal" else 0,
                             nb_layers, azimuths, view_azimuths, mode_batch, mode_chunk, beam, first_order, devices)
     ground = _brdf_args(surface, brdf, grd_alb, nb_angles,
                         _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if surface == "brdf" else 0,
-                        azimuths, view_mu, view_azimuths, mode_batch, mode_chunk, beam, source, first_order, devices, save_orders)
+                        azimuths, view_mu, view_azimuths, mode_batch, mode_chunk, beam, source, first_order, devices, save_orders,
+                        brdf_modes)
     if ground:
         surface, grd_alb = "specular", 0.0                   # the series' solves run over a black ground
     spherical = _beam_args(beam, earth_radius, azimuths, view_mu, view_azimuths, mode_batch, mode_chunk, first_order, devices)
@@ -609,6 +640,9 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     if azimuths is not None:
         M, nphi, lev = _azimuth_args(azimuths, n_modes, nphi_modes, levels, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface,
                                      devices, first_order, mode_batch=mode_batch, mode_chunk=mode_chunk)
+        if ground and M > BRDF_NPHI - 2:
+            raise ValueError("brdf_modes=True builds the ground's modes on %d azimuth nodes: n_modes must be <= %d (got %d)"
+                             % (BRDF_NPHI, BRDF_NPHI - 2, M))
     elif mode_batch or mode_chunk is not None:
         raise ValueError("mode_batch / mode_chunk belong to the azimuth-resolved call: give azimuths")
     if devices is not None and len(devices) > 1:
@@ -656,7 +690,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     if raise_on_error:
         _raise_status(r.status, N)
     out = BatchResult(I=r.I, n=r.n, status=r.status, tau=tau, mu=mu, idx_up=iu, idx_down=idn, I_saved=r.I_saved, beam_slant=sigma,
-                      bounces=bx.get("bounces"), bounce_ratio=bx.get("bounce_ratio"))
+                      bounces=bx.get("bounces"), bounce_ratio=bx.get("bounce_ratio"), bounce_orders=bx.get("bounce_orders"))
     if azimuths is not None:
         mu0v = np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
         if mode_batch:
@@ -667,7 +701,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                                                                    mie_atm, aer_phase_fun, g_aer, mie_aer, c_cap, device)
         else:
             out.I_azimuth, out.mode_status = azimuth_modes(s, tau, r, mu0v, azimuths, M, nphi, lev, atm_phase_fun, g_atm, mie_atm,
-                                                           aer_phase_fun, g_aer, mie_aer, device)
+                                                           aer_phase_fun, g_aer, mie_aer, device, ground=ground,
+                                                           bounce_orders=bx.get("bounce_orders"))
         if raise_on_error:
             _raise_status(out.mode_status, N)
     if view_mu is not None:
@@ -960,6 +995,8 @@ class _ModeLoop:
     d_tau: object = None     # [B, L]
     d_mu0: object = None     # [B]
     d_Im: object = None      # [B, L, 2N]: set by `begin` to the mode-0 field; after the solve of mode m, the field of mode m
+    d_target: object = None  # [B] int32: the order counts of mode 0, the handle's targets while the modes are solved
+    d_status: object = None  # [M, B] int32: the status of the solve of mode m in row m - 1 (set before the first mode)
     own: SimpleNamespace = field(default_factory=SimpleNamespace)
 
 
@@ -983,7 +1020,7 @@ def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, f
             c = _ModeLoop(dev=dev, B=B, L=L, D=D, M=M, nphi=nphi, phases=tuple(phases))
             c.d_tau = d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
             c.d_mu0 = d_mu0 = torch.from_numpy(np.array(mu0, dtype=np.float64)).to(dev)      # (a copy: broadcast views are read-only)
-            d_target = torch.from_numpy(np.ascontiguousarray(r.n, dtype=np.int32)).to(dev)
+            c.d_target = d_target = torch.from_numpy(np.ascontiguousarray(r.n, dtype=np.int32)).to(dev)
             begin(c)
             # modes m >= 1 of both phase functions: the matrices to the host (one fold each in set_phase), the first-order
             # vectors where the solve reads them
@@ -995,7 +1032,7 @@ def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, f
                 s.phase_p0_modes_device(kind, d_mu0.data_ptr(), p0.data_ptr(), B, 1, M, nphi, g)
                 d_P0.append(p0)
             d_n = torch.zeros(B, dtype=torch.int32, device=dev)
-            d_st = torch.zeros((M, B), dtype=torch.int32, device=dev)
+            c.d_status = d_st = torch.zeros((M, B), dtype=torch.int32, device=dev)
             s.set_order_targets(d_target.data_ptr())
             for m in range(1, M + 1):
                 s.synchronize()                              # (set_phase rewrites the matrices the previous mode's solve read)
@@ -1016,14 +1053,22 @@ def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, f
 
 
 def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
-                  mie_aer, device=0):
+                  mie_aer, device=0, ground=None, bounce_orders=None, brdf_nphi=BRDF_NPHI):
     """Modes m = 1..M of the solve `r` (the mode-0 result of handle `s`, whose columns are set): per mode the matrices and
     first-order vectors of both phase functions, a solve with the order counts of mode 0 (sosrt_set_order_targets), and the
     synthesis at `levels` (`_solve_modes` with the grid's synthesis as its step).  Returns (I_azimuth [B, nlev, 2N,
     len(azimuths)], mode status [M + 1, B]).  The handle's mode-0 phase matrices are put back and its targets cleared
-    afterwards, also on error."""
+    afterwards, also on error.
+
+    `ground` (the namespace of `_brdf_args`, `r` then being the result of `solve_brdf` over it) with `bounce_orders` [K, B] of
+    that solve: the BRDF GROUND'S MODES.  The operators (-1)^m R^m and beam rows r0^m of the modes 1..M are
+    built once, on the `brdf_nphi` nodes of mode 0's; per mode, between its black solve and its synthesis, the reflections 1..K
+    run on the resident field -- ground source, its unscattered field, a solve of bounce_orders[k - 1] orders started from it,
+    sum -- and the targets go back to mode 0's.  Their statuses join the mode's.  A Lambertian ground has no mode m >= 1: no
+    reflections are run for it."""
     import torch
     nlev = len(levels)
+    bounce = ground is not None and ground.kind != "lambertian"
 
     def begin(c):
         o = c.own
@@ -1032,9 +1077,37 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
         o.d_out = torch.empty((c.B, nlev, c.D, o.d_phi.numel()), dtype=torch.float64, device=c.dev)
         c.d_Im = torch.from_numpy(np.ascontiguousarray(r.I)).to(c.dev)
         step(c, 0)
+        if bounce:
+            M1 = s.N - 1
+            f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=c.dev)
+            o.d_scale = torch.from_numpy(np.array(ground.scale, dtype=np.float64)).to(c.dev)
+            o.d_orders = torch.from_numpy(np.ascontiguousarray(bounce_orders, dtype=np.int32)).to(c.dev)
+            o.d_R, o.d_r0 = f64(c.M, M1, M1), f64(c.M, c.B, M1)
+            s.brdf_operator_modes_device(ground.kind, o.d_R.data_ptr(), 1, c.M, ground.params, brdf_nphi, sign_odd=True)
+            s.brdf_beam_modes_device(ground.kind, c.d_mu0.data_ptr(), o.d_r0.data_ptr(), 1, c.M, ground.params, brdf_nphi, B=c.B)
+            o.d_S, o.d_G, o.d_Ik, o.d_ratio = f64(c.B, M1), f64(c.B, c.L, c.D), f64(c.B, c.L, c.D), f64(c.B)
+            o.d_nk, o.d_stk, o.d_gst = (torch.zeros(c.B, dtype=torch.int32, device=c.dev) for _ in range(3))
+
+    def reflections(c, m):
+        o = c.own
+        st = c.d_status[m - 1]
+        src = c.d_Im                                         # reflection 1 reflects the mode's black solve
+        for k in range(1, o.d_orders.shape[0] + 1):
+            s.ground_source_device(src.data_ptr(), c.d_tau.data_ptr(), o.d_R[m - 1].data_ptr(), o.d_S.data_ptr(),
+                                   o.d_r0[m - 1].data_ptr() if k == 1 else 0, o.d_scale.data_ptr(), B=c.B)
+            s.ground_first_order_device(c.d_tau.data_ptr(), o.d_S.data_ptr(), o.d_G.data_ptr(), o.d_gst.data_ptr(), B=c.B)
+            s.set_order_targets(o.d_orders[k - 1].data_ptr())
+            s.solve_device(c.d_tau.data_ptr(), 0, 0, o.d_Ik.data_ptr(), d_I1=o.d_G.data_ptr(), d_n_orders=o.d_nk.data_ptr(),
+                           d_status=o.d_stk.data_ptr())
+            s.bounce_accumulate_device(o.d_Ik.data_ptr(), c.d_Im.data_ptr(), o.d_ratio.data_ptr(), B=c.B)
+            st.copy_(torch.where(st != 0, st, torch.where(o.d_gst != 0, o.d_gst, o.d_stk)))
+            src = o.d_Ik
+        s.set_order_targets(c.d_target.data_ptr())
 
     def step(c, m):
         o = c.own
+        if bounce and m >= 1:
+            reflections(c, m)
         s.azimuth_accumulate_device(m, c.d_Im.data_ptr(), o.d_lev.data_ptr(), nlev, o.d_phi.data_ptr(), o.d_phi.numel(),
                                     o.d_out.data_ptr(), B=c.B)
 
@@ -1432,7 +1505,8 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
     if raise_on_error:
         _raise_status(r.status, N)
     return BatchResult(I=r.I, n=r.n, status=r.status, tau=np.tile(tau, (B, 1)), mu=mu, idx_up=int(r0[1]), idx_down=int(r0[2]) - 1,
-                       beam_slant=sigma, bounces=bx.get("bounces"), bounce_ratio=bx.get("bounce_ratio"))
+                       beam_slant=sigma, bounces=bx.get("bounces"), bounce_ratio=bx.get("bounce_ratio"),
+                       bounce_orders=bx.get("bounce_orders"))
 
 
 def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=None, P_aer=None, P0_aer=None, device=0,

@@ -487,6 +487,20 @@ class Solver:
         check(lib().sosrt_brdf_beam_dev(self._h, int(self.B if B is None else B), k, _ptr(p) if p.size else None, int(p.size),
                                         int(nphi), _vp(d_mu0), _vp(d_r0_out)))
 
+    def brdf_operator_modes_device(self, kind, d_R_out: int, m_first, m_count, params=(), nphi=65, sign_odd=False):
+        """The Fourier modes m_first .. m_first + m_count - 1 in azimuth of `brdf_operator_device`: d_R_out
+        [m_count, N-1, N-1] with rho^m = (1 / pi) int rho cos(m phi) dphi in place of the azimuth mean; sign_odd: mode m as
+        (-1)^m R^m, what `ground_source_device` takes for mode m.  Mode 0 has the bits of `brdf_operator_device`."""
+        k, p = self._brdf_kind(kind, params)
+        check(lib().sosrt_brdf_operator_modes_dev(self._h, k, _ptr(p) if p.size else None, int(p.size), int(nphi), int(m_first),
+                                                  int(m_count), int(bool(sign_odd)), _vp(d_R_out)))
+
+    def brdf_beam_modes_device(self, kind, d_mu0: int, d_r0_out: int, m_first, m_count, params=(), nphi=65, B: Optional[int] = None):
+        """The same modes of `brdf_beam_device`: d_r0_out [m_count, B, N-1] = rho^m(mu[N+1+i], d_mu0[b]) (no sign)."""
+        k, p = self._brdf_kind(kind, params)
+        check(lib().sosrt_brdf_beam_modes_dev(self._h, int(self.B if B is None else B), k, _ptr(p) if p.size else None, int(p.size),
+                                              int(nphi), int(m_first), int(m_count), _vp(d_mu0), _vp(d_r0_out)))
+
     def ground_source_device(self, d_I: int, d_tau: int, d_R: int, d_S_out: int, d_r0: int = 0, d_scale: int = 0,
                              B: Optional[int] = None):
         """d_S_out [B, N-1] = scale[b] (R I[b, L-1, 0 .. N-2] + r0[b] exp(-tau[b, L-1] / mu0[b])) with the columns' mu0; d_r0 0:
