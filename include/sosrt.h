@@ -713,6 +713,44 @@ int sosrt_brdf_operator_modes_dev(sosrt_t* h, int kind, const double* params /*h
 int sosrt_brdf_beam_modes_dev(sosrt_t* h, int B, int kind, const double* params /*host*/, int nparams, int nphi, int m_first,
                               int m_count, const double* d_mu0 /*[B]*/, double* d_r0_out /*[m_count][B][N-1]*/);
 
+/* ---- BRDF ground seen from a view lane: the ground's term of the view stage --------------------------------
+ * Over a BRDF ground the field is the sum over ground reflections I = sum_k I(k), and the radiance at a view cosine off the grid
+ * is the sum of (1) the closed-form first order over the black ground, (2) sosrt_view_radiance_dev on the SUMMED field with the
+ * black-ground columns (the stage is linear in d_I_src) and (3) the ground's own unscattered radiance at the view lanes:
+ *     upward lane V + v:   sum_k S_k[b][v] exp(-(tau[b][L-1] - tau[b][t]) / mu_view[v]),      downward lanes: +0,
+ *     S_k[b][v] = scale[b] (sum_j Rv[v][j] I(k-1)[b][L-1][j] + [k = 1] r0v[b][v] exp(-tau[b][L-1] / mu0[b])),
+ *     Rv[v][j] = 2 w_j |mu_j| rho_bar(mu_view[v], |mu_j|),   r0v[b][v] = rho_bar(mu_view[v], mu0[b]).
+ * No view lane is blended.  Per azimuth mode m the same with (-1)^m Rv^m, rho^m and the mode's fields; the beam's single
+ * reflection may instead be taken exactly at an azimuth, rho(mu_view, mu0, phi) (phi = 0: the hot spot).  Four stages, detected by
+ * symbol (SOSRT_VERSION is unchanged), enqueued on the handle's stream, without scratch; they write their outputs only.
+ *     sosrt_brdf_view_rows_modes_dev    d_out[m - m_first][j V + v] = 2 w_j |mu_j| rho^m(mu_view[v], |mu_j|)   ((-1)^m with sign_odd)
+ *     sosrt_brdf_view_beam_modes_dev    d_out[m - m_first][b][v] = rho^m(mu_view[v], mu0[b])
+ *     sosrt_brdf_view_beam_azimuth_dev  d_out[q][b][v] = rho(mu_view[v], mu0[b], d_phi[q]), no quadrature
+ * At a view cosine equal to the node mu[N+1+i] the first two have THE BITS OF sosrt_brdf_operator_modes_dev's column i and of
+ * sosrt_brdf_beam_modes_dev (mode 0: of the azimuth-mean entry points).
+ * sosrt_view_ground_dev: one workgroup per column, one lane per v, the sum over j ascending in fused multiply-adds -- the chain of
+ * sosrt_ground_source_dev, so a column's bits do not depend on B and at a node d_S_out equals that entry point's S[i].  d_I and
+ * d_Rv both NULL: the beam-only call; d_r0v NULL: the diffuse-only call; d_scale NULL: 1.  accumulate != 0 adds the upward lanes
+ * to d_out and leaves the downward ones; otherwise both are written (downward: +0).  d_S_out (nullable) receives S.
+ * Refused with SOSRT_E_INVALID, a message and nothing written: what the builders above refuse (single slab, B outside 1 .. the
+ * current columns, kind, nparams, RPV parameters, nphi, the range of modes, N < 4, null pointers); V outside 1..SOSRT_MAX_VIEWS; a
+ * mu_view that is not finite or outside [0.01, 1]; a level outside [0, L); nphi_out < 1; d_I without d_Rv or d_Rv without d_I;
+ * no source at all (d_I, d_Rv and d_r0v NULL). */
+int sosrt_brdf_view_rows_modes_dev(sosrt_t* h, int kind, const double* params /*host*/, int nparams, int nphi, int m_first,
+                                   int m_count, int sign_odd, int V, const double* mu_view /*host [V]*/,
+                                   double* d_out /*[m_count][N-1][V]*/);
+int sosrt_brdf_view_beam_modes_dev(sosrt_t* h, int B, int kind, const double* params /*host*/, int nparams, int nphi, int m_first,
+                                   int m_count, const double* d_mu0 /*[B]*/, int V, const double* mu_view /*host [V]*/,
+                                   double* d_out /*[m_count][B][V]*/);
+int sosrt_brdf_view_beam_azimuth_dev(sosrt_t* h, int B, int kind, const double* params /*host*/, int nparams,
+                                     const double* d_mu0 /*[B]*/, int V, const double* mu_view /*host [V]*/, int nphi_out,
+                                     const double* d_phi /*[nphi_out]*/, double* d_out /*[nphi_out][B][V]*/);
+int sosrt_view_ground_dev(sosrt_t* h, int B, int V, const double* mu_view /*host [V]*/, const double* d_tau /*[B][L]*/,
+                          const double* d_I /*[B][L][2N] or NULL*/, const double* d_Rv /*[N-1][V] or NULL*/,
+                          const double* d_r0v /*[B][V] or NULL*/, const double* d_scale /*[B] or NULL*/, int nlev,
+                          const int* levels /*host [nlev]*/, int accumulate, double* d_S_out /*[B][V] or NULL*/,
+                          double* d_out /*[B][nlev][2V]*/);
+
 /* ---- multi-GPU: one process per GPU, columns sharded, ONE collective at the end ------------------
  * Nothing in SOS_Aer_main_specular.py:104-458 couples columns, so the order loop never communicates; these entry
  * points only assemble the results of the ranks on `root` over RCCL (xGMI inside a node).  RCCL is bound at run time

@@ -1,5 +1,7 @@
 // BRDF ground (include/sosrt.h): the operator of a named BRDF, its beam row, the ground source of a field's
-// surface row, the ground source's unscattered field and the sum over ground reflections.  Stages beside the solve: they read
+// surface row, the ground source's unscattered field and the sum over ground reflections; the Fourier modes of the first two
+// (section 21); and their counterparts at view cosines off the grid with the ground's unscattered radiance at the view lanes
+// (section 22).  Stages beside the solve: they read
 // the grid and the columns of the last sosrt_set_columns* and write their outputs, nothing else -- the handle's columns,
 // resident field, order targets, phase state and first-order mode stay as they were.  Host code.
 #include <hip/hip_runtime.h>
@@ -139,6 +141,102 @@ int sosrt_bounce_accumulate_dev(sosrt_t* h, int B, const double* d_Ik, double* d
     prof_break(h);
     launch_bounce_accumulate(h->stream, h->g, B, d_Ik, d_I_total, d_ratio_out);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- the ground's term at view lanes off the grid ----
+// the view cosines of the four entry points below, as the view stage takes them (sosrt_view_radiance_dev)
+static int brdf_view_mu(int V, const double* mu_view, ViewMu& vm, const char* what) {
+    if (V < 1 || V > SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "%s: V=%d view cosines: must be 1..%d", what, V, SOSRT_MAX_VIEWS);
+    if (!mu_view) return fail(SOSRT_E_INVALID, "%s: null mu_view", what);
+    for (int v = 0; v < V; ++v)
+        if (!(std::isfinite(mu_view[v]) && mu_view[v] >= 0.01 && mu_view[v] <= 1))
+            return fail(SOSRT_E_INVALID, "%s: mu_view[%d] = %g: a view cosine must be finite and in [0.01, 1]", what, v, mu_view[v]);
+    for (int j = 0; j < 2 * kMaxViews; ++j) vm.s[j] = j < V ? mu_view[j] : 1.0;
+    return 0;
+}
+
+extern "C" {
+
+int sosrt_brdf_view_rows_modes_dev(sosrt_t* h, int kind, const double* params, int nparams, int nphi, int m_first, int m_count,
+                                   int sign_odd, int V, const double* mu_view, double* d_out) {
+    const char* what = "sosrt_brdf_view_rows_modes_dev";
+    if (int e = brdf_check(h, 0, false, what)) return e;
+    BrdfParams bp;
+    if (int e = brdf_params(kind, params, nparams, nphi, bp, what)) return e;
+    if (int e = brdf_mode_range(m_first, m_count, nphi, what)) return e;
+    ViewMu vm;
+    if (int e = brdf_view_mu(V, mu_view, vm, what)) return e;
+    if (!d_out) return fail(SOSRT_E_INVALID, "%s: null argument", what);
+    HIPCHK(hipSetDevice(h->device));
+    prof_break(h);
+    launch_brdf_view_rows_modes(h->stream, h->g, vm, V, bp, nphi, m_first, m_count, sign_odd, d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_brdf_view_beam_modes_dev(sosrt_t* h, int B, int kind, const double* params, int nparams, int nphi, int m_first,
+                                   int m_count, const double* d_mu0, int V, const double* mu_view, double* d_out) {
+    const char* what = "sosrt_brdf_view_beam_modes_dev";
+    if (int e = brdf_check(h, B, true, what)) return e;
+    BrdfParams bp;
+    if (int e = brdf_params(kind, params, nparams, nphi, bp, what)) return e;
+    if (int e = brdf_mode_range(m_first, m_count, nphi, what)) return e;
+    ViewMu vm;
+    if (int e = brdf_view_mu(V, mu_view, vm, what)) return e;
+    if (!d_mu0 || !d_out) return fail(SOSRT_E_INVALID, "%s: null argument", what);
+    HIPCHK(hipSetDevice(h->device));
+    prof_break(h);
+    launch_brdf_view_beam_modes(h->stream, B, vm, V, bp, nphi, m_first, m_count, d_mu0, d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_brdf_view_beam_azimuth_dev(sosrt_t* h, int B, int kind, const double* params, int nparams, const double* d_mu0, int V,
+                                     const double* mu_view, int nphi_out, const double* d_phi, double* d_out) {
+    const char* what = "sosrt_brdf_view_beam_azimuth_dev";
+    if (int e = brdf_check(h, B, true, what)) return e;
+    BrdfParams bp;
+    if (int e = brdf_params(kind, params, nparams, 3, bp, what)) return e;        // (no quadrature: any valid node count)
+    ViewMu vm;
+    if (int e = brdf_view_mu(V, mu_view, vm, what)) return e;
+    if (nphi_out < 1) return fail(SOSRT_E_INVALID, "%s: nphi_out = %d: at least one azimuth", what, nphi_out);
+    if ((long long)nphi_out * B * V > 0x7fffffffLL * 256) return fail(SOSRT_E_INVALID, "%s: output too large", what);
+    if (!d_mu0 || !d_phi || !d_out) return fail(SOSRT_E_INVALID, "%s: null argument", what);
+    HIPCHK(hipSetDevice(h->device));
+    prof_break(h);
+    launch_brdf_view_beam_azimuth(h->stream, B, vm, V, bp, d_mu0, nphi_out, d_phi, d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_view_ground_dev(sosrt_t* h, int B, int V, const double* mu_view, const double* d_tau, const double* d_I,
+                          const double* d_Rv, const double* d_r0v, const double* d_scale, int nlev, const int* levels,
+                          int accumulate, double* d_S_out, double* d_out) {
+    const char* what = "sosrt_view_ground_dev";
+    if (int e = brdf_check(h, B, true, what)) return e;
+    ViewMu vm;
+    if (int e = brdf_view_mu(V, mu_view, vm, what)) return e;
+    if (nlev < 1 || !levels) return fail(SOSRT_E_INVALID, "%s: no levels", what);
+    for (int i = 0; i < nlev; ++i)
+        if (levels[i] < 0 || levels[i] >= h->L)
+            return fail(SOSRT_E_INVALID, "%s: levels[%d] = %d is outside [0, %d)", what, i, levels[i], h->L);
+    if ((d_I == nullptr) != (d_Rv == nullptr))
+        return fail(SOSRT_E_INVALID, "%s: d_I and d_Rv go together (both NULL: the beam-only call)", what);
+    if (!d_I && !d_r0v) return fail(SOSRT_E_INVALID, "%s: neither a field with its rows nor beam rows: no source", what);
+    if (!d_tau || !d_out) return fail(SOSRT_E_INVALID, "%s: null argument", what);
+    HIPCHK(hipSetDevice(h->device));
+    prof_break(h);
+    for (int l0 = 0; l0 < nlev; l0 += kViewLevels) {
+        ViewLevels lv;
+        lv.n = nlev - l0 < kViewLevels ? nlev - l0 : kViewLevels;
+        for (int i = 0; i < kViewLevels; ++i) lv.t[i] = i < lv.n ? levels[l0 + i] : 0;
+        launch_view_ground(h->stream, h->g, B, V, vm, scalars_of(h), d_I, d_tau, d_Rv, d_r0v, d_scale, nlev, lv, accumulate != 0,
+                           d_S_out, d_out + (size_t)l0 * 2 * V);
+        HIPCHK(hipGetLastError());
+    }
     return 0;
 }
 

@@ -11,6 +11,11 @@
 //   k_ground_first_order   the unscattered upward field of S with the mu -> 0+ blend of the order loop's upward sweep on every
 //                          row: one workgroup per column, one wave per row, the row in LDS for the blend's search.
 //   k_bounce_accumulate    total += Ik and the column's ratio of the two fields on the TOA-up and surface-down lanes.
+//   k_brdf_view_rows_modes the same modes at view cosines off the grid, 2 w_j |mu_j| rho^m(mu_view_v, |mu_j|) and
+//   k_brdf_view_beam_modes rho^m(mu_view_v, mu0_b): the layout and loop of the two mode kernels, their bits at a node.
+//   k_brdf_view_beam_azimuth rho(mu_view_v, mu0_b, phi) at an azimuth itself, no quadrature.
+//   k_view_ground          the ground's unscattered radiance at the view lanes: k_ground_source's chain with the view rows, one
+//                          exp per (level, lane); downward lanes +0; written or accumulated.
 //
 // The kernels read the grid, the columns' mu0 (ColScalars) and their arguments, and write nothing but their outputs.
 #include "brdf.hpp"
@@ -321,7 +326,136 @@ __global__ __launch_bounds__(256) void k_bounce_accumulate(Grid g, int B, const 
     }
 }
 
+// ---- the ground's term at view lanes off the grid ----
+// The rows of the operator modes at view cosines in place of the upward nodes: (j, v) in place of (j, i), everything else as
+// k_brdf_operator_modes, so that at a view cosine equal to the node mu[N+1+i] the output has the bits of that kernel's column i.
+__global__ __launch_bounds__(256) void k_brdf_view_rows_modes(Grid g, ViewMu vm, int V, BrdfParams bp, int nphi, int m0, int nm,
+                                                              int sign_odd, double* __restrict__ R) {
+    __shared__ double s_cos[(2 + kModesPerLaunch) * kPhiChunk];
+    const int M = g.N - 1;
+    const long long pairs = (long long)M * V;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = idx < pairs;
+    const int j = live ? (int)(idx / V) : 0, v = live ? (int)(idx - (long long)j * V) : 0;
+    const double a = vm.s[v], b = -g.mu[j];
+    double rb[kModesPerLaunch];
+    azimuth_modes<kModesPerLaunch>(bp, live, a, b, nphi, m0, nm, s_cos, rb);
+    if (live) {
+        const double w = j == 0 ? (g.mu[1] - g.mu[0]) / 2 : j == M - 1 ? (g.mu[M - 1] - g.mu[M - 2]) / 2 : (g.mu[j + 1] - g.mu[j - 1]) / 2;
+#pragma unroll
+        for (int k = 0; k < kModesPerLaunch; ++k)
+            if (k < nm) {
+                const double x = 2.0 * w * b * rb[k];
+                R[(size_t)k * pairs + idx] = (sign_odd && ((m0 + k) & 1)) ? -x : x;
+            }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_brdf_view_beam_modes(int B, ViewMu vm, int V, BrdfParams bp, int nphi, int m0, int nm,
+                                                              const double* __restrict__ mu0, double* __restrict__ r0) {
+    __shared__ double s_cos[(2 + kModesPerLaunch) * kPhiChunk];
+    const long long n = (long long)B * V;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = idx < n;
+    const int b = live ? (int)(idx / V) : 0, v = live ? (int)(idx - (long long)b * V) : 0;
+    double rb[kModesPerLaunch];
+    azimuth_modes<kModesPerLaunch>(bp, live, vm.s[v], mu0[b], nphi, m0, nm, s_cos, rb);
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < kModesPerLaunch; ++k)
+            if (k < nm) r0[(size_t)k * n + idx] = rb[k];
+    }
+}
+
+// rho(mu_view_v, mu0_b, phi_q) at the azimuth itself, no quadrature: one lane per (q, b, v)
+__global__ __launch_bounds__(256) void k_brdf_view_beam_azimuth(int B, ViewMu vm, int V, BrdfParams bp, const double* __restrict__ mu0,
+                                                                int nphi_out, const double* __restrict__ phi, double* __restrict__ out) {
+    const long long n = (long long)B * V;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * nphi_out) return;
+    const int q = (int)(idx / n);
+    const long long e = idx - (long long)q * n;
+    const int b = (int)(e / V), v = (int)(e - (long long)b * V);
+    double r = 1.0;
+    if (bp.kind == SOSRT_BRDF_RPV) {
+        const Dir da = make_dir(vm.s[v]), db = make_dir(mu0[b]);
+        const double minnaert = pow(da.c * db.c * (da.c + db.c), bp.p[1] - 1.0);
+        const double sh = sin(0.5 * phi[q]);
+        r = rpv(bp, da, db, minnaert, cos(phi[q]), 2.0 * sh * sh);
+    }
+    out[idx] = r;
+}
+
+// The ground's unscattered radiance at the view lanes: S^view of k_ground_source's chain with the rows at the view cosines
+// ((j, v) in place of (j, i)), then one exp per (level, lane).  One workgroup per column, one lane per v; out [B][nlev_all][2V],
+// `out` offset to the first level of lv.
+__global__ __launch_bounds__(kMaxViews) void k_view_ground(Grid g, int B, int V, ViewMu vm, ColScalars sc,
+                                                           const double* __restrict__ I_all, const double* __restrict__ tau_all,
+                                                           const double* __restrict__ Rv, const double* __restrict__ r0v,
+                                                           const double* __restrict__ scale, int nlev_all, ViewLevels lv,
+                                                           int accumulate, double* __restrict__ S_out, double* __restrict__ out) {
+    const int L = g.L, D = g.D, M = g.N - 1;
+    const int b = blockIdx.x, v = threadIdx.x;
+    if (b >= B) return;                                      // (uniform over the workgroup)
+    extern __shared__ double s_I[];                          // [N-1] the downward surface row
+    if (I_all) {
+        const double* row = I_all + ((size_t)b * L + (L - 1)) * D;
+        for (int j = v; j < M; j += blockDim.x) s_I[j] = row[j];
+    }
+    __syncthreads();
+    if (v >= V) return;
+    const double* tau = tau_all + (size_t)b * L;
+    double acc = 0;
+    if (I_all)
+        for (int j = 0; j < M; ++j) acc = fma(Rv[(size_t)j * V + v], s_I[j], acc);
+    if (r0v) acc += r0v[(size_t)b * V + v] * exp(-tau[L - 1] / sc.mu0[b]);
+    const double S = scale ? scale[b] * acc : acc;
+    if (S_out) S_out[(size_t)b * V + v] = S;
+    const double tauL = tau[L - 1], mv = vm.s[v];
+    for (int l = 0; l < lv.n; ++l) {
+        const double dt = tauL - tau[lv.t[l]];
+        const double x = S * exp(-dt / mv);
+        double* o = out + ((size_t)b * nlev_all + l) * (2 * V);
+        if (accumulate) {
+            o[V + v] += x;
+        } else {
+            o[v] = 0.0;
+            o[V + v] = x;
+        }
+    }
+}
+
 }  // namespace
+
+void launch_brdf_view_rows_modes(hipStream_t s, const Grid& g, const ViewMu& vm, int V, BrdfParams bp, int nphi, int m_first,
+                                 int m_count, int sign_odd, double* R) {
+    const long long pairs = (long long)(g.N - 1) * V;
+    for (int m = 0; m < m_count; m += kModesPerLaunch)
+        hipLaunchKernelGGL(k_brdf_view_rows_modes, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, g, vm, V, bp, nphi,
+                           m_first + m, min(kModesPerLaunch, m_count - m), sign_odd, R + (size_t)m * pairs);
+}
+
+void launch_brdf_view_beam_modes(hipStream_t s, int B, const ViewMu& vm, int V, BrdfParams bp, int nphi, int m_first, int m_count,
+                                 const double* mu0, double* r0) {
+    const long long n = (long long)B * V;
+    for (int m = 0; m < m_count; m += kModesPerLaunch)
+        hipLaunchKernelGGL(k_brdf_view_beam_modes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, B, vm, V, bp, nphi,
+                           m_first + m, min(kModesPerLaunch, m_count - m), mu0, r0 + (size_t)m * n);
+}
+
+void launch_brdf_view_beam_azimuth(hipStream_t s, int B, const ViewMu& vm, int V, BrdfParams bp, const double* mu0, int nphi_out,
+                                   const double* phi, double* out) {
+    const long long n = (long long)B * V * nphi_out;
+    hipLaunchKernelGGL(k_brdf_view_beam_azimuth, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, B, vm, V, bp, mu0, nphi_out,
+                       phi, out);
+}
+
+void launch_view_ground(hipStream_t s, const Grid& g, int B, int V, const ViewMu& vm, ColScalars sc, const double* I,
+                        const double* tau, const double* Rv, const double* r0v, const double* scale, int nlev_all,
+                        const ViewLevels& lv, int accumulate, double* S_out, double* out) {
+    hipLaunchKernelGGL(k_view_ground, dim3((unsigned)B), dim3(kMaxViews), (size_t)(g.N - 1) * sizeof(double), s, g, B, V, vm, sc,
+                       I, tau, Rv, r0v, scale, nlev_all, lv, accumulate, S_out, out);
+}
 
 void launch_brdf_operator(hipStream_t s, const Grid& g, BrdfParams bp, int nphi, double* R) {
     const long long pairs = (long long)(g.N - 1) * (g.N - 1);

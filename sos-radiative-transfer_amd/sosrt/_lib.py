@@ -106,6 +106,12 @@ SIGNATURES = {
     "sosrt_brdf_beam_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sosrt_brdf_operator_modes_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "sosrt_brdf_beam_modes_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sosrt_brdf_view_rows_modes_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sosrt_brdf_view_beam_modes_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                               c_void_p]),
+    "sosrt_brdf_view_beam_azimuth_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                                 c_void_p]),
+    "sosrt_view_ground_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_ground_source_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 6),
     "sosrt_ground_first_order_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 4),
     "sosrt_bounce_accumulate_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 3),

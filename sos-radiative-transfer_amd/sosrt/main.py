@@ -67,6 +67,8 @@ class BatchResult:
     bounces: Optional[np.ndarray] = None      # [B] (surface='brdf'): the ground reflection at which the column's term fell below tol
     bounce_ratio: Optional[np.ndarray] = None  # [B] ... and the last term's share of the sum on the TOA-up and surface-down lanes
     bounce_orders: Optional[np.ndarray] = None  # [K, B] (surface='brdf'): the orders the solve of every ground reflection ran
+    I_view_ground: Optional[np.ndarray] = None          # [B, nlev, 2V] (brdf_view=True): the ground's unscattered radiance at the view lanes, a term of I_view
+    I_view_azimuth_ground: Optional[np.ndarray] = None  # [B, nlev, 2V, len(view_azimuths)] the same at (lane, azimuth), a term of I_view_azimuth
 
 
 _solvers = {}
@@ -364,21 +366,36 @@ BRDF_NPHI = 65
 
 def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None, view_azimuths=None, mode_batch=False,
                mode_chunk=None, beam="plane", source="solar", first_order="coded", devices=None, save_orders=False,
-               brdf_modes=False):
+               brdf_modes=False, brdf_view=False):
     """Checks of surface='brdf', made before any handle exists: None for every other surface, else a namespace (kind, params,
     R [N-1, N-1] or None, r0 [B, N-1] or None, scale [B], modes) of the ground `brdf` with `grd_alb` as its per-column scale;
-    modes: the call is the azimuth-resolved one over the ground's Fourier modes (`brdf_modes=True` with `azimuths`)."""
+    modes: the call is the azimuth-resolved one over the ground's Fourier modes (`brdf_modes=True` with `azimuths`); view: the
+    call adds the ground's term at the view lanes (`brdf_view=True` with `view_mu`)."""
     if not isinstance(brdf_modes, (bool, np.bool_)):
         raise ValueError("brdf_modes must be True or False (got %r)" % (brdf_modes,))
+    if not isinstance(brdf_view, (bool, np.bool_)):
+        raise ValueError("brdf_view must be True or False (got %r)" % (brdf_view,))
     if not (isinstance(surface, str) and surface == "brdf"):
         if brdf is not None:
             raise ValueError("brdf belongs to surface='brdf'")
         if brdf_modes:
             raise ValueError("brdf_modes belongs to surface='brdf' (with brdf= and azimuths=)")
+        if brdf_view:
+            raise ValueError("brdf_view belongs to surface='brdf' (with brdf= and view_mu=)")
         return None
     if brdf is None:
         raise ValueError("surface='brdf' needs brdf: 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0)")
-    if brdf_modes:
+    if brdf_view:
+        if view_mu is None:
+            raise ValueError("brdf_view=True is the view stage over the BRDF ground: give view_mu")
+        if azimuths is not None or brdf_modes:
+            raise ValueError("surface='brdf' with brdf_view=True is not available with azimuths / brdf_modes: view_mu and the "
+                             "grid's azimuth synthesis do not go together (the radiance at a view cosine and an azimuth is "
+                             "view_azimuths=[...])")
+        if mode_batch or mode_chunk is not None:
+            raise ValueError("surface='brdf' with brdf_view=True is not available with mode_batch / mode_chunk: the series in "
+                             "ground reflections runs inside the loop over the modes, on one mode's resident field")
+    elif brdf_modes:
         if azimuths is None:
             raise ValueError("brdf_modes=True is the azimuth-resolved call over the BRDF ground: give azimuths")
         if mode_batch or mode_chunk is not None or view_azimuths is not None:
@@ -387,8 +404,9 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
     elif azimuths is not None or mode_batch or mode_chunk is not None or view_azimuths is not None:
         raise ValueError("surface='brdf' is not available with azimuths / mode_batch / view_azimuths: only the azimuth mean "
                          "(mode m = 0) of the BRDF is built (azimuths over the ground's modes m >= 1: brdf_modes=True)")
-    if view_mu is not None:
-        raise ValueError("surface='brdf' is not available with view_mu: the view stage has no ground-reflection term")
+    if view_mu is not None and not brdf_view:
+        raise ValueError("surface='brdf' is not available with view_mu: the view stage has no ground-reflection term "
+                         "(the ground's term at the view lanes: brdf_view=True)")
     if beam != "plane":
         raise ValueError("surface='brdf' is not available with beam='spherical': the reflected beam is the plane one")
     if source != "solar":
@@ -410,7 +428,7 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
     if scale.shape not in ((), (1,), (B,)) or not np.all(np.isfinite(scale)) or np.any(scale < 0):
         raise ValueError("grd_alb (the ground's per-column scale under surface='brdf') must be finite, >= 0 and a scalar or [B] = (%d,)" % B)
     scale = np.ascontiguousarray(np.broadcast_to(scale.reshape(-1) if scale.ndim else scale, (B,)))
-    spec = SimpleNamespace(kind=None, params=(), R=None, r0=None, scale=scale, modes=bool(brdf_modes))
+    spec = SimpleNamespace(kind=None, params=(), R=None, r0=None, scale=scale, modes=bool(brdf_modes), view=bool(brdf_view))
     if isinstance(brdf, str):
         if brdf != "lambertian":
             raise ValueError("brdf must be 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0) (got %r)" % (brdf,))
@@ -435,6 +453,8 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
         raise ValueError("brdf as arrays is the pair (R [N-1, N-1], r0 [N-1] or [B, N-1])")
     if brdf_modes:
         raise ValueError("brdf as arrays (R, r0) carries no azimuth information: brdf_modes=True needs a named brdf")
+    if brdf_view:
+        raise ValueError("brdf as arrays (R, r0) carries no rows off the grid: brdf_view=True needs a named brdf")
     try:
         R, r0 = np.asarray(brdf[0], dtype=np.float64), np.asarray(brdf[1], dtype=np.float64)
     except (TypeError, ValueError):
@@ -449,7 +469,7 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
 
 
 def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BOUNCES, nphi=BRDF_NPHI, device=0, fetch_field=True,
-               want=(), z_profile=None, keep_device=False):
+               want=(), z_profile=None, keep_device=False, view=None):
     """The solve of handle `s` (grid, phase matrices set; columns set over a BLACK ground: the specular surface with albedo 0)
     over the BRDF GROUND `spec` of `_brdf_args`: the plain solve, then on the device the series in ground
     reflections -- ground source of the last term's downward surface row (and, in the first bounce, of the direct beam) ->
@@ -460,7 +480,12 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
     which the column fell below tol, "bounce_ratio" [B]: its last ratio, "bounce_orders" [K, B]: the orders the solve of every
     bounce ran}, dict of the wanted epilogue arrays); keep_device=True: the torch tensors {"I", "n", "status", "tau", "bounces",
     "bounce_ratio", "bounce_orders"} instead.  n is the black solve's; a column still
-    above tol at the cap has status COL_MAXORDERS, one whose ground rows fail the mu -> 0 search COL_INDEXERROR."""
+    above tol at the cap has status COL_MAXORDERS, one whose ground rows fail the mu -> 0 search COL_INDEXERROR.
+
+    `view` = (view_mu [V], levels) (a named BRDF only): also THE GROUND'S UNSCATTERED RADIANCE AT THE VIEW LANES,
+    summed over the reflections on the same sources the ground source reads -- the beam's single reflection written once, every
+    reflection's diffuse part accumulated (`Solver.view_ground_device`): "I_view_ground_beam", "I_view_ground_diffuse"
+    [B, nlev, 2V] and their sum "I_view_ground" join the second value.  The field and the counts do not change by a bit."""
     import torch
     if s.single_slab:
         raise ValueError("surface='brdf' is not available for the single slab: it has no ground")
@@ -482,10 +507,21 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
         d_nk, d_stk, d_gst = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(3))
         bounces = np.zeros(B, dtype=np.int32)
         orders = []
+        if view is not None:
+            vmu, vlev = view
+            V = len(vmu)
+            d_Rv, d_r0v = f64(M, V), f64(B, V)
+            s.brdf_view_rows_modes_device(spec.kind, vmu, d_Rv.data_ptr(), 0, 1, spec.params, nphi)
+            s.brdf_view_beam_modes_device(spec.kind, d_mu0.data_ptr(), vmu, d_r0v.data_ptr(), 0, 1, spec.params, nphi, B=B)
+            d_vb, d_vd = f64(B, len(vlev), 2 * V), f64(B, len(vlev), 2 * V)
+            s.view_ground_device(vmu, d_tau.data_ptr(), vlev, d_vb.data_ptr(), d_r0v=d_r0v.data_ptr(), d_scale=d_scale.data_ptr(), B=B)
         src = d_I                                            # bounce 1 reflects the black solve's surface row
         for k in range(1, max_bounces + 1):
             s.ground_source_device(src.data_ptr(), d_tau.data_ptr(), d_R.data_ptr(), d_S.data_ptr(),
                                    d_r0.data_ptr() if k == 1 else 0, d_scale.data_ptr(), B=B)
+            if view is not None:
+                s.view_ground_device(vmu, d_tau.data_ptr(), vlev, d_vd.data_ptr(), d_I=src.data_ptr(), d_Rv=d_Rv.data_ptr(),
+                                     d_scale=d_scale.data_ptr(), accumulate=k > 1, B=B)
             s.ground_first_order_device(d_tau.data_ptr(), d_S.data_ptr(), d_G.data_ptr(), d_gst.data_ptr(), B=B)
             s.solve_device(d_tau.data_ptr(), p0a, p0r, d_Ik.data_ptr(), tol=tol, d_I1=d_G.data_ptr(), d_n_orders=d_nk.data_ptr(),
                            d_status=d_stk.data_ptr())
@@ -501,7 +537,10 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
         late = torch.from_numpy(bounces == 0).to(dev) & (d_st == 0)
         d_st.copy_(torch.where(late, torch.full_like(d_st, _lib.COL_MAXORDERS), d_st))
         bounces[bounces == 0] = k
-        return {"bounces": torch.from_numpy(bounces).to(dev), "bounce_ratio": d_ratio, "bounce_orders": torch.stack(orders)}
+        out = {"bounces": torch.from_numpy(bounces).to(dev), "bounce_ratio": d_ratio, "bounce_orders": torch.stack(orders)}
+        if view is not None:
+            out.update(I_view_ground_beam=d_vb, I_view_ground_diffuse=d_vd, I_view_ground=d_vb + d_vd)
+        return out
 
     def epilogue(d_tau, d_I, d_zp, extra, out, B):
         s.epilogue_device(d_tau, d_I, d_zp, "crit", *out)
@@ -519,7 +558,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   view_mu=None, view_levels=(0, -1), view_quadrature="grid", view_azimuths=None,
                   view_first_order="exact", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None,
                   planck_surface=None, surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES,
-                  brdf_modes=False) -> BatchResult:
+                  brdf_modes=False, brdf_view=False) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -599,9 +638,9 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     so an albedo sweep is one batch; `brdf=('rpv', rho0, k, theta)`: Rahman-Pinty-Verstraete with its hot spot (grd_alb
     omitted or 1); `brdf=(R, r0)`: a caller's operator R [N-1, N-1] (upward lane N+1+i from downward lane j, the flux
     quadrature folded in) and beam row r0 [N-1] or [B, N-1], grd_alb a plain scale.  BatchResult.bounces / bounce_ratio [B]
-    / bounce_orders [K, B] (the orders of every reflection's solve); n is the black solve's.  Not with `view_mu`,
-    `view_azimuths`, `mode_batch`, `beam='spherical'`, `source='thermal'`, `first_order='readme'`, `save_orders` or several
-    `devices`; `azimuths` only with `brdf_modes=True`.
+    / bounce_orders [K, B] (the orders of every reflection's solve); n is the black solve's.  Not with `mode_batch`,
+    `beam='spherical'`, `source='thermal'`, `first_order='readme'`, `save_orders` or several `devices`; `azimuths` only with
+    `brdf_modes=True`, `view_mu` / `view_azimuths` only with `brdf_view=True`.
 
     `brdf_modes=True` (with `surface='brdf'`, a named `brdf` and `azimuths`): the AZIMUTH-RESOLVED RADIANCE OVER THE BRDF GROUND
     (DESIGN section 21).  The Fourier modes m = 1 .. `n_modes` of the BRDF are built on the device (on the BRDF_NPHI = 65 nodes of
@@ -611,20 +650,36 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     (phi = 0 at an upward mu = mu0) among it; the ground's modes fall off as 1 / m^2 only (the hot spot is a cusp), so what n_modes
     leaves out is larger than over the specular ground.  `brdf='lambertian'` has no modes m >= 1: its I_azimuth is mode 0 plus
     the atmosphere's modes over a black ground.  I, n, status, bounces and bounce_ratio are those of the call without
-    `azimuths`, bit for bit; mode_status [n_modes + 1, B] includes the reflections' solves and ground rows."""
+    `azimuths`, bit for bit; mode_status [n_modes + 1, B] includes the reflections' solves and ground rows.
+
+    `brdf_view=True` (with `surface='brdf'`, a named `brdf` and `view_mu`): the VIEW RADIANCE OVER THE BRDF GROUND (DESIGN section
+    22).  I_view = I_view_first + I_view_scattered + I_view_ground: the closed-form first order over the black ground, the view
+    stage on the field summed over the ground reflections, and the ground's own unscattered radiance at the view lanes,
+    BatchResult.I_view_ground [B, nlev, 2V] -- every reflection's ground source at the view cosines (rows of the BRDF's operator
+    built at mu_view, not interpolated from the grid) attenuated to the level; downward lanes 0; no view lane is blended.  With
+    `view_azimuths` (n_modes <= 63) the ground's Fourier modes are implied: per mode the reflections run on the mode's resident
+    field as under `brdf_modes`, the ground's term is accumulated per reflection with (-1)^m R^m at the view cosines, and
+    I_view_azimuth = _first + _scattered + I_view_azimuth_ground.  `view_first_order='exact'` (default) also takes the beam's
+    single reflection -- the largest carrier of RPV's hot spot -- from rho(mu_view, mu0, phi) at the azimuth itself, and the modes
+    then carry the diffuse part only; `'modes'` sums rho^m(mu_view, mu0).  I, n, status, bounces, bounce_ratio and bounce_orders
+    are those of the call without `view_mu`, I_view* those of the call without `view_azimuths`, bit for bit.  Not with the array
+    form (R, r0), `azimuths`, `brdf_modes`, `mode_batch`, `aer_set` or phase arrays."""
     thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
                             _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if source == "thermal" else 0,
                             nb_layers, azimuths, view_azimuths, mode_batch, mode_chunk, beam, first_order, devices)
     ground = _brdf_args(surface, brdf, grd_alb, nb_angles,
                         _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if surface == "brdf" else 0,
                         azimuths, view_mu, view_azimuths, mode_batch, mode_chunk, beam, source, first_order, devices, save_orders,
-                        brdf_modes)
+                        brdf_modes, brdf_view)
     if ground:
         surface, grd_alb = "specular", 0.0                   # the series' solves run over a black ground
     spherical = _beam_args(beam, earth_radius, azimuths, view_mu, view_azimuths, mode_batch, mode_chunk, first_order, devices)
     if view_azimuths is not None or view_first_order != "exact":
         vphi, vM, vnphi = _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_modes, nphi_modes, mode_batch,
                                              mode_chunk)
+        if ground and vM > BRDF_NPHI - 2:
+            raise ValueError("brdf_view=True builds the ground's modes on %d azimuth nodes: n_modes must be <= %d (got %d)"
+                             % (BRDF_NPHI, BRDF_NPHI - 2, vM))
     if view_mu is not None:
         vmu, vlev, vquad = _view_args(view_mu, view_levels, view_quadrature, nb_layers, P_atm, P_aer, P0_atm, P0_aer, surface,
                                       devices, first_order, azimuths, aer_set, atm_phase_fun, aer_phase_fun)
@@ -676,7 +731,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         if spherical:
             r, sigma, _ = solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, int(nb_layers)), earth_radius, tol, save_orders, device)
         elif ground:
-            r, bx, _ = solve_brdf(s, tau, P0a, P0r, ground, mu0, tol, max_bounces, device=device)
+            r, bx, _ = solve_brdf(s, tau, P0a, P0r, ground, mu0, tol, max_bounces, device=device,
+                                  view=(vmu, vlev) if ground.view else None)
         elif thermal:
             r, _ = solve_thermal(s, tau, *thermal, tol=tol, save_orders=save_orders, device=device)
         else:
@@ -711,11 +767,18 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         out.I_view_first, out.I_view_scattered = view_radiance(s, tau, r.I, mu0v, vmu, vlev, vquad, atm_phase_fun, g_atm, mie_atm,
                                                                aer_phase_fun, g_aer, mie_aer, device, thermal=thermal)
         out.I_view = out.I_view_first + out.I_view_scattered
+        if ground:
+            out.I_view_ground = bx["I_view_ground"]
+            out.I_view = out.I_view + out.I_view_ground
         if view_azimuths is not None:
-            out.I_view_azimuth_first, out.I_view_azimuth_scattered, out.view_mode_status = view_azimuth_modes(
+            out.I_view_azimuth_first, out.I_view_azimuth_scattered, out.I_view_azimuth_ground, out.view_mode_status = view_azimuth_modes(
                 s, tau, r, mu0v, vmu, vlev, vquad, vphi, vM, vnphi, view_first_order, out.I_view_first, out.I_view_scattered,
-                atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer, device)
+                atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer, device, ground=ground,
+                bounce_orders=bx.get("bounce_orders"),
+                ground0=bx.get("I_view_ground" if view_first_order == "modes" else "I_view_ground_diffuse"))
             out.I_view_azimuth = out.I_view_azimuth_first + out.I_view_azimuth_scattered
+            if ground:
+                out.I_view_azimuth = out.I_view_azimuth + out.I_view_azimuth_ground
             if raise_on_error:
                 _raise_status(out.view_mode_status, N)
     return out
@@ -1052,6 +1115,45 @@ def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, f
     return result, status
 
 
+def _reflection_buffers(s: Solver, c: _ModeLoop, ground, bounce_orders, brdf_nphi):
+    """What `_mode_reflections` reads, under c.own (called from a driver's `begin`): the operators (-1)^m R^m and beam rows r0^m of
+    the modes 1..c.M of the named BRDF `ground` on `brdf_nphi` nodes, its scale, the reflections' order counts and the buffers."""
+    import torch
+    o, M1 = c.own, s.N - 1
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=c.dev)
+    o.d_scale = torch.from_numpy(np.array(ground.scale, dtype=np.float64)).to(c.dev)
+    o.d_orders = torch.from_numpy(np.ascontiguousarray(bounce_orders, dtype=np.int32)).to(c.dev)
+    o.d_R, o.d_r0 = f64(c.M, M1, M1), f64(c.M, c.B, M1)
+    s.brdf_operator_modes_device(ground.kind, o.d_R.data_ptr(), 1, c.M, ground.params, brdf_nphi, sign_odd=True)
+    s.brdf_beam_modes_device(ground.kind, c.d_mu0.data_ptr(), o.d_r0.data_ptr(), 1, c.M, ground.params, brdf_nphi, B=c.B)
+    o.d_S, o.d_G, o.d_Ik, o.d_ratio = f64(c.B, M1), f64(c.B, c.L, c.D), f64(c.B, c.L, c.D), f64(c.B)
+    o.d_nk, o.d_stk, o.d_gst = (torch.zeros(c.B, dtype=torch.int32, device=c.dev) for _ in range(3))
+
+
+def _mode_reflections(s: Solver, c: _ModeLoop, m, hook=None):
+    """The reflections 1..K of mode m >= 1 on the resident field c.d_Im, which holds the mode's black solve and leaves as the sum
+    (DESIGN section 21): ground source, its unscattered field, a solve of bounce_orders[k - 1] orders started from it, sum; the
+    statuses join c.d_status[m - 1] and the targets go back to mode 0's.  `hook(k, src)` runs after the ground source of
+    reflection k, `src` being the field whose surface row it reflected (the view stage's ground term reads the same)."""
+    import torch
+    o = c.own
+    st = c.d_status[m - 1]
+    src = c.d_Im                                             # reflection 1 reflects the mode's black solve
+    for k in range(1, o.d_orders.shape[0] + 1):
+        s.ground_source_device(src.data_ptr(), c.d_tau.data_ptr(), o.d_R[m - 1].data_ptr(), o.d_S.data_ptr(),
+                               o.d_r0[m - 1].data_ptr() if k == 1 else 0, o.d_scale.data_ptr(), B=c.B)
+        if hook is not None:
+            hook(k, src)
+        s.ground_first_order_device(c.d_tau.data_ptr(), o.d_S.data_ptr(), o.d_G.data_ptr(), o.d_gst.data_ptr(), B=c.B)
+        s.set_order_targets(o.d_orders[k - 1].data_ptr())
+        s.solve_device(c.d_tau.data_ptr(), 0, 0, o.d_Ik.data_ptr(), d_I1=o.d_G.data_ptr(), d_n_orders=o.d_nk.data_ptr(),
+                       d_status=o.d_stk.data_ptr())
+        s.bounce_accumulate_device(o.d_Ik.data_ptr(), c.d_Im.data_ptr(), o.d_ratio.data_ptr(), B=c.B)
+        st.copy_(torch.where(st != 0, st, torch.where(o.d_gst != 0, o.d_gst, o.d_stk)))
+        src = o.d_Ik
+    s.set_order_targets(c.d_target.data_ptr())
+
+
 def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
                   mie_aer, device=0, ground=None, bounce_orders=None, brdf_nphi=BRDF_NPHI):
     """Modes m = 1..M of the solve `r` (the mode-0 result of handle `s`, whose columns are set): per mode the matrices and
@@ -1078,36 +1180,12 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
         c.d_Im = torch.from_numpy(np.ascontiguousarray(r.I)).to(c.dev)
         step(c, 0)
         if bounce:
-            M1 = s.N - 1
-            f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=c.dev)
-            o.d_scale = torch.from_numpy(np.array(ground.scale, dtype=np.float64)).to(c.dev)
-            o.d_orders = torch.from_numpy(np.ascontiguousarray(bounce_orders, dtype=np.int32)).to(c.dev)
-            o.d_R, o.d_r0 = f64(c.M, M1, M1), f64(c.M, c.B, M1)
-            s.brdf_operator_modes_device(ground.kind, o.d_R.data_ptr(), 1, c.M, ground.params, brdf_nphi, sign_odd=True)
-            s.brdf_beam_modes_device(ground.kind, c.d_mu0.data_ptr(), o.d_r0.data_ptr(), 1, c.M, ground.params, brdf_nphi, B=c.B)
-            o.d_S, o.d_G, o.d_Ik, o.d_ratio = f64(c.B, M1), f64(c.B, c.L, c.D), f64(c.B, c.L, c.D), f64(c.B)
-            o.d_nk, o.d_stk, o.d_gst = (torch.zeros(c.B, dtype=torch.int32, device=c.dev) for _ in range(3))
-
-    def reflections(c, m):
-        o = c.own
-        st = c.d_status[m - 1]
-        src = c.d_Im                                         # reflection 1 reflects the mode's black solve
-        for k in range(1, o.d_orders.shape[0] + 1):
-            s.ground_source_device(src.data_ptr(), c.d_tau.data_ptr(), o.d_R[m - 1].data_ptr(), o.d_S.data_ptr(),
-                                   o.d_r0[m - 1].data_ptr() if k == 1 else 0, o.d_scale.data_ptr(), B=c.B)
-            s.ground_first_order_device(c.d_tau.data_ptr(), o.d_S.data_ptr(), o.d_G.data_ptr(), o.d_gst.data_ptr(), B=c.B)
-            s.set_order_targets(o.d_orders[k - 1].data_ptr())
-            s.solve_device(c.d_tau.data_ptr(), 0, 0, o.d_Ik.data_ptr(), d_I1=o.d_G.data_ptr(), d_n_orders=o.d_nk.data_ptr(),
-                           d_status=o.d_stk.data_ptr())
-            s.bounce_accumulate_device(o.d_Ik.data_ptr(), c.d_Im.data_ptr(), o.d_ratio.data_ptr(), B=c.B)
-            st.copy_(torch.where(st != 0, st, torch.where(o.d_gst != 0, o.d_gst, o.d_stk)))
-            src = o.d_Ik
-        s.set_order_targets(c.d_target.data_ptr())
+            _reflection_buffers(s, c, ground, bounce_orders, brdf_nphi)
 
     def step(c, m):
         o = c.own
         if bounce and m >= 1:
-            reflections(c, m)
+            _mode_reflections(s, c, m)
         s.azimuth_accumulate_device(m, c.d_Im.data_ptr(), o.d_lev.data_ptr(), nlev, o.d_phi.data_ptr(), o.d_phi.numel(),
                                     o.d_out.data_ptr(), B=c.B)
 
@@ -1116,17 +1194,28 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
 
 
 def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azimuths, M, nphi, first_order, first0, scat0,
-                       atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer, device=0):
+                       atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer, device=0, ground=None, bounce_orders=None,
+                       ground0=None, brdf_nphi=BRDF_NPHI):
     """The view stage per Fourier mode: mode 0 is (`first0`, `scat0`), the result of `view_radiance` on
     r.I; per mode m >= 1 `_solve_modes` leaves the field I^m resident, `Solver.view_radiance_device` runs on it with the rows
     (-1)^m rows^m and p0rows^m of both phase functions (built for all modes once, before the loop), and the synthesis adds
     2 cos(m phi) times the result at the view lanes.  first_order 'exact': the first order is one closed-form evaluation per
     azimuth from p(c(lane, mu0, phi)) / Z0, written, not accumulated; 'modes': the sum of the modes' first orders.  Returns
-    (first [B, nlev, 2V, len(azimuths)], scattered (same shape), mode status [M + 1, B])."""
+    (first [B, nlev, 2V, len(azimuths)], scattered (same shape), None, mode status [M + 1, B]).
+
+    `ground` (the namespace of `_brdf_args`, a named BRDF; `r` the result of `solve_brdf` over it, `bounce_orders` [K, B] its
+    reflections' counts): THE VIEW STAGE OVER THE BRDF GROUND.  Per mode the reflections of
+    `_mode_reflections` run between the black solve and the view stage, which then reads the mode's summed field, and per
+    reflection the ground's term at the view lanes is accumulated from the same source with (-1)^m R^m at the view cosines
+    (`Solver.view_ground_device`).  `ground0` [B, nlev, 2V] is mode 0's ground term from `solve_brdf`: with first_order
+    'exact' its diffuse part -- the beam's single reflection is then rho(mu_view, mu0, phi) at the azimuth itself, written once
+    per azimuth, and the modes carry the diffuse part only -- with 'modes' the whole, and the modes add rho^m(mu_view, mu0).  A
+    Lambertian ground has no mode m >= 1.  The third value is then the ground's term [B, nlev, 2V, len(azimuths)]."""
     import torch
     V2, nlev, nout = 2 * len(view_mu), len(levels), len(azimuths)
     sgn = np.concatenate((-view_mu, view_mu))
     modes_first = first_order == "modes"
+    bounce = ground is not None and ground.kind != "lambertian"
 
     def begin(c):
         dev, B, o = c.dev, c.B, c.own
@@ -1151,6 +1240,22 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
         o.d_first = torch.from_numpy(np.ascontiguousarray(first0)).to(dev)
         o.d_out_scat = torch.empty((B, nlev, V2, nout), dtype=torch.float64, device=dev)
         o.d_out_first = torch.empty((B, nlev, V2, nout), dtype=torch.float64, device=dev) if modes_first else None
+        if ground is not None:
+            o.d_gr = torch.from_numpy(np.ascontiguousarray(ground0)).to(dev)
+            o.d_out_gr = torch.empty((B, nlev, V2, nout), dtype=torch.float64, device=dev)
+            o.d_scale = torch.from_numpy(np.array(ground.scale, dtype=np.float64)).to(dev)
+            if not modes_first:
+                o.d_r0phi = torch.empty((nout, B, V2 // 2), dtype=torch.float64, device=dev)
+                s.brdf_view_beam_azimuth_device(ground.kind, c.d_mu0.data_ptr(), view_mu, o.d_phi.data_ptr(), nout,
+                                                o.d_r0phi.data_ptr(), ground.params, B=B)
+        if bounce:
+            _reflection_buffers(s, c, ground, bounce_orders, brdf_nphi)
+            o.d_Rv = torch.empty((M, s.N - 1, V2 // 2), dtype=torch.float64, device=dev)
+            s.brdf_view_rows_modes_device(ground.kind, view_mu, o.d_Rv.data_ptr(), 1, M, ground.params, brdf_nphi, sign_odd=True)
+            if modes_first:
+                o.d_r0v = torch.empty((M, B, V2 // 2), dtype=torch.float64, device=dev)
+                s.brdf_view_beam_modes_device(ground.kind, c.d_mu0.data_ptr(), view_mu, o.d_r0v.data_ptr(), 1, M, ground.params,
+                                              brdf_nphi, B=B)
         accumulate(c, 0)
 
     def accumulate(c, m):
@@ -1159,9 +1264,21 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
         if modes_first:
             s.view_azimuth_accumulate_device(m, o.d_first.data_ptr(), nlev, V2, o.d_phi.data_ptr(), nout, o.d_out_first.data_ptr(),
                                              B=c.B)
+        if ground is not None and (m == 0 or bounce):
+            s.view_azimuth_accumulate_device(m, o.d_gr.data_ptr(), nlev, V2, o.d_phi.data_ptr(), nout, o.d_out_gr.data_ptr(), B=c.B)
+
+    def view_ground(c, m, k, src):
+        # reflection k of mode m at the view lanes, from the source the ground source has just read; the beam's share only where
+        # the modes carry it
+        o = c.own
+        s.view_ground_device(view_mu, c.d_tau.data_ptr(), levels, o.d_gr.data_ptr(), d_I=src.data_ptr(), d_Rv=o.d_Rv[m - 1].data_ptr(),
+                             d_r0v=o.d_r0v[m - 1].data_ptr() if modes_first and k == 1 else 0, d_scale=o.d_scale.data_ptr(),
+                             accumulate=k > 1, B=c.B)
 
     def step(c, m):
         o = c.own
+        if bounce:
+            _mode_reflections(s, c, m, hook=lambda k, src: view_ground(c, m, k, src))
         s.view_radiance_device(view_mu, c.d_tau.data_ptr(), c.d_Im.data_ptr(), o.rows[0][m - 1].data_ptr(),
                                o.rows[1][m - 1].data_ptr(), levels, d_scat_out=o.d_scat.data_ptr(),
                                d_first_out=o.d_first.data_ptr() if modes_first else 0,
@@ -1181,11 +1298,22 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
                                        quadrature=quadrature, B=c.B)
             s.synchronize()
             first = d_f.permute(1, 2, 3, 0).contiguous().cpu().numpy()   # (the azimuth last, as the synthesis writes it)
-        return first, o.d_out_scat.cpu().numpy()
+        gr = None
+        if ground is not None:
+            if not modes_first:
+                # the beam's single reflection at every azimuth itself, added to the synthesis of the diffuse part
+                d_gb = torch.empty((nout, c.B, nlev, V2), dtype=torch.float64, device=c.dev)
+                for i in range(nout):
+                    s.view_ground_device(view_mu, c.d_tau.data_ptr(), levels, d_gb[i].data_ptr(), d_r0v=o.d_r0phi[i].data_ptr(),
+                                         d_scale=o.d_scale.data_ptr(), B=c.B)
+                s.synchronize()
+                o.d_out_gr += d_gb.permute(1, 2, 3, 0)
+            gr = o.d_out_gr.cpu().numpy()
+        return first, o.d_out_scat.cpu().numpy(), gr
 
-    (first, scat), status = _solve_modes(s, tau, r, mu0, M, nphi, ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)),
-                                         device, begin, step, finish)
-    return first, scat, status
+    (first, scat, gr), status = _solve_modes(s, tau, r, mu0, M, nphi, ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)),
+                                             device, begin, step, finish)
+    return first, scat, gr, status
 
 
 # mode_batch=True: a chunk of c modes is a batch of c x B columns, and every field buffer of the handle (and the chunk's share of

@@ -520,6 +520,45 @@ class Solver:
         on the downward lanes of row L-1."""
         check(lib().sosrt_bounce_accumulate_dev(self._h, int(self.B if B is None else B), _vp(d_Ik), _vp(d_I_total), _vp(d_ratio_out)))
 
+    # ---- the BRDF ground's term at view lanes off the grid (sosrt.h; DESIGN section 22) -------------------
+    def brdf_view_rows_modes_device(self, kind, mu_view, d_out: int, m_first, m_count, params=(), nphi=65, sign_odd=False):
+        """Rows of `brdf_operator_modes_device` at the view cosines `mu_view` [V] (host) in place of the upward nodes: d_out
+        [m_count, N-1, V] with element (j, v) = 2 w_j |mu_j| rho^m(mu_view[v], |mu_j|) ((-1)^m with sign_odd).  At a node the
+        bits of that builder's column."""
+        k, p = self._brdf_kind(kind, params)
+        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
+        check(lib().sosrt_brdf_view_rows_modes_dev(self._h, k, _ptr(p) if p.size else None, int(p.size), int(nphi), int(m_first),
+                                                   int(m_count), int(bool(sign_odd)), int(m.size), _ptr(m), _vp(d_out)))
+
+    def brdf_view_beam_modes_device(self, kind, d_mu0: int, mu_view, d_out: int, m_first, m_count, params=(), nphi=65,
+                                    B: Optional[int] = None):
+        """The same of `brdf_beam_modes_device`: d_out [m_count, B, V] = rho^m(mu_view[v], d_mu0[b])."""
+        k, p = self._brdf_kind(kind, params)
+        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
+        check(lib().sosrt_brdf_view_beam_modes_dev(self._h, int(self.B if B is None else B), k, _ptr(p) if p.size else None,
+                                                   int(p.size), int(nphi), int(m_first), int(m_count), _vp(d_mu0), int(m.size),
+                                                   _ptr(m), _vp(d_out)))
+
+    def brdf_view_beam_azimuth_device(self, kind, d_mu0: int, mu_view, d_phi: int, nphi_out: int, d_out: int, params=(),
+                                      B: Optional[int] = None):
+        """rho(mu_view[v], d_mu0[b], d_phi[q]) at the azimuth itself (phi = 0: the hot spot), no quadrature: d_out [nphi_out, B, V]."""
+        k, p = self._brdf_kind(kind, params)
+        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
+        check(lib().sosrt_brdf_view_beam_azimuth_dev(self._h, int(self.B if B is None else B), k, _ptr(p) if p.size else None,
+                                                     int(p.size), _vp(d_mu0), int(m.size), _ptr(m), int(nphi_out), _vp(d_phi),
+                                                     _vp(d_out)))
+
+    def view_ground_device(self, mu_view, d_tau: int, levels, d_out: int, d_I: int = 0, d_Rv: int = 0, d_r0v: int = 0,
+                           d_scale: int = 0, accumulate=False, d_S_out: int = 0, B: Optional[int] = None):
+        """The ground's unscattered radiance at the view lanes: d_out [B, nlev, 2V], upward lanes (+)= S[b, v] exp(-(tau[b, L-1] -
+        tau[b, t]) / mu_view[v]) with S = scale[b] (Rv I[b, L-1, 0 .. N-2] + r0v[b] exp(-tau[b, L-1] / mu0[b])) (d_S_out [B, V],
+        optional); downward lanes +0 unless accumulating.  d_I, d_Rv 0: the beam-only call; d_r0v 0: the diffuse-only one."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
+        lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.int32)
+        check(lib().sosrt_view_ground_dev(self._h, int(self.B if B is None else B), int(m.size), _ptr(m), _vp(d_tau), _vp(d_I),
+                                          _vp(d_Rv), _vp(d_r0v), _vp(d_scale), int(lev.size), _ptr(lev), int(bool(accumulate)),
+                                          _vp(d_S_out), _vp(d_out)))
+
     # ---- phase functions on the device (phase:68-292) ----------------------------
     _KINDS ={"iso": _lib.PHASE_ISO, "rayleigh": _lib.PHASE_RAYLEIGH, "hg": _lib.PHASE_HG, "table": _lib.PHASE_TABLE}
 
