@@ -49,34 +49,7 @@ static int brdf_params(int kind, const double* params, int nparams, int nphi, Br
     return fail(SOSRT_E_INVALID, "%s: unknown BRDF kind %d", what, kind);
 }
 
-extern "C" {
-
-int sosrt_brdf_operator_dev(sosrt_t* h, int kind, const double* params, int nparams, int nphi, double* d_R_out) {
-    if (int e = brdf_check(h, 0, false, "sosrt_brdf_operator_dev")) return e;
-    BrdfParams bp;
-    if (int e = brdf_params(kind, params, nparams, nphi, bp, "sosrt_brdf_operator_dev")) return e;
-    if (!d_R_out) return fail(SOSRT_E_INVALID, "sosrt_brdf_operator_dev: null argument");
-    HIPCHK(hipSetDevice(h->device));
-    prof_break(h);
-    launch_brdf_operator(h->stream, h->g, bp, nphi, d_R_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int sosrt_brdf_beam_dev(sosrt_t* h, int B, int kind, const double* params, int nparams, int nphi, const double* d_mu0,
-                        double* d_r0_out) {
-    if (int e = brdf_check(h, B, true, "sosrt_brdf_beam_dev")) return e;
-    BrdfParams bp;
-    if (int e = brdf_params(kind, params, nparams, nphi, bp, "sosrt_brdf_beam_dev")) return e;
-    if (!d_mu0 || !d_r0_out) return fail(SOSRT_E_INVALID, "sosrt_brdf_beam_dev: null argument");
-    HIPCHK(hipSetDevice(h->device));
-    prof_break(h);
-    launch_brdf_beam(h->stream, h->g, B, bp, nphi, d_mu0, d_r0_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// the range of Fourier modes the two mode builders take (sosrt.h)
+// the range of Fourier modes the mode builders take (sosrt.h)
 static int brdf_mode_range(int m_first, int m_count, int nphi, const char* what) {
     const int m_max = SOSRT_MAX_MODES < nphi - 2 ? SOSRT_MAX_MODES : nphi - 2;
     if (m_first < 0 || m_count < 1 || m_first > m_max || m_count > m_max - m_first + 1)
@@ -85,32 +58,76 @@ static int brdf_mode_range(int m_first, int m_count, int nphi, const char* what)
     return 0;
 }
 
-int sosrt_brdf_operator_modes_dev(sosrt_t* h, int kind, const double* params, int nparams, int nphi, int m_first, int m_count,
-                                  int sign_odd, double* d_R_out) {
-    if (int e = brdf_check(h, 0, false, "sosrt_brdf_operator_modes_dev")) return e;
+// the view cosines of the entry points of section 22, as the view stage takes them (sosrt_view_radiance_dev)
+static int brdf_view_mu(int V, const double* mu_view, ViewMu& vm, const char* what) {
+    if (V < 1 || V > SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "%s: V=%d view cosines: must be 1..%d", what, V, SOSRT_MAX_VIEWS);
+    if (!mu_view) return fail(SOSRT_E_INVALID, "%s: null mu_view", what);
+    for (int v = 0; v < V; ++v)
+        if (!(std::isfinite(mu_view[v]) && mu_view[v] >= 0.01 && mu_view[v] <= 1))
+            return fail(SOSRT_E_INVALID, "%s: mu_view[%d] = %g: a view cosine must be finite and in [0.01, 1]", what, v, mu_view[v]);
+    for (int j = 0; j < 2 * kMaxViews; ++j) vm.s[j] = j < V ? mu_view[j] : 1.0;
+    return 0;
+}
+
+// The one path of the six builders (launch_brdf_pairs), entry point `what`: the handle and, where the call is per column (`beam`:
+// the second direction is d_mu0 [B], else the grid's downward nodes), B; the BRDF and its node count; the range of modes where the
+// call has one (`modes`, else mode 0 alone: the azimuth mean); the view cosines where it has them (`views`, else the grid's upward
+// nodes); the pointers.  In this order for every entry point, and all of it before the launch: a refused call writes nothing.
+static int brdf_build(sosrt_handle* h, const char* what, bool beam, int B, bool views, int V, const double* mu_view, int kind,
+                      const double* params, int nparams, int nphi, bool modes, int m_first, int m_count, int sign_odd,
+                      const double* d_mu0, double* d_out) {
+    if (int e = brdf_check(h, B, beam, what)) return e;
     BrdfParams bp;
-    if (int e = brdf_params(kind, params, nparams, nphi, bp, "sosrt_brdf_operator_modes_dev")) return e;
-    if (int e = brdf_mode_range(m_first, m_count, nphi, "sosrt_brdf_operator_modes_dev")) return e;
-    if (!d_R_out) return fail(SOSRT_E_INVALID, "sosrt_brdf_operator_modes_dev: null argument");
+    if (int e = brdf_params(kind, params, nparams, nphi, bp, what)) return e;
+    if (modes)
+        if (int e = brdf_mode_range(m_first, m_count, nphi, what)) return e;
+    ViewMu vm = {};
+    if (views)
+        if (int e = brdf_view_mu(V, mu_view, vm, what)) return e;
+    if ((beam && !d_mu0) || !d_out) return fail(SOSRT_E_INVALID, "%s: null argument", what);
     HIPCHK(hipSetDevice(h->device));
     prof_break(h);
-    launch_brdf_operator_modes(h->stream, h->g, bp, nphi, m_first, m_count, sign_odd, d_R_out);
+    launch_brdf_pairs(h->stream, h->g, vm, views ? V : 0, B, bp, nphi, modes ? m_first : 0, modes ? m_count : 1, sign_odd,
+                      beam ? d_mu0 : nullptr, d_out);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
+extern "C" {
+
+int sosrt_brdf_operator_dev(sosrt_t* h, int kind, const double* params, int nparams, int nphi, double* d_R_out) {
+    return brdf_build(h, "sosrt_brdf_operator_dev", false, 0, false, 0, nullptr, kind, params, nparams, nphi, false, 0, 1, 0, nullptr,
+                      d_R_out);
+}
+
+int sosrt_brdf_beam_dev(sosrt_t* h, int B, int kind, const double* params, int nparams, int nphi, const double* d_mu0,
+                        double* d_r0_out) {
+    return brdf_build(h, "sosrt_brdf_beam_dev", true, B, false, 0, nullptr, kind, params, nparams, nphi, false, 0, 1, 0, d_mu0,
+                      d_r0_out);
+}
+
+int sosrt_brdf_operator_modes_dev(sosrt_t* h, int kind, const double* params, int nparams, int nphi, int m_first, int m_count,
+                                  int sign_odd, double* d_R_out) {
+    return brdf_build(h, "sosrt_brdf_operator_modes_dev", false, 0, false, 0, nullptr, kind, params, nparams, nphi, true, m_first,
+                      m_count, sign_odd, nullptr, d_R_out);
+}
+
 int sosrt_brdf_beam_modes_dev(sosrt_t* h, int B, int kind, const double* params, int nparams, int nphi, int m_first, int m_count,
                               const double* d_mu0, double* d_r0_out) {
-    if (int e = brdf_check(h, B, true, "sosrt_brdf_beam_modes_dev")) return e;
-    BrdfParams bp;
-    if (int e = brdf_params(kind, params, nparams, nphi, bp, "sosrt_brdf_beam_modes_dev")) return e;
-    if (int e = brdf_mode_range(m_first, m_count, nphi, "sosrt_brdf_beam_modes_dev")) return e;
-    if (!d_mu0 || !d_r0_out) return fail(SOSRT_E_INVALID, "sosrt_brdf_beam_modes_dev: null argument");
-    HIPCHK(hipSetDevice(h->device));
-    prof_break(h);
-    launch_brdf_beam_modes(h->stream, h->g, B, bp, nphi, m_first, m_count, d_mu0, d_r0_out);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return brdf_build(h, "sosrt_brdf_beam_modes_dev", true, B, false, 0, nullptr, kind, params, nparams, nphi, true, m_first, m_count,
+                      0, d_mu0, d_r0_out);
+}
+
+int sosrt_brdf_view_rows_modes_dev(sosrt_t* h, int kind, const double* params, int nparams, int nphi, int m_first, int m_count,
+                                   int sign_odd, int V, const double* mu_view, double* d_out) {
+    return brdf_build(h, "sosrt_brdf_view_rows_modes_dev", false, 0, true, V, mu_view, kind, params, nparams, nphi, true, m_first,
+                      m_count, sign_odd, nullptr, d_out);
+}
+
+int sosrt_brdf_view_beam_modes_dev(sosrt_t* h, int B, int kind, const double* params, int nparams, int nphi, int m_first,
+                                   int m_count, const double* d_mu0, int V, const double* mu_view, double* d_out) {
+    return brdf_build(h, "sosrt_brdf_view_beam_modes_dev", true, B, true, V, mu_view, kind, params, nparams, nphi, true, m_first,
+                      m_count, 0, d_mu0, d_out);
 }
 
 int sosrt_ground_source_dev(sosrt_t* h, int B, const double* d_I, const double* d_tau, const double* d_R, const double* d_r0,
@@ -144,56 +161,7 @@ int sosrt_bounce_accumulate_dev(sosrt_t* h, int B, const double* d_Ik, double* d
     return 0;
 }
 
-}  // extern "C"
-
-// ---- the ground's term at view lanes off the grid ----
-// the view cosines of the four entry points below, as the view stage takes them (sosrt_view_radiance_dev)
-static int brdf_view_mu(int V, const double* mu_view, ViewMu& vm, const char* what) {
-    if (V < 1 || V > SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "%s: V=%d view cosines: must be 1..%d", what, V, SOSRT_MAX_VIEWS);
-    if (!mu_view) return fail(SOSRT_E_INVALID, "%s: null mu_view", what);
-    for (int v = 0; v < V; ++v)
-        if (!(std::isfinite(mu_view[v]) && mu_view[v] >= 0.01 && mu_view[v] <= 1))
-            return fail(SOSRT_E_INVALID, "%s: mu_view[%d] = %g: a view cosine must be finite and in [0.01, 1]", what, v, mu_view[v]);
-    for (int j = 0; j < 2 * kMaxViews; ++j) vm.s[j] = j < V ? mu_view[j] : 1.0;
-    return 0;
-}
-
-extern "C" {
-
-int sosrt_brdf_view_rows_modes_dev(sosrt_t* h, int kind, const double* params, int nparams, int nphi, int m_first, int m_count,
-                                   int sign_odd, int V, const double* mu_view, double* d_out) {
-    const char* what = "sosrt_brdf_view_rows_modes_dev";
-    if (int e = brdf_check(h, 0, false, what)) return e;
-    BrdfParams bp;
-    if (int e = brdf_params(kind, params, nparams, nphi, bp, what)) return e;
-    if (int e = brdf_mode_range(m_first, m_count, nphi, what)) return e;
-    ViewMu vm;
-    if (int e = brdf_view_mu(V, mu_view, vm, what)) return e;
-    if (!d_out) return fail(SOSRT_E_INVALID, "%s: null argument", what);
-    HIPCHK(hipSetDevice(h->device));
-    prof_break(h);
-    launch_brdf_view_rows_modes(h->stream, h->g, vm, V, bp, nphi, m_first, m_count, sign_odd, d_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int sosrt_brdf_view_beam_modes_dev(sosrt_t* h, int B, int kind, const double* params, int nparams, int nphi, int m_first,
-                                   int m_count, const double* d_mu0, int V, const double* mu_view, double* d_out) {
-    const char* what = "sosrt_brdf_view_beam_modes_dev";
-    if (int e = brdf_check(h, B, true, what)) return e;
-    BrdfParams bp;
-    if (int e = brdf_params(kind, params, nparams, nphi, bp, what)) return e;
-    if (int e = brdf_mode_range(m_first, m_count, nphi, what)) return e;
-    ViewMu vm;
-    if (int e = brdf_view_mu(V, mu_view, vm, what)) return e;
-    if (!d_mu0 || !d_out) return fail(SOSRT_E_INVALID, "%s: null argument", what);
-    HIPCHK(hipSetDevice(h->device));
-    prof_break(h);
-    launch_brdf_view_beam_modes(h->stream, B, vm, V, bp, nphi, m_first, m_count, d_mu0, d_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
+// ---- the ground's term at view lanes off the grid: what is not a builder of modes ----
 int sosrt_brdf_view_beam_azimuth_dev(sosrt_t* h, int B, int kind, const double* params, int nparams, const double* d_mu0, int V,
                                      const double* mu_view, int nphi_out, const double* d_phi, double* d_out) {
     const char* what = "sosrt_brdf_view_beam_azimuth_dev";

@@ -1,21 +1,22 @@
 // BRDF ground, gfx950: the stages of the series in ground reflections that runs around the order loop.
 //
-//   k_brdf_operator        R(i, j) = 2 w_j |mu_j| rho_bar(mu_i, |mu_j|): one lane per pair, the azimuth nodes in a loop; every
-//                          (pair, node) is evaluated once, the cosines of a chunk of nodes come from LDS.
-//   k_brdf_beam            r0[b][i] = rho_bar(mu_i, mu0[b]): one lane per (column, upward lane), the same loop.
-//   k_brdf_operator_modes   the Fourier modes m of R in azimuth, R^m(i, j) = 2 w_j |mu_j| rho^m(mu_i, |mu_j|), the same
-//   k_brdf_beam_modes      layout and loop: rho at a (pair, node) feeds the register accumulators of up to 8 modes per launch, the
-//                          nodes' weights times cos(m phi) come from LDS; mode 0 has the bits of the two kernels above.
-//   k_ground_source        S = scale (R I_surface + r0 e^{-tau*/mu0}): one workgroup per column, the surface row in LDS, one lane
-//                          per upward lane i, fused multiply-adds over j ascending (R is stored with the lanes i of one j contiguous).
+//   k_brdf_pairs<NM>       every builder of the named BRDF's Fourier modes in azimuth, rho^m(a, b) = (1 / pi) int_0^pi rho(a, b, phi)
+//                          cos(m phi) dphi on the trapezoid nodes: one lane per pair (a, b), the azimuth nodes in a loop, rho at a
+//                          (pair, node) evaluated once and fed to the register accumulators of NM modes, the nodes' cosines and
+//                          weights times cos(m phi) from LDS.  a: the grid's upward nodes mu_i (sections 20, 21) or view cosines
+//                          off the grid (section 22).  b: the grid's downward nodes, stored as the operator 2 w_j |mu_j| rho^m(a,
+//                          |mu_j|) with the optional (-1)^m, or the columns' mu0, stored as the beam row rho^m(a, mu0_b).  NM = 1
+//                          for a launch of one mode (the azimuth mean rho_bar is mode 0), NM = 8 otherwise; a mode's bits are the
+//                          same in both, and the same at a view cosine that is a node as at the node.
+//   k_ground_source        S = scale (R I_surface + r0 e^{-tau*/mu0}) (ground_chain): one workgroup per column, the surface row in
+//                          LDS, one lane per upward lane i, fused multiply-adds over j ascending (R is stored with the lanes i of
+//                          one j contiguous).
 //   k_ground_first_order   the unscattered upward field of S with the mu -> 0+ blend of the order loop's upward sweep on every
 //                          row: one workgroup per column, one wave per row, the row in LDS for the blend's search.
 //   k_bounce_accumulate    total += Ik and the column's ratio of the two fields on the TOA-up and surface-down lanes.
-//   k_brdf_view_rows_modes the same modes at view cosines off the grid, 2 w_j |mu_j| rho^m(mu_view_v, |mu_j|) and
-//   k_brdf_view_beam_modes rho^m(mu_view_v, mu0_b): the layout and loop of the two mode kernels, their bits at a node.
 //   k_brdf_view_beam_azimuth rho(mu_view_v, mu0_b, phi) at an azimuth itself, no quadrature.
-//   k_view_ground          the ground's unscattered radiance at the view lanes: k_ground_source's chain with the view rows, one
-//                          exp per (level, lane); downward lanes +0; written or accumulated.
+//   k_view_ground          (section 22) the ground's unscattered radiance at the view lanes: ground_chain with the rows at the view
+//                          cosines, one exp per (level, lane); downward lanes +0; written or accumulated.
 //
 // The kernels read the grid, the columns' mu0 (ColScalars) and their arguments, and write nothing but their outputs.
 #include "brdf.hpp"
@@ -56,62 +57,7 @@ __device__ __forceinline__ double rpv(const BrdfParams& bp, const Dir& a, const 
     return rho0 * minnaert * F * (1.0 + (1.0 - rho0) / (1.0 + G));
 }
 
-// (1 / pi) int_0^pi rho dphi by the trapezoid rule on nphi nodes; s_cos: 2 kPhiChunk doubles of the workgroup (cos phi and
-// 1 - cos phi of a chunk of nodes).  Every thread of the workgroup calls this (the chunk loop holds barriers); `live` says
-// whether the lane has a pair.
-__device__ __forceinline__ double azimuth_mean(const BrdfParams& bp, bool live, double ca, double cb, int nphi, double* s_cos) {
-    double* s_hav = s_cos + kPhiChunk;
-    const Dir a = make_dir(ca), b = make_dir(cb);
-    const double minnaert = bp.kind == SOSRT_BRDF_RPV ? pow(a.c * b.c * (a.c + b.c), bp.p[1] - 1.0) : 1.0;
-    const double h = 1.0 / (nphi - 1);
-    double acc = 0;
-    for (int q0 = 0; q0 < nphi; q0 += kPhiChunk) {
-        const int nq = min(kPhiChunk, nphi - q0);
-        __syncthreads();
-        for (int q = threadIdx.x; q < nq; q += blockDim.x) {
-            const double phi = kPi * (q0 + q) * h, sh = sin(0.5 * phi);
-            s_cos[q] = q0 + q == nphi - 1 ? -1.0 : cos(phi);
-            s_hav[q] = q0 + q == nphi - 1 ? 2.0 : 2.0 * sh * sh;
-        }
-        __syncthreads();
-        if (live) {
-            for (int q = 0; q < nq; ++q) {
-                const double v = bp.kind == SOSRT_BRDF_RPV ? rpv(bp, a, b, minnaert, s_cos[q], s_hav[q]) : 1.0;
-                const double w = (q0 + q == 0 || q0 + q == nphi - 1) ? 0.5 * h : h;
-                acc = fma(w, v, acc);
-            }
-        }
-    }
-    return acc;
-}
-
-__global__ __launch_bounds__(256) void k_brdf_operator(Grid g, BrdfParams bp, int nphi, double* __restrict__ R) {
-    __shared__ double s_cos[2 * kPhiChunk];
-    const int N = g.N, M = N - 1;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = idx < (long long)M * M;
-    const int j = live ? (int)(idx / M) : 0, i = live ? (int)(idx - (long long)j * M) : 0;
-    const double a = g.mu[N + 1 + i], b = -g.mu[j];
-    const double rb = azimuth_mean(bp, live, a, b, nphi, s_cos);
-    if (live) {
-        // trapezoid weight of node j among mu[0 .. N-2]
-        const double w = j == 0 ? (g.mu[1] - g.mu[0]) / 2 : j == M - 1 ? (g.mu[M - 1] - g.mu[M - 2]) / 2 : (g.mu[j + 1] - g.mu[j - 1]) / 2;
-        R[idx] = 2.0 * w * b * rb;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_brdf_beam(Grid g, int B, BrdfParams bp, int nphi, const double* __restrict__ mu0,
-                                                   double* __restrict__ r0) {
-    __shared__ double s_cos[2 * kPhiChunk];
-    const int N = g.N, M = N - 1;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = idx < (long long)B * M;
-    const int b = live ? (int)(idx / M) : 0, i = live ? (int)(idx - (long long)b * M) : 0;
-    const double rb = azimuth_mean(bp, live, g.mu[N + 1 + i], mu0[b], nphi, s_cos);
-    if (live) r0[idx] = rb;
-}
-
-// ---- Fourier modes of the BRDF in azimuth ----
+// ---- the BRDF's Fourier modes in azimuth (DESIGN sections 20 to 22; mode 0 is the azimuth mean) ----
 // cos(m phi_q) on the nphi nodes phi_q = pi q / (nphi - 1): the integer product m q reduced modulo the 2 (nphi - 1) nodes of the
 // full circle and folded onto [0, pi], so that m = 0 gives 1, node nphi - 1 gives (-1)^m and a quarter turn gives 0, all exactly.
 __device__ __forceinline__ double mode_cos(int m, int q, int nphi, double h) {
@@ -124,12 +70,13 @@ __device__ __forceinline__ double mode_cos(int m, int q, int nphi, double h) {
     return cos(kPi * r * h);
 }
 
-// rho^m(a, b) = (1 / pi) int_0^pi rho cos(m phi) dphi for the modes m0 .. m0 + nm - 1 (nm <= kModesPerLaunch) by the trapezoid
-// rule of azimuth_mean: rho at a (pair, node) is evaluated once and feeds the accumulators of all modes, which stay in registers
-// (the loops over k have a constant trip count and are unrolled; a mode k >= nm has weight 0).  s_cos: (2 + kModesPerLaunch)
-// kPhiChunk doubles of the workgroup: cos phi, 1 - cos phi and per mode the weight of the node times cos(m phi) for a chunk of
-// nodes.  With m = 0 the weight times 1 is the weight, so mode 0 has the bits of azimuth_mean.  Every thread of the workgroup
-// calls this.
+// rho^m(a, b) = (1 / pi) int_0^pi rho cos(m phi) dphi for the modes m0 .. m0 + nm - 1 (nm <= NM) by the trapezoid rule on nphi
+// nodes: rho at a (pair, node) is evaluated once and feeds the accumulators of all modes, which stay in registers (the loops
+// over k have a constant trip count and are unrolled; a mode k >= nm carries weight 0 into an accumulator of its own, so a
+// mode's bits do not depend on NM).  s_cos: (2 + NM) kPhiChunk doubles of the workgroup: cos phi, 1 - cos phi and per mode the
+// weight of the node times cos(m phi) for a chunk of nodes.  With m = 0 the weight times 1 is the weight: mode 0 is the plain
+// trapezoid sum, the azimuth mean.  Every thread of the workgroup calls this (the chunk loop holds barriers); `live` says
+// whether the lane has a pair.
 template <int NM>
 __device__ __forceinline__ void azimuth_modes(const BrdfParams& bp, bool live, double ca, double cb, int nphi, int m0, int nm,
                                               double* s_cos, double (&acc)[NM]) {
@@ -162,43 +109,55 @@ __device__ __forceinline__ void azimuth_modes(const BrdfParams& bp, bool live, d
     }
 }
 
-__global__ __launch_bounds__(256) void k_brdf_operator_modes(Grid g, BrdfParams bp, int nphi, int m0, int nm, int sign_odd,
-                                                             double* __restrict__ R) {
-    __shared__ double s_cos[(2 + kModesPerLaunch) * kPhiChunk];
+// trapezoid weight of node j among mu[0 .. N-2], the grid's downward nodes
+__device__ __forceinline__ double flux_weight(const Grid& g, int j) {
+    const int M = g.N - 1;
+    return j == 0 ? (g.mu[1] - g.mu[0]) / 2 : j == M - 1 ? (g.mu[M - 1] - g.mu[M - 2]) / 2 : (g.mu[j + 1] - g.mu[j - 1]) / 2;
+}
+
+// The modes m0 .. m0 + nm - 1 (nm <= NM) of every pair (first, second) of directions, out [nm][nSecond][nFirst].  First: the
+// view cosines vm.s[0 .. V-1], or with V = 0 the grid's upward nodes mu[N+1 ..].  Second: the columns' mu0[0 .. B-1], stored as
+// rho^m itself, or with mu0 = nullptr the grid's downward nodes |mu_j|, stored as 2 w_j |mu_j| rho^m, mode m as (-1)^m of it
+// where sign_odd.  A lane past the pairs stays for the barriers of the node loop.
+template <int NM>
+__global__ __launch_bounds__(256) void k_brdf_pairs(Grid g, ViewMu vm, int V, int B, BrdfParams bp, int nphi, int m0, int nm,
+                                                    int sign_odd, const double* __restrict__ mu0, double* __restrict__ out) {
+    __shared__ double s_cos[(2 + NM) * kPhiChunk];
     const int N = g.N, M = N - 1;
-    const long long pairs = (long long)M * M;
+    const int nFirst = V ? V : M;
+    const long long n = (long long)(mu0 ? B : M) * nFirst;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = idx < pairs;
-    const int j = live ? (int)(idx / M) : 0, i = live ? (int)(idx - (long long)j * M) : 0;
-    const double a = g.mu[N + 1 + i], b = -g.mu[j];
-    double rb[kModesPerLaunch];
-    azimuth_modes<kModesPerLaunch>(bp, live, a, b, nphi, m0, nm, s_cos, rb);
+    const bool live = idx < n;
+    const int second = live ? (int)(idx / nFirst) : 0, first = live ? (int)(idx - (long long)second * nFirst) : 0;
+    const double a = V ? vm.s[first] : g.mu[N + 1 + first], b = mu0 ? mu0[second] : -g.mu[second];
+    double rb[NM];
+    azimuth_modes<NM>(bp, live, a, b, nphi, m0, nm, s_cos, rb);
     if (live) {
-        const double w = j == 0 ? (g.mu[1] - g.mu[0]) / 2 : j == M - 1 ? (g.mu[M - 1] - g.mu[M - 2]) / 2 : (g.mu[j + 1] - g.mu[j - 1]) / 2;
+        const double w = mu0 ? 0.0 : flux_weight(g, second);
 #pragma unroll
-        for (int k = 0; k < kModesPerLaunch; ++k)
+        for (int k = 0; k < NM; ++k)
             if (k < nm) {
-                const double v = 2.0 * w * b * rb[k];
-                R[(size_t)k * pairs + idx] = (sign_odd && ((m0 + k) & 1)) ? -v : v;
+                double x = rb[k];
+                if (!mu0) {
+                    x = 2.0 * w * b * x;
+                    if (sign_odd && ((m0 + k) & 1)) x = -x;
+                }
+                out[(size_t)k * n + idx] = x;
             }
     }
 }
 
-__global__ __launch_bounds__(256) void k_brdf_beam_modes(Grid g, int B, BrdfParams bp, int nphi, int m0, int nm,
-                                                         const double* __restrict__ mu0, double* __restrict__ r0) {
-    __shared__ double s_cos[(2 + kModesPerLaunch) * kPhiChunk];
-    const int N = g.N, M = N - 1;
-    const long long n = (long long)B * M;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = idx < n;
-    const int b = live ? (int)(idx / M) : 0, i = live ? (int)(idx - (long long)b * M) : 0;
-    double rb[kModesPerLaunch];
-    azimuth_modes<kModesPerLaunch>(bp, live, g.mu[N + 1 + i], mu0[b], nphi, m0, nm, s_cos, rb);
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < kModesPerLaunch; ++k)
-            if (k < nm) r0[(size_t)k * n + idx] = rb[k];
-    }
+// S of one lane = scale (sum_j R[j n + lane] s_I[j] + r0 exp(-tauL / mu0)): the sum over the M entries of the surface row by
+// fused multiply-adds with j ascending, then the beam term (its exp evaluated only where r0, the lane's beam row, is given),
+// the scale last.  R (no field, no sum), r0 and scale (the column's) are nullable.
+__device__ __forceinline__ double ground_chain(const double* __restrict__ R, int n, int lane, const double* s_I, int M,
+                                               const double* __restrict__ r0, double tauL, double mu0,
+                                               const double* __restrict__ scale) {
+    double acc = 0;
+    if (R)
+        for (int j = 0; j < M; ++j) acc = fma(R[(size_t)j * n + lane], s_I[j], acc);
+    if (r0) acc += *r0 * exp(-tauL / mu0);
+    return scale ? *scale * acc : acc;
 }
 
 __global__ __launch_bounds__(1024) void k_ground_source(Grid g, int B, ColScalars sc, const double* __restrict__ I_all,
@@ -213,10 +172,8 @@ __global__ __launch_bounds__(1024) void k_ground_source(Grid g, int B, ColScalar
     for (int j = i; j < M; j += blockDim.x) s_I[j] = row[j];
     __syncthreads();
     if (i >= M) return;
-    double acc = 0;
-    for (int j = 0; j < M; ++j) acc = fma(R[(size_t)j * M + i], s_I[j], acc);
-    if (r0) acc += r0[(size_t)b * M + i] * exp(-tau_all[(size_t)b * L + (L - 1)] / sc.mu0[b]);
-    S_all[(size_t)b * M + i] = scale ? scale[b] * acc : acc;
+    S_all[(size_t)b * M + i] = ground_chain(R, M, i, s_I, M, r0 ? r0 + (size_t)b * M + i : nullptr, tau_all[(size_t)b * L + (L - 1)],
+                                            sc.mu0[b], scale ? scale + b : nullptr);
 }
 
 constexpr int kGfoWaves = 4;
@@ -327,46 +284,6 @@ __global__ __launch_bounds__(256) void k_bounce_accumulate(Grid g, int B, const 
 }
 
 // ---- the ground's term at view lanes off the grid ----
-// The rows of the operator modes at view cosines in place of the upward nodes: (j, v) in place of (j, i), everything else as
-// k_brdf_operator_modes, so that at a view cosine equal to the node mu[N+1+i] the output has the bits of that kernel's column i.
-__global__ __launch_bounds__(256) void k_brdf_view_rows_modes(Grid g, ViewMu vm, int V, BrdfParams bp, int nphi, int m0, int nm,
-                                                              int sign_odd, double* __restrict__ R) {
-    __shared__ double s_cos[(2 + kModesPerLaunch) * kPhiChunk];
-    const int M = g.N - 1;
-    const long long pairs = (long long)M * V;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = idx < pairs;
-    const int j = live ? (int)(idx / V) : 0, v = live ? (int)(idx - (long long)j * V) : 0;
-    const double a = vm.s[v], b = -g.mu[j];
-    double rb[kModesPerLaunch];
-    azimuth_modes<kModesPerLaunch>(bp, live, a, b, nphi, m0, nm, s_cos, rb);
-    if (live) {
-        const double w = j == 0 ? (g.mu[1] - g.mu[0]) / 2 : j == M - 1 ? (g.mu[M - 1] - g.mu[M - 2]) / 2 : (g.mu[j + 1] - g.mu[j - 1]) / 2;
-#pragma unroll
-        for (int k = 0; k < kModesPerLaunch; ++k)
-            if (k < nm) {
-                const double x = 2.0 * w * b * rb[k];
-                R[(size_t)k * pairs + idx] = (sign_odd && ((m0 + k) & 1)) ? -x : x;
-            }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_brdf_view_beam_modes(int B, ViewMu vm, int V, BrdfParams bp, int nphi, int m0, int nm,
-                                                              const double* __restrict__ mu0, double* __restrict__ r0) {
-    __shared__ double s_cos[(2 + kModesPerLaunch) * kPhiChunk];
-    const long long n = (long long)B * V;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = idx < n;
-    const int b = live ? (int)(idx / V) : 0, v = live ? (int)(idx - (long long)b * V) : 0;
-    double rb[kModesPerLaunch];
-    azimuth_modes<kModesPerLaunch>(bp, live, vm.s[v], mu0[b], nphi, m0, nm, s_cos, rb);
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < kModesPerLaunch; ++k)
-            if (k < nm) r0[(size_t)k * n + idx] = rb[k];
-    }
-}
-
 // rho(mu_view_v, mu0_b, phi_q) at the azimuth itself, no quadrature: one lane per (q, b, v)
 __global__ __launch_bounds__(256) void k_brdf_view_beam_azimuth(int B, ViewMu vm, int V, BrdfParams bp, const double* __restrict__ mu0,
                                                                 int nphi_out, const double* __restrict__ phi, double* __restrict__ out) {
@@ -386,7 +303,7 @@ __global__ __launch_bounds__(256) void k_brdf_view_beam_azimuth(int B, ViewMu vm
     out[idx] = r;
 }
 
-// The ground's unscattered radiance at the view lanes: S^view of k_ground_source's chain with the rows at the view cosines
+// The ground's unscattered radiance at the view lanes: S^view of k_ground_source's ground_chain with the rows at the view cosines
 // ((j, v) in place of (j, i)), then one exp per (level, lane).  One workgroup per column, one lane per v; out [B][nlev_all][2V],
 // `out` offset to the first level of lv.
 __global__ __launch_bounds__(kMaxViews) void k_view_ground(Grid g, int B, int V, ViewMu vm, ColScalars sc,
@@ -405,11 +322,8 @@ __global__ __launch_bounds__(kMaxViews) void k_view_ground(Grid g, int B, int V,
     __syncthreads();
     if (v >= V) return;
     const double* tau = tau_all + (size_t)b * L;
-    double acc = 0;
-    if (I_all)
-        for (int j = 0; j < M; ++j) acc = fma(Rv[(size_t)j * V + v], s_I[j], acc);
-    if (r0v) acc += r0v[(size_t)b * V + v] * exp(-tau[L - 1] / sc.mu0[b]);
-    const double S = scale ? scale[b] * acc : acc;
+    const double S = ground_chain(I_all ? Rv : nullptr, V, v, s_I, M, r0v ? r0v + (size_t)b * V + v : nullptr, tau[L - 1], sc.mu0[b],
+                                  scale ? scale + b : nullptr);
     if (S_out) S_out[(size_t)b * V + v] = S;
     const double tauL = tau[L - 1], mv = vm.s[v];
     for (int l = 0; l < lv.n; ++l) {
@@ -427,20 +341,16 @@ __global__ __launch_bounds__(kMaxViews) void k_view_ground(Grid g, int B, int V,
 
 }  // namespace
 
-void launch_brdf_view_rows_modes(hipStream_t s, const Grid& g, const ViewMu& vm, int V, BrdfParams bp, int nphi, int m_first,
-                                 int m_count, int sign_odd, double* R) {
-    const long long pairs = (long long)(g.N - 1) * V;
-    for (int m = 0; m < m_count; m += kModesPerLaunch)
-        hipLaunchKernelGGL(k_brdf_view_rows_modes, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, g, vm, V, bp, nphi,
-                           m_first + m, min(kModesPerLaunch, m_count - m), sign_odd, R + (size_t)m * pairs);
-}
-
-void launch_brdf_view_beam_modes(hipStream_t s, int B, const ViewMu& vm, int V, BrdfParams bp, int nphi, int m_first, int m_count,
-                                 const double* mu0, double* r0) {
-    const long long n = (long long)B * V;
-    for (int m = 0; m < m_count; m += kModesPerLaunch)
-        hipLaunchKernelGGL(k_brdf_view_beam_modes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, B, vm, V, bp, nphi,
-                           m_first + m, min(kModesPerLaunch, m_count - m), mu0, r0 + (size_t)m * n);
+void launch_brdf_pairs(hipStream_t s, const Grid& g, const ViewMu& vm, int V, int B, BrdfParams bp, int nphi, int m_first,
+                       int m_count, int sign_odd, const double* mu0, double* out) {
+    const long long n = (long long)(mu0 ? B : g.N - 1) * (V ? V : g.N - 1);
+    const dim3 blocks((unsigned)((n + 255) / 256));
+    for (int m = 0; m < m_count; m += kModesPerLaunch) {
+        const int nm = min(kModesPerLaunch, m_count - m);
+        const auto kernel = nm == 1 ? k_brdf_pairs<1> : k_brdf_pairs<kModesPerLaunch>;
+        hipLaunchKernelGGL(kernel, blocks, dim3(256), 0, s, g, vm, V, B, bp, nphi, m_first + m, nm, sign_odd, mu0,
+                           out + (size_t)m * n);
+    }
 }
 
 void launch_brdf_view_beam_azimuth(hipStream_t s, int B, const ViewMu& vm, int V, BrdfParams bp, const double* mu0, int nphi_out,
@@ -455,32 +365,6 @@ void launch_view_ground(hipStream_t s, const Grid& g, int B, int V, const ViewMu
                         const ViewLevels& lv, int accumulate, double* S_out, double* out) {
     hipLaunchKernelGGL(k_view_ground, dim3((unsigned)B), dim3(kMaxViews), (size_t)(g.N - 1) * sizeof(double), s, g, B, V, vm, sc,
                        I, tau, Rv, r0v, scale, nlev_all, lv, accumulate, S_out, out);
-}
-
-void launch_brdf_operator(hipStream_t s, const Grid& g, BrdfParams bp, int nphi, double* R) {
-    const long long pairs = (long long)(g.N - 1) * (g.N - 1);
-    hipLaunchKernelGGL(k_brdf_operator, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, g, bp, nphi, R);
-}
-
-void launch_brdf_beam(hipStream_t s, const Grid& g, int B, BrdfParams bp, int nphi, const double* mu0, double* r0) {
-    const long long n = (long long)B * (g.N - 1);
-    hipLaunchKernelGGL(k_brdf_beam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, B, bp, nphi, mu0, r0);
-}
-
-void launch_brdf_operator_modes(hipStream_t s, const Grid& g, BrdfParams bp, int nphi, int m_first, int m_count, int sign_odd,
-                                double* R) {
-    const long long pairs = (long long)(g.N - 1) * (g.N - 1);
-    for (int m = 0; m < m_count; m += kModesPerLaunch)
-        hipLaunchKernelGGL(k_brdf_operator_modes, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, g, bp, nphi, m_first + m,
-                           min(kModesPerLaunch, m_count - m), sign_odd, R + (size_t)m * pairs);
-}
-
-void launch_brdf_beam_modes(hipStream_t s, const Grid& g, int B, BrdfParams bp, int nphi, int m_first, int m_count, const double* mu0,
-                            double* r0) {
-    const long long n = (long long)B * (g.N - 1);
-    for (int m = 0; m < m_count; m += kModesPerLaunch)
-        hipLaunchKernelGGL(k_brdf_beam_modes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, B, bp, nphi, m_first + m,
-                           min(kModesPerLaunch, m_count - m), mu0, r0 + (size_t)m * n);
 }
 
 void launch_ground_source(hipStream_t s, const Grid& g, int B, ColScalars sc, const double* I, const double* tau, const double* R,

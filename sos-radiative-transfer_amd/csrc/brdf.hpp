@@ -12,16 +12,18 @@ struct BrdfParams {
     double p[3];                       // RPV: rho0, k, Theta
 };
 
-// R [N-1][N-1], element (j, i) at j (N-1) + i: 2 w_j |mu_j| rho_bar(mu[N+1+i], |mu_j|)
-void launch_brdf_operator(hipStream_t s, const Grid& g, BrdfParams bp, int nphi, double* R);
-// r0 [B][N-1]: rho_bar(mu[N+1+i], mu0[b])
-void launch_brdf_beam(hipStream_t s, const Grid& g, int B, BrdfParams bp, int nphi, const double* mu0, double* r0);
-// Fourier modes m_first .. m_first + m_count - 1 in azimuth, rho^m = (1 / pi) int_0^pi rho cos(m phi) dphi in
-// place of rho_bar: R [m_count][N-1][N-1], mode m as (-1)^m R^m where sign_odd; r0 [m_count][B][N-1].  Mode 0: the bits of the two above.
-void launch_brdf_operator_modes(hipStream_t s, const Grid& g, BrdfParams bp, int nphi, int m_first, int m_count, int sign_odd,
-                                double* R);
-void launch_brdf_beam_modes(hipStream_t s, const Grid& g, int B, BrdfParams bp, int nphi, int m_first, int m_count, const double* mu0,
-                            double* r0);
+// The Fourier modes m_first .. m_first + m_count - 1 in azimuth of the named BRDF, rho^m(a, b) = (1 / pi) int_0^pi rho cos(m phi)
+// dphi on nphi trapezoid nodes (mode 0: the azimuth mean rho_bar), for every pair of a first direction a and a second b.  a: the
+// view cosines vm.s[0 .. V-1], or with V = 0 the grid's upward nodes mu[N+1+i].  b: the columns' mu0 [B], or
+// with mu0 = nullptr the grid's downward nodes |mu_j| with the flux quadrature folded in.  The four layouts of out:
+//   V = 0, mu0 = nullptr   the operator   [m_count][N-1][N-1], element (j, i) = 2 w_j |mu_j| rho^m(mu[N+1+i], |mu_j|)
+//   V = 0, mu0             the beam rows  [m_count][B][N-1] = rho^m(mu[N+1+i], mu0[b])
+//   V > 0, mu0 = nullptr   the view rows  [m_count][N-1][V], element (j, v) = 2 w_j |mu_j| rho^m(mu_view_v, |mu_j|)
+//   V > 0, mu0             the view beam rows [m_count][B][V] = rho^m(mu_view_v, mu0[b])
+// sign_odd (the grid's b only): mode m as (-1)^m of it.  A mode's bits are the same however many modes a call takes and from which
+// it starts, and at a view cosine equal to a node those of the node.
+void launch_brdf_pairs(hipStream_t s, const Grid& g, const ViewMu& vm, int V, int B, BrdfParams bp, int nphi, int m_first,
+                       int m_count, int sign_odd, const double* mu0, double* out);
 // S [B][N-1] = scale (R I[L-1][0 .. N-2] + r0 exp(-tau[L-1] / mu0)); r0, scale nullable
 void launch_ground_source(hipStream_t s, const Grid& g, int B, ColScalars sc, const double* I, const double* tau, const double* R,
                           const double* r0, const double* scale, double* S);
@@ -29,13 +31,7 @@ void launch_ground_source(hipStream_t s, const Grid& g, int B, ColScalars sc, co
 void launch_ground_first_order(hipStream_t s, const Grid& g, int B, const double* tau, const double* S, double* G, int* status);
 // total += Ik; ratio [B]
 void launch_bounce_accumulate(hipStream_t s, const Grid& g, int B, const double* Ik, double* total, double* ratio);
-// The ground's term at view lanes; vm.s[0 .. V-1] are the view cosines.  Rows [m_count][N-1][V] = 2 w_j |mu_j|
-// rho^m(mu_view_v, |mu_j|) ((-1)^m with sign_odd), beam rows [m_count][B][V] = rho^m(mu_view_v, mu0_b): at a node the bits of the
-// two mode builders above.  Beam rows at azimuths [nphi_out][B][V] = rho(mu_view_v, mu0_b, phi_q).
-void launch_brdf_view_rows_modes(hipStream_t s, const Grid& g, const ViewMu& vm, int V, BrdfParams bp, int nphi, int m_first,
-                                 int m_count, int sign_odd, double* R);
-void launch_brdf_view_beam_modes(hipStream_t s, int B, const ViewMu& vm, int V, BrdfParams bp, int nphi, int m_first, int m_count,
-                                 const double* mu0, double* r0);
+// Beam rows at azimuths [nphi_out][B][V] = rho(mu_view_v, mu0_b, phi_q), no quadrature.
 void launch_brdf_view_beam_azimuth(hipStream_t s, int B, const ViewMu& vm, int V, BrdfParams bp, const double* mu0, int nphi_out,
                                    const double* phi, double* out);
 // out [B][nlev_all][2V] (offset to the first level of lv): lanes V + v (+)= S exp(-(tau[L-1] - tau[t]) / mu_view_v), S [B][V] =

@@ -468,19 +468,44 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
     return spec
 
 
+def _reflection_scratch(s: Solver, dev, B, L):
+    """The buffers of `_reflect`: d_S [B, N-1], d_G, d_Ik [B, L, 2N], d_ratio [B] and the int32 d_nk, d_stk, d_gst [B]."""
+    import torch
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    i32 = {k: torch.zeros(B, dtype=torch.int32, device=dev) for k in ("d_nk", "d_stk", "d_gst")}
+    return SimpleNamespace(d_S=f64(B, s.N - 1), d_G=f64(B, L, s.D), d_Ik=f64(B, L, s.D), d_ratio=f64(B), **i32)
+
+
+def _reflect(s: Solver, B, k, d_tau, d_total, R, r0, d_scale, buf, status, hook=None, **solve_kw):
+    """Ground reflection k >= 1, enqueued: the ground source (`R`, `d_scale`) of the downward surface row of `src`, the last term
+    buf.d_Ik (reflection 1: `d_total`, which holds the black solve, with the beam rows `r0`) -> `hook(k, src)`, for what reads the
+    same source -> its unscattered field -> the order loop from it (`solve_kw`: what else `Solver.solve_device` takes) into buf.d_Ik,
+    its orders into buf.d_nk -> d_total += buf.d_Ik, buf.d_ratio.  `status` [B] takes the ground field's, else the solve's, where 0."""
+    import torch
+    src = d_total if k == 1 else buf.d_Ik
+    s.ground_source_device(src.data_ptr(), d_tau.data_ptr(), R.data_ptr(), buf.d_S.data_ptr(), r0.data_ptr() if k == 1 else 0,
+                           d_scale.data_ptr(), B=B)
+    if hook is not None:
+        hook(k, src)
+    s.ground_first_order_device(d_tau.data_ptr(), buf.d_S.data_ptr(), buf.d_G.data_ptr(), buf.d_gst.data_ptr(), B=B)
+    s.solve_device(d_tau.data_ptr(), d_I_out=buf.d_Ik.data_ptr(), d_I1=buf.d_G.data_ptr(), d_n_orders=buf.d_nk.data_ptr(),
+                   d_status=buf.d_stk.data_ptr(), **solve_kw)
+    s.bounce_accumulate_device(buf.d_Ik.data_ptr(), d_total.data_ptr(), buf.d_ratio.data_ptr(), B=B)
+    status.copy_(torch.where(status != 0, status, torch.where(buf.d_gst != 0, buf.d_gst, buf.d_stk)))
+
+
 def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BOUNCES, nphi=BRDF_NPHI, device=0, fetch_field=True,
                want=(), z_profile=None, keep_device=False, view=None):
     """The solve of handle `s` (grid, phase matrices set; columns set over a BLACK ground: the specular surface with albedo 0)
     over the BRDF GROUND `spec` of `_brdf_args`: the plain solve, then on the device the series in ground
-    reflections -- ground source of the last term's downward surface row (and, in the first bounce, of the direct beam) ->
-    its unscattered field -> the order loop fed that field -> sum -- until every column's term is below `tol` of the sum on
-    the TOA-up and surface-down lanes, or `max_bounces`; B ratios come back per bounce, nothing else.  Every column runs every
-    bounce of the batch.  `want`: names of `Solver.epilogue` from the summed field (`epilogue_device`: over the black ground its
-    reflected-beam term is zero; the reflected beam is in the field).  Returns (SolveResult, {"bounces" [B]: the bounce at
-    which the column fell below tol, "bounce_ratio" [B]: its last ratio, "bounce_orders" [K, B]: the orders the solve of every
-    bounce ran}, dict of the wanted epilogue arrays); keep_device=True: the torch tensors {"I", "n", "status", "tau", "bounces",
-    "bounce_ratio", "bounce_orders"} instead.  n is the black solve's; a column still
-    above tol at the cap has status COL_MAXORDERS, one whose ground rows fail the mu -> 0 search COL_INDEXERROR.
+    reflections (`_reflect`, of the last term's downward surface row and, in the first bounce, of the direct beam) until every
+    column's term is below `tol` of the sum on the TOA-up and surface-down lanes, or `max_bounces`; B ratios come back per
+    bounce, nothing else.  Every column runs every bounce of the batch.  `want`: names of `Solver.epilogue` from the summed field
+    (`epilogue_device`: over the black ground its reflected-beam term is zero; the reflected beam is in the field).  Returns
+    (SolveResult, {"bounces" [B]: the bounce at which the column fell below tol, "bounce_ratio" [B]: its last ratio,
+    "bounce_orders" [K, B]: the orders the solve of every bounce ran}, dict of the wanted epilogue arrays); keep_device=True: the
+    torch tensors {"I", "n", "status", "tau", "bounces", "bounce_ratio", "bounce_orders"} instead.  n is the black solve's; a column
+    still above tol at the cap has status COL_MAXORDERS, one whose ground rows fail the mu -> 0 search COL_INDEXERROR.
 
     `view` = (view_mu [V], levels) (a named BRDF only): also THE GROUND'S UNSCATTERED RADIANCE AT THE VIEW LANES,
     summed over the reflections on the same sources the ground source reads -- the beam's single reflection written once, every
@@ -503,10 +528,8 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
             s.brdf_beam_device(spec.kind, d_mu0.data_ptr(), d_r0.data_ptr(), spec.params, nphi, B=B)
         else:
             d_R, d_r0 = up(spec.R.T), up(spec.r0)            # (the device reads the lanes i of one j contiguously)
-        d_S, d_G, d_Ik, d_ratio = f64(B, M), f64(B, L, s.D), f64(B, L, s.D), f64(B)
-        d_nk, d_stk, d_gst = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(3))
-        bounces = np.zeros(B, dtype=np.int32)
-        orders = []
+        buf = _reflection_scratch(s, dev, B, L)
+        bounces, orders, view_hook = np.zeros(B, dtype=np.int32), [], None
         if view is not None:
             vmu, vlev = view
             V = len(vmu)
@@ -515,29 +538,21 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
             s.brdf_view_beam_modes_device(spec.kind, d_mu0.data_ptr(), vmu, d_r0v.data_ptr(), 0, 1, spec.params, nphi, B=B)
             d_vb, d_vd = f64(B, len(vlev), 2 * V), f64(B, len(vlev), 2 * V)
             s.view_ground_device(vmu, d_tau.data_ptr(), vlev, d_vb.data_ptr(), d_r0v=d_r0v.data_ptr(), d_scale=d_scale.data_ptr(), B=B)
-        src = d_I                                            # bounce 1 reflects the black solve's surface row
-        for k in range(1, max_bounces + 1):
-            s.ground_source_device(src.data_ptr(), d_tau.data_ptr(), d_R.data_ptr(), d_S.data_ptr(),
-                                   d_r0.data_ptr() if k == 1 else 0, d_scale.data_ptr(), B=B)
-            if view is not None:
+            def view_hook(k, src):                          # reflection k's diffuse part, from the source the ground source has just read
                 s.view_ground_device(vmu, d_tau.data_ptr(), vlev, d_vd.data_ptr(), d_I=src.data_ptr(), d_Rv=d_Rv.data_ptr(),
                                      d_scale=d_scale.data_ptr(), accumulate=k > 1, B=B)
-            s.ground_first_order_device(d_tau.data_ptr(), d_S.data_ptr(), d_G.data_ptr(), d_gst.data_ptr(), B=B)
-            s.solve_device(d_tau.data_ptr(), p0a, p0r, d_Ik.data_ptr(), tol=tol, d_I1=d_G.data_ptr(), d_n_orders=d_nk.data_ptr(),
-                           d_status=d_stk.data_ptr())
-            s.bounce_accumulate_device(d_Ik.data_ptr(), d_I.data_ptr(), d_ratio.data_ptr(), B=B)
-            d_st.copy_(torch.where(d_st != 0, d_st, torch.where(d_gst != 0, d_gst, d_stk)))
-            src = d_Ik
-            orders.append(d_nk.clone())
+        for k in range(1, max_bounces + 1):
+            _reflect(s, B, k, d_tau, d_I, d_R, d_r0, d_scale, buf, d_st, view_hook, d_P0_atm=p0a, d_P0_aer=p0r, tol=tol)
+            orders.append(buf.d_nk.clone())
             s.synchronize()
-            ratio = d_ratio.cpu().numpy()
+            ratio = buf.d_ratio.cpu().numpy()
             bounces[(bounces == 0) & (ratio < tol)] = k
             if np.all(ratio < tol):
                 break
         late = torch.from_numpy(bounces == 0).to(dev) & (d_st == 0)
         d_st.copy_(torch.where(late, torch.full_like(d_st, _lib.COL_MAXORDERS), d_st))
         bounces[bounces == 0] = k
-        out = {"bounces": torch.from_numpy(bounces).to(dev), "bounce_ratio": d_ratio, "bounce_orders": torch.stack(orders)}
+        out = {"bounces": torch.from_numpy(bounces).to(dev), "bounce_ratio": buf.d_ratio, "bounce_orders": torch.stack(orders)}
         if view is not None:
             out.update(I_view_ground_beam=d_vb, I_view_ground_diffuse=d_vd, I_view_ground=d_vb + d_vd)
         return out
@@ -1120,37 +1135,23 @@ def _reflection_buffers(s: Solver, c: _ModeLoop, ground, bounce_orders, brdf_nph
     the modes 1..c.M of the named BRDF `ground` on `brdf_nphi` nodes, its scale, the reflections' order counts and the buffers."""
     import torch
     o, M1 = c.own, s.N - 1
-    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=c.dev)
     o.d_scale = torch.from_numpy(np.array(ground.scale, dtype=np.float64)).to(c.dev)
     o.d_orders = torch.from_numpy(np.ascontiguousarray(bounce_orders, dtype=np.int32)).to(c.dev)
-    o.d_R, o.d_r0 = f64(c.M, M1, M1), f64(c.M, c.B, M1)
+    o.d_R, o.d_r0 = (torch.empty(shape, dtype=torch.float64, device=c.dev) for shape in ((c.M, M1, M1), (c.M, c.B, M1)))
     s.brdf_operator_modes_device(ground.kind, o.d_R.data_ptr(), 1, c.M, ground.params, brdf_nphi, sign_odd=True)
     s.brdf_beam_modes_device(ground.kind, c.d_mu0.data_ptr(), o.d_r0.data_ptr(), 1, c.M, ground.params, brdf_nphi, B=c.B)
-    o.d_S, o.d_G, o.d_Ik, o.d_ratio = f64(c.B, M1), f64(c.B, c.L, c.D), f64(c.B, c.L, c.D), f64(c.B)
-    o.d_nk, o.d_stk, o.d_gst = (torch.zeros(c.B, dtype=torch.int32, device=c.dev) for _ in range(3))
+    o.buf = _reflection_scratch(s, c.dev, c.B, c.L)
 
 
 def _mode_reflections(s: Solver, c: _ModeLoop, m, hook=None):
     """The reflections 1..K of mode m >= 1 on the resident field c.d_Im, which holds the mode's black solve and leaves as the sum
-    (DESIGN section 21): ground source, its unscattered field, a solve of bounce_orders[k - 1] orders started from it, sum; the
-    statuses join c.d_status[m - 1] and the targets go back to mode 0's.  `hook(k, src)` runs after the ground source of
-    reflection k, `src` being the field whose surface row it reflected (the view stage's ground term reads the same)."""
-    import torch
+    (DESIGN section 21): `_reflect` with a solve of bounce_orders[k - 1] orders; the statuses join c.d_status[m - 1] and the targets
+    go back to mode 0's.  `hook(k, src)` runs after the ground source of reflection k, `src` being the field it reflected."""
     o = c.own
-    st = c.d_status[m - 1]
-    src = c.d_Im                                             # reflection 1 reflects the mode's black solve
     for k in range(1, o.d_orders.shape[0] + 1):
-        s.ground_source_device(src.data_ptr(), c.d_tau.data_ptr(), o.d_R[m - 1].data_ptr(), o.d_S.data_ptr(),
-                               o.d_r0[m - 1].data_ptr() if k == 1 else 0, o.d_scale.data_ptr(), B=c.B)
-        if hook is not None:
-            hook(k, src)
-        s.ground_first_order_device(c.d_tau.data_ptr(), o.d_S.data_ptr(), o.d_G.data_ptr(), o.d_gst.data_ptr(), B=c.B)
         s.set_order_targets(o.d_orders[k - 1].data_ptr())
-        s.solve_device(c.d_tau.data_ptr(), 0, 0, o.d_Ik.data_ptr(), d_I1=o.d_G.data_ptr(), d_n_orders=o.d_nk.data_ptr(),
-                       d_status=o.d_stk.data_ptr())
-        s.bounce_accumulate_device(o.d_Ik.data_ptr(), c.d_Im.data_ptr(), o.d_ratio.data_ptr(), B=c.B)
-        st.copy_(torch.where(st != 0, st, torch.where(o.d_gst != 0, o.d_gst, o.d_stk)))
-        src = o.d_Ik
+        _reflect(s, c.B, k, c.d_tau, c.d_Im, o.d_R[m - 1], o.d_r0[m - 1], o.d_scale, o.buf, c.d_status[m - 1], hook,
+                 d_P0_atm=0, d_P0_aer=0)
     s.set_order_targets(c.d_target.data_ptr())
 
 
@@ -1165,9 +1166,8 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
     `ground` (the namespace of `_brdf_args`, `r` then being the result of `solve_brdf` over it) with `bounce_orders` [K, B] of
     that solve: the BRDF GROUND'S MODES.  The operators (-1)^m R^m and beam rows r0^m of the modes 1..M are
     built once, on the `brdf_nphi` nodes of mode 0's; per mode, between its black solve and its synthesis, the reflections 1..K
-    run on the resident field -- ground source, its unscattered field, a solve of bounce_orders[k - 1] orders started from it,
-    sum -- and the targets go back to mode 0's.  Their statuses join the mode's.  A Lambertian ground has no mode m >= 1: no
-    reflections are run for it."""
+    run on the resident field (`_mode_reflections`), each a solve of bounce_orders[k - 1] orders, and their statuses join the
+    mode's.  A Lambertian ground has no mode m >= 1: no reflections are run for it."""
     import torch
     nlev = len(levels)
     bounce = ground is not None and ground.kind != "lambertian"

@@ -467,39 +467,42 @@ class Solver:
     # ---- BRDF ground (sosrt.h) --------------------------------------------------------
     _BRDF_KINDS = {"lambertian": _lib.BRDF_LAMBERTIAN, "rpv": _lib.BRDF_RPV}
 
-    def _brdf_kind(self, kind, params):
+    def _brdf_pack(self, kind, params):
+        """(kind, params, nparams) as the C entry points take a named BRDF"""
         k = self._BRDF_KINDS.get(kind)
         if k is None:
             raise ValueError("BRDF kind must be 'lambertian' or 'rpv' (got %r)" % (kind,))
         p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64))) if np.size(params) else np.zeros(0)
-        return k, p
+        return k, _ptr(p) if p.size else None, int(p.size)
+
+    @staticmethod
+    def _view_pack(mu_view):
+        """(V, mu_view) as the C entry points take view cosines"""
+        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
+        return int(m.size), _ptr(m)
 
     def brdf_operator_device(self, kind, d_R_out: int, params=(), nphi=65):
         """The reflection operator of a named BRDF ('lambertian', or 'rpv' with params (rho0, k, Theta)), its azimuth mean on
         `nphi` trapezoid nodes and the flux quadrature folded in: d_R_out [N-1, N-1] with element (j, i) = 2 w_j |mu_j|
         rho_bar(mu[N+1+i], |mu_j|), the upward lanes i of one downward lane j contiguous.  Enqueued on the handle's stream."""
-        k, p = self._brdf_kind(kind, params)
-        check(lib().sosrt_brdf_operator_dev(self._h, k, _ptr(p) if p.size else None, int(p.size), int(nphi), _vp(d_R_out)))
+        check(lib().sosrt_brdf_operator_dev(self._h, *self._brdf_pack(kind, params), int(nphi), _vp(d_R_out)))
 
     def brdf_beam_device(self, kind, d_mu0: int, d_r0_out: int, params=(), nphi=65, B: Optional[int] = None):
         """The reflection of the direct beam: d_r0_out [B, N-1] = rho_bar(mu[N+1+i], d_mu0[b])."""
-        k, p = self._brdf_kind(kind, params)
-        check(lib().sosrt_brdf_beam_dev(self._h, int(self.B if B is None else B), k, _ptr(p) if p.size else None, int(p.size),
-                                        int(nphi), _vp(d_mu0), _vp(d_r0_out)))
+        check(lib().sosrt_brdf_beam_dev(self._h, int(self.B if B is None else B), *self._brdf_pack(kind, params), int(nphi),
+                                        _vp(d_mu0), _vp(d_r0_out)))
 
     def brdf_operator_modes_device(self, kind, d_R_out: int, m_first, m_count, params=(), nphi=65, sign_odd=False):
         """The Fourier modes m_first .. m_first + m_count - 1 in azimuth of `brdf_operator_device`: d_R_out
         [m_count, N-1, N-1] with rho^m = (1 / pi) int rho cos(m phi) dphi in place of the azimuth mean; sign_odd: mode m as
         (-1)^m R^m, what `ground_source_device` takes for mode m.  Mode 0 has the bits of `brdf_operator_device`."""
-        k, p = self._brdf_kind(kind, params)
-        check(lib().sosrt_brdf_operator_modes_dev(self._h, k, _ptr(p) if p.size else None, int(p.size), int(nphi), int(m_first),
-                                                  int(m_count), int(bool(sign_odd)), _vp(d_R_out)))
+        check(lib().sosrt_brdf_operator_modes_dev(self._h, *self._brdf_pack(kind, params), int(nphi), int(m_first), int(m_count),
+                                                  int(bool(sign_odd)), _vp(d_R_out)))
 
     def brdf_beam_modes_device(self, kind, d_mu0: int, d_r0_out: int, m_first, m_count, params=(), nphi=65, B: Optional[int] = None):
         """The same modes of `brdf_beam_device`: d_r0_out [m_count, B, N-1] = rho^m(mu[N+1+i], d_mu0[b]) (no sign)."""
-        k, p = self._brdf_kind(kind, params)
-        check(lib().sosrt_brdf_beam_modes_dev(self._h, int(self.B if B is None else B), k, _ptr(p) if p.size else None, int(p.size),
-                                              int(nphi), int(m_first), int(m_count), _vp(d_mu0), _vp(d_r0_out)))
+        check(lib().sosrt_brdf_beam_modes_dev(self._h, int(self.B if B is None else B), *self._brdf_pack(kind, params), int(nphi),
+                                              int(m_first), int(m_count), _vp(d_mu0), _vp(d_r0_out)))
 
     def ground_source_device(self, d_I: int, d_tau: int, d_R: int, d_S_out: int, d_r0: int = 0, d_scale: int = 0,
                              B: Optional[int] = None):
@@ -525,37 +528,29 @@ class Solver:
         """Rows of `brdf_operator_modes_device` at the view cosines `mu_view` [V] (host) in place of the upward nodes: d_out
         [m_count, N-1, V] with element (j, v) = 2 w_j |mu_j| rho^m(mu_view[v], |mu_j|) ((-1)^m with sign_odd).  At a node the
         bits of that builder's column."""
-        k, p = self._brdf_kind(kind, params)
-        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
-        check(lib().sosrt_brdf_view_rows_modes_dev(self._h, k, _ptr(p) if p.size else None, int(p.size), int(nphi), int(m_first),
-                                                   int(m_count), int(bool(sign_odd)), int(m.size), _ptr(m), _vp(d_out)))
+        check(lib().sosrt_brdf_view_rows_modes_dev(self._h, *self._brdf_pack(kind, params), int(nphi), int(m_first), int(m_count),
+                                                   int(bool(sign_odd)), *self._view_pack(mu_view), _vp(d_out)))
 
     def brdf_view_beam_modes_device(self, kind, d_mu0: int, mu_view, d_out: int, m_first, m_count, params=(), nphi=65,
                                     B: Optional[int] = None):
         """The same of `brdf_beam_modes_device`: d_out [m_count, B, V] = rho^m(mu_view[v], d_mu0[b])."""
-        k, p = self._brdf_kind(kind, params)
-        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
-        check(lib().sosrt_brdf_view_beam_modes_dev(self._h, int(self.B if B is None else B), k, _ptr(p) if p.size else None,
-                                                   int(p.size), int(nphi), int(m_first), int(m_count), _vp(d_mu0), int(m.size),
-                                                   _ptr(m), _vp(d_out)))
+        check(lib().sosrt_brdf_view_beam_modes_dev(self._h, int(self.B if B is None else B), *self._brdf_pack(kind, params),
+                                                   int(nphi), int(m_first), int(m_count), _vp(d_mu0), *self._view_pack(mu_view),
+                                                   _vp(d_out)))
 
     def brdf_view_beam_azimuth_device(self, kind, d_mu0: int, mu_view, d_phi: int, nphi_out: int, d_out: int, params=(),
                                       B: Optional[int] = None):
         """rho(mu_view[v], d_mu0[b], d_phi[q]) at the azimuth itself (phi = 0: the hot spot), no quadrature: d_out [nphi_out, B, V]."""
-        k, p = self._brdf_kind(kind, params)
-        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
-        check(lib().sosrt_brdf_view_beam_azimuth_dev(self._h, int(self.B if B is None else B), k, _ptr(p) if p.size else None,
-                                                     int(p.size), _vp(d_mu0), int(m.size), _ptr(m), int(nphi_out), _vp(d_phi),
-                                                     _vp(d_out)))
+        check(lib().sosrt_brdf_view_beam_azimuth_dev(self._h, int(self.B if B is None else B), *self._brdf_pack(kind, params),
+                                                     _vp(d_mu0), *self._view_pack(mu_view), int(nphi_out), _vp(d_phi), _vp(d_out)))
 
     def view_ground_device(self, mu_view, d_tau: int, levels, d_out: int, d_I: int = 0, d_Rv: int = 0, d_r0v: int = 0,
                            d_scale: int = 0, accumulate=False, d_S_out: int = 0, B: Optional[int] = None):
         """The ground's unscattered radiance at the view lanes: d_out [B, nlev, 2V], upward lanes (+)= S[b, v] exp(-(tau[b, L-1] -
         tau[b, t]) / mu_view[v]) with S = scale[b] (Rv I[b, L-1, 0 .. N-2] + r0v[b] exp(-tau[b, L-1] / mu0[b])) (d_S_out [B, V],
         optional); downward lanes +0 unless accumulating.  d_I, d_Rv 0: the beam-only call; d_r0v 0: the diffuse-only one."""
-        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
         lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.int32)
-        check(lib().sosrt_view_ground_dev(self._h, int(self.B if B is None else B), int(m.size), _ptr(m), _vp(d_tau), _vp(d_I),
+        check(lib().sosrt_view_ground_dev(self._h, int(self.B if B is None else B), *self._view_pack(mu_view), _vp(d_tau), _vp(d_I),
                                           _vp(d_Rv), _vp(d_r0v), _vp(d_scale), int(lev.size), _ptr(lev), int(bool(accumulate)),
                                           _vp(d_S_out), _vp(d_out)))
 

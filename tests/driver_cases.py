@@ -27,6 +27,11 @@ PLANCK = np.linspace(0.4, 1.0, L)[None, :] * (1 + 0.1 * np.arange(3))[:, None]
 THERMAL = dict(source="thermal", planck=PLANCK, planck_surface=np.array([1.0, 1.1, 0.9]))
 TWO_AEROSOLS = dict(atm_phase_fun="rayleigh", aer_phase_fun=["hg", "rayleigh"], g_aer=[0.7, 0.0])
 VIEW_MU = np.array([0.3, 0.9])
+# BRDF ground.  Lambertian: T_AER halved once more (at T_AER column 1 ends with status 1).  RPV: no aerosol depth helps column 0,
+# whose low sun (mu0 = 0.3) leaves the ground's unscattered rows so steep towards mu -> 0 that their search runs off the grid at
+# tauStar_atm = 0.124 and below, however thin the aerosol; under tauStar_atm = 0.25 the beam at the ground is weak enough, and T_AER stays
+RPV = ("rpv", 0.2, 0.8, -0.1)
+RPV_T_ATM = 0.25
 # two aerosol layers (rows 12..15 and 18..20 of the 24), each with its own aerosol
 SLABS = [(58, 42, 0.05, 0.9, dict(name="hg", g=0.7)), (25, 17, 0.1, 0.8, "rayleigh")]
 
@@ -39,9 +44,9 @@ def fresh():
     M._solvers.clear()
 
 
-def _batch(names, t_aer=T_AER, **kw):
+def _batch(names, t_aer=T_AER, rho=RHO, **kw):
     from sosrt.main import SOS_Aer_batch
-    r = SOS_Aer_batch(MU0, GREY_T_AER if kw.get("source") == "thermal" else t_aer, RHO, raise_on_error=False, **SHAPE,
+    r = SOS_Aer_batch(MU0, GREY_T_AER if kw.get("source") == "thermal" else t_aer, rho, raise_on_error=False, **SHAPE,
                       **dict(PHASE, **kw))
     st = [r.status] + [getattr(r, k) for k in ("mode_status", "view_mode_status") if getattr(r, k) is not None]
     return {k: getattr(r, k) for k in names}, st
@@ -105,12 +110,72 @@ def _spectrum(one_batch):
     return out, [r.status for r in res]
 
 
+def _brdf_stages():
+    """The stages of the BRDF ground through the `Solver` methods, on a handle with the grid and three black columns: the six
+    builders of RPV on nphi = 300 nodes (two chunks of the kernels' 256) for the modes 0..9 (two launches of 8, the second ragged),
+    with and without the odd sign, at the grid's nodes and at V = 3 view cosines of which one is a node, for B = 3 columns; the
+    rows at azimuths; the ground source and the view ground with and without their optional terms."""
+    import torch
+    from sosrt import inputs
+    from sosrt.solver import Solver
+    dev = torch.device("cuda", 0)
+    B, M1, nm, nphi, p = 3, N - 1, 10, 300, RPV[1:]
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    f64 = lambda *shape: torch.full(shape, np.nan, dtype=torch.float64, device=dev)
+    mu = inputs.direction_grid(N)
+    mv = np.array([0.3, mu[N + 1 + 5], 0.9])
+    V = len(mv)
+    rng = np.random.default_rng(2432)
+    d_I = up(0.05 + rng.random((B, L, 2 * N)) * (1 + np.arange(2 * N) / N))
+    d_tau = up(np.linspace(0, 1, L)[None, :] * np.array([0.2, 0.3, 0.4])[:, None])
+    d_mu0, d_scale, d_phi = up(MU0), up([0.5, 1.0, 2.0]), up([0.0, 1.0, 2.0])
+    s = Solver(L, N, max_batch=B)
+    try:
+        s.set_grid(mu)
+        iu, idn = inputs.slab_indices(120, 25, 17, L)
+        s.set_columns(np.full(B, iu), np.full(B, idn), MU0, 0.0, 1.0, 0.95, 0.124 / L, 0.3 / (idn + 1 - iu), 0.424)
+        torch.cuda.synchronize()
+        o = dict(operator=f64(M1, M1), beam=f64(B, M1), beam_modes=f64(nm, B, M1), view_beam_modes=f64(nm, B, V),
+                 view_beam_azimuth=f64(3, B, V))
+        s.brdf_operator_device("rpv", o["operator"].data_ptr(), p, nphi)
+        s.brdf_beam_device("rpv", d_mu0.data_ptr(), o["beam"].data_ptr(), p, nphi, B=B)
+        s.brdf_beam_modes_device("rpv", d_mu0.data_ptr(), o["beam_modes"].data_ptr(), 0, nm, p, nphi, B=B)
+        s.brdf_view_beam_modes_device("rpv", d_mu0.data_ptr(), mv, o["view_beam_modes"].data_ptr(), 0, nm, p, nphi, B=B)
+        s.brdf_view_beam_azimuth_device("rpv", d_mu0.data_ptr(), mv, d_phi.data_ptr(), 3, o["view_beam_azimuth"].data_ptr(), p, B=B)
+        for sign in (False, True):
+            R, Rv = f64(nm, M1, M1), f64(nm, M1, V)
+            s.brdf_operator_modes_device("rpv", R.data_ptr(), 0, nm, p, nphi, sign_odd=sign)
+            s.brdf_view_rows_modes_device("rpv", mv, Rv.data_ptr(), 0, nm, p, nphi, sign_odd=sign)
+            o["operator_modes_sign%d" % sign], o["view_rows_modes_sign%d" % sign] = R, Rv
+        for name, opt in (("plain", False), ("beam_scale", True)):
+            o["ground_source_" + name] = S = f64(B, M1)
+            s.ground_source_device(d_I.data_ptr(), d_tau.data_ptr(), o["operator"].data_ptr(), S.data_ptr(),
+                                   o["beam"].data_ptr() if opt else 0, d_scale.data_ptr() if opt else 0, B=B)
+        Rv0, r0v = o["view_rows_modes_sign0"][0], o["view_beam_modes"][0]
+        lev, vg, o["view_ground_S"] = [0, L - 1], f64(B, 2, 2 * V), f64(B, V)
+        s.view_ground_device(mv, d_tau.data_ptr(), lev, vg.data_ptr(), d_I=d_I.data_ptr(), d_Rv=Rv0.data_ptr(), d_r0v=r0v.data_ptr(),
+                             d_scale=d_scale.data_ptr(), d_S_out=o["view_ground_S"].data_ptr(), B=B)
+        s.synchronize()
+        o["view_ground_written"] = vg.clone()
+        s.view_ground_device(mv, d_tau.data_ptr(), lev, vg.data_ptr(), d_I=d_I.data_ptr(), d_Rv=Rv0.data_ptr(), accumulate=True, B=B)
+        o["view_ground_accumulated"] = vg
+        s.synchronize()
+        return {k: v.cpu().numpy() for k, v in o.items()}, []
+    finally:
+        s.close()
+
+
 SOLVE = ("I", "n", "status", "I_saved")
 AZIMUTH = dict(azimuths=[0, 1.0, 3.0], n_modes=3)
 VIEW_AZIMUTH = dict(view_mu=VIEW_MU, view_azimuths=[0, 2.0], n_modes=3)
 VIEW_AZIMUTH_OUT = ("I_view_azimuth", "I_view_azimuth_first", "I_view_azimuth_scattered", "view_mode_status")
 THERMAL_VIEW = dict(THERMAL, **GREY, save_orders=True, view_mu=VIEW_MU)
 THERMAL_VIEW_OUT = ("I", "I_saved", "I_view_first", "I_view_scattered")
+# the BRDF ground: every field the result carries for the mode
+BRDF_OUT = ("I", "n", "status", "bounces", "bounce_ratio", "bounce_orders")
+BRDF_VIEW_OUT = BRDF_OUT + ("I_view", "I_view_first", "I_view_scattered", "I_view_ground")
+BRDF_VIEW_AZIMUTH_OUT = BRDF_VIEW_OUT + VIEW_AZIMUTH_OUT + ("I_view_azimuth_ground",)
+_rpv = lambda names, **kw: _batch(names, T_AER, 1.0, surface="brdf", brdf=RPV, tauStar_atm=RPV_T_ATM, **kw)
 
 CASES = {
     "batch_plain": lambda: _batch(SOLVE, save_orders=True),
@@ -139,6 +204,13 @@ CASES = {
     "band_solar": _band_solar,
     "spectrum_loop": lambda: _spectrum(False),
     "spectrum_one_batch": lambda: _spectrum(True),
+    "brdf_lambertian": lambda: _batch(BRDF_OUT, T_AER / 2, surface="brdf", brdf="lambertian"),
+    "brdf_rpv": lambda: _rpv(BRDF_OUT),
+    "brdf_rpv_azimuth": lambda: _rpv(BRDF_OUT + ("I_azimuth", "mode_status"), brdf_modes=True, **AZIMUTH),
+    "brdf_rpv_view": lambda: _rpv(BRDF_VIEW_OUT, view_mu=VIEW_MU, brdf_view=True),
+    "brdf_rpv_view_azimuth_exact": lambda: _rpv(BRDF_VIEW_AZIMUTH_OUT, view_first_order="exact", brdf_view=True, **VIEW_AZIMUTH),
+    "brdf_rpv_view_azimuth_modes": lambda: _rpv(BRDF_VIEW_AZIMUTH_OUT, view_first_order="modes", brdf_view=True, **VIEW_AZIMUTH),
+    "brdf_stages": _brdf_stages,
 }
 
 

@@ -6,7 +6,9 @@ in-tree library (the drivers are host code; the library is the same on both side
     SOSRT_LIB=$PWD/sos-radiative-transfer_amd/libsosrt.so python3 tools/record_driver_bits.py \\
         <dir>/sos-radiative-transfer_amd <commit hash> [out.json]
 
-on an MI355X (default out: tests/golden/driver_bits.json).  SHA-256 digests of every output of the cases of tests/driver_cases.py.
+on an MI355X (default out: tests/golden/driver_bits.json).  Where the commit under test changes the library too (the cases that
+call the `Solver` stages directly check it, not a driver), take a full export of the earlier commit built with its own build(), its
+package as <dir> and its library as SOSRT_LIB: the digests of the cases recorded before must come out unchanged.  SHA-256 digests of every output of the cases of tests/driver_cases.py.
 The tool refuses to write when the package it imported is the in-tree one, or when a column of any case has a non-zero status
 (it names the cases: shrink their optical depth until the earlier commit converges)."""
 import json
