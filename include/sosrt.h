@@ -799,6 +799,7 @@ int sosrt_plan_fix_count(double tau_ref, int N);  /* I1_In:124-127 */
 #define SOSRT_PLAN_GEMM_LIVE32_DEEP  3   /* ... both operands staged two chunks ahead (at most 32 live columns)                */
 #define SOSRT_PLAN_GEMM_LIVE16_REGS  4   /* ... 16 rows, a lane's matrix fragments in registers, no barrier in the k-loop (the   */
                                          /*     last few live columns of the symmetric form: a tile's latency is the launch's)    */
+/* (the library's own name for these is TransportKernel, csrc/kernels.hpp; 2 is its repair pass, reported in out[5], never here) */
 #define SOSRT_PLAN_TRANSPORT_GENERAL 0   /* kernels.hip k_transport                                                             */
 #define SOSRT_PLAN_TRANSPORT_FAST    1   /* transport_fast.hip (odd N, N > 256)                                                 */
 #define SOSRT_PLAN_TRANSPORT_RING    3   /* transport_ring.hip                                                                  */
@@ -830,7 +831,8 @@ int sosrt_profile_reset(sosrt_t* h);
 int sosrt_profile_get(sosrt_t* h, int kernel, double* total_ms, long long* launches, double* work /*flops or bytes*/);
 
 /* ---- diagnostics: device buffer [B][2][8] of clock64() stamps written by the fast transport kernel
- * (start, prologue done, downward done, surface done, upward done, end); NULL switches it off */
+ * (start, prologue done, downward done, surface done, upward done, end); NULL switches it off.  The buffer belongs to this
+ * handle: only its transport launches write it, and it is forgotten with the handle. */
 int sosrt_debug_stamps(sosrt_t* h, unsigned long long* d_stamps);
 
 /* ---- machine peaks measured on this device (roofline denominators) --------------------------- */

@@ -62,7 +62,7 @@ int sosrt_create(int device, int L, int N, int max_batch, int max_orders, sosrt_
     if (const char* ev = getenv("SOSRT_CONTRACT"))            // "full": the D x D product whatever the symmetry of the matrices
         if (strcmp(ev, "full") == 0) h->gemm.mode = SOSRT_CONTRACT_F64_FULL;
     if (const char* ev = getenv("SOSRT_TRANSPORT"))
-        h->tr.mode = strcmp(ev, "general") == 0 ? 0 : (strcmp(ev, "ring") == 0 ? 2 : (strcmp(ev, "scan") == 0 ? 4 : (strcmp(ev, "auto") == 0 ? 3 : 1)));
+        h->tr.mode = strcmp(ev, "general") == 0 ? TransportKnob::General : (strcmp(ev, "ring") == 0 ? TransportKnob::Ring : (strcmp(ev, "scan") == 0 ? TransportKnob::Scan : (strcmp(ev, "auto") == 0 ? TransportKnob::Auto : TransportKnob::Fast)));
     if (const char* ev = getenv("SOSRT_SCAN_COLS")) h->tr.scan_cols = atoi(ev);
     if (const char* ev = getenv("SOSRT_RING_MOMENTS")) h->tr.ring_moments = atoi(ev) != 0;
     if (const char* ev = getenv("SOSRT_SCAN_SPLIT")) h->tr.scan_split = atoi(ev);
@@ -83,9 +83,9 @@ int sosrt_create(int device, int L, int N, int max_batch, int max_orders, sosrt_
 #endif
     if (const char* ev = getenv("SOSRT_GROUP_RING_SLOTS")) h->grp.coresident_slots = atoi(ev);
     if (const char* ev = getenv("SOSRT_ORDER_LOOP")) h->ol.mode = atoi(ev) != 0;           // (A/B: 0 = every order as two launches)
-    if (const char* ev = getenv("SOSRT_RING_SLOTS")) g_ring_slots = atoi(ev);
+    if (const char* ev = getenv("SOSRT_RING_SLOTS")) h->tr.ring_slots = atoi(ev);
 #ifdef SOSRT_RING_DEBUG   // diagnostic builds only: the switches make the ring kernel skip work, its results are wrong
-    if (const char* ev = getenv("SOSRT_RING_DEBUG")) g_ring_debug = atoi(ev);
+    if (const char* ev = getenv("SOSRT_RING_DEBUG")) h->tr.ring_debug = atoi(ev);
 #endif
     Grid& g = h->g;
     g.L = L; g.N = N; g.D = 2 * N;
@@ -596,11 +596,12 @@ int sosrt_plan_fix_table(sosrt_t* h, int idx, int* s0, int* ns, double* C_out) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// diagnostics: cycle stamps of k_transport_fast ([B][2 waves][8] clock64 values; pass NULL to stop)
+// diagnostics: cycle stamps of k_transport_fast ([B][2 waves][8] clock64 values; pass NULL to stop), written by the transport
+// launches of this handle alone
 // ---------------------------------------------------------------------------------------------
 int sosrt_debug_stamps(sosrt_t* h, unsigned long long* d_stamps) {
     if (int e = need_gpu(h)) return e;
-    sosrt::g_transport_stamps = d_stamps;
+    h->tr.d_stamps = d_stamps;
     return 0;
 }
 

@@ -263,7 +263,7 @@ int sosrt_mie_timing(sosrt_t* h, double* ms) {
 
 }  // extern "C"
 
-static int phase_check(sosrt_handle* h, int kind, double g) {
+int sosrt::phase_check(sosrt_handle* h, int kind, double g) {
     if (int e = need_gpu(h)) return e;
     if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
     if (kind < SOSRT_PHASE_ISO || kind > SOSRT_PHASE_TABLE) return fail(SOSRT_E_INVALID, "unknown phase-function kind %d", kind);
@@ -272,13 +272,20 @@ static int phase_check(sosrt_handle* h, int kind, double g) {
     return 0;
 }
 
+PhaseFn sosrt::phase_fn(const sosrt_handle* h, int kind, double g) {
+    PhaseFn p{};
+    p.kind = kind; p.g = g;
+    p.tab_mu = h->pf.d_tab; p.tab_p = h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr; p.ntab = h->pf.ntab;
+    return p;
+}
+
 extern "C" {
 
 int sosrt_phase_p0_dev(sosrt_t* h, int B, int kind, double g, const double* d_mu0, double* d_P0_out) {
     if (int e = phase_check(h, kind, g)) return e;
     if (B < 1 || !d_mu0 || !d_P0_out) return fail(SOSRT_E_INVALID, "bad argument");
     HIPCHK(hipSetDevice(h->device));
-    launch_phase_p0(h->stream, h->g, h->grid.d_w, B, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr, h->pf.ntab, h->grid.d_phi,
+    launch_phase_p0(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g), h->grid.d_phi,
                     h->grid.d_phi + kNPhi, kNPhi, d_mu0, d_P0_out);
     HIPCHK(hipGetLastError());
     return 0;
@@ -302,7 +309,7 @@ int sosrt_phase_matrix_dev(sosrt_t* h, int kind, double g, double* d_P_out) {
     if (int e = phase_check(h, kind, g)) return e;
     if (!d_P_out) return fail(SOSRT_E_INVALID, "null argument");
     HIPCHK(hipSetDevice(h->device));
-    launch_phase_matrix(h->stream, h->g, h->grid.d_w, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr, h->pf.ntab, h->grid.d_phi,
+    launch_phase_matrix(h->stream, h->g, h->grid.d_w, phase_fn(h, kind, g), h->grid.d_phi,
                         h->grid.d_phi + kNPhi, kNPhi, d_P_out);
     HIPCHK(hipGetLastError());
     return 0;
@@ -318,7 +325,7 @@ int sosrt_phase_matrix(sosrt_t* h, int kind, double g, double* P_out) {
     if (int e = dalloc(&dP, n)) return e;
     int rc = 0;
     auto body = [&]() -> int {
-        launch_phase_matrix(s, h->g, h->grid.d_w, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr, h->pf.ntab, h->grid.d_phi,
+        launch_phase_matrix(s, h->g, h->grid.d_w, phase_fn(h, kind, g), h->grid.d_phi,
                             h->grid.d_phi + kNPhi, kNPhi, dP);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(P_out, dP, n * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -381,10 +388,10 @@ int sosrt_phase_modes(sosrt_t* h, int kind, double g, int m_first, int m_count, 
     if (int e = dalloc(&dP, m_count * DD)) return e;
     auto body = [&]() -> int {
         if (m_first == 0)                                  // mode 0 is the existing builder's output, bit for bit (25-point ring)
-            launch_phase_matrix(s, h->g, h->grid.d_w, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr, h->pf.ntab, h->grid.d_phi,
+            launch_phase_matrix(s, h->g, h->grid.d_w, phase_fn(h, kind, g), h->grid.d_phi,
                                 h->grid.d_phi + kNPhi, kNPhi, dP);
         if (mc > 0)
-            launch_phase_modes(s, h->g, h->grid.d_w, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr, h->pf.ntab, h->pf.d_modetab.p,
+            launch_phase_modes(s, h->g, h->grid.d_w, phase_fn(h, kind, g), h->pf.d_modetab.p,
                                h->pf.d_modetab.p + nphi, nphi, mf, mc, dP + (m_count - mc) * DD);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(P_out, dP, m_count * DD * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -406,10 +413,10 @@ int sosrt_phase_modes_dev(sosrt_t* h, int kind, double g, int m_first, int m_cou
     if (mc > 0)
         if (int e = modes_table(h, nphi, mf, mc)) return e;
     if (m_first == 0)
-        launch_phase_matrix(s, h->g, h->grid.d_w, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr, h->pf.ntab, h->grid.d_phi,
+        launch_phase_matrix(s, h->g, h->grid.d_w, phase_fn(h, kind, g), h->grid.d_phi,
                             h->grid.d_phi + kNPhi, kNPhi, d_P_out);
     if (mc > 0)
-        launch_phase_modes(s, h->g, h->grid.d_w, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr, h->pf.ntab, h->pf.d_modetab.p,
+        launch_phase_modes(s, h->g, h->grid.d_w, phase_fn(h, kind, g), h->pf.d_modetab.p,
                            h->pf.d_modetab.p + nphi, nphi, mf, mc, d_P_out + (m_count - mc) * DD);
     if (sign_odd) launch_negate_odd_modes(s, DD, m_first, m_count, d_P_out);
     HIPCHK(hipGetLastError());
@@ -425,10 +432,10 @@ int sosrt_phase_p0_modes_dev(sosrt_t* h, int B, int kind, double g, int m_first,
     if (mc > 0)
         if (int e = modes_table(h, nphi, mf, mc)) return e;
     if (m_first == 0)
-        launch_phase_p0(h->stream, h->g, h->grid.d_w, B, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr, h->pf.ntab, h->grid.d_phi,
+        launch_phase_p0(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g), h->grid.d_phi,
                         h->grid.d_phi + kNPhi, kNPhi, d_mu0, d_P0_out);
     if (mc > 0)
-        launch_phase_p0_modes(h->stream, h->g, h->grid.d_w, B, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr, h->pf.ntab,
+        launch_phase_p0_modes(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g),
                               h->pf.d_modetab.p, h->pf.d_modetab.p + nphi, nphi, mf, mc, d_mu0, d_P0_out + (size_t)(m_count - mc) * B * h->D);
     HIPCHK(hipGetLastError());
     return 0;

@@ -13,11 +13,7 @@ using namespace sosrt;
 static int view_batch_cap(const sosrt_handle* h) { return h->have_cols ? h->B : h->max_batch; }
 
 static int view_phase_check(sosrt_handle* h, int kind, double g, int V2, const double* mu_signed, ViewMu* vm) {
-    if (int e = need_gpu(h)) return e;
-    if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
-    if (kind < SOSRT_PHASE_ISO || kind > SOSRT_PHASE_TABLE) return fail(SOSRT_E_INVALID, "unknown phase-function kind %d", kind);
-    if (kind == SOSRT_PHASE_TABLE && !h->pf.d_tab) return fail(SOSRT_E_STATE, "sosrt_phase_table has not been called");
-    if (kind == SOSRT_PHASE_HG && !(std::fabs(g) < 1)) return fail(SOSRT_E_INVALID, "|g| must be < 1 (got %g)", g);
+    if (int e = phase_check(h, kind, g)) return e;
     if (V2 < 1 || V2 > 2 * SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "V2=%d exit cosines: must be 1..%d", V2, 2 * SOSRT_MAX_VIEWS);
     if (!mu_signed) return fail(SOSRT_E_INVALID, "null mu_signed");
     for (int j = 0; j < V2; ++j) {
@@ -36,8 +32,7 @@ int sosrt_phase_rows_dev(sosrt_t* h, int kind, double g, int V2, const double* m
     if (int e = view_phase_check(h, kind, g, V2, mu_signed, &vm)) return e;
     if (!d_rows_out) return fail(SOSRT_E_INVALID, "null output");
     HIPCHK(hipSetDevice(h->device));
-    launch_phase_rows(h->stream, h->g, h->grid.d_w, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr,
-                      h->pf.ntab, h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, V2, vm, d_rows_out);
+    launch_phase_rows(h->stream, h->g, h->grid.d_w, phase_fn(h, kind, g), h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, V2, vm, d_rows_out);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -48,8 +43,7 @@ int sosrt_phase_p0_rows_dev(sosrt_t* h, int B, int kind, double g, const double*
     if (int e = view_phase_check(h, kind, g, V2, mu_signed, &vm)) return e;
     if (B < 1 || !d_mu0 || !d_out) return fail(SOSRT_E_INVALID, "bad argument");
     HIPCHK(hipSetDevice(h->device));
-    launch_phase_p0_rows(h->stream, h->g, h->grid.d_w, B, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr,
-                         h->pf.ntab, h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, d_mu0, V2, vm, d_out);
+    launch_phase_p0_rows(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g), h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, d_mu0, V2, vm, d_out);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -155,8 +149,7 @@ int sosrt_phase_rows_modes_dev(sosrt_t* h, int kind, double g, int m_first, int 
     if (!d_rows_out) return fail(SOSRT_E_INVALID, "null output");
     HIPCHK(hipSetDevice(h->device));
     if (int e = modes_table(h, nphi, m_first, m_count)) return e;
-    launch_phase_rows_modes(h->stream, h->g, h->grid.d_w, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr,
-                            h->pf.ntab, h->pf.d_modetab.p, h->pf.d_modetab.p + nphi, nphi, m_first, m_count, sign_odd, V2, vm,
+    launch_phase_rows_modes(h->stream, h->g, h->grid.d_w, phase_fn(h, kind, g), h->pf.d_modetab.p, h->pf.d_modetab.p + nphi, nphi, m_first, m_count, sign_odd, V2, vm,
                             d_rows_out);
     HIPCHK(hipGetLastError());
     return 0;
@@ -172,8 +165,7 @@ int sosrt_phase_p0_rows_modes_dev(sosrt_t* h, int B, int kind, double g, int m_f
     if (B > view_batch_cap(h)) return fail(SOSRT_E_INVALID, "B=%d: the handle's current columns are %d", B, view_batch_cap(h));
     HIPCHK(hipSetDevice(h->device));
     if (int e = modes_table(h, nphi, m_first, m_count)) return e;
-    launch_phase_p0_rows_modes(h->stream, h->g, h->grid.d_w, B, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr,
-                               h->pf.ntab, h->pf.d_modetab.p, h->pf.d_modetab.p + nphi, nphi, m_first, m_count, d_mu0, V2, vm, d_out);
+    launch_phase_p0_rows_modes(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g), h->pf.d_modetab.p, h->pf.d_modetab.p + nphi, nphi, m_first, m_count, d_mu0, V2, vm, d_out);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -187,8 +179,7 @@ int sosrt_phase_p0_rows_azimuth_dev(sosrt_t* h, int B, int kind, double g, const
     if (B > view_batch_cap(h)) return fail(SOSRT_E_INVALID, "B=%d: the handle's current columns are %d", B, view_batch_cap(h));
     if ((long long)nphi_out * V2 > 0x7fffffffLL) return fail(SOSRT_E_INVALID, "nphi_out * V2 too large");
     HIPCHK(hipSetDevice(h->device));
-    launch_phase_p0_rows_azimuth(h->stream, h->g, h->grid.d_w, B, kind, g, h->pf.d_tab, h->pf.d_tab ? h->pf.d_tab + h->pf.ntab : nullptr,
-                                 h->pf.ntab, h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, d_mu0, V2, vm, nphi_out, d_phi, d_out);
+    launch_phase_p0_rows_azimuth(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g), h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, d_mu0, V2, vm, nphi_out, d_phi, d_out);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -517,16 +517,13 @@ void launch_epilogue(hipStream_t s, const Grid& g, const double* w, int B, const
                        z_profile, out);
 }
 
-void launch_phase_p0(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
-                     const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi,
-                     const double* mu0, double* P0) {
-    PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
+void launch_phase_p0(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
+                     const double* wphi, int nphi, const double* mu0, double* P0) {
     hipLaunchKernelGGL(k_phase_p0, dim3(B), dim3(256), 0, s, g, w, B, p, cosphi, wphi, nphi, mu0, P0);
 }
 
-void launch_phase_matrix(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
-                         const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi, double* P) {
-    PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
+void launch_phase_matrix(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi,
+                         const double* wphi, int nphi, double* P) {
     hipLaunchKernelGGL(k_phase_matrix, dim3(g.D), dim3(256), 0, s, g, w, p, cosphi, wphi, nphi, P);
 }
 
@@ -539,20 +536,16 @@ static void modes_dispatch(int mc, F&& f) {
     else f(std::integral_constant<int, kMaxModes + 1>());
 }
 
-void launch_phase_modes(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
-                        const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
-                        int m_count, double* P_out) {
-    PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
+void launch_phase_modes(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi, const double* tab,
+                        int nphi, int m_first, int m_count, double* P_out) {
     modes_dispatch(m_count, [&](auto k) {
         hipLaunchKernelGGL(k_phase_modes<decltype(k)::value>, dim3(g.D), dim3(256), 0, s, g, w, p, cosphi, tab, nphi, m_first,
                            m_count, P_out);
     });
 }
 
-void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
-                           const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
-                           int m_count, const double* mu0, double* P0_out) {
-    PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
+void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
+                           const double* tab, int nphi, int m_first, int m_count, const double* mu0, double* P0_out) {
     modes_dispatch(m_count, [&](auto k) {
         hipLaunchKernelGGL(k_phase_p0_modes<decltype(k)::value>, dim3(B), dim3(256), 0, s, g, w, B, p, cosphi, tab, nphi,
                            m_first, m_count, mu0, P0_out);

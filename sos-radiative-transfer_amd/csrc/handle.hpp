@@ -68,6 +68,13 @@ struct Prof {
     int open = -1;                       // opening event of the current bracket
     int adjacent = -1;                   // closing event of the previous bracket, if nothing was enqueued since
 };
+
+// SOSRT_TRANSPORT, in ascending order of what it allows (solve_shape compares with >=).  General: the general kernel; Fast: the
+// wave-independent register-streaming kernel (+ repair); Ring: the LDS-ring kernel; Auto (default): the ring kernel for
+// launches with many live columns (HBM-bound) and the chunk-parallel kernel (transport_scan.hip) for launches with at
+// most scan_cols (latency-bound); Scan: the chunk-parallel kernel always.  The ring and the chunk-parallel kernel share
+// their arithmetic (chunk-local recurrence), so the choice follows the live count without touching a column's bits.
+enum class TransportKnob { General = 0, Fast = 1, Ring = 2, Auto = 3, Scan = 4 };
 }  // namespace sosrt
 
 struct sosrt_handle {
@@ -203,11 +210,10 @@ struct sosrt_handle {
 
     struct Transport {                   // knobs of the transport
         int use_etab = 1;
-        // 0: general kernel, 1: wave-independent fast kernel (+ repair), 2: LDS-ring kernel, 3 (default): the ring kernel for
-        // launches with many live columns (HBM-bound) and the chunk-parallel kernel (transport_scan.hip) for launches with at
-        // most scan_cols (latency-bound), 4: the chunk-parallel kernel always.  The ring and the chunk-parallel kernel share
-        // their arithmetic (chunk-local recurrence), so the choice follows the live count without touching a column's bits.
-        int mode = 3;
+        sosrt::TransportKnob mode = sosrt::TransportKnob::Auto;
+        int ring_slots = 3;                  // SOSRT_RING_SLOTS: ring depth of the ring kernel (a column group beside another: grp.coresident_slots)
+        int ring_debug = 0;                  // SOSRT_RING_DEBUG, diagnostic builds only (-DSOSRT_RING_DEBUG)
+        unsigned long long* d_stamps = nullptr;   // sosrt_debug_stamps: the caller's buffer, written by this handle's transport kernels
         int scan_cols = 200;                 // SOSRT_SCAN_COLS
         bool ring_ok = false, scan_ok = false, scan_split_ok = false, fast_ok = false;
         int scan_split = 1;                  // SOSRT_SCAN_SPLIT: two workgroups per column when at most half as many columns are live as the device has CUs
@@ -371,8 +377,11 @@ int ensure_w32(sosrt_handle* h);
 int ensure_matrices(sosrt_handle* h, hipStream_t s);
 // api_columns.hip: groups the cache of combined matrices may hold
 int mix_group_cap(const sosrt_handle* h, bool sets);
-// api_phasefn.hip, shared with the mode builders at view lanes (api_view.hip): the checks of a mode range, and the upload of
-// cos(phi_q) and the weights of modes [mf, mf + mc) into pf.d_modetab (synchronises the handle's stream first)
+// api_phasefn.hip, shared with the builders at view lanes (api_view.hip): the checks of a phase function by kind, and the
+// function as the builders' kernels take it (the table of sosrt_phase_table, if any: cosines, then values); the checks of a mode
+// range, and the upload of cos(phi_q) and the weights of modes [mf, mf + mc) into pf.d_modetab (synchronises the handle's stream first)
+int phase_check(sosrt_handle* h, int kind, double g);
+PhaseFn phase_fn(const sosrt_handle* h, int kind, double g);
 int modes_check(sosrt_handle* h, int kind, double g, int m_first, int m_count, int nphi);
 int modes_table(sosrt_handle* h, int nphi, int mf, int mc);
 

@@ -1138,23 +1138,22 @@ void launch_tau_groups(hipStream_t s, const Grid& g, int B, const double* tau, u
 }
 
 template <int MAXT>
-static void launch_transport_t(hipStream_t s, dim3 grid, dim3 block, size_t shm, const TransportArgs& a, int mode) {
-    // mode 0: general kernel, 1: wave-independent fast kernel, 2: general kernel repairing flagged columns,
-    // 3: the fast kernel's sweeps fed through an LDS ring, 4: the chunk-parallel kernel (transport_scan.hip)
-    if (mode == 1) {
-        launch_transport_fast(s, grid, block, a);
-    } else if (mode == 3) {
-        launch_transport_ring(s, grid, a, g_ring_slots);
-    } else if (mode == 4) {
-        launch_transport_scan(s, grid, a);
-    } else if (mode == 2) {
+static void launch_transport_t(hipStream_t s, dim3 grid, dim3 block, size_t shm, const TransportArgs& a, TransportKernel kernel) {
+    switch (kernel) {
+    case TransportKernel::Fast: launch_transport_fast(s, grid, block, a); return;
+    case TransportKernel::Ring: launch_transport_ring(s, grid, a, a.slots & 0xff, a.slots >> 8); return;
+    case TransportKernel::Scan: launch_transport_scan(s, grid, a); return;
+    case TransportKernel::Repair:                    // the general kernel, for the flagged columns only
         if (a.accumulate) {
             if (a.saved) hipLaunchKernelGGL((k_transport<MAXT, true, true, true, true>), grid, block, shm, s, a);
             else hipLaunchKernelGGL((k_transport<MAXT, true, false, true, true>), grid, block, shm, s, a);
         } else {
             hipLaunchKernelGGL((k_transport<MAXT, false, false, true, true>), grid, block, shm, s, a);
         }
-    } else if (a.accumulate) {
+        return;
+    case TransportKernel::General: break;
+    }
+    if (a.accumulate) {
         if (a.Etab) {
             if (a.saved) hipLaunchKernelGGL((k_transport<MAXT, true, true, true>), grid, block, shm, s, a);
             else hipLaunchKernelGGL((k_transport<MAXT, true, false, true>), grid, block, shm, s, a);
@@ -1168,9 +1167,6 @@ static void launch_transport_t(hipStream_t s, dim3 grid, dim3 block, size_t shm,
     }
 }
 
-unsigned long long* g_transport_stamps = nullptr;
-int g_ring_slots = 3, g_ring_debug = 0;   // set by sosrt_debug_stamps (diagnostics)
-
 // True when both mu -> 0 treatments of a column fit in wave 0 of k_transport_fast.
 bool transport_fast_ok(const Plan& plan) {
     // every rewritten downward direction and its source directions must sit in the last wave
@@ -1179,28 +1175,15 @@ bool transport_fast_ok(const Plan& plan) {
     return true;
 }
 
-void launch_transport(hipStream_t s, const Grid& g, int B, const double* tau, const double* Jn, double* In, double* I,
-                      double* saved, size_t saved_col_stride, const ColDesc* desc, Conv cv, int order,
-                      int accumulate, const double* Etab, int mode, const int* erep, int live, const int* live_list,
-                      int ring_slots, int scan_split, double* scan_scratch, int* scan_sync, int nzcap, const double* mom,
-                      const double* lrV, int lr_rank) {
-    const int nt = round64(g.N);
-    const size_t shm = (size_t)(g.L + 2 * TC * (nt + 2) + 2 * nt + nt / 64 + 2) * sizeof(double);
-    TransportArgs a{g, tau, Jn, In, I, accumulate ? saved : nullptr, saved_col_stride, desc, cv, order, accumulate, Etab, Etab ? erep : nullptr, g_transport_stamps};
-    a.slots = ring_slots;
-    a.nzcap = nzcap > kRingZones ? nzcap : kRingZones;
-    if (mode == 3 && mom && accumulate && !saved && a.nzcap <= kRingZones) { a.mom = mom; a.lrV = lrV; a.lr_rank = lr_rank; }       // (the ring kernel alone reads moment records)
-    if (mode == 4 && scan_split && scan_scratch && scan_sync) { a.scan_split = 1; a.scan_scratch = scan_scratch; a.scan_sync = scan_sync; }
-    if ((mode == 3 || mode == 4) && accumulate && live > 0 && live < B && live_list) {       // ring / scan kernel over the live columns only
-        a.live = live;
-        a.live_list = live_list;
-        B = live;
-    }
+void launch_transport(hipStream_t s, TransportKernel kernel, int B, const TransportArgs& a) {
+    const int nt = round64(a.g.N);
+    const size_t shm = (size_t)(a.g.L + 2 * TC * (nt + 2) + 2 * nt + nt / 64 + 2) * sizeof(double);
+    const dim3 grid(a.live > 0 ? a.live : B);        // (over the live list: workgroup i takes column live_list[i])
     // the register budget follows the workgroup size: one column needs few waves, so they may be fat
-    if (nt <= 128) launch_transport_t<128>(s, dim3(B), dim3(nt), shm, a, mode);
-    else if (nt <= 256) launch_transport_t<256>(s, dim3(B), dim3(nt), shm, a, mode);
-    else if (nt <= 512) launch_transport_t<512>(s, dim3(B), dim3(nt), shm, a, mode);
-    else launch_transport_t<1024>(s, dim3(B), dim3(nt), shm, a, mode);
+    if (nt <= 128) launch_transport_t<128>(s, grid, dim3(nt), shm, a, kernel);
+    else if (nt <= 256) launch_transport_t<256>(s, grid, dim3(nt), shm, a, kernel);
+    else if (nt <= 512) launch_transport_t<512>(s, grid, dim3(nt), shm, a, kernel);
+    else launch_transport_t<1024>(s, grid, dim3(nt), shm, a, kernel);
 }
 
 // columns still iterating when the order budget is exhausted

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "phasefn.hpp"
 #include "plan.hpp"
 
 namespace sosrt {
@@ -102,6 +103,12 @@ constexpr int GEMM_WPS = SOSRT_GEMM_WPS;   // waves per SIMD the register budget
 // multiply-adds of the recurrence are sequential.
 constexpr int TC = 8;
 
+// The transport kernels by name; the values are the public SOSRT_PLAN_TRANSPORT_* of sosrt_plan_launch (tied in solve.hip).
+// Repair: the general kernel behind the register-streaming one, for the columns whose search left wave 0 (flag cv.redo).
+enum class TransportKernel { General = 0, Fast = 1, Repair = 2, Ring = 3, Scan = 4 };
+
+// What a transport launch is given: a by-value kernel argument, and the whole interface of launch_transport.  The host fills it in
+// one place (solve.hip: transport_args), by name; the launchers size and dispatch and leave every field as it came.
 struct TransportArgs {
     Grid g;
     const double* tau;
@@ -124,7 +131,9 @@ struct TransportArgs {
     // sweep tend to share their index modulo 8).
     int live = 0;
     const int* live_list = nullptr;
-    int slots = 0;             // ring depth of this launch (0: the default)
+    // host side, ring kernel: the ring depth of this launch in the low byte (ring_slots_word; the launcher takes at least two and
+    // as many as fit), above it the timing switches of a diagnostic build (-DSOSRT_RING_DEBUG), which reach the kernel as dbg_arg
+    int slots = 0;
     // most zones of any column of the batch (>= kRingZones): sizes the per-zone tables of the ring / chunk-parallel kernels and
     // selects their instantiation (beyond three zones: the one that tests the other boundaries too)
     int nzcap = kRingZones;
@@ -143,7 +152,8 @@ void launch_transport_fast(hipStream_t s, dim3 grid, dim3 block, const Transport
 // transport_ring.hip: same sweeps, rows streamed through an LDS ring by loader waves
 bool transport_ring_ok(const Grid& g);
 bool transport_ring_fits(const Grid& g, int nzcap);            // ... with the per-zone tables of up to nzcap zones
-void launch_transport_ring(hipStream_t s, dim3 grid, const TransportArgs& a, int slots);
+constexpr int ring_slots_word(int depth, int debug) { return (depth < 0 ? 0 : (depth > 255 ? 255 : depth)) | (debug << 8); }
+void launch_transport_ring(hipStream_t s, dim3 grid, const TransportArgs& a, int slots, int debug);
 // transport_scan.hip: the chunks of a sweep dealt to several waves (chunk-local recurrence + carried values)
 bool transport_scan_ok(const Grid& g);
 bool transport_scan_split_ok(const Grid& g);
@@ -159,8 +169,6 @@ constexpr int kOlArrive = 0, kOlState = 32, kOlLeft = 64, kOlAbort = 96, kOlOrde
 constexpr int kOlColStride = 64, kOlOrdDone = 0, kOlColStop = 1, kOlJnDone = 32;
 constexpr int kOlReady = 1, kOlNotResident = 2, kOlAborted = 3;            // state of a launch, as reported to the host
 inline size_t order_loop_sync_ints(int cols) { return (size_t)kOlCols + (size_t)cols * kOlColStride; }
-extern int g_ring_slots, g_ring_debug;                        // tuning (SOSRT_RING_SLOTS)
-extern unsigned long long* g_transport_stamps;   // diagnostics (sosrt_debug_stamps)
 
 // what the first kernel of a solve does besides the zone tables (all null: nothing)
 struct SolveSetup {
@@ -314,11 +322,9 @@ void launch_symfold(hipStream_t s, int nmat, int N, int D, int Dp, int Wld, cons
 void launch_gemm_tail(hipStream_t s, const GemmArgs& a, int cols, bool small_tiles, bool regs = false, const AtmSets* at = nullptr);
 void launch_smallmu(hipStream_t s, const Grid& g, int B, const double* tau, const double* Jn, double* In,
                     const ColDesc* desc, const int* active);
-void launch_transport(hipStream_t s, const Grid& g, int B, const double* tau, const double* Jn, double* In, double* I,
-                      double* saved, size_t saved_col_stride, const ColDesc* desc, Conv cv, int order, int accumulate,
-                      const double* Etab, int mode, const int* erep = nullptr, int live = 0, const int* live_list = nullptr,
-                      int ring_slots = 0, int scan_split = 0, double* scan_scratch = nullptr, int* scan_sync = nullptr,
-                      int nzcap = kRingZones, const double* mom = nullptr, const double* lrV = nullptr, int lr_rank = 0);
+// B workgroups' worth of columns (a.live of them when the launch runs over the live list): sizes the block and the LDS and
+// dispatches on the kernel's name, nothing else
+void launch_transport(hipStream_t s, TransportKernel kernel, int B, const TransportArgs& a);
 bool transport_fast_ok(const Plan& plan);
 // erep (nullable): tables are built only for columns with erep[b] == b
 void launch_attenuation(hipStream_t s, const Grid& g, int B, const double* tau, double* Etab, const int* erep);
@@ -340,21 +346,18 @@ struct EpilogueOut {
 void launch_epilogue(hipStream_t s, const Grid& g, const double* w, int B, const double* tau, const double* I,
                      const ColDesc* desc, int beam_norm, const double* z_profile, const EpilogueOut& out);
 // phase functions on the device; cosphi / wphi: cos(phi) and trapz weights of phi = linspace(0, pi, nphi)
-void launch_phase_p0(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
-                     const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi,
-                     const double* mu0, double* P0);
-void launch_phase_matrix(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
-                         const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi, double* P);
+void launch_phase_p0(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
+                     const double* wphi, int nphi, const double* mu0, double* P0);
+void launch_phase_matrix(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi,
+                         const double* wphi, int nphi, double* P);
 // Fourier modes of the phase function in azimuth (sosrt_phase_modes): modes [m_first, m_first + m_count) with m_first >= 1 of
 // P^m (P_out [m_count][D][D]) or of P0^m (P0_out [m_count][B][D]); tab [1 + m_count][nphi] holds the trapezoid weights of
 // phi = linspace(0, pi, nphi) (row 0, the m = 0 ring that normalises) and w_q cos(m phi_q) of each mode; cosphi [nphi].
 constexpr int kMaxModes = 64;      // SOSRT_MAX_MODES
-void launch_phase_modes(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
-                        const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
-                        int m_count, double* P_out);
-void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
-                           const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
-                           int m_count, const double* mu0, double* P0_out);
+void launch_phase_modes(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi, const double* tab,
+                        int nphi, int m_first, int m_count, double* P_out);
+void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
+                           const double* tab, int nphi, int m_first, int m_count, const double* mu0, double* P0_out);
 // out[b][lev][dir][j] (+)= (2 - delta_m0) I^m[b][levels[lev]][dir] cos(m phi[j])   (m == 0 writes, m >= 1 adds)
 void launch_azimuth_accumulate(hipStream_t s, const Grid& g, int B, int m, const double* Im, int nlev, const int* levels,
                                int nphi_out, const double* phi, double* out);
@@ -390,24 +393,22 @@ struct ViewLevels {
 };
 // rows [V2][D] of the stored phase matrix at exit cosines mu.s[j]; out [B][V2] the same of P0 (normalisers recomputed as
 // launch_phase_matrix / launch_phase_p0 compute them)
-void launch_phase_rows(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
-                       const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi, int V2,
-                       const ViewMu& mu, double* rows);
-void launch_phase_p0_rows(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
-                          const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi, const double* mu0,
-                          int V2, const ViewMu& mu, double* out);
+void launch_phase_rows(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi, const double* wphi,
+                       int nphi, int V2, const ViewMu& mu, double* rows);
+void launch_phase_p0_rows(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
+                          const double* wphi, int nphi, const double* mu0, int V2, const ViewMu& mu, double* out);
 // the same rows of the Fourier modes [m_first, m_first + m_count), m_first >= 1: rows [m_count][V2][D]
 // ((-1)^m rows^m with sign_odd), out [m_count][B][V2]; cosphi, tab as launch_phase_modes takes them
-void launch_phase_rows_modes(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
-                             const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
-                             int m_count, int sign_odd, int V2, const ViewMu& mu, double* rows);
-void launch_phase_p0_rows_modes(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
-                                const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
-                                int m_count, const double* mu0, int V2, const ViewMu& mu, double* out);
+void launch_phase_rows_modes(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi,
+                             const double* tab, int nphi, int m_first, int m_count, int sign_odd, int V2, const ViewMu& mu,
+                             double* rows);
+void launch_phase_p0_rows_modes(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
+                                const double* tab, int nphi, int m_first, int m_count, const double* mu0, int V2,
+                                const ViewMu& mu, double* out);
 // out [nphi_out][B][V2] = p(c(s_j, mu0_b, phi_i)) / Z0_b with launch_phase_p0_rows' normaliser (cosphi, wphi: its ring)
-void launch_phase_p0_rows_azimuth(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
-                                  const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi,
-                                  const double* mu0, int V2, const ViewMu& mu, int nphi_out, const double* phi, double* out);
+void launch_phase_p0_rows_azimuth(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
+                                  const double* wphi, int nphi, const double* mu0, int V2, const ViewMu& mu, int nphi_out,
+                                  const double* phi, double* out);
 // out [n][nphi_out] (+)= (2 - delta_m0) val[n] cos(m phi[j]), n = B nlev 2V   (m == 0 writes, m >= 1 adds; epilogue.hip)
 void launch_view_azimuth_accumulate(hipStream_t s, size_t n, int m, const double* val, int nphi_out, const double* phi, double* out);
 // S [nrows][2V] = diag(ca) Isrc W_atm + diag(cr) Isrc W_aer with the rows folded into Wfold [view_source_kpad(D)][view_source_cols(V)]

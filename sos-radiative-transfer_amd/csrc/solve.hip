@@ -1,5 +1,5 @@
-// The solve: the launch plan of an order (plan_order: host only, one place for the whole policy), the source-function
-// launch, the order loop of sosrt_solve_dev with its lagged convergence polling, and the step-level entry points
+// The solve: the launch plan of an order (plan_order: host only, one place for the whole policy), the arguments of a transport
+// launch (transport_args: one place for every condition on a field), the source-function launch, the order loop of sosrt_solve_dev with its lagged convergence polling, and the step-level entry points
 // around them (fluxes and the epilogue on a resident field are in api.hip).  Host code, and one kernel: k_init_from_I1, the
 // first order supplied by the caller.
 #include <hip/hip_runtime.h>
@@ -174,17 +174,20 @@ struct SolveShape {                      // what a solve fixes for all its order
     bool ring_like = false;              // the ring / chunk-parallel kernels take the batch (they hold its zone tables)
     bool fast = false;                   // a wave-independent kernel runs (else the general kernel)
     int nzcap = kRingZones;              // most zones of any column, at least three
-    int ring_mode = 1;                   // 3: ring-class kernels, 1: the register-streaming kernel
+    bool ring_mode = false;              // the wave-independent kernel is of the ring class (else the register-streaming kernel)
 };
+static_assert((int)TransportKernel::General == SOSRT_PLAN_TRANSPORT_GENERAL && (int)TransportKernel::Fast == SOSRT_PLAN_TRANSPORT_FAST &&
+              (int)TransportKernel::Ring == SOSRT_PLAN_TRANSPORT_RING && (int)TransportKernel::Scan == SOSRT_PLAN_TRANSPORT_SCAN,
+              "sosrt_plan_launch reports TransportKernel as SOSRT_PLAN_TRANSPORT_*");
 SolveShape solve_shape(const sosrt_handle* h, int max_nz) {
     SolveShape sh;
     // The ring / chunk-parallel kernels take columns of any zone count (an instantiation that tests every boundary of the zone
     // table, chosen when the batch holds such a column); the register-streaming kernel knows three zones, so a batch with more
     // goes to the general kernel where that one would run (odd N, N > 256).
-    sh.ring_like = h->tr.mode >= 2 && h->tr.ring_ok && (max_nz <= kRingZones || transport_ring_fits(h->g, max_nz));
-    sh.fast = h->tr.mode >= 1 && h->tr.fast_ok && (max_nz <= kRingZones || sh.ring_like);
+    sh.ring_like = h->tr.mode >= TransportKnob::Ring && h->tr.ring_ok && (max_nz <= kRingZones || transport_ring_fits(h->g, max_nz));
+    sh.fast = h->tr.mode >= TransportKnob::Fast && h->tr.fast_ok && (max_nz <= kRingZones || sh.ring_like);
     sh.nzcap = max_nz > kRingZones ? max_nz : kRingZones;
-    sh.ring_mode = (h->tr.mode >= 2 && h->tr.ring_ok) ? 3 : 1;
+    sh.ring_mode = h->tr.mode >= TransportKnob::Ring && h->tr.ring_ok;
     return sh;
 }
 struct OrderInputs {                     // what the plan of one order depends on besides the handle
@@ -203,7 +206,7 @@ struct LaunchPlan {
     int tail_cols = 0;                   // contraction over the live columns: capacity of the launch (0: dense tiling over the row lists)
     int live_cap = 0;                    // transport over the live list: its capacity (0: over all columns of the group)
     int gemm = SOSRT_PLAN_GEMM_DENSE;
-    int transport = SOSRT_PLAN_TRANSPORT_GENERAL;
+    TransportKernel transport = TransportKernel::General;
     int parts = 1;                       // chunk-parallel kernel: workgroups per column
     int repair = 0;                      // register-streaming kernel: the general kernel behind it for searches that leave wave 0
     int order_loop = 0;                  // this and every later order of the group in ONE order-loop launch
@@ -248,23 +251,23 @@ LaunchPlan plan_order(const sosrt_handle* h, const SolveShape& sh, const OrderIn
         // (where the shape has no ring kernel -- odd N, N > 256: the split form's WIDE instantiation -- the alternative is the
         // register-streaming kernel, one workgroup per column and 650 us per order at the shipped size against 133 for a round of
         // split workgroups: up to four rounds of them are the faster way)
-        const int split_cap = sh.ring_mode == 3 ? h->cu_count : 4 * h->cu_count;
+        const int split_cap = sh.ring_mode ? h->cu_count : 4 * h->cu_count;
         const bool can_split = h->tr.scan_split && h->tr.scan_split_ok && transport_scan_parts(g) * cols_now <= split_cap &&
                                (in.surface == SOSRT_SURFACE_SPECULAR || in.surface == SOSRT_SURFACE_NONE);
-        const bool want_scan = h->tr.mode == 4 || (h->tr.mode == 3 && cols_now <= h->tr.scan_cols);
+        const bool want_scan = h->tr.mode == TransportKnob::Scan || (h->tr.mode == TransportKnob::Auto && cols_now <= h->tr.scan_cols);
         // (the split form also takes the shapes no wave-independent kernel does -- the rewritten directions straddle two waves of a
         // half row, e.g. N = 70, 129, 257: sh.fast is false -- as long as the attenuation tables are built)
-        const bool split = can_split && transport_scan_fits(g, sh.nzcap, true) && (sh.fast || (h->tr.use_etab && h->tr.mode >= 3));
-        const bool scan = want_scan && ((sh.fast && sh.ring_mode == 3 && h->tr.scan_ok && transport_scan_fits(g, sh.nzcap, false)) || split);
-        pl.transport = scan ? SOSRT_PLAN_TRANSPORT_SCAN
-                            : (!sh.fast ? SOSRT_PLAN_TRANSPORT_GENERAL : (sh.ring_mode == 3 ? SOSRT_PLAN_TRANSPORT_RING : SOSRT_PLAN_TRANSPORT_FAST));
+        const bool split = can_split && transport_scan_fits(g, sh.nzcap, true) && (sh.fast || (h->tr.use_etab && h->tr.mode >= TransportKnob::Auto));
+        const bool scan = want_scan && ((sh.fast && sh.ring_mode && h->tr.scan_ok && transport_scan_fits(g, sh.nzcap, false)) || split);
+        pl.transport = scan ? TransportKernel::Scan
+                            : (!sh.fast ? TransportKernel::General : (sh.ring_mode ? TransportKernel::Ring : TransportKernel::Fast));
         if (scan && split) pl.parts = transport_scan_parts(g);
-        pl.repair = (h->N - 3 > 61 && pl.transport == SOSRT_PLAN_TRANSPORT_FAST) ? 1 : 0;
+        pl.repair = (h->N - 3 > 61 && pl.transport == TransportKernel::Fast) ? 1 : 0;
     }
     // order-loop kernel: the remaining orders in one launch once the live columns' transport workgroups are a small share of the
     // CUs it may take (the other workgroups contract).  It holds the chunk-parallel transport (three zones, no kept k_smallmu
     // lane) and the symmetric contraction's live-column tiles; the default transport policy only (a forced kernel stays forced).
-    if (h->ol.mode && in.cu_share > 0 && h->tr.mode == 3 && sh.fast && sh.ring_mode == 3 && sh.nzcap <= kRingZones &&
+    if (h->ol.mode && in.cu_share > 0 && h->tr.mode == TransportKnob::Auto && sh.fast && sh.ring_mode && sh.nzcap <= kRingZones &&
         use_sym(h) && in.simple_zones && in.slabs_mixed && !in.saving && !in.need_small && in.orders_left >= 1 &&
         in.known <= kOrderLoopMaxCols) {
         Grid gt = g;
@@ -282,8 +285,71 @@ LaunchPlan plan_order(const sosrt_handle* h, const SolveShape& sh, const OrderIn
     // f64 contraction, one W_atm for the batch, no saved orders, the ring kernel for every column of the group (its three-zone
     // instantiation) and no k_smallmu launch, which reads rows of Jn.  Anything else: rows of Jn, as always.
     pl.moments = (h->tr.ring_moments && use_lowrank(h) && use_sym(h) && !in.atm_sets && !in.saving && !pl.order_loop &&
-                  pl.transport == SOSRT_PLAN_TRANSPORT_RING && sh.nzcap <= kRingZones && !in.need_small) ? 1 : 0;
+                  pl.transport == TransportKernel::Ring && sh.nzcap <= kRingZones && !in.need_small) ? 1 : 0;
     return pl;
+}
+
+// The transport of the step entry (sosrt_transport), as a plan of its own and deliberately not plan_order's: a step has no live
+// count, so the Auto knob never picks the chunk-parallel kernel here, and that kernel runs in its one-workgroup form.
+LaunchPlan plan_step_transport(const sosrt_handle* h, const SolveShape& sh) {
+    LaunchPlan pl;
+    if (!sh.fast) return pl;                 // the general kernel, without attenuation tables
+    const bool scan = h->tr.mode == TransportKnob::Scan && h->tr.scan_ok && transport_scan_fits(h->g, sh.nzcap, false);
+    pl.transport = scan ? TransportKernel::Scan : (sh.ring_like ? TransportKernel::Ring : TransportKernel::Fast);
+    pl.repair = (h->N - 3 > 61 && !sh.ring_mode) ? 1 : 0;
+    return pl;
+}
+
+// One transport launch of a column group, by name: which columns, which buffers, which order.
+struct TransportCall {
+    int b0 = 0, nb = 0;                  // the group's first column and count
+    const double* tau = nullptr;         // whole-batch pointers (the builder offsets them to the group's first column) ...
+    double* In = nullptr;
+    double* I = nullptr;
+    double* saved = nullptr;             // ... this order's slot of the batch's first column; null: not saved
+    size_t saved_stride = 0;
+    Conv cv;                             // the group's
+    int order = 0;
+    bool accumulate = false;             // an order of a solve (else the step entry: In only)
+    bool etab = false;                   // the attenuation tables of this tau are built ...
+    const int* erep = nullptr;           // ... one per distinct profile ([batch], values are whole-batch column ids); null: one per column
+    bool need_small = true;              // some |mu| < 0.01 lane keeps its k_smallmu value
+    bool coresident = false;             // another column group runs beside this one
+};
+
+// The arguments of that launch with `kernel` (for an order-loop launch, whose transport role is the chunk-parallel kernel: Scan).
+// Every condition on a field is stated here, once, in terms of the kernel; launch_transport honours what it is given.
+int transport_args(const sosrt_handle* h, const TransportCall& c, const LaunchPlan& pl, const SolveShape& sh, TransportKernel kernel,
+                   TransportArgs* out) {
+    const bool ring_class = kernel == TransportKernel::Ring || kernel == TransportKernel::Scan;
+    const size_t LD = (size_t)h->L * h->D;
+    // The contraction of a moment order has written records and NOT the plain rows of Jn: the ring kernel must expand them
+    // (plan_order turns the mode on only where it can)
+    if (pl.moments && (kernel != TransportKernel::Ring || !c.accumulate || c.saved || sh.nzcap > kRingZones))
+        return fail(SOSRT_E_STATE, "internal: moment records planned for a transport launch that cannot read them");
+    TransportArgs a{};
+    a.g = h->g;
+    // once the device has reported that no |mu| < 0.01 lane keeps its k_smallmu value, the ring kernel
+    // need not stage those rows either
+    if (ring_class && !c.need_small) a.g.nsmall = 0;
+    a.tau = c.tau + (size_t)c.b0 * h->L; a.Jn = h->fld.d_Jn + (size_t)c.b0 * LD; a.desc = h->cols.d_desc + c.b0;
+    a.In = c.In ? c.In + (size_t)c.b0 * LD : nullptr; a.I = c.I ? c.I + (size_t)c.b0 * LD : nullptr;
+    a.saved = (c.accumulate && c.saved) ? c.saved + (size_t)c.b0 * c.saved_stride : nullptr; a.saved_col_stride = c.saved_stride;
+    a.cv = c.cv; a.order = c.order; a.accumulate = c.accumulate ? 1 : 0;
+    a.Etab = c.etab ? h->fld.d_E : nullptr;
+    a.erep = (c.etab && c.erep) ? c.erep + c.b0 : nullptr;      // (values are whole-batch column ids; the table base is not offset)
+    a.stamps = pl.order_loop ? nullptr : h->tr.d_stamps;         // (an order-loop launch has its own event log)
+    // over the live columns only: the grid is then `live` (an order-loop launch finds its live columns itself)
+    if (ring_class && c.accumulate && !pl.order_loop && pl.live_cap > 0 && pl.live_cap < c.nb) { a.live = pl.live_cap; a.live_list = h->gemm.d_livelist + c.b0; }
+    a.slots = ring_slots_word(c.coresident && h->grp.coresident_slots > 0 ? h->grp.coresident_slots : h->tr.ring_slots, h->tr.ring_debug);
+    a.nzcap = sh.nzcap > kRingZones ? sh.nzcap : kRingZones;
+    if (kernel == TransportKernel::Scan && (pl.order_loop ? pl.ol_parts : pl.parts) > 1) {
+        a.scan_split = 1;
+        a.scan_scratch = h->tr.d_scan_scratch + (size_t)c.b0 * transport_scan_scratch_doubles(); a.scan_sync = h->tr.d_scan_sync + 2 * c.b0;
+    }
+    if (pl.moments) { a.mom = h->tr.d_mom + (size_t)c.b0 * h->L * kMomDoubles; a.lrV = h->phase.d_lrV; a.lr_rank = h->phase.lr_rank; }
+    *out = a;
+    return 0;
 }
 
 // CUs of a device that order-loop launches of this process hold (their workgroups wait for each other, so every one of them must
@@ -348,7 +414,7 @@ int sosrt_plan_launch(sosrt_t* h, int batch, int live, int surface, int zones, i
     int ng = 0;
     LaunchPlan pl;
     if (int e = plan_query(h, batch, live, surface, zones, cus, 0, true, &ng, &pl)) return e;
-    out[0] = ng; out[1] = pl.gemm; out[2] = pl.tail_cols; out[3] = pl.transport; out[4] = pl.parts; out[5] = pl.repair;
+    out[0] = ng; out[1] = pl.gemm; out[2] = pl.tail_cols; out[3] = (int)pl.transport; out[4] = pl.parts; out[5] = pl.repair;
     out[6] = pl.order_loop; out[7] = pl.ol_parts; out[8] = pl.ol_grid;
     return 0;
 }
@@ -443,18 +509,21 @@ int sosrt_transport(sosrt_t* h, int B, const double* tau, const double* Jn, doub
     launch_smallmu(h->stream, h->g, B, h->fld.d_tau, h->fld.d_Jn, h->fld.d_InB, h->cols.d_desc, nullptr);
     prof_end(h, SOSRT_K_SMALLMU);
     prof_begin(h, SOSRT_K_TRANSPORT);
-    const bool ring_like = h->tr.mode >= 2 && h->tr.ring_ok && (h->cols.max_nz <= kRingZones || transport_ring_fits(h->g, h->cols.max_nz));
-    const int nzcap = h->cols.max_nz > kRingZones ? h->cols.max_nz : kRingZones;
-    if (h->tr.mode >= 1 && h->tr.fast_ok && (h->cols.max_nz <= kRingZones || ring_like)) {
+    const SolveShape sh = solve_shape(h, h->cols.max_nz);
+    const LaunchPlan pl = plan_step_transport(h, sh);
+    TransportCall c;
+    c.nb = B; c.tau = h->fld.d_tau; c.In = h->fld.d_InB; c.cv = make_conv(h, 0);
+    c.etab = pl.transport != TransportKernel::General;           // (tables for every column: no erep)
+    if (c.etab) {
         launch_attenuation(h->stream, h->g, B, h->fld.d_tau, h->fld.d_E, nullptr);
         HIPCHK(hipMemsetAsync(h->fld.d_redo, 0, B * sizeof(int), h->stream));
-        launch_transport(h->stream, h->g, B, h->fld.d_tau, h->fld.d_Jn, h->fld.d_InB, nullptr, nullptr, 0, h->cols.d_desc, make_conv(h, 0), 0, 0, h->fld.d_E,
-                         (h->tr.mode == 4 && h->tr.scan_ok && transport_scan_fits(h->g, nzcap, false)) ? 4 : (ring_like ? 3 : 1),
-                         nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nzcap);
-        if (h->N - 3 > 61 && !(h->tr.mode >= 2 && h->tr.ring_ok))
-            launch_transport(h->stream, h->g, B, h->fld.d_tau, h->fld.d_Jn, h->fld.d_InB, nullptr, nullptr, 0, h->cols.d_desc, make_conv(h, 0), 0, 0, h->fld.d_E, 2);
-    } else {
-        launch_transport(h->stream, h->g, B, h->fld.d_tau, h->fld.d_Jn, h->fld.d_InB, nullptr, nullptr, 0, h->cols.d_desc, make_conv(h, 0), 0, 0, nullptr, 0);
+    }
+    TransportArgs ta;
+    if (int e = transport_args(h, c, pl, sh, pl.transport, &ta)) return e;
+    launch_transport(h->stream, pl.transport, B, ta);
+    if (pl.repair) {
+        if (int e = transport_args(h, c, pl, sh, TransportKernel::Repair, &ta)) return e;
+        launch_transport(h->stream, TransportKernel::Repair, B, ta);
     }
     prof_end(h, SOSRT_K_TRANSPORT);
     HIPCHK(hipGetLastError());
@@ -703,14 +772,9 @@ struct SolveRun {
         hipStream_t sg = group_stream(h, k);
         const size_t fo = (size_t)q.b0 * LD;
         OrderLoopArgs oa;
-        Grid gt = g;
-        gt.nsmall = 0;
-        // (erep: values are whole-batch column ids; the table base is not offset)
-        oa.t = TransportArgs{gt, d_tau + (size_t)q.b0 * h->L, h->fld.d_Jn + fo, nullptr, d_I_out + fo, nullptr, 0, h->cols.d_desc + q.b0, q.cv, 0, 1, h->fld.d_E, h->fld.d_erep + q.b0, nullptr};
-        oa.t.nzcap = kRingZones;
-        oa.t.scan_split = pl.ol_parts > 1 ? 1 : 0;
-        oa.t.scan_scratch = h->tr.d_scan_scratch + (size_t)q.b0 * transport_scan_scratch_doubles();
-        oa.t.scan_sync = h->tr.d_scan_sync + 2 * q.b0;
+        TransportCall c = transport_call(k);
+        c.I = d_I_out; c.etab = true;
+        if (int e = transport_args(h, c, pl, shape, TransportKernel::Scan, &oa.t)) return e;
         oa.gm = gemm_args(h, true);
         oa.gm.A = nullptr; oa.gm.C = h->fld.d_Jn;
         oa.in0 = q.In_1;
@@ -743,14 +807,23 @@ struct SolveRun {
         return 0;
     }
 
+    // what every transport launch of a group's orders has in common (the caller adds its buffers and the order)
+    TransportCall transport_call(int k) const {
+        const GroupState& q = gs[k];
+        TransportCall c;
+        c.b0 = q.b0; c.nb = q.nb; c.tau = d_tau; c.cv = q.cv;
+        c.accumulate = true; c.erep = h->fld.d_erep;
+        c.need_small = h->fld.need_small; c.coresident = NG > 1;
+        return c;
+    }
+
     // one order of a group as two (or three) launches: source function, small-mu lanes, transport
-    void run_order(int k, const LaunchPlan& pl) {
+    int run_order(int k, const LaunchPlan& pl) {
         GroupState& q = gs[k];
         const Grid& g = h->g;
         hipStream_t sg = group_stream(h, k);
         const size_t fo = (size_t)q.b0 * LD;
         const double* tau_g = d_tau + (size_t)q.b0 * h->L;
-        const int* erep_g = h->fld.d_erep + q.b0;     // values are whole-batch column ids; the table base is not offset
         const int n = ++q.n;
         n_max = n > n_max ? n : n_max;
         // this launch also publishes the group's live count after order n-1
@@ -765,29 +838,25 @@ struct SolveRun {
             prof_end(h, SOSRT_K_SMALLMU, k);
         }
         prof_begin(h, SOSRT_K_TRANSPORT, k);
-        double* sv_n = (d_I_saved_out && n <= h->saved_slots) ? saved_of(k) + (size_t)(n - 1) * LD : nullptr;
-        if (pl.transport != SOSRT_PLAN_TRANSPORT_GENERAL) {
-            // once the device has reported that no |mu| < 0.01 lane keeps its k_smallmu value, the ring kernel
-            // need not stage those rows either
-            Grid gt = g;
-            if (pl.transport >= SOSRT_PLAN_TRANSPORT_RING && !h->fld.need_small) gt.nsmall = 0;
-            launch_transport(sg, gt, q.nb, tau_g, h->fld.d_Jn + fo, q.In + fo, d_I_out + fo, sv_n, saved_stride, h->cols.d_desc + q.b0, q.cv, n, 1,
-                             h->fld.d_E, pl.transport, erep_g, pl.live_cap, h->gemm.d_livelist + q.b0, NG > 1 ? h->grp.coresident_slots : 0,
-                             pl.parts > 1 ? 1 : 0, h->tr.d_scan_scratch + (size_t)q.b0 * transport_scan_scratch_doubles(),
-                             h->tr.d_scan_sync + 2 * q.b0, shape.nzcap,
-                             pl.moments ? h->tr.d_mom + (size_t)q.b0 * h->L * kMomDoubles : nullptr, h->phase.d_lrV, h->phase.lr_rank);
-            if (pl.repair)                           // register-streaming kernel: a search that leaves wave 0 is redone by the
-                launch_transport(sg, g, q.nb, tau_g, h->fld.d_Jn + fo, q.In + fo, d_I_out + fo, sv_n, saved_stride, h->cols.d_desc + q.b0, q.cv, n, 1,
-                                 h->fld.d_E, 2, erep_g);         // general kernel (flag cv.redo); the ring kernel redoes it itself
-        } else {
-            launch_transport(sg, g, q.nb, tau_g, h->fld.d_Jn + fo, q.In + fo, d_I_out + fo, sv_n, saved_stride, h->cols.d_desc + q.b0, q.cv, n, 1,
-                             h->tr.use_etab ? h->fld.d_E : nullptr, 0, erep_g);
+        TransportCall c = transport_call(k);
+        c.In = q.In; c.I = d_I_out; c.order = n;
+        if (d_I_saved_out && n <= h->saved_slots) { c.saved = d_I_saved_out + (size_t)(n - 1) * LD; c.saved_stride = saved_stride; }
+        c.etab = pl.transport != TransportKernel::General || h->tr.use_etab;
+        TransportArgs ta;
+        if (int e = transport_args(h, c, pl, shape, pl.transport, &ta)) return e;
+        launch_transport(sg, pl.transport, q.nb, ta);
+        if (pl.repair) {
+            // register-streaming kernel: a search that leaves wave 0 is redone by the general kernel (flag cv.redo); the ring
+            // kernel redoes it itself
+            if (int e = transport_args(h, c, pl, shape, TransportKernel::Repair, &ta)) return e;
+            launch_transport(sg, TransportKernel::Repair, q.nb, ta);
         }
         prof_end(h, SOSRT_K_TRANSPORT, k);
         ++h->tr.orders;
         if (pl.moments) ++h->tr.moment_orders;
         if (q.In_1 == d_I_out) { q.In_1 = q.In; q.In = h->fld.d_InA; }      // (after the second order: the buffer the first order left unused)
         else { double* tmp = q.In_1; q.In_1 = q.In; q.In = tmp; }
+        return 0;
     }
 
     // back onto the caller's stream; after the join the destructor has nothing left to do
@@ -884,7 +953,7 @@ int sosrt_solve_dev(sosrt_t* h, int B, const double* d_tau, const double* d_P0_a
             if (pl.order_loop) {
                 if (int e = r.launch_order_loop(k, pl)) return e;
             } else {
-                r.run_order(k, pl);
+                if (int e = r.run_order(k, pl)) return e;
             }
         }
         if (!progressed) __builtin_ia32_pause();      // (every live group is inside its order-loop launch)

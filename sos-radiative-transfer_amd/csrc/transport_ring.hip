@@ -717,7 +717,7 @@ inline size_t ring_extra_doubles(const Grid& g, int nt, int nzcap = kRingZones) 
 }
 
 template <int PIECES>
-void launch_p(hipStream_t s, dim3 grid, dim3 block, const TransportArgs& a, int NS) {
+void launch_p(hipStream_t s, dim3 grid, dim3 block, const TransportArgs& a, int NS, int debug) {
     const int nt = (int)block.x;
     const int narr = a.accumulate ? 3 : 2;
     const size_t shm = ((size_t)NS * narr * TC * 128 * PIECES + ring_extra_doubles(a.g, nt, a.nzcap)) * sizeof(double);
@@ -729,7 +729,7 @@ void launch_p(hipStream_t s, dim3 grid, dim3 block, const TransportArgs& a, int 
             hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                 (int)kRingLdsBytes);                                                                   \
         }                                                                                                      \
-        hipLaunchKernelGGL(kern, grid, block, shm, s, a, NS, g_ring_debug, ring_fixcap(a.g));                           \
+        hipLaunchKernelGGL(kern, grid, block, shm, s, a, NS, debug, ring_fixcap(a.g));                           \
     } while (0)
     // (a batch with a column of more than three zones: the instantiation that tests every boundary of the zone table, ZoneRows<true>)
 #define SOSRT_RING_LAUNCH(ACC_, SAVED_)                                                                        \
@@ -743,7 +743,7 @@ void launch_p(hipStream_t s, dim3 grid, dim3 block, const TransportArgs& a, int 
         static PerDeviceOnce big_lds;
         if (big_lds.first())
             hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRingLdsBytes);
-        hipLaunchKernelGGL(kern, grid, block, shm, s, a, NS, g_ring_debug, ring_fixcap(a.g));
+        hipLaunchKernelGGL(kern, grid, block, shm, s, a, NS, debug, ring_fixcap(a.g));
     } else if (a.accumulate) {
         if (a.saved) SOSRT_RING_LAUNCH(true, true);
         else SOSRT_RING_LAUNCH(true, false);
@@ -775,9 +775,8 @@ bool transport_ring_fits(const Grid& g, int nzcap) {
     return 2 * slot_bytes + ring_extra_doubles(g, (nwc + 4) * 64, nzcap < kRingZones ? kRingZones : nzcap) * sizeof(double) <= kRingLdsBytes;
 }
 
-// slots: ring depth wanted (2..6)
-void launch_transport_ring(hipStream_t s, dim3 grid, const TransportArgs& a, int slots) {
-    if (a.slots > 0) slots = a.slots;
+// slots: ring depth wanted (2..6); debug: the kernel's dbg_arg (diagnostic builds)
+void launch_transport_ring(hipStream_t s, dim3 grid, const TransportArgs& a, int slots, int debug) {
     const int N = a.g.N;
     const int nwc = (N + 63) / 64;
     const int pieces = N <= 128 ? 1 : 2;
@@ -787,8 +786,8 @@ void launch_transport_ring(hipStream_t s, dim3 grid, const TransportArgs& a, int
     const size_t extra = ring_extra_doubles(a.g, (int)block.x, a.nzcap) * sizeof(double);
     int NS = slots < 2 ? 2 : slots;
     while (NS > 2 && NS * slot_bytes + extra > kRingLdsBytes) --NS;
-    if (pieces == 1) launch_p<1>(s, grid, block, a, NS);
-    else launch_p<2>(s, grid, block, a, NS);
+    if (pieces == 1) launch_p<1>(s, grid, block, a, NS, debug);
+    else launch_p<2>(s, grid, block, a, NS, debug);
 }
 
 }  // namespace sosrt

@@ -542,17 +542,13 @@ __global__ __launch_bounds__(64) void k_view_first_order(ViewFirstArgs a, ViewMu
 
 }  // namespace
 
-void launch_phase_rows(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
-                       const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi, int V2,
-                       const ViewMu& mu, double* rows) {
-    PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
+void launch_phase_rows(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi, const double* wphi,
+                       int nphi, int V2, const ViewMu& mu, double* rows) {
     hipLaunchKernelGGL(k_phase_rows, dim3(g.D), dim3(256), 0, s, g, w, p, cosphi, wphi, nphi, V2, mu, rows);
 }
 
-void launch_phase_p0_rows(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
-                          const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi, const double* mu0,
-                          int V2, const ViewMu& mu, double* out) {
-    PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
+void launch_phase_p0_rows(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
+                          const double* wphi, int nphi, const double* mu0, int V2, const ViewMu& mu, double* out) {
     hipLaunchKernelGGL(k_phase_p0_rows, dim3(B), dim3(256), 0, s, g, w, p, cosphi, wphi, nphi, mu0, V2, mu, out);
 }
 
@@ -565,30 +561,27 @@ static void view_modes_dispatch(int mc, F&& f) {
     else f(std::integral_constant<int, kMaxModes + 1>());
 }
 
-void launch_phase_rows_modes(hipStream_t s, const Grid& g, const double* w, int kind, double gpar, const double* tab_mu,
-                             const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
-                             int m_count, int sign_odd, int V2, const ViewMu& mu, double* rows) {
-    PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
+void launch_phase_rows_modes(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi,
+                             const double* tab, int nphi, int m_first, int m_count, int sign_odd, int V2, const ViewMu& mu,
+                             double* rows) {
     view_modes_dispatch(m_count, [&](auto k) {
         hipLaunchKernelGGL(k_phase_rows_modes<decltype(k)::value>, dim3(g.D), dim3(256), 0, s, g, w, p, cosphi, tab, nphi, m_first,
                            m_count, sign_odd, V2, mu, rows);
     });
 }
 
-void launch_phase_p0_rows_modes(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
-                                const double* tab_p, int ntab, const double* cosphi, const double* tab, int nphi, int m_first,
-                                int m_count, const double* mu0, int V2, const ViewMu& mu, double* out) {
-    PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
+void launch_phase_p0_rows_modes(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
+                                const double* tab, int nphi, int m_first, int m_count, const double* mu0, int V2,
+                                const ViewMu& mu, double* out) {
     view_modes_dispatch(m_count, [&](auto k) {
         hipLaunchKernelGGL(k_phase_p0_rows_modes<decltype(k)::value>, dim3(B), dim3(256), 0, s, g, w, B, p, cosphi, tab, nphi,
                            m_first, m_count, mu0, V2, mu, out);
     });
 }
 
-void launch_phase_p0_rows_azimuth(hipStream_t s, const Grid& g, const double* w, int B, int kind, double gpar, const double* tab_mu,
-                                  const double* tab_p, int ntab, const double* cosphi, const double* wphi, int nphi,
-                                  const double* mu0, int V2, const ViewMu& mu, int nphi_out, const double* phi, double* out) {
-    PhaseFn p{kind, gpar, tab_mu, tab_p, ntab};
+void launch_phase_p0_rows_azimuth(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
+                                  const double* wphi, int nphi, const double* mu0, int V2, const ViewMu& mu, int nphi_out,
+                                  const double* phi, double* out) {
     hipLaunchKernelGGL(k_phase_p0_rows_azimuth, dim3(B), dim3(256), 0, s, g, w, B, p, cosphi, wphi, nphi, mu0, V2, mu, nphi_out,
                        phi, out);
 }
