@@ -817,6 +817,17 @@ int sosrt_plan_ring_moments(sosrt_t* h, int batch, int live, int surface, int zo
  * and the ring kernel ran in moment mode, and all the pairs that the two-launch loop ran (either pointer nullable).  The mode also
  * stays off while some |mu| < 0.01 lane keeps its k_smallmu value, which only the solve knows (SOSRT_PLAN_NEED_SMALLMU). */
 int sosrt_ring_moments_stats(sosrt_t* h, int* moment_orders, int* orders);
+/* The moment mode of the chunk-parallel kernel (transport_scan.hip), a second and separate decision of the same plan: in an order
+ * that kernel transports in its one-workgroup or split form (not the WIDE instantiation), under the conditions of the ring
+ * kernel's mode, the contraction writes the same records and the chunk-parallel kernel expands them -- the same bits.  *on = 1 or
+ * 0; never 1 where sosrt_plan_ring_moments answers 1.  Arguments and flags as above.  Knobs, read once at sosrt_create:
+ * SOSRT_SCAN_MOMENTS=0 turns the mode off for the handle; SOSRT_SCAN_MOMENTS_MIN=n keeps it to the orders whose column group has
+ * at least n planned live columns (default 128, measured on the headline sweep: DESIGN section 3a; below it the transport's
+ * launch sits on its latency floor, where the expansion costs more than the contraction's smaller writes save). */
+int sosrt_plan_scan_moments(sosrt_t* h, int batch, int live, int surface, int zones, int cus, int flags, int* on);
+/* What the last solve did: the (column group, order) pairs that the contraction and the chunk-parallel kernel ran in moment mode,
+ * and all the pairs that the two-launch loop ran (the same count sosrt_ring_moments_stats reports; either pointer nullable). */
+int sosrt_scan_moments_stats(sosrt_t* h, int* moment_orders, int* orders);
 
 /* ---- profiling: HIP-event timing of the dominant kernels on the handle's stream ------------- */
 #define SOSRT_K_GEMM      0

@@ -65,6 +65,8 @@ int sosrt_create(int device, int L, int N, int max_batch, int max_orders, sosrt_
         h->tr.mode = strcmp(ev, "general") == 0 ? TransportKnob::General : (strcmp(ev, "ring") == 0 ? TransportKnob::Ring : (strcmp(ev, "scan") == 0 ? TransportKnob::Scan : (strcmp(ev, "auto") == 0 ? TransportKnob::Auto : TransportKnob::Fast)));
     if (const char* ev = getenv("SOSRT_SCAN_COLS")) h->tr.scan_cols = atoi(ev);
     if (const char* ev = getenv("SOSRT_RING_MOMENTS")) h->tr.ring_moments = atoi(ev) != 0;
+    if (const char* ev = getenv("SOSRT_SCAN_MOMENTS")) h->tr.scan_moments = atoi(ev) != 0;
+    if (const char* ev = getenv("SOSRT_SCAN_MOMENTS_MIN")) h->tr.scan_moments_min_live = atoi(ev);
     if (const char* ev = getenv("SOSRT_SCAN_SPLIT")) h->tr.scan_split = atoi(ev);
     if (const char* ev = getenv("SOSRT_GEMM_TAIL")) h->gemm.gemm_tail_cols = atoi(ev);
     if (const char* ev = getenv("SOSRT_GEMM_TAIL_FRAC")) h->gemm.gemm_tail_frac = atof(ev);
@@ -306,6 +308,13 @@ int sosrt_order_loop_stats(sosrt_t* h, int* launches, int* refused, long long* c
 int sosrt_ring_moments_stats(sosrt_t* h, int* moment_orders, int* orders) {
     if (!h) return fail(SOSRT_E_INVALID, "null handle");
     if (moment_orders) *moment_orders = h->tr.moment_orders;
+    if (orders) *orders = h->tr.orders;
+    return 0;
+}
+
+int sosrt_scan_moments_stats(sosrt_t* h, int* moment_orders, int* orders) {
+    if (!h) return fail(SOSRT_E_INVALID, "null handle");
+    if (moment_orders) *moment_orders = h->tr.scan_moment_orders;
     if (orders) *orders = h->tr.orders;
     return 0;
 }

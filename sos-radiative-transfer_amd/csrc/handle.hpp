@@ -222,6 +222,15 @@ struct sosrt_handle {
         int ring_moments = 1;                // SOSRT_RING_MOMENTS=0: rows of Jn always (A/B inside one process)
         double* d_mom = nullptr;             // [max_batch][L][kMomDoubles] records
         int moment_orders = 0, orders = 0;   // the last solve: (group, order) pairs transported in moment mode / by the two-launch loop (sosrt_ring_moments_stats)
+        // Moment mode of the chunk-parallel kernel: the same records, expanded by k_transport_scan's MOM
+        // instantiations, in an order that kernel transports -- a second decision, LaunchPlan::scan_moments; ring_moments and its
+        // statistics keep their meaning
+        int scan_moments = 1;                // SOSRT_SCAN_MOMENTS=0: rows of Jn always in the chunk-parallel kernel's orders
+        // SOSRT_SCAN_MOMENTS_MIN: ... and below this many planned live columns of the group.  Measured, profiles/r08_scan_moments_threshold.txt:
+        // the smallest of 8 .. 200 from which no order of the headline loses (an order with 126 live columns gains 6 us, one with 96
+        // loses 1.6: the transport's launch is on its latency floor there and pays 3 us for the expansion, the contraction gains 2)
+        int scan_moments_min_live = 128;
+        int scan_moment_orders = 0;          // the last solve: pairs the chunk-parallel kernel transported in moment mode (sosrt_scan_moments_stats)
         double* d_scan_scratch = nullptr;    // [max_batch][transport_scan_scratch_doubles()] exchange rows of the split form
         int* d_scan_sync = nullptr;          // [max_batch][2] {arrivals, flags}, zero between launches
     } tr;

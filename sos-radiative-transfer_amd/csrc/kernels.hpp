@@ -141,7 +141,7 @@ struct TransportArgs {
     int scan_split = 0;
     double* scan_scratch = nullptr;
     int* scan_sync = nullptr;
-    // ring kernel, moment mode (plan_order: LaunchPlan::moments): the plain rows' source comes as moment records
+    // ring kernel and chunk-parallel kernel, moment mode (plan_order: LaunchPlan::moments / ::scan_moments): the plain rows' source comes as moment records
     // [B][L][kMomDoubles] (jn_gemm_tile.hpp, lowrank_rows) and is expanded with the factor V of W_atm = U V; Jn then holds
     // the slab rows only.  Null: every row of Jn is read, as always.
     const double* mom = nullptr;

@@ -84,7 +84,7 @@ struct SourceOpts {
     bool all_live = false;               // the host knows every column of the launch to be live
     bool regs_tile = false;              // live columns: the register-resident 16-row tile (SOSRT_PLAN_GEMM_LIVE16_REGS)
     int dense_live_cap = 0;              // > 0: the dense tiling writes the transport's live list, of this capacity
-    bool moments = false;                // the plain rows as moment records, not rows of Jn (LaunchPlan::moments)
+    bool moments = false;                // the plain rows as moment records, not rows of Jn (LaunchPlan::moments or ::scan_moments)
 };
 
 // Jn for every row of a column group (grp < 0: the whole batch) in one launch: plain rows against W_atm, slab rows
@@ -213,6 +213,7 @@ struct LaunchPlan {
     int ol_parts = 0;                    // ... workgroups per column of its transport role
     int ol_grid = 0;                     // ... workgroups of the launch
     int moments = 0;                     // both launches of the order: moment records for the plain rows, expanded by the ring kernel
+    int scan_moments = 0;                // ... expanded by the chunk-parallel kernel (never both)
 };
 LaunchPlan plan_order(const sosrt_handle* h, const SolveShape& sh, const OrderInputs& in) {
     LaunchPlan pl;
@@ -286,6 +287,13 @@ LaunchPlan plan_order(const sosrt_handle* h, const SolveShape& sh, const OrderIn
     // instantiation) and no k_smallmu launch, which reads rows of Jn.  Anything else: rows of Jn, as always.
     pl.moments = (h->tr.ring_moments && use_lowrank(h) && use_sym(h) && !in.atm_sets && !in.saving && !pl.order_loop &&
                   pl.transport == TransportKernel::Ring && sh.nzcap <= kRingZones && !in.need_small) ? 1 : 0;
+    // The same for an order the chunk-parallel kernel transports -- a decision of its own (pl.moments keeps its meaning): the
+    // kernel's one-workgroup and split forms have the MOM instantiation, its WIDE form does not; and only while the group's
+    // planned live count is at least scan_moments_min_live -- below, the launches sit on their latency floor, the records save
+    // nothing and the expansion lands on the computing waves' instruction streams (profiles/r08_scan_moments_threshold.txt).
+    pl.scan_moments = (h->tr.scan_moments && use_lowrank(h) && use_sym(h) && !in.atm_sets && !in.saving && !pl.order_loop &&
+                       pl.transport == TransportKernel::Scan && sh.nzcap <= kRingZones && !in.need_small &&
+                       !transport_scan_wide(g) && in.known >= h->tr.scan_moments_min_live) ? 1 : 0;
     return pl;
 }
 
@@ -325,7 +333,11 @@ int transport_args(const sosrt_handle* h, const TransportCall& c, const LaunchPl
     const size_t LD = (size_t)h->L * h->D;
     // The contraction of a moment order has written records and NOT the plain rows of Jn: the ring kernel must expand them
     // (plan_order turns the mode on only where it can)
-    if (pl.moments && (kernel != TransportKernel::Ring || !c.accumulate || c.saved || sh.nzcap > kRingZones))
+    // (or the chunk-parallel kernel, in its forms that have the MOM instantiation)
+    if ((pl.moments && (kernel != TransportKernel::Ring || !c.accumulate || c.saved || sh.nzcap > kRingZones)) ||
+        (pl.scan_moments && (kernel != TransportKernel::Scan || pl.order_loop || !c.accumulate || c.saved || sh.nzcap > kRingZones ||
+                             transport_scan_wide(h->g))) ||
+        (pl.moments && pl.scan_moments))
         return fail(SOSRT_E_STATE, "internal: moment records planned for a transport launch that cannot read them");
     TransportArgs a{};
     a.g = h->g;
@@ -347,7 +359,7 @@ int transport_args(const sosrt_handle* h, const TransportCall& c, const LaunchPl
         a.scan_split = 1;
         a.scan_scratch = h->tr.d_scan_scratch + (size_t)c.b0 * transport_scan_scratch_doubles(); a.scan_sync = h->tr.d_scan_sync + 2 * c.b0;
     }
-    if (pl.moments) { a.mom = h->tr.d_mom + (size_t)c.b0 * h->L * kMomDoubles; a.lrV = h->phase.d_lrV; a.lr_rank = h->phase.lr_rank; }
+    if (pl.moments || pl.scan_moments) { a.mom = h->tr.d_mom + (size_t)c.b0 * h->L * kMomDoubles; a.lrV = h->phase.d_lrV; a.lr_rank = h->phase.lr_rank; }
     *out = a;
     return 0;
 }
@@ -425,6 +437,15 @@ int sosrt_plan_ring_moments(sosrt_t* h, int batch, int live, int surface, int zo
     LaunchPlan pl;
     if (int e = plan_query(h, batch, live, surface, zones, cus, flags, false, &ng, &pl)) return e;
     *on = pl.moments;
+    return 0;
+}
+
+int sosrt_plan_scan_moments(sosrt_t* h, int batch, int live, int surface, int zones, int cus, int flags, int* on) {
+    if (!on) return fail(SOSRT_E_INVALID, "null argument");
+    int ng = 0;
+    LaunchPlan pl;
+    if (int e = plan_query(h, batch, live, surface, zones, cus, flags, false, &ng, &pl)) return e;
+    *on = pl.scan_moments;
     return 0;
 }
 
@@ -638,7 +659,7 @@ struct SolveRun {
         }
         if (int e = ensure_matrices(h, s)) return e;
         h->ol.launches = 0; h->ol.refused = 0;
-        h->tr.moment_orders = 0; h->tr.orders = 0;
+        h->tr.moment_orders = 0; h->tr.scan_moment_orders = 0; h->tr.orders = 0;
         for (bool& u : h->ol.group_used) u = false;
         tagbase = ((++h->fld.pub_seq) & 0x3fff) << 16;      // tag of order n = tagbase + n
         live_groups = NG;
@@ -830,7 +851,7 @@ struct SolveRun {
         SourceOpts so;
         so.tail_cols = pl.tail_cols; so.pub_tag = tagbase + n - 1; so.grp = k; so.all_live = q.known == q.nb;
         so.regs_tile = pl.gemm == SOSRT_PLAN_GEMM_LIVE16_REGS; so.dense_live_cap = pl.tail_cols > 0 ? 0 : pl.live_cap;
-        so.moments = pl.moments != 0;
+        so.moments = pl.moments != 0 || pl.scan_moments != 0;
         run_source(h, q.In_1, h->fld.d_Jn, h->fld.d_active, so);
         if (g.nsmall > 0 && h->fld.need_small) {      // skipped once the device has reported that every such lane is rewritten anyway
             prof_begin(h, SOSRT_K_SMALLMU, k);
@@ -854,6 +875,7 @@ struct SolveRun {
         prof_end(h, SOSRT_K_TRANSPORT, k);
         ++h->tr.orders;
         if (pl.moments) ++h->tr.moment_orders;
+        if (pl.scan_moments) ++h->tr.scan_moment_orders;
         if (q.In_1 == d_I_out) { q.In_1 = q.In; q.In = h->fld.d_InA; }      // (after the second order: the buffer the first order left unused)
         else { double* tmp = q.In_1; q.In_1 = q.In; q.In = tmp; }
         return 0;

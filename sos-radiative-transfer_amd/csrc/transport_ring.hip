@@ -665,18 +665,6 @@ __global__ __launch_bounds__(512) void k_transport_ring(TransportArgs a, int NS,
         // (spec:403-406 has no bound): redo that sweep here, row by row (redo_upward_sweep; the ring is free by now).
         bool missing;
         if constexpr (MOM) {
-            // (its plain rows: the records again, from memory -- the sweeps are over, a load may wait here)
-            struct RowsOfMoments {
-                const double* mom_col; const double* lrV; int r, D, m, sl0, sl1;
-                __device__ __forceinline__ double operator()(int t, double jn) const {
-                    if (!(t < sl0 || t > sl1)) return jn;
-                    double V[kLowRankMax] = {0, 0, 0, 0};
-#pragma unroll
-                    for (int q = 0; q < kLowRankMax; ++q)
-                        if (q < r) V[q] = lrV[(size_t)q * D + m];
-                    return lr_expand_record(mom_col + (size_t)t * kMomDoubles, V, r);
-                }
-            };
             const RowsOfMoments jsrc{mom_col, a.lrV, lr_rank, D, N + (tid < N ? tid : 0), sl0, sl1};
             missing = redo_upward_sweep<ACC, SAVED, MZ, 0, 0, RowsOfMoments>(L, N, RB, zr, s_hd, g.mu, rJ, rE, rIn, rI, rS, Bv, ring,
                                                                             rup_v, rup_i, jsrc);

@@ -6,7 +6,7 @@ namespace sosrt {
 
 namespace {
 
-template <bool ACC, bool SAVED, bool SPLIT, int NC = 0, bool MZ = false, bool WIDE = false>
+template <bool ACC, bool SAVED, bool SPLIT, int NC = 0, bool MZ = false, bool WIDE = false, bool MOM = false>
 __global__ __launch_bounds__(768) void k_transport_scan(TransportArgs a, int fixcap) {
     // SPLIT: ceil(N / 64) workgroups per column (two at N = 128, four at N = 256), part p = blockIdx.x mod that
     const int nparts = SPLIT ? ((NC ? NC : a.g.N) + 63) >> 6 : 1;
@@ -18,7 +18,7 @@ __global__ __launch_bounds__(768) void k_transport_scan(TransportArgs a, int fix
     } else if (ACC && !a.cv.active[b]) {
         return;
     }
-    (void)transport_scan_order<ACC, SAVED, SPLIT, NC, MZ, false, WIDE>(a, fixcap, b, part, ScanFused());
+    (void)transport_scan_order<ACC, SAVED, SPLIT, NC, MZ, false, WIDE, MOM>(a, fixcap, b, part, ScanFused());
 }
 
 // shapes of the split form that take its WIDE instantiation (transport_scan_body.hpp): odd N, N > 256, more than 64 chunks per sweep
@@ -54,9 +54,10 @@ void launch_scan_t(hipStream_t s, dim3 grid, const TransportArgs& a) {
     const int nwc = SPLIT ? 1 : (a.g.N + 63) / 64;
     const dim3 block((nwc * C::SW + NLOAD) * 64);
     const size_t shm = scan_lds_bytes<SPLIT>(a.g, a.nzcap);
-#define SOSRT_SCAN_LAUNCH_Z(ACC_, SAVED_, NC_, MZ_)                                                            \
+#define SOSRT_SCAN_LAUNCH_Z(ACC_, SAVED_, NC_, MZ_) SOSRT_SCAN_LAUNCH_M(ACC_, SAVED_, NC_, MZ_, false)
+#define SOSRT_SCAN_LAUNCH_M(ACC_, SAVED_, NC_, MZ_, MOM_)                                                      \
     do {                                                                                                       \
-        auto kern = k_transport_scan<ACC_, SAVED_, SPLIT, NC_, MZ_>;                                           \
+        auto kern = k_transport_scan<ACC_, SAVED_, SPLIT, NC_, MZ_, false, MOM_>;                              \
         static PerDeviceOnce big_lds;                                                                                 \
         if (big_lds.first()) {                                                                                        \
             hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
@@ -72,7 +73,12 @@ void launch_scan_t(hipStream_t s, dim3 grid, const TransportArgs& a) {
         else SOSRT_SCAN_LAUNCH_Z(ACC_, SAVED_, 0, false);                                                      \
     } while (0)
     static const bool kFixN = !(getenv("SOSRT_SCAN_NC") && atoi(getenv("SOSRT_SCAN_NC")) == 0);      // (A/B: 0 = the generic instantiation)
-    if (a.accumulate) {
+    if (a.mom) {
+        // moment mode (plan_order turns it on only for these launches): accumulating, no saved orders, up to three zones
+        if (SPLIT && kFixN && a.g.N == 128) SOSRT_SCAN_LAUNCH_M(true, false, SPLIT ? 128 : 0, false, true);
+        else if (SPLIT && kFixN && a.g.N == 256) SOSRT_SCAN_LAUNCH_M(true, false, SPLIT ? 256 : 0, false, true);
+        else SOSRT_SCAN_LAUNCH_M(true, false, 0, false, true);
+    } else if (a.accumulate) {
         if (a.saved) SOSRT_SCAN_LAUNCH(true, true);
         else if (SPLIT && kFixN && a.nzcap <= kRingZones && a.g.N == 128) SOSRT_SCAN_LAUNCH_N(true, false, SPLIT ? 128 : 0);
         else if (SPLIT && kFixN && a.nzcap <= kRingZones && a.g.N == 256) SOSRT_SCAN_LAUNCH_N(true, false, SPLIT ? 256 : 0);
@@ -83,6 +89,7 @@ void launch_scan_t(hipStream_t s, dim3 grid, const TransportArgs& a) {
 #undef SOSRT_SCAN_LAUNCH
 #undef SOSRT_SCAN_LAUNCH_N
 #undef SOSRT_SCAN_LAUNCH_Z
+#undef SOSRT_SCAN_LAUNCH_M
 }
 
 }  // namespace

@@ -72,6 +72,7 @@ constexpr int kScanScratch = 5 * kScanDirs + 16;           // doubles per column
 static_assert(kScanChunks * TC / 32 <= 32, "the flagged-row mask of the split form's exchange holds 32 ints: 128 chunks of TC rows");
 constexpr size_t kScanLdsBytes = 152 * 1024;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
+constexpr int kMomOut = 1 << 28;                           // moment mode: a per-lane offset beyond every record descriptor (the lane fetches nothing)
 constexpr unsigned kSpinLimit = 1u << 20;                  // (a carried value arrives within a few thousand polls)
 constexpr unsigned kFusedSpinLimit = 1u << 21;             // polls of a word another workgroup publishes (FUSED): seconds
 // NC: the number of directions per hemisphere as a compile-time constant (0: taken from the grid).  The computing waves of a lone
@@ -124,9 +125,17 @@ __device__ __forceinline__ bool fused_wait_ge(const int* p, int want, int* abort
     }
 }
 
-template <bool ACC, bool SAVED, bool SPLIT, int NC = 0, bool MZ = false, bool FUSED = false, bool WIDE = false>
+//
+// MOM (moment mode, as the ring kernel's: ACC, not SAVED, not MZ, not FUSED, not WIDE): the plain rows of Jn are not in memory.  The
+// contraction of the order wrote a record of kMomDoubles doubles per plain row instead (a.mom), and a row's elements are
+// lr_expand_record of it -- the bits the contraction would have written.  The loaders fetch a plain row's record where they would
+// fetch its row of Jn, into the start of the row's place in the stage (no instruction more per chunk); the computing waves read it
+// there, every lane the same address.  Slab rows come as rows of Jn.  Whether a row is plain is a scalar comparison with the
+// column's slab rows: once per chunk where the chunk lies inside a zone, per row in the chunks of the serial form.
+template <bool ACC, bool SAVED, bool SPLIT, int NC = 0, bool MZ = false, bool FUSED = false, bool WIDE = false, bool MOM = false>
 __device__ __forceinline__ int transport_scan_order(const TransportArgs& a, int fixcap, const int b, const int part, const ScanFused& fu) {
     static_assert(!WIDE || (SPLIT && !FUSED && NC == 0), "WIDE is an instantiation of the plain split form");
+    static_assert(!MOM || (ACC && !SAVED && !MZ && !FUSED && !WIDE), "moment mode: an accumulating order of three-zone columns, rows not saved");
     using Cfg = ScanCfg<SPLIT, WIDE>;
     constexpr int SW = Cfg::SW, NST = Cfg::NST, SROW = Cfg::SROW, STAGE = Cfg::STAGE;
     // SPLIT: ceil(N / 64) workgroups per column (two at N = 128, four at N = 256), part p
@@ -229,6 +238,11 @@ __device__ __forceinline__ int transport_scan_order(const TransportArgs& a, int 
     const __amdgpu_buffer_rsrc_t rIn = make_rsrc(a.In + (size_t)b * L * D, fbytes);
     const __amdgpu_buffer_rsrc_t rI = make_rsrc(ACC ? a.I + (size_t)b * L * D : a.In, ACC ? fbytes : 0);
     (void)rJ; (void)rE;
+    // moment mode: the slab rows [sl0, sl1] of the column -- zone 1 of a (clear, slab, clear) column; no such zone: every row is plain
+    const int sl0 = (MOM && nz == 3 && dg->mix[1]) ? dg->r0[1] : (1 << 30), sl1 = MOM ? dg->r0[2] - 1 : 0;
+    auto plain_row = [&](int t) __attribute__((always_inline)) { return MOM && (t < sl0 || t > sl1); };
+    const double* const mom_col = MOM ? a.mom + (size_t)b * L * kMomDoubles : nullptr;
+    const int lr_rank = MOM ? a.lr_rank : 0;
     const __amdgpu_buffer_rsrc_t rS = make_rsrc(SAVED ? a.saved + (size_t)b * a.saved_col_stride : a.In, SAVED ? fbytes : 0);
 
     // chunks with a zone boundary and the last chunk of each sweep: serial form (one bit per chunk of a sweep)
@@ -285,7 +299,9 @@ __device__ __forceinline__ int transport_scan_order(const TransportArgs& a, int 
     // does not go through the stage (LDS): the wave asks for its rows itself here and needs them only for its stores.
     // (clamp_t: whether rows of the chunk may fall outside the column -- the last chunk of a sweep only; a plain chunk's eight
     // row offsets are then plain additions: no measurable difference, alternating builds on one box)
-    auto take = [&](auto clamp_t, int gq, int vo_, int so0, int dso, double (&J)[TC], double (&E)[TC], double (&I)[TC], double& Jx) __attribute__((always_inline)) {
+    // (moment mode: tr0, dtr = the chunk's first row and the step to the next, V = V[q][m] of the thread's direction in this sweep)
+    auto take = [&](auto clamp_t, int gq, int vo_, int so0, int dso, double (&J)[TC], double (&E)[TC], double (&I)[TC], double& Jx, int tr0, int dtr,
+                    const double (&V)[kLowRankMax]) __attribute__((always_inline)) {
         constexpr bool CLAMP = decltype(clamp_t)::value;
         const int stg = gq % NST;
 #ifdef SOSRT_SCAN_STAMPS
@@ -299,12 +315,48 @@ __device__ __forceinline__ int transport_scan_order(const TransportArgs& a, int 
         // (a staged row holds the whole half row by direction, or -- split -- this workgroup's 64 directions by lane)
         const lds_double* st = (const lds_double*)(s_stage + (size_t)stg * STAGE + (SPLIT ? lane : (gq < NCH ? dirc_dn : dirc)));
         asm volatile("" ::: "memory");                      // (compiler only: the reads stay between the two flag accesses)
+        if constexpr (!MOM) {
 #pragma unroll
-        for (int u = 0; u < TC; ++u) {
-            J[u] = st[(0 * TC + u) * SROW];
-            E[u] = st[(1 * TC + u) * SROW];
+            for (int u = 0; u < TC; ++u) {
+                J[u] = st[(0 * TC + u) * SROW];
+                E[u] = st[(1 * TC + u) * SROW];
+            }
+            Jx = st[(2 * TC) * SROW];
+        } else {
+            // a plain row: the expansion of its record, which lies at the start of the row's place (every lane the same address)
+            const lds_double* rec = (const lds_double*)(s_stage + (size_t)stg * STAGE);
+#pragma unroll
+            for (int u = 0; u < TC; ++u) E[u] = st[(1 * TC + u) * SROW];
+            // (the run-time rank is tested once per chunk, not per term: in each arm lr_expand_record sees it as a constant and a row
+            // costs its r fmas, one product and the reads of r + 1 doubles -- with the test per term the computing waves of a
+            // launch on its latency floor paid 4 us per order instead of 3)
+            auto expand = [&](auto rank_t) __attribute__((always_inline)) {
+                constexpr int R = decltype(rank_t)::value;
+                if constexpr (!CLAMP) {
+                    // (a chunk of the chunk-local form lies inside one zone, and so does the row before it: all plain or all slab)
+#pragma unroll
+                    for (int u = 0; u < TC; ++u) J[u] = lr_expand_record(rec + (0 * TC + u) * SROW, V, R);
+                    Jx = lr_expand_record(rec + (2 * TC) * SROW, V, R);
+                } else {
+#pragma unroll
+                    for (int u = 0; u < TC; ++u) {
+                        const int t = min(max(tr0 + dtr * u, 0), L - 1);            // (the rows the loaders fetched at the ragged ends)
+                        J[u] = plain_row(t) ? lr_expand_record(rec + (0 * TC + u) * SROW, V, R) : st[(0 * TC + u) * SROW];
+                    }
+                    const int tx = min(max(tr0 - dtr, 0), L - 1);
+                    Jx = plain_row(tx) ? lr_expand_record(rec + (2 * TC) * SROW, V, R) : st[(2 * TC) * SROW];
+                }
+            };
+            if (!CLAMP && !plain_row(tr0)) {
+#pragma unroll
+                for (int u = 0; u < TC; ++u) J[u] = st[(0 * TC + u) * SROW];
+                Jx = st[(2 * TC) * SROW];
+            } else if (lr_rank == 2) expand(std::integral_constant<int, 2>{});
+            else if (lr_rank == 3) expand(std::integral_constant<int, 3>{});
+            else if (lr_rank == 1) expand(std::integral_constant<int, 1>{});
+            else if (lr_rank == 4) expand(std::integral_constant<int, 4>{});
+            else expand(std::integral_constant<int, 0>{});
         }
-        Jx = st[(2 * TC) * SROW];
         asm volatile("" ::: "memory");
         if (lane == 0) l_taken[stg * nwc + lg] = gq + 1;
         // (requested here, after the stage has been taken: asked for before the wait for the stage -- more lead time on paper --
@@ -351,22 +403,63 @@ __device__ __forceinline__ int transport_scan_order(const TransportArgs& a, int 
                 const int uu = u + hl;
                 const int row = up ? max(t0 - uu, 0) : min(t0 + uu, L - 1);
                 const int vo = vl + row * RB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (0 * TC + u) * SROW), 16, vo, half, 0, LDX);
+                if constexpr (MOM) {
+                    // The two rows' records are 64 bytes apart in a.mom (or, clamped at a ragged end, the same one): one descriptor
+                    // from the lower record to the end of the upper, the row's record chosen by the per-lane offset (a scalar
+                    // offset would count against the range); lanes 4 .. 31 of either half are out of range and fetch nothing.
+                    // A pair with one plain and one slab row (a zone boundary between them): each half by itself.
+                    const int ra = up ? max(t0 - u, 0) : min(t0 + u, L - 1), rb = up ? max(t0 - u - 1, 0) : min(t0 + u + 1, L - 1);
+                    const bool pa = plain_row(ra), pb = plain_row(rb);
+                    const int rlo = min(ra, rb);
+                    const __amdgpu_buffer_rsrc_t rX = make_rsrc(mom_col + (size_t)rlo * kMomDoubles, (max(ra, rb) - rlo + 1) * kMomDoubles * 8);
+                    const int vm = (lane & 31) < 4 ? (row - rlo) * (kMomDoubles * 8) + vl : kMomOut;
+                    if (pa && pb) {
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_t)(dst + (0 * TC + u) * SROW), 16, vm, 0, 0, 0);
+                    } else if (!pa && !pb) {
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (0 * TC + u) * SROW), 16, vo, half, 0, 0);
+                    } else if ((hl == 0) == pa) {
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_t)(dst + (0 * TC + u) * SROW), 16, vm, 0, 0, 0);
+                    } else {
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (0 * TC + u) * SROW), 16, vo, half, 0, 0);
+                    }
+                } else {
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (0 * TC + u) * SROW), 16, vo, half, 0, LDX);
+                }
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rE, (lds_ptr_t)(dst + (1 * TC + u) * SROW), 16, vo, half, 0, 0);
             }
             const int rx = up ? min(t0 + 1, L - 1) : max(t0 - 1, 0);     // the row before the chunk (unused by the first chunk)
-            if (lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (2 * TC) * SROW), 16, vl, rx * RB + half, 0, LDX);
+            if constexpr (MOM) {
+                const bool px = plain_row(rx);
+                const __amdgpu_buffer_rsrc_t rX = make_rsrc(px ? mom_col + (size_t)rx * kMomDoubles : a.Jn + (size_t)b * L * D, px ? kMomDoubles * 8 : fbytes);
+                if (lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_t)(dst + (2 * TC) * SROW), 16, px ? vl : vl + rx * RB + half, 0, 0, 0);
+            } else if (lane < 32) {
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (2 * TC) * SROW), 16, vl, rx * RB + half, 0, LDX);
+            }
         } else {
             const int vo = lane * 16;
 #pragma unroll
             for (int u = 0; u < TC; ++u) {
                 const int row = up ? max(t0 - u, 0) : min(t0 + u, L - 1);
                 const int so = row * RB + half;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (0 * TC + u) * SROW), 16, vo, so, 0, LDX);
+                if constexpr (MOM) {
+                    // a plain row: its record through a descriptor that starts at the record and ends behind it (lanes 4 .. 63 are out
+                    // of range and fetch nothing; a scalar offset would count against the range), as in the ring kernel
+                    const bool pr = plain_row(row);
+                    const __amdgpu_buffer_rsrc_t rX = make_rsrc(pr ? mom_col + (size_t)row * kMomDoubles : a.Jn + (size_t)b * L * D, pr ? kMomDoubles * 8 : fbytes);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_t)(dst + (0 * TC + u) * SROW), 16, vo, pr ? 0 : so, 0, 0);
+                } else {
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (0 * TC + u) * SROW), 16, vo, so, 0, LDX);
+                }
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rE, (lds_ptr_t)(dst + (1 * TC + u) * SROW), 16, vo, so, 0, 0);
             }
             const int rx = up ? min(t0 + 1, L - 1) : max(t0 - 1, 0);     // the row before the chunk (unused by the first chunk)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (2 * TC) * SROW), 16, vo, rx * RB + half, 0, LDX);
+            if constexpr (MOM) {
+                const bool px = plain_row(rx);
+                const __amdgpu_buffer_rsrc_t rX = make_rsrc(px ? mom_col + (size_t)rx * kMomDoubles : a.Jn + (size_t)b * L * D, px ? kMomDoubles * 8 : fbytes);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_t)(dst + (2 * TC) * SROW), 16, vo, px ? 0 : rx * RB + half, 0, 0);
+            } else {
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rJ, (lds_ptr_t)(dst + (2 * TC) * SROW), 16, vo, rx * RB + half, 0, LDX);
+            }
         }
     };
     // Loader `grp` carries the chunks g = grp, grp + SW, ... of both sweeps.  Chunk g goes into stage g mod NST once every
@@ -393,6 +486,15 @@ __device__ __forceinline__ int transport_scan_order(const TransportArgs& a, int 
     int g_next = grp;                                           // (loaders)
 
     const double mu_up = (valid && dir > 0) ? g.mu[N + dirc] : 1.0;
+    // moment mode: V[q][m] of this thread's downward and upward direction (loaded here: no global load may follow the first store)
+    double Vdn[kLowRankMax] = {0, 0, 0, 0}, Vup[kLowRankMax] = {0, 0, 0, 0};
+    if constexpr (MOM) {
+        if (!loader) {
+#pragma unroll
+            for (int q = 0; q < kLowRankMax; ++q)
+                if (q < lr_rank) { Vdn[q] = a.lrV[(size_t)q * D + dirc_dn]; Vup[q] = a.lrV[(size_t)q * D + N + dirc]; }
+        }
+    }
     // Transposed work items for the two mu -> 0 treatments: lane = 8 * (row of the chunk) + (position).
     const int uT = lane >> 3, pT = lane & 7;
     const double muT = (pT + 1 < N) ? g.mu[N + pT + 1] : 1.0;          // upward direction N + pT + 1
@@ -466,7 +568,7 @@ __device__ __forceinline__ int transport_scan_order(const TransportArgs& a, int 
             const int t0 = q * TC;
             double Jc[TC], Ec[TC], Ic[TC], Jx_;
             SCAN_CB(q);
-            take(special_t, q, vo, t0 * RB, RB, Jc, Ec, Ic, Jx_);
+            take(special_t, q, vo, t0 * RB, RB, Jc, Ec, Ic, Jx_, t0, 1, Vdn);
             SCAN_T0();
             const double Jprev = q > 0 ? Jx_ : 0.0;
             // extrapolation table of the zone (In_limit:113-141 as a linear map): chunk-local copies
@@ -794,7 +896,7 @@ __device__ __forceinline__ int transport_scan_order(const TransportArgs& a, int 
             const int t0 = L - 1 - j * TC;
             double Jc[TC], Ec[TC], Ic[TC], Jx_;
             SCAN_CB(NCH + j);
-            take(special_t, NCH + j, vo, t0 * RB, -RB, Jc, Ec, Ic, Jx_);
+            take(special_t, NCH + j, vo, t0 * RB, -RB, Jc, Ec, Ic, Jx_, t0, -1, Vup);
             SCAN_T0();
             const double Jnext = j > 0 ? Jx_ : 0.0;
             double cc[TC], v[TC];
@@ -1103,8 +1205,15 @@ __device__ __forceinline__ int transport_scan_order(const TransportArgs& a, int 
         // (one workgroup per column: thread tid < N holds direction tid; split: from the surface row, specular or none)
         const double U0 = SPLIT ? ((act && surface == SOSRT_SURFACE_SPECULAR) ? rho * s_sfc[N - 1 - tid] : 0.0) : Bv;
         __syncthreads();
-        const bool missing = redo_upward_sweep<ACC, SAVED, MZ, LDX, STX>(L, N, RB, zr, s_hd, g.mu, rJ, rE, rIn, rI, rS, U0,
-                                                            s_stage, rup_v, rup_i);
+        bool missing;
+        if constexpr (MOM) {
+            const RowsOfMoments jsrc{mom_col, a.lrV, lr_rank, D, N + (tid < N ? tid : 0), sl0, sl1};
+            missing = redo_upward_sweep<ACC, SAVED, MZ, LDX, STX, RowsOfMoments>(L, N, RB, zr, s_hd, g.mu, rJ, rE, rIn, rI, rS, U0,
+                                                                                  s_stage, rup_v, rup_i, jsrc);
+        } else {
+            missing = redo_upward_sweep<ACC, SAVED, MZ, LDX, STX>(L, N, RB, zr, s_hd, g.mu, rJ, rE, rIn, rI, rS, U0,
+                                                                   s_stage, rup_v, rup_i);
+        }
         if (missing) {                                                  // the reference raises IndexError (spec:404)
             if (tid == 0) {
                 a.cv.status[b] = SOSRT_COL_INDEXERROR;

@@ -143,7 +143,9 @@ __device__ __forceinline__ double lr_expand(const double (&M)[kLowRankMax], cons
     return ca * o;
 }
 // ... from a row's moment record {M_0 .. M_3, ca, padding} (kMomDoubles doubles, in LDS or in memory; every lane the same address)
-__device__ __forceinline__ double lr_expand_record(const double* rec, const double (&V)[kLowRankMax], int r) {
+// (Ptr: a generic pointer, or an explicit LDS pointer where the caller must not issue FLAT accesses: transport_scan_body.hpp)
+template <class Ptr>
+__device__ __forceinline__ double lr_expand_record(Ptr rec, const double (&V)[kLowRankMax], int r) {
     const double M[kLowRankMax] = {rec[0], rec[1], rec[2], rec[3]};
     return lr_expand(M, V, r, rec[4]);
 }
@@ -334,6 +336,19 @@ __device__ SOSRT_HELPER_INLINE bool finish_flagged_rows(const int* s_nf, int L, 
 // moment mode, the expansion of the row's moment record where the row is plain.
 struct RowsOfJn {
     __device__ __forceinline__ double operator()(int, double jn) const { return jn; }
+};
+// (its plain rows: the records again, from memory -- the sweeps are over, a load may wait here; [sl0, sl1]: the column's slab rows;
+// m: the thread's upward direction)
+struct RowsOfMoments {
+    const double* mom_col; const double* lrV; int r, D, m, sl0, sl1;
+    __device__ __forceinline__ double operator()(int t, double jn) const {
+        if (!(t < sl0 || t > sl1)) return jn;
+        double V[kLowRankMax] = {0, 0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < kLowRankMax; ++q)
+            if (q < r) V[q] = lrV[(size_t)q * D + m];
+        return lr_expand_record(mom_col + (size_t)t * kMomDoubles, V, r);
+    }
 };
 constexpr int kRedoRows = 8;
 template <bool ACC, bool SAVED, bool MZ, int LDX = 0, int STX = 0, class JSrc = RowsOfJn>

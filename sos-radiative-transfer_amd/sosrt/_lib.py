@@ -48,6 +48,8 @@ SIGNATURES = {
     "sosrt_plan_launch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, _ip]),
     "sosrt_plan_ring_moments": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, _ip]),
     "sosrt_ring_moments_stats": (c_int, [c_void_p, _ip, _ip]),
+    "sosrt_plan_scan_moments": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, _ip]),
+    "sosrt_scan_moments_stats": (c_int, [c_void_p, _ip, _ip]),
     "sosrt_set_first_order": (c_int, [c_void_p, c_int]),
     "sosrt_set_grid": (c_int, [c_void_p, c_void_p]),
     "sosrt_set_phase": (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -841,6 +841,24 @@ class Solver:
         check(lib().sosrt_ring_moments_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
+    def plan_scan_moments(self, batch, live, surface="specular", zones=3, cus=0, saved_orders=False, atm_sets=False,
+                          need_smallmu=False):
+        """Whether an order of `batch` columns with `live` of its first group live runs in the chunk-parallel kernel's moment mode
+        (sosrt_plan_scan_moments: a second decision of the plan plan_ring_moments asks); host only."""
+        sf = {"none": _lib.SURFACE_NONE, "specular": _lib.SURFACE_SPECULAR, "lambertian": _lib.SURFACE_LAMBERTIAN,
+              "lambertian_readme": _lib.SURFACE_LAMBERTIAN_README}[surface]
+        on = ctypes.c_int(0)
+        flags = (1 if saved_orders else 0) | (2 if atm_sets else 0) | (4 if need_smallmu else 0)
+        check(lib().sosrt_plan_scan_moments(self._h, int(batch), int(live), sf, int(zones), int(cus), flags, ctypes.byref(on)))
+        return bool(on.value)
+
+    def scan_moments_stats(self):
+        """(the (column group, order) pairs of the last solve that ran in the chunk-parallel kernel's moment mode, all the pairs
+        that its two-launch loop ran)"""
+        a, b = ctypes.c_int(), ctypes.c_int()
+        check(lib().sosrt_scan_moments_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     def microbench(self, which):
         """0: FP64 MFMA TFLOP/s, 1: streaming copy GB/s, 2: FP64 FMA TFLOP/s, measured on this device."""
         r = ctypes.c_double()
