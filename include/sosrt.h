@@ -674,16 +674,41 @@ int sosrt_band_reduce_dev(sosrt_t* h, int C, int K, int M, const double* d_weigh
  *
  * Refused with SOSRT_E_INVALID, a message and nothing written: the single-slab geometry; B outside 1 .. the current columns; a
  * null pointer (d_r0, d_scale, d_status and the params of a kind without any aside); nphi < 3 or > SOSRT_BRDF_MAX_NPHI; an
- * unknown kind or a wrong nparams; RPV parameters outside rho0 > 0, k > 0, |Theta| < 1; N < 4. */
-#define SOSRT_BRDF_LAMBERTIAN 0
-#define SOSRT_BRDF_RPV        1
-#define SOSRT_BRDF_MAX_NPHI   65537
+ * unknown kind or a wrong nparams; RPV parameters outside rho0 > 0, k > 0, |Theta| < 1; N < 4.
+ *
+ * The kernel-driven Ross-Li model, rho = f_iso + f_vol K_vol + f_geo K_geo, is linear in its weights, and its
+ * two kernels depend on the geometry only: they are two more kinds, each with params = { mu_floor } in [0, 1), and the isotropic
+ * term is SOSRT_BRDF_LAMBERTIAN.  Every builder here and below takes them, with the guarantees it gives for RPV.  Both are
+ * evaluated at a' = max(a, mu_floor), b' = max(b, mu_floor) (they carry sec theta and are not meant for grazing angles; 0: as
+ * written); s = sqrt(max(0, 1 - c^2)), t = s / c per direction; cos xi = clip(a' b' + s_a s_b cos phi, -1, 1), xi = acos(cos xi):
+ *     SOSRT_BRDF_ROSS_THICK    K_vol = ((pi/2 - xi) cos xi + sin xi) / (a' + b') - pi/4
+ *     SOSRT_BRDF_LI_SPARSE_R   K_geo = O - sec + (1 + cos xi) / (2 a' b'),   sec = 1/a' + 1/b'   (h/b = 2, b/r = 1),
+ *         O = (t - sin t cos t) sec / pi,   cos t = clip(2 sqrt(D^2 + (t_a t_b sin phi)^2) / sec, -1, 1),
+ *         D^2 = (t_a - t_b)^2 + 2 t_a t_b (1 - cos phi)   (RPV's non-cancelling form),   sin^2 phi = (1 - cos phi)(1 + cos phi).
+ * Neither is clamped: they cross zero, and K_geo is negative over most of the hemisphere.
+ *
+ * sosrt_ground_source_terms_dev: the ground source of K operator terms with per-column weights,
+ *     S[b][i] = sum_k weight[b][k] c_k,   c_k = sum_j R_k(i, j) I[b][L-1][j] + r0_k[b][i] exp(-tau[b][L-1] / mu0[b])   (d_r0 NULL: none),
+ * c_k the chain of sosrt_ground_source_dev without its scale, then acc = +0 and acc = fma(weight[b][k], c_k, acc) for k ascending.
+ * So with K = 1 S has the bits of sosrt_ground_source_dev with scale = weight (up to the sign of a zero), a term of weight 0
+ * leaves the bits alone, all weights 0 give +0, and a column's bits do not depend on B.  1 <= K <= SOSRT_BRDF_MAX_TERMS.  One
+ * workgroup per column, the surface row staged once for the K operators.  Refused as sosrt_ground_source_dev refuses, and for K
+ * outside its range or a null d_weight. */
+#define SOSRT_BRDF_LAMBERTIAN  0
+#define SOSRT_BRDF_RPV         1
+#define SOSRT_BRDF_ROSS_THICK  2
+#define SOSRT_BRDF_LI_SPARSE_R 3
+#define SOSRT_BRDF_MAX_NPHI    65537
+#define SOSRT_BRDF_MAX_TERMS   4
 int sosrt_brdf_operator_dev(sosrt_t* h, int kind, const double* params /*host*/, int nparams, int nphi, double* d_R_out /*[N-1][N-1], [j][i]*/);
 int sosrt_brdf_beam_dev(sosrt_t* h, int B, int kind, const double* params /*host*/, int nparams, int nphi, const double* d_mu0 /*[B]*/,
                         double* d_r0_out /*[B][N-1]*/);
 int sosrt_ground_source_dev(sosrt_t* h, int B, const double* d_I /*[B][L][2N]*/, const double* d_tau /*[B][L]*/,
                             const double* d_R /*[N-1][N-1], [j][i]*/, const double* d_r0 /*[B][N-1] or NULL*/,
                             const double* d_scale /*[B] or NULL*/, double* d_S_out /*[B][N-1]*/);
+int sosrt_ground_source_terms_dev(sosrt_t* h, int B, int K, const double* d_I /*[B][L][2N]*/, const double* d_tau /*[B][L]*/,
+                                  const double* d_R /*[K][N-1][N-1], each [j][i]*/, const double* d_r0 /*[K][B][N-1] or NULL*/,
+                                  const double* d_weight /*[B][K]*/, double* d_S_out /*[B][N-1]*/);
 int sosrt_ground_first_order_dev(sosrt_t* h, int B, const double* d_tau /*[B][L]*/, const double* d_S /*[B][N-1]*/,
                                  double* d_G_out /*[B][L][2N]*/, int* d_status /*[B] or NULL*/);
 int sosrt_bounce_accumulate_dev(sosrt_t* h, int B, const double* d_Ik /*[B][L][2N]*/, double* d_I_total /*[B][L][2N]*/,
@@ -735,7 +760,10 @@ int sosrt_brdf_beam_modes_dev(sosrt_t* h, int B, int kind, const double* params 
  * Refused with SOSRT_E_INVALID, a message and nothing written: what the builders above refuse (single slab, B outside 1 .. the
  * current columns, kind, nparams, RPV parameters, nphi, the range of modes, N < 4, null pointers); V outside 1..SOSRT_MAX_VIEWS; a
  * mu_view that is not finite or outside [0.01, 1]; a level outside [0, L); nphi_out < 1; d_I without d_Rv or d_Rv without d_I;
- * no source at all (d_I, d_Rv and d_r0v NULL). */
+ * no source at all (d_I, d_Rv and d_r0v NULL).
+ * sosrt_view_ground_terms_dev: sosrt_view_ground_dev over K operator terms with per-column weights, S as in
+ * sosrt_ground_source_terms_dev with Rv [K][N-1][V] and r0v [K][B][V] -- the same arithmetic and the same four consequences.  It
+ * refuses what sosrt_view_ground_dev refuses, K outside 1..SOSRT_BRDF_MAX_TERMS and a null d_weight. */
 int sosrt_brdf_view_rows_modes_dev(sosrt_t* h, int kind, const double* params /*host*/, int nparams, int nphi, int m_first,
                                    int m_count, int sign_odd, int V, const double* mu_view /*host [V]*/,
                                    double* d_out /*[m_count][N-1][V]*/);
@@ -750,6 +778,11 @@ int sosrt_view_ground_dev(sosrt_t* h, int B, int V, const double* mu_view /*host
                           const double* d_r0v /*[B][V] or NULL*/, const double* d_scale /*[B] or NULL*/, int nlev,
                           const int* levels /*host [nlev]*/, int accumulate, double* d_S_out /*[B][V] or NULL*/,
                           double* d_out /*[B][nlev][2V]*/);
+int sosrt_view_ground_terms_dev(sosrt_t* h, int B, int K, int V, const double* mu_view /*host [V]*/, const double* d_tau /*[B][L]*/,
+                                const double* d_I /*[B][L][2N] or NULL*/, const double* d_Rv /*[K][N-1][V] or NULL*/,
+                                const double* d_r0v /*[K][B][V] or NULL*/, const double* d_weight /*[B][K]*/, int nlev,
+                                const int* levels /*host [nlev]*/, int accumulate, double* d_S_out /*[B][V] or NULL*/,
+                                double* d_out /*[B][nlev][2V]*/);
 
 /* ---- multi-GPU: one process per GPU, columns sharded, ONE collective at the end ------------------
  * Nothing in SOS_Aer_main_specular.py:104-458 couples columns, so the order loop never communicates; these entry

@@ -46,7 +46,23 @@ static int brdf_params(int kind, const double* params, int nparams, int nphi, Br
         for (int i = 0; i < 3; ++i) bp.p[i] = params[i];
         return 0;
     }
+    if (kind == SOSRT_BRDF_ROSS_THICK || kind == SOSRT_BRDF_LI_SPARSE_R) {
+        const char* name = kind == SOSRT_BRDF_ROSS_THICK ? "SOSRT_BRDF_ROSS_THICK" : "SOSRT_BRDF_LI_SPARSE_R";
+        if (nparams != 1) return fail(SOSRT_E_INVALID, "%s: %s takes 1 parameter mu_floor (nparams=%d)", what, name, nparams);
+        if (!params) return fail(SOSRT_E_INVALID, "%s: null params", what);
+        if (!(std::isfinite(params[0]) && params[0] >= 0 && params[0] < 1))
+            return fail(SOSRT_E_INVALID, "%s: %s mu_floor=%g: need 0 <= mu_floor < 1", what, name, params[0]);
+        bp.p[0] = params[0];
+        return 0;
+    }
     return fail(SOSRT_E_INVALID, "%s: unknown BRDF kind %d", what, kind);
+}
+
+// the number of operator terms of the two terms entry points (sosrt.h)
+static int brdf_terms(int K, const char* what) {
+    if (K < 1 || K > SOSRT_BRDF_MAX_TERMS)
+        return fail(SOSRT_E_INVALID, "%s: K=%d operator terms: must be 1..%d (SOSRT_BRDF_MAX_TERMS)", what, K, SOSRT_BRDF_MAX_TERMS);
+    return 0;
 }
 
 // the range of Fourier modes the mode builders take (sosrt.h)
@@ -141,6 +157,19 @@ int sosrt_ground_source_dev(sosrt_t* h, int B, const double* d_I, const double* 
     return 0;
 }
 
+int sosrt_ground_source_terms_dev(sosrt_t* h, int B, int K, const double* d_I, const double* d_tau, const double* d_R,
+                                  const double* d_r0, const double* d_weight, double* d_S_out) {
+    const char* what = "sosrt_ground_source_terms_dev";
+    if (int e = brdf_check(h, B, true, what)) return e;
+    if (int e = brdf_terms(K, what)) return e;
+    if (!d_I || !d_tau || !d_R || !d_weight || !d_S_out) return fail(SOSRT_E_INVALID, "%s: null argument", what);
+    HIPCHK(hipSetDevice(h->device));
+    prof_break(h);
+    launch_ground_source_terms(h->stream, h->g, B, K, scalars_of(h), d_I, d_tau, d_R, d_r0, d_weight, d_S_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int sosrt_ground_first_order_dev(sosrt_t* h, int B, const double* d_tau, const double* d_S, double* d_G_out, int* d_status) {
     if (int e = brdf_check(h, B, true, "sosrt_ground_first_order_dev")) return e;
     if (!d_tau || !d_S || !d_G_out) return fail(SOSRT_E_INVALID, "sosrt_ground_first_order_dev: null argument");
@@ -180,11 +209,13 @@ int sosrt_brdf_view_beam_azimuth_dev(sosrt_t* h, int B, int kind, const double* 
     return 0;
 }
 
-int sosrt_view_ground_dev(sosrt_t* h, int B, int V, const double* mu_view, const double* d_tau, const double* d_I,
-                          const double* d_Rv, const double* d_r0v, const double* d_scale, int nlev, const int* levels,
-                          int accumulate, double* d_S_out, double* d_out) {
-    const char* what = "sosrt_view_ground_dev";
+// the one path of sosrt_view_ground_dev (d_weight is its d_scale, nullable) and sosrt_view_ground_terms_dev (`terms`, with K)
+static int view_ground(sosrt_handle* h, const char* what, int B, bool terms, int K, int V, const double* mu_view, const double* d_tau,
+                       const double* d_I, const double* d_Rv, const double* d_r0v, const double* d_weight, int nlev,
+                       const int* levels, int accumulate, double* d_S_out, double* d_out) {
     if (int e = brdf_check(h, B, true, what)) return e;
+    if (terms)
+        if (int e = brdf_terms(K, what)) return e;
     ViewMu vm;
     if (int e = brdf_view_mu(V, mu_view, vm, what)) return e;
     if (nlev < 1 || !levels) return fail(SOSRT_E_INVALID, "%s: no levels", what);
@@ -194,18 +225,36 @@ int sosrt_view_ground_dev(sosrt_t* h, int B, int V, const double* mu_view, const
     if ((d_I == nullptr) != (d_Rv == nullptr))
         return fail(SOSRT_E_INVALID, "%s: d_I and d_Rv go together (both NULL: the beam-only call)", what);
     if (!d_I && !d_r0v) return fail(SOSRT_E_INVALID, "%s: neither a field with its rows nor beam rows: no source", what);
-    if (!d_tau || !d_out) return fail(SOSRT_E_INVALID, "%s: null argument", what);
+    if (!d_tau || !d_out || (terms && !d_weight)) return fail(SOSRT_E_INVALID, "%s: null argument", what);
     HIPCHK(hipSetDevice(h->device));
     prof_break(h);
     for (int l0 = 0; l0 < nlev; l0 += kViewLevels) {
         ViewLevels lv;
         lv.n = nlev - l0 < kViewLevels ? nlev - l0 : kViewLevels;
         for (int i = 0; i < kViewLevels; ++i) lv.t[i] = i < lv.n ? levels[l0 + i] : 0;
-        launch_view_ground(h->stream, h->g, B, V, vm, scalars_of(h), d_I, d_tau, d_Rv, d_r0v, d_scale, nlev, lv, accumulate != 0,
-                           d_S_out, d_out + (size_t)l0 * 2 * V);
+        if (terms)
+            launch_view_ground_terms(h->stream, h->g, B, K, V, vm, scalars_of(h), d_I, d_tau, d_Rv, d_r0v, d_weight, nlev, lv,
+                                     accumulate != 0, d_S_out, d_out + (size_t)l0 * 2 * V);
+        else
+            launch_view_ground(h->stream, h->g, B, V, vm, scalars_of(h), d_I, d_tau, d_Rv, d_r0v, d_weight, nlev, lv,
+                               accumulate != 0, d_S_out, d_out + (size_t)l0 * 2 * V);
         HIPCHK(hipGetLastError());
     }
     return 0;
+}
+
+int sosrt_view_ground_dev(sosrt_t* h, int B, int V, const double* mu_view, const double* d_tau, const double* d_I,
+                          const double* d_Rv, const double* d_r0v, const double* d_scale, int nlev, const int* levels,
+                          int accumulate, double* d_S_out, double* d_out) {
+    return view_ground(h, "sosrt_view_ground_dev", B, false, 0, V, mu_view, d_tau, d_I, d_Rv, d_r0v, d_scale, nlev, levels, accumulate,
+                       d_S_out, d_out);
+}
+
+int sosrt_view_ground_terms_dev(sosrt_t* h, int B, int K, int V, const double* mu_view, const double* d_tau, const double* d_I,
+                                const double* d_Rv, const double* d_r0v, const double* d_weight, int nlev, const int* levels,
+                                int accumulate, double* d_S_out, double* d_out) {
+    return view_ground(h, "sosrt_view_ground_terms_dev", B, true, K, V, mu_view, d_tau, d_I, d_Rv, d_r0v, d_weight, nlev,
+                       levels, accumulate, d_S_out, d_out);
 }
 
 }  // extern "C"

@@ -8,15 +8,20 @@
 //                          |mu_j|) with the optional (-1)^m, or the columns' mu0, stored as the beam row rho^m(a, mu0_b).  NM = 1
 //                          for a launch of one mode (the azimuth mean rho_bar is mode 0), NM = 8 otherwise; a mode's bits are the
 //                          same in both, and the same at a view cosine that is a node as at the node.
+//                          The BRDF's kind is a template argument: the dispatch on it is made once, at the launch, and a kind's
+//                          node loop holds that kind's arithmetic alone.
 //   k_ground_source        S = scale (R I_surface + r0 e^{-tau*/mu0}) (ground_chain): one workgroup per column, the surface row in
 //                          LDS, one lane per upward lane i, fused multiply-adds over j ascending (R is stored with the lanes i of
 //                          one j contiguous).
+//   k_ground_source_terms  S = sum_k weight[b][k] (R_k I_surface + r0_k e^{-tau*/mu0}) (ground_terms): the same layout, the surface
+//                          row staged once for the K operators, which every column shares.
 //   k_ground_first_order   the unscattered upward field of S with the mu -> 0+ blend of the order loop's upward sweep on every
 //                          row: one workgroup per column, one wave per row, the row in LDS for the blend's search.
 //   k_bounce_accumulate    total += Ik and the column's ratio of the two fields on the TOA-up and surface-down lanes.
 //   k_brdf_view_beam_azimuth rho(mu_view_v, mu0_b, phi) at an azimuth itself, no quadrature.
 //   k_view_ground          (section 22) the ground's unscattered radiance at the view lanes: ground_chain with the rows at the view
 //                          cosines, one exp per (level, lane); downward lanes +0; written or accumulated.
+//   k_view_ground_terms    k_view_ground with ground_terms in place of ground_chain.
 //
 // The kernels read the grid, the columns' mu0 (ColScalars) and their arguments, and write nothing but their outputs.
 #include "brdf.hpp"
@@ -57,6 +62,52 @@ __device__ __forceinline__ double rpv(const BrdfParams& bp, const Dir& a, const 
     return rho0 * minnaert * F * (1.0 + (1.0 - rho0) / (1.0 + G));
 }
 
+// The two kernels of the Ross-Li model (sosrt.h), at directions already floored (pair_setup).  cos xi of the phase angle is
+// clamped for acos; both are symmetric in (a, b) as written.
+__device__ __forceinline__ double cos_xi(const Dir& a, const Dir& b, double cphi) {
+    return fmin(1.0, fmax(-1.0, a.c * b.c + a.s * b.s * cphi));
+}
+// SOSRT_BRDF_ROSS_THICK: ((pi/2 - xi) cos xi + sin xi) / (a + b) - pi/4; inv_sum = 1 / (a + b)
+__device__ __forceinline__ double ross_thick(const Dir& a, const Dir& b, double inv_sum, double cphi) {
+    const double cx = cos_xi(a, b, cphi), xi = acos(cx);
+    return ((0.5 * kPi - xi) * cx + sin(xi)) * inv_sum - 0.25 * kPi;
+}
+// SOSRT_BRDF_LI_SPARSE_R with h/b = 2, b/r = 1: O - sec + (1 + cos xi) / (2 a b), O = (t - sin t cos t) sec / pi, cos t = 2
+// sqrt(D^2 + (tan a tan b sin phi)^2) / sec; sec = 1/a + 1/b.  D^2 in RPV's non-cancelling form, and sin^2 phi = hav (2 - hav)
+// from the same input, a product of two non-negative numbers.
+__device__ __forceinline__ double li_sparse_r(const Dir& a, const Dir& b, double sec, double cphi, double hav) {
+    const double cx = cos_xi(a, b, cphi);
+    const double dt = a.t - b.t, tt = a.t * b.t;
+    const double D2 = fmax(0.0, dt * dt + 2.0 * tt * hav);
+    const double ct = fmin(1.0, fmax(-1.0, 2.0 * sqrt(D2 + (tt * tt) * (hav * (2.0 - hav))) / sec));
+    const double t = acos(ct);
+    const double O = (t - sin(t) * ct) * sec / kPi;
+    return O - sec + 0.5 * (1.0 + cx) / (a.c * b.c);
+}
+
+// What a pair (a, b) computes once, before its azimuth nodes: the two directions (the Ross-Li kernels': floored at p[0]) and one
+// number `pre` of the kind's: RPV's Minnaert factor, 1 / (a + b) of Ross-Thick, sec of Li-Sparse.
+template <int KIND>
+__device__ __forceinline__ void pair_setup(const BrdfParams& bp, double ca, double cb, Dir& a, Dir& b, double& pre) {
+    if constexpr (KIND == SOSRT_BRDF_ROSS_THICK || KIND == SOSRT_BRDF_LI_SPARSE_R) {
+        a = make_dir(fmax(ca, bp.p[0]));
+        b = make_dir(fmax(cb, bp.p[0]));
+        pre = KIND == SOSRT_BRDF_ROSS_THICK ? 1.0 / (a.c + b.c) : 1.0 / a.c + 1.0 / b.c;
+    } else {
+        a = make_dir(ca);
+        b = make_dir(cb);
+        pre = KIND == SOSRT_BRDF_RPV ? pow(a.c * b.c * (a.c + b.c), bp.p[1] - 1.0) : 1.0;
+    }
+}
+// rho(a, b, phi) of kind KIND
+template <int KIND>
+__device__ __forceinline__ double brdf_value(const BrdfParams& bp, const Dir& a, const Dir& b, double pre, double cphi, double hav) {
+    if constexpr (KIND == SOSRT_BRDF_RPV) return rpv(bp, a, b, pre, cphi, hav);
+    else if constexpr (KIND == SOSRT_BRDF_ROSS_THICK) return ross_thick(a, b, pre, cphi);
+    else if constexpr (KIND == SOSRT_BRDF_LI_SPARSE_R) return li_sparse_r(a, b, pre, cphi, hav);
+    else return 1.0;
+}
+
 // ---- the BRDF's Fourier modes in azimuth (DESIGN sections 20 to 22; mode 0 is the azimuth mean) ----
 // cos(m phi_q) on the nphi nodes phi_q = pi q / (nphi - 1): the integer product m q reduced modulo the 2 (nphi - 1) nodes of the
 // full circle and folded onto [0, pi], so that m = 0 gives 1, node nphi - 1 gives (-1)^m and a quarter turn gives 0, all exactly.
@@ -77,13 +128,14 @@ __device__ __forceinline__ double mode_cos(int m, int q, int nphi, double h) {
 // weight of the node times cos(m phi) for a chunk of nodes.  With m = 0 the weight times 1 is the weight: mode 0 is the plain
 // trapezoid sum, the azimuth mean.  Every thread of the workgroup calls this (the chunk loop holds barriers); `live` says
 // whether the lane has a pair.
-template <int NM>
+template <int NM, int KIND>
 __device__ __forceinline__ void azimuth_modes(const BrdfParams& bp, bool live, double ca, double cb, int nphi, int m0, int nm,
                                               double* s_cos, double (&acc)[NM]) {
     double* s_hav = s_cos + kPhiChunk;
     double* s_wc = s_cos + 2 * kPhiChunk;                    // [NM][kPhiChunk]
-    const Dir a = make_dir(ca), b = make_dir(cb);
-    const double minnaert = bp.kind == SOSRT_BRDF_RPV ? pow(a.c * b.c * (a.c + b.c), bp.p[1] - 1.0) : 1.0;
+    Dir a, b;
+    double pre;
+    pair_setup<KIND>(bp, ca, cb, a, b, pre);
     const double h = 1.0 / (nphi - 1);
 #pragma unroll
     for (int k = 0; k < NM; ++k) acc[k] = 0;
@@ -101,7 +153,7 @@ __device__ __forceinline__ void azimuth_modes(const BrdfParams& bp, bool live, d
         __syncthreads();
         if (live) {
             for (int q = 0; q < nq; ++q) {
-                const double v = bp.kind == SOSRT_BRDF_RPV ? rpv(bp, a, b, minnaert, s_cos[q], s_hav[q]) : 1.0;
+                const double v = brdf_value<KIND>(bp, a, b, pre, s_cos[q], s_hav[q]);
 #pragma unroll
                 for (int k = 0; k < NM; ++k) acc[k] = fma(s_wc[k * kPhiChunk + q], v, acc[k]);
             }
@@ -118,8 +170,8 @@ __device__ __forceinline__ double flux_weight(const Grid& g, int j) {
 // The modes m0 .. m0 + nm - 1 (nm <= NM) of every pair (first, second) of directions, out [nm][nSecond][nFirst].  First: the
 // view cosines vm.s[0 .. V-1], or with V = 0 the grid's upward nodes mu[N+1 ..].  Second: the columns' mu0[0 .. B-1], stored as
 // rho^m itself, or with mu0 = nullptr the grid's downward nodes |mu_j|, stored as 2 w_j |mu_j| rho^m, mode m as (-1)^m of it
-// where sign_odd.  A lane past the pairs stays for the barriers of the node loop.
-template <int NM>
+// where sign_odd.  A lane past the pairs stays for the barriers of the node loop.  KIND: bp.kind, the launch's choice.
+template <int NM, int KIND>
 __global__ __launch_bounds__(256) void k_brdf_pairs(Grid g, ViewMu vm, int V, int B, BrdfParams bp, int nphi, int m0, int nm,
                                                     int sign_odd, const double* __restrict__ mu0, double* __restrict__ out) {
     __shared__ double s_cos[(2 + NM) * kPhiChunk];
@@ -131,7 +183,7 @@ __global__ __launch_bounds__(256) void k_brdf_pairs(Grid g, ViewMu vm, int V, in
     const int second = live ? (int)(idx / nFirst) : 0, first = live ? (int)(idx - (long long)second * nFirst) : 0;
     const double a = V ? vm.s[first] : g.mu[N + 1 + first], b = mu0 ? mu0[second] : -g.mu[second];
     double rb[NM];
-    azimuth_modes<NM>(bp, live, a, b, nphi, m0, nm, s_cos, rb);
+    azimuth_modes<NM, KIND>(bp, live, a, b, nphi, m0, nm, s_cos, rb);
     if (live) {
         const double w = mu0 ? 0.0 : flux_weight(g, second);
 #pragma unroll
@@ -174,6 +226,39 @@ __global__ __launch_bounds__(1024) void k_ground_source(Grid g, int B, ColScalar
     if (i >= M) return;
     S_all[(size_t)b * M + i] = ground_chain(R, M, i, s_I, M, r0 ? r0 + (size_t)b * M + i : nullptr, tau_all[(size_t)b * L + (L - 1)],
                                             sc.mu0[b], scale ? scale + b : nullptr);
+}
+
+// S of one lane over K operator terms = sum_k weight[k] c_k, c_k the ground_chain of term k without a scale (its operator R + k
+// strideR, its beam row r0[k strideR0]): acc = +0, then acc = fma(weight[k], c_k, acc) with k ascending.  With K = 1 that is
+// round(weight c), the bits of ground_chain with scale = weight; a term of weight 0 leaves acc as it is; all weights 0 give +0.
+__device__ __forceinline__ double ground_terms(int K, const double* __restrict__ R, size_t strideR, int n, int lane, const double* s_I,
+                                               int M, const double* __restrict__ r0, size_t strideR0, double tauL, double mu0,
+                                               const double* __restrict__ weight) {
+    double acc = 0;
+    for (int k = 0; k < K; ++k) {
+        const double c = ground_chain(R ? R + k * strideR : nullptr, n, lane, s_I, M, r0 ? r0 + k * strideR0 : nullptr, tauL, mu0,
+                                      nullptr);
+        acc = fma(weight[k], c, acc);
+    }
+    return acc;
+}
+
+// k_ground_source over K terms: R [K][N-1][N-1], r0 [K][B][N-1] (nullable), weight [B][K].  The surface row is staged once; the
+// K operators are the same for every column (L2 serves them after the first), each read with the lanes i of one j contiguous.
+__global__ __launch_bounds__(1024) void k_ground_source_terms(Grid g, int B, int K, ColScalars sc, const double* __restrict__ I_all,
+                                                              const double* __restrict__ tau_all, const double* __restrict__ R,
+                                                              const double* __restrict__ r0, const double* __restrict__ weight,
+                                                              double* __restrict__ S_all) {
+    const int L = g.L, N = g.N, D = g.D, M = N - 1;
+    const int b = blockIdx.x, i = threadIdx.x;
+    if (b >= B) return;                                      // (uniform over the workgroup)
+    extern __shared__ double s_I[];                          // [N-1] the downward surface row
+    const double* row = I_all + ((size_t)b * L + (L - 1)) * D;
+    for (int j = i; j < M; j += blockDim.x) s_I[j] = row[j];
+    __syncthreads();
+    if (i >= M) return;
+    S_all[(size_t)b * M + i] = ground_terms(K, R, (size_t)M * M, M, i, s_I, M, r0 ? r0 + (size_t)b * M + i : nullptr, (size_t)B * M,
+                                            tau_all[(size_t)b * L + (L - 1)], sc.mu0[b], weight + (size_t)b * K);
 }
 
 constexpr int kGfoWaves = 4;
@@ -284,6 +369,16 @@ __global__ __launch_bounds__(256) void k_bounce_accumulate(Grid g, int B, const 
 }
 
 // ---- the ground's term at view lanes off the grid ----
+// rho(ca, cb, phi) of a Ross-Li kernel at an azimuth itself, with the inputs of the node loop: cos phi and 2 sin^2(phi / 2)
+template <int KIND>
+__device__ __forceinline__ double value_at(const BrdfParams& bp, double ca, double cb, double phi) {
+    Dir a, b;
+    double pre;
+    pair_setup<KIND>(bp, ca, cb, a, b, pre);
+    const double sh = sin(0.5 * phi);
+    return brdf_value<KIND>(bp, a, b, pre, cos(phi), 2.0 * sh * sh);
+}
+
 // rho(mu_view_v, mu0_b, phi_q) at the azimuth itself, no quadrature: one lane per (q, b, v)
 __global__ __launch_bounds__(256) void k_brdf_view_beam_azimuth(int B, ViewMu vm, int V, BrdfParams bp, const double* __restrict__ mu0,
                                                                 int nphi_out, const double* __restrict__ phi, double* __restrict__ out) {
@@ -299,8 +394,46 @@ __global__ __launch_bounds__(256) void k_brdf_view_beam_azimuth(int B, ViewMu vm
         const double minnaert = pow(da.c * db.c * (da.c + db.c), bp.p[1] - 1.0);
         const double sh = sin(0.5 * phi[q]);
         r = rpv(bp, da, db, minnaert, cos(phi[q]), 2.0 * sh * sh);
+    } else if (bp.kind == SOSRT_BRDF_ROSS_THICK) {
+        r = value_at<SOSRT_BRDF_ROSS_THICK>(bp, vm.s[v], mu0[b], phi[q]);
+    } else if (bp.kind == SOSRT_BRDF_LI_SPARSE_R) {
+        r = value_at<SOSRT_BRDF_LI_SPARSE_R>(bp, vm.s[v], mu0[b], phi[q]);
     }
     out[idx] = r;
+}
+
+// k_view_ground over K terms (ground_terms): Rv [K][N-1][V], r0v [K][B][V], weight [B][K]
+__global__ __launch_bounds__(kMaxViews) void k_view_ground_terms(Grid g, int B, int K, int V, ViewMu vm, ColScalars sc,
+                                                                 const double* __restrict__ I_all, const double* __restrict__ tau_all,
+                                                                 const double* __restrict__ Rv, const double* __restrict__ r0v,
+                                                                 const double* __restrict__ weight, int nlev_all, ViewLevels lv,
+                                                                 int accumulate, double* __restrict__ S_out, double* __restrict__ out) {
+    const int L = g.L, D = g.D, M = g.N - 1;
+    const int b = blockIdx.x, v = threadIdx.x;
+    if (b >= B) return;                                      // (uniform over the workgroup)
+    extern __shared__ double s_I[];                          // [N-1] the downward surface row
+    if (I_all) {
+        const double* row = I_all + ((size_t)b * L + (L - 1)) * D;
+        for (int j = v; j < M; j += blockDim.x) s_I[j] = row[j];
+    }
+    __syncthreads();
+    if (v >= V) return;
+    const double* tau = tau_all + (size_t)b * L;
+    const double S = ground_terms(K, I_all ? Rv : nullptr, (size_t)M * V, V, v, s_I, M, r0v ? r0v + (size_t)b * V + v : nullptr,
+                                  (size_t)B * V, tau[L - 1], sc.mu0[b], weight + (size_t)b * K);
+    if (S_out) S_out[(size_t)b * V + v] = S;
+    const double tauL = tau[L - 1], mv = vm.s[v];
+    for (int l = 0; l < lv.n; ++l) {
+        const double dt = tauL - tau[lv.t[l]];
+        const double x = S * exp(-dt / mv);
+        double* o = out + ((size_t)b * nlev_all + l) * (2 * V);
+        if (accumulate) {
+            o[V + v] += x;
+        } else {
+            o[v] = 0.0;
+            o[V + v] = x;
+        }
+    }
 }
 
 // The ground's unscattered radiance at the view lanes: S^view of k_ground_source's ground_chain with the rows at the view cosines
@@ -345,9 +478,16 @@ void launch_brdf_pairs(hipStream_t s, const Grid& g, const ViewMu& vm, int V, in
                        int m_count, int sign_odd, const double* mu0, double* out) {
     const long long n = (long long)(mu0 ? B : g.N - 1) * (V ? V : g.N - 1);
     const dim3 blocks((unsigned)((n + 255) / 256));
+    // [kind][one mode or up to kModesPerLaunch]; api_brdf.hip lets no other kind through
+    static constexpr decltype(&k_brdf_pairs<1, 0>) kernels[4][2] = {
+        {k_brdf_pairs<1, SOSRT_BRDF_LAMBERTIAN>, k_brdf_pairs<kModesPerLaunch, SOSRT_BRDF_LAMBERTIAN>},
+        {k_brdf_pairs<1, SOSRT_BRDF_RPV>, k_brdf_pairs<kModesPerLaunch, SOSRT_BRDF_RPV>},
+        {k_brdf_pairs<1, SOSRT_BRDF_ROSS_THICK>, k_brdf_pairs<kModesPerLaunch, SOSRT_BRDF_ROSS_THICK>},
+        {k_brdf_pairs<1, SOSRT_BRDF_LI_SPARSE_R>, k_brdf_pairs<kModesPerLaunch, SOSRT_BRDF_LI_SPARSE_R>},
+    };
     for (int m = 0; m < m_count; m += kModesPerLaunch) {
         const int nm = min(kModesPerLaunch, m_count - m);
-        const auto kernel = nm == 1 ? k_brdf_pairs<1> : k_brdf_pairs<kModesPerLaunch>;
+        const auto kernel = kernels[bp.kind][nm == 1 ? 0 : 1];
         hipLaunchKernelGGL(kernel, blocks, dim3(256), 0, s, g, vm, V, B, bp, nphi, m_first + m, nm, sign_odd, mu0,
                            out + (size_t)m * n);
     }
@@ -372,6 +512,20 @@ void launch_ground_source(hipStream_t s, const Grid& g, int B, ColScalars sc, co
     const int threads = (g.N - 1 + 63) / 64 * 64;
     hipLaunchKernelGGL(k_ground_source, dim3((unsigned)B), dim3(threads), (size_t)(g.N - 1) * sizeof(double), s, g, B, sc, I, tau,
                        R, r0, scale, S);
+}
+
+void launch_ground_source_terms(hipStream_t s, const Grid& g, int B, int K, ColScalars sc, const double* I, const double* tau,
+                                const double* R, const double* r0, const double* weight, double* S) {
+    const int threads = (g.N - 1 + 63) / 64 * 64;
+    hipLaunchKernelGGL(k_ground_source_terms, dim3((unsigned)B), dim3(threads), (size_t)(g.N - 1) * sizeof(double), s, g, B, K, sc, I,
+                       tau, R, r0, weight, S);
+}
+
+void launch_view_ground_terms(hipStream_t s, const Grid& g, int B, int K, int V, const ViewMu& vm, ColScalars sc, const double* I,
+                              const double* tau, const double* Rv, const double* r0v, const double* weight, int nlev_all,
+                              const ViewLevels& lv, int accumulate, double* S_out, double* out) {
+    hipLaunchKernelGGL(k_view_ground_terms, dim3((unsigned)B), dim3(kMaxViews), (size_t)(g.N - 1) * sizeof(double), s, g, B, K, V, vm,
+                       sc, I, tau, Rv, r0v, weight, nlev_all, lv, accumulate, S_out, out);
 }
 
 void launch_ground_first_order(hipStream_t s, const Grid& g, int B, const double* tau, const double* S, double* G, int* status) {

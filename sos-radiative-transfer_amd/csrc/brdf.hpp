@@ -9,7 +9,7 @@ namespace sosrt {
 
 struct BrdfParams {
     int kind;                          // SOSRT_BRDF_*
-    double p[3];                       // RPV: rho0, k, Theta
+    double p[3];                       // RPV: rho0, k, Theta; the Ross-Li kernels: mu_floor
 };
 
 // The Fourier modes m_first .. m_first + m_count - 1 in azimuth of the named BRDF, rho^m(a, b) = (1 / pi) int_0^pi rho cos(m phi)
@@ -27,6 +27,14 @@ void launch_brdf_pairs(hipStream_t s, const Grid& g, const ViewMu& vm, int V, in
 // S [B][N-1] = scale (R I[L-1][0 .. N-2] + r0 exp(-tau[L-1] / mu0)); r0, scale nullable
 void launch_ground_source(hipStream_t s, const Grid& g, int B, ColScalars sc, const double* I, const double* tau, const double* R,
                           const double* r0, const double* scale, double* S);
+// S [B][N-1] = sum_k weight[b][k] (R_k I[L-1][0 .. N-2] + r0_k[b] exp(-tau[L-1] / mu0)), k ascending in fused multiply-adds from +0;
+// R [K][N-1][N-1], r0 [K][B][N-1] (nullable), weight [B][K].  K = 1: the bits of launch_ground_source with scale = weight.
+void launch_ground_source_terms(hipStream_t s, const Grid& g, int B, int K, ColScalars sc, const double* I, const double* tau,
+                                const double* R, const double* r0, const double* weight, double* S);
+// launch_view_ground with the same sum over K terms: Rv [K][N-1][V], r0v [K][B][V], weight [B][K]
+void launch_view_ground_terms(hipStream_t s, const Grid& g, int B, int K, int V, const ViewMu& vm, ColScalars sc, const double* I,
+                              const double* tau, const double* Rv, const double* r0v, const double* weight, int nlev_all,
+                              const ViewLevels& lv, int accumulate, double* S_out, double* out);
 // G [B][L][D]: the unscattered field of S with the mu -> 0+ blend on every row; status [B] nullable
 void launch_ground_first_order(hipStream_t s, const Grid& g, int B, const double* tau, const double* S, double* G, int* status);
 // total += Ik; ratio [B]

@@ -24,7 +24,8 @@ MAX_MODES = 64
 MAX_PHASE_SETS = 64
 MAX_VIEWS = 64
 VIEW_QUAD_GRID, VIEW_QUAD_LINEAR = 0, 1
-BRDF_LAMBERTIAN, BRDF_RPV = 0, 1
+BRDF_LAMBERTIAN, BRDF_RPV, BRDF_ROSS_THICK, BRDF_LI_SPARSE_R = 0, 1, 2, 3
+BRDF_MAX_TERMS = 4
 
 _dp = POINTER(c_double)
 _ip = POINTER(c_int)
@@ -115,6 +116,8 @@ SIGNATURES = {
                                                  c_void_p]),
     "sosrt_view_ground_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_ground_source_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 6),
+    "sosrt_ground_source_terms_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 6),
+    "sosrt_view_ground_terms_dev": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 6 + [c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_ground_first_order_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 4),
     "sosrt_bounce_accumulate_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 3),
     "sosrt_comm_unique_id": (c_int, [c_void_p]),

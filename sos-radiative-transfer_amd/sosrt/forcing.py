@@ -122,8 +122,9 @@ def toa_net_flux(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, z0
     """Net flux at the top of the atmosphere, -F_down[0] - F_up[0] (crit:377-382), for arrays of
     (tauStar_aer, alb_aer).  beam='spherical' (with `earth_radius`, km): the direct beam on its slant path through spherical
     shells, in the solve and in the flux's beam terms (main.SOS_Aer_batch); `radiative_forcing` and `critical_albedo` pass
-    both keywords on.  surface='brdf' with `brdf` ('lambertian', ('rpv', rho0, k, theta) or arrays (R, r0)): the BRDF ground
-    of main.SOS_Aer_batch, grd_alb its scale; `radiative_forcing` and `critical_albedo` pass these on too."""
+    both keywords on.  surface='brdf' with `brdf` ('lambertian', ('rpv', rho0, k, theta), ('ross_li', f_iso, f_vol, f_geo[,
+    mu_floor]) or arrays (R, r0)): the BRDF ground of main.SOS_Aer_batch, grd_alb its scale; `radiative_forcing` and
+    `critical_albedo` pass these on too."""
     _beam_args(beam, earth_radius)
     if surface not in ("specular", "brdf"):
         raise ValueError("surface must be 'specular' or 'brdf' (got %r)" % (surface,))

@@ -41,6 +41,8 @@ class ColumnResult:
     beam_slant: Optional[np.ndarray] = None   # [L] (beam='spherical'): slant optical depth of the direct beam at every level
     bounces: Optional[int] = None             # (surface='brdf'): ground reflections summed until the series' term fell below tol
     bounce_ratio: Optional[float] = None      # ... and the last term's share of the sum
+    black_sky_albedo: Optional[float] = None  # (brdf=('ross_li', ...)): the ground's directional-hemispherical reflectance at mu0
+    white_sky_albedo: Optional[float] = None  # ... and its bihemispherical reflectance, both on the grid's trapezoid
 
 
 @dataclass
@@ -69,6 +71,8 @@ class BatchResult:
     bounce_orders: Optional[np.ndarray] = None  # [K, B] (surface='brdf'): the orders the solve of every ground reflection ran
     I_view_ground: Optional[np.ndarray] = None          # [B, nlev, 2V] (brdf_view=True): the ground's unscattered radiance at the view lanes, a term of I_view
     I_view_azimuth_ground: Optional[np.ndarray] = None  # [B, nlev, 2V, len(view_azimuths)] the same at (lane, azimuth), a term of I_view_azimuth
+    black_sky_albedo: Optional[np.ndarray] = None  # [B] (brdf=('ross_li', ...)): the ground's directional-hemispherical reflectance at mu0
+    white_sky_albedo: Optional[np.ndarray] = None  # [B] ... and its bihemispherical reflectance, both on the grid's trapezoid
 
 
 _solvers = {}
@@ -362,13 +366,16 @@ def solve_thermal(s: Solver, tau, planck, planck_surface, emissivity=None, tol=1
 
 MAX_BOUNCES = 32
 BRDF_NPHI = 65
+ROSS_LI_MU_FLOOR = 0.17364817766693033    # cos 80 deg: the Ross-Li kernels carry sec theta and are not meant for grazing angles
 
 
 def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None, view_azimuths=None, mode_batch=False,
                mode_chunk=None, beam="plane", source="solar", first_order="coded", devices=None, save_orders=False,
                brdf_modes=False, brdf_view=False):
     """Checks of surface='brdf', made before any handle exists: None for every other surface, else a namespace (kind, params,
-    R [N-1, N-1] or None, r0 [B, N-1] or None, scale [B], modes) of the ground `brdf` with `grd_alb` as its per-column scale;
+    R [N-1, N-1] or None, r0 [B, N-1] or None, scale [B], modes; terms, weight) of the ground `brdf` with `grd_alb` as its
+    per-column scale; terms: None, or for ('ross_li', ...) the (kind, params) of its operator terms, with weight [B, K] their
+    per-column weights (DESIGN section 24);
     modes: the call is the azimuth-resolved one over the ground's Fourier modes (`brdf_modes=True` with `azimuths`); view: the
     call adds the ground's term at the view lanes (`brdf_view=True` with `view_mu`)."""
     if not isinstance(brdf_modes, (bool, np.bool_)):
@@ -384,7 +391,8 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
             raise ValueError("brdf_view belongs to surface='brdf' (with brdf= and view_mu=)")
         return None
     if brdf is None:
-        raise ValueError("surface='brdf' needs brdf: 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0)")
+        raise ValueError("surface='brdf' needs brdf: 'lambertian', ('rpv', rho0, k, theta), ('ross_li', f_iso, f_vol, f_geo[, "
+                         "mu_floor]) or the arrays (R, r0)")
     if brdf_view:
         if view_mu is None:
             raise ValueError("brdf_view=True is the view stage over the BRDF ground: give view_mu")
@@ -428,7 +436,8 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
     if scale.shape not in ((), (1,), (B,)) or not np.all(np.isfinite(scale)) or np.any(scale < 0):
         raise ValueError("grd_alb (the ground's per-column scale under surface='brdf') must be finite, >= 0 and a scalar or [B] = (%d,)" % B)
     scale = np.ascontiguousarray(np.broadcast_to(scale.reshape(-1) if scale.ndim else scale, (B,)))
-    spec = SimpleNamespace(kind=None, params=(), R=None, r0=None, scale=scale, modes=bool(brdf_modes), view=bool(brdf_view))
+    spec = SimpleNamespace(kind=None, params=(), R=None, r0=None, scale=scale, modes=bool(brdf_modes), view=bool(brdf_view),
+                           terms=None, weight=None)
     if isinstance(brdf, str):
         if brdf != "lambertian":
             raise ValueError("brdf must be 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0) (got %r)" % (brdf,))
@@ -436,9 +445,32 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
         return spec
     if not isinstance(brdf, (tuple, list)) or len(brdf) < 2:
         raise ValueError("brdf must be 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0) (got %r)" % (brdf,))
+    if isinstance(brdf[0], str) and brdf[0] == "ross_li":
+        if len(brdf) not in (4, 5):
+            raise ValueError("the Ross-Li brdf is ('ross_li', f_iso, f_vol, f_geo) or ('ross_li', f_iso, f_vol, f_geo, mu_floor) "
+                             "(got %r)" % (brdf,))
+        try:
+            f = [np.asarray(x, dtype=np.float64) for x in brdf[1:4]]
+            floor = float(brdf[4]) if len(brdf) == 5 else ROSS_LI_MU_FLOOR
+        except (TypeError, ValueError):
+            raise ValueError("the Ross-Li weights f_iso, f_vol, f_geo and mu_floor must be numbers (got %r)" % (brdf[1:],)) from None
+        if any(x.shape not in ((), (1,), (B,)) or not np.all(np.isfinite(x)) or np.any(x < 0) for x in f):
+            raise ValueError("the Ross-Li weights f_iso, f_vol, f_geo must each be finite, >= 0 and a scalar or [B] = (%d,)" % B)
+        if all(np.all(x == 0) for x in f):
+            raise ValueError("the Ross-Li weights f_iso, f_vol, f_geo are all zero: a black ground is surface='specular' with "
+                             "grd_alb=0")
+        if not (np.isfinite(floor) and 0 <= floor < 1):
+            raise ValueError("the Ross-Li mu_floor=%g: need 0 <= mu_floor < 1" % floor)
+        if np.any(scale != 1):
+            raise ValueError("brdf=('ross_li', ...) carries its amplitude in its weights: grd_alb must be omitted or 1")
+        spec.kind, spec.params = "ross_li", (floor,)
+        spec.terms = (("lambertian", ()), ("ross_thick", (floor,)), ("li_sparse_r", (floor,)))
+        spec.weight = np.ascontiguousarray(np.stack([np.broadcast_to(x.reshape(-1) if x.ndim else x, (B,)) for x in f], axis=1))
+        return spec
     if isinstance(brdf[0], str):
         if brdf[0] != "rpv" or len(brdf) != 4:
-            raise ValueError("a named brdf is 'lambertian' or ('rpv', rho0, k, theta) (got %r)" % (brdf,))
+            raise ValueError("a named brdf is 'lambertian', ('rpv', rho0, k, theta) or ('ross_li', f_iso, f_vol, f_geo[, mu_floor]) "
+                             "(got %r)" % (brdf,))
         try:
             rho0, k, theta = (float(x) for x in brdf[1:])
         except (TypeError, ValueError):
@@ -476,15 +508,53 @@ def _reflection_scratch(s: Solver, dev, B, L):
     return SimpleNamespace(d_S=f64(B, s.N - 1), d_G=f64(B, L, s.D), d_Ik=f64(B, L, s.D), d_ratio=f64(B), **i32)
 
 
-def _reflect(s: Solver, B, k, d_tau, d_total, R, r0, d_scale, buf, status, hook=None, **solve_kw):
-    """Ground reflection k >= 1, enqueued: the ground source (`R`, `d_scale`) of the downward surface row of `src`, the last term
+def _per_term(ground, dev, shape, build, axis=0, skip_iso=False):
+    """What a builder of the named BRDF `ground` fills, `build(kind, params, address)` writing a tensor of `shape`: that tensor,
+    or for a ground of operator terms (ground.terms) the terms' tensors stacked along `axis`.  skip_iso: the isotropic term is
+    not built and stays +0 (its modes m >= 1)."""
+    import torch
+    if not ground.terms:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+        build(ground.kind, ground.params, out.data_ptr())
+        return out
+    parts = []
+    for kind, params in ground.terms:
+        if skip_iso and kind == "lambertian":
+            parts.append(torch.zeros(shape, dtype=torch.float64, device=dev))
+            continue
+        parts.append(torch.empty(shape, dtype=torch.float64, device=dev))
+        build(kind, params, parts[-1].data_ptr())
+    return torch.stack(parts, dim=axis).contiguous()
+
+
+def _ground_scale(ground, dev):
+    """The per-column factor of the ground source on the device: the scale [B], or the weights [B, K] of a ground of terms."""
+    import torch
+    return torch.from_numpy(np.array(ground.scale if ground.terms is None else ground.weight, dtype=np.float64)).to(dev)
+
+
+def _view_ground(s: Solver, ground, mu_view, d_tau, levels, d_out, d_scale, **kw):
+    """`Solver.view_ground_device` for the ground `ground`, `d_scale` of `_ground_scale` (a ground of terms: the terms kernel)."""
+    if ground.terms:
+        s.view_ground_terms_device(len(ground.terms), mu_view, d_tau, levels, d_scale, d_out, **kw)
+    else:
+        s.view_ground_device(mu_view, d_tau, levels, d_out, d_scale=d_scale, **kw)
+
+
+def _reflect(s: Solver, B, k, d_tau, d_total, R, r0, d_scale, buf, status, hook=None, terms=0, **solve_kw):
+    """Ground reflection k >= 1, enqueued: the ground source (`R`, `d_scale`; terms = K > 0: the stacks `R` [K, N-1, N-1], `r0`
+    [K, B, N-1] and the weights `d_scale` [B, K], `Solver.ground_source_terms_device`) of the downward surface row of `src`, the last term
     buf.d_Ik (reflection 1: `d_total`, which holds the black solve, with the beam rows `r0`) -> `hook(k, src)`, for what reads the
     same source -> its unscattered field -> the order loop from it (`solve_kw`: what else `Solver.solve_device` takes) into buf.d_Ik,
     its orders into buf.d_nk -> d_total += buf.d_Ik, buf.d_ratio.  `status` [B] takes the ground field's, else the solve's, where 0."""
     import torch
     src = d_total if k == 1 else buf.d_Ik
-    s.ground_source_device(src.data_ptr(), d_tau.data_ptr(), R.data_ptr(), buf.d_S.data_ptr(), r0.data_ptr() if k == 1 else 0,
-                           d_scale.data_ptr(), B=B)
+    if terms:
+        s.ground_source_terms_device(terms, src.data_ptr(), d_tau.data_ptr(), R.data_ptr(), d_scale.data_ptr(), buf.d_S.data_ptr(),
+                                     r0.data_ptr() if k == 1 else 0, B=B)
+    else:
+        s.ground_source_device(src.data_ptr(), d_tau.data_ptr(), R.data_ptr(), buf.d_S.data_ptr(), r0.data_ptr() if k == 1 else 0,
+                               d_scale.data_ptr(), B=B)
     if hook is not None:
         hook(k, src)
     s.ground_first_order_device(d_tau.data_ptr(), buf.d_S.data_ptr(), buf.d_G.data_ptr(), buf.d_gst.data_ptr(), B=B)
@@ -507,6 +577,11 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
     torch tensors {"I", "n", "status", "tau", "bounces", "bounce_ratio", "bounce_orders"} instead.  n is the black solve's; a column
     still above tol at the cap has status COL_MAXORDERS, one whose ground rows fail the mu -> 0 search COL_INDEXERROR.
 
+    A ground of operator terms (spec.terms, the Ross-Li ground): the K operators and beam-row stacks are built
+    once (`_per_term`), every reflection's ground source sums them with the column's weights (`Solver.ground_source_terms_device`),
+    and "black_sky_albedo" / "white_sky_albedo" [B], sum_i 2 w_i mu_i sum_k f_k r0_k[b][i] and sum_i 2 w_i mu_i sum_j sum_k f_k
+    R_k[j][i] on the upward nodes' trapezoid, join the second value.
+
     `view` = (view_mu [V], levels) (a named BRDF only): also THE GROUND'S UNSCATTERED RADIANCE AT THE VIEW LANES,
     summed over the reflections on the same sources the ground source reads -- the beam's single reflection written once, every
     reflection's diffuse part accumulated (`Solver.view_ground_device`): "I_view_ground_beam", "I_view_ground_diffuse"
@@ -521,11 +596,11 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
     def post(up, dev, d_tau, d_I, d_n, d_st, B, p0a, p0r):
         L, M = d_tau.shape[1], s.N - 1
         f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
-        d_scale = up(spec.scale)
+        d_scale, K = _ground_scale(spec, dev), len(spec.terms or ())
         if spec.R is None:
-            d_mu0, d_R, d_r0 = up(np.broadcast_to(np.asarray(mu0, dtype=np.float64), (B,))), f64(M, M), f64(B, M)
-            s.brdf_operator_device(spec.kind, d_R.data_ptr(), spec.params, nphi)
-            s.brdf_beam_device(spec.kind, d_mu0.data_ptr(), d_r0.data_ptr(), spec.params, nphi, B=B)
+            d_mu0 = up(np.broadcast_to(np.asarray(mu0, dtype=np.float64), (B,)))
+            d_R = _per_term(spec, dev, (M, M), lambda kind, par, out: s.brdf_operator_device(kind, out, par, nphi))
+            d_r0 = _per_term(spec, dev, (B, M), lambda kind, par, out: s.brdf_beam_device(kind, d_mu0.data_ptr(), out, par, nphi, B=B))
         else:
             d_R, d_r0 = up(spec.R.T), up(spec.r0)            # (the device reads the lanes i of one j contiguously)
         buf = _reflection_scratch(s, dev, B, L)
@@ -533,16 +608,16 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
         if view is not None:
             vmu, vlev = view
             V = len(vmu)
-            d_Rv, d_r0v = f64(M, V), f64(B, V)
-            s.brdf_view_rows_modes_device(spec.kind, vmu, d_Rv.data_ptr(), 0, 1, spec.params, nphi)
-            s.brdf_view_beam_modes_device(spec.kind, d_mu0.data_ptr(), vmu, d_r0v.data_ptr(), 0, 1, spec.params, nphi, B=B)
+            d_Rv = _per_term(spec, dev, (M, V), lambda kind, par, out: s.brdf_view_rows_modes_device(kind, vmu, out, 0, 1, par, nphi))
+            d_r0v = _per_term(spec, dev, (B, V), lambda kind, par, out: s.brdf_view_beam_modes_device(kind, d_mu0.data_ptr(), vmu, out,
+                                                                                                     0, 1, par, nphi, B=B))
             d_vb, d_vd = f64(B, len(vlev), 2 * V), f64(B, len(vlev), 2 * V)
-            s.view_ground_device(vmu, d_tau.data_ptr(), vlev, d_vb.data_ptr(), d_r0v=d_r0v.data_ptr(), d_scale=d_scale.data_ptr(), B=B)
+            _view_ground(s, spec, vmu, d_tau.data_ptr(), vlev, d_vb.data_ptr(), d_scale.data_ptr(), d_r0v=d_r0v.data_ptr(), B=B)
             def view_hook(k, src):                          # reflection k's diffuse part, from the source the ground source has just read
-                s.view_ground_device(vmu, d_tau.data_ptr(), vlev, d_vd.data_ptr(), d_I=src.data_ptr(), d_Rv=d_Rv.data_ptr(),
-                                     d_scale=d_scale.data_ptr(), accumulate=k > 1, B=B)
+                _view_ground(s, spec, vmu, d_tau.data_ptr(), vlev, d_vd.data_ptr(), d_scale.data_ptr(), d_I=src.data_ptr(),
+                             d_Rv=d_Rv.data_ptr(), accumulate=k > 1, B=B)
         for k in range(1, max_bounces + 1):
-            _reflect(s, B, k, d_tau, d_I, d_R, d_r0, d_scale, buf, d_st, view_hook, d_P0_atm=p0a, d_P0_aer=p0r, tol=tol)
+            _reflect(s, B, k, d_tau, d_I, d_R, d_r0, d_scale, buf, d_st, view_hook, K, d_P0_atm=p0a, d_P0_aer=p0r, tol=tol)
             orders.append(buf.d_nk.clone())
             s.synchronize()
             ratio = buf.d_ratio.cpu().numpy()
@@ -555,6 +630,15 @@ def solve_brdf(s: Solver, tau, P0a, P0r, spec, mu0, tol=1e-4, max_bounces=MAX_BO
         out = {"bounces": torch.from_numpy(bounces).to(dev), "bounce_ratio": buf.d_ratio, "bounce_orders": torch.stack(orders)}
         if view is not None:
             out.update(I_view_ground_beam=d_vb, I_view_ground_diffuse=d_vd, I_view_ground=d_vb + d_vd)
+        if K:
+            # the albedos of the weighted ground on the grid's own quadrature, from the rows already built: 2 w_i mu_i over the
+            # upward nodes, w their trapezoid weights
+            u = s.mu[s.N + 1:]
+            w = np.empty(M)
+            w[0], w[-1], w[1:-1] = (u[1] - u[0]) / 2, (u[-1] - u[-2]) / 2, (u[2:] - u[:-2]) / 2
+            d_wmu = up(2 * w * u)
+            out.update(black_sky_albedo=torch.einsum("bk,kbi,i->b", d_scale, d_r0, d_wmu),
+                       white_sky_albedo=torch.einsum("bk,k->b", d_scale, torch.einsum("kji,i->k", d_R, d_wmu)))
         return out
 
     def epilogue(d_tau, d_I, d_zp, extra, out, B):
@@ -651,7 +735,12 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     operator and the order loop transports and scatters that ground source, until every column's term is below `tol` of the
     sum or `max_bounces` (32; a column still above has status COL_MAXORDERS).  `brdf='lambertian'`: grd_alb[b] is the albedo,
     so an albedo sweep is one batch; `brdf=('rpv', rho0, k, theta)`: Rahman-Pinty-Verstraete with its hot spot (grd_alb
-    omitted or 1); `brdf=(R, r0)`: a caller's operator R [N-1, N-1] (upward lane N+1+i from downward lane j, the flux
+    omitted or 1); `brdf=('ross_li', f_iso, f_vol, f_geo[, mu_floor])`: the kernel-driven Ross-Thick / Li-Sparse-Reciprocal model
+    rho = f_iso + f_vol K_vol + f_geo K_geo, every weight a scalar or [B] -- finite, >= 0, not all zero; the
+    three operators are built once and every column's ground source sums them with its own weights, so a batch of pixels each
+    with its own BRDF is one batch; both kernels are evaluated at max(mu, mu_floor), default ROSS_LI_MU_FLOOR = cos 80 deg (0:
+    the formulas as written); rho is not clamped and can go negative for a large f_geo; grd_alb omitted or 1; the result then
+    also has black_sky_albedo and white_sky_albedo [B] on the grid's quadrature; `brdf=(R, r0)`: a caller's operator R [N-1, N-1] (upward lane N+1+i from downward lane j, the flux
     quadrature folded in) and beam row r0 [N-1] or [B, N-1], grd_alb a plain scale.  BatchResult.bounces / bounce_ratio [B]
     / bounce_orders [K, B] (the orders of every reflection's solve); n is the black solve's.  Not with `mode_batch`,
     `beam='spherical'`, `source='thermal'`, `first_order='readme'`, `save_orders` or several `devices`; `azimuths` only with
@@ -761,7 +850,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     if raise_on_error:
         _raise_status(r.status, N)
     out = BatchResult(I=r.I, n=r.n, status=r.status, tau=tau, mu=mu, idx_up=iu, idx_down=idn, I_saved=r.I_saved, beam_slant=sigma,
-                      bounces=bx.get("bounces"), bounce_ratio=bx.get("bounce_ratio"), bounce_orders=bx.get("bounce_orders"))
+                      bounces=bx.get("bounces"), bounce_ratio=bx.get("bounce_ratio"), bounce_orders=bx.get("bounce_orders"),
+                      black_sky_albedo=bx.get("black_sky_albedo"), white_sky_albedo=bx.get("white_sky_albedo"))
     if azimuths is not None:
         mu0v = np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
         if mode_batch:
@@ -1132,14 +1222,18 @@ def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, f
 
 def _reflection_buffers(s: Solver, c: _ModeLoop, ground, bounce_orders, brdf_nphi):
     """What `_mode_reflections` reads, under c.own (called from a driver's `begin`): the operators (-1)^m R^m and beam rows r0^m of
-    the modes 1..c.M of the named BRDF `ground` on `brdf_nphi` nodes, its scale, the reflections' order counts and the buffers."""
+    the modes 1..c.M of the named BRDF `ground` on `brdf_nphi` nodes, its scale (a ground of terms: the stacks [M, K, ...] and the
+    weights), the reflections' order counts and the buffers."""
     import torch
     o, M1 = c.own, s.N - 1
-    o.d_scale = torch.from_numpy(np.array(ground.scale, dtype=np.float64)).to(c.dev)
+    o.d_scale = _ground_scale(ground, c.dev)
     o.d_orders = torch.from_numpy(np.ascontiguousarray(bounce_orders, dtype=np.int32)).to(c.dev)
-    o.d_R, o.d_r0 = (torch.empty(shape, dtype=torch.float64, device=c.dev) for shape in ((c.M, M1, M1), (c.M, c.B, M1)))
-    s.brdf_operator_modes_device(ground.kind, o.d_R.data_ptr(), 1, c.M, ground.params, brdf_nphi, sign_odd=True)
-    s.brdf_beam_modes_device(ground.kind, c.d_mu0.data_ptr(), o.d_r0.data_ptr(), 1, c.M, ground.params, brdf_nphi, B=c.B)
+    # (a ground of terms: [M, K, ...], a mode's K operators contiguous; its isotropic term has no mode m >= 1 and stays +0)
+    o.d_R = _per_term(ground, c.dev, (c.M, M1, M1), lambda kind, par, out: s.brdf_operator_modes_device(
+        kind, out, 1, c.M, par, brdf_nphi, sign_odd=True), axis=1, skip_iso=True)
+    o.d_r0 = _per_term(ground, c.dev, (c.M, c.B, M1), lambda kind, par, out: s.brdf_beam_modes_device(
+        kind, c.d_mu0.data_ptr(), out, 1, c.M, par, brdf_nphi, B=c.B), axis=1, skip_iso=True)
+    o.terms = len(ground.terms or ())
     o.buf = _reflection_scratch(s, c.dev, c.B, c.L)
 
 
@@ -1150,7 +1244,7 @@ def _mode_reflections(s: Solver, c: _ModeLoop, m, hook=None):
     o = c.own
     for k in range(1, o.d_orders.shape[0] + 1):
         s.set_order_targets(o.d_orders[k - 1].data_ptr())
-        _reflect(s, c.B, k, c.d_tau, c.d_Im, o.d_R[m - 1], o.d_r0[m - 1], o.d_scale, o.buf, c.d_status[m - 1], hook,
+        _reflect(s, c.B, k, c.d_tau, c.d_Im, o.d_R[m - 1], o.d_r0[m - 1], o.d_scale, o.buf, c.d_status[m - 1], hook, o.terms,
                  d_P0_atm=0, d_P0_aer=0)
     s.set_order_targets(c.d_target.data_ptr())
 
@@ -1243,19 +1337,18 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
         if ground is not None:
             o.d_gr = torch.from_numpy(np.ascontiguousarray(ground0)).to(dev)
             o.d_out_gr = torch.empty((B, nlev, V2, nout), dtype=torch.float64, device=dev)
-            o.d_scale = torch.from_numpy(np.array(ground.scale, dtype=np.float64)).to(dev)
+            o.d_scale = _ground_scale(ground, dev)
             if not modes_first:
-                o.d_r0phi = torch.empty((nout, B, V2 // 2), dtype=torch.float64, device=dev)
-                s.brdf_view_beam_azimuth_device(ground.kind, c.d_mu0.data_ptr(), view_mu, o.d_phi.data_ptr(), nout,
-                                                o.d_r0phi.data_ptr(), ground.params, B=B)
+                # (a ground of terms: [nout, K, B, V], the terms' values at the azimuth, summed with the weights by the terms kernel)
+                o.d_r0phi = _per_term(ground, dev, (nout, B, V2 // 2), lambda kind, par, out: s.brdf_view_beam_azimuth_device(
+                    kind, c.d_mu0.data_ptr(), view_mu, o.d_phi.data_ptr(), nout, out, par, B=B), axis=1)
         if bounce:
             _reflection_buffers(s, c, ground, bounce_orders, brdf_nphi)
-            o.d_Rv = torch.empty((M, s.N - 1, V2 // 2), dtype=torch.float64, device=dev)
-            s.brdf_view_rows_modes_device(ground.kind, view_mu, o.d_Rv.data_ptr(), 1, M, ground.params, brdf_nphi, sign_odd=True)
+            o.d_Rv = _per_term(ground, dev, (M, s.N - 1, V2 // 2), lambda kind, par, out: s.brdf_view_rows_modes_device(
+                kind, view_mu, out, 1, M, par, brdf_nphi, sign_odd=True), axis=1, skip_iso=True)
             if modes_first:
-                o.d_r0v = torch.empty((M, B, V2 // 2), dtype=torch.float64, device=dev)
-                s.brdf_view_beam_modes_device(ground.kind, c.d_mu0.data_ptr(), view_mu, o.d_r0v.data_ptr(), 1, M, ground.params,
-                                              brdf_nphi, B=B)
+                o.d_r0v = _per_term(ground, dev, (M, B, V2 // 2), lambda kind, par, out: s.brdf_view_beam_modes_device(
+                    kind, c.d_mu0.data_ptr(), view_mu, out, 1, M, par, brdf_nphi, B=B), axis=1, skip_iso=True)
         accumulate(c, 0)
 
     def accumulate(c, m):
@@ -1271,9 +1364,9 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
         # reflection k of mode m at the view lanes, from the source the ground source has just read; the beam's share only where
         # the modes carry it
         o = c.own
-        s.view_ground_device(view_mu, c.d_tau.data_ptr(), levels, o.d_gr.data_ptr(), d_I=src.data_ptr(), d_Rv=o.d_Rv[m - 1].data_ptr(),
-                             d_r0v=o.d_r0v[m - 1].data_ptr() if modes_first and k == 1 else 0, d_scale=o.d_scale.data_ptr(),
-                             accumulate=k > 1, B=c.B)
+        _view_ground(s, ground, view_mu, c.d_tau.data_ptr(), levels, o.d_gr.data_ptr(), o.d_scale.data_ptr(), d_I=src.data_ptr(),
+                     d_Rv=o.d_Rv[m - 1].data_ptr(), d_r0v=o.d_r0v[m - 1].data_ptr() if modes_first and k == 1 else 0,
+                     accumulate=k > 1, B=c.B)
 
     def step(c, m):
         o = c.own
@@ -1304,8 +1397,8 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
                 # the beam's single reflection at every azimuth itself, added to the synthesis of the diffuse part
                 d_gb = torch.empty((nout, c.B, nlev, V2), dtype=torch.float64, device=c.dev)
                 for i in range(nout):
-                    s.view_ground_device(view_mu, c.d_tau.data_ptr(), levels, d_gb[i].data_ptr(), d_r0v=o.d_r0phi[i].data_ptr(),
-                                         d_scale=o.d_scale.data_ptr(), B=c.B)
+                    _view_ground(s, ground, view_mu, c.d_tau.data_ptr(), levels, d_gb[i].data_ptr(), o.d_scale.data_ptr(),
+                                 d_r0v=o.d_r0phi[i].data_ptr(), B=c.B)
                 s.synchronize()
                 o.d_out_gr += d_gb.permute(1, 2, 3, 0)
             gr = o.d_out_gr.cpu().numpy()
@@ -1634,7 +1727,8 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
         _raise_status(r.status, N)
     return BatchResult(I=r.I, n=r.n, status=r.status, tau=np.tile(tau, (B, 1)), mu=mu, idx_up=int(r0[1]), idx_down=int(r0[2]) - 1,
                        beam_slant=sigma, bounces=bx.get("bounces"), bounce_ratio=bx.get("bounce_ratio"),
-                       bounce_orders=bx.get("bounce_orders"))
+                       bounce_orders=bx.get("bounce_orders"), black_sky_albedo=bx.get("black_sky_albedo"),
+                       white_sky_albedo=bx.get("white_sky_albedo"))
 
 
 def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=None, P_aer=None, P0_aer=None, device=0,
@@ -1671,4 +1765,6 @@ def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=Non
     return ColumnResult(I=r.I[0], I_saved=None if ground else r.I_saved[0, :n].copy(), n=n, tau=r.tau[0], mu=r.mu, idx_up=r.idx_up,
                         idx_down=r.idx_down, status=int(r.status[0]), beam_slant=None if r.beam_slant is None else r.beam_slant[0],
                         bounces=None if r.bounces is None else int(r.bounces[0]),
-                        bounce_ratio=None if r.bounce_ratio is None else float(r.bounce_ratio[0]))
+                        bounce_ratio=None if r.bounce_ratio is None else float(r.bounce_ratio[0]),
+                        black_sky_albedo=None if r.black_sky_albedo is None else float(r.black_sky_albedo[0]),
+                        white_sky_albedo=None if r.white_sky_albedo is None else float(r.white_sky_albedo[0]))

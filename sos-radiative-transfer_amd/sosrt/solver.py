@@ -465,13 +465,14 @@ class Solver:
                                           int(bool(accumulate))))
 
     # ---- BRDF ground (sosrt.h) --------------------------------------------------------
-    _BRDF_KINDS = {"lambertian": _lib.BRDF_LAMBERTIAN, "rpv": _lib.BRDF_RPV}
+    _BRDF_KINDS = {"lambertian": _lib.BRDF_LAMBERTIAN, "rpv": _lib.BRDF_RPV, "ross_thick": _lib.BRDF_ROSS_THICK,
+                   "li_sparse_r": _lib.BRDF_LI_SPARSE_R}
 
     def _brdf_pack(self, kind, params):
         """(kind, params, nparams) as the C entry points take a named BRDF"""
         k = self._BRDF_KINDS.get(kind)
         if k is None:
-            raise ValueError("BRDF kind must be 'lambertian' or 'rpv' (got %r)" % (kind,))
+            raise ValueError("BRDF kind must be 'lambertian', 'rpv', 'ross_thick' or 'li_sparse_r' (got %r)" % (kind,))
         p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64))) if np.size(params) else np.zeros(0)
         return k, _ptr(p) if p.size else None, int(p.size)
 
@@ -510,6 +511,15 @@ class Solver:
         no beam term; d_scale 0: 1.  d_R as `brdf_operator_device` writes it."""
         check(lib().sosrt_ground_source_dev(self._h, int(self.B if B is None else B), _vp(d_I), _vp(d_tau), _vp(d_R), _vp(d_r0),
                                             _vp(d_scale), _vp(d_S_out)))
+
+    def ground_source_terms_device(self, K: int, d_I: int, d_tau: int, d_R: int, d_weight: int, d_S_out: int, d_r0: int = 0,
+                                   B: Optional[int] = None):
+        """`ground_source_device` over K operator terms with per-column weights (the Ross-Li ground): d_S_out
+        [B, N-1] = sum_k weight[b, k] (R[k] I[b, L-1, 0 .. N-2] + r0[k, b] exp(-tau[b, L-1] / mu0[b])), k ascending in fused
+        multiply-adds from +0.  d_R [K, N-1, N-1], d_r0 [K, B, N-1] (0: no beam term), d_weight [B, K].  With K = 1 the bits of
+        `ground_source_device` with scale = weight; a term of weight 0 leaves the bits alone."""
+        check(lib().sosrt_ground_source_terms_dev(self._h, int(self.B if B is None else B), int(K), _vp(d_I), _vp(d_tau), _vp(d_R),
+                                                  _vp(d_r0), _vp(d_weight), _vp(d_S_out)))
 
     def ground_first_order_device(self, d_tau: int, d_S: int, d_G_out: int, d_status: int = 0, B: Optional[int] = None):
         """The unscattered upward field of the ground source d_S [B, N-1], with the mu -> 0+ blend of the order loop on every
@@ -553,6 +563,15 @@ class Solver:
         check(lib().sosrt_view_ground_dev(self._h, int(self.B if B is None else B), *self._view_pack(mu_view), _vp(d_tau), _vp(d_I),
                                           _vp(d_Rv), _vp(d_r0v), _vp(d_scale), int(lev.size), _ptr(lev), int(bool(accumulate)),
                                           _vp(d_S_out), _vp(d_out)))
+
+    def view_ground_terms_device(self, K: int, mu_view, d_tau: int, levels, d_weight: int, d_out: int, d_I: int = 0, d_Rv: int = 0,
+                                 d_r0v: int = 0, accumulate=False, d_S_out: int = 0, B: Optional[int] = None):
+        """`view_ground_device` over K operator terms with per-column weights, as `ground_source_terms_device`: d_Rv [K, N-1, V],
+        d_r0v [K, B, V], d_weight [B, K]."""
+        lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.int32)
+        check(lib().sosrt_view_ground_terms_dev(self._h, int(self.B if B is None else B), int(K), *self._view_pack(mu_view),
+                                                _vp(d_tau), _vp(d_I), _vp(d_Rv), _vp(d_r0v), _vp(d_weight), int(lev.size), _ptr(lev),
+                                                int(bool(accumulate)), _vp(d_S_out), _vp(d_out)))
 
     # ---- phase functions on the device (phase:68-292) ----------------------------
     _KINDS ={"iso": _lib.PHASE_ISO, "rayleigh": _lib.PHASE_RAYLEIGH, "hg": _lib.PHASE_HG, "table": _lib.PHASE_TABLE}
