@@ -1,6 +1,6 @@
 // Phase functions on the device: the table of SOSRT_PHASE_TABLE, Lorenz-Mie tables, the builders of P0 and
 // of the phase matrix, their Fourier modes in azimuth, order targets and the azimuth synthesis.  Host code;
-// the kernels are in kernels.hip.
+// the builders' kernels are in phase.hip, the Mie and synthesis kernels in epilogue.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -279,16 +279,66 @@ PhaseFn sosrt::phase_fn(const sosrt_handle* h, int kind, double g) {
     return p;
 }
 
+PhaseJob sosrt::phase_job(const sosrt_handle* h, int kind, double g, int mf, int mc, int nphi) {
+    PhaseJob j{};
+    j.p = phase_fn(h, kind, g);
+    j.w = h->grid.d_w;
+    j.cosphi = mc ? h->pf.d_modetab.p : h->grid.d_phi;
+    j.wq = mc ? h->pf.d_modetab.p + nphi : h->grid.d_phi + kNPhi;
+    j.nphi = mc ? nphi : kNPhi;
+    j.m_first = mf; j.m_count = mc;
+    return j;
+}
+
+namespace {
+
+// A host-pointer entry around its device entry: n doubles of output (and `extra` more of scratch behind them) are allocated, dev
+// fills them on the handle's stream, they are copied out, the stream is synchronised and the buffer freed
+template <typename F>
+int to_host(sosrt_handle* h, size_t n, size_t extra, double* out, F&& dev) {
+    hipStream_t s = h->stream;
+    double* d = nullptr;
+    if (int e = dalloc(&d, n + extra)) return e;
+    auto body = [&]() -> int {
+        if (int e = dev(d)) return e;
+        HIPCHK(hipMemcpyAsync(out, d, n * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(s);
+    hipFree(d);
+    return rc;
+}
+
+// Modes [m_first, m_first + m_count) of the matrix (d_mu0 == nullptr, out [m_count][D][D]) or of P0 (out [m_count][B][D]): mode 0
+// is the 25-node builder's output, bit for bit; the modes m >= 1 of the request come from the mode builder on nphi nodes
+int build_modes(sosrt_handle* h, int kind, double g, int m_first, int m_count, int nphi, int sign_odd, int B, const double* d_mu0,
+                double* d_out) {
+    const int mf = m_first > 0 ? m_first : 1, mc = m_first > 0 ? m_count : m_count - 1;   // modes m >= 1 of the request
+    PhaseJob j = phase_job(h, kind, g);
+    j.mu0 = d_mu0; j.B = B; j.out = d_out;
+    if (m_first == 0) launch_phase_builder(h->stream, h->g, nullptr, j);
+    if (mc > 0) {
+        if (int e = modes_table(h, nphi, mf, mc)) return e;
+        j = phase_job(h, kind, g, mf, mc, nphi);
+        j.sign_odd = sign_odd; j.mu0 = d_mu0; j.B = B;
+        j.out = d_out + (size_t)(m_count - mc) * (d_mu0 ? B : h->D) * h->D;
+        launch_phase_builder(h->stream, h->g, nullptr, j);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 int sosrt_phase_p0_dev(sosrt_t* h, int B, int kind, double g, const double* d_mu0, double* d_P0_out) {
     if (int e = phase_check(h, kind, g)) return e;
     if (B < 1 || !d_mu0 || !d_P0_out) return fail(SOSRT_E_INVALID, "bad argument");
     HIPCHK(hipSetDevice(h->device));
-    launch_phase_p0(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g), h->grid.d_phi,
-                    h->grid.d_phi + kNPhi, kNPhi, d_mu0, d_P0_out);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return build_modes(h, kind, g, 0, 1, 0, 0, B, d_mu0, d_P0_out);
 }
 
 int sosrt_phase_p0(sosrt_t* h, int B, int kind, double g, const double* mu0, double* P0_out) {
@@ -309,32 +359,14 @@ int sosrt_phase_matrix_dev(sosrt_t* h, int kind, double g, double* d_P_out) {
     if (int e = phase_check(h, kind, g)) return e;
     if (!d_P_out) return fail(SOSRT_E_INVALID, "null argument");
     HIPCHK(hipSetDevice(h->device));
-    launch_phase_matrix(h->stream, h->g, h->grid.d_w, phase_fn(h, kind, g), h->grid.d_phi,
-                        h->grid.d_phi + kNPhi, kNPhi, d_P_out);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return build_modes(h, kind, g, 0, 1, 0, 0, 0, nullptr, d_P_out);
 }
 
 int sosrt_phase_matrix(sosrt_t* h, int kind, double g, double* P_out) {
     if (int e = phase_check(h, kind, g)) return e;
     if (!P_out) return fail(SOSRT_E_INVALID, "null argument");
     HIPCHK(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    double* dP = nullptr;
-    const size_t n = (size_t)h->D * h->D;
-    if (int e = dalloc(&dP, n)) return e;
-    int rc = 0;
-    auto body = [&]() -> int {
-        launch_phase_matrix(s, h->g, h->grid.d_w, phase_fn(h, kind, g), h->grid.d_phi,
-                            h->grid.d_phi + kNPhi, kNPhi, dP);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(P_out, dP, n * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return 0;
-    };
-    rc = body();
-    hipFree(dP);
-    return rc;
+    return to_host(h, (size_t)h->D * h->D, 0, P_out, [&](double* dP) { return sosrt_phase_matrix_dev(h, kind, g, dP); });
 }
 
 }  // extern "C"
@@ -375,52 +407,19 @@ int sosrt::modes_table(sosrt_handle* h, int nphi, int mf, int mc) {
 
 extern "C" {
 
-int sosrt_phase_modes(sosrt_t* h, int kind, double g, int m_first, int m_count, int nphi, double* P_out) {
-    if (int e = modes_check(h, kind, g, m_first, m_count, nphi)) return e;
-    if (!P_out) return fail(SOSRT_E_INVALID, "null argument");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    const size_t DD = (size_t)h->D * h->D;
-    const int mf = m_first > 0 ? m_first : 1, mc = m_first > 0 ? m_count : m_count - 1;   // modes m >= 1 of the request
-    if (mc > 0)
-        if (int e = modes_table(h, nphi, mf, mc)) return e;
-    double* dP = nullptr;
-    if (int e = dalloc(&dP, m_count * DD)) return e;
-    auto body = [&]() -> int {
-        if (m_first == 0)                                  // mode 0 is the existing builder's output, bit for bit (25-point ring)
-            launch_phase_matrix(s, h->g, h->grid.d_w, phase_fn(h, kind, g), h->grid.d_phi,
-                                h->grid.d_phi + kNPhi, kNPhi, dP);
-        if (mc > 0)
-            launch_phase_modes(s, h->g, h->grid.d_w, phase_fn(h, kind, g), h->pf.d_modetab.p,
-                               h->pf.d_modetab.p + nphi, nphi, mf, mc, dP + (m_count - mc) * DD);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(P_out, dP, m_count * DD * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return 0;
-    };
-    const int rc = body();
-    hipFree(dP);
-    return rc;
-}
-
 int sosrt_phase_modes_dev(sosrt_t* h, int kind, double g, int m_first, int m_count, int nphi, int sign_odd, double* d_P_out) {
     if (int e = modes_check(h, kind, g, m_first, m_count, nphi)) return e;
     if (!d_P_out) return fail(SOSRT_E_INVALID, "null argument");
     HIPCHK(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    const size_t DD = (size_t)h->D * h->D;
-    const int mf = m_first > 0 ? m_first : 1, mc = m_first > 0 ? m_count : m_count - 1;   // modes m >= 1 of the request
-    if (mc > 0)
-        if (int e = modes_table(h, nphi, mf, mc)) return e;
-    if (m_first == 0)
-        launch_phase_matrix(s, h->g, h->grid.d_w, phase_fn(h, kind, g), h->grid.d_phi,
-                            h->grid.d_phi + kNPhi, kNPhi, d_P_out);
-    if (mc > 0)
-        launch_phase_modes(s, h->g, h->grid.d_w, phase_fn(h, kind, g), h->pf.d_modetab.p,
-                           h->pf.d_modetab.p + nphi, nphi, mf, mc, d_P_out + (m_count - mc) * DD);
-    if (sign_odd) launch_negate_odd_modes(s, DD, m_first, m_count, d_P_out);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return build_modes(h, kind, g, m_first, m_count, nphi, sign_odd, 0, nullptr, d_P_out);
+}
+
+int sosrt_phase_modes(sosrt_t* h, int kind, double g, int m_first, int m_count, int nphi, double* P_out) {
+    if (int e = modes_check(h, kind, g, m_first, m_count, nphi)) return e;
+    if (!P_out) return fail(SOSRT_E_INVALID, "null argument");
+    HIPCHK(hipSetDevice(h->device));
+    return to_host(h, (size_t)m_count * h->D * h->D, 0, P_out,
+                   [&](double* dP) { return sosrt_phase_modes_dev(h, kind, g, m_first, m_count, nphi, 0, dP); });
 }
 
 int sosrt_phase_p0_modes_dev(sosrt_t* h, int B, int kind, double g, int m_first, int m_count, int nphi, const double* d_mu0,
@@ -428,17 +427,7 @@ int sosrt_phase_p0_modes_dev(sosrt_t* h, int B, int kind, double g, int m_first,
     if (int e = modes_check(h, kind, g, m_first, m_count, nphi)) return e;
     if (B < 1 || !d_mu0 || !d_P0_out) return fail(SOSRT_E_INVALID, "bad argument");
     HIPCHK(hipSetDevice(h->device));
-    const int mf = m_first > 0 ? m_first : 1, mc = m_first > 0 ? m_count : m_count - 1;
-    if (mc > 0)
-        if (int e = modes_table(h, nphi, mf, mc)) return e;
-    if (m_first == 0)
-        launch_phase_p0(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g), h->grid.d_phi,
-                        h->grid.d_phi + kNPhi, kNPhi, d_mu0, d_P0_out);
-    if (mc > 0)
-        launch_phase_p0_modes(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g),
-                              h->pf.d_modetab.p, h->pf.d_modetab.p + nphi, nphi, mf, mc, d_mu0, d_P0_out + (size_t)(m_count - mc) * B * h->D);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return build_modes(h, kind, g, m_first, m_count, nphi, 0, B, d_mu0, d_P0_out);
 }
 
 int sosrt_phase_p0_modes(sosrt_t* h, int B, int kind, double g, int m_first, int m_count, int nphi, const double* mu0,
@@ -448,21 +437,11 @@ int sosrt_phase_p0_modes(sosrt_t* h, int B, int kind, double g, int m_first, int
     for (int b = 0; b < B; ++b)
         if (!(mu0[b] > 0 && mu0[b] <= 1)) return fail(SOSRT_E_INVALID, "column %d: mu0 must be in (0, 1]", b);
     HIPCHK(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
     const size_t n = (size_t)m_count * B * h->D;
-    double* dP = nullptr;
-    if (int e = dalloc(&dP, n + B)) return e;
-    auto body = [&]() -> int {
-        HIPCHK(hipMemcpyAsync(dP + n, mu0, B * sizeof(double), hipMemcpyHostToDevice, s));
-        if (int e = sosrt_phase_p0_modes_dev(h, B, kind, g, m_first, m_count, nphi, dP + n, dP)) return e;
-        HIPCHK(hipMemcpyAsync(P0_out, dP, n * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return 0;
-    };
-    const int rc = body();
-    (void)hipStreamSynchronize(s);
-    hipFree(dP);
-    return rc;
+    return to_host(h, n, B, P0_out, [&](double* dP) -> int {
+        HIPCHK(hipMemcpyAsync(dP + n, mu0, B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        return sosrt_phase_p0_modes_dev(h, B, kind, g, m_first, m_count, nphi, dP + n, dP);
+    });
 }
 
 int sosrt_set_order_targets(sosrt_t* h, const int* d_targets) {

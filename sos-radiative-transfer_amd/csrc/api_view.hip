@@ -32,7 +32,9 @@ int sosrt_phase_rows_dev(sosrt_t* h, int kind, double g, int V2, const double* m
     if (int e = view_phase_check(h, kind, g, V2, mu_signed, &vm)) return e;
     if (!d_rows_out) return fail(SOSRT_E_INVALID, "null output");
     HIPCHK(hipSetDevice(h->device));
-    launch_phase_rows(h->stream, h->g, h->grid.d_w, phase_fn(h, kind, g), h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, V2, vm, d_rows_out);
+    PhaseJob j = phase_job(h, kind, g);
+    j.V2 = V2; j.out = d_rows_out;
+    launch_phase_builder(h->stream, h->g, &vm, j);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -43,7 +45,9 @@ int sosrt_phase_p0_rows_dev(sosrt_t* h, int B, int kind, double g, const double*
     if (int e = view_phase_check(h, kind, g, V2, mu_signed, &vm)) return e;
     if (B < 1 || !d_mu0 || !d_out) return fail(SOSRT_E_INVALID, "bad argument");
     HIPCHK(hipSetDevice(h->device));
-    launch_phase_p0_rows(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g), h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, d_mu0, V2, vm, d_out);
+    PhaseJob j = phase_job(h, kind, g);
+    j.mu0 = d_mu0; j.B = B; j.V2 = V2; j.out = d_out;
+    launch_phase_builder(h->stream, h->g, &vm, j);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -149,8 +153,9 @@ int sosrt_phase_rows_modes_dev(sosrt_t* h, int kind, double g, int m_first, int 
     if (!d_rows_out) return fail(SOSRT_E_INVALID, "null output");
     HIPCHK(hipSetDevice(h->device));
     if (int e = modes_table(h, nphi, m_first, m_count)) return e;
-    launch_phase_rows_modes(h->stream, h->g, h->grid.d_w, phase_fn(h, kind, g), h->pf.d_modetab.p, h->pf.d_modetab.p + nphi, nphi, m_first, m_count, sign_odd, V2, vm,
-                            d_rows_out);
+    PhaseJob j = phase_job(h, kind, g, m_first, m_count, nphi);
+    j.sign_odd = sign_odd; j.V2 = V2; j.out = d_rows_out;
+    launch_phase_builder(h->stream, h->g, &vm, j);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -165,7 +170,9 @@ int sosrt_phase_p0_rows_modes_dev(sosrt_t* h, int B, int kind, double g, int m_f
     if (B > view_batch_cap(h)) return fail(SOSRT_E_INVALID, "B=%d: the handle's current columns are %d", B, view_batch_cap(h));
     HIPCHK(hipSetDevice(h->device));
     if (int e = modes_table(h, nphi, m_first, m_count)) return e;
-    launch_phase_p0_rows_modes(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g), h->pf.d_modetab.p, h->pf.d_modetab.p + nphi, nphi, m_first, m_count, d_mu0, V2, vm, d_out);
+    PhaseJob j = phase_job(h, kind, g, m_first, m_count, nphi);
+    j.mu0 = d_mu0; j.B = B; j.V2 = V2; j.out = d_out;
+    launch_phase_builder(h->stream, h->g, &vm, j);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -179,7 +186,9 @@ int sosrt_phase_p0_rows_azimuth_dev(sosrt_t* h, int B, int kind, double g, const
     if (B > view_batch_cap(h)) return fail(SOSRT_E_INVALID, "B=%d: the handle's current columns are %d", B, view_batch_cap(h));
     if ((long long)nphi_out * V2 > 0x7fffffffLL) return fail(SOSRT_E_INVALID, "nphi_out * V2 too large");
     HIPCHK(hipSetDevice(h->device));
-    launch_phase_p0_rows_azimuth(h->stream, h->g, h->grid.d_w, B, phase_fn(h, kind, g), h->grid.d_phi, h->grid.d_phi + kNPhi, kNPhi, d_mu0, V2, vm, nphi_out, d_phi, d_out);
+    PhaseJob j = phase_job(h, kind, g);
+    j.mu0 = d_mu0; j.B = B; j.V2 = V2; j.nphi_out = nphi_out; j.phi = d_phi; j.out = d_out;
+    launch_phase_builder(h->stream, h->g, &vm, j);
     HIPCHK(hipGetLastError());
     return 0;
 }

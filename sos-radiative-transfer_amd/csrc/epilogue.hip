@@ -7,13 +7,7 @@
 //                   at the top of the atmosphere (crit:382).  One workgroup per column, one wavefront per
 //                   layer row at a time (a row of 2N doubles is read once, coalesced); the per-level net
 //                   flux stays in LDS for the finite differences of the heating rate.
-//   k_phase_p0      azimuth-averaged first-order phase function P0(mu, mu0) of every column of a sweep
-//                   (phase:86-103, 148-165, 245-262): a mu0 sweep needs a fresh P0 per column.
-//   k_phase_matrix  P(mu, mu') with the reference's column normalisation (phase:107-131, 169-193, 266-290).
-//   k_phase_modes / k_phase_p0_modes
-//                   Fourier modes m >= 1 of the same two in azimuth (the azimuth-resolved solve): one
-//                   evaluation of p per (pair, phi node) feeds every requested mode and the m = 0 ring that normalises.
-//   k_azimuth_accumulate
+//   k_azimuth_accumulate / k_view_azimuth_accumulate / k_azimuth_synthesize
 //                   synthesis I(phi) = sum_m (2 - delta_m0) I^m cos(m phi) on the requested levels.
 //   k_mie_coefficients / k_mie_angles / k_mie_integrate
 //                   the table p(cos Theta) of a Mie sphere or of a log-normal ensemble of them (phase:299, 398-489; the
@@ -21,14 +15,10 @@
 //                   (DESIGN section 12): a_n, b_n and the efficiencies with one lane per (ensemble, radius), the angular
 //                   sums with one lane per table abscissa and a_n, b_n as wave-uniform loads, then the trapezoid over radii.
 //
-// Phase-function kinds: isotropic (phase:68), Rayleigh (phase:79), Henyey-Greenstein (phase:141) and a
-// tabulated function with the reference's linear interpolation (phase:198-236; fwc:3,173 is its table).
+// The builders of the phase matrix, of P0 and of their Fourier modes are in phase.hip.
 #include "kernels.hpp"
 
-#include <type_traits>
-
 #include "../../include/sosrt.h"
-#include "phasefn.hpp"
 
 namespace sosrt {
 
@@ -40,18 +30,6 @@ __device__ __forceinline__ double wsum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// sum over the workgroup; every thread gets the result
-__device__ double bsum(double x, double* s_red) {
-    const int tid = threadIdx.x, nw = blockDim.x >> 6;
-    const double v = wsum(x);
-    __syncthreads();
-    if ((tid & 63) == 0) s_red[tid >> 6] = v;
-    __syncthreads();
-    double r = 0;
-    for (int i = 0; i < nw; ++i) r += s_red[i];
-    return r;
 }
 
 __global__ __launch_bounds__(256) void k_epilogue(Grid g, const double* __restrict__ w_all, int B,
@@ -118,127 +96,6 @@ __global__ __launch_bounds__(256) void k_epilogue(Grid g, const double* __restri
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// phase functions
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_phase_p0(Grid g, const double* __restrict__ w_all, int B, PhaseFn p,
-                                                  const double* __restrict__ cosphi, const double* __restrict__ wphi,
-                                                  int nphi, const double* __restrict__ mu0_all,
-                                                  double* __restrict__ P0_all) {
-    const int b = blockIdx.x, tid = threadIdx.x, D = g.D;
-    __shared__ double s_red[8];
-    const double mu0 = mu0_all[b];
-    const double s0 = sqrt(1 - mu0 * mu0);
-    double* P0 = P0_all + (size_t)b * D;
-    if (p.kind == SOSRT_PHASE_ISO) {                                  // phase:68-76: ones, no normalisation
-        for (int m = tid; m < D; m += blockDim.x) P0[m] = 1.0;
-        return;
-    }
-    double part = 0;
-    for (int m0 = 0; m0 < D; m0 += blockDim.x) {
-        const int m = m0 + tid;
-        if (m < D) {
-            const double mu = g.mu[m];
-            const double v = ring(p, mu * mu0, s0 * sqrt(1 - mu * mu), cosphi, wphi, nphi) / (4 * SOSRT_PI);   // phase:101
-            P0[m] = v;
-            part += w_all[m] * v;
-        }
-    }
-    const double norm = bsum(part, s_red);                            // trapz(P0, mu), phase:103
-    for (int m = tid; m < D; m += blockDim.x) P0[m] = P0[m] / norm * 2;
-}
-
-__global__ __launch_bounds__(256) void k_phase_matrix(Grid g, const double* __restrict__ w_all, PhaseFn p,
-                                                      const double* __restrict__ cosphi, const double* __restrict__ wphi,
-                                                      int nphi, double* __restrict__ P) {
-    const int n = blockIdx.x, tid = threadIdx.x, D = g.D;             // column n: incidence direction mu[n]
-    __shared__ double s_red[8];
-    if (p.kind == SOSRT_PHASE_ISO) {                                  // phase:74: 2 everywhere, no normalisation
-        for (int m = tid; m < D; m += blockDim.x) P[(size_t)m * D + n] = 2.0;
-        return;
-    }
-    const double mun = g.mu[n], sn = sqrt(1 - mun * mun);
-    double part = 0;
-    for (int m0 = 0; m0 < D; m0 += blockDim.x) {
-        const int m = m0 + tid;
-        if (m < D) {
-            const double mu = g.mu[m];
-            const double v = ring(p, mu * mun, sn * sqrt(1 - mu * mu), cosphi, wphi, nphi) / (2 * SOSRT_PI);   // phase:128
-            P[(size_t)m * D + n] = v;
-            part += w_all[m] * v;
-        }
-    }
-    const double norm = bsum(part, s_red);                            // trapz(P[:, n], mu), phase:131
-    for (int m = tid; m < D; m += blockDim.x) P[(size_t)m * D + n] = 4 * P[(size_t)m * D + n] / norm;
-}
-
-// P^m[a][n] = R^m(a, n) / (2 pi) * 4 / Z_n, Z_n = trapz_mu(R^0(., n) / (2 pi)); out [mc][D][D]; one workgroup per column n
-template <int K>
-__global__ __launch_bounds__(256) void k_phase_modes(Grid g, const double* __restrict__ w_all, PhaseFn p,
-                                                     const double* __restrict__ cosphi, const double* __restrict__ tab,
-                                                     int nphi, int mf, int mc, double* __restrict__ P) {
-    const int n = blockIdx.x, tid = threadIdx.x, D = g.D;
-    const size_t DD = (size_t)D * D;
-    __shared__ double s_red[8];
-    if (p.kind == SOSRT_PHASE_ISO) {                                  // no azimuth dependence: every mode m >= 1 vanishes
-        for (int j = 0; j < mc; ++j)
-            for (int m = tid; m < D; m += blockDim.x) P[j * DD + (size_t)m * D + n] = 0.0;
-        return;
-    }
-    const double mun = g.mu[n], sn = sqrt(1 - mun * mun);
-    double part = 0;
-    for (int m0 = 0; m0 < D; m0 += blockDim.x) {
-        const int m = m0 + tid;
-        if (m < D) {
-            const double mu = g.mu[m];
-            double acc[K];
-            ring_modes<K>(p, mu * mun, sn * sqrt(1 - mu * mu), cosphi, tab, nphi, mf, mc, acc);
-            part += w_all[m] * (acc[0] / (2 * SOSRT_PI));
-#pragma unroll
-            for (int j = 1; j < K; ++j)
-                if (j <= mc) P[(j - 1) * DD + (size_t)m * D + n] = vanishes(p, mf + j - 1) ? 0.0 : acc[j] / (2 * SOSRT_PI);
-        }
-    }
-    const double norm = bsum(part, s_red);
-    for (int m = tid; m < D; m += blockDim.x)                         // (each thread rescales what it wrote)
-        for (int j = 0; j < mc; ++j) P[j * DD + (size_t)m * D + n] = 4 * P[j * DD + (size_t)m * D + n] / norm;
-}
-
-// P0^m[b][a] = R^m(a, mu0_b) / (4 pi) * 2 / Z0_b, Z0_b = trapz_mu(R^0(., mu0_b) / (4 pi)); out [mc][B][D]; one workgroup per column
-template <int K>
-__global__ __launch_bounds__(256) void k_phase_p0_modes(Grid g, const double* __restrict__ w_all, int B, PhaseFn p,
-                                                        const double* __restrict__ cosphi, const double* __restrict__ tab,
-                                                        int nphi, int mf, int mc, const double* __restrict__ mu0_all,
-                                                        double* __restrict__ P0_all) {
-    const int b = blockIdx.x, tid = threadIdx.x, D = g.D;
-    const size_t BD = (size_t)B * D;
-    __shared__ double s_red[8];
-    double* P0 = P0_all + (size_t)b * D;
-    if (p.kind == SOSRT_PHASE_ISO) {
-        for (int j = 0; j < mc; ++j)
-            for (int m = tid; m < D; m += blockDim.x) P0[j * BD + m] = 0.0;
-        return;
-    }
-    const double mu0 = mu0_all[b];
-    const double s0 = sqrt(1 - mu0 * mu0);
-    double part = 0;
-    for (int m0 = 0; m0 < D; m0 += blockDim.x) {
-        const int m = m0 + tid;
-        if (m < D) {
-            const double mu = g.mu[m];
-            double acc[K];
-            ring_modes<K>(p, mu * mu0, s0 * sqrt(1 - mu * mu), cosphi, tab, nphi, mf, mc, acc);
-            part += w_all[m] * (acc[0] / (4 * SOSRT_PI));
-#pragma unroll
-            for (int j = 1; j < K; ++j)
-                if (j <= mc) P0[(j - 1) * BD + m] = vanishes(p, mf + j - 1) ? 0.0 : acc[j] / (4 * SOSRT_PI);
-        }
-    }
-    const double norm = bsum(part, s_red);
-    for (int m = tid; m < D; m += blockDim.x)
-        for (int j = 0; j < mc; ++j) P0[j * BD + m] = P0[j * BD + m] / norm * 2;
-}
-
 // one term of the synthesis, sum_m (2 - delta_m0) I^m cos(m phi): both kernels below add it, in ascending m
 __device__ __forceinline__ double azimuth_term(double acc, double v, int m, double phi) { return acc + 2 * v * cos(m * phi); }
 
@@ -297,15 +154,6 @@ __global__ __launch_bounds__(256) void k_azimuth_synthesize(int B, int L, int D,
         o[i] = acc;
     }
 }
-
-// sosrt_phase_modes_dev, sign_odd: mode m is handed on as (-1)^m P^m (negation is exact)
-__global__ void k_negate_odd_modes(size_t n, int m_first, int m_count, double* __restrict__ P) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int j = 0; j < m_count; ++j)
-        if ((m_first + j) & 1) P[(size_t)j * n + i] = -P[(size_t)j * n + i];
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // Lorenz-Mie series and the log-normal ensemble (sosrt/mie.py; Bohren & Huffman 1983 ch. 4)
@@ -517,41 +365,6 @@ void launch_epilogue(hipStream_t s, const Grid& g, const double* w, int B, const
                        z_profile, out);
 }
 
-void launch_phase_p0(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
-                     const double* wphi, int nphi, const double* mu0, double* P0) {
-    hipLaunchKernelGGL(k_phase_p0, dim3(B), dim3(256), 0, s, g, w, B, p, cosphi, wphi, nphi, mu0, P0);
-}
-
-void launch_phase_matrix(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi,
-                         const double* wphi, int nphi, double* P) {
-    hipLaunchKernelGGL(k_phase_matrix, dim3(g.D), dim3(256), 0, s, g, w, p, cosphi, wphi, nphi, P);
-}
-
-template <typename F>
-static void modes_dispatch(int mc, F&& f) {
-    // accumulators: the m = 0 ring plus mc modes, rounded up to a compiled size
-    if (mc + 1 <= 9) f(std::integral_constant<int, 9>());
-    else if (mc + 1 <= 17) f(std::integral_constant<int, 17>());
-    else if (mc + 1 <= 33) f(std::integral_constant<int, 33>());
-    else f(std::integral_constant<int, kMaxModes + 1>());
-}
-
-void launch_phase_modes(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi, const double* tab,
-                        int nphi, int m_first, int m_count, double* P_out) {
-    modes_dispatch(m_count, [&](auto k) {
-        hipLaunchKernelGGL(k_phase_modes<decltype(k)::value>, dim3(g.D), dim3(256), 0, s, g, w, p, cosphi, tab, nphi, m_first,
-                           m_count, P_out);
-    });
-}
-
-void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
-                           const double* tab, int nphi, int m_first, int m_count, const double* mu0, double* P0_out) {
-    modes_dispatch(m_count, [&](auto k) {
-        hipLaunchKernelGGL(k_phase_p0_modes<decltype(k)::value>, dim3(B), dim3(256), 0, s, g, w, B, p, cosphi, tab, nphi,
-                           m_first, m_count, mu0, P0_out);
-    });
-}
-
 void launch_azimuth_accumulate(hipStream_t s, const Grid& g, int B, int m, const double* Im, int nlev, const int* levels,
                                int nphi_out, const double* phi, double* out) {
     hipLaunchKernelGGL(k_azimuth_accumulate, dim3(B * nlev), dim3(256), 0, s, g.L, g.D, m, Im, nlev, levels, nphi_out, phi, out);
@@ -565,10 +378,6 @@ void launch_view_azimuth_accumulate(hipStream_t s, size_t n, int m, const double
 void launch_azimuth_synthesize(hipStream_t s, const Grid& g, int B, int M, const double* I0, const double* Im, int nlev,
                                const int* levels, int nphi_out, const double* phi, double* out) {
     hipLaunchKernelGGL(k_azimuth_synthesize, dim3(B * nlev), dim3(256), 0, s, B, g.L, g.D, M, I0, Im, nlev, levels, nphi_out, phi, out);
-}
-
-void launch_negate_odd_modes(hipStream_t s, size_t n, int m_first, int m_count, double* P) {
-    hipLaunchKernelGGL(k_negate_odd_modes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, m_first, m_count, P);
 }
 
 void launch_mie_coefficients(hipStream_t s, int nlanes, int R, int n_cap, const double* x, const int* nmax, const int* nstart,

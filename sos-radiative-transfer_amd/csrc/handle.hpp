@@ -13,6 +13,7 @@
 #include "../../include/sosrt.h"
 #include "comm.hpp"
 #include "kernels.hpp"
+#include "phasefn.hpp"
 #include "plan.hpp"
 
 namespace sosrt {
@@ -388,9 +389,12 @@ int ensure_matrices(sosrt_handle* h, hipStream_t s);
 int mix_group_cap(const sosrt_handle* h, bool sets);
 // api_phasefn.hip, shared with the builders at view lanes (api_view.hip): the checks of a phase function by kind, and the
 // function as the builders' kernels take it (the table of sosrt_phase_table, if any: cosines, then values); the checks of a mode
-// range, and the upload of cos(phi_q) and the weights of modes [mf, mf + mc) into pf.d_modetab (synchronises the handle's stream first)
+// range, and the upload of cos(phi_q) and the weights of modes [mf, mf + mc) into pf.d_modetab (synchronises the handle's stream
+// first); the job of a builder on the handle's grid (phasefn.hpp): with mc == 0 the reference's 25-node ring, else the modes
+// [mf, mf + mc) on the table modes_table uploaded for them.  The caller adds what selects the builder (mu0, B, V2, ...) and out.
 int phase_check(sosrt_handle* h, int kind, double g);
 PhaseFn phase_fn(const sosrt_handle* h, int kind, double g);
+PhaseJob phase_job(const sosrt_handle* h, int kind, double g, int mf = 0, int mc = 0, int nphi = 0);
 int modes_check(sosrt_handle* h, int kind, double g, int m_first, int m_count, int nphi);
 int modes_table(sosrt_handle* h, int nphi, int mf, int mc);
 

@@ -2,7 +2,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "phasefn.hpp"
 #include "plan.hpp"
 
 namespace sosrt {
@@ -345,19 +344,7 @@ struct EpilogueOut {
 // w: np.trapz weights on the whole direction grid [D]; z_profile [L] (nullable: no heating rate)
 void launch_epilogue(hipStream_t s, const Grid& g, const double* w, int B, const double* tau, const double* I,
                      const ColDesc* desc, int beam_norm, const double* z_profile, const EpilogueOut& out);
-// phase functions on the device; cosphi / wphi: cos(phi) and trapz weights of phi = linspace(0, pi, nphi)
-void launch_phase_p0(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
-                     const double* wphi, int nphi, const double* mu0, double* P0);
-void launch_phase_matrix(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi,
-                         const double* wphi, int nphi, double* P);
-// Fourier modes of the phase function in azimuth (sosrt_phase_modes): modes [m_first, m_first + m_count) with m_first >= 1 of
-// P^m (P_out [m_count][D][D]) or of P0^m (P0_out [m_count][B][D]); tab [1 + m_count][nphi] holds the trapezoid weights of
-// phi = linspace(0, pi, nphi) (row 0, the m = 0 ring that normalises) and w_q cos(m phi_q) of each mode; cosphi [nphi].
 constexpr int kMaxModes = 64;      // SOSRT_MAX_MODES
-void launch_phase_modes(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi, const double* tab,
-                        int nphi, int m_first, int m_count, double* P_out);
-void launch_phase_p0_modes(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
-                           const double* tab, int nphi, int m_first, int m_count, const double* mu0, double* P0_out);
 // out[b][lev][dir][j] (+)= (2 - delta_m0) I^m[b][levels[lev]][dir] cos(m phi[j])   (m == 0 writes, m >= 1 adds)
 void launch_azimuth_accumulate(hipStream_t s, const Grid& g, int B, int m, const double* Im, int nlev, const int* levels,
                                int nphi_out, const double* phi, double* out);
@@ -365,8 +352,6 @@ void launch_azimuth_accumulate(hipStream_t s, const Grid& g, int B, int m, const
 // the terms added in ascending m (the bits of the sequence of launches above)
 void launch_azimuth_synthesize(hipStream_t s, const Grid& g, int B, int M, const double* I0, const double* Im, int nlev,
                                const int* levels, int nphi_out, const double* phi, double* out);
-// P[j] = -P[j] for the odd modes m_first + j of P [m_count][n] (sosrt_phase_modes_dev, sign_odd)
-void launch_negate_odd_modes(hipStream_t s, size_t n, int m_first, int m_count, double* P);
 // Lorenz-Mie tables (sosrt_mie_ensembles).  nlanes = S * R spheres, lane = s * R + i; x, nmax, nstart [nlanes]
 // (size parameter, terms of the series, start of the downward recurrence: from the host, mie.mie_coefficients' counts);
 // ab [nlanes][n_cap][4] and qw [nlanes][kMieQ] workspaces; tn [n_cap + 1]: (n + 1) / n; part [S][mie_chunks(R)][ntab].
@@ -391,24 +376,6 @@ struct ViewLevels {
     int n;
     int t[kViewLevels];
 };
-// rows [V2][D] of the stored phase matrix at exit cosines mu.s[j]; out [B][V2] the same of P0 (normalisers recomputed as
-// launch_phase_matrix / launch_phase_p0 compute them)
-void launch_phase_rows(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi, const double* wphi,
-                       int nphi, int V2, const ViewMu& mu, double* rows);
-void launch_phase_p0_rows(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
-                          const double* wphi, int nphi, const double* mu0, int V2, const ViewMu& mu, double* out);
-// the same rows of the Fourier modes [m_first, m_first + m_count), m_first >= 1: rows [m_count][V2][D]
-// ((-1)^m rows^m with sign_odd), out [m_count][B][V2]; cosphi, tab as launch_phase_modes takes them
-void launch_phase_rows_modes(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi,
-                             const double* tab, int nphi, int m_first, int m_count, int sign_odd, int V2, const ViewMu& mu,
-                             double* rows);
-void launch_phase_p0_rows_modes(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
-                                const double* tab, int nphi, int m_first, int m_count, const double* mu0, int V2,
-                                const ViewMu& mu, double* out);
-// out [nphi_out][B][V2] = p(c(s_j, mu0_b, phi_i)) / Z0_b with launch_phase_p0_rows' normaliser (cosphi, wphi: its ring)
-void launch_phase_p0_rows_azimuth(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
-                                  const double* wphi, int nphi, const double* mu0, int V2, const ViewMu& mu, int nphi_out,
-                                  const double* phi, double* out);
 // out [n][nphi_out] (+)= (2 - delta_m0) val[n] cos(m phi[j]), n = B nlev 2V   (m == 0 writes, m >= 1 adds; epilogue.hip)
 void launch_view_azimuth_accumulate(hipStream_t s, size_t n, int m, const double* val, int nphi_out, const double* phi, double* out);
 // S [nrows][2V] = diag(ca) Isrc W_atm + diag(cr) Isrc W_aer with the rows folded into Wfold [view_source_kpad(D)][view_source_cols(V)]

@@ -1,11 +1,12 @@
-// The phase functions of the azimuth builders and their ring rule, shared by epilogue.hip (k_phase_p0, k_phase_matrix and the
-// Fourier modes) and view.hip (the same at view cosines off the grid).
+// The phase functions of the builders in phase.hip, their ring rules, and the one launcher of those builders (the matrix, P0, their
+// Fourier modes in azimuth, and the rows of all four at view cosines off the grid).
 // Phase-function kinds: isotropic (phase:68), Rayleigh (phase:79), Henyey-Greenstein (phase:141) and a
 // tabulated function with the reference's linear interpolation (phase:198-236; fwc:3,173 is its table).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/sosrt.h"
+#include "kernels.hpp"
 
 namespace sosrt {
 
@@ -72,5 +73,30 @@ __device__ __forceinline__ void ring_modes(const PhaseFn& p, double cc, double s
 // Rayleigh's p is quadratic in cos phi: its modes m >= 3 are zero, not rounding noise (a matrix of noise has no flip symmetry to
 // rounding and would cost the solve of that mode the full contraction product)
 __device__ __forceinline__ bool vanishes(const PhaseFn& p, int m) { return p.kind == SOSRT_PHASE_RAYLEIGH && m >= 3; }
+
+// One launch of a phase builder (phase.hip).  What is built follows from the fields:
+//   second direction  mu0 == nullptr: the grid's mu[n], a column of the matrix, tables [D exits][D] or rows [V2][D];
+//                     else the batch columns' mu0 [B] (device), tables [B][D exits] or [B][V2]
+//   exit directions   V2 == 0: the grid's 2N nodes; else the view cosines vm.s[0 .. V2)
+//   ring rule         m_count == 0: the azimuth mean on nphi trapezoid nodes, cosphi [nphi] and wq [nphi] their weights, one table;
+//                     else the modes [m_first, m_first + m_count), m_first >= 1, m_count <= kMaxModes: m_count tables, mode m as
+//                     (-1)^m of it with sign_odd; wq [1 + m_count][nphi] holds the trapezoid weights (row 0, the m = 0 ring that
+//                     normalises) and w_q cos(m phi_q) of each mode (modes_table, handle.hpp)
+//   phi != nullptr    (mu0, view cosines, the plain ring) point values at the azimuths phi [nphi_out] (device) in place of a ring:
+//                     out [nphi_out][B][V2] = p(c(s_j, mu0_b, phi_i)) / Z0_b
+// w [D]: np.trapz weights on the whole direction grid.
+struct PhaseJob {
+    PhaseFn p;
+    const double* w;
+    const double* cosphi;
+    const double* wq;
+    int nphi, m_first, m_count, sign_odd;
+    const double* mu0;
+    int B, V2, nphi_out;
+    const double* phi;
+    double* out;
+};
+// vm may be null where V2 == 0
+void launch_phase_builder(hipStream_t s, const Grid& g, const ViewMu* vm, const PhaseJob& job);
 
 }  // namespace sosrt

@@ -1,19 +1,6 @@
 // View radiance: the radiance of a solved field at view cosines that are not nodes of the direction grid,
 // by integrating the field's source function along the line of sight at the view cosine itself.  gfx950.
 //
-//   k_phase_rows / k_phase_p0_rows
-//                     rows of the stored phase matrix, and of P0, at exit cosines s_j off the grid, with the stored matrix's
-//                     own normalisers: rows[j][n] = 4 ring(s_j, mu_n) / trapz_a ring(mu_a, mu_n), p0rows[b][j] =
-//                     2 ring(s_j, mu0_b) / trapz_a ring(mu_a, mu0_b).  The normaliser is recomputed by the rule of
-//                     k_phase_matrix / k_phase_p0 (a workgroup reduction over the 2N grid exit directions), so at a node the
-//                     row is the matrix's row.
-//   k_phase_rows_modes / k_phase_p0_rows_modes
-//                     the same rows of the Fourier modes m >= 1 of the phase function: R^m(s_j, mu_n) /
-//                     (2 pi) * 4 / Z_n and R^m(s_j, mu0_b) / (4 pi) * 2 / Z0_b with the nphi-node normalisers of k_phase_modes /
-//                     k_phase_p0_modes, recomputed by their rule, so at a node the row is the mode matrix's row.
-//   k_phase_p0_rows_azimuth
-//                     p(c(s_j, mu0_b, phi_i)) / Z0_b: the first-order phase value at a view lane and an azimuth, the sum the
-//                     modes of P0 converge to, with the normaliser of k_phase_p0_rows.
 //   k_view_fold       W[k][c] = w_k rows[c][2N-1-k]: the rows folded as the contraction's matrices are (I1_In:73, spec:321);
 //                     the atmosphere's rows in the columns c < CP/2, the aerosol's from CP/2 on, zero padding.
 //   k_view_source     S[b][t][j] = ca(b,t) sum_k W_atm[k][j] Isrc[b][t][k] + cr(b,t) sum_k W_aer[k][j] Isrc[b][t][k]: a
@@ -28,213 +15,17 @@
 //   k_view_first_order
 //                     the closed-form first order (spec:104-292, I1_In:13-58) at the lanes s_j and the requested levels only:
 //                     the chain through the zone-boundary rows, O(zones) exponentials per level.
+// The rows of the phase matrix, of P0 and of their Fourier modes at the view cosines come from the builders of phase.hip, with
+// the stored matrix's own normalisers: at a node the row is the matrix's row.
 #include "kernels.hpp"
 
-#include <type_traits>
-
 #include "../../include/sosrt.h"
-#include "phasefn.hpp"
 
 namespace sosrt {
 
 namespace {
 
 #define SOSRT_PI 3.14159265358979323846
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the workgroup; every thread gets the result (the reduction of k_phase_matrix, term for term)
-__device__ double bsum(double x, double* s_red) {
-    const int tid = threadIdx.x, nw = blockDim.x >> 6;
-    const double v = wsum(x);
-    __syncthreads();
-    if ((tid & 63) == 0) s_red[tid >> 6] = v;
-    __syncthreads();
-    double r = 0;
-    for (int i = 0; i < nw; ++i) r += s_red[i];
-    return r;
-}
-
-// one workgroup per incidence direction mu[n] (a column of the stored matrix)
-__global__ __launch_bounds__(256) void k_phase_rows(Grid g, const double* __restrict__ w_all, PhaseFn p,
-                                                    const double* __restrict__ cosphi, const double* __restrict__ wphi,
-                                                    int nphi, int V2, ViewMu vm, double* __restrict__ rows) {
-    const int n = blockIdx.x, tid = threadIdx.x, D = g.D;
-    __shared__ double s_red[8];
-    if (p.kind == SOSRT_PHASE_ISO) {                                  // phase:74: 2 everywhere, no normalisation
-        for (int j = tid; j < V2; j += blockDim.x) rows[(size_t)j * D + n] = 2.0;
-        return;
-    }
-    const double mun = g.mu[n], sn = sqrt(1 - mun * mun);
-    double part = 0;
-    for (int m0 = 0; m0 < D; m0 += blockDim.x) {
-        const int m = m0 + tid;
-        if (m < D) {
-            const double mu = g.mu[m];
-            const double v = ring(p, mu * mun, sn * sqrt(1 - mu * mu), cosphi, wphi, nphi) / (2 * SOSRT_PI);   // phase:128
-            part += w_all[m] * v;
-        }
-    }
-    const double norm = bsum(part, s_red);                            // trapz(P[:, n], mu), phase:131
-    for (int j = tid; j < V2; j += blockDim.x) {
-        const double s = vm.s[j];
-        const double v = ring(p, s * mun, sn * sqrt(1 - s * s), cosphi, wphi, nphi) / (2 * SOSRT_PI);
-        rows[(size_t)j * D + n] = 4 * v / norm;
-    }
-}
-
-// one workgroup per column b (solar direction mu0[b])
-__global__ __launch_bounds__(256) void k_phase_p0_rows(Grid g, const double* __restrict__ w_all, PhaseFn p,
-                                                       const double* __restrict__ cosphi, const double* __restrict__ wphi,
-                                                       int nphi, const double* __restrict__ mu0_all, int V2, ViewMu vm,
-                                                       double* __restrict__ out) {
-    const int b = blockIdx.x, tid = threadIdx.x, D = g.D;
-    __shared__ double s_red[8];
-    double* o = out + (size_t)b * V2;
-    if (p.kind == SOSRT_PHASE_ISO) {                                  // phase:68-76: ones, no normalisation
-        for (int j = tid; j < V2; j += blockDim.x) o[j] = 1.0;
-        return;
-    }
-    const double mu0 = mu0_all[b];
-    const double s0 = sqrt(1 - mu0 * mu0);
-    double part = 0;
-    for (int m0 = 0; m0 < D; m0 += blockDim.x) {
-        const int m = m0 + tid;
-        if (m < D) {
-            const double mu = g.mu[m];
-            const double v = ring(p, mu * mu0, s0 * sqrt(1 - mu * mu), cosphi, wphi, nphi) / (4 * SOSRT_PI);   // phase:101
-            part += w_all[m] * v;
-        }
-    }
-    const double norm = bsum(part, s_red);                            // trapz(P0, mu), phase:103
-    for (int j = tid; j < V2; j += blockDim.x) {
-        const double s = vm.s[j];
-        const double v = ring(p, s * mu0, s0 * sqrt(1 - s * s), cosphi, wphi, nphi) / (4 * SOSRT_PI);
-        o[j] = v / norm * 2;
-    }
-}
-
-// Rows of mode mf + j - 1 at the exit cosines s_j: one workgroup per incidence direction mu[n]; rows [mc][V2][D].  The
-// normaliser is the m = 0 ring of k_phase_modes over the 2N grid exits (ring_modes' accumulator 0, the same reduction);
-// sign: mode m is written as (-1)^m rows^m.  The normaliser comes from ring_modes<1>, k_phase_modes' from accumulator 0 of
-// ring_modes<K>: the same expression, so the row at a node has the mode matrix's bits as long as the compiler contracts both
-// instantiations alike -- tests/test_gpu_view_azimuth.py asserts that equality at all four K; it is not guaranteed by construction.
-template <int K>
-__global__ __launch_bounds__(256) void k_phase_rows_modes(Grid g, const double* __restrict__ w_all, PhaseFn p,
-                                                          const double* __restrict__ cosphi, const double* __restrict__ tab,
-                                                          int nphi, int mf, int mc, int sign, int V2, ViewMu vm,
-                                                          double* __restrict__ rows) {
-    const int n = blockIdx.x, tid = threadIdx.x, D = g.D;
-    const size_t VD = (size_t)V2 * D;
-    __shared__ double s_red[8];
-    if (p.kind == SOSRT_PHASE_ISO) {                                  // no azimuth dependence: every mode m >= 1 vanishes
-        for (int j = 0; j < mc; ++j)
-            for (int v = tid; v < V2; v += blockDim.x) rows[j * VD + (size_t)v * D + n] = 0.0;
-        return;
-    }
-    const double mun = g.mu[n], sn = sqrt(1 - mun * mun);
-    double part = 0;
-    for (int m0 = 0; m0 < D; m0 += blockDim.x) {
-        const int m = m0 + tid;
-        if (m < D) {
-            const double mu = g.mu[m];
-            double a0[1];
-            ring_modes<1>(p, mu * mun, sn * sqrt(1 - mu * mu), cosphi, tab, nphi, mf, 0, a0);
-            part += w_all[m] * (a0[0] / (2 * SOSRT_PI));
-        }
-    }
-    const double norm = bsum(part, s_red);
-    for (int v = tid; v < V2; v += blockDim.x) {
-        const double s = vm.s[v];
-        double acc[K];
-        ring_modes<K>(p, s * mun, sn * sqrt(1 - s * s), cosphi, tab, nphi, mf, mc, acc);
-#pragma unroll
-        for (int j = 1; j < K; ++j)
-            if (j <= mc) {
-                const double r = vanishes(p, mf + j - 1) ? 0.0 : acc[j] / (2 * SOSRT_PI);
-                const double o = 4 * r / norm;
-                rows[(j - 1) * VD + (size_t)v * D + n] = (sign && ((mf + j - 1) & 1)) ? -o : o;
-            }
-    }
-}
-
-// The same of P0: one workgroup per column b; out [mc][B][V2]
-template <int K>
-__global__ __launch_bounds__(256) void k_phase_p0_rows_modes(Grid g, const double* __restrict__ w_all, int B, PhaseFn p,
-                                                             const double* __restrict__ cosphi, const double* __restrict__ tab,
-                                                             int nphi, int mf, int mc, const double* __restrict__ mu0_all,
-                                                             int V2, ViewMu vm, double* __restrict__ out) {
-    const int b = blockIdx.x, tid = threadIdx.x, D = g.D;
-    const size_t BV = (size_t)B * V2;
-    __shared__ double s_red[8];
-    double* o = out + (size_t)b * V2;
-    if (p.kind == SOSRT_PHASE_ISO) {
-        for (int j = 0; j < mc; ++j)
-            for (int v = tid; v < V2; v += blockDim.x) o[j * BV + v] = 0.0;
-        return;
-    }
-    const double mu0 = mu0_all[b];
-    const double s0 = sqrt(1 - mu0 * mu0);
-    double part = 0;
-    for (int m0 = 0; m0 < D; m0 += blockDim.x) {
-        const int m = m0 + tid;
-        if (m < D) {
-            const double mu = g.mu[m];
-            double a0[1];
-            ring_modes<1>(p, mu * mu0, s0 * sqrt(1 - mu * mu), cosphi, tab, nphi, mf, 0, a0);
-            part += w_all[m] * (a0[0] / (4 * SOSRT_PI));
-        }
-    }
-    const double norm = bsum(part, s_red);
-    for (int v = tid; v < V2; v += blockDim.x) {
-        const double s = vm.s[v];
-        double acc[K];
-        ring_modes<K>(p, s * mu0, s0 * sqrt(1 - s * s), cosphi, tab, nphi, mf, mc, acc);
-#pragma unroll
-        for (int j = 1; j < K; ++j)
-            if (j <= mc) {
-                const double r = vanishes(p, mf + j - 1) ? 0.0 : acc[j] / (4 * SOSRT_PI);
-                o[(j - 1) * BV + v] = r / norm * 2;
-            }
-    }
-}
-
-// out[i][b][j] = p(c(s_j, mu0_b, phi_i)) / Z0_b, Z0_b the normaliser of k_phase_p0_rows (25-node ring): one workgroup per column
-__global__ __launch_bounds__(256) void k_phase_p0_rows_azimuth(Grid g, const double* __restrict__ w_all, int B, PhaseFn p,
-                                                               const double* __restrict__ cosphi, const double* __restrict__ wphi,
-                                                               int nphi, const double* __restrict__ mu0_all, int V2, ViewMu vm,
-                                                               int nout, const double* __restrict__ phi, double* __restrict__ out) {
-    const int b = blockIdx.x, tid = threadIdx.x, D = g.D;
-    const size_t BV = (size_t)B * V2;
-    __shared__ double s_red[8];
-    double* o = out + (size_t)b * V2;
-    if (p.kind == SOSRT_PHASE_ISO) {
-        for (int i = tid; i < nout * V2; i += blockDim.x) o[(size_t)(i / V2) * BV + i % V2] = 1.0;
-        return;
-    }
-    const double mu0 = mu0_all[b];
-    const double s0 = sqrt(1 - mu0 * mu0);
-    double part = 0;
-    for (int m0 = 0; m0 < D; m0 += blockDim.x) {
-        const int m = m0 + tid;
-        if (m < D) {
-            const double mu = g.mu[m];
-            const double v = ring(p, mu * mu0, s0 * sqrt(1 - mu * mu), cosphi, wphi, nphi) / (4 * SOSRT_PI);
-            part += w_all[m] * v;
-        }
-    }
-    const double norm = bsum(part, s_red);
-    for (int i = tid; i < nout * V2; i += blockDim.x) {
-        const int q = i / V2, j = i - q * V2;
-        const double s = vm.s[j];
-        const double c = -(s * mu0 + s0 * sqrt(1 - s * s) * cos(phi[q]));
-        o[(size_t)q * BV + j] = p(c) / norm;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // source at the view lanes
@@ -541,50 +332,6 @@ __global__ __launch_bounds__(64) void k_view_first_order(ViewFirstArgs a, ViewMu
 }
 
 }  // namespace
-
-void launch_phase_rows(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi, const double* wphi,
-                       int nphi, int V2, const ViewMu& mu, double* rows) {
-    hipLaunchKernelGGL(k_phase_rows, dim3(g.D), dim3(256), 0, s, g, w, p, cosphi, wphi, nphi, V2, mu, rows);
-}
-
-void launch_phase_p0_rows(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
-                          const double* wphi, int nphi, const double* mu0, int V2, const ViewMu& mu, double* out) {
-    hipLaunchKernelGGL(k_phase_p0_rows, dim3(B), dim3(256), 0, s, g, w, p, cosphi, wphi, nphi, mu0, V2, mu, out);
-}
-
-// accumulators of the mode builders: the m = 0 ring plus mc modes, rounded up to a compiled size (as epilogue.hip's)
-template <typename F>
-static void view_modes_dispatch(int mc, F&& f) {
-    if (mc + 1 <= 9) f(std::integral_constant<int, 9>());
-    else if (mc + 1 <= 17) f(std::integral_constant<int, 17>());
-    else if (mc + 1 <= 33) f(std::integral_constant<int, 33>());
-    else f(std::integral_constant<int, kMaxModes + 1>());
-}
-
-void launch_phase_rows_modes(hipStream_t s, const Grid& g, const double* w, const PhaseFn& p, const double* cosphi,
-                             const double* tab, int nphi, int m_first, int m_count, int sign_odd, int V2, const ViewMu& mu,
-                             double* rows) {
-    view_modes_dispatch(m_count, [&](auto k) {
-        hipLaunchKernelGGL(k_phase_rows_modes<decltype(k)::value>, dim3(g.D), dim3(256), 0, s, g, w, p, cosphi, tab, nphi, m_first,
-                           m_count, sign_odd, V2, mu, rows);
-    });
-}
-
-void launch_phase_p0_rows_modes(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
-                                const double* tab, int nphi, int m_first, int m_count, const double* mu0, int V2,
-                                const ViewMu& mu, double* out) {
-    view_modes_dispatch(m_count, [&](auto k) {
-        hipLaunchKernelGGL(k_phase_p0_rows_modes<decltype(k)::value>, dim3(B), dim3(256), 0, s, g, w, B, p, cosphi, tab, nphi,
-                           m_first, m_count, mu0, V2, mu, out);
-    });
-}
-
-void launch_phase_p0_rows_azimuth(hipStream_t s, const Grid& g, const double* w, int B, const PhaseFn& p, const double* cosphi,
-                                  const double* wphi, int nphi, const double* mu0, int V2, const ViewMu& mu, int nphi_out,
-                                  const double* phi, double* out) {
-    hipLaunchKernelGGL(k_phase_p0_rows_azimuth, dim3(B), dim3(256), 0, s, g, w, B, p, cosphi, wphi, nphi, mu0, V2, mu, nphi_out,
-                       phi, out);
-}
 
 int view_source_cols(int V) { return V <= 16 ? 64 : V <= 32 ? 128 : 256; }
 int view_source_kpad(int D) { return (D + VS_KC - 1) / VS_KC * VS_KC; }

@@ -8,7 +8,7 @@ this package's own Mie series (sosrt/mie.py) because `miepython` is not availabl
 their parity is unpinned.
 
 `phase_function(...)` is the host (NumPy) builder; `phase_function_device(...)` evaluates
-the same azimuth averages with the HIP kernels of csrc/epilogue.hip -- P0(mu, mu0) for a
+the same azimuth averages with the HIP kernels of csrc/phase.hip -- P0(mu, mu0) for a
 whole array of mu0 at once (a mu0 sweep needs a fresh P0 per column) and P(mu, mu').
 """
 import os

@@ -1,5 +1,5 @@
 """The view-radiance stage on the device (csrc/view.hip, csrc/api_view.hip) through the C ABI: the builders of
-phase rows off the grid, the source contraction, the two sweeps in both quadratures and the closed-form first order, against
+phase rows off the grid (csrc/phase.hip), the source contraction, the two sweeps in both quadratures and the closed-form first order, against
 the NumPy model of tests/view_np.py (which tests/test_view_host.py pins to the oracle), against the device's own field at the
 nodes of the direction grid, and against a known answer."""
 import ctypes

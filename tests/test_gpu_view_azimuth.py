@@ -1,5 +1,5 @@
 """Azimuth-resolved view radiance on the device (csrc/view.hip, csrc/api_view.hip) through the C ABI: the mode
-rows and first-order phase values at view lanes, the view stage on the field of a Fourier mode, the synthesis over the view
+rows and first-order phase values at view lanes (csrc/phase.hip), the view stage on the field of a Fourier mode, the synthesis over the view
 lanes and the driver SOS_Aer_batch(..., view_mu=, view_azimuths=), against the NumPy model of tests/view_azimuth_np.py (which
 tests/test_view_azimuth_host.py pins to the mode builders and to a direct view radiance) and against the device's own mode
 fields at the nodes of the direction grid.
