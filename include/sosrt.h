@@ -693,11 +693,26 @@ int sosrt_band_reduce_dev(sosrt_t* h, int C, int K, int M, const double* d_weigh
  * So with K = 1 S has the bits of sosrt_ground_source_dev with scale = weight (up to the sign of a zero), a term of weight 0
  * leaves the bits alone, all weights 0 give +0, and a column's bits do not depend on B.  1 <= K <= SOSRT_BRDF_MAX_TERMS.  One
  * workgroup per column, the surface row staged once for the K operators.  Refused as sosrt_ground_source_dev refuses, and for K
- * outside its range or a null d_weight. */
+ * outside its range or a null d_weight.
+ *
+ * SOSRT_BRDF_COX_MUNK: the sun glint of a rough water surface, the isotropic Gaussian slope distribution of
+ * Cox and Munk with the unpolarised Fresnel reflectance of a real index and, optionally, the bidirectional Smith shadowing.
+ * params = { sigma2, refractive_index, shadow }, exactly three: sigma2 finite and > 0 (the slope variance; Cox and Munk's wind
+ * law is 0.003 + 0.00512 U), refractive_index finite and > 1, shadow exactly 0 or 1.  With s = sqrt(max(0, 1 - c^2)):
+ *     rho = F(cos chi) exp(-t2 / sigma2) (1 + t2)^2 / (4 sigma2 a b) S,
+ *     h2 = (s_a - s_b)^2 + 2 s_a s_b (1 + cos phi),   t2 = h2 / (a + b)^2,   cos^2 chi = (h2 + (a + b)^2) / 4,
+ *     F(c) = (r_s^2 + r_p^2) / 2,   g = sqrt(n^2 - 1 + c^2),   r_s = (c - g) / (c + g),   r_p = (n^2 c - g) / (n^2 c + g),
+ *     S = 1 / (1 + Lambda(a) + Lambda(b)) (shadow = 1; else 1),
+ *     Lambda(c) = (sqrt(sigma2 / pi) exp(-cot^2 / sigma2) / cot - erfc(cot / sqrt(sigma2))) / 2,   cot = c / s,   Lambda(1) = 0.
+ * phi = pi is the specular direction (phi = 0 with a = b is back-scatter, as for every kind).  h2 and cos^2 chi are sums of
+ * non-negative terms; rho is symmetric in (a, b) and not clamped (toward grazing angles its hemispherical integral exceeds 1).
+ * Every builder here and below takes the kind, with the guarantees it gives for RPV; a ground f_iso + f_glint rho is two operator
+ * terms with SOSRT_BRDF_LAMBERTIAN.  Refused like the other kinds: nparams != 3, null params, a parameter outside its range. */
 #define SOSRT_BRDF_LAMBERTIAN  0
 #define SOSRT_BRDF_RPV         1
 #define SOSRT_BRDF_ROSS_THICK  2
 #define SOSRT_BRDF_LI_SPARSE_R 3
+#define SOSRT_BRDF_COX_MUNK    4
 #define SOSRT_BRDF_MAX_NPHI    65537
 #define SOSRT_BRDF_MAX_TERMS   4
 int sosrt_brdf_operator_dev(sosrt_t* h, int kind, const double* params /*host*/, int nparams, int nphi, double* d_R_out /*[N-1][N-1], [j][i]*/);

@@ -55,6 +55,20 @@ static int brdf_params(int kind, const double* params, int nparams, int nphi, Br
         bp.p[0] = params[0];
         return 0;
     }
+    if (kind == SOSRT_BRDF_COX_MUNK) {
+        if (nparams != 3)
+            return fail(SOSRT_E_INVALID, "%s: SOSRT_BRDF_COX_MUNK takes 3 parameters sigma2, refractive_index, shadow (nparams=%d)", what,
+                        nparams);
+        if (!params) return fail(SOSRT_E_INVALID, "%s: null params", what);
+        if (!(std::isfinite(params[0]) && params[0] > 0))
+            return fail(SOSRT_E_INVALID, "%s: SOSRT_BRDF_COX_MUNK sigma2=%g: need a finite slope variance > 0", what, params[0]);
+        if (!(std::isfinite(params[1]) && params[1] > 1))
+            return fail(SOSRT_E_INVALID, "%s: SOSRT_BRDF_COX_MUNK refractive_index=%g: need a finite real index > 1", what, params[1]);
+        if (!(params[2] == 0 || params[2] == 1))
+            return fail(SOSRT_E_INVALID, "%s: SOSRT_BRDF_COX_MUNK shadow=%g: need exactly 0 or 1", what, params[2]);
+        for (int i = 0; i < 3; ++i) bp.p[i] = params[i];
+        return 0;
+    }
     return fail(SOSRT_E_INVALID, "%s: unknown BRDF kind %d", what, kind);
 }
 

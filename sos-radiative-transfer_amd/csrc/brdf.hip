@@ -85,14 +85,52 @@ __device__ __forceinline__ double li_sparse_r(const Dir& a, const Dir& b, double
     return O - sec + 0.5 * (1.0 + cx) / (a.c * b.c);
 }
 
+// SOSRT_BRDF_COX_MUNK (sosrt.h): the sun glint of an isotropic Gaussian slope distribution of variance
+// sigma2 = p[0] over water of real index p[1].  Smith's Lambda of one direction, for the shadowing 1 / (1 + Lambda(a) + Lambda(b)):
+// cot = c / s; at c = 1 (the grid's last node) cot is infinite and Lambda = 0.
+__device__ __forceinline__ double smith_lambda(const Dir& d, double sigma2) {
+    if (!(d.s > 0.0)) return 0.0;
+    const double cot = d.c / d.s;
+    return 0.5 * (sqrt(sigma2 / kPi) * exp(-(cot * cot) / sigma2) / cot - erfc(cot / sqrt(sigma2)));
+}
+// What the glint of a pair does not owe to the azimuth: S / (4 sigma2 a b), S = 1 / (1 + Lambda(a) + Lambda(b)) where p[2], else 1.
+__device__ __forceinline__ double cox_munk_pre(const BrdfParams& bp, const Dir& a, const Dir& b) {
+    const double sigma2 = bp.p[0];
+    const double S = bp.p[2] != 0.0 ? 1.0 / (1.0 + smith_lambda(a, sigma2) + smith_lambda(b, sigma2)) : 1.0;
+    return S / (4.0 * sigma2 * a.c * b.c);
+}
+// rho(a, b, phi) = F(cos chi) exp(-t2 / sigma2) (1 + t2)^2 pre.  With h2 = |horizontal part of a + b|^2, t2 = h2 / (a + b)^2 is
+// tan^2 of the facet's tilt and cos^2 chi = |a + b|^2 / 4 = (h2 + (a + b)^2) / 4 of the angle of incidence on it.  2 - hav = 1 + cos
+// phi: h2 = (s_a - s_b)^2 + 2 s_a s_b (2 - hav) is a sum of two non-negative terms, and so is cos^2 chi -- 1 + cos xi formed by
+// subtraction (cos xi = a b - s_a s_b (1 - hav)) would cancel toward grazing specular geometry.  phi = pi is the specular direction.
+// F = (r_s^2 + r_p^2) / 2 is the unpolarised Fresnel reflectance.  Symmetric in (a, b) as written.  What depends on the pair alone
+// (1 / (a + b)^2, 1 / sigma2, n^2) leaves the node loop; a node costs one exp, two sqrt and the two Fresnel divisions.
+__device__ __forceinline__ double cox_munk(const BrdfParams& bp, const Dir& a, const Dir& b, double pre, double hav) {
+    const double n2 = bp.p[1] * bp.p[1], inv_sigma2 = 1.0 / bp.p[0];
+    const double sum = a.c + b.c, sum2 = sum * sum, inv_sum2 = 1.0 / sum2;
+    const double ds = a.s - b.s;
+    const double h2 = ds * ds + 2.0 * (a.s * b.s) * (2.0 - hav);
+    const double t2 = h2 * inv_sum2;
+    const double c2 = 0.25 * (h2 + sum2);
+    const double c = sqrt(c2), g = sqrt(n2 - 1.0 + c2);
+    const double rs = (c - g) / (c + g), rp = (n2 * c - g) / (n2 * c + g);
+    const double F = 0.5 * (rs * rs + rp * rp);
+    const double q = 1.0 + t2;
+    return F * exp(-t2 * inv_sigma2) * (q * q) * pre;
+}
+
 // What a pair (a, b) computes once, before its azimuth nodes: the two directions (the Ross-Li kernels': floored at p[0]) and one
-// number `pre` of the kind's: RPV's Minnaert factor, 1 / (a + b) of Ross-Thick, sec of Li-Sparse.
+// number `pre` of the kind's: RPV's Minnaert factor, 1 / (a + b) of Ross-Thick, sec of Li-Sparse, Cox-Munk's S / (4 sigma2 a b).
 template <int KIND>
 __device__ __forceinline__ void pair_setup(const BrdfParams& bp, double ca, double cb, Dir& a, Dir& b, double& pre) {
     if constexpr (KIND == SOSRT_BRDF_ROSS_THICK || KIND == SOSRT_BRDF_LI_SPARSE_R) {
         a = make_dir(fmax(ca, bp.p[0]));
         b = make_dir(fmax(cb, bp.p[0]));
         pre = KIND == SOSRT_BRDF_ROSS_THICK ? 1.0 / (a.c + b.c) : 1.0 / a.c + 1.0 / b.c;
+    } else if constexpr (KIND == SOSRT_BRDF_COX_MUNK) {
+        a = make_dir(ca);
+        b = make_dir(cb);
+        pre = cox_munk_pre(bp, a, b);
     } else {
         a = make_dir(ca);
         b = make_dir(cb);
@@ -105,6 +143,7 @@ __device__ __forceinline__ double brdf_value(const BrdfParams& bp, const Dir& a,
     if constexpr (KIND == SOSRT_BRDF_RPV) return rpv(bp, a, b, pre, cphi, hav);
     else if constexpr (KIND == SOSRT_BRDF_ROSS_THICK) return ross_thick(a, b, pre, cphi);
     else if constexpr (KIND == SOSRT_BRDF_LI_SPARSE_R) return li_sparse_r(a, b, pre, cphi, hav);
+    else if constexpr (KIND == SOSRT_BRDF_COX_MUNK) return cox_munk(bp, a, b, pre, hav);
     else return 1.0;
 }
 
@@ -369,7 +408,7 @@ __global__ __launch_bounds__(256) void k_bounce_accumulate(Grid g, int B, const 
 }
 
 // ---- the ground's term at view lanes off the grid ----
-// rho(ca, cb, phi) of a Ross-Li kernel at an azimuth itself, with the inputs of the node loop: cos phi and 2 sin^2(phi / 2)
+// rho(ca, cb, phi) of a Ross-Li kernel or of Cox-Munk at an azimuth itself, with the inputs of the node loop: cos phi and 2 sin^2(phi / 2)
 template <int KIND>
 __device__ __forceinline__ double value_at(const BrdfParams& bp, double ca, double cb, double phi) {
     Dir a, b;
@@ -398,6 +437,8 @@ __global__ __launch_bounds__(256) void k_brdf_view_beam_azimuth(int B, ViewMu vm
         r = value_at<SOSRT_BRDF_ROSS_THICK>(bp, vm.s[v], mu0[b], phi[q]);
     } else if (bp.kind == SOSRT_BRDF_LI_SPARSE_R) {
         r = value_at<SOSRT_BRDF_LI_SPARSE_R>(bp, vm.s[v], mu0[b], phi[q]);
+    } else if (bp.kind == SOSRT_BRDF_COX_MUNK) {
+        r = value_at<SOSRT_BRDF_COX_MUNK>(bp, vm.s[v], mu0[b], phi[q]);
     }
     out[idx] = r;
 }
@@ -479,11 +520,12 @@ void launch_brdf_pairs(hipStream_t s, const Grid& g, const ViewMu& vm, int V, in
     const long long n = (long long)(mu0 ? B : g.N - 1) * (V ? V : g.N - 1);
     const dim3 blocks((unsigned)((n + 255) / 256));
     // [kind][one mode or up to kModesPerLaunch]; api_brdf.hip lets no other kind through
-    static constexpr decltype(&k_brdf_pairs<1, 0>) kernels[4][2] = {
+    static constexpr decltype(&k_brdf_pairs<1, 0>) kernels[5][2] = {
         {k_brdf_pairs<1, SOSRT_BRDF_LAMBERTIAN>, k_brdf_pairs<kModesPerLaunch, SOSRT_BRDF_LAMBERTIAN>},
         {k_brdf_pairs<1, SOSRT_BRDF_RPV>, k_brdf_pairs<kModesPerLaunch, SOSRT_BRDF_RPV>},
         {k_brdf_pairs<1, SOSRT_BRDF_ROSS_THICK>, k_brdf_pairs<kModesPerLaunch, SOSRT_BRDF_ROSS_THICK>},
         {k_brdf_pairs<1, SOSRT_BRDF_LI_SPARSE_R>, k_brdf_pairs<kModesPerLaunch, SOSRT_BRDF_LI_SPARSE_R>},
+        {k_brdf_pairs<1, SOSRT_BRDF_COX_MUNK>, k_brdf_pairs<kModesPerLaunch, SOSRT_BRDF_COX_MUNK>},
     };
     for (int m = 0; m < m_count; m += kModesPerLaunch) {
         const int nm = min(kModesPerLaunch, m_count - m);

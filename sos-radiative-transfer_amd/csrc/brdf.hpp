@@ -9,7 +9,7 @@ namespace sosrt {
 
 struct BrdfParams {
     int kind;                          // SOSRT_BRDF_*
-    double p[3];                       // RPV: rho0, k, Theta; the Ross-Li kernels: mu_floor
+    double p[3];                       // RPV: rho0, k, Theta; the Ross-Li kernels: mu_floor; Cox-Munk: sigma2, n, shadow
 };
 
 // The Fourier modes m_first .. m_first + m_count - 1 in azimuth of the named BRDF, rho^m(a, b) = (1 / pi) int_0^pi rho cos(m phi)

@@ -24,7 +24,7 @@ MAX_MODES = 64
 MAX_PHASE_SETS = 64
 MAX_VIEWS = 64
 VIEW_QUAD_GRID, VIEW_QUAD_LINEAR = 0, 1
-BRDF_LAMBERTIAN, BRDF_RPV, BRDF_ROSS_THICK, BRDF_LI_SPARSE_R = 0, 1, 2, 3
+BRDF_LAMBERTIAN, BRDF_RPV, BRDF_ROSS_THICK, BRDF_LI_SPARSE_R, BRDF_COX_MUNK = 0, 1, 2, 3, 4
 BRDF_MAX_TERMS = 4
 
 _dp = POINTER(c_double)

@@ -123,7 +123,7 @@ def toa_net_flux(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, z0
     (tauStar_aer, alb_aer).  beam='spherical' (with `earth_radius`, km): the direct beam on its slant path through spherical
     shells, in the solve and in the flux's beam terms (main.SOS_Aer_batch); `radiative_forcing` and `critical_albedo` pass
     both keywords on.  surface='brdf' with `brdf` ('lambertian', ('rpv', rho0, k, theta), ('ross_li', f_iso, f_vol, f_geo[,
-    mu_floor]) or arrays (R, r0)): the BRDF ground of main.SOS_Aer_batch, grd_alb its scale; `radiative_forcing` and
+    mu_floor]), ('cox_munk', wind_speed[, refractive_index[, f_iso[, f_glint[, shadow]]]]) or arrays (R, r0)): the BRDF ground of main.SOS_Aer_batch, grd_alb its scale; `radiative_forcing` and
     `critical_albedo` pass these on too."""
     _beam_args(beam, earth_radius)
     if surface not in ("specular", "brdf"):

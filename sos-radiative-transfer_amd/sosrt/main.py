@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib
 from .inputs import direction_grid, slab_indices, tau_profile
+from .ocean import slope_variance
 from .solver import DevicePhaseSets, Solver
 
 # the literals of SOS_Aer_main_specular.py:23-96
@@ -41,7 +42,7 @@ class ColumnResult:
     beam_slant: Optional[np.ndarray] = None   # [L] (beam='spherical'): slant optical depth of the direct beam at every level
     bounces: Optional[int] = None             # (surface='brdf'): ground reflections summed until the series' term fell below tol
     bounce_ratio: Optional[float] = None      # ... and the last term's share of the sum
-    black_sky_albedo: Optional[float] = None  # (brdf=('ross_li', ...)): the ground's directional-hemispherical reflectance at mu0
+    black_sky_albedo: Optional[float] = None  # (brdf=('ross_li', ...) or ('cox_munk', ...)): the ground's directional-hemispherical reflectance at mu0
     white_sky_albedo: Optional[float] = None  # ... and its bihemispherical reflectance, both on the grid's trapezoid
 
 
@@ -71,7 +72,7 @@ class BatchResult:
     bounce_orders: Optional[np.ndarray] = None  # [K, B] (surface='brdf'): the orders the solve of every ground reflection ran
     I_view_ground: Optional[np.ndarray] = None          # [B, nlev, 2V] (brdf_view=True): the ground's unscattered radiance at the view lanes, a term of I_view
     I_view_azimuth_ground: Optional[np.ndarray] = None  # [B, nlev, 2V, len(view_azimuths)] the same at (lane, azimuth), a term of I_view_azimuth
-    black_sky_albedo: Optional[np.ndarray] = None  # [B] (brdf=('ross_li', ...)): the ground's directional-hemispherical reflectance at mu0
+    black_sky_albedo: Optional[np.ndarray] = None  # [B] (brdf=('ross_li', ...) or ('cox_munk', ...)): the ground's directional-hemispherical reflectance at mu0
     white_sky_albedo: Optional[np.ndarray] = None  # [B] ... and its bihemispherical reflectance, both on the grid's trapezoid
 
 
@@ -367,6 +368,46 @@ def solve_thermal(s: Solver, tau, planck, planck_surface, emissivity=None, tol=1
 MAX_BOUNCES = 32
 BRDF_NPHI = 65
 ROSS_LI_MU_FLOOR = 0.17364817766693033    # cos 80 deg: the Ross-Li kernels carry sec theta and are not meant for grazing angles
+COX_MUNK_INDEX = 1.34                     # sea water in the visible
+COX_MUNK_MAX_WINDS = _lib.BRDF_MAX_TERMS - 1   # every distinct wind is one glint term beside the isotropic one
+
+
+def _cox_munk_args(spec, brdf, B):
+    """The ocean ground ('cox_munk', wind_speed[, refractive_index[, f_iso[, f_glint[, shadow]]]]) of `_brdf_args` (DESIGN section
+    26), rho = f_iso + f_glint rho_glint: spec.terms = the isotropic term, then one glint term (sigma2, n, shadow) per distinct
+    wind speed, ascending; spec.weight [B, 1 + winds] = f_iso, then f_glint on the column's own wind and 0 on the others."""
+    if not 2 <= len(brdf) <= 6:
+        raise ValueError("the Cox-Munk brdf is ('cox_munk', wind_speed[, refractive_index[, f_iso[, f_glint[, shadow]]]]) (got %r)" % (brdf,))
+    shadow = brdf[5] if len(brdf) > 5 else True
+    if not (isinstance(shadow, (bool, np.bool_)) or (isinstance(shadow, (int, float, np.integer, np.floating)) and shadow in (0, 1))):
+        raise ValueError("the Cox-Munk shadow must be True or False (got %r)" % (shadow,))
+    try:
+        wind = np.asarray(brdf[1], dtype=np.float64)
+        n = float(brdf[2]) if len(brdf) > 2 else COX_MUNK_INDEX
+        f = [np.asarray(brdf[i] if len(brdf) > i else d, dtype=np.float64) for i, d in ((3, 0.0), (4, 1.0))]
+    except (TypeError, ValueError):
+        raise ValueError("the Cox-Munk wind_speed, refractive_index, f_iso and f_glint must be numbers (got %r)" % (brdf[1:],)) from None
+    if wind.shape not in ((), (1,), (B,)) or not np.all(np.isfinite(wind)) or np.any(wind < 0):
+        raise ValueError("the Cox-Munk wind_speed (m/s at 10 m) must be finite, >= 0 and a scalar or [B] = (%d,)" % B)
+    if not (np.isfinite(n) and n > 1):
+        raise ValueError("the Cox-Munk refractive_index=%g: need a finite real index > 1" % n)
+    if any(x.shape not in ((), (1,), (B,)) or not np.all(np.isfinite(x)) or np.any(x < 0) for x in f):
+        raise ValueError("the Cox-Munk weights f_iso, f_glint must each be finite, >= 0 and a scalar or [B] = (%d,)" % B)
+    if all(np.all(x == 0) for x in f):
+        raise ValueError("the Cox-Munk weights f_iso, f_glint are both zero: a black ground is surface='specular' with grd_alb=0")
+    if np.any(spec.scale != 1):
+        raise ValueError("brdf=('cox_munk', ...) carries its amplitude in its weights: grd_alb must be omitted or 1")
+    column = lambda x: np.broadcast_to(x.reshape(-1) if x.ndim else x, (B,))
+    winds, own = np.unique(column(wind), return_inverse=True)
+    if len(winds) > COX_MUNK_MAX_WINDS:
+        raise ValueError("brdf=('cox_munk', ...) takes at most %d distinct wind speeds in one batch (got %d): every wind is an "
+                         "operator term of its own; make one call per wind" % (COX_MUNK_MAX_WINDS, len(winds)))
+    spec.kind, spec.params = "cox_munk", (n, float(shadow))
+    spec.terms = (("lambertian", ()),) + tuple(("cox_munk", (float(slope_variance(u)), n, float(shadow))) for u in winds)
+    spec.weight = np.zeros((B, 1 + len(winds)))
+    spec.weight[:, 0] = column(f[0])
+    spec.weight[np.arange(B), 1 + own.reshape(-1)] = column(f[1])
+    return spec
 
 
 def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None, view_azimuths=None, mode_batch=False,
@@ -374,7 +415,7 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
                brdf_modes=False, brdf_view=False):
     """Checks of surface='brdf', made before any handle exists: None for every other surface, else a namespace (kind, params,
     R [N-1, N-1] or None, r0 [B, N-1] or None, scale [B], modes; terms, weight) of the ground `brdf` with `grd_alb` as its
-    per-column scale; terms: None, or for ('ross_li', ...) the (kind, params) of its operator terms, with weight [B, K] their
+    per-column scale; terms: None, or for ('ross_li', ...) and ('cox_munk', ...) the (kind, params) of its operator terms, with weight [B, K] their
     per-column weights (DESIGN section 24);
     modes: the call is the azimuth-resolved one over the ground's Fourier modes (`brdf_modes=True` with `azimuths`); view: the
     call adds the ground's term at the view lanes (`brdf_view=True` with `view_mu`)."""
@@ -392,7 +433,7 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
         return None
     if brdf is None:
         raise ValueError("surface='brdf' needs brdf: 'lambertian', ('rpv', rho0, k, theta), ('ross_li', f_iso, f_vol, f_geo[, "
-                         "mu_floor]) or the arrays (R, r0)")
+                         "mu_floor]), ('cox_munk', wind_speed[, refractive_index[, f_iso[, f_glint[, shadow]]]]) or the arrays (R, r0)")
     if brdf_view:
         if view_mu is None:
             raise ValueError("brdf_view=True is the view stage over the BRDF ground: give view_mu")
@@ -440,11 +481,13 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
                            terms=None, weight=None)
     if isinstance(brdf, str):
         if brdf != "lambertian":
-            raise ValueError("brdf must be 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0) (got %r)" % (brdf,))
+            raise ValueError("brdf must be 'lambertian', ('rpv', rho0, k, theta), ('ross_li', ...), ('cox_munk', ...) or the arrays (R, r0) "
+                             "(got %r)" % (brdf,))
         spec.kind = "lambertian"
         return spec
     if not isinstance(brdf, (tuple, list)) or len(brdf) < 2:
-        raise ValueError("brdf must be 'lambertian', ('rpv', rho0, k, theta) or the arrays (R, r0) (got %r)" % (brdf,))
+        raise ValueError("brdf must be 'lambertian', ('rpv', rho0, k, theta), ('ross_li', ...), ('cox_munk', ...) or the arrays (R, r0) "
+                         "(got %r)" % (brdf,))
     if isinstance(brdf[0], str) and brdf[0] == "ross_li":
         if len(brdf) not in (4, 5):
             raise ValueError("the Ross-Li brdf is ('ross_li', f_iso, f_vol, f_geo) or ('ross_li', f_iso, f_vol, f_geo, mu_floor) "
@@ -467,10 +510,12 @@ def _brdf_args(surface, brdf, grd_alb, nb_angles, B, azimuths=None, view_mu=None
         spec.terms = (("lambertian", ()), ("ross_thick", (floor,)), ("li_sparse_r", (floor,)))
         spec.weight = np.ascontiguousarray(np.stack([np.broadcast_to(x.reshape(-1) if x.ndim else x, (B,)) for x in f], axis=1))
         return spec
+    if isinstance(brdf[0], str) and brdf[0] == "cox_munk":
+        return _cox_munk_args(spec, brdf, B)
     if isinstance(brdf[0], str):
         if brdf[0] != "rpv" or len(brdf) != 4:
-            raise ValueError("a named brdf is 'lambertian', ('rpv', rho0, k, theta) or ('ross_li', f_iso, f_vol, f_geo[, mu_floor]) "
-                             "(got %r)" % (brdf,))
+            raise ValueError("a named brdf is 'lambertian', ('rpv', rho0, k, theta), ('ross_li', f_iso, f_vol, f_geo[, mu_floor]) or "
+                             "('cox_munk', wind_speed[, refractive_index[, f_iso[, f_glint[, shadow]]]]) (got %r)" % (brdf,))
         try:
             rho0, k, theta = (float(x) for x in brdf[1:])
         except (TypeError, ValueError):
@@ -740,7 +785,17 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     three operators are built once and every column's ground source sums them with its own weights, so a batch of pixels each
     with its own BRDF is one batch; both kernels are evaluated at max(mu, mu_floor), default ROSS_LI_MU_FLOOR = cos 80 deg (0:
     the formulas as written); rho is not clamped and can go negative for a large f_geo; grd_alb omitted or 1; the result then
-    also has black_sky_albedo and white_sky_albedo [B] on the grid's quadrature; `brdf=(R, r0)`: a caller's operator R [N-1, N-1] (upward lane N+1+i from downward lane j, the flux
+    also has black_sky_albedo and white_sky_albedo [B] on the grid's quadrature;
+    `brdf=('cox_munk', wind_speed[, refractive_index[, f_iso[, f_glint[, shadow]]]])`: the OCEAN, rho = f_iso +
+    f_glint rho_glint with the sun glint of Cox and Munk's isotropic Gaussian slopes, sigma^2 = 0.003 + 0.00512 wind_speed (m/s at
+    10 m; `ocean.slope_variance`), the unpolarised Fresnel reflectance of refractive_index (default COX_MUNK_INDEX = 1.34) and,
+    with shadow (default True), the bidirectional Smith shadowing; f_iso (default 0: the water-leaving and whitecap reflectance,
+    `ocean.whitecap_fraction`) and f_glint (default 1) are scalars or [B], finite, >= 0, not both zero; wind_speed is a scalar
+    or [B] with at most COX_MUNK_MAX_WINDS = 3 distinct values -- every wind is an operator term, a column weighs its own with
+    f_glint and the others with 0, and has the bits it has in a batch at its wind alone; more winds: one call per wind.  The
+    specular direction is phi = pi.  rho_glint is not clamped: toward grazing incidence its directional-hemispherical reflectance
+    on the grid's trapezoid exceeds 1 (1.07 on the lowest node at N = 128, 2 m/s).  grd_alb omitted or 1; black_sky_albedo and
+    white_sky_albedo as for 'ross_li'; `brdf=(R, r0)`: a caller's operator R [N-1, N-1] (upward lane N+1+i from downward lane j, the flux
     quadrature folded in) and beam row r0 [N-1] or [B, N-1], grd_alb a plain scale.  BatchResult.bounces / bounce_ratio [B]
     / bounce_orders [K, B] (the orders of every reflection's solve); n is the black solve's.  Not with `mode_batch`,
     `beam='spherical'`, `source='thermal'`, `first_order='readme'`, `save_orders` or several `devices`; `azimuths` only with

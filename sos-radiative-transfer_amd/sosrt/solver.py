@@ -466,13 +466,13 @@ class Solver:
 
     # ---- BRDF ground (sosrt.h) --------------------------------------------------------
     _BRDF_KINDS = {"lambertian": _lib.BRDF_LAMBERTIAN, "rpv": _lib.BRDF_RPV, "ross_thick": _lib.BRDF_ROSS_THICK,
-                   "li_sparse_r": _lib.BRDF_LI_SPARSE_R}
+                   "li_sparse_r": _lib.BRDF_LI_SPARSE_R, "cox_munk": _lib.BRDF_COX_MUNK}
 
     def _brdf_pack(self, kind, params):
         """(kind, params, nparams) as the C entry points take a named BRDF"""
         k = self._BRDF_KINDS.get(kind)
         if k is None:
-            raise ValueError("BRDF kind must be 'lambertian', 'rpv', 'ross_thick' or 'li_sparse_r' (got %r)" % (kind,))
+            raise ValueError("BRDF kind must be 'lambertian', 'rpv', 'ross_thick', 'li_sparse_r' or 'cox_munk' (got %r)" % (kind,))
         p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64))) if np.size(params) else np.zeros(0)
         return k, _ptr(p) if p.size else None, int(p.size)
 
