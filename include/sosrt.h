@@ -558,6 +558,24 @@ int sosrt_epilogue_beam_dev(sosrt_t* h, int B, const double* d_tau, const double
                             double* d_flux_down, double* d_flux_up, double* d_diffusivity, double* d_heating_rate,
                             double* d_net_toa, const double* d_sigma /*[B][L]*/);
 
+/* ---- pseudo-spherical direct beam at view lanes -----------------------------------------------------------
+ * sosrt_view_first_order_beam_dev: the first order of sosrt_first_order_beam_dev at view cosines off the direction grid -- its
+ * recurrences with a = mu_view[v] in place of |mu_m|, on the signed lanes of sosrt_view_radiance_dev, (-mu_view, +mu_view): lane j
+ * and its mirror j +- V.  q of a zone from the p0 rows at the lane, (w_atm p0_atm[j] f_atm + w_aer p0_aer[j] f_aer) / (4 pi); the
+ * two level exclusions and the reflected beam R as there; U_{L-1} = rho D_{L-1}[mirror]; no mu = 0 lane (mu_view >= 0.01); phi is
+ * exact at mu_view = mu0.  With sigma = tau / mu0 it is the d_first_out of sosrt_view_radiance_dev to rounding, but for lanes within
+ * 1e-4 of mu0, where that one takes its limit form (up to 1e-4 of the maximum apart).  Detected by symbol; SOSRT_VERSION is unchanged.
+ * nset sets of p0 rows (the azimuths of an exact first order, or 1) share one evaluation of the geometry: a lane's value is linear
+ * in (p0_atm[j], p0_aer[j], p0_atm[mirror], p0_aer[mirror]) and the kernel carries the four coefficients.  d_p0rows_* [nset][B][2V];
+ * d_first_out [nset][B][nlev][2V].  Enqueued on the handle's stream; reads the columns of the last sosrt_set_columns* and writes
+ * nothing but its output.  Refused with SOSRT_E_INVALID, a message and nothing written: what sosrt_first_order_beam_dev refuses;
+ * V, mu_view, nlev, levels outside the limits of sosrt_view_radiance_dev; a Lambertian surface; columns off aerosol set 0, a
+ * per-zone P0 layout or atmosphere phase sets; nset < 1; a null pointer. */
+int sosrt_view_first_order_beam_dev(sosrt_t* h, int B, int V, const double* mu_view /*host [V]*/, const double* d_tau /*[B][L]*/,
+                                    const double* d_sigma /*[B][L]*/, int nset, const double* d_p0rows_atm /*[nset][B][2V]*/,
+                                    const double* d_p0rows_aer /*[nset][B][2V]*/, int nlev, const int* levels /*host*/,
+                                    double* d_first_out /*[nset][B][nlev][2V]*/);
+
 /* ---- thermal emission: Planck sources in the layers and at the ground ------------------------------------
  * Every other solve is driven by the solar beam.  This stage computes the radiation the layers and the ground EMIT, the field
  * I_0 of a thermal problem; the order loop scatters and transports it as it is -- the full field is

@@ -1,18 +1,20 @@
 // Pseudo-spherical direct beam (include/sosrt.h): the slant path of the beam, the first order on a beam
-// path and the epilogue with its beam terms.  A stage beside the solve: it reads the columns of the last sosrt_set_columns* and
-// writes its outputs, nothing else -- the handle's columns, resident field, order targets and phase state stay as they were.
-// Host code.
+// path -- on the grid and at view lanes off it -- and the epilogue with its beam terms.  A stage beside the
+// solve: it reads the columns of the last sosrt_set_columns* and writes its outputs, nothing else -- the handle's columns,
+// resident field, order targets and phase state stay as they were.  Host code.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "beam.hpp"
+#include "beam_view.hpp"
 #include "handle.hpp"
 
 using namespace sosrt;
 
-// what the three entry points refuse alike; every check comes before the first launch, so a refused call writes nothing
+// what the entry points refuse alike; every check comes before the first launch, so a refused call writes nothing
 static int beam_check(sosrt_handle* h, int B, const char* what) {
     if (int e = need_gpu(h)) return e;
     if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
@@ -89,6 +91,58 @@ int sosrt_epilogue_beam_dev(sosrt_t* h, int B, const double* d_tau, const double
     EpilogueOut out{d_flux_down, d_flux_up, d_diffusivity, d_heating_rate, d_net_toa};
     launch_epilogue_beam(h->stream, h->g, h->grid.d_w, B, scalars_of(h), d_tau, d_sigma, d_I, beam_norm, d_z_profile, out);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int sosrt_view_first_order_beam_dev(sosrt_t* h, int B, int V, const double* mu_view, const double* d_tau, const double* d_sigma,
+                                    int nset, const double* d_p0rows_atm, const double* d_p0rows_aer, int nlev, const int* levels,
+                                    double* d_first_out) {
+    const char* what = "sosrt_view_first_order_beam_dev";
+    if (int e = beam_check(h, B, what)) return e;
+    // ---- the limits of sosrt_view_radiance_dev; every check comes before the first launch, so a refused call writes nothing ----
+    if (V < 1 || V > SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "%s: V=%d view cosines: must be 1..%d", what, V, SOSRT_MAX_VIEWS);
+    if (!mu_view) return fail(SOSRT_E_INVALID, "%s: null mu_view", what);
+    for (int v = 0; v < V; ++v)
+        if (!(std::isfinite(mu_view[v]) && mu_view[v] >= 0.01 && mu_view[v] <= 1))
+            return fail(SOSRT_E_INVALID, "%s: mu_view[%d] = %g: a view cosine must be finite and in [0.01, 1]", what, v, mu_view[v]);
+    if (nset < 1) return fail(SOSRT_E_INVALID, "%s: nset=%d: at least one set of p0 rows", what, nset);
+    if (nlev < 1 || !levels) return fail(SOSRT_E_INVALID, "%s: no levels", what);
+    for (int i = 0; i < nlev; ++i)
+        if (levels[i] < 0 || levels[i] >= h->L)
+            return fail(SOSRT_E_INVALID, "%s: levels[%d] = %d is outside [0, %d)", what, i, levels[i], h->L);
+    if (h->surface == SOSRT_SURFACE_LAMBERTIAN || h->surface == SOSRT_SURFACE_LAMBERTIAN_README)
+        return fail(SOSRT_E_INVALID, "%s: the first order at view cosines is not available over a Lambertian surface (the handle's "
+                                     "surface), as the view stage is not", what);
+    if (h->cols.max_set_used > 0 || h->cols.p0_zones > 0)
+        return fail(SOSRT_E_INVALID, "%s: not available with several aerosol phase sets (sosrt_set_phase_sets, sosrt_set_aerosol_sets): "
+                                     "d_p0rows_aer is one row per column", what);
+    if (h->cols.max_atm_used > 0)
+        return fail(SOSRT_E_INVALID, "%s: not available with atmosphere phase sets (sosrt_set_atm_phase_sets, sosrt_set_atmosphere_sets): "
+                                     "d_p0rows_atm is one row per column", what);
+    if (!d_tau) return fail(SOSRT_E_INVALID, "%s: null d_tau", what);
+    if (!d_sigma) return fail(SOSRT_E_INVALID, "%s: null d_sigma", what);
+    if (!d_p0rows_atm || !d_p0rows_aer) return fail(SOSRT_E_INVALID, "%s: null d_p0rows_atm or d_p0rows_aer", what);
+    if (!d_first_out) return fail(SOSRT_E_INVALID, "%s: null d_first_out", what);
+    HIPCHK(hipSetDevice(h->device));
+    prof_break(h);
+    ViewMu vm;
+    for (int j = 0; j < 2 * kMaxViews; ++j) vm.s[j] = 0;
+    for (int v = 0; v < V; ++v) { vm.s[v] = -mu_view[v]; vm.s[V + v] = mu_view[v]; }
+    // levels in chunks of kViewLevels, as the view stage takes them; within a chunk sorted by row for the sweeps' cursor
+    for (int l0 = 0; l0 < nlev; l0 += kViewLevels) {
+        BeamViewLevels lv;
+        lv.n = nlev - l0 < kViewLevels ? nlev - l0 : kViewLevels;
+        int order[kViewLevels];
+        for (int i = 0; i < lv.n; ++i) order[i] = i;
+        std::stable_sort(order, order + lv.n, [&](int x, int y) { return levels[l0 + x] < levels[l0 + y]; });
+        for (int i = 0; i < kViewLevels; ++i) {
+            lv.t[i] = i < lv.n ? levels[l0 + order[i]] : -1;
+            lv.idx[i] = i < lv.n ? order[i] : 0;
+        }
+        launch_view_first_order_beam(h->stream, h->L, B, V, nset, nlev, scalars_of(h), d_tau, d_sigma, d_p0rows_atm, d_p0rows_aer,
+                                     vm, lv, d_first_out + (size_t)l0 * 2 * V);
+        HIPCHK(hipGetLastError());
+    }
     return 0;
 }
 

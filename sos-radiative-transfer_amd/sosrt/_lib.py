@@ -100,6 +100,8 @@ SIGNATURES = {
     "sosrt_beam_slant_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "sosrt_first_order_beam_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 5),
     "sosrt_epilogue_beam_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 7),
+    "sosrt_view_first_order_beam_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int,
+                                                c_void_p, c_void_p]),
     "sosrt_emission_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 5),
     "sosrt_emission_view_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_void_p]),
     "sosrt_epilogue_emission_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 8),

@@ -158,12 +158,18 @@ EARTH_RADIUS_KM = 6371.0
 
 
 def _beam_args(beam, earth_radius, azimuths=None, view_mu=None, view_azimuths=None, mode_batch=False, mode_chunk=None,
-               first_order="coded", devices=None):
-    """Checks of the `beam` keyword, made before any handle exists: True for the pseudo-spherical beam.  The stages it refuses
-    compute first orders of their own, and those are plane closed forms."""
+               first_order="coded", devices=None, beam_stages=False):
+    """Checks of the `beam` keyword, made before any handle exists: True for the pseudo-spherical beam.  Without
+    `beam_stages=True` the stages that compute first orders of their own are refused: those are plane closed forms.  With it
+     `azimuths`, `view_mu` and `view_azimuths` take their first orders on the slant path; the mode batch stays
+    refused."""
     if not isinstance(beam, str) or beam not in ("plane", "spherical"):
         raise ValueError("beam must be 'plane' or 'spherical' (got %r)" % (beam,))
+    if not isinstance(beam_stages, (bool, np.bool_)):
+        raise ValueError("beam_stages must be True or False (got %r)" % (beam_stages,))
     if beam == "plane":
+        if beam_stages:
+            raise ValueError("beam_stages=True belongs to beam='spherical': the plane beam's stages need no keyword")
         return False
     try:
         er = float(earth_radius)
@@ -171,10 +177,13 @@ def _beam_args(beam, earth_radius, azimuths=None, view_mu=None, view_azimuths=No
         raise ValueError("earth_radius must be a number of kilometres (got %r)" % (earth_radius,)) from None
     if not (np.isfinite(er) and er > 0):
         raise ValueError("earth_radius must be finite and > 0 km (got %r)" % (earth_radius,))
-    if azimuths is not None or mode_batch or mode_chunk is not None:
+    if beam_stages and (mode_batch or mode_chunk is not None):
+        raise ValueError("beam='spherical' is not available with mode_batch / mode_chunk, also with beam_stages=True: the batched "
+                         "modes take their first orders from the order loop's plane closed form")
+    if not beam_stages and (azimuths is not None or mode_batch or mode_chunk is not None):
         raise ValueError("beam='spherical' is not available with azimuths / mode_batch: the first order of a Fourier mode m >= 1 is "
                          "the plane closed form")
-    if view_mu is not None or view_azimuths is not None:
+    if not beam_stages and (view_mu is not None or view_azimuths is not None):
         raise ValueError("beam='spherical' is not available with view_mu / view_azimuths: the first order at a view cosine is the "
                          "plane closed form")
     if first_order != "coded":
@@ -702,7 +711,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   view_mu=None, view_levels=(0, -1), view_quadrature="grid", view_azimuths=None,
                   view_first_order="exact", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None,
                   planck_surface=None, surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES,
-                  brdf_modes=False, brdf_view=False) -> BatchResult:
+                  brdf_modes=False, brdf_view=False, beam_stages=False) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -763,6 +772,16 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     is the beam's slant optical depth at every level (None for 'plane').  `beam='plane'` (default) is the code path as it
     was.  Works with phase functions by name or as arrays, `aer_set` and `save_orders`; not with `azimuths`, `view_mu`,
     `view_azimuths`, `mode_batch`, `first_order='readme'` or several `devices` (their first orders are plane closed forms).
+
+    `beam_stages=True` (opt-in, with `beam='spherical'`): THE SPHERE IN THE AZIMUTH AND VIEW STAGES.  `azimuths`,
+    `view_mu` and `view_azimuths` are then accepted, and every first order they compute is taken on the slant path of the mode-0
+    solve (`beam_slant`): on the grid the first order of every Fourier mode (`Solver.first_order_beam_device` fed the mode's P0
+    vectors, then the solve from it), at the view lanes the layer-by-layer first order at the view cosine
+    (`Solver.view_first_order_beam_device`; with `view_first_order='exact'` one call serves all azimuths).  The scattered terms
+    are plane-parallel and inherit the sphere through the field.  At mu0 = 0.21 the TOA view radiance moves by a few per cent of
+    its maximum.  I, n and beam_slant are those of the spherical call without the stages, bit for bit.  Still refused:
+    `mode_batch` / `mode_chunk`, `surface='brdf'`, `source='thermal'`, `first_order='readme'`, several `devices`.  With
+    `beam='plane'` the keyword is a ValueError.
 
     `source='thermal'`: THERMAL EMISSION instead of the solar beam (`solve_thermal`).  `planck` ([L] or [B, L]) is the Planck
     radiance at every level in any unit -- the field comes out in it (`thermal.planck_radiance` gives W m-2 sr-1 um-1) --
@@ -832,7 +851,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                         brdf_modes, brdf_view)
     if ground:
         surface, grd_alb = "specular", 0.0                   # the series' solves run over a black ground
-    spherical = _beam_args(beam, earth_radius, azimuths, view_mu, view_azimuths, mode_batch, mode_chunk, first_order, devices)
+    spherical = _beam_args(beam, earth_radius, azimuths, view_mu, view_azimuths, mode_batch, mode_chunk, first_order, devices,
+                           beam_stages)
     if view_azimuths is not None or view_first_order != "exact":
         vphi, vM, vnphi = _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_modes, nphi_modes, mode_batch,
                                              mode_chunk)
@@ -918,14 +938,14 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
         else:
             out.I_azimuth, out.mode_status = azimuth_modes(s, tau, r, mu0v, azimuths, M, nphi, lev, atm_phase_fun, g_atm, mie_atm,
                                                            aer_phase_fun, g_aer, mie_aer, device, ground=ground,
-                                                           bounce_orders=bx.get("bounce_orders"))
+                                                           bounce_orders=bx.get("bounce_orders"), sigma=sigma)
         if raise_on_error:
             _raise_status(out.mode_status, N)
     if view_mu is not None:
         mu0v = np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
         out.view_mu_signed = np.concatenate((-vmu, vmu))
         out.I_view_first, out.I_view_scattered = view_radiance(s, tau, r.I, mu0v, vmu, vlev, vquad, atm_phase_fun, g_atm, mie_atm,
-                                                               aer_phase_fun, g_aer, mie_aer, device, thermal=thermal)
+                                                               aer_phase_fun, g_aer, mie_aer, device, thermal=thermal, sigma=sigma)
         out.I_view = out.I_view_first + out.I_view_scattered
         if ground:
             out.I_view_ground = bx["I_view_ground"]
@@ -935,7 +955,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                 s, tau, r, mu0v, vmu, vlev, vquad, vphi, vM, vnphi, view_first_order, out.I_view_first, out.I_view_scattered,
                 atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer, device, ground=ground,
                 bounce_orders=bx.get("bounce_orders"),
-                ground0=bx.get("I_view_ground" if view_first_order == "modes" else "I_view_ground_diffuse"))
+                ground0=bx.get("I_view_ground" if view_first_order == "modes" else "I_view_ground_diffuse"), sigma=sigma)
             out.I_view_azimuth = out.I_view_azimuth_first + out.I_view_azimuth_scattered
             if ground:
                 out.I_view_azimuth = out.I_view_azimuth + out.I_view_azimuth_ground
@@ -1016,11 +1036,13 @@ def _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_mod
 
 
 def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
-                  mie_aer, device=0, thermal=None):
+                  mie_aer, device=0, thermal=None, sigma=None):
     """The view stage on the field `I` [B, L, 2N] of handle `s` (whose columns are set): rows of both phase functions at the
     signed lanes, then `Solver.view_radiance_device` with I_src = I.  Returns (first order, scattered), each [B, nlev, 2V].
     `thermal` = (planck [B, L], planck_surface [B], emissivity [B] or None): I is a thermal field, and the first term is the
-    emission at the view lanes (`Solver.emission_view_device`) instead of the solar first order."""
+    emission at the view lanes (`Solver.emission_view_device`) instead of the solar first order.  `sigma` [B, L] (the
+    `beam_slant` of `solve_spherical`): the first term is the first order on that beam path at the view lanes
+    (`Solver.view_first_order_beam_device`) instead of the plane closed form."""
     import torch
     B, L = tau.shape
     D, V2 = s.D, 2 * len(view_mu)
@@ -1051,6 +1073,11 @@ def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase
             d_es = None if thermal[2] is None else up(thermal[2])
             s.emission_view_device(view_mu, d_tau.data_ptr(), d_pl.data_ptr(), d_bs.data_ptr(), levels, first,
                                    0 if d_es is None else d_es.data_ptr(), B=B)
+            first = p0_atm = p0_aer = 0
+        elif sigma is not None:
+            # likewise: the first order on the slant path is this stage's own
+            d_sig = up(sigma)
+            s.view_first_order_beam_device(view_mu, d_tau.data_ptr(), d_sig.data_ptr(), p0_atm, p0_aer, levels, first, B=B)
             first = p0_atm = p0_aer = 0
         s.view_radiance_device(view_mu, d_tau.data_ptr(), d_I.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), levels,
                                d_scat_out=d_scat.data_ptr(), d_first_out=first, d_p0rows_atm=p0_atm, d_p0rows_aer=p0_aer,
@@ -1132,7 +1159,8 @@ def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=No
     from . import mie as _mie
     wl, t_aer, t_atm, m, r_m, sig = _spectrum_args(wavelengths, tauStar_aer, angstrom, lambda_ref, aer, alb_aer, tauStar_atm_ref)
     _beam_args(batch_kw.get("beam", "plane"), batch_kw.get("earth_radius", EARTH_RADIUS_KM), view_mu=batch_kw.get("view_mu"),
-               view_azimuths=batch_kw.get("view_azimuths"), first_order=batch_kw.get("first_order", "coded"))
+               view_azimuths=batch_kw.get("view_azimuths"), first_order=batch_kw.get("first_order", "coded"),
+               beam_stages=batch_kw.get("beam_stages", False))
     for k in ("P_aer", "P0_aer", "aer_phase_fun", "mie_aer", "tauStar_atm", "devices", "azimuths"):
         if k in batch_kw:
             raise ValueError("SOS_Aer_spectrum sets %s itself" % k)
@@ -1220,10 +1248,26 @@ class _ModeLoop:
     d_Im: object = None      # [B, L, 2N]: set by `begin` to the mode-0 field; after the solve of mode m, the field of mode m
     d_target: object = None  # [B] int32: the order counts of mode 0, the handle's targets while the modes are solved
     d_status: object = None  # [M, B] int32: the status of the solve of mode m in row m - 1 (set before the first mode)
+    d_sigma: object = None   # [B, L]: the beam's slant path (beam='spherical' with beam_stages=True), else None
     own: SimpleNamespace = field(default_factory=SimpleNamespace)
 
 
-def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, finish):
+def _beam_mode_first(s: Solver):
+    """The per-mode first-order hook of `_solve_modes` for a beam path c.d_sigma: the first order of mode m
+    layer by layer on that path from the mode's P0 vectors, into one buffer all modes reuse; its address is the `d_I1` of the
+    mode's solve."""
+    import torch
+    own = {}
+
+    def first(c, m, p0a, p0r):
+        if "I1" not in own:
+            own["I1"] = torch.empty((c.B, c.L, c.D), dtype=torch.float64, device=c.dev)
+        s.first_order_beam_device(c.d_tau.data_ptr(), c.d_sigma.data_ptr(), p0a, p0r, own["I1"].data_ptr(), B=c.B)
+        return own["I1"].data_ptr()
+    return first
+
+
+def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, finish, sigma=None, first=None):
     """The loop over the Fourier modes m = 1..M of the solve `r` (the mode-0 result of handle `s`, whose columns are set): per
     mode the matrices and first-order vectors of both phase functions `phases` = ((name, g, mie) of the atmosphere, of the
     aerosol), a solve with the order counts of mode 0 (sosrt_set_order_targets) into the resident c.d_Im, then `step(c, m)`.
@@ -1231,7 +1275,9 @@ def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, f
     Mie-derived function's table on the handle first: the handle holds one table at a time.  `begin(c)` runs
     before the modes are built and sets c.d_Im to the mode-0 field; `finish(c)` after the last mode, and its value is returned
     with the mode status [M + 1, B].  The handle's mode-0 phase matrices are put back and its targets cleared afterwards, also
-    on error."""
+    on error.  `sigma` [B, L]: a beam path, uploaded to c.d_sigma before `begin`.  `first(c, m, p0a, p0r)` (optional) -> the address
+    of a first order [B, L, 2N] of mode m from the mode's P0 vectors (addresses): the mode's solve starts from it (`d_I1`) instead
+    of the handle's own first order; without it the loop is the code as it was."""
     import torch
     B, L = tau.shape
     D = s.D
@@ -1244,6 +1290,8 @@ def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, f
             c.d_tau = d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
             c.d_mu0 = d_mu0 = torch.from_numpy(np.array(mu0, dtype=np.float64)).to(dev)      # (a copy: broadcast views are read-only)
             c.d_target = d_target = torch.from_numpy(np.ascontiguousarray(r.n, dtype=np.int32)).to(dev)
+            if sigma is not None:
+                c.d_sigma = torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)).to(dev)
             begin(c)
             # modes m >= 1 of both phase functions: the matrices to the host (one fold each in set_phase), the first-order
             # vectors where the solve reads them
@@ -1262,8 +1310,13 @@ def _solve_modes(s: Solver, tau, r, mu0, M, nphi, phases, device, begin, step, f
                 # the solve of mode m takes (-1)^m P^m: its contraction reads P[a][flip b], the stored matrix at phi + pi
                 sgn = -1.0 if m & 1 else 1.0
                 s.set_phase(sgn * Pm[0][m - 1], sgn * Pm[1][m - 1])
-                s.solve_device(d_tau.data_ptr(), d_P0[0][m - 1].data_ptr(), d_P0[1][m - 1].data_ptr(), c.d_Im.data_ptr(),
-                               d_n_orders=d_n.data_ptr(), d_status=d_st[m - 1].data_ptr())
+                if first is None:
+                    s.solve_device(d_tau.data_ptr(), d_P0[0][m - 1].data_ptr(), d_P0[1][m - 1].data_ptr(), c.d_Im.data_ptr(),
+                                   d_n_orders=d_n.data_ptr(), d_status=d_st[m - 1].data_ptr())
+                else:
+                    d_I1 = first(c, m, d_P0[0][m - 1].data_ptr(), d_P0[1][m - 1].data_ptr())
+                    s.solve_device(d_tau.data_ptr(), d_P0[0][m - 1].data_ptr(), d_P0[1][m - 1].data_ptr(), c.d_Im.data_ptr(),
+                                   d_I1=d_I1, d_n_orders=d_n.data_ptr(), d_status=d_st[m - 1].data_ptr())
                 step(c, m)
             s.synchronize()
             status[1:] = d_st.cpu().numpy()
@@ -1305,7 +1358,7 @@ def _mode_reflections(s: Solver, c: _ModeLoop, m, hook=None):
 
 
 def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
-                  mie_aer, device=0, ground=None, bounce_orders=None, brdf_nphi=BRDF_NPHI):
+                  mie_aer, device=0, ground=None, bounce_orders=None, brdf_nphi=BRDF_NPHI, sigma=None):
     """Modes m = 1..M of the solve `r` (the mode-0 result of handle `s`, whose columns are set): per mode the matrices and
     first-order vectors of both phase functions, a solve with the order counts of mode 0 (sosrt_set_order_targets), and the
     synthesis at `levels` (`_solve_modes` with the grid's synthesis as its step).  Returns (I_azimuth [B, nlev, 2N,
@@ -1316,7 +1369,10 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
     that solve: the BRDF GROUND'S MODES.  The operators (-1)^m R^m and beam rows r0^m of the modes 1..M are
     built once, on the `brdf_nphi` nodes of mode 0's; per mode, between its black solve and its synthesis, the reflections 1..K
     run on the resident field (`_mode_reflections`), each a solve of bounce_orders[k - 1] orders, and their statuses join the
-    mode's.  A Lambertian ground has no mode m >= 1: no reflections are run for it."""
+    mode's.  A Lambertian ground has no mode m >= 1: no reflections are run for it.
+
+    `sigma` [B, L] (the `beam_slant` of `solve_spherical`, `r` being its result): every mode's solve starts from the first order
+    on that beam path (`_beam_mode_first`)."""
     import torch
     nlev = len(levels)
     bounce = ground is not None and ground.kind != "lambertian"
@@ -1339,12 +1395,13 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
                                     o.d_out.data_ptr(), B=c.B)
 
     return _solve_modes(s, tau, r, mu0, M, nphi, ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)), device,
-                        begin, step, lambda c: c.own.d_out.cpu().numpy())
+                        begin, step, lambda c: c.own.d_out.cpu().numpy(), sigma=sigma,
+                        first=None if sigma is None else _beam_mode_first(s))
 
 
 def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azimuths, M, nphi, first_order, first0, scat0,
                        atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer, device=0, ground=None, bounce_orders=None,
-                       ground0=None, brdf_nphi=BRDF_NPHI):
+                       ground0=None, brdf_nphi=BRDF_NPHI, sigma=None):
     """The view stage per Fourier mode: mode 0 is (`first0`, `scat0`), the result of `view_radiance` on
     r.I; per mode m >= 1 `_solve_modes` leaves the field I^m resident, `Solver.view_radiance_device` runs on it with the rows
     (-1)^m rows^m and p0rows^m of both phase functions (built for all modes once, before the loop), and the synthesis adds
@@ -1359,7 +1416,12 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
     (`Solver.view_ground_device`).  `ground0` [B, nlev, 2V] is mode 0's ground term from `solve_brdf`: with first_order
     'exact' its diffuse part -- the beam's single reflection is then rho(mu_view, mu0, phi) at the azimuth itself, written once
     per azimuth, and the modes carry the diffuse part only -- with 'modes' the whole, and the modes add rho^m(mu_view, mu0).  A
-    Lambertian ground has no mode m >= 1.  The third value is then the ground's term [B, nlev, 2V, len(azimuths)]."""
+    Lambertian ground has no mode m >= 1.  The third value is then the ground's term [B, nlev, 2V, len(azimuths)].
+
+    `sigma` [B, L] (the `beam_slant` of `solve_spherical`; `r`, `first0` and `scat0` from it): THE SPHERE IN THE STAGE (DESIGN
+    section 27).  Every mode's solve starts from the first order on that beam path, and the first order at the view lanes is
+    `Solver.view_first_order_beam_device` on it: per mode with p0rows^m ('modes'), or ONE call with the azimuths as its sets
+    ('exact'), which evaluates the lanes' geometry once."""
     import torch
     V2, nlev, nout = 2 * len(view_mu), len(levels), len(azimuths)
     sgn = np.concatenate((-view_mu, view_mu))
@@ -1427,11 +1489,15 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
         o = c.own
         if bounce:
             _mode_reflections(s, c, m, hook=lambda k, src: view_ground(c, m, k, src))
+        plane_first = modes_first and sigma is None
+        if modes_first and sigma is not None:
+            s.view_first_order_beam_device(view_mu, c.d_tau.data_ptr(), c.d_sigma.data_ptr(), o.p0rows[0][m - 1].data_ptr(),
+                                           o.p0rows[1][m - 1].data_ptr(), levels, o.d_first.data_ptr(), B=c.B)
         s.view_radiance_device(view_mu, c.d_tau.data_ptr(), c.d_Im.data_ptr(), o.rows[0][m - 1].data_ptr(),
                                o.rows[1][m - 1].data_ptr(), levels, d_scat_out=o.d_scat.data_ptr(),
-                               d_first_out=o.d_first.data_ptr() if modes_first else 0,
-                               d_p0rows_atm=o.p0rows[0][m - 1].data_ptr() if modes_first else 0,
-                               d_p0rows_aer=o.p0rows[1][m - 1].data_ptr() if modes_first else 0, quadrature=quadrature, B=c.B)
+                               d_first_out=o.d_first.data_ptr() if plane_first else 0,
+                               d_p0rows_atm=o.p0rows[0][m - 1].data_ptr() if plane_first else 0,
+                               d_p0rows_aer=o.p0rows[1][m - 1].data_ptr() if plane_first else 0, quadrature=quadrature, B=c.B)
         accumulate(c, m)
 
     def finish(c):
@@ -1440,10 +1506,15 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
             first = o.d_out_first.cpu().numpy()
         else:
             d_f = torch.empty((nout, c.B, nlev, V2), dtype=torch.float64, device=c.dev)
-            for i in range(nout):
-                s.view_radiance_device(view_mu, c.d_tau.data_ptr(), 0, 0, 0, levels, d_first_out=d_f[i].data_ptr(),
-                                       d_p0rows_atm=o.p0exact[0][i].data_ptr(), d_p0rows_aer=o.p0exact[1][i].data_ptr(),
-                                       quadrature=quadrature, B=c.B)
+            if sigma is not None:
+                # the azimuths as the sets of one call: a lane's geometry does not depend on the azimuth
+                s.view_first_order_beam_device(view_mu, c.d_tau.data_ptr(), c.d_sigma.data_ptr(), o.p0exact[0].data_ptr(),
+                                               o.p0exact[1].data_ptr(), levels, d_f.data_ptr(), nset=nout, B=c.B)
+            else:
+                for i in range(nout):
+                    s.view_radiance_device(view_mu, c.d_tau.data_ptr(), 0, 0, 0, levels, d_first_out=d_f[i].data_ptr(),
+                                           d_p0rows_atm=o.p0exact[0][i].data_ptr(), d_p0rows_aer=o.p0exact[1][i].data_ptr(),
+                                           quadrature=quadrature, B=c.B)
             s.synchronize()
             first = d_f.permute(1, 2, 3, 0).contiguous().cpu().numpy()   # (the azimuth last, as the synthesis writes it)
         gr = None
@@ -1460,7 +1531,8 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
         return first, o.d_out_scat.cpu().numpy(), gr
 
     (first, scat, gr), status = _solve_modes(s, tau, r, mu0, M, nphi, ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)),
-                                             device, begin, step, finish)
+                                             device, begin, step, finish, sigma=sigma,
+                                             first=None if sigma is None else _beam_mode_first(s))
     return first, scat, gr, status
 
 

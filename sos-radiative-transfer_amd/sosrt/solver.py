@@ -416,6 +416,19 @@ class Solver:
                                             0 if beam_norm == "crit" else 1, _vp(d_z), _vp(d_flux_down), _vp(d_flux_up),
                                             _vp(d_diffusivity), _vp(d_heating_rate), _vp(d_net_toa), _vp(d_sigma)))
 
+    def view_first_order_beam_device(self, mu_view, d_tau: int, d_sigma: int, d_p0rows_atm: int, d_p0rows_aer: int, levels,
+                                     d_first_out: int, nset: int = 1, B: Optional[int] = None):
+        """`first_order_beam_device` at the view cosines `mu_view` [V] (host, each in [0.01, 1], V <= 64) and the rows `levels`
+        (DESIGN section 27): d_first_out [nset, B, nlev, 2V] on the signed lanes (-mu_view, +mu_view) from the p0 rows
+        d_p0rows_atm, d_p0rows_aer [nset, B, 2V] (the azimuths of an exact first order, or one set); the geometry of a lane is
+        evaluated once for all sets.  Specular or no surface."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
+        lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.int32)
+        check(lib().sosrt_view_first_order_beam_dev(self._h, int(self.B if B is None else B), int(m.size),
+                                                    _ptr(m) if m.size else None, _vp(d_tau), _vp(d_sigma), int(nset),
+                                                    _vp(d_p0rows_atm), _vp(d_p0rows_aer), int(lev.size),
+                                                    _ptr(lev) if lev.size else None, _vp(d_first_out)))
+
     # ---- thermal emission (sosrt.h; DESIGN section 18) ----------------------------------------------
     def emission_device(self, d_tau: int, d_planck: int, d_planck_surface: int, d_I0_out: int, d_emissivity: int = 0,
                         B: Optional[int] = None):
