@@ -508,6 +508,46 @@ int sosrt_phase_p0_rows_azimuth_dev(sosrt_t* h, int B, int kind, double g, const
 int sosrt_view_azimuth_accumulate_dev(sosrt_t* h, int B, int m, int nlev, int V2, const double* d_val /*[B][nlev][V2]*/,
                                       int nphi_out, const double* d_phi /*[nphi_out]*/, double* d_out /*[B][nlev][V2][nphi_out]*/);
 
+/* ---- delta-M scaling of a forward-peaked phase function, with a TMS first order -----------------------
+ * The builders sample a phase function at the 2N nodes of the grid through a 25-node azimuth ring; a function whose forward
+ * peak is narrower than the grid (the cloud table fwc: p(1) / mean = 5e4) is not held by that quadrature.  Delta-M (Wiscombe
+ * 1977) replaces it by the Legendre series truncated at order Lambda with the fraction f = chi_Lambda of the scattering moved
+ * into the direct beam: the truncated table is smooth, the optical depth and albedo of the aerosol are scaled by the caller
+ * (tau' = tau (1 - w f), w' = (1 - f) w / (1 - w f)), and the solve is an ordinary solve.  Detected by symbol; SOSRT_VERSION
+ * is unchanged.
+ *
+ * sosrt_phase_moments[_dev]: chi[s][l] = int p~ P_l dx / int p~ dx, l = 0 .. lmax, of S tables tab_p [S][ntab] on one abscissa
+ * tab_mu [ntab] (ascending; NULL: the uniform abscissa of sosrt_phase_table_dev), p~ the table's piecewise-linear interpolant
+ * -- the function the builders read -- so chi[s][0] = 1; norm[s] (may be NULL) = 1/2 int p~ dx.  The rule is the definition:
+ * 4-node Gauss-Legendre on every table interval, P_l by the upward recurrence P_{l+1} = a_l x P_l - b_l P_{l-1}, a_l =
+ * (2l + 1) / (l + 1), b_l = l / (l + 1); exact to rounding for l <= 6.  Sums run in a fixed order that ntab and lmax set (no
+ * floating-point atomics): the same call gives the same bits, and table s of a batch the bits of its single call.
+ *
+ * sosrt_phase_delta_m[_dev]: f[s] = chi[s][order] and tab_out[s][i] = sum_{l < order} (2l + 1) (chi[s][l] - f) / (1 - f)
+ * P_l(x_i), l ascending, on the same abscissa: the table of the truncated function, normalised like the moments (its mean
+ * over [-1, 1] is 1).  A slightly negative f (a converged series) is accepted.  f_out may be NULL.
+ *
+ * Caps: 2 <= ntab <= SOSRT_DELTAM_MAX_NTAB, 1 <= lmax <= SOSRT_DELTAM_MAX_LMAX, 1 <= order <= lmax, 1 <= S <= 65535; beyond
+ * them, for |f| >= 1 - 1e-6 and for a moment that is not finite: SOSRT_E_INVALID, a message, nothing written.  The host forms
+ * also refuse a tab_mu that is not strictly ascending.  _dev: every pointer is a device pointer and the work is enqueued on
+ * the handle's stream; sosrt_phase_delta_m_dev copies the S (lmax + 1) moments to the host for its refusals and waits for them.
+ *
+ * sosrt_phase_p0_normaliser_dev: d_Z_out[b] = Z0_b, the 25-node normaliser sosrt_phase_p0_rows_azimuth_dev divides by, and
+ * nothing else: point values of one function times Z0 / Z0' carry the normaliser of another -- the TMS first order takes the
+ * exact table's values with the truncated table's normaliser.  (Isotropic: 1, the value the rule gives.) */
+#define SOSRT_DELTAM_MAX_NTAB 65536
+#define SOSRT_DELTAM_MAX_LMAX 128
+int sosrt_phase_moments(sosrt_t* h, int S, const double* tab_mu /*[ntab] or NULL*/, const double* tab_p /*[S][ntab]*/, int ntab,
+                        int lmax, double* chi_out /*[S][lmax + 1]*/, double* norm_out /*[S] or NULL*/);
+int sosrt_phase_moments_dev(sosrt_t* h, int S, const double* d_tab_mu /*[ntab] or NULL*/, const double* d_tab_p /*[S][ntab]*/,
+                            int ntab, int lmax, double* d_chi_out /*[S][lmax + 1]*/, double* d_norm_out /*[S] or NULL*/);
+int sosrt_phase_delta_m(sosrt_t* h, int S, const double* chi /*[S][lmax + 1]*/, int lmax, int order,
+                        const double* tab_mu /*[ntab] or NULL*/, int ntab, double* tab_out /*[S][ntab]*/, double* f_out /*[S] or NULL*/);
+int sosrt_phase_delta_m_dev(sosrt_t* h, int S, const double* d_chi /*[S][lmax + 1]*/, int lmax, int order,
+                            const double* d_tab_mu /*[ntab] or NULL*/, int ntab, double* d_tab_out /*[S][ntab]*/,
+                            double* d_f_out /*[S] or NULL*/);
+int sosrt_phase_p0_normaliser_dev(sosrt_t* h, int B, int kind, double g, const double* d_mu0 /*[B]*/, double* d_Z_out /*[B]*/);
+
 /* ---- pseudo-spherical direct beam: the slant path of the beam, first order and flux terms on it ---------
  * Every solve attenuates the direct solar beam as exp(-tau / mu0), the plane-parallel secant law; at low sun that is the largest
  * physical error of the path (at mu0 = 0.21 the converged field of the EVA column moves by 6.7 % of its maximum).  In the

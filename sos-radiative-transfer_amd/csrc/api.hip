@@ -203,6 +203,7 @@ int sosrt_destroy(sosrt_t* h) {
         h->cols.d_Wmix.release(); h->cols.d_Wmix_s.release(); h->cols.d_Wmix32.release(); h->cols.d_P0rz.release();
         h->phase.d_Wrsets.release(); h->phase.d_Wrsets_s.release(); h->phase.d_Wasets.release(); h->phase.d_lrUsets.release();
         h->phase.d_lrVsets.release(); h->phase.d_lrranks.release(); h->pf.d_modetab.release(); h->pf.d_mie.release(); h->pf.h_mie.release();
+        h->pf.d_deltam.release();
         h->view.d_fold.release(); h->view.d_S.release(); h->view.d_rc.release(); h->view.d_desc.release();
         for (auto& e : h->view.ev)
             if (e) hipEventDestroy(e);

@@ -278,6 +278,7 @@ struct sosrt_handle {
         sosrt::GrowBuf<char, true> h_mie;
         hipEvent_t mie_ev = nullptr, mie_t[4] = {nullptr, nullptr, nullptr, nullptr};
         bool mie_timed = false;
+        sosrt::GrowBuf<double> d_deltam;     // delta-M (api_deltam.hip): the chunks' partial moments, or the series' coefficients
     } pf;
 
     struct View {                        // view radiance (api_view.hip): scratch of its own, so that the stage leaves the handle as it was

@@ -11,6 +11,9 @@
 //   k_phase_p0_azimuth
 //                     p(c(s_j, mu0_b, phi_i)) / Z0_b: the first-order phase value at a view lane and an azimuth, the sum the modes
 //                     of P0 converge to, with the normaliser of the plain P0 rows.
+//   k_phase_p0_normaliser
+//                     Z0_b itself and nothing else: what rescales point values of one function by the normaliser of another (the
+//                     TMS first order of DESIGN section 28).
 //
 // The normalisation is a policy with one owner: normaliser() is the reference's trapz over the 2N grid exits of the m = 0 ring
 // of a second direction, Constants<SECOND> holds the factor in front of the ring and the rescaling by the normaliser.  A row at
@@ -172,6 +175,17 @@ __global__ __launch_bounds__(256) void k_phase_p0_azimuth(Grid g, ViewMu vm, Pha
     }
 }
 
+// out[b] = Z0_b, the normaliser k_phase_p0_azimuth divides by (for the isotropic function, which that kernel does not
+// normalise, the value the rule gives: 1): one workgroup per column
+__global__ __launch_bounds__(256) void k_phase_p0_normaliser(Grid g, PhaseJob job, PHASE_JOB_ARRAYS) {
+    const PhaseJob a = with_arrays(job, w, cosphi, wq, mu0, phi, out);
+    __shared__ double s_red[8];
+    const double c0 = a.mu0[blockIdx.x];
+    const double s0 = sqrt(1 - c0 * c0);
+    const double norm = normaliser<MU0, 0>(g, a, 0, c0, s0, s_red, [](int, const double(&)[1]) {});
+    if (threadIdx.x == 0) a.out[blockIdx.x] = norm;
+}
+
 // accumulators of the mode builders: the m = 0 ring plus mc modes, rounded up to a compiled size (column of the table below)
 int modes_dispatch(int mc) { return mc == 0 ? 0 : mc + 1 <= 9 ? 1 : mc + 1 <= 17 ? 2 : mc + 1 <= 33 ? 3 : 4; }
 
@@ -193,6 +207,11 @@ void launch_phase_builder(hipStream_t s, const Grid& g, const ViewMu* vm, const 
     const auto kernel = job.phi ? k_phase_p0_azimuth : kernels[job.mu0 ? MU0 : COLUMN][job.V2 ? LANES : NODES][modes_dispatch(job.m_count)];
     hipLaunchKernelGGL(kernel, dim3(job.mu0 ? job.B : g.D), dim3(256), 0, s, g, vm ? *vm : ViewMu{}, job, job.w, job.cosphi, job.wq,
                        job.mu0, job.phi, job.out);
+}
+
+void launch_phase_p0_normaliser(hipStream_t s, const Grid& g, const PhaseJob& job) {
+    hipLaunchKernelGGL(k_phase_p0_normaliser, dim3(job.B), dim3(256), 0, s, g, job, job.w, job.cosphi, job.wq, job.mu0, job.phi,
+                       job.out);
 }
 
 }  // namespace sosrt

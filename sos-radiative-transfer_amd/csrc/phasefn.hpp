@@ -98,5 +98,8 @@ struct PhaseJob {
 };
 // vm may be null where V2 == 0
 void launch_phase_builder(hipStream_t s, const Grid& g, const ViewMu* vm, const PhaseJob& job);
+// out [B] = the normaliser of the plain P0 rows of the columns mu0 [B] (the plain ring): the Z0_b of the point values above,
+// and nothing else
+void launch_phase_p0_normaliser(hipStream_t s, const Grid& g, const PhaseJob& job);
 
 }  // namespace sosrt

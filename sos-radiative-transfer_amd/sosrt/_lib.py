@@ -97,6 +97,11 @@ SIGNATURES = {
     "sosrt_phase_p0_rows_modes_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_phase_p0_rows_azimuth_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_view_azimuth_accumulate_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "sosrt_phase_moments": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sosrt_phase_moments_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sosrt_phase_delta_m": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "sosrt_phase_delta_m_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "sosrt_phase_p0_normaliser_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
     "sosrt_beam_slant_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "sosrt_first_order_beam_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 5),
     "sosrt_epilogue_beam_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 7),

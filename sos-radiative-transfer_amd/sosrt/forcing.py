@@ -20,7 +20,8 @@ from __future__ import annotations
 import numpy as np
 
 from .inputs import direction_grid, phase_function, slab_indices, tau_profile
-from .main import EARTH_RADIUS_KM, _beam_args, _brdf_args, _raise_unconverged, get_solver, solve_brdf, solve_spherical
+from .main import (EARTH_RADIUS_KM, _beam_args, _brdf_args, _delta_m_aerosol, _delta_m_args, _raise_unconverged, device_phase,
+                   get_solver, solve_brdf, solve_spherical)
 
 
 def _net_flux_columns(tau, idx_up, idx_down, mu, mu0, grd_alb, alb_atm, alb_aer, dtau_atm, dtau_aer, tauStar_tot, P_atm, P_aer,
@@ -118,18 +119,33 @@ def _solve_fluxes(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, geom
 
 def toa_net_flux(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, z0=120, z_up=25, z_down=17, nb_layers=200,
                  nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, phases=None,
-                 max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, surface="specular", brdf=None):
+                 max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, surface="specular", brdf=None, delta_m=None,
+                 mie_aer=None):
     """Net flux at the top of the atmosphere, -F_down[0] - F_up[0] (crit:377-382), for arrays of
     (tauStar_aer, alb_aer).  beam='spherical' (with `earth_radius`, km): the direct beam on its slant path through spherical
     shells, in the solve and in the flux's beam terms (main.SOS_Aer_batch); `radiative_forcing` and `critical_albedo` pass
     both keywords on.  surface='brdf' with `brdf` ('lambertian', ('rpv', rho0, k, theta), ('ross_li', f_iso, f_vol, f_geo[,
     mu_floor]), ('cox_munk', wind_speed[, refractive_index[, f_iso[, f_glint[, shadow]]]]) or arrays (R, r0)): the BRDF ground of main.SOS_Aer_batch, grd_alb its scale; `radiative_forcing` and
-    `critical_albedo` pass these on too."""
+    `critical_albedo` pass these on too.  `delta_m=Lambda` (2 .. 128; `mie_aer` as in main.SOS_Aer_batch): the aerosol
+    delta-M-scaled -- its phase arrays from the truncated table, built on the device, and tauStar_aer and
+    alb_aer scaled per column; the flux is the epilogue's on the scaled column, whose direct beam contains the forward-scattered
+    light.  Not with `phases`, beam='spherical' or surface='brdf'.  `radiative_forcing` and `critical_albedo` pass it on: the
+    bisection runs on the unscaled albedo."""
+    dm = _delta_m_args(delta_m, aer_phase_fun, P_aer=None if phases is None else phases[3], surface=surface, beam=beam)
     _beam_args(beam, earth_radius)
     if surface not in ("specular", "brdf"):
         raise ValueError("surface must be 'specular' or 'brdf' (got %r)" % (surface,))
     _brdf_args(surface, brdf, grd_alb, nb_angles, int(np.broadcast(np.atleast_1d(tauStar_aer), np.atleast_1d(alb_aer)).size), beam=beam)
     ta, wa = np.broadcast_arrays(np.atleast_1d(np.asarray(tauStar_aer, dtype=float)), np.atleast_1d(np.asarray(alb_aer, dtype=float)))
+    if dm is not None:
+        mu = direction_grid(nb_angles)
+        s = get_solver(int(nb_layers), int(nb_angles), ta.size, max_orders, device)
+        if not s.same_grid(mu):
+            s.set_grid(mu)
+        P0a, Pa = device_phase(s, atm_phase_fun, [mu0], g_atm)
+        phase, ta, wa = _delta_m_aerosol(s, dm, aer_phase_fun, g_aer, mie_aer, ta, wa, device)
+        P0r, Pr = device_phase(s, phase[0], [mu0], phase[1], phase[2])
+        phases = (P0a[0], Pa, P0r[0], Pr)
     if phases is None:
         mu = direction_grid(nb_angles)
         P0a, Pa = phase_function(atm_phase_fun, nb_angles, mu, mu0, g_atm)

@@ -44,6 +44,9 @@ class ColumnResult:
     bounce_ratio: Optional[float] = None      # ... and the last term's share of the sum
     black_sky_albedo: Optional[float] = None  # (brdf=('ross_li', ...) or ('cox_munk', ...)): the ground's directional-hemispherical reflectance at mu0
     white_sky_albedo: Optional[float] = None  # ... and its bihemispherical reflectance, both on the grid's trapezoid
+    delta_m_f: Optional[float] = None           # (delta_m=...): the truncated fraction f = chi_Lambda of the aerosol's scattering
+    tauStar_aer_scaled: Optional[float] = None  # ... the aerosol optical depth the column was solved with
+    alb_aer_scaled: Optional[float] = None      # ... and its single-scattering albedo
 
 
 @dataclass
@@ -74,6 +77,9 @@ class BatchResult:
     I_view_azimuth_ground: Optional[np.ndarray] = None  # [B, nlev, 2V, len(view_azimuths)] the same at (lane, azimuth), a term of I_view_azimuth
     black_sky_albedo: Optional[np.ndarray] = None  # [B] (brdf=('ross_li', ...) or ('cox_munk', ...)): the ground's directional-hemispherical reflectance at mu0
     white_sky_albedo: Optional[np.ndarray] = None  # [B] ... and its bihemispherical reflectance, both on the grid's trapezoid
+    delta_m_f: Optional[float] = None                  # (delta_m=...): the truncated fraction f = chi_Lambda of the aerosol's scattering
+    tauStar_aer_scaled: Optional[np.ndarray] = None    # [B] ... the aerosol optical depth the columns were solved with
+    alb_aer_scaled: Optional[np.ndarray] = None        # [B] ... and its single-scattering albedo
 
 
 _solvers = {}
@@ -192,6 +198,54 @@ def _beam_args(beam, earth_radius, azimuths=None, view_mu=None, view_azimuths=No
     if devices is not None and len(devices) > 1:
         raise ValueError("beam='spherical' is not available with devices=[...]: solve each shard with SOS_Aer_batch(device=...)")
     return True
+
+
+def _delta_m_args(delta_m, aer_phase_fun="hg", azimuths=None, aer_set=None, P_aer=None, P0_aer=None, mode_batch=False,
+                  mode_chunk=None, surface="specular", beam="plane", source="solar", first_order="coded", devices=None):
+    """Checks of the `delta_m` keyword, made before any handle exists: None, or a namespace with the order Lambda that
+    `_prepare_batch` fills (f, the truncated table, the scaled optics).  What has no delta-M form yet is refused."""
+    if delta_m is None:
+        return None
+    from .deltam import check_order
+    order = check_order(delta_m)
+    no = lambda what, why: ValueError("delta_m is not available with %s: %s" % (what, why))
+    if aer_set is not None or isinstance(aer_phase_fun, (list, tuple)):
+        raise no("aer_set / a list of aerosols", "one aerosol is truncated per call")
+    if P_aer is not None or P0_aer is not None:
+        raise no("P_aer / P0_aer arrays", "the moments are taken of a named phase function")
+    if aer_phase_fun in ("iso", "rayleigh"):
+        raise ValueError("delta_m is for a forward-peaked aerosol: %r has no peak to truncate" % (aer_phase_fun,))
+    if azimuths is not None:
+        raise no("azimuths", "the grid's synthesis has no exact first order; view_mu with view_azimuths has the TMS one")
+    if mode_batch or mode_chunk is not None:
+        raise no("mode_batch / mode_chunk", "they belong to azimuths")
+    if surface == "brdf":
+        raise no("surface='brdf'", "the ground's series reflects the unscaled beam")
+    if beam != "plane":
+        raise no("beam='spherical'", "the slant path is not scaled")
+    if source != "solar":
+        raise no("source='thermal'", "emission has no beam to move the forward peak into")
+    if first_order != "coded":
+        raise no("first_order='readme'", "the README's first order is not scaled")
+    if devices is not None and len(devices) > 1:
+        raise no("devices=[...]", "solve each shard with SOS_Aer_batch(device=...)")
+    return SimpleNamespace(order=order)
+
+
+def _delta_m_aerosol(s: Solver, dm, aer_phase_fun, g_aer, mie_aer, tauStar_aer, alb_aer, device):
+    """Delta-M of the aerosol on handle `s` (whose grid is set), into the namespace `dm` of `_delta_m_args`: f, the exact
+    function as `_phase_kind` takes it, the truncated one as the named table ('table', 0, dict(table=...)) every later builder
+    of the call resolves, and the scaled optics.  Returns (the truncated function's (name, g, mie), tauStar_aer', alb_aer')."""
+    from .deltam import delta_m, scale_optics
+    with _on_torch_stream(s, device):
+        dm.f, _, keep = delta_m(s, aer_phase_fun, dm.order, g_aer, mie_aer)
+        table = (keep["tab_mu"].cpu().numpy(), keep["truncated"].cpu().numpy())
+        exact = None if keep["exact"] is None else keep["exact"].cpu().numpy()
+    # (the exact function with mean 1 over [-1, 1], as the truncated one has: HG is, a table is divided by its norm)
+    dm.exact = (aer_phase_fun, g_aer, mie_aer) if exact is None else ("table", 0.0, dict(table=(table[0], exact)))
+    dm.phase = ("table", 0.0, dict(table=table))
+    dm.tauStar_aer, dm.alb_aer = scale_optics(tauStar_aer, alb_aer, dm.f)
+    return dm.phase, dm.tauStar_aer, dm.alb_aer
 
 
 def _solve_resident(s: Solver, tau, P0a, P0r, seed, epilogue, tol=1e-4, save_orders=False, device=0, fetch_field=True, want=(),
@@ -711,7 +765,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   view_mu=None, view_levels=(0, -1), view_quadrature="grid", view_azimuths=None,
                   view_first_order="exact", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None,
                   planck_surface=None, surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES,
-                  brdf_modes=False, brdf_view=False, beam_stages=False) -> BatchResult:
+                  brdf_modes=False, brdf_view=False, beam_stages=False, delta_m=None) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -841,7 +895,27 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     single reflection -- the largest carrier of RPV's hot spot -- from rho(mu_view, mu0, phi) at the azimuth itself, and the modes
     then carry the diffuse part only; `'modes'` sums rho^m(mu_view, mu0).  I, n, status, bounces, bounce_ratio and bounce_orders
     are those of the call without `view_mu`, I_view* those of the call without `view_azimuths`, bit for bit.  Not with the array
-    form (R, r0), `azimuths`, `brdf_modes`, `mode_batch`, `aer_set` or phase arrays."""
+    form (R, r0), `azimuths`, `brdf_modes`, `mode_batch`, `aer_set` or phase arrays.
+
+    `delta_m=Lambda` (2 .. 128; default None, the code path as it was): DELTA-M SCALING OF A FORWARD-PEAKED AEROSOL (DESIGN section
+    28; `sosrt.deltam`).  The Legendre moments chi_l of the aerosol's phase function are taken on the device, the fraction f =
+    chi_Lambda of its scattering is counted as unscattered, and the columns are solved with the table of the series truncated at
+    Lambda -- sum over l < Lambda of (2l + 1) (chi_l - f) / (1 - f) P_l -- and the aerosol's tauStar_aer (1 - alb_aer f) and
+    (1 - f) alb_aer / (1 - alb_aer f): an ordinary solve of a smooth function, in far fewer orders, and for a function the grid's
+    quadrature does not hold (the cloud table 'fwc') the one that solves at all.  I, tau, fluxes and heating rates are those of
+    the SCALED column: its direct beam contains the forward-scattered light, which is the method.  BatchResult.delta_m_f,
+    tauStar_aer_scaled and alb_aer_scaled [B] say what was solved.  With `view_mu` the first order is the truncated function's,
+    the ring mean: TMS is not applied to the azimuth mean.  With `view_mu` and `view_azimuths`, `n_modes` defaults to Lambda - 1,
+    where the azimuth series of the truncated function ends, and `view_first_order='exact'` is the TMS FIRST ORDER (Nakajima &
+    Tanaka 1988): the aerosol's values at (lane, azimuth) come from the exact function, divided by (1 - f), with the normaliser
+    of the truncated table -- the grid's quadrature correction for the function the solve sees; `'modes'` stays the truncated
+    series.  For a named aerosol 'hg' / 'fwc' / 'table' / 'mie' / 'eva' / 'wildfire'; not with `azimuths`, `aer_set` or lists,
+    `P_aer` / `P0_aer`, `mode_batch`, `surface='brdf'`, `beam='spherical'`, `source='thermal'`, `first_order='readme'` or
+    several `devices`."""
+    dm = _delta_m_args(delta_m, aer_phase_fun, azimuths, aer_set, P_aer, P0_aer, mode_batch, mode_chunk, surface, beam, source,
+                       first_order, devices)
+    if dm is not None and view_azimuths is not None and n_modes is None:
+        n_modes = dm.order - 1                               # where the azimuth series of the truncated function ends
     thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
                             _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if source == "thermal" else 0,
                             nb_layers, azimuths, view_azimuths, mode_batch, mode_chunk, beam, first_order, devices)
@@ -903,7 +977,9 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     s, tau, P0a, P0r, mu, iu, idn, N = _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
                                                       nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm,
                                                       mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device,
-                                                      aer_set=aer_set)
+                                                      aer_set=aer_set, delta_m=dm)
+    if dm is not None:
+        aer_phase_fun, g_aer, mie_aer = dm.phase             # what the view stages resolve: the truncated table
     sigma = None
     bx = {}
     try:
@@ -927,8 +1003,10 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     out = BatchResult(I=r.I, n=r.n, status=r.status, tau=tau, mu=mu, idx_up=iu, idx_down=idn, I_saved=r.I_saved, beam_slant=sigma,
                       bounces=bx.get("bounces"), bounce_ratio=bx.get("bounce_ratio"), bounce_orders=bx.get("bounce_orders"),
                       black_sky_albedo=bx.get("black_sky_albedo"), white_sky_albedo=bx.get("white_sky_albedo"))
+    if dm is not None:
+        out.delta_m_f, out.tauStar_aer_scaled, out.alb_aer_scaled = dm.f, dm.tauStar_aer, dm.alb_aer
     if azimuths is not None:
-        mu0v = np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
+        mu0v =np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
         if mode_batch:
             L_ = tau.shape[1]
             colargs = (np.full(tau.shape[0], iu), np.full(tau.shape[0], idn), cols[0], cols[2], cols[4], cols[5], cols[3] / L_,
@@ -955,7 +1033,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                 s, tau, r, mu0v, vmu, vlev, vquad, vphi, vM, vnphi, view_first_order, out.I_view_first, out.I_view_scattered,
                 atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer, device, ground=ground,
                 bounce_orders=bx.get("bounce_orders"),
-                ground0=bx.get("I_view_ground" if view_first_order == "modes" else "I_view_ground_diffuse"), sigma=sigma)
+                ground0=bx.get("I_view_ground" if view_first_order == "modes" else "I_view_ground_diffuse"), sigma=sigma, tms=dm)
             out.I_view_azimuth = out.I_view_azimuth_first + out.I_view_azimuth_scattered
             if ground:
                 out.I_view_azimuth = out.I_view_azimuth + out.I_view_azimuth_ground
@@ -1153,7 +1231,8 @@ def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=No
     bits of the loop while both take the single pass.  The matrices stay on the device: `Solver.phase_matrix_device` writes
     them where `Solver.set_phase_sets_device` folds them.
     `beam='spherical'` and `earth_radius` are passed on like every further keyword: each wavelength's batch is then solved with
-    the pseudo-spherical direct beam, and its BatchResult carries `beam_slant`.
+    the pseudo-spherical direct beam, and its BatchResult carries `beam_slant`.  `delta_m` is refused: the batches take their
+    aerosol as arrays.
     Returns (list of BatchResult, one per wavelength; bulk [W, 3]: albedo, asymmetry parameter, mean extinction cross-section)."""
     import torch
     from . import mie as _mie
@@ -1164,6 +1243,9 @@ def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=No
     for k in ("P_aer", "P0_aer", "aer_phase_fun", "mie_aer", "tauStar_atm", "devices", "azimuths"):
         if k in batch_kw:
             raise ValueError("SOS_Aer_spectrum sets %s itself" % k)
+    if batch_kw.get("delta_m") is not None:
+        raise ValueError("delta_m is not available with SOS_Aer_spectrum: it hands P_aer / P0_aer arrays to every batch; call "
+                         "SOS_Aer_batch(delta_m=...) per wavelength")
     m = np.array([_mie.refractive_index(v, indx_convention) for v in m])
     mu0v, _ = np.broadcast_arrays(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), np.atleast_1d(np.asarray(grd_alb, dtype=np.float64)))
     L, N, W = int(nb_layers), int(nb_angles), wl.size
@@ -1401,7 +1483,7 @@ def azimuth_modes(s: Solver, tau, r, mu0, azimuths, M, nphi, levels, atm_phase_f
 
 def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azimuths, M, nphi, first_order, first0, scat0,
                        atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer, device=0, ground=None, bounce_orders=None,
-                       ground0=None, brdf_nphi=BRDF_NPHI, sigma=None):
+                       ground0=None, brdf_nphi=BRDF_NPHI, sigma=None, tms=None):
     """The view stage per Fourier mode: mode 0 is (`first0`, `scat0`), the result of `view_radiance` on
     r.I; per mode m >= 1 `_solve_modes` leaves the field I^m resident, `Solver.view_radiance_device` runs on it with the rows
     (-1)^m rows^m and p0rows^m of both phase functions (built for all modes once, before the loop), and the synthesis adds
@@ -1421,7 +1503,12 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
     `sigma` [B, L] (the `beam_slant` of `solve_spherical`; `r`, `first0` and `scat0` from it): THE SPHERE IN THE STAGE (DESIGN
     section 27).  Every mode's solve starts from the first order on that beam path, and the first order at the view lanes is
     `Solver.view_first_order_beam_device` on it: per mode with p0rows^m ('modes'), or ONE call with the azimuths as its sets
-    ('exact'), which evaluates the lanes' geometry once."""
+    ('exact'), which evaluates the lanes' geometry once.
+
+    `tms` (the namespace of `_delta_m_args`; the aerosol of the call is its truncated table): THE TMS FIRST ORDER (DESIGN section
+    28).  With first_order 'exact' the aerosol's point values are those of the exact function `tms.exact`, divided by 1 - tms.f,
+    with the normaliser of the truncated table: exact / Z_exact from `Solver.phase_p0_rows_azimuth_device`, times Z_exact /
+    Z_trunc from two calls of `Solver.p0_normaliser_device`.  Everything else is the stage on the truncated function."""
     import torch
     V2, nlev, nout = 2 * len(view_mu), len(levels), len(azimuths)
     sgn = np.concatenate((-view_mu, view_mu))
@@ -1434,7 +1521,7 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
         o.d_phi = torch.from_numpy(np.ascontiguousarray(azimuths, dtype=np.float64)).to(dev)
         o.rows, o.p0rows, o.p0exact = [], [], []
         # (the handle runs on torch's current stream here: the builders are ordered after the allocations and uploads)
-        for phase in c.phases:
+        for i_phase, phase in enumerate(c.phases):
             kind, g = _phase_kind(s, *phase)
             rw = torch.empty((M, V2, c.D), dtype=torch.float64, device=dev)
             s.phase_rows_modes_device(kind, sgn, rw.data_ptr(), 1, M, nphi, g, sign_odd=True)
@@ -1443,6 +1530,17 @@ def view_azimuth_modes(s: Solver, tau, r, mu0, view_mu, levels, quadrature, azim
                 p0 = torch.empty((M, B, V2), dtype=torch.float64, device=dev)
                 s.phase_p0_rows_modes_device(kind, c.d_mu0.data_ptr(), sgn, p0.data_ptr(), B, 1, M, nphi, g)
                 o.p0rows.append(p0)
+            elif tms is not None and i_phase == 1:
+                # the exact function's values with the truncated table's normaliser, over 1 - f (the handle holds one table at
+                # a time: the truncated one's normaliser first, then the exact function's values and normaliser)
+                d_Z = torch.empty((2, B), dtype=torch.float64, device=dev)
+                s.p0_normaliser_device(kind, c.d_mu0.data_ptr(), d_Z[0].data_ptr(), B, g)
+                kind, g = _phase_kind(s, *tms.exact)
+                p0 = torch.empty((nout, B, V2), dtype=torch.float64, device=dev)
+                s.phase_p0_rows_azimuth_device(kind, c.d_mu0.data_ptr(), sgn, o.d_phi.data_ptr(), nout, p0.data_ptr(), B, g)
+                s.p0_normaliser_device(kind, c.d_mu0.data_ptr(), d_Z[1].data_ptr(), B, g)
+                p0 *= (d_Z[1] / d_Z[0] / (1.0 - tms.f))[None, :, None]
+                o.p0exact.append(p0)
             else:
                 p0 = torch.empty((nout, B, V2), dtype=torch.float64, device=dev)
                 s.phase_p0_rows_azimuth_device(kind, c.d_mu0.data_ptr(), sgn, o.d_phi.data_ptr(), nout, p0.data_ptr(), B, g)
@@ -1647,9 +1745,11 @@ def azimuth_modes_batched(s: Solver, tau, r, colargs, azimuths, M, nphi, levels,
 
 def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down, nb_layers, nb_angles,
                    atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm, mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface,
-                   max_orders, device, p0_on_host=True, aer_set=None):
+                   max_orders, device, p0_on_host=True, aer_set=None, delta_m=None):
     """Everything before the order loop (spec:23-96): optical-depth grids, direction grid, phase matrices folded into the
-    handle, per-column scalars.  Returns the solver and the per-column inputs."""
+    handle, per-column scalars.  Returns the solver and the per-column inputs.  `delta_m` (the namespace of `_delta_m_args`):
+    the aerosol is delta-M-scaled first (`_delta_m_aerosol`) -- its P0 and P come from the truncated table, and the optical-depth
+    grid and the columns from the scaled tauStar_aer and alb_aer -- and the namespace is filled."""
     mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer = _broadcast_columns(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm,
                                                                                   alb_aer)
     B = mu0.shape[0]
@@ -1658,6 +1758,12 @@ def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0,
         z_down, z_up = z_up, z_down
     mu = direction_grid(N)
     iu, idn = slab_indices(z0, z_up, z_down, L)
+    if delta_m is not None:
+        s = get_solver(L, N, B, max_orders, device)
+        if not s.same_grid(mu):
+            s.set_grid(mu)
+        (aer_phase_fun, g_aer, mie_aer), tauStar_aer, alb_aer = _delta_m_aerosol(s, delta_m, aer_phase_fun, g_aer, mie_aer,
+                                                                                 tauStar_aer, alb_aer, device)
     tau = np.stack([tau_profile(tauStar_atm[b], tauStar_aer[b], z0, z_up, z_down, L) for b in range(B)])
     s = get_solver(L, N, B, max_orders, device)
     if not s.same_grid(mu):
@@ -1727,7 +1833,7 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
                        mie_atm=None, mie_aer=None, P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular",
                        tol=1e-4, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar",
                        planck=None, planck_surface=None, surface_emissivity=None, aer_set=None, brdf=None,
-                       max_bounces=MAX_BOUNCES):
+                       max_bounces=MAX_BOUNCES, delta_m=None):
     """`SOS_Aer_batch` with the RESULT LEFT ON THE DEVICE: returns ({"I": [B, L, 2N] float64, "n": [B] int32, "status": [B]
     int32, "tau": [B, L]} as torch tensors on cuda:`device`, (mu, idx_up, idx_down)).  The solve is enqueued on torch's
     current stream for that device, so the tensors are ordered like any torch result.  What `dist.solve_sharded` gathers.
@@ -1736,7 +1842,10 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
     `SOS_Aer_batch`.  `aer_set` [B] with a list of names in `aer_phase_fun` (or a stack `P_aer`): several aerosols in one batch,
     as in `SOS_Aer_batch`; the cached handle's columns are back on aerosol set 0 when the call returns, also on error.
     `surface='brdf'` with `brdf=` (and `max_bounces`): the BRDF ground of `SOS_Aer_batch`; the dict then also holds "bounces"
-    and "bounce_ratio" [B]."""
+    and "bounce_ratio" [B].  `delta_m=Lambda`: the delta-M-scaled aerosol of `SOS_Aer_batch` (same refusals); the dict then also
+    holds "delta_m_f" (a float) and the host arrays "tauStar_aer_scaled", "alb_aer_scaled" [B], and I and tau are the scaled
+    column's."""
+    dm = _delta_m_args(delta_m, aer_phase_fun, aer_set=aer_set, P_aer=P_aer, P0_aer=P0_aer, surface=surface, beam=beam, source=source)
     thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
                             _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if source == "thermal" else 0,
                             nb_layers, beam=beam)
@@ -1749,8 +1858,11 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
     s, tau, P0a, P0r, mu, iu, idn, N = _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
                                                       nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm,
                                                       mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device,
-                                                      aer_set=aer_set)
+                                                      aer_set=aer_set, delta_m=dm)
     try:
+        if dm is not None:
+            out = _solve_resident(s, tau, P0a, P0r, None, None, tol, device=device, keep_device=True)
+            return dict(out, delta_m_f=dm.f, tauStar_aer_scaled=dm.tauStar_aer, alb_aer_scaled=dm.alb_aer), (mu, iu, idn)
         if spherical:
             return solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, int(nb_layers)), earth_radius, tol, device=device,
                                    keep_device=True), (mu, iu, idn)
@@ -1768,7 +1880,7 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
                    atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, mie_atm=None, mie_aer=None, P_atm=None,
                    P_aer=None, surface="specular", tol=1e-4, max_orders=256, device=0, raise_on_error=True, beam="plane",
                    earth_radius=EARTH_RADIUS_KM, source="solar", planck=None, planck_surface=None,
-                   surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES) -> BatchResult:
+                   surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES, delta_m=None) -> BatchResult:
     """Columns with SEVERAL aerosol layers (the reference has one): `slabs` = [(z_up, z_down, tauStar_aer,
     alb_aer), ...] from the top down, shared by the B columns of the arrays `mu0`, `grd_alb`.  Every formula of the path is
     evaluated per zone as the reference writes it for its three zones; one layer gives `SOS_Aer_batch`'s result bit for
@@ -1779,8 +1891,12 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
     result are those of the first layer.  `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of
     `SOS_Aer_batch`, BatchResult.beam_slant [B, L].  `source='thermal'` (with `planck`, `planck_surface`,
     `surface_emissivity`): the thermal field of `SOS_Aer_batch`; every aerosol layer emits with its own albedo.
-    `surface='brdf'` with `brdf=` (and `max_bounces`): the BRDF ground of `SOS_Aer_batch`; BatchResult.bounces / bounce_ratio."""
+    `surface='brdf'` with `brdf=` (and `max_bounces`): the BRDF ground of `SOS_Aer_batch`; BatchResult.bounces / bounce_ratio.
+    `delta_m` is refused: every slab would need its own truncated fraction."""
     from .inputs import tau_profile_slabs
+    if delta_m is not None:
+        raise ValueError("delta_m is not available with SOS_Aer_layers: every slab would need its own truncated fraction; "
+                         "SOS_Aer_batch(delta_m=...) scales the one slab of its columns")
     thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
                             _batch_width(mu0, grd_alb) if source == "thermal" else 0, nb_layers, beam=beam)
     spherical = _beam_args(beam, earth_radius)
@@ -1860,13 +1976,17 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
 
 def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=None, P_aer=None, P0_aer=None, device=0,
             first_order="coded", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None, planck_surface=None,
-            surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES, **overrides) -> ColumnResult:
+            surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES, delta_m=None, **overrides) -> ColumnResult:
     """One column with the reference's parameter names (spec:19-96).  `surface` selects the file of
     the reference that would be run ('specular' | 'lambertian'); P*/P0* accept pre-built phase
     arrays.  `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of `SOS_Aer_batch`;
     ColumnResult.beam_slant [L].  `source='thermal'` (with `planck` [L], `planck_surface`, `surface_emissivity`): the thermal
     field of `SOS_Aer_batch`.  `surface='brdf'` with `brdf=` (and `max_bounces`): the BRDF ground of `SOS_Aer_batch`;
-    ColumnResult.bounces / bounce_ratio; I_saved is None (the field is a sum over ground reflections) and n the black solve's."""
+    ColumnResult.bounces / bounce_ratio; I_saved is None (the field is a sum over ground reflections) and n the black solve's.
+    `delta_m=Lambda`: the delta-M-scaled aerosol of `SOS_Aer_batch` (same refusals); I, I_saved and tau are the scaled column's,
+    ColumnResult.delta_m_f / tauStar_aer_scaled / alb_aer_scaled say what was solved."""
+    _delta_m_args(delta_m, overrides.get("aer_phase_fun", DEFAULTS["aer_phase_fun"]), P_aer=P_aer, P0_aer=P0_aer, surface=surface,
+                  beam=beam, source=source, first_order=first_order)
     _thermal_args(source, planck, planck_surface, surface_emissivity, 1,
                   overrides.get("nb_layers", DEFAULTS["nb_layers"]), beam=beam, first_order=first_order)
     _beam_args(beam, earth_radius, first_order=first_order)
@@ -1887,11 +2007,14 @@ def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=Non
                       P0_aer=None if P0_aer is None else np.asarray(P0_aer)[None],
                       surface=surface, tol=tol, max_orders=max_orders, save_orders=not ground, device=device, first_order=first_order,
                       beam=beam, earth_radius=earth_radius, source=source, planck=planck, planck_surface=planck_surface,
-                      surface_emissivity=surface_emissivity, brdf=brdf, max_bounces=max_bounces)
+                      surface_emissivity=surface_emissivity, brdf=brdf, max_bounces=max_bounces, delta_m=delta_m)
     n = int(r.n[0])
     return ColumnResult(I=r.I[0], I_saved=None if ground else r.I_saved[0, :n].copy(), n=n, tau=r.tau[0], mu=r.mu, idx_up=r.idx_up,
                         idx_down=r.idx_down, status=int(r.status[0]), beam_slant=None if r.beam_slant is None else r.beam_slant[0],
                         bounces=None if r.bounces is None else int(r.bounces[0]),
                         bounce_ratio=None if r.bounce_ratio is None else float(r.bounce_ratio[0]),
                         black_sky_albedo=None if r.black_sky_albedo is None else float(r.black_sky_albedo[0]),
-                        white_sky_albedo=None if r.white_sky_albedo is None else float(r.white_sky_albedo[0]))
+                        white_sky_albedo=None if r.white_sky_albedo is None else float(r.white_sky_albedo[0]),
+                        delta_m_f=r.delta_m_f,
+                        tauStar_aer_scaled=None if r.tauStar_aer_scaled is None else float(r.tauStar_aer_scaled[0]),
+                        alb_aer_scaled=None if r.alb_aer_scaled is None else float(r.alb_aer_scaled[0]))

@@ -665,6 +665,61 @@ class Solver:
         """`phase_matrix` left on the device: d_P_out is the address of [2N, 2N] float64; enqueued on the handle's stream."""
         check(lib().sosrt_phase_matrix_dev(self._h, self._KINDS[kind], float(g), ctypes.c_void_p(d_P_out) if d_P_out else None))
 
+    # ---- delta-M scaling (sosrt.h; DESIGN section 28) ----
+    def phase_moments(self, tab_p, lmax, tab_mu=None):
+        """Legendre moments of the piecewise-linear interpolant of S tables `tab_p` [S, ntab] (or [ntab]) on `tab_mu` [ntab]
+        (None: linspace(-1, 1, ntab)) -> (chi [S, lmax + 1] with chi[:, 0] = 1, norm [S] = half the integral of the table); a
+        single table gives (chi [lmax + 1], norm)."""
+        p = np.ascontiguousarray(tab_p, dtype=np.float64)
+        one = p.ndim == 1
+        p = np.atleast_2d(p)
+        tm = None if tab_mu is None else _f64(tab_mu, (p.shape[1],), "tab_mu")
+        chi, norm = np.empty((p.shape[0], max(int(lmax), 0) + 1)), np.empty(p.shape[0])
+        check(lib().sosrt_phase_moments(self._h, int(p.shape[0]), _ptr(tm), _ptr(p), int(p.shape[1]), int(lmax), _ptr(chi), _ptr(norm)))
+        return (chi[0], float(norm[0])) if one else (chi, norm)
+
+    def phase_moments_device(self, d_tab_p: int, S: int, ntab: int, lmax: int, d_chi_out: int, d_norm_out: int = 0, d_tab_mu: int = 0):
+        """The same on device addresses, enqueued on the handle's stream: d_tab_p [S, ntab], d_chi_out [S, lmax + 1], d_norm_out
+        [S] or 0, d_tab_mu [ntab] or 0 for the uniform abscissa."""
+        check(lib().sosrt_phase_moments_dev(self._h, int(S), _vp(d_tab_mu), _vp(d_tab_p), int(ntab), int(lmax), _vp(d_chi_out),
+                                            _vp(d_norm_out)))
+
+    def delta_m_table(self, chi, order, ntab=None, tab_mu=None):
+        """The delta-M table of the moments `chi` [S, lmax + 1] (or [lmax + 1]) truncated at `order`: (table [S, ntab] = sum over
+        l < order of (2l + 1) (chi_l - f) / (1 - f) P_l on `tab_mu` (None: linspace(-1, 1, ntab)), f [S] = chi[:, order]); a
+        single set of moments gives (table [ntab], f)."""
+        c = np.ascontiguousarray(chi, dtype=np.float64)
+        one = c.ndim == 1
+        c = np.atleast_2d(c)
+        tm = None if tab_mu is None else np.ascontiguousarray(tab_mu, dtype=np.float64)
+        n = int(ntab) if tm is None else int(tm.size)
+        out, f = np.empty((c.shape[0], max(n, 0))), np.empty(c.shape[0])
+        check(lib().sosrt_phase_delta_m(self._h, int(c.shape[0]), _ptr(c), int(c.shape[1]) - 1, int(order), _ptr(tm), n, _ptr(out),
+                                        _ptr(f)))
+        return (out[0], float(f[0])) if one else (out, f)
+
+    def delta_m_table_device(self, d_chi: int, S: int, lmax: int, order: int, ntab: int, d_tab_out: int, d_f_out: int = 0,
+                             d_tab_mu: int = 0):
+        """The same on device addresses: d_chi [S, lmax + 1], d_tab_out [S, ntab], d_f_out [S] or 0.  Waits for the moments (the
+        refusals are made on the host), then enqueues on the handle's stream."""
+        check(lib().sosrt_phase_delta_m_dev(self._h, int(S), _vp(d_chi), int(lmax), int(order), _vp(d_tab_mu), int(ntab),
+                                            _vp(d_tab_out), _vp(d_f_out)))
+
+    def p0_normaliser_device(self, kind, d_mu0: int, d_Z_out: int, B: int, g=0.0):
+        """d_Z_out [B] = the normaliser `phase_p0_rows_azimuth_device` divides the point values of column b by."""
+        check(lib().sosrt_phase_p0_normaliser_dev(self._h, int(B), self._KINDS[kind], float(g), _vp(d_mu0), _vp(d_Z_out)))
+
+    def p0_normaliser(self, kind, mu0, g=0.0):
+        """The same for a host array of mu0 -> [len(mu0)]."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        d_mu0 = torch.from_numpy(np.array(np.atleast_1d(mu0), dtype=np.float64)).to(dev)
+        d_Z = torch.empty(d_mu0.shape[0], dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.p0_normaliser_device(kind, d_mu0.data_ptr(), d_Z.data_ptr(), d_mu0.shape[0], g)
+        self.synchronize()
+        return d_Z.cpu().numpy()
+
     # ---- Fourier modes in azimuth (sosrt.h: azimuth-resolved radiance; DESIGN section 11) ----
     def phase_modes(self, kind, m_first, m_count, nphi=25, g=0.0):
         """Modes m_first .. m_first + m_count - 1 of P -> [m_count, 2N, 2N].  Mode 0 is `phase_matrix` bit for bit; modes
