@@ -7,15 +7,17 @@ import numpy as np
 EARTH_RADIUS_KM = 6371.0
 
 
-def slant_path(tau, z, mu0, earth_radius=EARTH_RADIUS_KM):
+def slant_path(tau, z, mu0, earth_radius=EARTH_RADIUS_KM, dtype=np.float64):
     """sigma [L]: sigma_0 = 0, sigma_t = sum_{k=1..t} (tau_k - tau_{k-1}) c_{t,k} with
-    c_{t,k} = (r_{k-1} + r_k) / (sqrt(r_{k-1}^2 - p^2) + sqrt(r_k^2 - p^2)), r = R_e + z, p^2 = r_t^2 (1 - mu0^2)."""
-    tau = np.asarray(tau, dtype=np.float64)
-    r = float(earth_radius) + np.asarray(z, dtype=np.float64)
+    c_{t,k} = (r_{k-1} + r_k) / (sqrt(r_{k-1}^2 - p^2) + sqrt(r_k^2 - p^2)), r = R_e + z, p^2 = r_t^2 (1 - mu0^2).
+    dtype: the type every operation runs in (np.longdouble: the same formulas, to measure what float64 loses)."""
+    tau = np.asarray(tau, dtype=dtype)
+    r = dtype(earth_radius) + np.asarray(z, dtype=dtype)
     L = tau.size
     if not (mu0 > 0):
         raise ValueError("mu0 must be > 0")
-    sig = np.zeros(L)
+    mu0 = dtype(mu0)
+    sig = np.zeros(L, dtype=dtype)
     d = np.diff(tau)
     for t in range(1, L):
         p2 = r[t] * r[t] * (1.0 - mu0 * mu0)
@@ -36,9 +38,9 @@ def slant_uniform_closed_form(z, mu0, kappa, earth_radius=EARTH_RADIUS_KM):
     return kappa * (np.sqrt(r[0] * r[0] - p2) - r * mu0)
 
 
-def phi(y):
+def phi(y, dtype=np.float64):
     """-expm1(-y) / y with phi(0) = 1."""
-    y = np.asarray(y, dtype=np.float64)
+    y = np.asarray(y, dtype=dtype)
     safe = np.where(y == 0, 1.0, y)
     return np.where(y == 0, 1.0, -np.expm1(-safe) / safe)
 
@@ -57,17 +59,17 @@ def zone_q(c, P0_aer_zone=None):
     return out
 
 
-def first_order_beam(c, sigma, P0_aer_zone=None):
-    """The first order of column `c` (oracle.Column) on the beam path sigma [L]: I1 [L][2N]."""
-    tau, mu, N, mu0 = np.asarray(c.tau, dtype=np.float64), c.mu, c.N, c.mu0
-    sigma = np.asarray(sigma, dtype=np.float64)
+def first_order_beam(c, sigma, P0_aer_zone=None, dtype=np.float64):
+    """The first order of column `c` (oracle.Column) on the beam path sigma [L]: I1 [L][2N].  dtype: as in slant_path."""
+    tau, mu, N, mu0 = np.asarray(c.tau, dtype=dtype), np.asarray(c.mu, dtype=dtype), c.N, dtype(c.mu0)
+    sigma = np.asarray(sigma, dtype=dtype)
     L = tau.size
     D = 2 * N
-    F0 = np.pi / mu0
-    T = c.tauStar_tot
+    F0 = dtype(np.pi) / mu0
+    T = dtype(c.tauStar_tot)
     R = F0 * c.grd_alb * np.exp(-sigma[L - 1] - (T - tau[L - 1]) / mu0)
     zones = c.zones
-    qz = zone_q(c, P0_aer_zone)
+    qz = [np.asarray(q, dtype=dtype) for q in zone_q(c, P0_aer_zone)]
     zone_of = np.zeros(L, dtype=int)
     first_row, last_row = np.zeros(L, dtype=bool), np.zeros(L, dtype=bool)
     for zi, z in enumerate(zones):
@@ -79,19 +81,19 @@ def first_order_beam(c, sigma, P0_aer_zone=None):
     mirror = D - 1 - np.arange(D)
     e_dir = F0 * np.exp(-sigma)                  # F0 e^{-sigma_t}
     e_ref = R * np.exp(-(T - tau) / mu0)         # R e^{-(T - tau_t) / mu0}
-    I1 = np.zeros((L, D))
+    I1 = np.zeros((L, D), dtype=dtype)
     with np.errstate(all="ignore"):
         a = np.abs(mu[:N])
         # downward, D_0 = 0; layer (t-1, t) takes the q of row t
-        Dn = np.zeros(N)
+        Dn = np.zeros(N, dtype=dtype)
         for t in range(1, L):
             q = qz[zone_of[t]]
             dl = tau[t] - tau[t - 1]
             s = (sigma[t] - sigma[t - 1]) / dl
             E = np.exp(-dl / a)
-            Dn = Dn * E + q[:N] * e_dir[t] * (dl / a) * phi((1 / a - s) * dl)
+            Dn = Dn * E + q[:N] * e_dir[t] * (dl / a) * phi((1 / a - s) * dl, dtype)
             if not first_row[t]:
-                Dn = Dn + q[mirror[:N]] * e_ref[t] * (dl / a) * phi((1 / a + 1 / mu0) * dl)
+                Dn = Dn + q[mirror[:N]] * e_ref[t] * (dl / a) * phi((1 / a + 1 / mu0) * dl, dtype)
             I1[t, :N] = Dn
         # surface and upward; layer (t, t+1) takes the q of row t
         a = np.abs(mu[N:])
@@ -102,9 +104,9 @@ def first_order_beam(c, sigma, P0_aer_zone=None):
             dl = tau[t + 1] - tau[t]
             s = (sigma[t + 1] - sigma[t]) / dl
             E = np.exp(-dl / a)
-            Up = Up * E + q[N:] * e_dir[t] * (dl / a) * phi((1 / a + s) * dl)
+            Up = Up * E + q[N:] * e_dir[t] * (dl / a) * phi((1 / a + s) * dl, dtype)
             if not last_row[t]:
-                Up = Up + q[mirror[N:]] * e_ref[t] * (dl / a) * phi((1 / a - 1 / mu0) * dl)
+                Up = Up + q[mirror[N:]] * e_ref[t] * (dl / a) * phi((1 / a - 1 / mu0) * dl, dtype)
             I1[t, N:] = Up
     # the two mu = 0 nodes
     for t in range(L):

@@ -27,17 +27,18 @@ def zone_q_rows(c, p0a, p0r):
     return out
 
 
-def view_first_order_beam(c, sigma, p0a, p0r, mu_view):
-    """The first order of column `c` (oracle.Column) on the beam path sigma [L] at the signed lanes of `mu_view`: [L][2V]."""
-    tau, mu0 = np.asarray(c.tau, dtype=np.float64), c.mu0
-    sigma = np.asarray(sigma, dtype=np.float64)
-    a = np.asarray(mu_view, dtype=np.float64)
+def view_first_order_beam(c, sigma, p0a, p0r, mu_view, dtype=np.float64):
+    """The first order of column `c` (oracle.Column) on the beam path sigma [L] at the signed lanes of `mu_view`: [L][2V].
+    dtype: the type every operation runs in (np.longdouble: the same formulas, to measure what float64 loses)."""
+    tau, mu0 = np.asarray(c.tau, dtype=dtype), dtype(c.mu0)
+    sigma = np.asarray(sigma, dtype=dtype)
+    a = np.asarray(mu_view, dtype=dtype)
     L, V = tau.size, a.size
-    F0 = np.pi / mu0
-    T = c.tauStar_tot
+    F0 = dtype(np.pi) / mu0
+    T = dtype(c.tauStar_tot)
     R = F0 * c.grd_alb * np.exp(-sigma[L - 1] - (T - tau[L - 1]) / mu0)
     zones = c.zones
-    qz = zone_q_rows(c, p0a, p0r)
+    qz = [np.asarray(q, dtype=dtype) for q in zone_q_rows(c, p0a, p0r)]
     zone_of = np.zeros(L, dtype=int)
     first_row, last_row = np.zeros(L, dtype=bool), np.zeros(L, dtype=bool)
     for zi, z in enumerate(zones):
@@ -49,18 +50,18 @@ def view_first_order_beam(c, sigma, p0a, p0r, mu_view):
     lo, hi = np.arange(V), V + np.arange(V)      # the downward lanes and their mirrors
     e_dir = F0 * np.exp(-sigma)                  # F0 e^{-sigma_t}
     e_ref = R * np.exp(-(T - tau) / mu0)         # R e^{-(T - tau_t) / mu0}
-    out = np.zeros((L, 2 * V))
+    out = np.zeros((L, 2 * V), dtype=dtype)
     with np.errstate(all="ignore"):
         # downward, D_0 = 0; layer (t-1, t) takes the q of row t
-        Dn = np.zeros(V)
+        Dn = np.zeros(V, dtype=dtype)
         for t in range(1, L):
             q = qz[zone_of[t]]
             dl = tau[t] - tau[t - 1]
             ds = sigma[t] - sigma[t - 1]
             E = np.exp(-dl / a)
-            Dn = Dn * E + q[lo] * e_dir[t] * (dl / a) * S.phi(dl / a - ds)
+            Dn = Dn * E + q[lo] * e_dir[t] * (dl / a) * S.phi(dl / a - ds, dtype)
             if not first_row[t]:
-                Dn = Dn + q[hi] * e_ref[t] * (dl / a) * S.phi((1 / a + 1 / mu0) * dl)
+                Dn = Dn + q[hi] * e_ref[t] * (dl / a) * S.phi((1 / a + 1 / mu0) * dl, dtype)
             out[t, lo] = Dn
         # surface and upward; layer (t, t+1) takes the q of row t
         Up = c.grd_alb * out[L - 1, lo]
@@ -70,9 +71,9 @@ def view_first_order_beam(c, sigma, p0a, p0r, mu_view):
             dl = tau[t + 1] - tau[t]
             ds = sigma[t + 1] - sigma[t]
             E = np.exp(-dl / a)
-            Up = Up * E + q[hi] * e_dir[t] * (dl / a) * S.phi(dl / a + ds)
+            Up = Up * E + q[hi] * e_dir[t] * (dl / a) * S.phi(dl / a + ds, dtype)
             if not last_row[t]:
-                Up = Up + q[lo] * e_ref[t] * (dl / a) * S.phi(dl / a - dl / mu0)
+                Up = Up + q[lo] * e_ref[t] * (dl / a) * S.phi(dl / a - dl / mu0, dtype)
             out[t, hi] = Up
     return out
 

@@ -6,11 +6,12 @@ import numpy as np
 _trapz = getattr(np, "trapezoid", None) or np.trapz
 
 
-def linear_weights(x):
+def linear_weights(x, dtype=np.float64):
     """(w0, w1, E) of a source linear in tau over a layer of slant thickness x = Delta / a, attenuated exactly: E = e^{-x},
     A = (1 - E) / x, w0 = 1 - A (the row the sweep arrives at), w1 = A - E (the row it leaves); both 0 at x = 0.  expm1 keeps the
-    digits of 1 - E, and below x = 0.25 the two differences are summed as the series sum (-1)^{n+1} x^n / (n+1)! [times n]."""
-    x = np.asarray(x, dtype=np.float64)
+    digits of 1 - E, and below x = 0.25 the two differences are summed as the series sum (-1)^{n+1} x^n / (n+1)! [times n].
+    dtype: the type every operation runs in (np.longdouble: the same formulas, to measure what float64 loses)."""
+    x = np.asarray(x, dtype=dtype)
     E = np.exp(-x)
     safe = np.where(x == 0, 1.0, x)
     A = -np.expm1(-safe) / safe
@@ -41,7 +42,7 @@ def boundary(c, down):
     """What the order loop reflects of the downward surface row `down` [N] (oracle._transport): [N] on the upward directions
     N .. 2N-1 (the entry of the mu = 0 node is not used)."""
     N, mu = c.N, c.mu
-    out = np.zeros(N)
+    out = np.zeros(N, dtype=np.asarray(down).dtype)
     rev = np.arange(N - 2, -1, -1)
     if c.surface == "specular":
         out[1:] = c.grd_alb * down[rev]
@@ -52,52 +53,53 @@ def boundary(c, down):
     return out
 
 
-def _sweeps(tau, b, eps, a, ground_of):
+def _sweeps(tau, b, eps, a, ground_of, dtype=np.float64):
     """Downward and upward sweeps at the cosines a [K] > 0: (D [L][K], U [L][K]); ground_of(D_{L-1}) -> U_{L-1}."""
+    tau, b, eps, a = (np.asarray(x, dtype=dtype) for x in (tau, b, eps, a))
     L = len(tau)
-    D, U = np.zeros((L, a.size)), np.zeros((L, a.size))
+    D, U = np.zeros((L, a.size), dtype=dtype), np.zeros((L, a.size), dtype=dtype)
     for t in range(1, L):
-        w0, w1, E = linear_weights((tau[t] - tau[t - 1]) / a)
+        w0, w1, E = linear_weights((tau[t] - tau[t - 1]) / a, dtype)
         D[t] = D[t - 1] * E + eps[t] * (w0 * b[t] + w1 * b[t - 1])
     U[L - 1] = ground_of(D[L - 1])
     for t in range(L - 2, -1, -1):
-        w0, w1, E = linear_weights((tau[t + 1] - tau[t]) / a)
+        w0, w1, E = linear_weights((tau[t + 1] - tau[t]) / a, dtype)
         U[t] = U[t + 1] * E + eps[t + 1] * (w0 * b[t] + w1 * b[t + 1])
     return D, U
 
 
-def emission(c, planck, planck_surface, emissivity=None):
+def emission(c, planck, planck_surface, emissivity=None, dtype=np.float64):
     """I_0 [L][2N] of column `c` (oracle.Column): planck [L] at the levels, the ground's planck_surface and emissivity
-    (None: 1 - grd_alb)."""
-    tau, mu, N = np.asarray(c.tau, dtype=np.float64), c.mu, c.N
-    b = np.asarray(planck, dtype=np.float64)
+    (None: 1 - grd_alb).  dtype: as in linear_weights."""
+    tau, mu, N = np.asarray(c.tau, dtype=dtype), c.mu, c.N
+    b = np.asarray(planck, dtype=dtype)
     L = tau.size
     es = 1 - c.grd_alb if emissivity is None else float(emissivity)
     eps = zone_eps(c)
-    I0 = np.zeros((L, 2 * N))
+    I0 = np.zeros((L, 2 * N), dtype=dtype)
     a = np.abs(mu[:N - 1])[::-1]                              # |mu| of directions N-2 .. 0 = mu of directions N+1 .. 2N-1
 
     def ground_of(down):                                     # down[j]: direction N-2-j
-        full = np.zeros(N)
+        full = np.zeros(N, dtype=dtype)
         full[:N - 1] = down[::-1]
         return boundary(c, full)[1:] + es * planck_surface
 
-    D, U = _sweeps(tau, b, eps, a, ground_of)
+    D, U = _sweeps(tau, b, eps, a, ground_of, dtype)
     I0[:, :N - 1] = D[:, ::-1]
     I0[:, N + 1:] = U
     I0[:, N - 1] = I0[:, N] = eps * b                        # the two mu = 0 nodes
     return I0
 
 
-def emission_view(c, planck, planck_surface, mu_view, levels, emissivity=None):
+def emission_view(c, planck, planck_surface, mu_view, levels, emissivity=None, dtype=np.float64):
     """[nlev][2V] on the signed lanes (-mu_view, +mu_view): the sweeps at a = mu_view; specular ground or none."""
-    tau = np.asarray(c.tau, dtype=np.float64)
-    a = np.atleast_1d(np.asarray(mu_view, dtype=np.float64))
+    tau = np.asarray(c.tau, dtype=dtype)
+    a = np.atleast_1d(np.asarray(mu_view, dtype=dtype))
     es = 1 - c.grd_alb if emissivity is None else float(emissivity)
     if c.surface not in ("specular", None):
         raise ValueError("the view lanes have no Lambertian ground")
     rho = c.grd_alb if c.surface == "specular" else 0.0
-    D, U = _sweeps(tau, np.asarray(planck, dtype=np.float64), zone_eps(c), a, lambda down: rho * down + es * planck_surface)
+    D, U = _sweeps(tau, np.asarray(planck, dtype=dtype), zone_eps(c), a, lambda down: rho * down + es * planck_surface, dtype)
     lev = np.atleast_1d(levels)
     return np.concatenate((D[lev], U[lev]), axis=1)
 
