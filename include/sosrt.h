@@ -656,6 +656,41 @@ int sosrt_epilogue_emission_dev(sosrt_t* h, int B, const double* d_tau, const do
                                 double* d_flux_down, double* d_flux_up, double* d_diffusivity, double* d_heating_rate,
                                 double* d_net_toa);   /* outputs nullable as in sosrt_epilogue_dev */
 
+/* ---- gas absorption profiles: per-level weights on the source function ------------------------------------
+ * A pure absorber added to a layer multiplies the source of that level by w_t = Delta tau_scattering / (Delta tau_scattering +
+ * Delta tau_gas), for both constituents alike, while tau carries the gas.  The ABI takes two weights per row, one on each row
+ * coefficient of the contraction: while set, the coefficients of every solve and of sosrt_source are (alb_atm f_atm / 4)
+ * w_atm[b][t] and (alb_aer f_aer / 4) w_aer[b][t] -- any per-level albedo of the atmosphere and any per-level aerosol fraction
+ * of a slab, relative to the zone's nominal values.  Detected by symbol; SOSRT_VERSION is unchanged.
+ *
+ * sosrt_set_row_weights_dev: copies the weights of the first B columns (device arrays [B][L]) into buffers of the handle, in
+ * stream order; the other columns of the batch keep weight one.  One NULL stands for ones, both NULL clear the weights.  They
+ * belong to the columns of the last sosrt_set_columns / sosrt_set_columns_zones: either call clears them.  While set, slab rows
+ * run the two-pass form of the contraction (cleared: the grouping is restored), the order-loop launch stays off, and the entries
+ * that evaluate one constant per zone -- sosrt_first_order, sosrt_solve[_dev] without a caller's first order,
+ * sosrt_first_order_beam_dev, sosrt_view_first_order_beam_dev, sosrt_view_radiance_dev, sosrt_emission_dev,
+ * sosrt_emission_view_dev -- return SOSRT_E_STATE with a message and write nothing, as do sosrt_set_aerosol_sets and
+ * sosrt_set_atmosphere_sets (set the sets first, then the weights).  The BRDF ground's stages (sosrt_ground_*_dev,
+ * sosrt_view_ground*_dev, sosrt_bounce_accumulate_dev) read no albedo and no fraction of the columns -- they reflect a surface row and
+ * attenuate along tau -- and stay open.  With no weights set nothing changes: not a launch, not a bit.
+ * The weights are not read back: finite and >= 0 is the caller's contract.  Refused with a message, nothing written: the
+ * single-slab geometry, B outside 1..the current columns, no columns set, columns on atmosphere sets.
+ *
+ * sosrt_first_order_profile_dev: the recurrences of sosrt_first_order_beam_dev (level choices, the two exclusions, R, phi and the
+ * mu = 0 lane as there; d_sigma = tau / mu0 is the plane beam, sosrt_beam_slant_dev on the total tau the sphere) with the handle's
+ * weights in q, row by row:  q_t[m] = (alb_atm f_atm w_atm,t P0_atm[m] + alb_aer f_aer w_aer,t P0_aer[m]) / 4 pi.
+ * sosrt_emission_profile_dev: sosrt_emission_dev with eps_t = 1 - (alb_atm f_atm w_atm,t + alb_aer f_aer w_aer,t) per row in
+ * place of the zone's; the same sweeps, the same boundary.
+ * Both refuse what their models refuse (L > 1024 here: two more rows of L doubles in LDS), and a handle with no weights set
+ * (SOSRT_E_STATE). */
+int sosrt_set_row_weights_dev(sosrt_t* h, int B, const double* d_w_atm /*[B][L] or NULL*/, const double* d_w_aer /*[B][L] or NULL*/);
+int sosrt_first_order_profile_dev(sosrt_t* h, int B, const double* d_tau /*[B][L]*/, const double* d_sigma /*[B][L]*/,
+                                  const double* d_P0_atm /*[B][2N]*/, const double* d_P0_aer /*[B][2N] or [B][nzmax][2N]*/,
+                                  double* d_I1_out /*[B][L][2N]: the d_I1_in of sosrt_solve_dev*/);
+int sosrt_emission_profile_dev(sosrt_t* h, int B, const double* d_tau /*[B][L]*/, const double* d_planck /*[B][L]*/,
+                               const double* d_planck_surface /*[B]*/, const double* d_emissivity /*[B], NULL: 1 - grd_alb*/,
+                               double* d_I0_out /*[B][L][2N]*/);
+
 /* ---- band integration: spectral points in one batch --------------------------------------------------------
  * A batch of K spectral points x C physical columns is solved as K C library columns laid out point-major, b = k C + c.  Two
  * stages beside the solve, detected by symbol (SOSRT_VERSION is unchanged).  Both are enqueued on the handle's stream; the Planck

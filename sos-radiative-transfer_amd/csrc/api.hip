@@ -201,6 +201,7 @@ int sosrt_destroy(sosrt_t* h) {
         if (h->fld.h_pub) hipHostFree(h->fld.h_pub);
         if (h->ol.h_done) hipHostFree(h->ol.h_done);
         h->cols.d_Wmix.release(); h->cols.d_Wmix_s.release(); h->cols.d_Wmix32.release(); h->cols.d_P0rz.release();
+        h->cols.d_rwa.release(); h->cols.d_rwr.release();
         h->phase.d_Wrsets.release(); h->phase.d_Wrsets_s.release(); h->phase.d_Wasets.release(); h->phase.d_lrUsets.release();
         h->phase.d_lrVsets.release(); h->phase.d_lrranks.release(); h->pf.d_modetab.release(); h->pf.d_mie.release(); h->pf.h_mie.release();
         h->pf.d_deltam.release();

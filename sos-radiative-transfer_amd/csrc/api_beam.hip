@@ -71,6 +71,7 @@ int sosrt_beam_slant_dev(sosrt_t* h, int B, const double* d_tau, const double* d
 int sosrt_first_order_beam_dev(sosrt_t* h, int B, const double* d_tau, const double* d_sigma, const double* d_P0_atm,
                                const double* d_P0_aer, double* d_I1_out) {
     if (int e = beam_check(h, B, "sosrt_first_order_beam_dev")) return e;
+    if (int e = no_row_weights(h, "sosrt_first_order_beam_dev")) return e;
     if (!d_tau || !d_sigma || !d_P0_atm || !d_P0_aer || !d_I1_out)
         return fail(SOSRT_E_INVALID, "sosrt_first_order_beam_dev: null argument");
     HIPCHK(hipSetDevice(h->device));
@@ -99,6 +100,7 @@ int sosrt_view_first_order_beam_dev(sosrt_t* h, int B, int V, const double* mu_v
                                     double* d_first_out) {
     const char* what = "sosrt_view_first_order_beam_dev";
     if (int e = beam_check(h, B, what)) return e;
+    if (int e = no_row_weights(h, what)) return e;
     // ---- the limits of sosrt_view_radiance_dev; every check comes before the first launch, so a refused call writes nothing ----
     if (V < 1 || V > SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "%s: V=%d view cosines: must be 1..%d", what, V, SOSRT_MAX_VIEWS);
     if (!mu_view) return fail(SOSRT_E_INVALID, "%s: null mu_view", what);

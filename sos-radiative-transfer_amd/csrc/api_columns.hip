@@ -103,6 +103,8 @@ static int set_columns_impl(sosrt_handle* h, int B, int geometry, int surface, c
     const size_t mb = h->max_batch;
     const int L = h->L;
     h->resident = false;                     // the descriptors of the resident field's columns are about to change
+    h->cols.rw_on = false;                   // per-level weights belong to the columns they were set for
+    h->cols.rw_regrouped = false;
     std::vector<double> sc(7 * mb, 0.0);
     std::vector<int> slab, plain, iup(B, 0), idn(B, 0);
     auto zone_end = [&](int b, int z) { return z + 1 < nz[b] ? zr0[b * kMaxZones + z + 1] - 1 : L - 1; };
@@ -322,6 +324,7 @@ int sosrt_set_aerosol_sets(sosrt_t* h, int B, int nzmax, const int* zone_set) {
     if (!h->have_cols) return fail(SOSRT_E_STATE, "sosrt_set_columns has not been called");
     if (B != h->B) return fail(SOSRT_E_INVALID, "B=%d does not match sosrt_set_columns (B=%d)", B, h->B);
     if (h->geom != SOSRT_GEOM_THREE_ZONE) return fail(SOSRT_E_INVALID, "aerosol sets need the three-zone geometry (a single slab has no aerosol)");
+    if (h->cols.rw_on) return fail(SOSRT_E_STATE, "sosrt_set_aerosol_sets groups the slab rows again: clear the per-level weights first (sosrt_set_row_weights_dev)");
     // nzmax = 1: one set per column, for each of its aerosol zones; else one per zone of the caller's table
     std::vector<int> zset((size_t)B * kMaxZones, 0);
     int top = 0;
@@ -370,6 +373,7 @@ int sosrt_set_atmosphere_sets(sosrt_t* h, int B, const int* col_set) {
         top = aset[b] > top ? aset[b] : top;
     }
     if (top == 0 && h->cols.max_atm_used == 0) return 0;      // all on set 0 before and after: nothing to do
+    if (h->cols.rw_on) return fail(SOSRT_E_STATE, "sosrt_set_atmosphere_sets groups the slab rows again: clear the per-level weights first (sosrt_set_row_weights_dev)");
     if (top > 0) {
         // (what sosrt_set_atm_phase_sets accepted S_atm > 1 under; sosrt_set_contraction / sosrt_set_first_order keep it so)
         if (!use_lowrank(h) || !use_sym(h))
@@ -395,6 +399,50 @@ int sosrt_set_atmosphere_sets(sosrt_t* h, int B, const int* col_set) {
     h->resident = false;
     if (slabs)
         if (int e = fits ? apply_mix_groups(h, B, mg) : apply_two_pass_rows(h, B)) return e;
+    return 0;
+}
+
+// Per-level weights on the row coefficients.  While set the slab rows run the two-pass form, which multiplies
+// by the coefficients row by row (a combined matrix has them baked in); clearing restores the grouping the columns had.
+int sosrt_set_row_weights_dev(sosrt_t* h, int B, const double* d_w_atm, const double* d_w_aer) {
+    if (int e = need_gpu(h)) return e;
+    if (!h->have_cols) return fail(SOSRT_E_STATE, "sosrt_set_row_weights_dev: sosrt_set_columns has not been called");
+    if (h->geom != SOSRT_GEOM_THREE_ZONE)
+        return fail(SOSRT_E_INVALID, "sosrt_set_row_weights_dev: per-level weights are for three-zone and zone-table columns; the single slab "
+                                     "(SOSRT_GEOM_SINGLE_SLAB) has no layer-by-layer first order to go with them");
+    if (B < 1 || B > h->B) return fail(SOSRT_E_INVALID, "sosrt_set_row_weights_dev: B=%d, the handle's current columns are %d (sosrt_set_columns)", B, h->B);
+    const bool on = d_w_atm || d_w_aer;
+    if (on && h->cols.max_atm_used > 0)
+        return fail(SOSRT_E_INVALID, "sosrt_set_row_weights_dev: the two-pass form that weighted slab rows take reads one W_atm, and the current "
+                                     "columns use atmosphere sets (sosrt_set_atmosphere_sets)");
+    HIPCHK(hipSetDevice(h->device));
+    prof_break(h);
+    if (on) {
+        // columns B .. of the batch, if any, keep weight one
+        const size_t n = (size_t)h->B * h->L;
+        if (int e = h->cols.d_rwa.reserve((size_t)h->max_batch * h->L)) return e;
+        if (int e = h->cols.d_rwr.reserve((size_t)h->max_batch * h->L)) return e;
+        launch_row_weights_copy(h->stream, n, (size_t)B * h->L, d_w_atm, d_w_aer, h->cols.d_rwa.p, h->cols.d_rwr.p);
+        HIPCHK(hipGetLastError());
+        if (!h->cols.rw_on && h->cols.mix_groups > 0) {
+            HIPCHK(hipStreamSynchronize(h->stream));           // (the row lists are rewritten by blocking copies)
+            if (int e = apply_two_pass_rows(h, h->B)) return e;
+            h->cols.rw_regrouped = true;
+        }
+        h->cols.rw_on = true;
+        return 0;
+    }
+    if (!h->cols.rw_on) return 0;
+    h->cols.rw_on = false;
+    if (h->cols.rw_regrouped) {
+        h->cols.rw_regrouped = false;
+        MixGroups mg;
+        const int cap = mix_group_cap(h, h->cols.max_set_used > 0 || h->cols.max_atm_used > 0);
+        if (collect_mix_groups(h, h->B, h->cols.c_zset, h->cols.c_atmset, cap, mg) && !mg.ca.empty()) {
+            HIPCHK(hipStreamSynchronize(h->stream));
+            if (int e = apply_mix_groups(h, h->B, mg)) return e;
+        }
+    }
     return 0;
 }
 

@@ -29,6 +29,7 @@ extern "C" {
 int sosrt_emission_dev(sosrt_t* h, int B, const double* d_tau, const double* d_planck, const double* d_planck_surface,
                        const double* d_emissivity, double* d_I0_out) {
     if (int e = emission_check(h, B, "sosrt_emission_dev")) return e;
+    if (int e = no_row_weights(h, "sosrt_emission_dev")) return e;
     if (!d_tau || !d_planck || !d_planck_surface || !d_I0_out) return fail(SOSRT_E_INVALID, "sosrt_emission_dev: null argument");
     HIPCHK(hipSetDevice(h->device));
     prof_break(h);
@@ -41,6 +42,7 @@ int sosrt_emission_view_dev(sosrt_t* h, int B, int V, const double* mu_view, con
                             const double* d_planck_surface, const double* d_emissivity, int nlev, const int* levels,
                             double* d_out) {
     if (int e = emission_check(h, B, "sosrt_emission_view_dev")) return e;
+    if (int e = no_row_weights(h, "sosrt_emission_view_dev")) return e;
     if (V < 1 || V > SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "sosrt_emission_view_dev: V=%d view cosines: must be 1..%d", V, SOSRT_MAX_VIEWS);
     if (!mu_view) return fail(SOSRT_E_INVALID, "sosrt_emission_view_dev: null mu_view");
     for (int v = 0; v < V; ++v)

@@ -59,6 +59,7 @@ int sosrt_view_radiance_dev(sosrt_t* h, int B, int V, const double* mu_view, con
     if (int e = need_gpu(h)) return e;
     if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
     if (!h->have_cols) return fail(SOSRT_E_STATE, "sosrt_set_columns has not been called");
+    if (int e = no_row_weights(h, "sosrt_view_radiance_dev")) return e;
     // ---- what the stage refuses: every check comes before the first launch, so a refused call changes nothing ----
     if (B < 1 || B > h->B) return fail(SOSRT_E_INVALID, "B=%d: the handle's current columns are %d (sosrt_set_columns)", B, h->B);
     if (V < 1 || V > SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "V=%d view cosines: must be 1..%d", V, SOSRT_MAX_VIEWS);

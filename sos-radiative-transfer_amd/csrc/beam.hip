@@ -12,6 +12,7 @@
 // The kernels read the columns as sosrt_set_columns* uploaded them (ColScalars: scalars and zone tables) and write nothing but
 // their outputs.
 #include "beam.hpp"
+#include "stage_math.hpp"
 
 #include "../../include/sosrt.h"
 
@@ -20,16 +21,6 @@ namespace sosrt {
 namespace {
 
 #define SOSRT_PI 3.14159265358979323846
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// phi(y) = (1 - e^{-y}) / y, phi(0) = 1: the mean of e^{-y s} over s in [0, 1].  expm1 keeps every bit next to y = 0, where a
-// direction's attenuation and the beam's cancel (the closed forms of the coded first order switch to a limit form there).
-__device__ __forceinline__ double phi1(double y) { return y == 0.0 ? 1.0 : -expm1(-y) / y; }
 
 // ------------------------------------------------------------------------------------------
 // k_beam_slant

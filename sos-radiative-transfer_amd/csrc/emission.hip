@@ -10,43 +10,13 @@
 // The kernels read the columns as sosrt_set_columns* uploaded them (ColScalars: scalars and zone tables) and write nothing but
 // their outputs.
 #include "emission.hpp"
+#include "stage_math.hpp"
 
 #include "../../include/sosrt.h"
 
 namespace sosrt {
 
 namespace {
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// The Planck radiance is linear in tau between two levels and attenuated exactly: with x = Delta / a, E = e^{-x}, A = (1 - E) / x
-// the row the sweep arrives at weighs w0 = 1 - A and the row it leaves w1 = A - E (both 0 at x = 0).  Both differences cancel at
-// small x; below 0.25 the alternating series
-//     w0 = sum_{n>=1} (-1)^{n+1} x^n / (n+1)!,   w1 = sum_{n>=1} (-1)^{n+1} n x^n / (n+1)!
-// is summed to 12 terms (the first term dropped is 0.25^13 / 14! = 2e-19): the rule of SOSRT_VIEW_QUAD_LINEAR (view.hip).
-constexpr double kLinSeries = 0.25;
-__device__ __forceinline__ void linear_weights(double x, double E, double& w0, double& w1) {
-    if (x < kLinSeries) {
-        constexpr double f[13] = {1.0 / 2, 1.0 / 6, 1.0 / 24, 1.0 / 120, 1.0 / 720, 1.0 / 5040, 1.0 / 40320, 1.0 / 362880,
-                                  1.0 / 3628800, 1.0 / 39916800, 1.0 / 479001600, 1.0 / 6227020800.0, 1.0 / 87178291200.0};
-        double s0 = 0, s1 = 0;
-#pragma unroll
-        for (int n = 12; n >= 1; --n) {                      // Horner, innermost term first
-            s0 = f[n - 1] - x * s0;
-            s1 = n * f[n - 1] - x * s1;
-        }
-        w0 = x * s0;
-        w1 = x * s1;
-    } else {
-        const double a = (1 - E) / x;
-        w0 = 1 - a;
-        w1 = a - E;
-    }
-}
 
 // emission coefficient of zone z of column b: 1 - omega_atm in a clear zone, 1 - (omega_atm f_atm + omega_aer f_aer) in an
 // aerosol zone, f of spec:149

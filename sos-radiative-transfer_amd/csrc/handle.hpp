@@ -15,6 +15,7 @@
 #include "kernels.hpp"
 #include "phasefn.hpp"
 #include "plan.hpp"
+#include "profile.hpp"
 
 namespace sosrt {
 
@@ -194,6 +195,11 @@ struct sosrt_handle {
         double *d_mixca = nullptr, *d_mixcr = nullptr;
         int* d_mixgroup = nullptr;
         int* d_slabtilegroup = nullptr;      // [tiles] group of every 32-row slab tile of the dense contraction
+        // Per-level weights on the row coefficients (sosrt_set_row_weights_dev): while set, every k_prepare of a
+        // solve or a source step is followed by one launch that multiplies d_rca / d_rcr by them, and the slab rows take two passes
+        bool rw_on = false;
+        bool rw_regrouped = false;           // setting them took the slab rows off their combined matrices: clearing puts them back
+        sosrt::GrowBuf<double> d_rwa, d_rwr; // [B][L] copies of the caller's w_atm / w_aer (ones where it passed none)
     } cols;
 
     struct Contraction {                 // knobs of the contraction (plan_order, run_source)
@@ -376,6 +382,18 @@ inline ColScalars scalars_of(sosrt_handle* h) {
     sc.alb_aer = d + 3 * mb; sc.dtau_atm = d + 4 * mb; sc.dtau_aer = d + 5 * mb;
     sc.T = d + 6 * mb;
     return sc;
+}
+
+// behind launch_prepare, wherever the row coefficients feed a contraction: rowcoef *= weights (nothing while no weights are set)
+inline void apply_row_weights(sosrt_handle* h, hipStream_t s, int B) {
+    if (h->cols.rw_on) launch_row_weights_apply(s, (size_t)B * h->L, h->cols.d_rwa.p, h->cols.d_rwr.p, h->cols.d_rca, h->cols.d_rcr);
+}
+// the guard of the entries that evaluate per-zone constants (first order, view stage, emission): not on a weighted column
+inline int no_row_weights(const sosrt_handle* h, const char* what) {
+    if (h && h->cols.rw_on)
+        return fail(SOSRT_E_STATE, "%s evaluates one constant per zone, and per-level weights are set (sosrt_set_row_weights_dev): use "
+                                   "sosrt_first_order_profile_dev / sosrt_emission_profile_dev, or clear the weights", what);
+    return 0;
 }
 
 inline bool use_sym(const sosrt_handle* h) {

@@ -201,6 +201,7 @@ struct OrderInputs {                     // what the plan of one order depends o
     int orders_left = 1 << 30;           // order budget from this order on
     int cu_share = 0;                    // CUs an order-loop launch of this group may take (0: none)
     bool atm_sets = false;               // some column reads an atmosphere phase set other than W_atm
+    bool row_weights = false;            // per-level weights on the row coefficients (sosrt_set_row_weights_dev)
 };
 struct LaunchPlan {
     int tail_cols = 0;                   // contraction over the live columns: capacity of the launch (0: dense tiling over the row lists)
@@ -269,7 +270,7 @@ LaunchPlan plan_order(const sosrt_handle* h, const SolveShape& sh, const OrderIn
     // CUs it may take (the other workgroups contract).  It holds the chunk-parallel transport (three zones, no kept k_smallmu
     // lane) and the symmetric contraction's live-column tiles; the default transport policy only (a forced kernel stays forced).
     if (h->ol.mode && in.cu_share > 0 && h->tr.mode == TransportKnob::Auto && sh.fast && sh.ring_mode && sh.nzcap <= kRingZones &&
-        use_sym(h) && in.simple_zones && in.slabs_mixed && !in.saving && !in.need_small && in.orders_left >= 1 &&
+        use_sym(h) && in.simple_zones && in.slabs_mixed && !in.saving && !in.row_weights && !in.need_small && in.orders_left >= 1 &&
         in.known <= kOrderLoopMaxCols) {
         Grid gt = g;
         gt.nsmall = 0;
@@ -475,6 +476,7 @@ extern "C" {
 int sosrt_first_order(sosrt_t* h, int B, const double* tau, const double* P0_atm, const double* P0_aer,
                       double* I1_out) {
     if (int e = check_ready(h, B, false)) return e;
+    if (int e = no_row_weights(h, "sosrt_first_order")) return e;
     if (!tau || !P0_atm || !I1_out) return fail(SOSRT_E_INVALID, "null argument");
     if (h->geom == SOSRT_GEOM_THREE_ZONE && !P0_aer) return fail(SOSRT_E_INVALID, "three-zone geometry needs P0_aer");
     HIPCHK(hipSetDevice(h->device));
@@ -509,6 +511,7 @@ int sosrt_source(sosrt_t* h, int B, const double* In_1, double* Jn_out) {
     // the row coefficients depend on tau only through the zone bounds; prepare needs a tau buffer
     // for the a4b buckets, which the source function does not use
     launch_prepare(h->stream, h->g, B, h->geom, h->surface, scalars_of(h), h->fld.d_tau, h->cols.d_desc, h->cols.d_rca, h->cols.d_rcr);
+    apply_row_weights(h, h->stream, B);
     run_source(h, h->fld.d_InA, h->fld.d_Jn, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(Jn_out, h->fld.d_Jn, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -647,6 +650,7 @@ struct SolveRun {
         su.scan_sync = h->tr.d_scan_sync;
         launch_prepare(s, g, B, h->geom, h->surface, scalars_of(h), d_tau, h->cols.d_desc, h->cols.d_rca, h->cols.d_rcr,
                        h->fld.d_nactive + sosrt_handle::kMaxGroups, su);
+        apply_row_weights(h, s, B);
         h->fld.need_small = true;
         small_tag = ((++h->fld.pub_seq) & 0x3fffffff) | 0x40000000;       // never equals an order tag
         shape = solve_shape(h, h->cols.max_nz);
@@ -782,6 +786,7 @@ struct SolveRun {
         oi.need_small = h->g.nsmall > 0 && h->fld.need_small; oi.saving = d_I_saved_out != nullptr;
         oi.orders_left = h->order_budget - q.n;
         oi.atm_sets = h->cols.max_atm_used > 0;
+        oi.row_weights = h->cols.rw_on;
         oi.cu_share = (q.ol_off || h->d_targets || h->cols.max_atm_used > 0) ? 0 : h->cu_count / NG;   // (no order-loop launch with order targets, or atmosphere sets)
         return oi;
     }
@@ -916,6 +921,7 @@ int sosrt_solve_dev(sosrt_t* h, int B, const double* d_tau, const double* d_P0_a
     if (int e = check_ready(h, B, true)) return e;
     if (!d_tau || !d_I_out) return fail(SOSRT_E_INVALID, "null argument");
     if (!d_I1_in && !d_P0_atm) return fail(SOSRT_E_INVALID, "P0_atm is required unless I1 is supplied");
+    if (int e = d_I1_in ? 0 : no_row_weights(h, "sosrt_solve_dev without a caller's first order")) return e;
     if (!d_I1_in && h->geom == SOSRT_GEOM_THREE_ZONE && !d_P0_aer) return fail(SOSRT_E_INVALID, "three-zone geometry needs P0_aer");
     if (h->max_orders >= 65536) return fail(SOSRT_E_INVALID, "max_orders must be < 65536");
     HIPCHK(hipSetDevice(h->device));
@@ -987,6 +993,7 @@ int sosrt_solve(sosrt_t* h, int B, const double* tau, const double* P0_atm, cons
                 const double* I1_in, double* I_out, double* I_saved_out, int* n_orders_out, int* status_out) {
     if (int e = check_ready(h, B, true)) return e;
     if (!tau) return fail(SOSRT_E_INVALID, "null argument");
+    if (int e = I1_in ? 0 : no_row_weights(h, "sosrt_solve without a caller's first order")) return e;
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     h->resident = false;

@@ -14,6 +14,7 @@ maximum and hands the maximum back as the scale, which re-enters in the weighted
 from __future__ import annotations
 
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
@@ -162,6 +163,20 @@ def _per_column(a, C, name):
     return np.ascontiguousarray(np.broadcast_to(a, (C,)))
 
 
+def _gas_points(gas_tau, K, C, L):
+    """`gas_tau` of a band call, [K, L] or [K, C, L] -- each spectral point its own cumulative absorption profile -- as [K, C, L],
+    or None.  Shape and values are checked here, once, before any handle exists (main._gas_args)."""
+    if gas_tau is None:
+        return None
+    g = _array(gas_tau, "gas_tau")
+    if g.shape not in ((K, L), (K, C, L)):
+        raise ValueError("gas_tau must have the shape [K, L] = (%d, %d) or [K, C, L] = (%d, %d, %d): the gas absorption profile of "
+                         "every spectral point (got %s)" % (K, L, K, C, L, g.shape))
+    g = np.ascontiguousarray(np.broadcast_to(g[:, None, :] if g.ndim == 2 else g, (K, C, L)))
+    main._gas_args(g.reshape(K * C, L), K * C, L)
+    return g
+
+
 def _points_per_solve(points_per_solve, K, C, L, N):
     if points_per_solve is None:
         return int(max(1, min(K, BAND_FIELD_BYTES // (C * L * 2 * N * 8))))
@@ -267,7 +282,7 @@ def band_thermal(bands, temperature, surface_temperature, tauStar_aer, grd_alb, 
                  surface_emissivity=None, want=WANT, points_per_solve=None, per_point=False, z0=120, z_up=25, z_down=17,
                  nb_layers=200, nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, mie_atm=None,
                  mie_aer=None, surface="specular", tol=1e-4, max_orders=256, device=0, beam="plane", azimuths=None,
-                 view_azimuths=None, devices=None, first_order="coded") -> BandResult:
+                 view_azimuths=None, devices=None, first_order="coded", gas_tau=None) -> BandResult:
     """LONGWAVE FLUXES AND HEATING RATES SUMMED OVER K SPECTRAL POINTS, for C columns: sum_k weights[k] x (the thermal solve of
     point k with the Planck radiance of band k as its source), in W m-2 (the heating rate in the epilogue's unit per W m-2).
 
@@ -290,12 +305,18 @@ def band_thermal(bands, temperature, surface_temperature, tauStar_aer, grd_alb, 
     not additive); beam='spherical', azimuths, view_azimuths, devices, first_order='readme'; shapes that do not broadcast to
     [K, C]; bands with nu_hi <= nu_lo; temperatures <= 0.  ValueError after the Planck stage, before any solve: a (band, column)
     whose radiances all underflow to 0 (a band far in the Wien tail of a cold column, x = 100 h c nu / (k T) above about 745),
-    which the stage cannot normalise (scale 0)."""
+    which the stage cannot normalise (scale 0).
+
+    `gas_tau` [K, L] or [K, C, L] (default None, the code path as it was): EVERY SPECTRAL POINT ITS OWN GAS ABSORPTION PROFILE
+    (DESIGN section 29), the cumulative absorption optical depth of the gases at the levels for that point -- 0 at the top, finite,
+    non-decreasing.  Point k is solved on tau0 + gas_tau[k] with the row weights of `inputs.gas_row_weights` in its emission
+    coefficient and its source function (`main.solve_profile`), so the heating rate gets the vertical structure of the gas."""
     want = _refuse(want, beam, azimuths, view_azimuths, devices, first_order)
     L, N = int(nb_layers), int(nb_angles)
     lo, hi, T, Ts, pp, rho, es = _thermal_inputs(bands, temperature, surface_temperature, tauStar_aer, grd_alb, tauStar_atm, alb_atm,
                                                  alb_aer, weights, surface_emissivity, L)
     K, C = pp["weights"].shape
+    gas_all = _gas_points(gas_tau, K, C, L)
     P = _points_per_solve(points_per_solve, K, C, L, N)
     import torch
     s = main.get_solver(L, N, P * C, max_orders, device)
@@ -318,10 +339,16 @@ def band_thermal(bands, temperature, surface_temperature, tauStar_aer, grd_alb, 
 
     def solve_chunk(k0, k1, B):
         flat = lambda a: a[k0:k1].reshape(B)
+        # (checked by _gas_points: the namespace _prepare_batch fills, as main._gas_args returns it)
+        gas = None if gas_all is None else SimpleNamespace(gas_tau=gas_all[k0:k1].reshape(B, L), tau0=None, w=None)
         _, tau, _, _, _, _, _, _ = main._prepare_batch(
             np.full(B, 0.5), flat(pp["tauStar_aer"]), np.tile(rho, k1 - k0), flat(pp["tauStar_atm"]), flat(pp["alb_atm"]),
             flat(pp["alb_aer"]), z0, z_up, z_down, L, N, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm, mie_aer, None, None,
-            None, None, surface, max_orders, device)
+            None, None, surface, max_orders, device, gas=gas)
+        if gas is not None:
+            return main.solve_profile(s, tau, None, None, gas.w, thermal=(d_pl[k0:k1].reshape(B, L), d_bs[k0:k1].reshape(B),
+                                                                           None if d_es is None else d_es[:B]),
+                                      tol=tol, keep_device=True, device=device)
         return main.solve_thermal(s, tau, d_pl[k0:k1].reshape(B, L), d_bs[k0:k1].reshape(B), None if d_es is None else d_es[:B],
                                   tol=tol, keep_device=True, device=device)
 
@@ -334,7 +361,7 @@ def band_thermal(bands, temperature, surface_temperature, tauStar_aer, grd_alb, 
 
 
 def band_thermal_forcing(bands, temperature, surface_temperature, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, alb_aer,
-                         weights=None, surface_emissivity=None, nb_layers=200, **kw):
+                         weights=None, surface_emissivity=None, nb_layers=200, gas_tau=None, **kw):
     """Band-integrated longwave forcing of the aerosol layer, [C] in W m-2: the band-summed outgoing flux of the same columns
     with tauStar_aer = 0 minus the one with the layer -- positive where the layer keeps radiation in, the sign of
     `thermal.thermal_forcing` and `forcing.radiative_forcing`.  The columns with and without the layer are one batch of 2 C
@@ -348,6 +375,9 @@ def band_thermal_forcing(bands, temperature, surface_temperature, tauStar_aer, g
                                                  alb_aer, weights, surface_emissivity, nb_layers)
     C = rho.size
     two = lambda a: np.concatenate((a, a), axis=-1)
+    gas_all = _gas_points(gas_tau, lo.size, C, int(nb_layers))
+    if gas_all is not None:
+        kw["gas_tau"] = np.concatenate((gas_all, gas_all), axis=1)       # (the columns without the layer keep the gas)
     r = band_thermal((lo, hi), np.concatenate((T, T)), two(Ts), np.concatenate((pp["tauStar_aer"], np.zeros_like(pp["tauStar_aer"])), axis=1),
                      two(rho), tauStar_atm=two(pp["tauStar_atm"]), alb_atm=two(pp["alb_atm"]), alb_aer=two(pp["alb_aer"]),
                      weights=two(pp["weights"]), surface_emissivity=None if es is None else two(es), want=("flux_up",),
@@ -390,7 +420,7 @@ def band_solar(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, a
                points_per_solve=None, per_point=False, point_aerosol=None, z0=120, z_up=25, z_down=17, nb_layers=200, nb_angles=128,
                atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, mie_atm=None, mie_aer=None, surface="specular",
                tol=1e-4, max_orders=256, device=0, beam="plane", azimuths=None, view_azimuths=None, devices=None,
-               first_order="coded") -> BandResult:
+               first_order="coded", gas_tau=None) -> BandResult:
     """SHORTWAVE FLUXES AND HEATING RATES SUMMED OVER K SPECTRAL POINTS, for C columns: sum_k solar_flux[k] x (the epilogue of
     the solar solve of point k).  `solar_flux` [K] or [K, C] is the weight of every point; mu0 and grd_alb are per column
     (scalars or [C]); tauStar_aer, tauStar_atm, alb_atm and alb_aer per point (scalars, [K] or [K, C]).
@@ -403,12 +433,15 @@ def band_solar(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, a
     `aer_phase_fun` may be a list of names (with `g_aer` / `mie_aer` single values or lists of its length) and `point_aerosol`
     [K] the aerosol of every point: the driver makes them the `aer_set` of the batch, at most MAX_PHASE_SETS.  The atmosphere's
     phase function is the same for all points.  Pipeline: `solve_batch_device` of P C columns per chunk, `epilogue_device`,
-    `band_reduce_device` (no scale); `points_per_solve`, `per_point`, `want` and the refusals as `band_thermal`."""
+    `band_reduce_device` (no scale); `points_per_solve`, `per_point`, `want` and the refusals as `band_thermal`.
+    `gas_tau` [K, L] or [K, C, L]: every spectral point its own gas absorption profile, as in `band_thermal` (the solar first
+    order layer by layer with the weights in its scattering coefficient, the beam terms of the fluxes on the total tau)."""
     want = _refuse(want, beam, azimuths, view_azimuths, devices, first_order)
     L, N = int(nb_layers), int(nb_angles)
     pp, mu0c, rho, sets = _solar_inputs(solar_flux, mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, aer_phase_fun,
                                         point_aerosol, beam_norm)
     K, C = pp["solar_flux"].shape
+    gas_all = _gas_points(gas_tau, K, C, L)
     P = _points_per_solve(points_per_solve, K, C, L, N)
     import torch
     s = main.get_solver(L, N, P * C, max_orders, device)
@@ -426,7 +459,8 @@ def band_solar(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, a
             tile(mu0c), flat(pp["tauStar_aer"]), tile(rho), tauStar_atm=flat(pp["tauStar_atm"]), alb_atm=flat(pp["alb_atm"]),
             alb_aer=flat(pp["alb_aer"]), z0=z0, z_up=z_up, z_down=z_down, nb_layers=L, nb_angles=N, atm_phase_fun=atm_phase_fun,
             g_atm=g_atm, aer_phase_fun=aer_phase_fun, g_aer=g_aer, mie_atm=mie_atm, mie_aer=mie_aer, surface=surface, tol=tol,
-            max_orders=max_orders, device=device, aer_set=None if sets is None else np.repeat(sets[k0:k1], C))[0]
+            max_orders=max_orders, device=device, aer_set=None if sets is None else np.repeat(sets[k0:k1], C),
+            gas_tau=None if gas_all is None else gas_all[k0:k1].reshape(B, L))[0]
 
     def epilogue(d, acc, B):
         s.epilogue_device(d["tau"].data_ptr(), d["I"].data_ptr(), 0 if d_z is None else d_z.data_ptr(), beam_norm,
@@ -437,7 +471,7 @@ def band_solar(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, a
 
 
 def band_solar_forcing(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, alb_aer, beam_norm="crit",
-                       aer_phase_fun="hg", point_aerosol=None, **kw):
+                       aer_phase_fun="hg", point_aerosol=None, gas_tau=None, **kw):
     """Band-integrated shortwave forcing of the aerosol layer, [C]: the band-summed TOA net flux with the layer minus the one of
     the same columns with tauStar_aer = 0, the sign of `forcing.radiative_forcing` (the weights as `band_solar` defines them).
     The columns with and without the layer are one batch of 2 C columns per point."""
@@ -450,6 +484,9 @@ def band_solar_forcing(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, al
                                         point_aerosol, beam_norm)
     C = rho.size
     two = lambda a: np.concatenate((a, a), axis=-1)
+    gas_all = _gas_points(gas_tau, pp["solar_flux"].shape[0], C, int(kw.get("nb_layers", 200)))
+    if gas_all is not None:
+        kw["gas_tau"] = np.concatenate((gas_all, gas_all), axis=1)       # (the columns without the layer keep the gas)
     r = band_solar(two(pp["solar_flux"]), two(mu0c), np.concatenate((pp["tauStar_aer"], np.zeros_like(pp["tauStar_aer"])), axis=1),
                    two(rho), tauStar_atm=two(pp["tauStar_atm"]), alb_atm=two(pp["alb_atm"]), alb_aer=two(pp["alb_aer"]),
                    beam_norm=beam_norm, aer_phase_fun=aer_phase_fun, point_aerosol=point_aerosol, want=("net_toa",), **kw)

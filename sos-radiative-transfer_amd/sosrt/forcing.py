@@ -19,15 +19,17 @@ from __future__ import annotations
 
 import numpy as np
 
-from .inputs import direction_grid, phase_function, slab_indices, tau_profile
-from .main import (EARTH_RADIUS_KM, _beam_args, _brdf_args, _delta_m_aerosol, _delta_m_args, _raise_unconverged, device_phase,
-                   get_solver, solve_brdf, solve_spherical)
+from .inputs import direction_grid, gas_row_weights, phase_function, slab_indices, tau_profile
+from .main import (EARTH_RADIUS_KM, _beam_args, _brdf_args, _delta_m_aerosol, _delta_m_args, _gas_args, _raise_unconverged,
+                   device_phase, get_solver, solve_brdf, solve_profile, solve_spherical)
 
 
 def _net_flux_columns(tau, idx_up, idx_down, mu, mu0, grd_alb, alb_atm, alb_aer, dtau_atm, dtau_aer, tauStar_tot, P_atm, P_aer,
                       P0_atm, P0_aer, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, z0=120,
-                      surface="specular", brdf=None):
+                      surface="specular", brdf=None, gas=None):
     """TOA net flux (crit:382) of B columns on their grids tau [B, L]; per-column arrays or scalars otherwise.
+    gas (the namespace of main._gas_args): the absorbing gas of main.SOS_Aer_batch -- tau and tauStar_tot are the scattering
+    column's on the way in and get the gas here (main.solve_profile, the flux epilogue on the total tau).
     beam='spherical': the pseudo-spherical direct beam (main.solve_spherical) on the altitudes np.linspace(z0, 0, L), and the
     flux's beam terms on the same slant path (the beam epilogue).  surface='brdf' with `brdf`: the BRDF ground of
     main.SOS_Aer_batch (main.solve_brdf), grd_alb its per-column scale; the flux of the summed field."""
@@ -43,10 +45,18 @@ def _net_flux_columns(tau, idx_up, idx_down, mu, mu0, grd_alb, alb_atm, alb_aer,
         s.set_grid(mu)
     if not s.same_phase(P_atm, P_aer):
         s.set_phase(P_atm, P_aer)
+    if gas is not None:
+        gas.tau0 = tau
+        tau, gas.w = gas_row_weights(tau, gas.gas_tau)
+        tauStar_tot = np.broadcast_to(np.asarray(tauStar_tot, dtype=np.float64), (B,)) + gas.gas_tau[:, -1]
     s.set_columns(np.full(B, idx_up), np.full(B, idx_down), mu0, grd_alb, alb_atm, alb_aer, dtau_atm, dtau_aer, tauStar_tot)
     P0a = np.ascontiguousarray(np.broadcast_to(np.asarray(P0_atm, dtype=np.float64), (B, 2 * N)))
     P0r = np.ascontiguousarray(np.broadcast_to(np.asarray(P0_aer, dtype=np.float64), (B, 2 * N)))
-    if spherical:
+    if gas is not None:
+        r, _, epi = solve_profile(s, tau, P0a, P0r, gas.w, np.broadcast_to(np.asarray(mu0, dtype=np.float64), (B,)),
+                                  np.linspace(z0, 0, L) if spherical else None, earth_radius, device=device, fetch_field=False,
+                                  want=("net_toa",))
+    elif spherical:
         r, _, epi = solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, L), earth_radius, device=device, fetch_field=False,
                                     want=("net_toa",))
     elif ground:
@@ -54,7 +64,7 @@ def _net_flux_columns(tau, idx_up, idx_down, mu, mu0, grd_alb, alb_atm, alb_aer,
     else:
         r = s.solve(tau, P0a, P0r, fetch_field=False)
     _raise_unconverged(r.status, N, max_orders)
-    return epi["net_toa"] if spherical or ground else s.epilogue(want=("net_toa",))["net_toa"]
+    return epi["net_toa"] if spherical or ground or gas is not None else s.epilogue(want=("net_toa",))["net_toa"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -105,7 +115,7 @@ def SOS_Aer_critical_albedo(tauStar_aer, dtau_aer, tauStar_atm, dtau_atm, P_aer,
 # batched over (tauStar_aer, alb_aer)
 # ---------------------------------------------------------------------------------------------
 def _solve_fluxes(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, geom, phases, max_orders, device, beam="plane",
-                  earth_radius=EARTH_RADIUS_KM, surface="specular", brdf=None):
+                  earth_radius=EARTH_RADIUS_KM, surface="specular", brdf=None, gas=None):
     """TOA net flux (crit:382) of B columns; arrays of length B for tauStar_aer and alb_aer."""
     z0, z_up, z_down, L, N = geom
     P0_atm, P_atm, P0_aer, P_aer = phases
@@ -114,13 +124,13 @@ def _solve_fluxes(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, geom
     ta = np.asarray(tauStar_aer, dtype=np.float64)
     return _net_flux_columns(tau, iu, idn, direction_grid(N), mu0, grd_alb, alb_atm, alb_aer, tauStar_atm / L,
                              ta / (idn + 1 - iu), tauStar_atm + ta, P_atm, P_aer, P0_atm, P0_aer, max_orders, device, beam, earth_radius,
-                             z0, surface, brdf)
+                             z0, surface, brdf, gas)
 
 
 def toa_net_flux(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, z0=120, z_up=25, z_down=17, nb_layers=200,
                  nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, phases=None,
                  max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, surface="specular", brdf=None, delta_m=None,
-                 mie_aer=None):
+                 mie_aer=None, gas_tau=None):
     """Net flux at the top of the atmosphere, -F_down[0] - F_up[0] (crit:377-382), for arrays of
     (tauStar_aer, alb_aer).  beam='spherical' (with `earth_radius`, km): the direct beam on its slant path through spherical
     shells, in the solve and in the flux's beam terms (main.SOS_Aer_batch); `radiative_forcing` and `critical_albedo` pass
@@ -130,7 +140,11 @@ def toa_net_flux(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, z0
     delta-M-scaled -- its phase arrays from the truncated table, built on the device, and tauStar_aer and
     alb_aer scaled per column; the flux is the epilogue's on the scaled column, whose direct beam contains the forward-scattered
     light.  Not with `phases`, beam='spherical' or surface='brdf'.  `radiative_forcing` and `critical_albedo` pass it on: the
-    bisection runs on the unscaled albedo."""
+    bisection runs on the unscaled albedo.  `gas_tau` ([L] or [B, L]): the absorbing gas of main.SOS_Aer_batch, its cumulative
+    absorption optical depth at the levels; with beam='spherical' on the slant path of the total tau; not with surface='brdf' or
+    delta_m.  `radiative_forcing` passes it on: the baseline column keeps the gas."""
+    gas = _gas_args(gas_tau, lambda: int(np.broadcast(np.atleast_1d(tauStar_aer), np.atleast_1d(alb_aer)).size), nb_layers,
+                    surface=surface, delta_m=delta_m)
     dm = _delta_m_args(delta_m, aer_phase_fun, P_aer=None if phases is None else phases[3], surface=surface, beam=beam)
     _beam_args(beam, earth_radius)
     if surface not in ("specular", "brdf"):
@@ -152,7 +166,7 @@ def toa_net_flux(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, z0
         P0r, Pr = phase_function(aer_phase_fun, nb_angles, mu, mu0, g_aer)
         phases = (P0a, Pa, P0r, Pr)
     return _solve_fluxes(mu0, tauStar_atm, ta, grd_alb, alb_atm, wa, (z0, z_up, z_down, nb_layers, nb_angles), phases, max_orders, device,
-                         beam, earth_radius, surface, brdf)
+                         beam, earth_radius, surface, brdf, gas)
 
 
 def radiative_forcing(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, *, baseline="no_aerosol", **kw):
@@ -162,6 +176,9 @@ def radiative_forcing(mu0, tauStar_atm, tauStar_aer, grd_alb, alb_atm, alb_aer, 
     with_aer = toa_net_flux(mu0, tauStar_atm, ta, grd_alb, alb_atm, alb_aer, **kw)
     if baseline == "coded":
         return with_aer - with_aer
+    if kw.get("gas_tau") is not None and np.ndim(kw["gas_tau"]) == 2:
+        # every column its own gas: every column its own baseline
+        return with_aer - toa_net_flux(mu0, tauStar_atm, np.zeros_like(with_aer), grd_alb, alb_atm, np.ones_like(with_aer), **kw)
     base = toa_net_flux(mu0, tauStar_atm, [0.0], grd_alb, alb_atm, [1.0], **kw)[0]
     return with_aer - base
 

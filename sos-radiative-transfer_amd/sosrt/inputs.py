@@ -63,6 +63,20 @@ def tau_profile(tauStar_atm, tauStar_aer, z0, z_up, z_down, nb_layers):
     return tau
 
 
+def gas_row_weights(tau0, gas_tau):
+    """(tau, w) of a column with an absorbing gas: `tau0` [..., L] the grid of the scattering column
+    (`tau_profile`), `gas_tau` [..., L] the cumulative absorption optical depth of the gas at the same levels (0 at the top,
+    non-decreasing).  tau = tau0 + gas_tau, and the weight on the source function of row t >= 1 is the share of scattering in
+    the extinction of the layer above it, w_t = dtau0_t / (dtau0_t + dgas_t) with d x_t = x_t - x_{t-1}; w_0 = w_1 (a row carries
+    the layer above it: the convention of the emission and beam kernels and of the zone rows).  A layer with no extinction at
+    all has weight 1."""
+    tau0, gas = np.broadcast_arrays(np.asarray(tau0, dtype=np.float64), np.asarray(gas_tau, dtype=np.float64))
+    d0, dg = np.diff(tau0, axis=-1), np.diff(gas, axis=-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        w1 = np.where(d0 + dg > 0, d0 / (d0 + dg), 1.0)
+    return tau0 + gas, np.concatenate((w1[..., :1], w1), axis=-1)
+
+
 def tau_profile_slabs(tauStar_atm, slabs, z0, nb_layers):
     """SOS_Aer_tau_profile.py:15-27 with several aerosol layers: `slabs` = [(z_up, z_down, tauStar_aer), ...]
     from the top down, each a linear ramp of its aerosol optical depth over its rows on top of the uniform molecular

@@ -15,7 +15,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .inputs import direction_grid, slab_indices, tau_profile
+from .inputs import direction_grid, gas_row_weights, slab_indices, tau_profile
 from .ocean import slope_variance
 from .solver import DevicePhaseSets, Solver
 
@@ -47,6 +47,8 @@ class ColumnResult:
     delta_m_f: Optional[float] = None           # (delta_m=...): the truncated fraction f = chi_Lambda of the aerosol's scattering
     tauStar_aer_scaled: Optional[float] = None  # ... the aerosol optical depth the column was solved with
     alb_aer_scaled: Optional[float] = None      # ... and its single-scattering albedo
+    gas_tau: Optional[np.ndarray] = None        # [L] (gas_tau=...): the gas absorption optical depth the column was solved with
+    row_weight: Optional[np.ndarray] = None     # [L] ... and the weight on the source function of every row
 
 
 @dataclass
@@ -80,6 +82,8 @@ class BatchResult:
     delta_m_f: Optional[float] = None                  # (delta_m=...): the truncated fraction f = chi_Lambda of the aerosol's scattering
     tauStar_aer_scaled: Optional[np.ndarray] = None    # [B] ... the aerosol optical depth the columns were solved with
     alb_aer_scaled: Optional[np.ndarray] = None        # [B] ... and its single-scattering albedo
+    gas_tau: Optional[np.ndarray] = None               # [B, L] (gas_tau=...): the gas absorption optical depth of every column (tau includes it)
+    row_weight: Optional[np.ndarray] = None            # [B, L] ... and the weight on the source function of every row
 
 
 _solvers = {}
@@ -428,6 +432,110 @@ def solve_thermal(s: Solver, tau, planck, planck_surface, emissivity=None, tol=1
     return r if keep_device else (r[0], r[2])
 
 
+def _gas_args(gas_tau, B, nb_layers, azimuths=None, view_mu=None, view_azimuths=None, mode_batch=False, mode_chunk=None,
+              surface="specular", delta_m=None, first_order="coded", save_orders=False, devices=None):
+    """Checks of the `gas_tau` keyword, made before any handle exists: None, or a namespace with gas_tau [B, L] that
+    `_prepare_batch` fills (tau0, the row weights).  B is a number or a callable that gives it.  The stages that evaluate one
+    constant per zone are refused (open items)."""
+    if gas_tau is None:
+        return None
+    no = lambda what, why: ValueError("gas_tau is not available with %s: %s" % (what, why))
+    if azimuths is not None:
+        raise no("azimuths", "the first order of a Fourier mode evaluates one scattering coefficient per zone")
+    if view_mu is not None or view_azimuths is not None:
+        raise no("view_mu / view_azimuths", "the view stage evaluates one scattering coefficient per zone")
+    if mode_batch or mode_chunk is not None:
+        raise no("mode_batch / mode_chunk", "they belong to azimuths")
+    if surface == "brdf":
+        raise no("surface='brdf'", "the ground's series takes its first orders from the order loop's closed form")
+    if delta_m is not None:
+        raise no("delta_m", "the scaled column's first order is the closed form")
+    if first_order != "coded":
+        raise no("first_order='readme'", "the README's first order has no layer-by-layer form")
+    if save_orders:
+        raise no("save_orders", "the per-order history starts from the handle's own first order")
+    if devices is not None and len(devices) > 1:
+        raise no("devices=[...]", "solve each shard with SOS_Aer_batch(device=...)")
+    B, L = int(B() if callable(B) else B), int(nb_layers)
+    try:
+        g = np.asarray(gas_tau, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("gas_tau must be numbers") from None
+    if g.shape not in ((L,), (B, L)):
+        raise ValueError("gas_tau must have the shape [L] = (%d,) or [B, L] = (%d, %d): the cumulative absorption optical depth of "
+                         "the gases at every level (got %s)" % (L, B, L, g.shape))
+    if not np.all(np.isfinite(g)):
+        raise ValueError("gas_tau must be finite")
+    if np.any(g[..., 0] != 0):
+        raise ValueError("gas_tau is cumulative from the top: it must be 0 at level 0")
+    if np.any(np.diff(g, axis=-1) < 0):
+        raise ValueError("gas_tau is cumulative from the top: it must not decrease with the level")
+    return SimpleNamespace(gas_tau=np.ascontiguousarray(np.broadcast_to(g, (B, L))), tau0=None, w=None)
+
+
+def solve_profile(s: Solver, tau, P0a, P0r, w, mu0=None, z=None, earth_radius=EARTH_RADIUS_KM, thermal=None, tol=1e-4, device=0,
+                  fetch_field=True, want=(), z_profile=None, keep_device=False, w_aer=None):
+    """The solve of handle `s` (grid, phase matrices and columns set) with PER-LEVEL WEIGHTS ON THE SOURCE FUNCTION (DESIGN section
+    29): `w` [B, L] multiplies the atmosphere's row coefficient, `w_aer` (default `w`: an absorbing gas weighs both alike) the
+    aerosol's (`Solver.set_row_weights_device`); `tau` [B, L] is the total optical depth, gas included.  Solar (`mu0` [B]): the
+    first order layer by layer with the weights in its scattering coefficient (`first_order_profile_device`) on the plane beam
+    sigma = tau / mu0, or with `z` [L] (km, descending) on the slant path of `beam_slant_device`; `thermal` = (planck [B, L],
+    planck_surface [B], emissivity [B] or None): the emitted field with the weights in its emission coefficient
+    (`emission_profile_device`).  Then the order loop from that field, and for the names `want` the epilogue that goes with the
+    source.  Returns (SolveResult, sigma [B, L] or None, dict of the wanted epilogue arrays); keep_device=True: the torch tensors
+    {"I", "n", "status", "tau"[, "beam_slant"]} instead.  The weights are cleared when the call returns, also on error."""
+    import torch
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), tau.shape))
+    wr = w if w_aer is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w_aer, dtype=np.float64), tau.shape))
+    if not (np.all(np.isfinite(w)) and np.all(w >= 0) and np.all(np.isfinite(wr)) and np.all(wr >= 0)):
+        raise ValueError("the row weights must be finite and >= 0")
+    if thermal is None and mu0 is None:
+        raise ValueError("solve_profile needs mu0 (the solar source) or thermal")
+
+    def seed(up, dev, d_tau, B, p0a, p0r):
+        L = d_tau.shape[1]
+        d_w = up(w)
+        d_wr = d_w if wr is w else up(wr)
+        s.set_row_weights_device(d_w.data_ptr(), d_wr.data_ptr(), B=B)
+        d_I1 = torch.empty((B, L, s.D), dtype=torch.float64, device=dev)
+        if thermal is not None:
+            def src(a, shape):
+                return a.contiguous() if isinstance(a, torch.Tensor) else up(np.broadcast_to(a, shape))
+            d_pl, d_bs = src(thermal[0], (B, L)), src(thermal[1], (B,))
+            d_es = None if thermal[2] is None else src(thermal[2], (B,))
+            s.emission_profile_device(d_tau.data_ptr(), d_pl.data_ptr(), d_bs.data_ptr(), d_I1.data_ptr(),
+                                      0 if d_es is None else d_es.data_ptr(), B=B)
+            return d_I1, {}
+        if z is None:
+            d_sig = up(tau / np.broadcast_to(np.asarray(mu0, dtype=np.float64), (B,))[:, None])
+        else:
+            d_z = up(z)
+            d_sig = torch.empty((B, L), dtype=torch.float64, device=dev)
+            s.beam_slant_device(d_tau.data_ptr(), d_z.data_ptr(), d_sig.data_ptr(), earth_radius, B=B)
+        s.first_order_profile_device(d_tau.data_ptr(), d_sig.data_ptr(), p0a, p0r, d_I1.data_ptr(), B=B)
+        return d_I1, {"beam_slant": d_sig}
+
+    def epilogue(d_tau, d_I, d_zp, extra, out, B):
+        if thermal is not None:
+            s.epilogue_emission_device(d_tau, d_I, d_zp, *out, B=B)
+        elif z is None:
+            s.epilogue_device(d_tau, d_I, d_zp, "crit", *out)
+        else:
+            s.epilogue_beam_device(d_tau, d_I, extra["beam_slant"].data_ptr(), d_zp, "crit", *out, B=B)
+
+    try:
+        r = _solve_resident(s, tau, None if thermal is not None else P0a, None if thermal is not None else P0r, seed, epilogue, tol,
+                            False, device, fetch_field, want, z_profile, keep_device)
+    finally:
+        s.set_row_weights_device(0, 0)
+    if keep_device:
+        if z is None:
+            r.pop("beam_slant", None)
+        return r
+    return r[0], (r[1].get("beam_slant") if z is not None else None), r[2]
+
+
 MAX_BOUNCES = 32
 BRDF_NPHI = 65
 ROSS_LI_MU_FLOOR = 0.17364817766693033    # cos 80 deg: the Ross-Li kernels carry sec theta and are not meant for grazing angles
@@ -765,7 +873,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   view_mu=None, view_levels=(0, -1), view_quadrature="grid", view_azimuths=None,
                   view_first_order="exact", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None,
                   planck_surface=None, surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES,
-                  brdf_modes=False, brdf_view=False, beam_stages=False, delta_m=None) -> BatchResult:
+                  brdf_modes=False, brdf_view=False, beam_stages=False, delta_m=None, gas_tau=None) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -911,7 +1019,20 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     of the truncated table -- the grid's quadrature correction for the function the solve sees; `'modes'` stays the truncated
     series.  For a named aerosol 'hg' / 'fwc' / 'table' / 'mie' / 'eva' / 'wildfire'; not with `azimuths`, `aer_set` or lists,
     `P_aer` / `P0_aer`, `mode_batch`, `surface='brdf'`, `beam='spherical'`, `source='thermal'`, `first_order='readme'` or
-    several `devices`."""
+    several `devices`.
+
+    `gas_tau` ([L] or [B, L]; default None, the code path as it was): an ABSORBING GAS WHOSE AMOUNT VARIES WITH HEIGHT (DESIGN
+    section 29; `solve_profile`).  It is the cumulative absorption optical depth of the gases at the L levels: 0 at the top,
+    finite, non-decreasing.  The column is solved on tau = tau0 + gas_tau (tau0 the grid of `inputs.tau_profile`), and the source
+    function of row t is weighted by the share of scattering in the layer above it, w_t = dtau0_t / (dtau0_t + dgas_t), w_0 = w_1
+    (`inputs.gas_row_weights`), for molecules and aerosol alike: the first order layer by layer with the weights in its
+    scattering coefficient, the order loop with the weights on its row coefficients, and with `source='thermal'` the emission
+    coefficient 1 - w_t (the zone's albedo) per row, so the gas emits.  Works with `beam='spherical'` (the slant path of the total
+    tau), `aer_set` and phase arrays.  BatchResult.tau is the total, gas_tau and row_weight [B, L] say what was solved.  Not with
+    `azimuths`, `view_mu`, `view_azimuths`, `mode_batch`, `surface='brdf'`, `delta_m`, `first_order='readme'`, `save_orders` or
+    several `devices`: those stages evaluate one constant per zone."""
+    gas = _gas_args(gas_tau, lambda: _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer), nb_layers, azimuths,
+                    view_mu, view_azimuths, mode_batch, mode_chunk, surface, delta_m, first_order, save_orders, devices)
     dm = _delta_m_args(delta_m, aer_phase_fun, azimuths, aer_set, P_aer, P0_aer, mode_batch, mode_chunk, surface, beam, source,
                        first_order, devices)
     if dm is not None and view_azimuths is not None and n_modes is None:
@@ -977,13 +1098,16 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     s, tau, P0a, P0r, mu, iu, idn, N = _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
                                                       nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm,
                                                       mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device,
-                                                      aer_set=aer_set, delta_m=dm)
+                                                      aer_set=aer_set, delta_m=dm, gas=gas)
     if dm is not None:
         aer_phase_fun, g_aer, mie_aer = dm.phase             # what the view stages resolve: the truncated table
     sigma = None
     bx = {}
     try:
-        if spherical:
+        if gas is not None:
+            r, sigma, _ = solve_profile(s, tau, P0a, P0r, gas.w, np.broadcast_to(np.asarray(mu0, dtype=np.float64), (tau.shape[0],)),
+                                        np.linspace(z0, 0, int(nb_layers)) if spherical else None, earth_radius, thermal, tol, device)
+        elif spherical:
             r, sigma, _ = solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, int(nb_layers)), earth_radius, tol, save_orders, device)
         elif ground:
             r, bx, _ = solve_brdf(s, tau, P0a, P0r, ground, mu0, tol, max_bounces, device=device,
@@ -1005,6 +1129,8 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                       black_sky_albedo=bx.get("black_sky_albedo"), white_sky_albedo=bx.get("white_sky_albedo"))
     if dm is not None:
         out.delta_m_f, out.tauStar_aer_scaled, out.alb_aer_scaled = dm.f, dm.tauStar_aer, dm.alb_aer
+    if gas is not None:
+        out.gas_tau, out.row_weight = gas.gas_tau, gas.w
     if azimuths is not None:
         mu0v =np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
         if mode_batch:
@@ -1246,6 +1372,9 @@ def SOS_Aer_spectrum(wavelengths, mu0, tauStar_aer, grd_alb, aer, *, angstrom=No
     if batch_kw.get("delta_m") is not None:
         raise ValueError("delta_m is not available with SOS_Aer_spectrum: it hands P_aer / P0_aer arrays to every batch; call "
                          "SOS_Aer_batch(delta_m=...) per wavelength")
+    if batch_kw.get("gas_tau") is not None:
+        raise ValueError("gas_tau is not available with SOS_Aer_spectrum yet: a gas profile belongs to one wavelength; call "
+                         "SOS_Aer_batch(gas_tau=...) per wavelength, or bands.band_solar(gas_tau=[K, L])")
     m = np.array([_mie.refractive_index(v, indx_convention) for v in m])
     mu0v, _ = np.broadcast_arrays(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), np.atleast_1d(np.asarray(grd_alb, dtype=np.float64)))
     L, N, W = int(nb_layers), int(nb_angles), wl.size
@@ -1745,11 +1874,13 @@ def azimuth_modes_batched(s: Solver, tau, r, colargs, azimuths, M, nphi, levels,
 
 def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down, nb_layers, nb_angles,
                    atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm, mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface,
-                   max_orders, device, p0_on_host=True, aer_set=None, delta_m=None):
+                   max_orders, device, p0_on_host=True, aer_set=None, delta_m=None, gas=None):
     """Everything before the order loop (spec:23-96): optical-depth grids, direction grid, phase matrices folded into the
     handle, per-column scalars.  Returns the solver and the per-column inputs.  `delta_m` (the namespace of `_delta_m_args`):
     the aerosol is delta-M-scaled first (`_delta_m_aerosol`) -- its P0 and P come from the truncated table, and the optical-depth
-    grid and the columns from the scaled tauStar_aer and alb_aer -- and the namespace is filled."""
+    grid and the columns from the scaled tauStar_aer and alb_aer -- and the namespace is filled.  `gas` (the namespace of
+    `_gas_args`): the returned tau and the columns' tauStar_tot include the gas, and the namespace gets tau0 and the row weights w
+    (`inputs.gas_row_weights`); dtau_atm and dtau_aer stay the scattering column's, they only form the fractions."""
     mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer = _broadcast_columns(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm,
                                                                                   alb_aer)
     B = mu0.shape[0]
@@ -1765,6 +1896,11 @@ def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0,
         (aer_phase_fun, g_aer, mie_aer), tauStar_aer, alb_aer = _delta_m_aerosol(s, delta_m, aer_phase_fun, g_aer, mie_aer,
                                                                                  tauStar_aer, alb_aer, device)
     tau = np.stack([tau_profile(tauStar_atm[b], tauStar_aer[b], z0, z_up, z_down, L) for b in range(B)])
+    tauStar_tot = tauStar_atm + tauStar_aer
+    if gas is not None:
+        gas.tau0 = tau
+        tau, gas.w = gas_row_weights(tau, gas.gas_tau)
+        tauStar_tot = tauStar_tot + gas.gas_tau[:, -1]
     s = get_solver(L, N, B, max_orders, device)
     if not s.same_grid(mu):
         s.set_grid(mu)
@@ -1822,7 +1958,7 @@ def _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0,
     if P0_atm is not None:
         P0a = np.ascontiguousarray(np.broadcast_to(P0_atm, (B, 2 * N)))
     s.set_columns(np.full(B, iu), np.full(B, idn), mu0, grd_alb, alb_atm, alb_aer,
-                  tauStar_atm / L, tauStar_aer / (idn + 1 - iu), tauStar_atm + tauStar_aer, surface=surface)
+                  tauStar_atm / L, tauStar_aer / (idn + 1 - iu), tauStar_tot, surface=surface)
     if aer_set is not None:
         s.set_aerosol_sets(sets.astype(np.int32))
     return s, tau, P0a, P0r, mu, iu, idn, N
@@ -1833,7 +1969,7 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
                        mie_atm=None, mie_aer=None, P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular",
                        tol=1e-4, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar",
                        planck=None, planck_surface=None, surface_emissivity=None, aer_set=None, brdf=None,
-                       max_bounces=MAX_BOUNCES, delta_m=None):
+                       max_bounces=MAX_BOUNCES, delta_m=None, gas_tau=None):
     """`SOS_Aer_batch` with the RESULT LEFT ON THE DEVICE: returns ({"I": [B, L, 2N] float64, "n": [B] int32, "status": [B]
     int32, "tau": [B, L]} as torch tensors on cuda:`device`, (mu, idx_up, idx_down)).  The solve is enqueued on torch's
     current stream for that device, so the tensors are ordered like any torch result.  What `dist.solve_sharded` gathers.
@@ -1844,7 +1980,10 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
     `surface='brdf'` with `brdf=` (and `max_bounces`): the BRDF ground of `SOS_Aer_batch`; the dict then also holds "bounces"
     and "bounce_ratio" [B].  `delta_m=Lambda`: the delta-M-scaled aerosol of `SOS_Aer_batch` (same refusals); the dict then also
     holds "delta_m_f" (a float) and the host arrays "tauStar_aer_scaled", "alb_aer_scaled" [B], and I and tau are the scaled
-    column's."""
+    column's.  `gas_tau` ([L] or [B, L]): the absorbing gas of `SOS_Aer_batch` (same refusals); tau is the total, and the dict then
+    also holds the host arrays "gas_tau" and "row_weight" [B, L]."""
+    gas = _gas_args(gas_tau, lambda: _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer), nb_layers, surface=surface,
+                    delta_m=delta_m)
     dm = _delta_m_args(delta_m, aer_phase_fun, aer_set=aer_set, P_aer=P_aer, P0_aer=P0_aer, surface=surface, beam=beam, source=source)
     thermal = _thermal_args(source, planck, planck_surface, surface_emissivity,
                             _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) if source == "thermal" else 0,
@@ -1858,8 +1997,13 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
     s, tau, P0a, P0r, mu, iu, idn, N = _prepare_batch(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
                                                       nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm,
                                                       mie_aer, P_atm, P_aer, P0_atm, P0_aer, surface, max_orders, device,
-                                                      aer_set=aer_set, delta_m=dm)
+                                                      aer_set=aer_set, delta_m=dm, gas=gas)
     try:
+        if gas is not None:
+            out = solve_profile(s, tau, P0a, P0r, gas.w, np.broadcast_to(np.asarray(mu0, dtype=np.float64), (tau.shape[0],)),
+                                np.linspace(z0, 0, int(nb_layers)) if spherical else None, earth_radius, thermal, tol, device,
+                                keep_device=True)
+            return dict(out, gas_tau=gas.gas_tau, row_weight=gas.w), (mu, iu, idn)
         if dm is not None:
             out = _solve_resident(s, tau, P0a, P0r, None, None, tol, device=device, keep_device=True)
             return dict(out, delta_m_f=dm.f, tauStar_aer_scaled=dm.tauStar_aer, alb_aer_scaled=dm.alb_aer), (mu, iu, idn)
@@ -1880,7 +2024,7 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
                    atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, mie_atm=None, mie_aer=None, P_atm=None,
                    P_aer=None, surface="specular", tol=1e-4, max_orders=256, device=0, raise_on_error=True, beam="plane",
                    earth_radius=EARTH_RADIUS_KM, source="solar", planck=None, planck_surface=None,
-                   surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES, delta_m=None) -> BatchResult:
+                   surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES, delta_m=None, gas_tau=None) -> BatchResult:
     """Columns with SEVERAL aerosol layers (the reference has one): `slabs` = [(z_up, z_down, tauStar_aer,
     alb_aer), ...] from the top down, shared by the B columns of the arrays `mu0`, `grd_alb`.  Every formula of the path is
     evaluated per zone as the reference writes it for its three zones; one layer gives `SOS_Aer_batch`'s result bit for
@@ -1892,8 +2036,12 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
     `SOS_Aer_batch`, BatchResult.beam_slant [B, L].  `source='thermal'` (with `planck`, `planck_surface`,
     `surface_emissivity`): the thermal field of `SOS_Aer_batch`; every aerosol layer emits with its own albedo.
     `surface='brdf'` with `brdf=` (and `max_bounces`): the BRDF ground of `SOS_Aer_batch`; BatchResult.bounces / bounce_ratio.
-    `delta_m` is refused: every slab would need its own truncated fraction."""
+    `delta_m` is refused: every slab would need its own truncated fraction.  `gas_tau` is refused too (an open item of DESIGN
+    section 29)."""
     from .inputs import tau_profile_slabs
+    if gas_tau is not None:
+        raise ValueError("gas_tau is not available with SOS_Aer_layers yet: SOS_Aer_batch(gas_tau=...) takes the gas profile of its "
+                         "one-slab columns")
     if delta_m is not None:
         raise ValueError("delta_m is not available with SOS_Aer_layers: every slab would need its own truncated fraction; "
                          "SOS_Aer_batch(delta_m=...) scales the one slab of its columns")
@@ -1976,7 +2124,7 @@ def SOS_Aer_layers(mu0, grd_alb, slabs, *, tauStar_atm=0.124, alb_atm=1.0, z0=12
 
 def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=None, P_aer=None, P0_aer=None, device=0,
             first_order="coded", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None, planck_surface=None,
-            surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES, delta_m=None, **overrides) -> ColumnResult:
+            surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES, delta_m=None, gas_tau=None, **overrides) -> ColumnResult:
     """One column with the reference's parameter names (spec:19-96).  `surface` selects the file of
     the reference that would be run ('specular' | 'lambertian'); P*/P0* accept pre-built phase
     arrays.  `beam='spherical'` (with `earth_radius`, km): the pseudo-spherical direct beam of `SOS_Aer_batch`;
@@ -1984,7 +2132,10 @@ def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=Non
     field of `SOS_Aer_batch`.  `surface='brdf'` with `brdf=` (and `max_bounces`): the BRDF ground of `SOS_Aer_batch`;
     ColumnResult.bounces / bounce_ratio; I_saved is None (the field is a sum over ground reflections) and n the black solve's.
     `delta_m=Lambda`: the delta-M-scaled aerosol of `SOS_Aer_batch` (same refusals); I, I_saved and tau are the scaled column's,
-    ColumnResult.delta_m_f / tauStar_aer_scaled / alb_aer_scaled say what was solved."""
+    ColumnResult.delta_m_f / tauStar_aer_scaled / alb_aer_scaled say what was solved.  `gas_tau` [L]: the absorbing gas of
+    `SOS_Aer_batch` (same refusals); tau is the total, ColumnResult.gas_tau / row_weight say what was solved, and I_saved is None
+    (the per-order history is not kept under weights)."""
+    _gas_args(gas_tau, 1, overrides.get("nb_layers", DEFAULTS["nb_layers"]), surface=surface, delta_m=delta_m, first_order=first_order)
     _delta_m_args(delta_m, overrides.get("aer_phase_fun", DEFAULTS["aer_phase_fun"]), P_aer=P_aer, P0_aer=P0_aer, surface=surface,
                   beam=beam, source=source, first_order=first_order)
     _thermal_args(source, planck, planck_surface, surface_emissivity, 1,
@@ -2005,11 +2156,12 @@ def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=Non
                       mie_atm=mie["atm"], mie_aer=mie["aer"], P_atm=P_atm, P_aer=P_aer,
                       P0_atm=None if P0_atm is None else np.asarray(P0_atm)[None],
                       P0_aer=None if P0_aer is None else np.asarray(P0_aer)[None],
-                      surface=surface, tol=tol, max_orders=max_orders, save_orders=not ground, device=device, first_order=first_order,
+                      surface=surface, tol=tol, max_orders=max_orders, save_orders=not ground and gas_tau is None, device=device,
+                      first_order=first_order, gas_tau=gas_tau,
                       beam=beam, earth_radius=earth_radius, source=source, planck=planck, planck_surface=planck_surface,
                       surface_emissivity=surface_emissivity, brdf=brdf, max_bounces=max_bounces, delta_m=delta_m)
     n = int(r.n[0])
-    return ColumnResult(I=r.I[0], I_saved=None if ground else r.I_saved[0, :n].copy(), n=n, tau=r.tau[0], mu=r.mu, idx_up=r.idx_up,
+    return ColumnResult(I=r.I[0], I_saved=None if ground or gas_tau is not None else r.I_saved[0, :n].copy(), n=n, tau=r.tau[0], mu=r.mu, idx_up=r.idx_up,
                         idx_down=r.idx_down, status=int(r.status[0]), beam_slant=None if r.beam_slant is None else r.beam_slant[0],
                         bounces=None if r.bounces is None else int(r.bounces[0]),
                         bounce_ratio=None if r.bounce_ratio is None else float(r.bounce_ratio[0]),
@@ -2017,4 +2169,5 @@ def SOS_Aer(surface="specular", tol=1e-4, max_orders=256, P_atm=None, P0_atm=Non
                         white_sky_albedo=None if r.white_sky_albedo is None else float(r.white_sky_albedo[0]),
                         delta_m_f=r.delta_m_f,
                         tauStar_aer_scaled=None if r.tauStar_aer_scaled is None else float(r.tauStar_aer_scaled[0]),
-                        alb_aer_scaled=None if r.alb_aer_scaled is None else float(r.alb_aer_scaled[0]))
+                        alb_aer_scaled=None if r.alb_aer_scaled is None else float(r.alb_aer_scaled[0]),
+                        gas_tau=None if r.gas_tau is None else r.gas_tau[0], row_weight=None if r.row_weight is None else r.row_weight[0])

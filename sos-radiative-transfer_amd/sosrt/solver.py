@@ -455,6 +455,26 @@ class Solver:
                                                 _vp(d_flux_down), _vp(d_flux_up), _vp(d_diffusivity), _vp(d_heating_rate),
                                                 _vp(d_net_toa)))
 
+    # ---- gas absorption profiles: per-level weights (sosrt.h) ------------------------
+    def set_row_weights_device(self, d_w_atm: int = 0, d_w_aer: int = 0, B: Optional[int] = None):
+        """Per-level weights on the two row coefficients of the source function: d_w_atm, d_w_aer [B, L] (device addresses,
+        copied in stream order; finite and >= 0).  One 0 stands for ones, both 0 clear the weights; `set_columns*` clears them
+        too.  While set, the first order is `first_order_profile_device`, the emission `emission_profile_device`, and the
+        entries that evaluate one constant per zone raise SosrtError."""
+        check(lib().sosrt_set_row_weights_dev(self._h, int(self.B if B is None else B), _vp(d_w_atm), _vp(d_w_aer)))
+
+    def first_order_profile_device(self, d_tau: int, d_sigma: int, d_P0_atm: int, d_P0_aer: int, d_I1_out: int,
+                                   B: Optional[int] = None):
+        """`first_order_beam_device` with the handle's weights in the scattering coefficient of every row."""
+        check(lib().sosrt_first_order_profile_dev(self._h, int(self.B if B is None else B), _vp(d_tau), _vp(d_sigma),
+                                                  _vp(d_P0_atm), _vp(d_P0_aer), _vp(d_I1_out)))
+
+    def emission_profile_device(self, d_tau: int, d_planck: int, d_planck_surface: int, d_I0_out: int, d_emissivity: int = 0,
+                                B: Optional[int] = None):
+        """`emission_device` with the handle's weights in the emission coefficient of every row."""
+        check(lib().sosrt_emission_profile_dev(self._h, int(self.B if B is None else B), _vp(d_tau), _vp(d_planck),
+                                               _vp(d_planck_surface), _vp(d_emissivity), _vp(d_I0_out)))
+
     # ---- band integration (sosrt.h; DESIGN section 19) --------------------------------------------------
     def planck_bands_device(self, d_T: int, d_T_surface: int, nu_lo, nu_hi, d_planck_out: int, d_planck_surface_out: int,
                             d_scale_out: int = 0, C: int = 1, normalise=True):

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .main import _batch_width, _prepare_batch, _raise_unconverged, _thermal_args, solve_thermal
+from .main import _batch_width, _gas_args, _prepare_batch, _raise_unconverged, _thermal_args, solve_profile, solve_thermal
 
 # CODATA 2018 (exact since the 2019 redefinition of the SI)
 PLANCK_H = 6.62607015e-34          # J s
@@ -32,18 +32,23 @@ def planck_radiance(T_kelvin, wavelength_um):
 def thermal_toa_flux(tauStar_aer, grd_alb, planck, planck_surface, surface_emissivity=None, *, tauStar_atm=0.124, alb_atm=1.0,
                      alb_aer=1.0, z0=120, z_up=25, z_down=17, nb_layers=200, nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0,
                      aer_phase_fun="hg", g_aer=0.7, mie_atm=None, mie_aer=None, surface="specular", tol=1e-4, max_orders=256,
-                     device=0):
+                     device=0, gas_tau=None):
     """Outgoing flux at the top of the atmosphere of B thermal columns, [B], in the unit of `planck` (times a steradian): the
     upward trapezoid flux of the thermal field of `SOS_Aer_batch(source='thermal')`, from the emission epilogue.  The
     per-column arguments (tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer) broadcast; planck [L] or [B, L],
-    planck_surface and surface_emissivity scalars or [B]."""
+    planck_surface and surface_emissivity scalars or [B].  `gas_tau` ([L] or [B, L]): the absorbing -- and so emitting -- gas of
+    `SOS_Aer_batch`, its cumulative absorption optical depth at the levels; `thermal_forcing` passes it on."""
     B = _batch_width(tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer)
+    gas = _gas_args(gas_tau, B, nb_layers)
     thermal = _thermal_args("thermal", planck, planck_surface, surface_emissivity, B, nb_layers)
     # (the sun does not enter: any mu0 serves the phase functions' P0 rows, which the thermal solve does not read)
     s, tau, _, _, _, _, _, N = _prepare_batch(np.full(B, 0.5), tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, z0, z_up, z_down,
                                               nb_layers, nb_angles, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm, mie_aer,
-                                              None, None, None, None, surface, max_orders, device)
-    r, epi = solve_thermal(s, tau, *thermal, tol=tol, want=("flux_up",), device=device, fetch_field=False)
+                                              None, None, None, None, surface, max_orders, device, gas=gas)
+    if gas is not None:
+        r, _, epi = solve_profile(s, tau, None, None, gas.w, thermal=thermal, tol=tol, want=("flux_up",), device=device, fetch_field=False)
+    else:
+        r, epi = solve_thermal(s, tau, *thermal, tol=tol, want=("flux_up",), device=device, fetch_field=False)
     _raise_unconverged(r.status, N, max_orders)
     return epi["flux_up"][:, 0].copy()
 
