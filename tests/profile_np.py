@@ -75,16 +75,17 @@ def row_q(c, w_atm, w_aer, P0_aer_zone=None):
     return q
 
 
-def first_order_profile(c, sigma, w_atm, w_aer, P0_aer_zone=None):
-    """spherical_np.first_order_beam with q of a ROW: the same recurrences, level choices, exclusions, R, phi and mu = 0 lane."""
-    tau, mu, N, mu0 = np.asarray(c.tau, dtype=np.float64), np.asarray(c.mu, dtype=np.float64), c.N, float(c.mu0)
-    sigma = np.asarray(sigma, dtype=np.float64)
+def first_order_profile(c, sigma, w_atm, w_aer, P0_aer_zone=None, dtype=np.float64):
+    """spherical_np.first_order_beam with q of a ROW: the same recurrences, level choices, exclusions, R, phi and mu = 0 lane.
+    dtype: the type every operation runs in (np.longdouble: the same formulas, to measure what float64 loses)."""
+    tau, mu, N, mu0 = np.asarray(c.tau, dtype=dtype), np.asarray(c.mu, dtype=dtype), c.N, dtype(c.mu0)
+    sigma = np.asarray(sigma, dtype=dtype)
     L, D = tau.size, 2 * N
-    F0 = np.pi / mu0
-    Tt = float(c.tauStar_tot)
+    F0 = dtype(np.pi) / mu0
+    Tt = dtype(c.tauStar_tot)
     R = F0 * c.grd_alb * np.exp(-sigma[L - 1] - (Tt - tau[L - 1]) / mu0)
     zones = c.zones
-    q = row_q(c, w_atm, w_aer, P0_aer_zone)
+    q = np.asarray(row_q(c, w_atm, w_aer, P0_aer_zone), dtype=dtype)
     first_row, last_row = np.zeros(L, dtype=bool), np.zeros(L, dtype=bool)
     for zi, z in enumerate(zones):
         if zi > 0:
@@ -94,17 +95,17 @@ def first_order_profile(c, sigma, w_atm, w_aer, P0_aer_zone=None):
     mirror = D - 1 - np.arange(D)
     e_dir = F0 * np.exp(-sigma)
     e_ref = R * np.exp(-(Tt - tau) / mu0)
-    I1 = np.zeros((L, D))
+    I1 = np.zeros((L, D), dtype=dtype)
     with np.errstate(all="ignore"):
         a = np.abs(mu[:N])
-        Dn = np.zeros(N)
+        Dn = np.zeros(N, dtype=dtype)
         for t in range(1, L):
             dl = tau[t] - tau[t - 1]
             s = (sigma[t] - sigma[t - 1]) / dl
             E = np.exp(-dl / a)
-            Dn = Dn * E + q[t, :N] * e_dir[t] * (dl / a) * S.phi((1 / a - s) * dl)
+            Dn = Dn * E + q[t, :N] * e_dir[t] * (dl / a) * S.phi((1 / a - s) * dl, dtype)
             if not first_row[t]:
-                Dn = Dn + q[t, mirror[:N]] * e_ref[t] * (dl / a) * S.phi((1 / a + 1 / mu0) * dl)
+                Dn = Dn + q[t, mirror[:N]] * e_ref[t] * (dl / a) * S.phi((1 / a + 1 / mu0) * dl, dtype)
             I1[t, :N] = Dn
         a = np.abs(mu[N:])
         Up = c.grd_alb * I1[L - 1, mirror[N:]]
@@ -113,9 +114,9 @@ def first_order_profile(c, sigma, w_atm, w_aer, P0_aer_zone=None):
             dl = tau[t + 1] - tau[t]
             s = (sigma[t + 1] - sigma[t]) / dl
             E = np.exp(-dl / a)
-            Up = Up * E + q[t, N:] * e_dir[t] * (dl / a) * S.phi((1 / a + s) * dl)
+            Up = Up * E + q[t, N:] * e_dir[t] * (dl / a) * S.phi((1 / a + s) * dl, dtype)
             if not last_row[t]:
-                Up = Up + q[t, mirror[N:]] * e_ref[t] * (dl / a) * S.phi((1 / a - 1 / mu0) * dl)
+                Up = Up + q[t, mirror[N:]] * e_ref[t] * (dl / a) * S.phi((1 / a - 1 / mu0) * dl, dtype)
             I1[t, N:] = Up
     for t in range(L):
         for m in (N - 1, N):
@@ -138,22 +139,23 @@ def row_eps(c, w_atm, w_aer):
     return eps
 
 
-def emission_profile(c, planck, planck_surface, w_atm, w_aer, emissivity=None):
-    """thermal_np.emission with the emission coefficient of a ROW: the same sweeps, the same boundary."""
-    tau, mu, N = np.asarray(c.tau, dtype=np.float64), c.mu, c.N
-    b = np.asarray(planck, dtype=np.float64)
+def emission_profile(c, planck, planck_surface, w_atm, w_aer, emissivity=None, dtype=np.float64):
+    """thermal_np.emission with the emission coefficient of a ROW: the same sweeps, the same boundary.  dtype: as in
+    first_order_profile."""
+    tau, mu, N = np.asarray(c.tau, dtype=dtype), c.mu, c.N
+    b = np.asarray(planck, dtype=dtype)
     L = tau.size
     es = 1 - c.grd_alb if emissivity is None else float(emissivity)
     eps = row_eps(c, w_atm, w_aer)
-    I0 = np.zeros((L, 2 * N))
+    I0 = np.zeros((L, 2 * N), dtype=dtype)
     a = np.abs(mu[:N - 1])[::-1]
 
     def ground_of(down):
-        full = np.zeros(N)
+        full = np.zeros(N, dtype=dtype)
         full[:N - 1] = down[::-1]
         return T.boundary(c, full)[1:] + es * planck_surface
 
-    D, U = T._sweeps(tau, b, eps, a, ground_of)
+    D, U = T._sweeps(tau, b, eps, a, ground_of, dtype)
     I0[:, :N - 1] = D[:, ::-1]
     I0[:, N + 1:] = U
     I0[:, N - 1] = I0[:, N] = eps * b

@@ -16,6 +16,12 @@ random arrays.
     cap-L         (32, 2048, 2)   64 KiB of dynamic LDS; 32 level blocks with B > 1; L >> 256 in the epilogues
     cap-L-2slabs  (32, 2048, 2)   cap-L on a two-slab zone table: zone boundaries beyond row 256 (beam and emission only)
     many-columns  (130, 24, 70)   3 blocks per column with B = 70: b = blockIdx.x / nblk with a remainder; 2 live lanes
+    profile-cap-L (32, 1024, 2)   the profile stage's cap (kProfileMaxL): 48 KiB of dynamic LDS in k_first_order_profile
+    profile-cap-L-2slabs          profile-cap-L on the two-slab zone table: zone boundaries deep in a long column, a P0 per zone
+
+The profile stage (k_first_order_profile, k_emission_profile; `PROFILE`) runs at floor, shipped-N, cap-N,
+many-columns and the two profile-cap-L shapes on the beam's and the thermal columns, with weights of profile_np.random_weights
+per column.
 
 Does float64 NumPy hold the tests' bounds at this depth?  At cap-L a recurrence runs over 2047 rows, at cap-N a dot product
 over 1023 or 2048 terms.  `float64_gaps()` evaluates the models a second time in np.longdouble (x87 extended, 64-bit mantissa) --
@@ -42,17 +48,26 @@ tests/stage_shape_cases.py; also in profiles/stage_shapes_errors.txt):
     brdf_np.ground_source at view lanes V=64      cap-N         7.8e-16                 1e-13
     view_np.source V=64                           cap-N         3.1e-16                 1e-10
 
+    profile_np.first_order_profile (worst path)   profile-cap-L          3.2e-15         1e-12
+    profile_np.first_order_profile (worst path)   profile-cap-L-2slabs   3.4e-15         1e-12
+    profile_np.first_order_profile, P0 per zone   profile-cap-L-2slabs   5.3e-15         1e-12
+    profile_np.emission_profile (worst surface)   profile-cap-L          6.6e-14         1e-12
+    profile_np.emission_profile (worst surface)   profile-cap-L-2slabs   5.0e-14         1e-12
+    (`profile_float64_gaps()`; every figure in profiles/brdf_builder_shapes_errors.txt)
+
 Every gap but the emitted field's at cap-L is below a tenth of its bound: there the tests compare the device with the float64
 models.  The emitted field at L = 2048 is the exception.  Its layers are equally thick, so a lane multiplies by the same
 E = exp(-x) 2047 times, and the rounding of that one number (half an ulp of a value next to 1) adds up linearly instead of
 averaging out: 2047 * 1.1e-16 = 2.3e-13.  For the emitted field and its view lanes at cap-L and cap-L-2slabs the tests therefore
 compare the device with the long double evaluation (`thermal_reference`, `thermal_view_reference`), rounded to float64; the
-bound stays 1e-12."""
+bound stays 1e-12.  At the profile stage's cap of 1024 layers the weighted emitted field's gap is half of that and under a tenth of
+the bound (`profile_float64_gaps()`; profile_np's two stage models take the dtype for it): the float64 model is the reference."""
 import functools
 
 import numpy as np
 
 import brdf_np as G
+import profile_np as P
 import ross_li_np as RL
 import sos_oracle as O
 import spherical_np as S
@@ -62,11 +77,14 @@ import view_np as VN
 
 # (N, L, B)
 SHAPES = {"floor": (4, 24, 3), "headline": (128, 200, 2), "shipped-N": (501, 24, 3), "cap-N": (1024, 24, 2), "cap-L": (32, 2048, 2),
-          "cap-L-2slabs": (32, 2048, 2), "many-columns": (130, 24, 70)}
+          "cap-L-2slabs": (32, 2048, 2), "many-columns": (130, 24, 70), "profile-cap-L": (32, 1024, 2), "profile-cap-L-2slabs": (32, 1024, 2)}
 SIX = ["floor", "headline", "shipped-N", "cap-N", "cap-L", "many-columns"]
 WITH_SLABS = SIX + ["cap-L-2slabs"]                          # the stages that read a zone table: the beam, emission
 VIEW_SHAPES = ["floor", "headline", "shipped-N", "cap-N"]
 CAP_L = ("cap-L", "cap-L-2slabs")
+# the profile stage (k_first_order_profile, k_emission_profile): kProfileMaxL = 1024 layers in place of 2048
+PROFILE = ["floor", "shipped-N", "cap-N", "many-columns", "profile-cap-L", "profile-cap-L-2slabs"]
+PROFILE_CAP_L = ("profile-cap-L", "profile-cap-L-2slabs")
 FN_ATM, FN_AER = VN.phase_fn("rayleigh"), VN.phase_fn("hg", 0.7)
 SUNS = (0.05, 1.0, 0.21, 0.6)                                # MU0S of tests/test_gpu_spherical.py; every shape has 0.05 and 1.0
 RHOS = (0.3, 0.0, 0.5, 0.1, 0.2)
@@ -106,7 +124,7 @@ def beam_columns(name):
     mu0 = np.array([SUNS[b % 4] for b in range(B)])
     P0a, P0r = (VN.phase_p0_rows(fn, mu, mu0, mu) for fn in (FN_ATM, FN_AER))
     Z2 = no_matrix(N)[1]
-    if name == "cap-L-2slabs":
+    if name.endswith("2slabs"):
         return tuple(O.make_column_slabs(mu0[b], S.Z0, S.TWO_SLABS, L, S.T_ATM, RHOS[b % 5], 1.0, N, P0a[b], Z2, P0r[b], Z2) for b in range(B))
     return tuple(O.make_column(mu0[b], S.Z0, 25, 17, L, S.T_ATM, S.T_AER, RHOS[b % 5], 1.0, 0.97, N, P0a[b], Z2, P0r[b], Z2) for b in range(B))
 
@@ -157,7 +175,7 @@ def thermal_columns(name, surface):
     if B == 2:
         par = [THERMAL_BASE[0], THERMAL_BASE[2]]
     Z1, Z2 = no_matrix(N)
-    if name == "cap-L-2slabs":
+    if name.endswith("2slabs"):
         return tuple(O.make_column_slabs(T.MU0, T.Z0, T.TWO_SLABS, L, ta, r, wa, N, Z1, Z2, Z1, Z2, surface=surface) for r, ta, wa, _, _ in par)
     return tuple(O.make_column(T.MU0, T.Z0, 25, 17, L, ta, tr, r, wa, wr, N, Z1, Z2, Z1, Z2, surface=surface) for r, ta, wa, tr, wr in par)
 
@@ -288,6 +306,74 @@ def rough_then_smooth(S):
     return S
 
 
+# ---- per-level weights on the source function -------------------------------------------------------------------------
+FN_AER_B = VN.phase_fn("hg", 0.3)                            # the second aerosol of the P0-per-zone case
+
+
+@functools.lru_cache(maxsize=None)
+def profile_weights(name, thermal=False):
+    """(w_atm, w_aer) [B, L] of profile_np.random_weights per column (jumps at the first slab's first and last row, rows of
+    exact 1 and exact 0), on the beam's columns or on the thermal ones"""
+    cols = thermal_columns(name, "specular") if thermal else beam_columns(name)
+    w = [P.random_weights(c, 500 + b) for b, c in enumerate(cols)]
+    return frozen(np.stack([x[0] for x in w]), np.stack([x[1] for x in w]))
+
+
+@functools.lru_cache(maxsize=None)
+def profile_sigma(name, path):
+    """the beam's path [B, L]: tau / mu0 on the plane, spherical_np.slant_path on the sphere"""
+    if path == "plane":
+        return frozen(np.stack([S.plane_path(c.tau, c.mu0) for c in beam_columns(name)]))
+    return beam_model(name)[0]
+
+
+@functools.lru_cache(maxsize=None)
+def profile_p0_zones(name):
+    """[B, 5, 2N]: a P0 of the aerosol per zone of the two-slab table, the first slab's HG(0.7), the second's HG(0.3)"""
+    cols = beam_columns(name)
+    mu0 = [c.mu0 for c in cols]
+    P0b = VN.phase_p0_rows(FN_AER_B, cols[0].mu, mu0, cols[0].mu)
+    P0z = np.zeros((len(cols), 5, 2 * cols[0].N))
+    for b, c in enumerate(cols):
+        P0z[b, 1], P0z[b, 3] = c.P0_aer, P0b[b]
+    return frozen(P0z)
+
+
+@functools.lru_cache(maxsize=None)
+def profile_first_order_model(name, path, zp0=False, dtype=np.float64):
+    """I1 [B, L, 2N] of profile_np.first_order_profile on the path; zp0: with profile_p0_zones"""
+    cols, sig = beam_columns(name), profile_sigma(name, path)
+    wa, wr = profile_weights(name)
+    P0z = profile_p0_zones(name) if zp0 else [None] * len(cols)
+    return frozen(np.stack([P.first_order_profile(c, sig[b], wa[b], wr[b], P0_aer_zone=P0z[b], dtype=dtype) for b, c in enumerate(cols)]))
+
+
+@functools.lru_cache(maxsize=None)
+def profile_emission_model(name, surface, explicit, dtype=np.float64):
+    cols = thermal_columns(name, surface)
+    pl, bs, es = thermal_sources(name)
+    wa, wr = profile_weights(name, True)
+    return frozen(np.stack([P.emission_profile(c, pl[b], bs[b], wa[b], wr[b], es[b] if explicit else None, dtype=dtype) for b, c in enumerate(cols)]))
+
+
+def profile_float64_gaps():
+    """[(model, shape, gap)] at the two profile-cap-L shapes, as float64_gaps"""
+    ld = np.longdouble
+    out = []
+    worst = lambda a, l: max(_gap(a[b], l[b]) for b in range(len(a)))
+    for name in PROFILE_CAP_L:
+        for path in ("plane", "slant"):
+            out.append(("profile_np.first_order_profile " + path, name, worst(profile_first_order_model(name, path), profile_first_order_model(name, path, False, ld))))
+    name = "profile-cap-L-2slabs"
+    out.append(("profile_np.first_order_profile, P0 per zone", name, worst(profile_first_order_model(name, "plane", True), profile_first_order_model(name, "plane", True, ld))))
+    for name in PROFILE_CAP_L:
+        for surface in ("specular", "lambertian", "lambertian_readme"):
+            for explicit in (False, True):
+                out.append(("profile_np.emission_profile %s%s" % (surface, " emissivity given" if explicit else ""), name,
+                            worst(profile_emission_model(name, surface, explicit), profile_emission_model(name, surface, explicit, ld))))
+    return out
+
+
 # ---- float64 against long double ------------------------------------------------------------------------------------------------------
 def _gap(a, b):
     return float(np.max(np.abs(a - b)) / np.max(np.abs(b)))
@@ -359,5 +445,5 @@ def float64_gaps():
 
 
 if __name__ == "__main__":
-    for model, shape, gap in float64_gaps():
-        print("%-46s %-13s float64 vs longdouble %.1e" % (model, shape, gap))
+    for model, shape, gap in float64_gaps() + profile_float64_gaps():
+        print("%-46s %-20s float64 vs longdouble %.1e" % (model, shape, gap))

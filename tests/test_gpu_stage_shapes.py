@@ -26,6 +26,14 @@ What each test reaches that no other test of the suite does:
                                      the refusals of beam_check and emission_check at kBeamMaxL + 1, of V = SOSRT_MAX_VIEWS + 1
     test_view_scratch_grows_and_shrinks_with_the_call
                                      the handle's view scratch (d_fold, d_S) from V = 5 to 64 and back, from 6 levels to 300 and back
+    test_first_order_profile_kernel  k_first_order_profile<false>: 48 KiB of dynamic LDS at kProfileMaxL = 1024; nblk = 1, 3 (with B =
+                                     70: b = blockIdx.x / nblk with a remainder), 8, 16; zone boundaries deep in a long column
+    test_first_order_profile_kernel_with_a_p0_per_zone
+                                     k_first_order_profile<true> at L = 1024 on the two-slab table
+    test_emission_profile_kernel     k_emission_profile's 1024-thread workgroup and its cross-wave sum over 16 waves on both
+                                     Lambertian grounds; L = 1024
+    test_profile_stage_refuses_L_1025
+                                     the refusal of profile_check at kProfileMaxL + 1
 
 At cap-L the emitted field is compared with the model's long double evaluation (stage_shape_cases.thermal_reference): float64
 NumPy alone is 2e-13 from it there, a fifth of the bound of 1e-12, which stays."""
@@ -42,6 +50,7 @@ import thermal_np as T
 import view_np as VN
 from sosrt.solver import Solver
 from test_gpu_brdf import smooth_source
+from test_gpu_profile import KERNEL_BAR, UNIT_BAR, set_cols, set_weights
 from test_gpu_spherical import SURFACES, _err, _torch, dev, handle, host, sync
 from test_gpu_thermal import handle as thermal_handle
 from test_gpu_view import off_grid_columns, three_zone_solver
@@ -506,7 +515,131 @@ def test_view_ground_terms(name, V):
     s.close()
 
 
+# ---- per-level weights on the source function ----------------------------------------------------------------------------
+def run_first_order(s, d, B, L, profile=True):
+    out = Guarded((B, L, s.D))
+    sync()
+    f = s.first_order_profile_device if profile else s.first_order_beam_device
+    f(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), out.ptr, B=B)
+    return out.get(s)
+
+
+@pytest.mark.parametrize("path", ["plane", "slant"])
+@pytest.mark.parametrize("name", C.PROFILE)
+def test_first_order_profile_kernel(name, path):
+    cols, s, tau, P0a, P0r = beam_handle(name)
+    B, L = tau.shape
+    wa, wr = C.profile_weights(name)
+    ref = C.profile_first_order_model(name, path)
+    d = [dev(x) for x in (tau, C.profile_sigma(name, path), P0a, P0r)]
+    keep = set_weights(s, wa, wr)
+    got = run_first_order(s, d, B, L)
+    assert np.all(np.isfinite(got))
+    worst = max(_err(got[b], ref[b]) for b in range(B))
+    print("%s %s: first-order profile kernel vs model %.3e of the field maximum" % (name, path, worst))
+    assert worst <= KERNEL_BAR
+    assert np.array_equal(run_first_order(s, d, B, L), got)                  # the same call: the same bits
+    assert np.array_equal(run_first_order(s, d, 1, L)[0], got[0])            # the first column alone: the same bits
+    keep = set_weights(s, np.ones_like(wa), None)                            # unit weights: the beam kernel
+    unit = run_first_order(s, d, B, L)
+    keep = set_weights(s, None, None)
+    beam = run_first_order(s, d, B, L, profile=False)
+    e = max(_err(unit[b], beam[b]) for b in range(B))
+    print("%s %s: unit weights vs sosrt_first_order_beam_dev %.3e (bit-equal: %s)" % (name, path, e, np.array_equal(unit, beam)))
+    assert e <= UNIT_BAR
+    del keep
+    s.close()
+
+
+def test_first_order_profile_kernel_with_a_p0_per_zone():
+    """ZP0 = true at L = 1024: [B][5][2N] P0 of the aerosol, as the kernel takes it after sosrt_set_aerosol_sets on a zone table"""
+    name = "profile-cap-L-2slabs"
+    cols = C.beam_columns(name)
+    N, L, B = C.SHAPES[name]
+    mu = cols[0].mu
+    s = Solver(L, N, max_batch=B, max_orders=1)
+    s.set_grid(mu)
+    s.set_phase_sets(O.phase_rayleigh(N, mu, 0.5)[1], np.stack([O.phase_hg(N, mu, 0.5, 0.7)[1], O.phase_hg(N, mu, 0.5, 0.3)[1]]))
+    set_cols(s, cols)
+    s.set_aerosol_sets(np.tile(np.array([0, 0, 0, 1, 0], dtype=np.int32), (B, 1)))
+    tau = np.stack([c.tau for c in cols])
+    d = [dev(x) for x in (tau, C.profile_sigma(name, "plane"), np.stack([c.P0_atm for c in cols]), C.profile_p0_zones(name))]
+    keep = set_weights(s, *C.profile_weights(name))
+    got, ref = run_first_order(s, d, B, L), C.profile_first_order_model(name, "plane", True)
+    assert np.all(np.isfinite(got))
+    worst = max(_err(got[b], ref[b]) for b in range(B))
+    plain = max(_err(C.profile_first_order_model(name, "plane")[b], ref[b]) for b in range(B))
+    print("%s, a P0 per zone: first-order profile kernel vs model %.3e (the model with one P0 is %.1e from it)" % (name, worst, plain))
+    assert worst <= KERNEL_BAR and plain > 1e-3
+    assert np.array_equal(run_first_order(s, d, B, L), got) and np.array_equal(run_first_order(s, d, 1, L)[0], got[0])
+    del keep
+    s.close()
+
+
+@pytest.mark.parametrize("surface", SURFACES)
+@pytest.mark.parametrize("name", C.PROFILE)
+def test_emission_profile_kernel(name, surface):
+    cols = C.thermal_columns(name, surface)
+    pl, bs, es = C.thermal_sources(name)
+    s, tau = thermal_handle(cols, phase=False, max_orders=1)
+    B, L = tau.shape
+    wa, wr = C.profile_weights(name, True)
+    d = [dev(x) for x in (tau, pl, bs, es)]
+
+    def run(explicit, B=B, profile=True):
+        out = Guarded((B, L, s.D))
+        sync()
+        f = s.emission_profile_device if profile else s.emission_device
+        f(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.ptr, d[3].data_ptr() if explicit else 0, B=B)
+        return out.get(s)
+
+    keep = set_weights(s, wa, wr)
+    for explicit in (False, True):
+        ref = C.profile_emission_model(name, surface, explicit)
+        got = run(explicit)
+        assert np.all(np.isfinite(got))
+        worst = max(_err(got[b], ref[b]) for b in range(B))
+        print("%s %s emissivity %s: emission profile kernel vs model %.3e of the field maximum" % (name, surface, "given" if explicit else "1 - rho", worst))
+        assert worst <= KERNEL_BAR
+    assert np.array_equal(run(True), got) and np.array_equal(run(True, B=1)[0], got[0])
+    keep = set_weights(s, None, np.ones_like(wr))                            # unit weights: the emission kernel
+    unit = run(False)
+    keep = set_weights(s, None, None)
+    plain = run(False, profile=False)
+    e = max(_err(unit[b], plain[b]) for b in range(B))
+    print("%s %s: unit weights vs sosrt_emission_dev %.3e (bit-equal: %s)" % (name, surface, e, np.array_equal(unit, plain)))
+    assert e <= UNIT_BAR
+    del keep
+    s.close()
+
+
 # ---- the limits ------------------------------------------------------------------------------------------------------------------------------
+def test_profile_stage_refuses_L_1025():
+    """One layer above kProfileMaxL = 1024 the handle exists and takes weights, and both entries of the profile stage refuse it
+    with SOSRT_E_INVALID and a message that names 1024; the guarded outputs stay NaN.  (At L = 1024 the same calls are served: the
+    profile-cap-L cases above.)"""
+    L, N, B = 1025, 32, 2
+    s = Solver(L, N, max_batch=B, max_orders=1)
+    s.set_grid(O.make_mu(N))
+    iu, idn = O.slab_indices(S.Z0, 25, 17, L)
+    s.set_columns(np.full(B, iu), np.full(B, idn), [0.5, 0.6], 0.3, 1.0, 0.97, S.T_ATM / L, S.T_AER / (idn + 1 - iu), S.T_ATM + S.T_AER)
+    tau = np.stack([O.tau_profile(S.T_ATM, S.T_AER, S.Z0, 25, 17, L)] * B)
+    d_tau, d_sig, d_P0, d_bs = dev(tau), dev(tau / 0.5), dev(np.ones((B, 2 * N))), dev(np.ones(B))
+    keep = set_weights(s, np.full((B, L), 0.5), None)
+    out = Guarded((B, L, 2 * N))
+    sync()
+    t = d_tau.data_ptr()
+    calls = {"sosrt_first_order_profile_dev": lambda: s.first_order_profile_device(t, d_sig.data_ptr(), d_P0.data_ptr(), d_P0.data_ptr(), out.ptr),
+             "sosrt_emission_profile_dev": lambda: s.emission_profile_device(t, t, d_bs.data_ptr(), out.ptr)}
+    for what, call in calls.items():
+        with pytest.raises(ValueError) as ei:
+            call()
+        assert what in str(ei.value) and "1024" in str(ei.value), str(ei.value)
+        assert np.all(np.isnan(out.get(s))), "%s: a refused call wrote to its output" % what
+    del keep
+    s.close()
+
+
 def test_beam_and_emission_refuse_L_2049():
     """One layer above kBeamMaxL = kEmissionMaxL = 2048 the handle exists, and each of the four beam entries and of the three
     emission entries refuses it with SOSRT_E_INVALID and a message that names 2048, writing nothing.  (At L = 2048 the same

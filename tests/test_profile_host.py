@@ -272,3 +272,13 @@ def test_no_gas_is_the_default_everywhere():
               thermal.thermal_toa_flux, bands.band_thermal, bands.band_solar, bands.band_thermal_forcing, bands.band_solar_forcing):
         assert inspect.signature(f).parameters["gas_tau"].default is None, f.__name__
     assert main._gas_args(None, lambda: pytest.fail("the batch width was taken"), 24) is None
+
+
+def test_float64_holds_the_stage_bound_at_the_profile_cap():
+    """tests/test_gpu_stage_shapes.py compares the two profile stage kernels at L = 1024 with the float64 models: their distance
+    from their own long double evaluation stays under a tenth of the bound of 1e-12 (stage_shape_cases.profile_float64_gaps)"""
+    import stage_shape_cases as C
+    gaps = C.profile_float64_gaps()
+    assert {shape for _, shape, _ in gaps} == set(C.PROFILE_CAP_L) and len(gaps) == 17
+    for model, shape, gap in gaps:
+        assert gap <= 1e-13, (model, shape, gap)
