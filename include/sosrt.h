@@ -673,6 +673,8 @@ int sosrt_epilogue_emission_dev(sosrt_t* h, int B, const double* d_tau, const do
  * sosrt_set_atmosphere_sets (set the sets first, then the weights).  The BRDF ground's stages (sosrt_ground_*_dev,
  * sosrt_view_ground*_dev, sosrt_bounce_accumulate_dev) read no albedo and no fraction of the columns -- they reflect a surface row and
  * attenuate along tau -- and stay open.  With no weights set nothing changes: not a launch, not a bit.
+ * At view lanes the weighted forms are entries of their own (below): sosrt_view_radiance_profile_dev,
+ * sosrt_view_first_order_profile_dev and sosrt_emission_view_profile_dev.
  * The weights are not read back: finite and >= 0 is the caller's contract.  Refused with a message, nothing written: the
  * single-slab geometry, B outside 1..the current columns, no columns set, columns on atmosphere sets.
  *
@@ -690,6 +692,39 @@ int sosrt_first_order_profile_dev(sosrt_t* h, int B, const double* d_tau /*[B][L
 int sosrt_emission_profile_dev(sosrt_t* h, int B, const double* d_tau /*[B][L]*/, const double* d_planck /*[B][L]*/,
                                const double* d_planck_surface /*[B]*/, const double* d_emissivity /*[B], NULL: 1 - grd_alb*/,
                                double* d_I0_out /*[B][L][2N]*/);
+
+/* ---- gas absorption at view angles: per-level weights in the view stage ------------------------------------
+ * The radiance at view cosines off the grid of a column whose rows carry the weights of sosrt_set_row_weights_dev.  Three entries
+ * beside the guarded ones, which keep their guards; detected by symbol, SOSRT_VERSION is unchanged.  All three need weights to
+ * be set (SOSRT_E_STATE with a message otherwise) and refuse, before the first launch and with nothing written, what their
+ * unweighted models refuse -- the single slab, B outside 1..the current columns, V, mu_view or levels outside the view stage's
+ * limits, a Lambertian surface, null pointers; the two that take phase rows also several aerosol phase sets or atmosphere sets
+ * -- and L > 1024.  Enqueued on the handle's stream; nothing but the outputs and the view stage's own scratch is written.
+ *
+ * sosrt_view_radiance_profile_dev: the scattered term of sosrt_view_radiance_dev (the same code, the same kernels) with the
+ * handle's weights on the stage's row coefficients: S_t = w_atm,t ca_t (rows_atm . I_src,t) + w_aer,t cr_t (rows_aer . I_src,t).
+ * It has no first-order arguments: under weights the first term is one of the two entries below.  With I_src = I - I_last of a
+ * weighted solve and SOSRT_VIEW_QUAD_GRID it gives, at a node's cosine, the grid's own I - I1.
+ *
+ * sosrt_view_first_order_profile_dev: the argument list, output layout and recurrences of sosrt_view_first_order_beam_dev (the two
+ * exclusions, R, phi, the four coefficient chains; d_sigma = tau / mu0 is the plane beam, sosrt_beam_slant_dev on the total tau
+ * the sphere) with A and Rz of a row:  A_t = alb_atm w_atm,t f_atm / 4 pi,  Rz_t = alb_aer w_aer,t f_aer / 4 pi.
+ *
+ * sosrt_emission_view_profile_dev: sosrt_emission_view_dev with eps_t = 1 - (alb_atm f_atm w_atm,t + alb_aer f_aer w_aer,t) per
+ * row, the expression of sosrt_emission_profile_dev; specular surface or SOSRT_SURFACE_NONE.
+ * With unit weights the three have the bits of their unweighted models. */
+int sosrt_view_radiance_profile_dev(sosrt_t* h, int B, int V, const double* mu_view /*host [V]*/, const double* d_tau /*[B][L]*/,
+                                    const double* d_I_src /*[B][L][2N]*/, const double* d_rows_atm /*[2V][2N]*/,
+                                    const double* d_rows_aer /*[2V][2N]*/, int quadrature, int nlev, const int* levels /*host*/,
+                                    double* d_scat_out /*[B][nlev][2V]*/);
+int sosrt_view_first_order_profile_dev(sosrt_t* h, int B, int V, const double* mu_view /*host [V]*/, const double* d_tau /*[B][L]*/,
+                                       const double* d_sigma /*[B][L]*/, int nset, const double* d_p0rows_atm /*[nset][B][2V]*/,
+                                       const double* d_p0rows_aer /*[nset][B][2V]*/, int nlev, const int* levels /*host*/,
+                                       double* d_first_out /*[nset][B][nlev][2V]*/);
+int sosrt_emission_view_profile_dev(sosrt_t* h, int B, int V, const double* mu_view /*host [V]*/, const double* d_tau /*[B][L]*/,
+                                    const double* d_planck /*[B][L]*/, const double* d_planck_surface /*[B]*/,
+                                    const double* d_emissivity /*[B], NULL: 1 - grd_alb*/, int nlev, const int* levels /*host*/,
+                                    double* d_out /*[B][nlev][2V]*/);
 
 /* ---- band integration: spectral points in one batch --------------------------------------------------------
  * A batch of K spectral points x C physical columns is solved as K C library columns laid out point-major, b = k C + c.  Two

@@ -8,8 +8,9 @@
 
 using namespace sosrt;
 
-// what the two entry points refuse alike; every check comes before the launch, so a refused call writes nothing
-static int profile_check(sosrt_handle* h, int B, const char* what) {
+// what the entry points of the stage refuse alike, here and at view lanes (api_view.hip, api_profile_view.hip); every check comes
+// before the launch, so a refused call writes nothing
+int sosrt::profile_check(sosrt_handle* h, int B, const char* what) {
     if (int e = need_gpu(h)) return e;
     if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
     if (!h->have_cols) return fail(SOSRT_E_STATE, "sosrt_set_columns has not been called");

@@ -52,14 +52,24 @@ int sosrt_phase_p0_rows_dev(sosrt_t* h, int B, int kind, double g, const double*
     return 0;
 }
 
-int sosrt_view_radiance_dev(sosrt_t* h, int B, int V, const double* mu_view, const double* d_tau, const double* d_I_src,
-                            const double* d_rows_atm, const double* d_rows_aer, const double* d_p0rows_atm,
-                            const double* d_p0rows_aer, int quadrature, int nlev, const int* levels, double* d_scat_out,
-                            double* d_first_out) {
-    if (int e = need_gpu(h)) return e;
-    if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
-    if (!h->have_cols) return fail(SOSRT_E_STATE, "sosrt_set_columns has not been called");
-    if (int e = no_row_weights(h, "sosrt_view_radiance_dev")) return e;
+}  // extern "C"
+
+// The body of sosrt_view_radiance_dev and of sosrt_view_radiance_profile_dev.  profile: the handle's
+// per-level weights are required and multiply the stage's row coefficients behind launch_prepare, as apply_row_weights does for
+// the solve's; the source kernel multiplies by the coefficients row by row, so nothing else changes.  Without it the weights
+// are refused (the first order here is a closed form per zone) and no launch is added.
+static int view_radiance_body(sosrt_t* h, int B, int V, const double* mu_view, const double* d_tau, const double* d_I_src,
+                              const double* d_rows_atm, const double* d_rows_aer, const double* d_p0rows_atm,
+                              const double* d_p0rows_aer, int quadrature, int nlev, const int* levels, double* d_scat_out,
+                              double* d_first_out, bool profile) {
+    if (profile) {
+        if (int e = profile_check(h, B, "sosrt_view_radiance_profile_dev")) return e;
+    } else {
+        if (int e = need_gpu(h)) return e;
+        if (!h->have_grid) return fail(SOSRT_E_STATE, "sosrt_set_grid has not been called");
+        if (!h->have_cols) return fail(SOSRT_E_STATE, "sosrt_set_columns has not been called");
+        if (int e = no_row_weights(h, "sosrt_view_radiance_dev")) return e;
+    }
     // ---- what the stage refuses: every check comes before the first launch, so a refused call changes nothing ----
     if (B < 1 || B > h->B) return fail(SOSRT_E_INVALID, "B=%d: the handle's current columns are %d (sosrt_set_columns)", B, h->B);
     if (V < 1 || V > SOSRT_MAX_VIEWS) return fail(SOSRT_E_INVALID, "V=%d view cosines: must be 1..%d", V, SOSRT_MAX_VIEWS);
@@ -112,6 +122,10 @@ int sosrt_view_radiance_dev(sosrt_t* h, int B, int V, const double* mu_view, con
     double* rcr = rca + (size_t)h->max_batch * L;
     launch_prepare(s, h->g, B, h->geom, h->surface, scalars_of(h), d_tau, vw.d_desc.p, rca, rcr);
     HIPCHK(hipGetLastError());
+    if (profile) {
+        launch_row_weights_apply(s, (size_t)B * L, h->cols.d_rwa.p, h->cols.d_rwr.p, rca, rcr);
+        HIPCHK(hipGetLastError());
+    }
     vw.timed_scat = vw.timed_first = false;
     if (d_scat_out) {
         HIPCHK(hipEventRecord(vw.ev[0], s));
@@ -140,6 +154,25 @@ int sosrt_view_radiance_dev(sosrt_t* h, int B, int V, const double* mu_view, con
     HIPCHK(hipEventRecord(vw.ev[3], s));
     vw.timed_first = d_first_out != nullptr;
     return 0;
+}
+
+extern "C" {
+
+int sosrt_view_radiance_dev(sosrt_t* h, int B, int V, const double* mu_view, const double* d_tau, const double* d_I_src,
+                            const double* d_rows_atm, const double* d_rows_aer, const double* d_p0rows_atm,
+                            const double* d_p0rows_aer, int quadrature, int nlev, const int* levels, double* d_scat_out,
+                            double* d_first_out) {
+    return view_radiance_body(h, B, V, mu_view, d_tau, d_I_src, d_rows_atm, d_rows_aer, d_p0rows_atm, d_p0rows_aer, quadrature, nlev,
+                              levels, d_scat_out, d_first_out, false);
+}
+
+int sosrt_view_radiance_profile_dev(sosrt_t* h, int B, int V, const double* mu_view, const double* d_tau, const double* d_I_src,
+                                    const double* d_rows_atm, const double* d_rows_aer, int quadrature, int nlev, const int* levels,
+                                    double* d_scat_out) {
+    // the scattered term only: the first term under weights is sosrt_view_first_order_profile_dev / sosrt_emission_view_profile_dev
+    if (h && !d_scat_out) return fail(SOSRT_E_INVALID, "sosrt_view_radiance_profile_dev: null d_scat_out");
+    return view_radiance_body(h, B, V, mu_view, d_tau, d_I_src, d_rows_atm, d_rows_aer, nullptr, nullptr, quadrature, nlev, levels,
+                              d_scat_out, nullptr, true);
 }
 
 // ---------------------------------------------------------------------------------------------

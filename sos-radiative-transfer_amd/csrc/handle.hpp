@@ -396,6 +396,10 @@ inline int no_row_weights(const sosrt_handle* h, const char* what) {
     return 0;
 }
 
+// api_profile.hip: what every entry of the weighted stages refuses (no grid, no columns, the single slab, B outside the current
+// columns, L > kProfileMaxL, no weights set)
+int profile_check(sosrt_handle* h, int B, const char* what);
+
 inline bool use_sym(const sosrt_handle* h) {
     return (h->gemm.mode == SOSRT_CONTRACT_F64 || h->gemm.mode == SOSRT_CONTRACT_F64_DENSE) && h->phase.sym_ok;
 }

@@ -40,13 +40,6 @@ __global__ __launch_bounds__(256) void k_row_weights_apply(size_t n, const doubl
     rowcoef_r[i] *= w_aer[i];
 }
 
-// zone of row t of a column (nz <= kMaxZones ascending first rows)
-__device__ __forceinline__ int zone_of(const int* zr0, int nz, int t) {
-    int z = 0;
-    while (z + 1 < nz && t >= zr0[z + 1]) ++z;
-    return z;
-}
-
 // ------------------------------------------------------------------------------------------
 // k_first_order_profile: the recurrences, level choices, exclusions, R, phi and mu = 0 lane of k_first_order_beam, with
 //   q_t[m] = (omega_atm w_atm,t P0_atm[m] f_atm + omega_aer w_aer,t P0_aer[m] f_aer) / 4 pi        (f of row t's zone; clear: f_atm = 1)

@@ -1,7 +1,9 @@
-// Arithmetic shared by the stage kernels of beam.hip, emission.hip and profile.hip: the profile kernels have the bits of the
-// kernels they generalise only while the three files evaluate these expressions alike, so they live in one place.
+// Arithmetic shared by the stage kernels of beam.hip, emission.hip, profile.hip and profile_view.hip: the profile kernels have
+// the bits of the kernels they generalise only while the files evaluate these expressions alike, so they live in one place.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
 
 namespace sosrt {
 
@@ -38,6 +40,29 @@ __device__ __forceinline__ void linear_weights(double x, double E, double& w0, d
         w0 = 1 - a;
         w1 = a - E;
     }
+}
+
+// zone of row t of a column (nz <= kMaxZones ascending first rows)
+__device__ __forceinline__ int zone_of(const int* zr0, int nz, int t) {
+    int z = 0;
+    while (z + 1 < nz && t >= zr0[z + 1]) ++z;
+    return z;
+}
+
+// emission coefficient of row t (zone z) of column b under per-level weights:
+//   eps_t = 1 - (omega_atm w_atm,t f_atm + omega_aer w_aer,t f_aer)        (f of spec:149; clear zone: 1 - omega_atm w_atm,t)
+// wat = omega_atm w_atm,t; wr_all[i] the row's aerosol weight, read in an aerosol zone only.  k_emission_profile (profile.hip)
+// spells the same expression in its prologue: calling this there changed that kernel's register allocation, and its assembly
+// is kept as DESIGN section 29 measured it
+__device__ __forceinline__ double row_eps(const ColScalars& sc, int b, int z, double wat, double da, const double* __restrict__ wr_all,
+                                          size_t i) {
+    double eps = 1.0 - wat;
+    if (sc.zmix[(size_t)b * kMaxZones + z]) {
+        const double dr = sc.zdtr[(size_t)b * kMaxZones + z];
+        const double wrt = sc.zwr[(size_t)b * kMaxZones + z] * wr_all[i];
+        eps = 1.0 - (wat * (da / (da + dr)) + wrt * (dr / (da + dr)));
+    }
+    return eps;
 }
 
 }  // namespace sosrt

@@ -113,6 +113,10 @@ SIGNATURES = {
     "sosrt_set_row_weights_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "sosrt_first_order_profile_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 5),
     "sosrt_emission_profile_dev": (c_int, [c_void_p, c_int] + [c_void_p] * 5),
+    "sosrt_view_radiance_profile_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p]),
+    "sosrt_view_first_order_profile_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int,
+                                                                                          c_void_p, c_void_p]),
+    "sosrt_emission_view_profile_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_void_p]),
     "sosrt_planck_bands_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 3),
     "sosrt_band_reduce_dev": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 4 + [c_int]),
     "sosrt_brdf_operator_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),

@@ -7,7 +7,7 @@ independent columns that share (nb_layers, nb_angles, phase matrices) in one lau
 """
 from __future__ import annotations
 
-from contextlib import contextmanager
+from contextlib import contextmanager, nullcontext
 from dataclasses import dataclass, field
 from types import SimpleNamespace
 from typing import Optional
@@ -433,16 +433,26 @@ def solve_thermal(s: Solver, tau, planck, planck_surface, emissivity=None, tol=1
 
 
 def _gas_args(gas_tau, B, nb_layers, azimuths=None, view_mu=None, view_azimuths=None, mode_batch=False, mode_chunk=None,
-              surface="specular", delta_m=None, first_order="coded", save_orders=False, devices=None):
+              surface="specular", delta_m=None, first_order="coded", save_orders=False, devices=None, gas_view=False):
     """Checks of the `gas_tau` keyword, made before any handle exists: None, or a namespace with gas_tau [B, L] that
     `_prepare_batch` fills (tau0, the row weights).  B is a number or a callable that gives it.  The stages that evaluate one
-    constant per zone are refused (open items)."""
+    constant per zone are refused (open items); `gas_view=True` opens `view_mu`, whose stage then runs on
+    the weighted entries."""
+    if not isinstance(gas_view, (bool, np.bool_)):
+        raise ValueError("gas_view must be True or False (got %r)" % (gas_view,))
     if gas_tau is None:
+        if gas_view:
+            raise ValueError("gas_view=True belongs to gas_tau: without a gas profile the view stage needs no keyword")
         return None
     no = lambda what, why: ValueError("gas_tau is not available with %s: %s" % (what, why))
     if azimuths is not None:
         raise no("azimuths", "the first order of a Fourier mode evaluates one scattering coefficient per zone")
-    if view_mu is not None or view_azimuths is not None:
+    if gas_view:
+        if view_mu is None:
+            raise ValueError("gas_view=True is the view stage under gas_tau: give view_mu")
+        if view_azimuths is not None:
+            raise no("view_azimuths, also with gas_view=True", "the modes m >= 1 are not solved under per-level weights yet")
+    elif view_mu is not None or view_azimuths is not None:
         raise no("view_mu / view_azimuths", "the view stage evaluates one scattering coefficient per zone")
     if mode_batch or mode_chunk is not None:
         raise no("mode_batch / mode_chunk", "they belong to azimuths")
@@ -474,7 +484,7 @@ def _gas_args(gas_tau, B, nb_layers, azimuths=None, view_mu=None, view_azimuths=
 
 
 def solve_profile(s: Solver, tau, P0a, P0r, w, mu0=None, z=None, earth_radius=EARTH_RADIUS_KM, thermal=None, tol=1e-4, device=0,
-                  fetch_field=True, want=(), z_profile=None, keep_device=False, w_aer=None):
+                  fetch_field=True, want=(), z_profile=None, keep_device=False, w_aer=None, post=None):
     """The solve of handle `s` (grid, phase matrices and columns set) with PER-LEVEL WEIGHTS ON THE SOURCE FUNCTION (DESIGN section
     29): `w` [B, L] multiplies the atmosphere's row coefficient, `w_aer` (default `w`: an absorbing gas weighs both alike) the
     aerosol's (`Solver.set_row_weights_device`); `tau` [B, L] is the total optical depth, gas included.  Solar (`mu0` [B]): the
@@ -483,7 +493,10 @@ def solve_profile(s: Solver, tau, P0a, P0r, w, mu0=None, z=None, earth_radius=EA
     planck_surface [B], emissivity [B] or None): the emitted field with the weights in its emission coefficient
     (`emission_profile_device`).  Then the order loop from that field, and for the names `want` the epilogue that goes with the
     source.  Returns (SolveResult, sigma [B, L] or None, dict of the wanted epilogue arrays); keep_device=True: the torch tensors
-    {"I", "n", "status", "tau"[, "beam_slant"]} instead.  The weights are cleared when the call returns, also on error."""
+    {"I", "n", "status", "tau"[, "beam_slant"]} instead.  `post(dev, d_tau, d_I, d_sigma, B)` runs behind the solve, on the
+    resident field and inside the stream scope, WHILE THE WEIGHTS ARE SET (the view stage of DESIGN section 30): torch tensors
+    d_tau [B, L], d_I [B, L, 2N] and d_sigma [B, L] (the beam path of the first order; None with `thermal`); what it returns is
+    dropped.  The weights are cleared when the call returns, also on error."""
     import torch
     tau = np.ascontiguousarray(tau, dtype=np.float64)
     w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), tau.shape))
@@ -492,6 +505,8 @@ def solve_profile(s: Solver, tau, P0a, P0r, w, mu0=None, z=None, earth_radius=EA
         raise ValueError("the row weights must be finite and >= 0")
     if thermal is None and mu0 is None:
         raise ValueError("solve_profile needs mu0 (the solar source) or thermal")
+
+    kept = {}
 
     def seed(up, dev, d_tau, B, p0a, p0r):
         L = d_tau.shape[1]
@@ -514,6 +529,7 @@ def solve_profile(s: Solver, tau, P0a, P0r, w, mu0=None, z=None, earth_radius=EA
             d_sig = torch.empty((B, L), dtype=torch.float64, device=dev)
             s.beam_slant_device(d_tau.data_ptr(), d_z.data_ptr(), d_sig.data_ptr(), earth_radius, B=B)
         s.first_order_profile_device(d_tau.data_ptr(), d_sig.data_ptr(), p0a, p0r, d_I1.data_ptr(), B=B)
+        kept["sigma"] = d_sig
         return d_I1, {"beam_slant": d_sig}
 
     def epilogue(d_tau, d_I, d_zp, extra, out, B):
@@ -524,9 +540,13 @@ def solve_profile(s: Solver, tau, P0a, P0r, w, mu0=None, z=None, earth_radius=EA
         else:
             s.epilogue_beam_device(d_tau, d_I, extra["beam_slant"].data_ptr(), d_zp, "crit", *out, B=B)
 
+    def after(up, dev, d_tau, d_I, d_n, d_st, B, p0a, p0r):
+        post(dev, d_tau, d_I, kept.get("sigma"), B)
+        return {}
+
     try:
         r = _solve_resident(s, tau, None if thermal is not None else P0a, None if thermal is not None else P0r, seed, epilogue, tol,
-                            False, device, fetch_field, want, z_profile, keep_device)
+                            False, device, fetch_field, want, z_profile, keep_device, None if post is None else after)
     finally:
         s.set_row_weights_device(0, 0)
     if keep_device:
@@ -873,7 +893,7 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
                   view_mu=None, view_levels=(0, -1), view_quadrature="grid", view_azimuths=None,
                   view_first_order="exact", beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar", planck=None,
                   planck_surface=None, surface_emissivity=None, brdf=None, max_bounces=MAX_BOUNCES,
-                  brdf_modes=False, brdf_view=False, beam_stages=False, delta_m=None, gas_tau=None) -> BatchResult:
+                  brdf_modes=False, brdf_view=False, beam_stages=False, delta_m=None, gas_tau=None, gas_view=False) -> BatchResult:
     """Solve B independent columns (arrays mu0, tauStar_aer, grd_alb broadcast to a common length;
     tauStar_atm, alb_atm, alb_aer may be arrays too).  Phase functions that are not handed in as arrays are built on the
     device (`device_phase`): any name of `inputs.phase_function`, `mie_atm` / `mie_aer` = dict(r=, lambda0=, indx=, r_m=,
@@ -1029,10 +1049,19 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     scattering coefficient, the order loop with the weights on its row coefficients, and with `source='thermal'` the emission
     coefficient 1 - w_t (the zone's albedo) per row, so the gas emits.  Works with `beam='spherical'` (the slant path of the total
     tau), `aer_set` and phase arrays.  BatchResult.tau is the total, gas_tau and row_weight [B, L] say what was solved.  Not with
-    `azimuths`, `view_mu`, `view_azimuths`, `mode_batch`, `surface='brdf'`, `delta_m`, `first_order='readme'`, `save_orders` or
-    several `devices`: those stages evaluate one constant per zone."""
+    `azimuths`, `view_mu` (without `gas_view=True`, below), `view_azimuths`, `mode_batch`, `surface='brdf'`, `delta_m`,
+    `first_order='readme'`, `save_orders` or several `devices`: those stages evaluate one constant per zone.
+
+    `gas_view=True` (opt-in, with `gas_tau` and `view_mu`): THE GAS AT VIEW ANGLES.  The view stage runs on
+    the resident field while the weights are set, on the weighted entries: the scattered term with the weights on the stage's row
+    coefficients, the first term layer by layer with the weights in its scattering coefficient (on tau / mu0, or on the sphere's
+    slant path with `beam='spherical', beam_stages=True`), and with `source='thermal'` the weighted emission at the lanes.
+    Returns `view_mu_signed`, `I_view_first`, `I_view_scattered` and `I_view` as a view call does; `view_levels` and
+    `view_quadrature` as there, and the view stage's own refusals (`aer_set`, phase arrays) hold.  I and n are those of the call
+    without `view_mu`.  Still refused under `gas_tau`: `view_azimuths`, `azimuths`, `mode_batch`, `surface='brdf'`, `delta_m`,
+    `first_order='readme'`, `save_orders`, several `devices`."""
     gas = _gas_args(gas_tau, lambda: _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer), nb_layers, azimuths,
-                    view_mu, view_azimuths, mode_batch, mode_chunk, surface, delta_m, first_order, save_orders, devices)
+                    view_mu, view_azimuths, mode_batch, mode_chunk, surface, delta_m, first_order, save_orders, devices, gas_view)
     dm = _delta_m_args(delta_m, aer_phase_fun, azimuths, aer_set, P_aer, P0_aer, mode_batch, mode_chunk, surface, beam, source,
                        first_order, devices)
     if dm is not None and view_azimuths is not None and n_modes is None:
@@ -1105,8 +1134,17 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     bx = {}
     try:
         if gas is not None:
-            r, sigma, _ = solve_profile(s, tau, P0a, P0r, gas.w, np.broadcast_to(np.asarray(mu0, dtype=np.float64), (tau.shape[0],)),
-                                        np.linspace(z0, 0, int(nb_layers)) if spherical else None, earth_radius, thermal, tol, device)
+            mu0v = np.broadcast_to(np.asarray(mu0, dtype=np.float64), (tau.shape[0],))
+            gv = {}
+
+            def gas_views(dev, d_tau, d_I, d_sigma, B):
+                # the view stage on the resident field, while the weights are set
+                gv["first"], gv["scat"] = view_radiance(s, d_tau, d_I, mu0v, vmu, vlev, vquad, atm_phase_fun, g_atm, mie_atm,
+                                                        aer_phase_fun, g_aer, mie_aer, device, thermal=thermal, sigma=d_sigma,
+                                                        profile=True, dev=dev)
+            r, sigma, _ = solve_profile(s, tau, P0a, P0r, gas.w, mu0v,
+                                        np.linspace(z0, 0, int(nb_layers)) if spherical else None, earth_radius, thermal, tol, device,
+                                        post=gas_views if view_mu is not None else None)
         elif spherical:
             r, sigma, _ = solve_spherical(s, tau, P0a, P0r, np.linspace(z0, 0, int(nb_layers)), earth_radius, tol, save_orders, device)
         elif ground:
@@ -1148,8 +1186,12 @@ def SOS_Aer_batch(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=1.0, 
     if view_mu is not None:
         mu0v = np.broadcast_to(np.atleast_1d(np.asarray(mu0, dtype=np.float64)), (tau.shape[0],))
         out.view_mu_signed = np.concatenate((-vmu, vmu))
-        out.I_view_first, out.I_view_scattered = view_radiance(s, tau, r.I, mu0v, vmu, vlev, vquad, atm_phase_fun, g_atm, mie_atm,
-                                                               aer_phase_fun, g_aer, mie_aer, device, thermal=thermal, sigma=sigma)
+        if gas is not None:
+            out.I_view_first, out.I_view_scattered = gv["first"], gv["scat"]
+        else:
+            out.I_view_first, out.I_view_scattered = view_radiance(s, tau, r.I, mu0v, vmu, vlev, vquad, atm_phase_fun, g_atm,
+                                                                   mie_atm, aer_phase_fun, g_aer, mie_aer, device, thermal=thermal,
+                                                                   sigma=sigma)
         out.I_view = out.I_view_first + out.I_view_scattered
         if ground:
             out.I_view_ground = bx["I_view_ground"]
@@ -1240,22 +1282,26 @@ def _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_mod
 
 
 def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
-                  mie_aer, device=0, thermal=None, sigma=None):
+                  mie_aer, device=0, thermal=None, sigma=None, profile=False, dev=None):
     """The view stage on the field `I` [B, L, 2N] of handle `s` (whose columns are set): rows of both phase functions at the
     signed lanes, then `Solver.view_radiance_device` with I_src = I.  Returns (first order, scattered), each [B, nlev, 2V].
     `thermal` = (planck [B, L], planck_surface [B], emissivity [B] or None): I is a thermal field, and the first term is the
     emission at the view lanes (`Solver.emission_view_device`) instead of the solar first order.  `sigma` [B, L] (the
     `beam_slant` of `solve_spherical`): the first term is the first order on that beam path at the view lanes
-    (`Solver.view_first_order_beam_device`) instead of the plane closed form."""
+    (`Solver.view_first_order_beam_device`) instead of the plane closed form.  `profile=True`: the handle
+    carries per-level weights, and the stage runs on the three weighted entries (`Solver.view_radiance_profile_device`,
+    `view_first_order_profile_device`, `emission_view_profile_device`); the first term is always explicit, on `sigma` or, where
+    none is given, on the plane beam sigma = tau / mu0 -- no closed form is used under weights.  `dev`: the caller is inside a
+    stream scope of its own on that torch device (the `post` of `solve_profile`), and tau, I and sigma are tensors there."""
     import torch
     B, L = tau.shape
     D, V2 = s.D, 2 * len(view_mu)
     sgn = np.concatenate((-view_mu, view_mu))
-    with _on_torch_stream(s, device) as dev:
+    with (_on_torch_stream(s, device) if dev is None else nullcontext(dev)) as dev:
         up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)    # (a copy: broadcast inputs are read-only)
         # (the field is large and already contiguous: uploaded from where it lies, not through a host copy)
-        d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
-        d_I = torch.from_numpy(np.ascontiguousarray(I)).to(dev)
+        d_tau = tau if isinstance(tau, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
+        d_I = I if isinstance(I, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(I)).to(dev)
         d_mu0 = up(mu0)
         rows, p0rows = [], []
         for phase in ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)):
@@ -1271,6 +1317,19 @@ def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase
         d_first = torch.empty((B, len(levels), V2), dtype=torch.float64, device=dev)
         torch.cuda.current_stream(dev).synchronize()
         first, p0_atm, p0_aer = d_first.data_ptr(), p0rows[0].data_ptr(), p0rows[1].data_ptr()
+        if profile:
+            if thermal is not None:
+                d_pl, d_bs = up(thermal[0]), up(thermal[1])
+                d_es = None if thermal[2] is None else up(thermal[2])
+                s.emission_view_profile_device(view_mu, d_tau.data_ptr(), d_pl.data_ptr(), d_bs.data_ptr(), levels, first,
+                                               0 if d_es is None else d_es.data_ptr(), B=B)
+            else:
+                d_sig = d_tau / d_mu0[:, None] if sigma is None else sigma if isinstance(sigma, torch.Tensor) else up(sigma)
+                s.view_first_order_profile_device(view_mu, d_tau.data_ptr(), d_sig.data_ptr(), p0_atm, p0_aer, levels, first, B=B)
+            s.view_radiance_profile_device(view_mu, d_tau.data_ptr(), d_I.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), levels,
+                                           d_scat.data_ptr(), quadrature=quadrature, B=B)
+            s.synchronize()
+            return d_first.cpu().numpy(), d_scat.cpu().numpy()
         if thermal is not None:
             # the first term is the emission at the lanes: the view stage gets no first-order addresses and leaves it alone
             d_pl, d_bs = up(thermal[0]), up(thermal[1])

@@ -475,6 +475,42 @@ class Solver:
         check(lib().sosrt_emission_profile_dev(self._h, int(self.B if B is None else B), _vp(d_tau), _vp(d_planck),
                                                _vp(d_planck_surface), _vp(d_emissivity), _vp(d_I0_out)))
 
+    # ---- gas absorption at view angles: the weights in the view stage (sosrt.h) --------
+    def view_radiance_profile_device(self, mu_view, d_tau: int, d_I_src: int, d_rows_atm: int, d_rows_aer: int, levels,
+                                     d_scat_out: int, quadrature="grid", B: Optional[int] = None):
+        """The scattered term of `view_radiance_device` with the handle's weights on the stage's row coefficients:
+        d_scat_out [B, nlev, 2V].  It has no first-order arguments: under weights the first term is
+        `view_first_order_profile_device` or `emission_view_profile_device`.  Needs weights to be set."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
+        lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.int32)
+        q = self._QUADS.get(quadrature, quadrature)
+        if isinstance(q, str) or isinstance(q, bool) or not isinstance(q, (int, np.integer)):
+            raise ValueError("quadrature must be 'grid' or 'linear' (got %r)" % (quadrature,))
+        check(lib().sosrt_view_radiance_profile_dev(self._h, int(self.B if B is None else B), int(m.size),
+                                                    _ptr(m) if m.size else None, _vp(d_tau), _vp(d_I_src), _vp(d_rows_atm),
+                                                    _vp(d_rows_aer), int(q), int(lev.size), _ptr(lev) if lev.size else None,
+                                                    _vp(d_scat_out)))
+
+    def view_first_order_profile_device(self, mu_view, d_tau: int, d_sigma: int, d_p0rows_atm: int, d_p0rows_aer: int, levels,
+                                        d_first_out: int, nset: int = 1, B: Optional[int] = None):
+        """`view_first_order_beam_device` with the handle's weights in the scattering coefficient of every row (d_sigma =
+        tau / mu0 is the plane beam, `beam_slant_device` on the total tau the sphere): d_first_out [nset, B, nlev, 2V]."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
+        lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.int32)
+        check(lib().sosrt_view_first_order_profile_dev(self._h, int(self.B if B is None else B), int(m.size),
+                                                       _ptr(m) if m.size else None, _vp(d_tau), _vp(d_sigma), int(nset),
+                                                       _vp(d_p0rows_atm), _vp(d_p0rows_aer), int(lev.size),
+                                                       _ptr(lev) if lev.size else None, _vp(d_first_out)))
+
+    def emission_view_profile_device(self, mu_view, d_tau: int, d_planck: int, d_planck_surface: int, levels, d_out: int,
+                                     d_emissivity: int = 0, B: Optional[int] = None):
+        """`emission_view_device` with the handle's weights in the emission coefficient of every row: d_out [B, nlev, 2V]."""
+        m = np.ascontiguousarray(np.atleast_1d(mu_view), dtype=np.float64)
+        lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.int32)
+        check(lib().sosrt_emission_view_profile_dev(self._h, int(self.B if B is None else B), int(m.size),
+                                                    _ptr(m) if m.size else None, _vp(d_tau), _vp(d_planck), _vp(d_planck_surface),
+                                                    _vp(d_emissivity), int(lev.size), _ptr(lev) if lev.size else None, _vp(d_out)))
+
     # ---- band integration (sosrt.h; DESIGN section 19) --------------------------------------------------
     def planck_bands_device(self, d_T: int, d_T_surface: int, nu_lo, nu_hi, d_planck_out: int, d_planck_surface_out: int,
                             d_scale_out: int = 0, C: int = 1, normalise=True):
