@@ -762,6 +762,33 @@ int sosrt_band_reduce_dev(sosrt_t* h, int C, int K, int M, const double* d_weigh
                           const double* d_scale /*[K][C] or NULL: 1*/, const double* d_x /*[K][C][M]*/,
                           double* d_out /*[C][M]*/, int accumulate);
 
+/* ---- brightness temperature of a band-summed radiance ------------------------------------------------------
+ * The inverse of the Planck stage.  T_out[c][m] is the temperature T at which
+ *     f_c(T) = sum_k w[k][c] B_k(T)
+ * equals radiance[c][m]; B_k is the band radiance of sosrt_planck_bands_dev over [nu_lo[k], nu_hi[k]] (the same S / G split, the
+ * same constants, the same non-cancelling difference), w the weights of sosrt_band_reduce_dev without the scales (the scale is a
+ * property of the normalised source, not of the channel); a NULL d_weight stands for ones.  g-points of one band: K equal pairs of
+ * edges, weights that sum to 1.  Sub-bands of a response function: distinct edges, the response as weights.  f_c is strictly
+ * increasing in T for weights >= 0 that are not all zero.
+ * Iteration, per element: Newton on ln f in the variable u = 1 / T (close to linear in the Wien regime), from T = 250 K:
+ *     u' = u + ln(f / R) f / (T^2 f'),  T' = 1 / u',
+ *     f' = sum_k w_k dB_k/dT,  dB/dT = 4 B / T + (2 k^4 / h^3 c^2) T^3 [x_lo^4 / (e^x_lo - 1) - x_hi^4 / (e^x_hi - 1)]
+ * (expm1; the first bracket term is 0 at x_lo = 0), safeguarded by a bracket [1 K, 1e5 K] that every evaluation tightens (f < R
+ * raises the lower end to T, f > R lowers the upper end to T): an iterate that is not finite or falls outside the closed bracket
+ * is replaced by the bracket's geometric mean.  The first accepted Newton step with |T' - T| <= 1e-9 T' is applied and ends the
+ * iteration (quadratic convergence leaves the result at rounding); at most 40 iterations, and an element that has not stopped by
+ * then is NaN.  NaN also where the radiance is not finite or <= 0, where it lies outside (f(1 K), f(1e5 K)), and where the
+ * column's weights are all zero or one is negative.  Nothing is read back to be checked.  Within 1e-12 relative of the NumPy form
+ * for bands of 10 cm^-1 and more (narrower bands lose digits as the Planck stage does).
+ * One lane per element; the band edges travel by value, so K <= 64: the sum over the bands sits inside the iteration and cannot
+ * be split over launches.  A stage beside the solve, detected by symbol (SOSRT_VERSION is unchanged), enqueued on the handle's
+ * stream; nothing of the handle's solve state is read or written.
+ * Refused with SOSRT_E_INVALID, a message and nothing written: C, K or M < 1; K > 64; a null nu_lo, nu_hi, d_radiance or d_T_out;
+ * an edge that is not finite or is negative; nu_hi <= nu_lo. */
+int sosrt_brightness_temperature_dev(sosrt_t* h, int C, int K, int M, const double* nu_lo /*host [K], cm^-1*/,
+                                     const double* nu_hi /*host [K]*/, const double* d_weight /*[K][C] or NULL: 1*/,
+                                     const double* d_radiance /*[C][M], W m^-2 sr^-1*/, double* d_T_out /*[C][M], kelvin*/);
+
 /* ---- BRDF ground: a series in ground reflections around the order loop -------------------------------------
  * The field over a ground that reflects by a bidirectional reflectance factor rho(mu_out, mu_in, phi) is the sum over the number
  * of ground reflections: the solve over a black ground (specular surface, grd_alb = 0), then per reflection ("bounce") the

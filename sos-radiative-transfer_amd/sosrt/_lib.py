@@ -119,6 +119,7 @@ SIGNATURES = {
     "sosrt_emission_view_profile_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_void_p]),
     "sosrt_planck_bands_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 3),
     "sosrt_band_reduce_dev": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 4 + [c_int]),
+    "sosrt_brightness_temperature_dev": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
     "sosrt_brdf_operator_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "sosrt_brdf_beam_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sosrt_brdf_operator_modes_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -78,6 +78,84 @@ def planck_band(T, nu_lo, nu_hi):
     return ((RADIANCE * t2) * t2) * np.where(xh < 1.0, below, np.where(xl >= 1.0, above, mixed))
 
 
+BRIGHTNESS_BRACKET = (1.0, 1e5)     # kelvin
+BRIGHTNESS_START = 250.0
+BRIGHTNESS_STOP = 1e-9              # the accepted Newton step that ends the iteration, relative to T
+BRIGHTNESS_ITERATIONS = 40
+BRIGHTNESS_MAX_BANDS = 64           # the device entry's band edges travel by value
+
+
+def _slope_term(x):
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        x2 = x * x
+        return np.where(x > 0.0, (x2 * x2) / np.expm1(np.where(x > 0.0, x, 1.0)), 0.0)
+
+
+def _channel(T, lo, hi, w):
+    """f = sum_k w[k] B_k(T) and df/dT, k ascending: T [...], lo / hi [K, 1..], w [K, ...]."""
+    f, df = np.zeros_like(T), np.zeros_like(T)
+    t3 = (RADIANCE * T) * (T * T)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in range(lo.shape[0]):
+            B = planck_band(T, lo[k], hi[k])
+            dB = 4.0 * B / T + t3 * (_slope_term((C2 * lo[k]) / T) - _slope_term((C2 * hi[k]) / T))
+            f = f + w[k] * B
+            df = df + w[k] * dB
+    return f, df
+
+
+def brightness_temperature(radiance, nu_lo, nu_hi, weights=None, return_iterations=False):
+    """BRIGHTNESS TEMPERATURE OF A BAND-SUMMED RADIANCE (host NumPy): the temperature T (kelvin) at which
+    f(T) = sum_k weights[k] planck_band(T, nu_lo[k], nu_hi[k]) equals `radiance` (W m-2 sr-1, any shape).  `nu_lo`, `nu_hi`: [K]
+    (or scalars: one band) in cm^-1; `weights`: None (ones), [K], or [K, ...] broadcasting against the radiance behind the
+    leading K -- g-point weights of one band (equal edges, sum 1) or the response over sub-bands.
+
+    Newton on ln f in u = 1 / T from 250 K, u' = u + ln(f / R) f / (T^2 f'), with dB/dT = 4 B / T + 2 k^4 / (h^3 c^2) T^3
+    [x_lo^4 / (e^x_lo - 1) - x_hi^4 / (e^x_hi - 1)]; a bracket [1 K, 1e5 K] that every evaluation tightens, and whose geometric
+    mean replaces an iterate that is not finite or leaves it; the first accepted Newton step with |dT| <= 1e-9 T is applied and
+    ends the iteration; at most 40 iterations, then NaN.  NaN where the radiance is not finite or <= 0, lies outside
+    (f(1 K), f(1e5 K)), or the weights are all zero or one is negative.  The arithmetic of
+    `Solver.brightness_temperature_device`; `return_iterations=True`: (T, the evaluations each element took, 0 where NaN from
+    the start)."""
+    R = np.asarray(radiance, dtype=np.float64)
+    lo, hi = np.atleast_1d(np.asarray(nu_lo, dtype=np.float64)), np.atleast_1d(np.asarray(nu_hi, dtype=np.float64))
+    if lo.ndim != 1 or lo.shape != hi.shape or lo.size < 1:
+        raise ValueError("brightness_temperature needs nu_lo and nu_hi as two arrays [K] of one length")
+    if np.any(~np.isfinite(lo)) or np.any(~np.isfinite(hi)) or np.any(lo < 0) or np.any(hi <= lo):
+        raise ValueError("brightness_temperature needs finite band edges with 0 <= nu_lo < nu_hi (cm^-1)")
+    K = lo.size
+    w = np.ones((K,) + (1,) * R.ndim) if weights is None else np.asarray(weights, dtype=np.float64)
+    if w.ndim == 1:
+        w = w.reshape((-1,) + (1,) * R.ndim)
+    try:
+        w = np.broadcast_to(w, (K,) + R.shape)
+    except ValueError:
+        raise ValueError("weights of the shape %s do not broadcast to [K, ...] = %s" % (np.shape(weights), (K,) + R.shape)) from None
+    lo, hi = lo.reshape((K,) + (1,) * R.ndim), hi.reshape((K,) + (1,) * R.ndim)
+    with np.errstate(invalid="ignore"):
+        live = np.isfinite(R) & (R > 0) & np.all(w >= 0, axis=0) & (np.sum(w, axis=0) > 0)
+        a, b = np.full(R.shape, BRIGHTNESS_BRACKET[0]), np.full(R.shape, BRIGHTNESS_BRACKET[1])
+        live = live & (_channel(a, lo, hi, w)[0] < R) & (R < _channel(b, lo, hi, w)[0])
+    T = np.full(R.shape, BRIGHTNESS_START)
+    out, its = np.full(R.shape, np.nan), np.zeros(R.shape, dtype=np.int64)
+    for it in range(BRIGHTNESS_ITERATIONS):
+        if not np.any(live):
+            break
+        f, df = _channel(T, lo, hi, w)
+        a, b = np.where(live & (f < R), T, a), np.where(live & (f > R), T, b)
+        with np.errstate(all="ignore"):
+            Tn = 1.0 / (1.0 / T + (np.log(f / R) * f) / ((T * T) * df))
+            newton = (Tn >= a) & (Tn <= b)
+        Tn = np.where(newton, Tn, np.sqrt(a * b))
+        with np.errstate(invalid="ignore"):
+            stop = live & newton & (np.abs(Tn - T) <= BRIGHTNESS_STOP * Tn)
+        T = np.where(live, Tn, T)
+        its = its + live
+        out = np.where(stop, T, out)
+        live = live & ~stop
+    return (out, its) if return_iterations else out
+
+
 def wavenumber_bands(edges_um):
     """(nu_lo [K], nu_hi [K]) in cm^-1 of the K bands between K + 1 wavelength edges in micrometres (strictly ascending or
     descending; band k lies between edges k and k + 1)."""
@@ -99,16 +177,23 @@ class BandResult:
     status: np.ndarray                    # [K, C]
     scale: Optional[np.ndarray] = None    # [K, C] (thermal) the maximum each point's source was divided by, W m-2 sr-1
     point_net_toa: Optional[np.ndarray] = None   # [K, C] (per_point=True) every point's own net_toa, unweighted, scale applied
+    # with view_mu: the channel's radiance at the view lanes, summed over the points like the fluxes
+    view_mu_signed: Optional[np.ndarray] = None          # [2V] the lanes (-view_mu, +view_mu)
+    I_view_first: Optional[np.ndarray] = None            # [C, nlev, 2V] the first term: emission (thermal) or first order (solar)
+    I_view_scattered: Optional[np.ndarray] = None        # [C, nlev, 2V]
+    I_view: Optional[np.ndarray] = None                  # [C, nlev, 2V] their sum
+    brightness_temperature: Optional[np.ndarray] = None  # [C, nlev, 2V] (thermal, brightness=True) kelvin; NaN where I_view is 0
+    point_I_view: Optional[np.ndarray] = None            # [K, C, nlev, 2V] (per_point=True) every point's I_view, unweighted, scale applied
 
 
 # ---- checks made before any handle exists ---------------------------------------------------------------------------------------
-def _refuse(want, beam, azimuths, view_azimuths, devices, first_order):
+def _refuse(want, beam, azimuths, view_azimuths, devices, first_order, views=False):
     want = tuple(want)
     if "diffusivity" in want:
         raise ValueError("want: 'diffusivity' is a ratio of two integrals of the field, not additive over spectral points; sum "
                          "flux_down and flux_up and form it from them")
     bad = [k for k in want if k not in WANT]
-    if bad or not want:
+    if bad or (not want and not views):
         raise ValueError("want must name some of %s (got %r)" % (WANT, want))
     if beam != "plane":
         raise ValueError("beam='spherical' is not available in the band drivers: the slant-path first order is solved per batch "
@@ -186,6 +271,81 @@ def _points_per_solve(points_per_solve, K, C, L, N):
     return min(P, K)
 
 
+def _view_points(view_mu, view_levels, view_quadrature, L, surface, atm_phase_fun, aer_phase_fun, point_aerosol=None):
+    """Checks of `view_mu` in a band call, made before any handle exists: None, or (view_mu [V], levels as row indices,
+    quadrature) as `main._view_args` returns them."""
+    if view_mu is None:
+        return None
+    if point_aerosol is not None or isinstance(aer_phase_fun, (list, tuple)):
+        raise ValueError("view_mu is not available in the band drivers with a list of aerosols in aer_phase_fun (point_aerosol): "
+                         "the view stage reads one aerosol phase function; call per aerosol and add the sums")
+    if surface != "specular":
+        raise ValueError("view_mu is not available in the band drivers with surface=%r: the first term at the view lanes (the "
+                         "emission, the solar first order) is specular / none only, and the Lambertian boundary of the orders "
+                         "n >= 2 needs the grid's surface row of every order" % (surface,))
+    return main._view_args(view_mu, view_levels, view_quadrature, L, None, None, None, None, surface, None, "coded", None, None,
+                           atm_phase_fun, aer_phase_fun)
+
+
+def _brightness_args(brightness, view, weights, K):
+    """Checks of `brightness` in `band_thermal`, made before any handle exists: whether the brightness stage runs."""
+    if not isinstance(brightness, (bool, np.bool_)):
+        raise ValueError("brightness must be True or False (got %r)" % (brightness,))
+    if view is None or not brightness:
+        return False
+    if K > BRIGHTNESS_MAX_BANDS:
+        raise ValueError("brightness=True takes at most %d bands (got K = %d): the sum over the bands sits inside the inversion, "
+                         "whose band edges travel by value; pass brightness=False and invert the channel's I_view yourself"
+                         % (BRIGHTNESS_MAX_BANDS, K))
+    if np.any(~(weights >= 0)) or np.any(~(weights.sum(axis=0) > 0)):
+        c = int(np.flatnonzero(np.any(~(weights >= 0), axis=0) | ~(weights.sum(axis=0) > 0))[0])
+        raise ValueError("brightness=True needs weights >= 0 that are not all zero in a column (column %d: %s): the channel's "
+                         "radiance must increase with temperature; pass brightness=False" % (c, weights[:, c]))
+    return True
+
+
+class _Views:
+    """The device side of the band sum of view radiances: the view stage on a chunk's resident field, and the summed first and
+    scattered terms [C, nlev, 2V].  The phase rows and p0 rows are built once, at the first (and largest) chunk."""
+
+    def __init__(self, torch, dev, view, phases, device, C, per_point):
+        self.vmu, self.vlev, self.vquad = view
+        self.phases, self.device, self.dev, self.C = phases, device, dev, C
+        shape = (C, len(self.vlev), 2 * len(self.vmu))
+        self.M = shape[1] * shape[2]
+        self.first = torch.zeros(shape, dtype=torch.float64, device=dev)
+        self.scat = torch.zeros(shape, dtype=torch.float64, device=dev)
+        self.points = [] if per_point else None
+        self.rows = self.cur = None
+
+    def stage(self, s, d_tau, d_I, mu0, thermal=None, sigma=None, profile=False):
+        """The view stage on B columns, inside a stream scope: both terms [B, nlev, 2V] stay on the device for `reduce`."""
+        import torch
+        if self.rows is None:
+            d_mu0 = torch.from_numpy(np.array(mu0, dtype=np.float64, order="C")).to(self.dev)
+            self.rows = main.view_rows(s, self.vmu, d_mu0, self.phases[:3], self.phases[3:], self.dev)
+        self.cur = main.view_radiance(s, d_tau, d_I, mu0, self.vmu, self.vlev, self.vquad, *self.phases, self.device, thermal=thermal,
+                                      sigma=sigma, profile=profile, dev=self.dev, keep_device=True, rows=self.rows)
+
+    def reduce(self, s, P, d_weight, d_scale, first):
+        for x, o in zip(self.cur, (self.first, self.scat)):
+            s.band_reduce_device(x.data_ptr(), o.data_ptr(), self.C, P, self.M, d_weight, d_scale, accumulate=not first)
+        if self.points is not None:
+            self.points.append(self.cur[0] + self.cur[1])
+        self.cur = None
+
+
+def _view_result(r, vw, d_view, scale=None):
+    """The view fields of BandResult `r` from the sums of `vw` and their sum `d_view` [C, nlev, 2V], formed on the device."""
+    import torch
+    r.view_mu_signed = np.concatenate((-vw.vmu, vw.vmu))
+    r.I_view_first, r.I_view_scattered, r.I_view = vw.first.cpu().numpy(), vw.scat.cpu().numpy(), d_view.cpu().numpy()
+    if vw.points is not None:
+        K = r.n.shape[0]
+        p = torch.cat(vw.points).cpu().numpy().reshape((K,) + r.I_view.shape)
+        r.point_I_view = p if scale is None else p * scale[:, :, None, None]
+
+
 def _thermal_inputs(bands, temperature, surface_temperature, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, weights,
                     surface_emissivity, nb_layers):
     """Every array of a thermal band call at its full shape: (nu_lo [K], nu_hi [K], T [C, L], T_s [C], dict of the per-point
@@ -249,13 +409,15 @@ class _Sum:
         return {k: (host[k][:, 0] if k == "net_toa" else host[k]) if k in host else None for k in WANT}
 
 
-def _sum_points(s, device, acc, P, d_weight, d_scale, solve_chunk, epilogue, N, max_orders):
+def _sum_points(s, device, acc, P, d_weight, d_scale, solve_chunk, epilogue, N, max_orders, views=None, view_stage=None):
     """The chunk loop of both drivers: per chunk of P points `solve_chunk(k0, k1, B)` -> the tensors {"I", "n", "status",
     "tau"} of its B = (k1 - k0) C columns, left on the device; then, with the handle `s` on torch's stream, `epilogue(d, acc,
     B)` into the chunk buffers of `acc` and `band_reduce_device` with the weights d_weight [K, C] (and the scales d_scale
     [K, C], or None), accumulating over the chunks -- the chunks run in ascending order, so the sum adds the points in
     ascending order.  Any non-zero status raises (`N`, `max_orders`: for the message).  Returns (n [K, C], status [K, C], every
-    point's net_toa [K, C] or None); the summed arrays are `acc.result()`."""
+    point's net_toa [K, C] or None); the summed arrays are `acc.result()`.  `views` (a `_Views`, with `view_mu`): in the same
+    scope `view_stage(d, k0, k1, B)` runs the view stage on the chunk where `solve_chunk` has not (it has under `gas_tau`, while
+    the weights were set), and both terms are reduced like the epilogue's buffers; `acc` may then have nothing to sum."""
     import torch
     (K, C), per_point = d_weight.shape, acc.per_point
     n_all, st_all, net_all = [], [], []
@@ -264,8 +426,13 @@ def _sum_points(s, device, acc, P, d_weight, d_scale, solve_chunk, epilogue, N, 
         B = (k1 - k0) * C
         d = solve_chunk(k0, k1, B)
         with main._on_torch_stream(s, device):
-            epilogue(d, acc, B)
-            acc.reduce(s, k1 - k0, d_weight[k0:k1].data_ptr(), 0 if d_scale is None else d_scale[k0:k1].data_ptr(), k0 == 0)
+            w_ptr, s_ptr = d_weight[k0:k1].data_ptr(), 0 if d_scale is None else d_scale[k0:k1].data_ptr()
+            if acc.names:
+                epilogue(d, acc, B)
+            acc.reduce(s, k1 - k0, w_ptr, s_ptr, k0 == 0)
+            if views is not None:
+                view_stage(d, k0, k1, B)
+                views.reduce(s, k1 - k0, w_ptr, s_ptr, k0 == 0)
             if per_point:
                 net_all.append(acc.buf["net_toa"][:B, 0].clone())
         n_all.append(d["n"])
@@ -282,7 +449,8 @@ def band_thermal(bands, temperature, surface_temperature, tauStar_aer, grd_alb, 
                  surface_emissivity=None, want=WANT, points_per_solve=None, per_point=False, z0=120, z_up=25, z_down=17,
                  nb_layers=200, nb_angles=128, atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, mie_atm=None,
                  mie_aer=None, surface="specular", tol=1e-4, max_orders=256, device=0, beam="plane", azimuths=None,
-                 view_azimuths=None, devices=None, first_order="coded", gas_tau=None) -> BandResult:
+                 view_azimuths=None, devices=None, first_order="coded", gas_tau=None, view_mu=None, view_levels=(0, -1),
+                 view_quadrature="grid", brightness=True) -> BandResult:
     """LONGWAVE FLUXES AND HEATING RATES SUMMED OVER K SPECTRAL POINTS, for C columns: sum_k weights[k] x (the thermal solve of
     point k with the Planck radiance of band k as its source), in W m-2 (the heating rate in the epilogue's unit per W m-2).
 
@@ -310,12 +478,25 @@ def band_thermal(bands, temperature, surface_temperature, tauStar_aer, grd_alb, 
     `gas_tau` [K, L] or [K, C, L] (default None, the code path as it was): EVERY SPECTRAL POINT ITS OWN GAS ABSORPTION PROFILE
     (DESIGN section 29), the cumulative absorption optical depth of the gases at the levels for that point -- 0 at the top, finite,
     non-decreasing.  Point k is solved on tau0 + gas_tau[k] with the row weights of `inputs.gas_row_weights` in its emission
-    coefficient and its source function (`main.solve_profile`), so the heating rate gets the vertical structure of the gas."""
-    want = _refuse(want, beam, azimuths, view_azimuths, devices, first_order)
+    coefficient and its source function (`main.solve_profile`), so the heating rate gets the vertical structure of the gas.
+
+    `view_mu` [V] (default None, the code path as it was): THE CHANNEL'S RADIANCE AT VIEW ANGLES.  Per chunk
+    the view stage of `SOS_Aer_batch(source='thermal', view_mu=...)` runs on the resident field -- the emission at the lanes
+    plus the scattered term, under `gas_tau` the weighted entries of `gas_view=True`, while the weights are set -- and both terms
+    are summed over the points like the fluxes, with the weights and the scales: `view_mu_signed` [2V], `I_view_first`,
+    `I_view_scattered` and `I_view` [C, nlev, 2V] in W m-2 sr-1, the lanes and `view_levels` / `view_quadrature` as in
+    `SOS_Aer_batch`; the same bits for every `points_per_solve`.  `brightness=True` adds `brightness_temperature` [C, nlev, 2V],
+    kelvin, from `Solver.brightness_temperature_device` on the summed `I_view` with `weights` and `bands` (NaN where the radiance
+    is 0: the downward lanes at the top).  `per_point=True` adds `point_I_view` [K, C, nlev, 2V].  `want=()` is then allowed: no
+    epilogue runs.  Refused before any handle exists: a surface other than 'specular'; what the view stage refuses
+    (`main._view_args`); with brightness=True more than 64 bands, and weights that are negative or all zero in a column."""
+    view = _view_points(view_mu, view_levels, view_quadrature, int(nb_layers), surface, atm_phase_fun, aer_phase_fun)
+    want = _refuse(want, beam, azimuths, view_azimuths, devices, first_order, views=view is not None)
     L, N = int(nb_layers), int(nb_angles)
     lo, hi, T, Ts, pp, rho, es = _thermal_inputs(bands, temperature, surface_temperature, tauStar_aer, grd_alb, tauStar_atm, alb_atm,
                                                  alb_aer, weights, surface_emissivity, L)
     K, C = pp["weights"].shape
+    brightness = _brightness_args(brightness, view, pp["weights"], K)
     gas_all = _gas_points(gas_tau, K, C, L)
     P = _points_per_solve(points_per_solve, K, C, L, N)
     import torch
@@ -329,6 +510,8 @@ def band_thermal(bands, temperature, surface_temperature, tauStar_aer, grd_alb, 
         d_es = None if es is None else up(np.tile(es, P))
         d_z = up(np.linspace(z0, 0, L)) if "heating_rate" in want else None
         acc = _Sum(torch, dev, want, per_point, P * C, C, L)
+        vw = None if view is None else _Views(torch, dev, view, (atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer),
+                                              device, C, per_point)
         s.planck_bands_device(d_T.data_ptr(), d_Ts.data_ptr(), lo, hi, d_pl.data_ptr(), d_bs.data_ptr(), d_scale.data_ptr(), C=C)
     scale = d_scale.cpu().numpy()
     if not np.all(scale > 0):
@@ -336,6 +519,9 @@ def band_thermal(bands, temperature, surface_temperature, tauStar_aer, grd_alb, 
         raise ValueError("band %d = [%g, %g] cm^-1 has no Planck radiance in double precision at the temperatures of column %d "
                          "(every value underflows to 0, scale = %r): there is no source to normalise; leave the band out"
                          % (k, lo[k], hi[k], c, float(scale[k, c])))
+
+    def sources(k0, k1, B):
+        return d_pl[k0:k1].reshape(B, L), d_bs[k0:k1].reshape(B), None if d_es is None else d_es[:B]
 
     def solve_chunk(k0, k1, B):
         flat = lambda a: a[k0:k1].reshape(B)
@@ -346,18 +532,33 @@ def band_thermal(bands, temperature, surface_temperature, tauStar_aer, grd_alb, 
             flat(pp["alb_aer"]), z0, z_up, z_down, L, N, atm_phase_fun, g_atm, aer_phase_fun, g_aer, mie_atm, mie_aer, None, None,
             None, None, surface, max_orders, device, gas=gas)
         if gas is not None:
-            return main.solve_profile(s, tau, None, None, gas.w, thermal=(d_pl[k0:k1].reshape(B, L), d_bs[k0:k1].reshape(B),
-                                                                           None if d_es is None else d_es[:B]),
-                                      tol=tol, keep_device=True, device=device)
-        return main.solve_thermal(s, tau, d_pl[k0:k1].reshape(B, L), d_bs[k0:k1].reshape(B), None if d_es is None else d_es[:B],
-                                  tol=tol, keep_device=True, device=device)
+            # the view stage on the resident field, while the weights are set (as gas_view=True of SOS_Aer_batch)
+            gas_views = lambda dev, d_tau, d_I, d_sigma, B: vw.stage(s, d_tau, d_I, np.full(B, 0.5), thermal=sources(k0, k1, B),
+                                                                     profile=True)
+            return main.solve_profile(s, tau, None, None, gas.w, thermal=sources(k0, k1, B), tol=tol, keep_device=True,
+                                      device=device, post=None if vw is None else gas_views)
+        return main.solve_thermal(s, tau, *sources(k0, k1, B), tol=tol, keep_device=True, device=device)
 
     def epilogue(d, acc, B):
         s.epilogue_emission_device(d["tau"].data_ptr(), d["I"].data_ptr(), 0 if d_z is None else d_z.data_ptr(),
                                    acc.ptr("flux_down"), acc.ptr("flux_up"), 0, acc.ptr("heating_rate"), acc.ptr("net_toa"), B=B)
 
-    n, status, point = _sum_points(s, device, acc, P, d_w, d_scale, solve_chunk, epilogue, N, max_orders)
-    return BandResult(n=n, status=status, scale=scale, point_net_toa=None if point is None else point * scale, **acc.result())
+    def view_stage(d, k0, k1, B):
+        if gas_all is None:
+            vw.stage(s, d["tau"], d["I"], np.full(B, 0.5), thermal=sources(k0, k1, B))
+
+    n, status, point = _sum_points(s, device, acc, P, d_w, d_scale, solve_chunk, epilogue, N, max_orders, vw, view_stage)
+    r = BandResult(n=n, status=status, scale=scale, point_net_toa=None if point is None else point * scale, **acc.result())
+    if vw is not None:
+        d_Tb = None
+        with main._on_torch_stream(s, device):
+            d_view = vw.first + vw.scat
+            if brightness:
+                d_Tb = torch.empty_like(d_view)
+                s.brightness_temperature_device(d_view.data_ptr(), d_Tb.data_ptr(), lo, hi, C, vw.M, d_w.data_ptr())
+        _view_result(r, vw, d_view, scale)
+        r.brightness_temperature = None if d_Tb is None else d_Tb.cpu().numpy()
+    return r
 
 
 def band_thermal_forcing(bands, temperature, surface_temperature, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, alb_aer,
@@ -420,7 +621,7 @@ def band_solar(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, a
                points_per_solve=None, per_point=False, point_aerosol=None, z0=120, z_up=25, z_down=17, nb_layers=200, nb_angles=128,
                atm_phase_fun="rayleigh", g_atm=0.0, aer_phase_fun="hg", g_aer=0.7, mie_atm=None, mie_aer=None, surface="specular",
                tol=1e-4, max_orders=256, device=0, beam="plane", azimuths=None, view_azimuths=None, devices=None,
-               first_order="coded", gas_tau=None) -> BandResult:
+               first_order="coded", gas_tau=None, view_mu=None, view_levels=(0, -1), view_quadrature="grid") -> BandResult:
     """SHORTWAVE FLUXES AND HEATING RATES SUMMED OVER K SPECTRAL POINTS, for C columns: sum_k solar_flux[k] x (the epilogue of
     the solar solve of point k).  `solar_flux` [K] or [K, C] is the weight of every point; mu0 and grd_alb are per column
     (scalars or [C]); tauStar_aer, tauStar_atm, alb_atm and alb_aer per point (scalars, [K] or [K, C]).
@@ -435,8 +636,18 @@ def band_solar(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, a
     phase function is the same for all points.  Pipeline: `solve_batch_device` of P C columns per chunk, `epilogue_device`,
     `band_reduce_device` (no scale); `points_per_solve`, `per_point`, `want` and the refusals as `band_thermal`.
     `gas_tau` [K, L] or [K, C, L]: every spectral point its own gas absorption profile, as in `band_thermal` (the solar first
-    order layer by layer with the weights in its scattering coefficient, the beam terms of the fluxes on the total tau)."""
-    want = _refuse(want, beam, azimuths, view_azimuths, devices, first_order)
+    order layer by layer with the weights in its scattering coefficient, the beam terms of the fluxes on the total tau).
+
+    `view_mu` [V] (default None, the code path as it was): THE CHANNEL'S RADIANCE AT VIEW ANGLES, as in
+    `band_thermal`: per chunk the view stage of `SOS_Aer_batch(view_mu=...)` on the resident field -- the closed-form first
+    order plus the scattered term, under `gas_tau` the weighted entries of `gas_view=True` on sigma = tau / mu0 -- each term summed
+    with solar_flux[k, c] exactly as the epilogue outputs are (no scale): `view_mu_signed`, `I_view_first`, `I_view_scattered`,
+    `I_view` [C, nlev, 2V], with per_point=True `point_I_view` [K, C, nlev, 2V]; `want=()` is then allowed.  The sums carry the
+    solve's F0 = pi / mu0 like the fluxes: the factor mu0 E_k / pi in solar_flux[k] makes them a radiance in the unit of E_k per
+    steradian.  No brightness temperature is formed.  Refused besides: a surface other than 'specular', and a list of aerosols
+    (`point_aerosol`) -- the view stage reads one aerosol phase function."""
+    view = _view_points(view_mu, view_levels, view_quadrature, int(nb_layers), surface, atm_phase_fun, aer_phase_fun, point_aerosol)
+    want = _refuse(want, beam, azimuths, view_azimuths, devices, first_order, views=view is not None)
     L, N = int(nb_layers), int(nb_angles)
     pp, mu0c, rho, sets = _solar_inputs(solar_flux, mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer, aer_phase_fun,
                                         point_aerosol, beam_norm)
@@ -450,24 +661,38 @@ def band_solar(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, a
     d_w = up(pp["solar_flux"])
     d_z = up(np.linspace(z0, 0, L)) if "heating_rate" in want else None
     acc = _Sum(torch, dev, want, per_point, P * C, C, L)
+    vw = None if view is None else _Views(torch, dev, view, (atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer, mie_aer), device,
+                                          C, per_point)
 
     def solve_chunk(k0, k1, B):
         flat = lambda a: a[k0:k1].reshape(B)
         tile = lambda a: np.tile(a, k1 - k0)
+        # the view stage on the resident field, while the weights are set (as gas_view=True of SOS_Aer_batch)
+        gas_views = lambda dev, d_tau, d_I, d_sigma, B: vw.stage(s, d_tau, d_I, tile(mu0c), sigma=d_sigma, profile=True)
         # (the handle's stream, its columns and their aerosol sets are solve_batch_device's to set and to put back)
         return main.solve_batch_device(
             tile(mu0c), flat(pp["tauStar_aer"]), tile(rho), tauStar_atm=flat(pp["tauStar_atm"]), alb_atm=flat(pp["alb_atm"]),
             alb_aer=flat(pp["alb_aer"]), z0=z0, z_up=z_up, z_down=z_down, nb_layers=L, nb_angles=N, atm_phase_fun=atm_phase_fun,
             g_atm=g_atm, aer_phase_fun=aer_phase_fun, g_aer=g_aer, mie_atm=mie_atm, mie_aer=mie_aer, surface=surface, tol=tol,
             max_orders=max_orders, device=device, aer_set=None if sets is None else np.repeat(sets[k0:k1], C),
-            gas_tau=None if gas_all is None else gas_all[k0:k1].reshape(B, L))[0]
+            gas_tau=None if gas_all is None else gas_all[k0:k1].reshape(B, L),
+            profile_post=None if vw is None or gas_all is None else gas_views)[0]
 
     def epilogue(d, acc, B):
         s.epilogue_device(d["tau"].data_ptr(), d["I"].data_ptr(), 0 if d_z is None else d_z.data_ptr(), beam_norm,
                           acc.ptr("flux_down"), acc.ptr("flux_up"), 0, acc.ptr("heating_rate"), acc.ptr("net_toa"))
 
-    n, status, point = _sum_points(s, device, acc, P, d_w, None, solve_chunk, epilogue, N, max_orders)
-    return BandResult(n=n, status=status, point_net_toa=point, **acc.result())
+    def view_stage(d, k0, k1, B):
+        if gas_all is None:
+            vw.stage(s, d["tau"], d["I"], np.tile(mu0c, k1 - k0))
+
+    n, status, point = _sum_points(s, device, acc, P, d_w, None, solve_chunk, epilogue, N, max_orders, vw, view_stage)
+    r = BandResult(n=n, status=status, point_net_toa=point, **acc.result())
+    if vw is not None:
+        with main._on_torch_stream(s, device):
+            d_view = vw.first + vw.scat
+        _view_result(r, vw, d_view)
+    return r
 
 
 def band_solar_forcing(solar_flux, mu0, tauStar_aer, grd_alb, *, tauStar_atm, alb_atm, alb_aer, beam_norm="crit",

@@ -1281,8 +1281,29 @@ def _view_azimuth_args(view_azimuths, view_first_order, view_mu, azimuths, n_mod
     return (_angle_array(view_azimuths, "view_azimuths"),) + _mode_counts(n_modes, nphi_modes)
 
 
+def view_rows(s: Solver, view_mu, d_mu0, atm, aer, dev):
+    """The rows of both phase functions at the signed view lanes, built on handle `s` (grid set, on torch's stream of `dev`):
+    ([rows_atm, rows_aer] each [2V, 2N], [p0rows_atm, p0rows_aer] each [B, 2V] for the suns `d_mu0` [B], a tensor on `dev`).
+    `atm`, `aer`: (name, g, mie).  They depend on the view cosines, the phase names and the suns only, so a driver that runs the
+    view stage chunk by chunk builds them once (`view_radiance(rows=...)`)."""
+    import torch
+    B, V2 = d_mu0.shape[0], 2 * len(view_mu)
+    sgn = np.concatenate((-view_mu, view_mu))
+    rows, p0rows = [], []
+    for phase in (atm, aer):
+        kind, g = _phase_kind(s, *phase)
+        rw = torch.empty((V2, s.D), dtype=torch.float64, device=dev)
+        p0 = torch.empty((B, V2), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        s.phase_rows_device(kind, sgn, rw.data_ptr(), g)
+        s.phase_p0_rows_device(kind, d_mu0.data_ptr(), sgn, p0.data_ptr(), B, g)
+        rows.append(rw)
+        p0rows.append(p0)
+    return rows, p0rows
+
+
 def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase_fun, g_atm, mie_atm, aer_phase_fun, g_aer,
-                  mie_aer, device=0, thermal=None, sigma=None, profile=False, dev=None):
+                  mie_aer, device=0, thermal=None, sigma=None, profile=False, dev=None, keep_device=False, rows=None):
     """The view stage on the field `I` [B, L, 2N] of handle `s` (whose columns are set): rows of both phase functions at the
     signed lanes, then `Solver.view_radiance_device` with I_src = I.  Returns (first order, scattered), each [B, nlev, 2V].
     `thermal` = (planck [B, L], planck_surface [B], emissivity [B] or None): I is a thermal field, and the first term is the
@@ -1292,27 +1313,23 @@ def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase
     carries per-level weights, and the stage runs on the three weighted entries (`Solver.view_radiance_profile_device`,
     `view_first_order_profile_device`, `emission_view_profile_device`); the first term is always explicit, on `sigma` or, where
     none is given, on the plane beam sigma = tau / mu0 -- no closed form is used under weights.  `dev`: the caller is inside a
-    stream scope of its own on that torch device (the `post` of `solve_profile`), and tau, I and sigma are tensors there."""
+    stream scope of its own on that torch device (the `post` of `solve_profile`), and tau, I and sigma are tensors there.
+    `keep_device=True`: both terms come back as torch tensors on that device, nothing crosses PCIe, and the sources in `thermal`
+    may be tensors there too.  `rows`: what `view_rows` returned for at least these B columns' suns, instead of building them."""
     import torch
     B, L = tau.shape
-    D, V2 = s.D, 2 * len(view_mu)
-    sgn = np.concatenate((-view_mu, view_mu))
+    V2 = 2 * len(view_mu)
     with (_on_torch_stream(s, device) if dev is None else nullcontext(dev)) as dev:
-        up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)    # (a copy: broadcast inputs are read-only)
+        # (a copy: broadcast inputs are read-only; a tensor is used where it lies)
+        up = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)
         # (the field is large and already contiguous: uploaded from where it lies, not through a host copy)
         d_tau = tau if isinstance(tau, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tau)).to(dev)
         d_I = I if isinstance(I, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(I)).to(dev)
         d_mu0 = up(mu0)
-        rows, p0rows = [], []
-        for phase in ((atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer)):
-            kind, g = _phase_kind(s, *phase)
-            rw = torch.empty((V2, D), dtype=torch.float64, device=dev)
-            p0 = torch.empty((B, V2), dtype=torch.float64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()
-            s.phase_rows_device(kind, sgn, rw.data_ptr(), g)
-            s.phase_p0_rows_device(kind, d_mu0.data_ptr(), sgn, p0.data_ptr(), B, g)
-            rows.append(rw)
-            p0rows.append(p0)
+        if rows is None:
+            rows, p0rows = view_rows(s, view_mu, d_mu0, (atm_phase_fun, g_atm, mie_atm), (aer_phase_fun, g_aer, mie_aer), dev)
+        else:
+            rows, p0rows = rows[0], [p[:B] for p in rows[1]]
         d_scat = torch.empty((B, len(levels), V2), dtype=torch.float64, device=dev)
         d_first = torch.empty((B, len(levels), V2), dtype=torch.float64, device=dev)
         torch.cuda.current_stream(dev).synchronize()
@@ -1329,7 +1346,7 @@ def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase
             s.view_radiance_profile_device(view_mu, d_tau.data_ptr(), d_I.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), levels,
                                            d_scat.data_ptr(), quadrature=quadrature, B=B)
             s.synchronize()
-            return d_first.cpu().numpy(), d_scat.cpu().numpy()
+            return (d_first, d_scat) if keep_device else (d_first.cpu().numpy(), d_scat.cpu().numpy())
         if thermal is not None:
             # the first term is the emission at the lanes: the view stage gets no first-order addresses and leaves it alone
             d_pl, d_bs = up(thermal[0]), up(thermal[1])
@@ -1346,7 +1363,7 @@ def view_radiance(s: Solver, tau, I, mu0, view_mu, levels, quadrature, atm_phase
                                d_scat_out=d_scat.data_ptr(), d_first_out=first, d_p0rows_atm=p0_atm, d_p0rows_aer=p0_aer,
                                quadrature=quadrature, B=B)
         s.synchronize()
-        return d_first.cpu().numpy(), d_scat.cpu().numpy()
+        return (d_first, d_scat) if keep_device else (d_first.cpu().numpy(), d_scat.cpu().numpy())
 
 
 def _columns_to_set0(s, B):
@@ -2028,7 +2045,7 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
                        mie_atm=None, mie_aer=None, P_atm=None, P_aer=None, P0_atm=None, P0_aer=None, surface="specular",
                        tol=1e-4, max_orders=256, device=0, beam="plane", earth_radius=EARTH_RADIUS_KM, source="solar",
                        planck=None, planck_surface=None, surface_emissivity=None, aer_set=None, brdf=None,
-                       max_bounces=MAX_BOUNCES, delta_m=None, gas_tau=None):
+                       max_bounces=MAX_BOUNCES, delta_m=None, gas_tau=None, profile_post=None):
     """`SOS_Aer_batch` with the RESULT LEFT ON THE DEVICE: returns ({"I": [B, L, 2N] float64, "n": [B] int32, "status": [B]
     int32, "tau": [B, L]} as torch tensors on cuda:`device`, (mu, idx_up, idx_down)).  The solve is enqueued on torch's
     current stream for that device, so the tensors are ordered like any torch result.  What `dist.solve_sharded` gathers.
@@ -2040,7 +2057,8 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
     and "bounce_ratio" [B].  `delta_m=Lambda`: the delta-M-scaled aerosol of `SOS_Aer_batch` (same refusals); the dict then also
     holds "delta_m_f" (a float) and the host arrays "tauStar_aer_scaled", "alb_aer_scaled" [B], and I and tau are the scaled
     column's.  `gas_tau` ([L] or [B, L]): the absorbing gas of `SOS_Aer_batch` (same refusals); tau is the total, and the dict then
-    also holds the host arrays "gas_tau" and "row_weight" [B, L]."""
+    also holds the host arrays "gas_tau" and "row_weight" [B, L]; `profile_post` is then the `post` of `solve_profile`: it runs
+    behind the solve while the weights are set (the view stage of `bands.band_solar`)."""
     gas = _gas_args(gas_tau, lambda: _batch_width(mu0, tauStar_aer, grd_alb, tauStar_atm, alb_atm, alb_aer), nb_layers, surface=surface,
                     delta_m=delta_m)
     dm = _delta_m_args(delta_m, aer_phase_fun, aer_set=aer_set, P_aer=P_aer, P0_aer=P0_aer, surface=surface, beam=beam, source=source)
@@ -2061,7 +2079,7 @@ def solve_batch_device(mu0, tauStar_aer, grd_alb, *, tauStar_atm=0.124, alb_atm=
         if gas is not None:
             out = solve_profile(s, tau, P0a, P0r, gas.w, np.broadcast_to(np.asarray(mu0, dtype=np.float64), (tau.shape[0],)),
                                 np.linspace(z0, 0, int(nb_layers)) if spherical else None, earth_radius, thermal, tol, device,
-                                keep_device=True)
+                                keep_device=True, post=profile_post)
             return dict(out, gas_tau=gas.gas_tau, row_weight=gas.w), (mu, iu, idn)
         if dm is not None:
             out = _solve_resident(s, tau, P0a, P0r, None, None, tol, device=device, keep_device=True)

@@ -533,6 +533,19 @@ class Solver:
         check(lib().sosrt_band_reduce_dev(self._h, int(C), int(K), int(M), _vp(d_weight), _vp(d_scale), _vp(d_x), _vp(d_out),
                                           int(bool(accumulate))))
 
+    def brightness_temperature_device(self, d_radiance: int, d_T_out: int, nu_lo, nu_hi, C: int, M: int, d_weight: int = 0):
+        """The brightness temperature of a band-summed radiance: d_T_out [C, M] (kelvin) is the temperature
+        at which sum_k weight[k, c] B_k(T) equals d_radiance [C, M] (W m-2 sr-1), B_k the band radiance of `planck_bands_device`
+        over [nu_lo[k], nu_hi[k]] (host, cm^-1, K <= 64); d_weight [K, C] or 0 for ones.  NaN where there is no such
+        temperature in (1 K, 1e5 K): a radiance that is not finite or <= 0, weights of a column that are all zero or hold a
+        negative one.  Device addresses; enqueued on the handle's stream; nothing but the output is written."""
+        lo = np.ascontiguousarray(np.atleast_1d(nu_lo), dtype=np.float64)
+        hi = np.ascontiguousarray(np.atleast_1d(nu_hi), dtype=np.float64)
+        if lo.ndim != 1 or lo.shape != hi.shape:
+            raise ValueError("nu_lo and nu_hi must be two arrays [K] of one length")
+        check(lib().sosrt_brightness_temperature_dev(self._h, int(C), int(lo.size), int(M), _ptr(lo) if lo.size else None,
+                                                     _ptr(hi) if hi.size else None, _vp(d_weight), _vp(d_radiance), _vp(d_T_out)))
+
     # ---- BRDF ground (sosrt.h; DESIGN section 20) --------------------------------------------------------
     _BRDF_KINDS = {"lambertian": _lib.BRDF_LAMBERTIAN, "rpv": _lib.BRDF_RPV, "ross_thick": _lib.BRDF_ROSS_THICK,
                    "li_sparse_r": _lib.BRDF_LI_SPARSE_R, "cox_munk": _lib.BRDF_COX_MUNK}
