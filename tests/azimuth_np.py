@@ -9,9 +9,10 @@ import numpy as np
 _trapz = getattr(np, "trapezoid", None) or np.trapz
 
 
-def ring_modes(fn, mu_a, mu_b, ms, nphi):
-    """[len(ms), len(mu_a), len(mu_b)]"""
-    phi = np.linspace(0, np.pi, nphi)
+def ring_modes(fn, mu_a, mu_b, ms, nphi, dtype=np.float64):
+    """[len(ms), len(mu_a), len(mu_b)]; dtype: the arithmetic (the float64 cosines and azimuth nodes, taken into it exactly)"""
+    phi = np.linspace(0, np.pi, nphi).astype(dtype)
+    mu_a, mu_b = np.asarray(mu_a).astype(dtype), np.asarray(mu_b).astype(dtype)
     cc = mu_a[:, None] * mu_b[None, :]
     ss = np.sqrt(1 - mu_b * mu_b)[None, :] * np.sqrt(1 - mu_a * mu_a)[:, None]
     cp = np.cos(0 - phi)
